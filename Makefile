@@ -10,8 +10,8 @@ test: build
 test-gpu:           # on an MI355X
 	python -m pytest tests -x -q -m gpu
 
-bench:              # on an MI355X
-	python bench.py
+bench:              # on an MI355X: the headline and everything measured beside it
+	python bench.py --full
 
 sanitize:           # ASan + UBSan run of the CPU oracle's tests
 	$(MAKE) -C oracle sanitize

@@ -17,9 +17,14 @@ viewport per GPU on an orbit of camera poses).  The path has no exchange step, s
 each GPU's HBM (like the inputs); `value` includes ONE RCCL gather of every rank's last frame to rank 0 inside the
 timed region (--gather final, the default: north_star's "final RCCL gather"); --gather every gathers EVERY frame
 (two in flight, overlapped with the next render; root ingress over xGMI then sets the step time; the default of
---shard bands, where a frame only exists once it is assembled), --gather none skips the collective; the other
-modes' rates are measured in further loops and reported beside it (SURVEY.md 8e asks for with and without).  At
+--shard bands, where a frame only exists once it is assembled), --gather none skips the collective; with --full the other
+modes' rates are measured in further loops and reported beside it (SURVEY.md 8e asks for with and without), and at
 N > 1 the headline run is followed by BASELINE configs[4] (one 3840x2160 clouds_high_rm viewport per GPU).
+
+A plain run does what the headline needs and no more: set up, warm up, time the K steps, write --dump-outputs if given, print the
+line.  --full adds everything else this file measures, each in runs of its own after the headline: the sustained pass and isolated
+launches, the tile-feedback-off rate, the --also extras, the CPU baseline and the hit fraction (N = 1), the other gather modes and
+configs[4] (N > 1).
 
 Output: rank 0 prints ONE compact JSON line (<= 6 KB: compact_record) as the LAST line of stdout -- the record the
 driver parses -- and writes everything measured (every extra's roofline blocks, notes, motion cells) to
@@ -60,6 +65,7 @@ ISSUE_SPEC = {"valu": 2.0, "trans": 8.0}
 ISSUE_MEASURED = {"fast": 2.2, "slow": 4.1, "trans": 8.1, "poison_cycles_per_trans": 3.4}
 PROFILE_DIR = "profiles/round6"  # no fallback to earlier rounds: "clouds_high" meant the LOD-0 sampler there
 COMPACT_LIMIT = 6144         # bytes of the final stdout line (the driver keeps the last 8 KB of stdout)
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: a larger frame is written as a seeded sample of its pixels
 
 
 def pmc_summary(workload, w, h):
@@ -203,6 +209,21 @@ def write_detail(result):
         return path if rel.startswith("..") else rel
     except OSError:
         return None
+
+
+def dump_outputs(directory, rgba):
+    """--dump-outputs: the (h, w, 4) float32 frame the last timed step drew, as DIR/rgba.npy -- what a caller of the render path receives, so
+    that two builds can be compared output for output (the inputs are synthetic and seeded: the same arguments give the same inputs).
+    A frame above DUMP_LIMIT_BYTES is written as its pixels at a fixed seeded sample of positions (the same for every run of that size)."""
+    import numpy as np
+
+    a = rgba.cpu().numpy()
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        px = a.reshape(-1, a.shape[-1])
+        n = DUMP_LIMIT_BYTES // 2 // px[0].nbytes
+        a = px[np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "rgba.npy"), a)
 
 
 def _r(x, digits=6):
@@ -349,6 +370,13 @@ def parse_args():
                          "(SURVEY.md 8d), BASELINE configs[2] (clouds_high 1080p) and configs[3] (clouds_high_rm 3840x2160); '' to skip.  "
                          "name+2vp goes LAST: after two contexts have drawn concurrently on two extra streams, later single-stream draws of the "
                          "same process measure 10-20 %% slower (profiles/round4/bench_order_effect.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the sustained pass and isolated launches, the tile-feedback-off rate, the "
+                         "--also extras, the CPU baseline, the hit fraction, at N > 1 the other gather modes and BASELINE configs[4], with --shard "
+                         "tiles the loop without the collective and the assembled-frame check.  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write the frame the last timed step drew to DIR/rgba.npy (float32, height x width x 4; "
+                         f"above {DUMP_LIMIT_BYTES // 10**6} MB a fixed seeded sample of its pixels, pixels x 4)")
     return ap.parse_args()
 
 
@@ -537,13 +565,14 @@ class TimedRun:
         self.isolated_ms = None
         self.sustained = None
         self.out = None
+        self.last = None   # keep_last: a copy of the frame the last of the K timed steps drew
 
     @property
     def kernel_avg_ms(self):
         return self.event_ms / self.steps if self.steps else 0.0
 
 
-def time_workload(torch, node, cam, depth, steps, warmup, out=None, sequence=None, sustained=False, isolated=True):
+def time_workload(torch, node, cam, depth, steps, warmup, out=None, sequence=None, sustained=False, isolated=True, keep_last=False):
     """Single-GPU timed loop.  `sequence`: None (the same frame every step) or a list of (native frame, depth tensor), one
     camera pose per step, replayed ping-pong (--motion); the host then stays at most FRAMES_IN_FLIGHT frames ahead of the GPU,
     like a swap chain, instead of enqueueing the whole run at once."""
@@ -609,6 +638,8 @@ def time_workload(torch, node, cam, depth, steps, warmup, out=None, sequence=Non
     run.dt, run.event_ms = timed(steps)
     run.steps = steps
     run.out = out
+    if keep_last:   # before the sustained pass and the isolated launches draw into `out` again (another pose under --motion)
+        run.last = out.clone()
     if sustained:
         n2 = max(steps, int(SUSTAINED_MS / max(run.dt / steps * 1e3, 1e-3)) + 1)
         dt2, ev2 = timed(n2)
@@ -930,6 +961,8 @@ def main():
         raise SystemExit("--stub-renderer tests the N > 1 launch path: give --gpus 2 or more")
     if (args.backend == "gloo") != bool(args.stub_renderer):
         raise SystemExit("--backend gloo and --stub-renderer go together (a test of the launch path on a host without a GPU); the product path is RCCL")
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("ATMO_BENCH_FORCE_DIST") == "1"):
+        raise SystemExit("--dump-outputs is a single-GPU option (--gpus 1)")
     self_launch(args)
     if args.gather is None:
         args.gather = "every" if args.shard == "bands" else "final"
@@ -1004,8 +1037,12 @@ def main():
         if motion is not None:
             cams = motion_cameras(S, w, h, motion, max(64, min(args.steps, 256)), args.pose)
             sequence = [(node.prepare_frame(c), depth_ground_sphere_torch(torch, S, c, device)) for c in cams]
-        run = time_workload(torch, node, cam, depth, args.steps, args.warmup, sequence=sequence, sustained=True)
+        run = time_workload(torch, node, cam, depth, args.steps, args.warmup, sequence=sequence, sustained=args.full, isolated=args.full,
+                            keep_last=bool(args.dump_outputs))
         dt_max, launches, kernel_ms = run.dt, run.steps, run.event_ms
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, run.last)
+            run.last = None
         gather_mode = "none (single GPU)"
     else:
         if strong:
@@ -1051,16 +1088,16 @@ def main():
         # the rates WITHOUT the gather and with only the FINAL gather next to the headline mode's (same loop)
         final_gather_rate = None
         scale = 1 if strong else world
-        if args.gather != "none":
+        if args.full and args.gather != "none":
             dt_ng, _, _ = timed_loop_distributed(torch, dist, render_into, h, w, device, args.steps, max(2, args.warmup // 4),
                                                  "none", None, bands=bands)
             no_gather_rate = scale * rays * args.steps / dt_ng / 1e6
-        if args.gather != "final":
+        if args.full and args.gather != "final":
             dt_fg, _, _ = timed_loop_distributed(torch, dist, render_into, h, w, device, args.steps, max(2, args.warmup // 4),
                                                  "final", None, bands=bands)
             final_gather_rate = scale * rays * args.steps / dt_fg / 1e6
         every_gather_rate = None
-        if args.gather != "every":
+        if args.full and args.gather != "every":
             dt_eg, _, _ = timed_loop_distributed(torch, dist, render_into, h, w, device, args.steps, max(2, args.warmup // 4),
                                                  "every", None, bands=bands)
             every_gather_rate = scale * rays * args.steps / dt_eg / 1e6
@@ -1068,14 +1105,15 @@ def main():
     result = None
     if rank == 0:
         value = (1 if strong else world) * rays * args.steps / dt_max / 1e6
-        if no_gather_rate is None:
+        if no_gather_rate is None and (not multi or args.gather == "none"):
             no_gather_rate = value
         pmc = None if (strong or args.pose != "P_space" or motion is not None) else pmc_summary(args.workload + ("@lod0" if lod0 else ""), w, h)
         kernel_avg_ms = kernel_ms / launches if launches else 0.0
         launch_rays = rays if not strong else w * (bands[0][1] - bands[0][0])  # rank 0's kernel shades its band only
+        hit_fraction = None
         if stub:
             pmc, hit_fraction = None, 0.0
-        else:
+        elif args.full:
             frame_img = node.render(cam, depth)
             torch.cuda.synchronize()
             hit_fraction = float((frame_img.abs().sum(dim=-1) > 0).float().mean().item())
@@ -1107,14 +1145,14 @@ def main():
                             + ("" if world == 1 or strong else f" on rank 0, orbit poses on ranks 1..{world - 1}; one viewport per GPU"),
                 "width": w, "height": h, "rays_per_step_per_gpu": rays if not strong else None,
                 "hit_fraction": hit_fraction,
-                "mrays_per_s_hit_only": value * hit_fraction,
+                "mrays_per_s_hit_only": None if hit_fraction is None else value * hit_fraction,
                 "gather": gather_mode,
                 "mrays_per_s_no_gather": no_gather_rate,
                 "mrays_per_s_final_gather": (value if args.gather == "final" else final_gather_rate) if multi else None,
                 "mrays_per_s_gather_every": (value if args.gather == "every" else every_gather_rate) if multi else None,
                 # what the collective adds to the K-step region (the same loop with and without it): one gather of a frame per rank in
                 # "final" mode -- a constant, so its share of `value` shrinks with K
-                "gather_ms_in_timed_region": ((dt_max - dt_ng) * 1e3 if (multi and args.gather != "none") else None),
+                "gather_ms_in_timed_region": ((dt_max - dt_ng) * 1e3 if dt_ng is not None else None),
                 "shard": (f"one viewport in row bands of equal {args.band_cost} cost: " + str(bands)) if strong else "one viewport per GPU",
                 "kernel": node.kernel_name,
             },
@@ -1134,13 +1172,13 @@ def main():
 
     # the conservative figure beside the headline: the same workload in row-major tile order (atmo_set_tile_feedback 0) -- what a panning
     # camera gets on the cloudless kernels (profiles/round3/ab_tile_feedback_motion.txt)
-    if not multi and rank == 0 and motion is None and args.also.strip(", "):  # (not in the single-workload runs of tools/profile.sh: --also "")
+    if args.full and not multi and rank == 0 and motion is None and args.also.strip(", "):  # (not in the single-workload runs of tools/profile.sh: --also "")
         r_off = run_workload(torch, S, args.workload, w, h, args.pose, args.steps, args.warmup, textures, params, local_rank,
                              with_frame_stats=False, node_extra=dict(tile_feedback=0), sampler="lod0" if lod0 else None)
         result["config"]["mrays_per_s_feedback_off"] = r_off["Mrays/s"]
 
     # ---- extras ----------------------------------------------------------------------------------------
-    if not multi and args.also and rank == 0:
+    if args.full and not multi and args.also and rank == 0:
         extra = {}
         ex_steps, ex_warm = max(10, args.steps // 4), max(3, args.warmup // 4)
         for item in [x for x in args.also.split(",") if x]:
@@ -1171,14 +1209,14 @@ def main():
             extra[item] = run_workload(torch, S, name, ew, eh, epose, ex_steps, ex_warm, textures, params, local_rank, sampler=sampler,
                                        node_extra=node_extra, env=env)
         result["extra"] = extra
-    if multi and not strong and args.workload == "direct32x8" and os.environ.get("ATMO_BENCH_NO_CONFIG4") != "1":
+    if args.full and multi and not strong and args.workload == "direct32x8" and os.environ.get("ATMO_BENCH_NO_CONFIG4") != "1":
         # BASELINE.json configs[4]: independent 3840x2160 clouds_high_rm viewports, one per GPU, gathered to rank 0 over xGMI
         c4 = bench_config4(torch, dist, S, textures, params, local_rank, rank, world, max(5, args.steps // 8), 2, stub=stub)
         if rank == 0:
             result.setdefault("extra", {})["config4_clouds_high_rm_3840x2160"] = c4
 
     if rank == 0:
-        if not multi and not args.no_cpu_baseline:
+        if args.full and not multi and not args.no_cpu_baseline:
             from godot_atmosphere_shader_amd.demo import CONFIGS
             ocfg = CONFIGS[config_name][1]
             lut = None
@@ -1262,23 +1300,26 @@ def main_tile_strips(args, torch, dist, S, textures, params, config_name, desc, 
         loop(8, False)
         torch.cuda.synchronize()
     dt, _ = timed(args.steps, True)
-    dt_ng, ev_ng = timed(args.steps, False)
-    # what every rank's launch took, without the collective (HIP events around its K un-bracketed launches)
-    per_rank = torch.zeros(world, dtype=torch.float64, device=device)
-    per_rank[rank] = ev_ng / args.steps
-    dist.all_reduce(per_rank)
-    if rank == 0:
-        assembled = g.gather()
-    else:
-        g.gather()
+    dt_ng = per_rank = identical = None
+    if args.full:
+        dt_ng, ev_ng = timed(args.steps, False)
+        # what every rank's launch took, without the collective (HIP events around its K un-bracketed launches)
+        per_rank = torch.zeros(world, dtype=torch.float64, device=device)
+        per_rank[rank] = ev_ng / args.steps
+        dist.all_reduce(per_rank)
+        if rank == 0:
+            assembled = g.gather()
+            want = node.render(cam, depth)
+            torch.cuda.synchronize()
+            identical = bool(torch.equal(assembled, want))
+        else:
+            g.gather()
     result = None
     if rank == 0:
-        want = node.render(cam, depth)
-        torch.cuda.synchronize()
-        identical = bool(torch.equal(assembled, want))
         rays = w * h
         value = rays * args.steps / dt / 1e6
-        k_ms = float(per_rank.max().item())
+        k_ms = None if per_rank is None else float(per_rank.max().item())
+        slowest = 0 if per_rank is None else int(per_rank.argmax().item())
         result = {
             "metric": f"Mrays/s, {args.workload} at {w}x{h}; % HBM roofline; one viewport in tile strips over {world} GPUs, gather every",
             "value": value, "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -1288,12 +1329,14 @@ def main_tile_strips(args, torch, dist, S, textures, params, config_name, desc, 
                        "width": w, "height": h, "kernel": node.kernel_name, "gather": "strips of every frame gathered into the frame on rank 0, inside the timed region",
                        "shard": f"{len(strips[0]) and sum(len(s) for s in strips)} strips of {STRIP_TILE_ROWS * th} rows dealt LPT by measured cost: "
                                 f"{[len(s) for s in strips]} strips per rank, {[int(t.size) for t in tiles]} tiles",
-                       "mrays_per_s_no_gather": rays * args.steps / dt_ng / 1e6, "mrays_per_s_gather_every": value,
-                       "gather_ms_in_timed_region": (dt - dt_ng) * 1e3,
-                       "kernel_ms_per_rank": [float(v) for v in per_rank.tolist()], "assembled_frame_equals_single_gpu_frame": identical},
-            "roofline": hbm_roofline(k_ms, args.steps, int(tiles[int(per_rank.argmax().item())].size) * tw * th, None),
+                       "mrays_per_s_no_gather": None if dt_ng is None else rays * args.steps / dt_ng / 1e6, "mrays_per_s_gather_every": value,
+                       "gather_ms_in_timed_region": None if dt_ng is None else (dt - dt_ng) * 1e3,
+                       "kernel_ms_per_rank": None if per_rank is None else [float(v) for v in per_rank.tolist()],
+                       "assembled_frame_equals_single_gpu_frame": identical},
+            "roofline": hbm_roofline(k_ms, args.steps, int(tiles[slowest].size) * tw * th, None),
         }
-        result["roofline"]["kernel_timing"] = "HIP events around the K un-bracketed tile-list launches of the slowest rank (loop without the collective)"
+        if per_rank is not None:
+            result["roofline"]["kernel_timing"] = "HIP events around the K un-bracketed tile-list launches of the slowest rank (loop without the collective)"
     node.close()
     dist.barrier()
     dist.destroy_process_group()

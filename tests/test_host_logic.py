@@ -484,11 +484,17 @@ def test_bench_gpus_n_launches_its_own_ranks(tmp_path):
     """`python3 bench.py --gpus N` typed WITHOUT torch.distributed.run used to exit with a message for N > 1, so the first
     8-GPU node would have produced no scaling curve.  Now it starts the N ranks itself as a child process (bench.self_launch; before torch is
     imported, never an exec).  Run here on CPU through the test switch --backend gloo --stub-renderer (no kernel, frames are torch fills): two
-    ranks rendezvous on 127.0.0.1, run the barrier / max-over-ranks timed loop with the final gather, the configs[4]-shaped loop after it,
-    and rank 0's JSON record is the LAST stdout line of the command the user typed -- saying what ran (ranks, backend, gather mode) and that
-    it was the stub."""
+    ranks rendezvous on 127.0.0.1, run the barrier / max-over-ranks timed loop with the final gather, with --full the other gather modes'
+    loops and the configs[4]-shaped loop after it, and rank 0's JSON record is the LAST stdout line of the command the user typed -- saying
+    what ran (ranks, backend, gather mode) and that it was the stub."""
+    # a plain run times the headline loop only
     p, rec = _run_bench_as_typed(tmp_path, "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--stub-renderer",
                                  "--width", "64", "--height", "36")
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert rec is not None and rec["steps"] == 3 and rec["value"] > 0 and rec["gather_mode"] == "final"
+    assert "extra" not in rec and "mrays_per_s_no_gather" not in rec["config"] and "mrays_per_s_gather_every" not in rec["config"]
+    p, rec = _run_bench_as_typed(tmp_path, "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--stub-renderer",
+                                 "--width", "64", "--height", "36", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     assert rec is not None, p.stdout[-2000:]
     assert rec["n_gpus"] == 2 and rec["ranks"] == 2 and rec["backend"] == "gloo" and rec["steps"] == 3 and rec["warmup"] == 1
@@ -504,6 +510,50 @@ def test_bench_gpus_n_launches_its_own_ranks(tmp_path):
     assert p.returncode == 0 and rec["ranks"] == 2 and rec["scaling"] == "strong" and rec["gather_mode"] == "every" and rec["shard_mode"] == "bands"
 
 
+def test_bench_dump_outputs_file(tmp_path):
+    """bench.py --dump-outputs: a frame up to the size limit is written whole; a larger one (3840x2160: 133 MB) as its pixels at fixed seeded
+    positions -- the same positions in every run, under the limit, float32."""
+    import torch
+
+    import bench
+
+    small = torch.arange(36 * 64 * 4, dtype=torch.float32).reshape(36, 64, 4)
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    got = np.load(tmp_path / "a" / "rgba.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    big = torch.arange(2160 * 3840, dtype=torch.float32).reshape(2160, 3840, 1).expand(2160, 3840, 4)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    b, c = np.load(tmp_path / "b" / "rgba.npy"), np.load(tmp_path / "c" / "rgba.npy")
+    assert b.dtype == np.float32 and b.ndim == 2 and b.shape[1] == 4 and 0 < b.nbytes <= bench.DUMP_LIMIT_BYTES and np.array_equal(b, c)
+    idx = b[:, 0].astype(np.int64)   # each sampled pixel carries its own index: distinct, in order, and the pixel's values
+    assert np.all(np.diff(idx) > 0) and np.array_equal(b, big.numpy().reshape(-1, 4)[idx])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_is_the_timed_frame(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (a plain run): exactly K timed steps, and DIR/rgba.npy is the frame the headline
+    workload draws -- the same bits as a fresh context drawing the same pose in this process."""
+    import torch
+
+    from godot_atmosphere_shader_amd.demo import demo_params, demo_textures, make_node
+
+    p, rec = _run_bench_as_typed(tmp_path, "--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "192", "--height", "108",
+                                 "--dump-outputs", str(tmp_path / "out"))
+    assert p.returncode == 0 and rec is not None, p.stderr[-2000:]
+    assert rec["steps"] == 3 and rec["ms_per_step"] == pytest.approx(rec["timed_region_ms"] / 3, rel=1e-3)
+    assert "extra" not in rec and "cpu_baseline" not in rec
+    got = np.load(tmp_path / "out" / "rgba.npy")
+    cam = S.Camera.from_pose(192, 108, "P_space")
+    node = make_node("no_clouds_32x8_direct", demo_textures(), demo_params(), device=0)
+    want = node.render(cam, torch.from_numpy(S.depth_ground_sphere(cam)).cuda())
+    torch.cuda.synchronize()
+    want = want.cpu().numpy()
+    node.close()
+    assert got.dtype == np.float32 and got.shape == (108, 192, 4) and np.array_equal(got, want)
+    assert np.abs(got).sum(axis=-1).astype(bool).mean() > 0.1   # the planet is in the frame
+
+
 def test_bench_launch_errors_are_loud(tmp_path):
     """The child's exit code is the command's exit code; the test switches cannot reach the product path."""
     import bench
@@ -512,6 +562,8 @@ def test_bench_launch_errors_are_loud(tmp_path):
     assert p.returncode != 0 and rec is None and "--stub-renderer" in p.stderr
     p, rec = _run_bench_as_typed(tmp_path, "--gpus", "1", "--stub-renderer", "--backend", "gloo")
     assert p.returncode != 0 and rec is None
+    p, rec = _run_bench_as_typed(tmp_path, "--gpus", "2", "--dump-outputs", str(tmp_path / "out"))   # one frame per rank: refused before anything starts
+    assert p.returncode != 0 and rec is None and "--dump-outputs" in p.stderr and "torch.distributed.run" not in p.stderr
     if not _has_gpu():
         # the real N > 1 command on a host without GPUs: every rank fails loudly, the launcher's code comes back, no JSON line
         p, rec = _run_bench_as_typed(tmp_path, "--gpus", "2", "--steps", "1", "--warmup", "0")

@@ -3,8 +3,8 @@ shader source (all seven planet_atmosphere_*.gdshader variants and optical_depth
 tests/golden/gdshader_vm.py in this container, where /root/reference exists (tests/golden/make_reference_vectors.py).
 
   -m "not gpu":  the CPU oracle against those vectors (this is what pins oracle/atmo_oracle.c to something outside this
-                 repo's reading of the shader), the host mirror of atmosphere_vertex, the interpreter's own unit tests, and --
-                 only where /root/reference is present -- a re-execution of a sample of the vectors.
+                 repo's reading of the shader), the host mirror of atmosphere_vertex, the interpreter's own unit tests.
+                 tests/checks/reference_tree.py re-executes a sample of the vectors from a reference checkout.
   -m gpu:        the HIP path through the C ABI against the same vectors, tolerance BASELINE.json's 1e-4; LUT bake bit-exact.
 
 Nothing here reads /root/reference on the GPU box.
@@ -156,25 +156,6 @@ def test_oracle_equals_reference_double_precision_switch(oracle32, vectors, text
     plain, _ = oracle32.render(params, dict(textures, optical_depth=vectors["lut_demo"]), RS.VARIANTS["planet_atmosphere_clouds"],
                                frame, vectors["depth_demo_P_limb"])
     assert np.abs(plain - want).max() > 1e-3
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/addons/zylann.atmosphere/shaders"), reason="needs the reference tree")
-def test_vectors_reproduce_from_the_reference_tree(vectors, textures, oracle32):
-    """Where the reference is present (the build container), re-execute a sample of the vectors from its source."""
-    import make_reference_vectors as G
-    import vm_textures as T
-
-    lut, _ = G.run_bake(RS.scenes()["alt"][0])
-    assert np.array_equal(lut.view(np.uint32), vectors["lut_alt"].view(np.uint32))
-    params, model = RS.scenes()["alt"]
-    cube = textures["cubemap"]
-    padded = T.pad_cubemap(cube, lambda f, i, j: oracle32.cube_texel(cube, f, i, j))
-    units = dict(u_optical_depth_texture=T.LutTexture(lut), u_blue_noise_texture=T.ByteTexture2D(textures["blue_noise"]),
-                 u_cloud_shape_texture=T.ShapeTexture(textures["shape"]), u_cloud_coverage_cubemap=T.CubeTexture(padded))
-    cam = RS.camera_from_fixture(vectors, RS.W, RS.H, "P_clouds")
-    rgba, _, _, _ = G.run_frame("planet_atmosphere_clouds_high_rm", None, params, np.linalg.inv(model), model, cam,
-                                vectors["depth_alt_P_clouds"], units)
-    assert np.array_equal(rgba, vectors["rgba_alt_P_clouds_planet_atmosphere_clouds_high_rm"])
 
 
 # ------------------------------------------------------------------- round 3 vectors (reference_exec_r3.npz): LOD, 32 / 64 steps

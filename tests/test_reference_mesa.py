@@ -14,9 +14,10 @@ inversesqrt, dot sums in another order, exp is 1.1e-6 relative (18 ulp), pow 1e-
     deviation is explained, pixel by pixel, by fp32 sensitivity;
   * discard masks, the vertex-stage varyings and the LUT bake of the demo scene are compared EXACTLY (the bake: 65 536 of 65 536 texels bit-identical).
 
-  -m "not gpu":  the CPU oracle against Mesa's vectors; the interpreter's vectors against Mesa's; where /root/reference and Mesa are present, a re-run.
+  -m "not gpu":  the CPU oracle against Mesa's vectors; the interpreter's vectors against Mesa's (tests/checks/reference_tree.py re-runs Mesa on a
+                 reference checkout).
   -m gpu:        the HIP path through the C ABI against Mesa's vectors (small frames and whole rows at the BASELINE sizes, both cubemap samplers).
-Nothing here needs Mesa or /root/reference at run time except the one test that says so."""
+Nothing here needs Mesa or the reference at run time."""
 import os
 import sys
 
@@ -372,69 +373,6 @@ def test_minified_frames_differ_from_mesa_by_two_named_choices(oracle32, vm, mes
     else:
         assert e.max() <= 5e-5                                          # every pixel, the last row included: 1.6e-5 measured
         assert e_stated.max() > 10 * e.max()
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/addons/zylann.atmosphere/shaders"), reason="needs the reference tree (the build container)")
-def test_what_mesa_compiles_is_the_references_text():
-    """mesa_exec.translate: between the prelude it puts in front (the #version line, the engine built-ins) and the main() it appends, the source handed to
-    Mesa's compiler is the reference's files with their #includes pasted in, and every line that differs from the file on disk is one of the four
-    declared edits: a `uniform` declaration stripped of hints and default, a `varying` turned into a global, a `shader_type` / `render_mode` line
-    dropped, a trailing comma removed in front of `)`.  No statement inside a function body is touched."""
-    import re
-    import mesa_exec as M
-
-    shaders = sorted(f for f in os.listdir(M.SHADERS) if f.endswith(".gdshader"))
-    assert len(shaders) == 8
-    edited = {"uniform": 0, "varying": 0, "dropped": 0, "comma": 0}
-    total = 0
-    for f in shaders:
-        path = os.path.join(M.SHADERS, f)
-        original = M.flatten(path, {}).split("\n")
-        for stage in ("fragment", "vertex") if "planet_atmosphere" in f else ("canvas",):
-            src, _ = M.translate(path, stage=stage)
-            begin = src.index("out vec4 MGL_out;\n") + len("out vec4 MGL_out;\n")
-            body = src[begin:src.rindex("\nvoid main() {")].split("\n")
-            assert len(body) == len(original), f
-            for k, (a, b) in enumerate(zip(original, body)):
-                total += 1
-                if a == b:
-                    continue
-                if re.match(r"\s*uniform\s", a):
-                    ty, name = re.match(r"\s*uniform\s+(\w+)\s+(\w+)", a).groups()
-                    assert b.strip() == f"uniform {ty} {name};", (a, b)     # hints and default gone, nothing else
-                    edited["uniform"] += 1
-                elif re.match(r"\s*varying\s", a):
-                    assert b.strip() == a.strip()[len("varying"):].strip(), (a, b)
-                    edited["varying"] += 1
-                elif re.match(r"\s*(shader_type|render_mode)\b", a):
-                    assert re.sub(r"^\s*(shader_type|render_mode)\b[^;]*;", "", a) == b, (a, b)
-                    edited["dropped"] += 1
-                else:
-                    # a trailing comma in front of `)`: on this line, or at its end with the `)` opening the next line
-                    same_line = re.sub(r",(\s*)\)", r"\1)", a)
-                    line_end = (a.rstrip()[:-1] + a[len(a.rstrip()):]) if a.rstrip().endswith(",") and original[k + 1].lstrip().startswith(")") else None
-                    assert b in (same_line, line_end), (a, b)
-                    edited["comma"] += 1
-    print(f"\n{total} lines of reference text handed to Mesa over {len(shaders)} shaders x stages; edited: {edited}")
-    assert edited["uniform"] > 100 and edited["varying"] > 10 and edited["dropped"] > 10 and 0 < edited["comma"] < 400
-
-
-@pytest.mark.skipif(not (os.path.isdir("/root/reference/addons/zylann.atmosphere/shaders") and os.path.exists("/usr/lib/x86_64-linux-gnu/dri/swrast_dri.so")),
-                    reason="needs the reference tree and Mesa's swrast_dri.so (the build container)")
-def test_mesa_vectors_reproduce_here(vm, mesa, textures):
-    """Where the reference and Mesa are present: compile the text again, draw one frame and one bake, the same bits as the committed vectors."""
-    import subprocess
-    code = ("import sys, numpy as np; sys.path.insert(0, %r); sys.path.insert(0, %r); import mesa_exec as M, reference_scenes as RS;"
-            "from godot_atmosphere_shader_amd import scene as S; z = np.load(%r); m = np.load(%r); p, model = RS.scenes()['alt'];"
-            "tex = dict(lut=z['lut_alt'], blue=S.make_blue_noise(), shape=S.make_shape_texture(RS.SHAPE_N), cubemap=S.make_coverage_cubemap(RS.CUBE_N));"
-            "cam = RS.camera_from_fixture(z, RS.W, RS.H, 'P_clouds');"
-            "rgba, disc, vary = M.run_frame('planet_atmosphere_clouds_high_rm', None, p, np.linalg.inv(model), model, cam, z['depth_alt_P_clouds'], tex);"
-            "assert np.array_equal(rgba, m['rgba_alt_P_clouds_planet_atmosphere_clouds_high_rm']);"
-            "lut, _ = M.run_bake(p); assert np.array_equal(lut.view(np.uint32), m['lut_alt'].view(np.uint32)); print('same bits')"
-            % (os.path.dirname(GOLDEN[:-len('/golden')]), GOLDEN, os.path.join(GOLDEN, "reference_exec.npz"), os.path.join(GOLDEN, "reference_exec_mesa.npz")))
-    # (a process of its own: llvmpipe's worker threads and LLVM's JIT stay out of the test process)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "same bits" in r.stdout, r.stderr[-2000:]
 
 
 # ------------------------------------------------------------------------------------------------------ GPU

@@ -21,5 +21,5 @@ export TMPDIR=/tmp
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $DST/default_cmd -o s -- $PY $R/bench.py --also "" > $DST/bench_default_under_rocprof.json 2> $DST/bench_default_under_rocprof.err)
 cp $DST/default_cmd/s_kernel_stats.csv $DST/bench_default_command_kernel_stats.csv 2>/dev/null
 rm -rf $DST/default_cmd
-ATMO_BENCH_DETAIL=$DST/bench_default.json python3 bench.py > $DST/bench_default_line.json 2> $DST/bench_default.err
+ATMO_BENCH_DETAIL=$DST/bench_default.json python3 bench.py --full > $DST/bench_default_line.json 2> $DST/bench_default.err
 ls $DST
