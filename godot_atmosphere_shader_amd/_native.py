@@ -15,7 +15,7 @@ VARIANT_V1_NO_CLOUDS, VARIANT_V1_CLOUDS, VARIANT_V1_CLOUDS_HIGH = 4, 5, 6
 LIGHT_LUT, LIGHT_DIRECT = 0, 1
 TEX_2D_R32F, TEX_2D_R8, TEX_3D_R8, TEX_CUBE_R8 = range(4)
 MEM_HOST, MEM_DEVICE = 0, 1
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # every symbol include/atmo.h declares: the surface a host binds (each replaces a reference interface)
 CORE_SYMBOLS = (
@@ -28,9 +28,11 @@ CORE_SYMBOLS = (
 DEBUG_SYMBOLS = (
     "atmo_set_lane_split", "atmo_debug_motion_px", "atmo_get_feedback_stats", "atmo_set_timing", "atmo_get_timing", "atmo_host_layout_cubemap", "atmo_host_layout_shape",
     "atmo_host_layout_lut", "atmo_host_cubemap_mip", "atmo_read_texture_layout", "atmo_selftest_exact_math", "atmo_debug_marched_optical_depth", "atmo_debug_log2_cr", "atmo_kernel_name", "atmo_build_id",
-    "atmo_get_host_wait_stats", "atmo_get_split_stats", "atmo_debug_create_host_only", "atmo_debug_frame_constants",
+    "atmo_get_host_wait_stats", "atmo_get_split_stats", "atmo_debug_create_host_only", "atmo_debug_frame_constants", "atmo_debug_proxy_launch_rect",
 )
-EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS
+# every symbol include/atmo_scene.h declares: drawing several atmospheres into one frame (the far-mode BoxMesh draw)
+SCENE_SYMBOLS = ("atmo_render_proxy", "atmo_render_proxy_composite")
+EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS
 
 
 class AtmoFrame(C.Structure):
@@ -118,6 +120,9 @@ def load() -> C.CDLL:
         "atmo_debug_create_host_only": (ip, [ip, ip, ip, ip, ip, C.POINTER(vp)]),
         "atmo_debug_frame_constants": (ip, [vp, C.POINTER(AtmoFrame), ip, C.POINTER(C.c_float), ip, C.POINTER(ip)]),
         "atmo_last_error_string": (cp, [vp]),
+        "atmo_debug_proxy_launch_rect": (ip, [vp, C.POINTER(AtmoFrame), fp, C.c_float, C.POINTER(ip), C.POINTER(ip)]),
+        "atmo_render_proxy": (ip, [vp, C.POINTER(AtmoFrame), fp, C.c_float, vp, vp, vp]),
+        "atmo_render_proxy_composite": (ip, [vp, C.POINTER(AtmoFrame), fp, C.c_float, vp, vp, vp]),
     }
     # ATMO_HIP_LIB names an A/B build (tools/ab_build_commit.sh: possibly an OLDER commit's library): entry points it lacks are skipped
     # (callers of those guard with hasattr) and its ABI version is not held against it.  The in-tree library must match exactly.
@@ -134,8 +139,9 @@ def load() -> C.CDLL:
     if have != ABI_VERSION:
         # An A/B library may be older, but only a version whose AtmoFrame layout and shared entry points are KNOWN to be what this binding
         # declares may be driven with it, and the caller has to name it: ATMO_HIP_LIB_ABI=3 (ABI 3 = round 3: the same AtmoFrame, no
-        # atmo_set_target_cleared / atmo_render_tiles, atmo_set_sampler_lod without the -1 mode).  Anything else could corrupt memory silently.
-        allowed = {3}
+        # atmo_set_target_cleared / atmo_render_tiles, atmo_set_sampler_lod without the -1 mode) or 4 (ABI 4: the same AtmoFrame and atmo.h calls,
+        # no atmo_scene.h).  Anything else could corrupt memory silently.
+        allowed = {3, 4}
         named = os.environ.get("ATMO_HIP_LIB_ABI", "")
         if not (ab_build and named.isdigit() and int(named) == have and have in allowed):
             raise RuntimeError(f"libatmo_hip.so has ABI version {have}, this binding is written for {ABI_VERSION}; rebuild it"

@@ -7,9 +7,11 @@
 // HIP device every compute entry point fails with ATMO_E_NO_DEVICE / ATMO_E_HIP.
 #include "../../include/atmo.h"
 #include "../../include/atmo_debug.h"
+#include "../../include/atmo_scene.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1441,6 +1443,43 @@ int atmo_measure_tile_costs(AtmoContext *ctx, const AtmoFrame *frame, const floa
     return rc;
 }
 
+// Remembers the stream a draw was enqueued on and puts its marker event behind the draw (AtmoContext::DrawStream): what texture updates on other
+// streams wait for.  *marker: the event recorded, or null.
+static int note_draw_stream(AtmoContext *ctx, hipStream_t s, hipEvent_t *marker) {
+    *marker = nullptr;
+    AtmoContext::DrawStream *ds = nullptr;
+    for (AtmoContext::DrawStream &d : ctx->draw_streams) if (d.stream == s) ds = &d;
+    if (!ds) {
+        if (ctx->draw_streams.size() < 8) {
+            ctx->draw_streams.emplace_back();
+            ds = &ctx->draw_streams.back();
+            ds->stream = s;
+        } else {
+            // a host that draws on a new stream every frame: bounded memory.  The least recently used entry makes room (its marker is
+            // re-recorded for the new stream); what it stood for can only be waited for device-wide from now on: the next update does
+            ds = &ctx->draw_streams[0];
+            for (AtmoContext::DrawStream &d : ctx->draw_streams) if (d.last_use < ds->last_use) ds = &d;
+            ds->stream = s;
+            ds->recorded = false;
+            ctx->draw_streams_many = true;
+        }
+    }
+    ds->recorded = false;   // whatever marker it carries is not behind THIS draw
+    ds->last_use = ++ctx->draw_stream_clock;
+    const bool home = s == ctx->tex_stream;   // the stream of the last texture update (the null stream before the first)
+    if (ctx->draw_events && (!home || ctx->draw_events == 2)) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        const bool capturing = hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
+        if (!capturing) {   // (a draw inside a graph capture gets no marker: replays are the caller's to order)
+            if (!ds->last_draw) HIP_TRY(ctx, hipEventCreateWithFlags(&ds->last_draw, hipEventDisableTiming));
+            HIP_TRY(ctx, hipEventRecord(ds->last_draw, s));
+            ds->recorded = true;
+            *marker = ds->last_draw;
+        }
+    }
+    return ATMO_OK;
+}
+
 static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream, bool composite,
                        const uint32_t *tiles_dev, int n_tiles, int n_heavy) {
     if (!ctx) return ATMO_E_ARG;
@@ -1752,38 +1791,7 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
     }
     if (fb) fb->n += 1;
     hipEvent_t marker = nullptr;   // the draw stream's marker, when this draw recorded one (re-recorded behind the in-stream sort below)
-    {   // remember the stream and put its marker behind this draw
-        AtmoContext::DrawStream *ds = nullptr;
-        for (AtmoContext::DrawStream &d : ctx->draw_streams) if (d.stream == s) ds = &d;
-        if (!ds) {
-            if (ctx->draw_streams.size() < 8) {
-                ctx->draw_streams.emplace_back();
-                ds = &ctx->draw_streams.back();
-                ds->stream = s;
-            } else {
-                // a host that draws on a new stream every frame: bounded memory.  The least recently used entry makes room (its marker is
-                // re-recorded for the new stream); what it stood for can only be waited for device-wide from now on: the next update does
-                ds = &ctx->draw_streams[0];
-                for (AtmoContext::DrawStream &d : ctx->draw_streams) if (d.last_use < ds->last_use) ds = &d;
-                ds->stream = s;
-                ds->recorded = false;
-                ctx->draw_streams_many = true;
-            }
-        }
-        ds->recorded = false;   // whatever marker it carries is not behind THIS draw
-        ds->last_use = ++ctx->draw_stream_clock;
-        const bool home = s == ctx->tex_stream;   // the stream of the last texture update (the null stream before the first)
-        if (ctx->draw_events && (!home || ctx->draw_events == 2)) {
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            const bool capturing = hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
-            if (!capturing) {   // (a draw inside a graph capture gets no marker: replays are the caller's to order)
-                if (!ds->last_draw) HIP_TRY(ctx, hipEventCreateWithFlags(&ds->last_draw, hipEventDisableTiming));
-                HIP_TRY(ctx, hipEventRecord(ds->last_draw, s));
-                ds->recorded = true;
-                marker = ds->last_draw;
-            }
-        }
-    }
+    { const int rc0 = note_draw_stream(ctx, s, &marker); if (rc0 != ATMO_OK) return rc0; }
     ctx->last_split = split;
     ctx->launch_counter += 1;  // counted only once the launch was accepted
     if (timed) {
@@ -2000,6 +2008,226 @@ int atmo_debug_frame_constants(AtmoContext *ctx, const AtmoFrame *frame, int cub
     if (!out) return ATMO_OK;
     if (capacity < (int)v.size()) return fail(ctx, ATMO_E_ARG, "atmo_debug_frame_constants: buffer too small");
     std::memcpy(out, v.data(), v.size() * sizeof(float));
+    return ATMO_OK;
+}
+
+
+// ---- the far-mode draw through the BoxMesh proxy (include/atmo_scene.h) ------------------------------------------------------------------
+// 4 x 4 matrices column-major in double: m[col * 4 + row]
+static void mat4_mul_d(const double *a, const double *b, double *c) {
+    for (int col = 0; col < 4; ++col)
+        for (int row = 0; row < 4; ++row) {
+            double acc = 0.0;
+            for (int k = 0; k < 4; ++k) acc += a[k * 4 + row] * b[col * 4 + k];
+            c[col * 4 + row] = acc;
+        }
+}
+static bool mat4_inverse_d(const double *m, double *inv) {   // Gauss-Jordan with partial pivoting; false: singular or not finite
+    double a[4][8];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) { a[r][c] = m[c * 4 + r]; a[r][c + 4] = r == c ? 1.0 : 0.0; }
+    for (int c = 0; c < 4; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < 4; ++r) if (std::fabs(a[r][c]) > std::fabs(a[piv][c])) piv = r;
+        if (!(std::fabs(a[piv][c]) > 0.0) || !std::isfinite(a[piv][c])) return false;
+        for (int k = 0; k < 8; ++k) std::swap(a[c][k], a[piv][k]);
+        const double d = a[c][c];
+        for (int k = 0; k < 8; ++k) a[c][k] /= d;
+        for (int r = 0; r < 4; ++r)
+            if (r != c && a[r][c] != 0.0) {
+                const double f = a[r][c];
+                for (int k = 0; k < 8; ++k) a[r][k] -= f * a[c][k];
+            }
+    }
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) inv[c * 4 + r] = a[r][c + 4];
+    return true;
+}
+
+// The proxy's per-draw constants (atmo::ProxyConsts, built in double and rounded once) and the launch: the pixel rectangle of the box's part between the
+// near and the far plane, grown by one pixel and cut to the frame's rect, and its tile grid.  `f` is the frame as the kernels see it (DOUBLE_PRECISION
+// applied).  A covered pixel's fragment lies on a front face between the planes: every front face is clipped against the two planes in clip space
+// (0 <= z <= w: reverse-Z, linear along an edge), the vertices left are projected to pixel centres (the prologue's uv = (p + 0.5) / size).  *tiles = 0: nothing
+// to draw (behind the camera, beyond the far plane, off the rect).  Launch origin as render_impl's: even under the declared sampler.
+static int proxy_setup(AtmoContext *ctx, const char *who, const AtmoFrame *f, const float *model_matrix, float box_size, bool lod,
+                       atmo::ProxyConsts &pc, int rect[4], int *tiles_x, int *tiles_y) {
+    double ip[16], iv[16], m[16], mi[16], v[16], p[16], t[16], k[16], pv[16];
+    for (int i = 0; i < 16; ++i) { ip[i] = f->inv_projection_matrix[i]; iv[i] = f->inv_view_matrix[i]; m[i] = model_matrix[i]; }
+    if (!mat4_inverse_d(m, mi)) return fail(ctx, ATMO_E_ARG, std::string(who) + ": model_matrix is singular");
+    if (!mat4_inverse_d(iv, v)) return fail(ctx, ATMO_E_ARG, std::string(who) + ": inv_view_matrix is singular");
+    if (!mat4_inverse_d(ip, p)) return fail(ctx, ATMO_E_ARG, std::string(who) + ": inv_projection_matrix is singular");
+    mat4_mul_d(mi, iv, t);
+    mat4_mul_d(t, ip, k);   // NDC -> the proxy's model space, homogeneous
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) pc.k[r][c] = (float)k[c * 4 + r];
+    const double h = 0.5 * (double)box_size;
+    pc.half = (float)h;
+    mat4_mul_d(v, m, t);
+    mat4_mul_d(p, t, pv);   // model -> clip
+    // Which faces can hold a fragment: the front faces, those whose plane has the eye on its outer side.  The eye is the point every pixel's segment
+    // points away from: clip (0, 0, 1, 0) -> the proxy's model space, K's third column (a point for a perspective projection, a direction -- the side
+    // opposite to the view direction -- for an orthographic one).
+    double eye[4] = {k[8], k[9], k[10], k[11]};
+    bool eye_point = std::fabs(eye[3]) > 1e-12 * (std::fabs(eye[0]) + std::fabs(eye[1]) + std::fabs(eye[2]));
+    if (eye_point) {
+        for (int r = 0; r < 3; ++r) eye[r] /= eye[3];
+    } else {
+        double dn[3], df[3];   // the centre pixel's near and far end
+        for (int r = 0; r < 3; ++r) { dn[r] = (k[8 + r] + k[12 + r]) / (k[11] + k[15]); df[r] = k[12 + r] / k[15]; }
+        if (eye[0] * (df[0] - dn[0]) + eye[1] * (df[1] - dn[1]) + eye[2] * (df[2] - dn[2]) > 0.0)
+            for (int r = 0; r < 3; ++r) eye[r] = -eye[r];
+    }
+    const double W = f->viewport_w, H = f->viewport_h;
+    double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+    bool unbounded = false;
+    for (int face = 0; face < 6; ++face) {
+        const int ax = face >> 1;
+        const double sg = (face & 1) ? -1.0 : 1.0;
+        if (!(sg * eye[ax] > (eye_point ? h : 0.0))) continue;   // a back face (or the eye on its plane): culled
+        // the face's square in clip space, clipped by the far plane (z >= 0) and the near plane (w - z >= 0), Sutherland-Hodgman
+        const int u = (ax + 1) % 3, w3 = (ax + 2) % 3;
+        std::vector<std::array<double, 4>> poly, next;
+        for (int c = 0; c < 4; ++c) {
+            double mp[3];
+            mp[ax] = sg * h;
+            mp[u] = (c == 1 || c == 2) ? h : -h;
+            mp[w3] = (c >= 2) ? h : -h;
+            std::array<double, 4> q;
+            for (int r = 0; r < 4; ++r) q[r] = pv[0 * 4 + r] * mp[0] + pv[1 * 4 + r] * mp[1] + pv[2 * 4 + r] * mp[2] + pv[3 * 4 + r];
+            poly.push_back(q);
+        }
+        for (int pl = 0; pl < 2 && !poly.empty(); ++pl) {
+            auto g = [pl](const std::array<double, 4> &q) { return pl == 0 ? q[2] : q[3] - q[2]; };
+            next.clear();
+            for (size_t i = 0; i < poly.size(); ++i) {
+                const std::array<double, 4> &A = poly[i], &B = poly[(i + 1) % poly.size()];
+                const double ga = g(A), gb = g(B);
+                if (ga >= 0.0) next.push_back(A);
+                if ((ga >= 0.0) != (gb >= 0.0)) {
+                    const double tt = ga / (ga - gb);
+                    std::array<double, 4> X;
+                    for (int r = 0; r < 4; ++r) X[r] = A[r] + tt * (B[r] - A[r]);
+                    next.push_back(X);
+                }
+            }
+            poly.swap(next);
+        }
+        for (const std::array<double, 4> &q : poly) {
+            if (!(q[3] > 0.0)) { unbounded = true; continue; }
+            const double px = (q[0] / q[3] + 1.0) * 0.5 * W - 0.5, py = (q[1] / q[3] + 1.0) * 0.5 * H - 0.5;   // pixel-centre coordinates
+            if (!std::isfinite(px) || !std::isfinite(py)) { unbounded = true; continue; }
+            xmin = std::fmin(xmin, px); xmax = std::fmax(xmax, px);
+            ymin = std::fmin(ymin, py); ymax = std::fmax(ymax, py);
+        }
+    }
+    rect[0] = f->x0; rect[1] = f->y0; rect[2] = f->x0; rect[3] = f->y0;   // empty
+    *tiles_x = *tiles_y = 0;
+    if (unbounded) {   // a degenerate projection: the whole rect (the fragment test decides every pixel)
+        rect[2] = f->x1; rect[3] = f->y1;
+    } else if (xmin <= xmax && ymin <= ymax) {
+        auto cut = [](double x, int lo, int hi) { return (int)std::fmin(std::fmax(x, (double)lo), (double)hi); };
+        rect[0] = cut(std::floor(xmin) - 1.0, f->x0, f->x1);
+        rect[1] = cut(std::floor(ymin) - 1.0, f->y0, f->y1);
+        rect[2] = cut(std::ceil(xmax) + 2.0, f->x0, f->x1);
+        rect[3] = cut(std::ceil(ymax) + 2.0, f->y0, f->y1);
+    }
+    if (rect[2] <= rect[0] || rect[3] <= rect[1]) { rect[2] = rect[0]; rect[3] = rect[1]; return ATMO_OK; }
+    atmo::RenderConsts g;   // (render_grid reads the rect and the grid origin only)
+    g.x0 = rect[0]; g.y0 = rect[1]; g.x1 = rect[2]; g.y1 = rect[3];
+    g.gx0 = lod ? rect[0] & ~1 : rect[0];
+    g.gy0 = lod ? rect[1] & ~1 : rect[1];
+    atmo::render_grid(g, 1, tiles_x, tiles_y);
+    return ATMO_OK;
+}
+
+// The family a proxy draw of this context uses, or ATMO_E_STATE when there is no proxy kernel for its mode (proxy_family_supported).
+static int proxy_family(AtmoContext *ctx, const char *who, const AtmoFrame *frame, int *flags, bool *lod) {
+    const char *why_not = nullptr;
+    (void)resolve_sampler_lod(ctx, &why_not);
+    if (ctx->sampler_lod == 1 && why_not) return fail(ctx, ATMO_E_STATE, why_not);
+    int split = 1;
+    launch_shape(ctx, frame, flags, &split, lod);
+    if (split != 1 || !atmo::proxy_family_supported(*flags))
+        return fail(ctx, ATMO_E_STATE, std::string(who) + ": no proxy kernel for this context's mode (proxy draws exist for the default forms: atmo_set_precision 1, "
+                                                          "up to 32 view steps, one lane per ray)");
+    return ATMO_OK;
+}
+
+static int proxy_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev, float *rgba_dev,
+                      void *stream, bool composite) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = composite ? "atmo_render_proxy_composite" : "atmo_render_proxy";
+    if (!frame || !model_matrix) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null frame or model_matrix");
+    if (!(box_size > 0.0f) || !std::isfinite(box_size)) return fail(ctx, ATMO_E_ARG, std::string(who) + ": box_size must be positive and finite");
+    if (frame->viewport_w < 1 || frame->viewport_h < 1 || frame->viewport_w > 65536 || frame->viewport_h > 65536)
+        return fail(ctx, ATMO_E_ARG, std::string(who) + ": bad viewport size");
+    if (frame->x0 < 0 || frame->y0 < 0 || frame->x1 > frame->viewport_w || frame->y1 > frame->viewport_h || frame->x0 > frame->x1 || frame->y0 > frame->y1)
+        return fail(ctx, ATMO_E_ARG, std::string(who) + ": rect outside the viewport");
+    if (!depth_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null device pointer");
+    if ((reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, std::string(who) + ": rgba_dev must be 16-byte aligned");
+    if (!(ctx->flags & (atmo::KF_LIGHT_DIRECT | atmo::KF_LITE)) && !(ctx->lut.ptr && ctx->lut4.ptr))
+        return fail(ctx, ATMO_E_STATE, std::string(who) + ": u_optical_depth_texture not set (call atmo_bake_optical_depth or atmo_set_texture)");
+    if ((ctx->flags & atmo::KF_CLOUDS) && !ctx->shape.ptr) return fail(ctx, ATMO_E_STATE, std::string(who) + ": u_cloud_shape_texture not set");
+    int flags = 0;
+    bool lod = false;
+    { const int rc0 = proxy_family(ctx, who, frame, &flags, &lod); if (rc0 != ATMO_OK) return rc0; }
+    if (frame->x0 == frame->x1 || frame->y0 == frame->y1) return ATMO_OK;
+    AtmoFrame fixed = *frame;
+    if (ctx->host_double_precision) for (int k = 12; k < 15; ++k) fixed.inv_view_matrix[k] *= -1.0f;   // as render_impl (main:118-125)
+    atmo::ProxyConsts pc;
+    int rect[4], gx = 0, gy = 0;
+    { const int rc0 = proxy_setup(ctx, who, &fixed, model_matrix, box_size, lod, pc, rect, &gx, &gy); if (rc0 != ATMO_OK) return rc0; }
+    if (gx == 0 || gy == 0) return ATMO_OK;   // nothing of the box is on this rect between the planes: no launch
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    atmo::RenderConsts rc;
+    fill_consts(ctx, &fixed, depth_dev, rgba_dev, rc);   // the output stays addressed by the FRAME's rect (plain) or the viewport (composite)
+    if (composite) {
+        rc.out_pitch = fixed.viewport_w;
+        rc.out_x0 = 0;
+        rc.out_y0 = 0;
+        rc.composite = 1;
+        rc.store_discards = 0;
+    }
+    rc.x0 = rect[0]; rc.y0 = rect[1]; rc.x1 = rect[2]; rc.y1 = rect[3];
+    rc.gx0 = lod ? rect[0] & ~1 : rect[0];
+    rc.gy0 = lod ? rect[1] & ~1 : rect[1];
+    rc.tiles_x = gx;
+    hipStream_t s = (hipStream_t)stream;
+    { const int rc0 = tex_order(ctx, s); if (rc0 != ATMO_OK) return rc0; }
+    HIP_TRY(ctx, atmo::launch_render_proxy(flags, rc, pc, s));
+    ctx->last_flags = flags | atmo::KF_PROXY;
+    ctx->last_split = 1;
+    hipEvent_t marker = nullptr;
+    return note_draw_stream(ctx, s, &marker);
+}
+
+int atmo_render_proxy(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev, float *rgba_dev,
+                      void *stream) {
+    return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, rgba_dev, stream, false);
+}
+
+int atmo_render_proxy_composite(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev,
+                                float *scene_rgba_dev, void *stream) {
+    return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, scene_rgba_dev, stream, true);
+}
+
+int atmo_debug_proxy_launch_rect(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, int *rect_out, int *tiles_out) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_debug_proxy_launch_rect";
+    if (!frame || !model_matrix || !rect_out || !tiles_out) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null argument");
+    if (!(box_size > 0.0f) || !std::isfinite(box_size)) return fail(ctx, ATMO_E_ARG, std::string(who) + ": box_size must be positive and finite");
+    if (frame->viewport_w < 1 || frame->viewport_h < 1 || frame->x0 < 0 || frame->y0 < 0 || frame->x1 > frame->viewport_w ||
+        frame->y1 > frame->viewport_h || frame->x0 > frame->x1 || frame->y0 > frame->y1)
+        return fail(ctx, ATMO_E_ARG, std::string(who) + ": bad viewport or rect");
+    int flags = 0, split = 1;
+    bool lod = false;
+    launch_shape(ctx, frame, &flags, &split, &lod);   // the grid origin: even under the declared sampler
+    AtmoFrame fixed = *frame;
+    if (ctx->host_double_precision) for (int k = 12; k < 15; ++k) fixed.inv_view_matrix[k] *= -1.0f;
+    atmo::ProxyConsts pc;
+    int gx = 0, gy = 0;
+    { const int rc0 = proxy_setup(ctx, who, &fixed, model_matrix, box_size, lod, pc, rect_out, &gx, &gy); if (rc0 != ATMO_OK) return rc0; }
+    *tiles_out = gx * gy;
     return ATMO_OK;
 }
 

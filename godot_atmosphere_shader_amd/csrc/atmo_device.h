@@ -124,9 +124,25 @@ enum KernelFlags : int { KF_CLOUDS = 1, KF_CLOUD_LIGHT_RM = 2, KF_LIGHT_DIRECT =
                           KF_ATMO_REF = 64 /* the v2 atmosphere march in the reference's operation order (atmo_set_precision 2) */,
                           KF_VIEW_POS = 128 /* view_steps > 32: the fast v2 march accumulates the view-space position like the reference (march_atmosphere<VIEWPOS>) */,
                           KF_GEO = 256 /* the block -> tile map is the geometric order's closed form (RenderConsts::geo_rows): a twin of the plain direct-light kernel, so that
-                                          the draws that do not use it keep their preamble to the byte (the lookup compiled in cost a still camera 0.6 %) */ };
+                                          the draws that do not use it keep their preamble to the byte (the lookup compiled in cost a still camera 0.6 %) */,
+                          KF_PROXY = 512 /* the far-mode BoxMesh draw (atmo_render_proxy, include/atmo_scene.h): shade_pixel first evaluates the proxy fragment test
+                                            (ProxyConsts); its own kernel (atmo_render_proxy_kernel), so the kernels of atmo_render stay what they were */ };
+
+// The far-mode draw's proxy (planet_atmosphere.gd:300-321: a BoxMesh of edge box_size centred on the node, rasterised with back-face culling, near / far
+// clipping and Godot 4.3's reverse-Z GREATER_OR_EQUAL depth test).  Pixel (nx, ny) of the existing prologue's NDC: its segment from the near plane (z = 1) to
+// the far plane (z = 0) is inv_p (nx, ny, z, 1), in the proxy's model space  H(z) = K (nx, ny, z, 1) = a + z b,  K = model^-1 inv_view inv_p (affine times
+// projective: homogeneous coordinates, w > 0 between the planes).  |H_i| <= h H_w is linear in z for each of the six faces, so the part of the segment inside
+// the closed box is an interval [z_lo, z_hi] of depths, solved in closed form: covered = the interval is not empty and excludes z = 1 (the near end lies
+// outside); the front-face fragment's depth is its near end, z_in = z_hi.  Built by the host in double and rounded once (proxy_consts in atmo_api.hip).
+struct ProxyConsts {
+    float k[4][4];   // [host] rows x, y, z, w of K (row-major here: k[row][col])
+    float half;      // [host] box_size / 2
+};
 
 hipError_t launch_render(int flags, int split, const RenderConsts &rc, hipStream_t stream, int tile_list_blocks = 0);  // > 0: rc.tile_order lists that many tiles of the rect's grid
+// the proxy draws: one lane per ray, row-major grid of the rect in rc; flags = a draw's family without KF_PROXY (proxy_family_supported)
+bool proxy_family_supported(int flags);
+hipError_t launch_render_proxy(int flags, const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream);
 hipError_t launch_bake(const BakeConsts &bc, hipStream_t stream);
 hipError_t launch_tile_order(uint32_t *cost, uint32_t *order, int tiles_x, int tiles_y, int rx, int ry, uint32_t *tmp1, uint32_t *tmp2,
                              uint32_t *scratch, hipStream_t stream, uint32_t *order2 = nullptr, uint32_t *class_totals = nullptr);

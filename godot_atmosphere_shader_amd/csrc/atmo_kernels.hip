@@ -1912,8 +1912,34 @@ __device__ __forceinline__ float2 march_clouds_rm_queue(const RenderConsts &rc, 
     return make_float2(rec.total_light, 1.0f - rec.one_minus_alpha);
 }
 
+// The proxy fragment test of the far-mode draw (KF_PROXY; ProxyConsts states the geometry): true = pixel (px, py) is a fragment of the BoxMesh's
+// front face -- its near-to-far segment starts outside the closed box and enters it -- and that fragment passes the depth test.  The test is Godot 4.3's
+// for a spatial material with depth_draw_opaque and no depth_test_disabled under its reverse-Z forward renderers: GREATER_OR_EQUAL against the depth
+// buffer (engine behaviour, not in the reference tree).  Each face's half-space c0 + z c1 <= 0 bounds the segment's depth interval from one side.
+__device__ __forceinline__ bool proxy_fragment_passes(const ProxyConsts &pc, const RenderConsts &rc, const int px, const int py) {
+    const float nx = pixel_coord<true>((float)px + 0.5f, rc.vw, rc.rcp_vw) * 2.0f - 1.0f;   // the prologue's NDC (the same bits as its pixel_coord)
+    const float ny = pixel_coord<true>((float)py + 0.5f, rc.vh, rc.rcp_vh) * 2.0f - 1.0f;
+    float a[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) a[r] = pc.k[r][0] * nx + pc.k[r][1] * ny + pc.k[r][3];
+    float z_lo = 0.0f, z_hi = 1.0f;
+    bool empty = false;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {   // faces +x, -x, +y, -y, +z, -z:  +-H_i - h H_w <= 0
+        const float sg = (i & 1) ? -1.0f : 1.0f;
+        const float c0 = sg * a[i >> 1] - pc.half * a[3];
+        const float c1 = sg * pc.k[i >> 1][2] - pc.half * pc.k[3][2];
+        if (c1 > 0.0f) z_hi = fminf(z_hi, ieee_div(-c0, c1));
+        else if (c1 < 0.0f) z_lo = fmaxf(z_lo, ieee_div(-c0, c1));
+        else empty = empty || c0 > 0.0f;
+    }
+    // covered: the segment meets the box (a non-empty interval) and its near end z = 1 is not inside it; the fragment's depth is the entry's, z_hi
+    if (empty || z_lo > z_hi || !(z_hi < 1.0f)) return false;
+    return z_hi >= rc.depth[(size_t)py * rc.w + px];
+}
+
 template <int FLAGS, int LSTEPS, int SPLIT>
-__device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int tile_x, const int tile_y) {
+__device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int tile_x, const int tile_y, const ProxyConsts *pc = nullptr) {
     constexpr bool CLOUDS = (FLAGS & KF_CLOUDS) != 0;
     constexpr bool RM = (FLAGS & KF_CLOUD_LIGHT_RM) != 0;
     constexpr bool DIRECT = (FLAGS & KF_LIGHT_DIRECT) != 0;
@@ -1922,7 +1948,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     constexpr bool LOD = (FLAGS & KF_CUBE_LOD) != 0;
     constexpr bool ATMO_REF = (FLAGS & KF_ATMO_REF) != 0;
     constexpr bool VIEWPOS = (FLAGS & KF_VIEW_POS) != 0;
+    constexpr bool PROXY = (FLAGS & KF_PROXY) != 0;
     static_assert(!VIEWPOS || (!LITE && !ATMO_REF && SPLIT == 1), "KF_VIEW_POS: the fast v2 march, one lane per ray");
+    static_assert(!PROXY || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0), "proxy draws: the default forms, one lane per ray, row-major");
     constexpr bool DIET = !DIRECT && !((FLAGS & KF_CLOUDS) && (FLAGS & KF_CLOUD_LIGHT_RM));
     constexpr bool FASTMISS = (ATMO_FAST_MISS_MASK >> ((DIRECT ? 1 : 0) + (CLOUDS ? 2 : 0) + (LITE ? 4 : 0))) & 1;
     static_assert(!LOD || (CLOUDS && PRECISE), "implicit cubemap LOD: precise cloud kernels");
@@ -1960,7 +1988,21 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     QuadRegs qregs;
     if constexpr (LOD) quad_regs_define(qregs);  // all 64 lanes are still here: nothing else may ever live in these registers
     if (LOD ? (px >= rc.w || py >= rc.h) : (px >= rc.x1 || py >= rc.y1)) return;
-    const bool helper = LOD && (px < rc.x0 || py < rc.y0 || px >= rc.x1 || py >= rc.y1);
+    bool helper = LOD && (px < rc.x0 || py < rc.y0 || px >= rc.x1 || py >= rc.y1);
+    if constexpr (PROXY) {
+        // The far-mode draw: only the box's passing fragments are shaded and stored.  In front of every store of this function (the sure-miss and the
+        // discard store included).  Without the declared sampler a failing lane simply leaves.  With it, a failing pixel becomes a HELPER, like a pixel
+        // outside the rect: it marches for its quad mates and stores nothing -- a partner's picture depends on that pixel's ray alone, so a passing pixel
+        // is bit-identical to atmo_render's -- and a quad with no passing pixel leaves whole.
+        const bool pass = proxy_fragment_passes(*pc, rc, px, py);
+        if constexpr (LOD) {
+            const unsigned long long drawn = __builtin_amdgcn_ballot_w64(pass && !helper);
+            if (((drawn >> (lane & ~3)) & 0xFull) == 0) return;
+            helper = helper || !pass;
+        } else {
+            if (!pass) return;
+        }
+    }
     float4 *out = rc.out + (size_t)(py - rc.out_y0) * (size_t)rc.out_pitch + (px - rc.out_x0);
 
     // --- sure-miss test in front of the exact prologue (round 3) ----------------------------------------
@@ -2240,6 +2282,13 @@ __device__ __forceinline__ uint32_t geo_tile(const RenderConsts &rc, uint32_t b)
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
 __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_kernel(const RenderConsts rc) {
     ATMO_RENDER_KERNEL_BODY
+}
+// The far-mode proxy draw (KF_PROXY; atmo_render_proxy): the launch grid covers the box's screen rectangle only (the host clips it), row-major, no tile
+// order, no cost feedback -- its grid changes every frame.  A kernel of its own, so that atmo_render's kernels keep their code to the byte.
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_proxy_kernel(const RenderConsts rc, const ProxyConsts pc) {
+    static_assert((FLAGS & KF_PROXY) != 0, "proxy kernels carry KF_PROXY");
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, &pc);
 }
 // the same kernel under an 80-SGPR cap (8 waves per SIMD), for the families render_sgpr_cap80 names (none in the shipped build)
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
@@ -2856,11 +2905,61 @@ static hipError_t launch_render_grid(int flags, int split, const RenderConsts &r
     return hipErrorInvalidValue;
 }
 
+// The families a proxy draw exists for (atmo_render_proxy): what a default context selects -- one lane per ray, the precise cloud and v1 forms, up to
+// 32 view steps.  Precision 0 and 2, long view marches (KF_VIEW_POS) and lane split have no proxy kernel: the host refuses those draws (ATMO_E_STATE).
+template <int FLAGS, int LSTEPS>
+static hipError_t launch_p(const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream) {
+    int gx, gy;
+    render_grid(rc, 1, &gx, &gy);
+    if (gx != rc.tiles_x || gx < 1 || gy < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((atmo_render_proxy_kernel<FLAGS | KF_PROXY, LSTEPS>), dim3(gx, gy), dim3(TILE_W * TILE_H), 0, stream, rc, pc);
+    return hipGetLastError();
+}
+template <int FLAGS>
+static hipError_t launch_p_direct(const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream) {   // 8 light steps unrolled, as launch_direct
+    return rc.light_steps == 8 ? launch_p<FLAGS, 8>(rc, pc, stream) : launch_p<FLAGS, 0>(rc, pc, stream);
+}
+hipError_t launch_render_proxy(int flags, const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream) {
+    switch (flags) {
+    case 0: return launch_p<0, 0>(rc, pc, stream);
+    case KF_LIGHT_DIRECT: return launch_p_direct<KF_LIGHT_DIRECT>(rc, pc, stream);
+    case KF_PRECISE | KF_CLOUDS: return launch_p<KF_PRECISE | KF_CLOUDS, 0>(rc, pc, stream);
+    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_p<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, pc, stream);
+    case KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_p_direct<KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, pc, stream);
+    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT: return launch_p_direct<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, pc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: return launch_p<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS, 0>(rc, pc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_p<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, pc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_p_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, pc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
+        return launch_p_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, pc, stream);
+    case KF_PRECISE | KF_LITE: return launch_p<KF_PRECISE | KF_LITE, 0>(rc, pc, stream);
+    case KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_p<KF_PRECISE | KF_LITE | KF_CLOUDS, 0>(rc, pc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_p<KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS, 0>(rc, pc, stream);
+    default: return hipErrorInvalidValue;   // (the host asks proxy_family_supported first)
+    }
+}
+bool proxy_family_supported(int flags) {
+    switch (flags) {
+    case 0: case KF_LIGHT_DIRECT:
+    case KF_PRECISE | KF_CLOUDS: case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM:
+    case KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM:
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
+    case KF_PRECISE | KF_LITE: case KF_PRECISE | KF_LITE | KF_CLOUDS: case KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS:
+        return true;
+    default: return false;
+    }
+}
+
 const char *render_kernel_name(int flags, int light_steps, int split) {
-    // demangled template name as rocprofv3 prints it: atmo_render_kernel<FLAGS, LSTEPS, SPLIT>
+    // demangled template name as rocprofv3 prints it: atmo_render_kernel<FLAGS, LSTEPS, SPLIT>; atmo_render_proxy_kernel<FLAGS, LSTEPS> for KF_PROXY
     static thread_local char name[64];
     const bool v2_precise = (flags & KF_ATMO_REF) != 0;  // its light march is a run-time loop
     const int lsteps = ((flags & KF_LIGHT_DIRECT) && light_steps == 8 && !v2_precise && !(flags & KF_VIEW_POS)) ? 8 : 0;
+    if (flags & KF_PROXY) {
+        snprintf(name, sizeof(name), "atmo_render_proxy_kernel<%d, %d>", flags, lsteps);
+        return name;
+    }
     snprintf(name, sizeof(name), "atmo_render_kernel%s<%d, %d, %d>", render_sgpr_cap80(flags) ? "_s80" : "", flags, lsteps, split == 2 ? 2 : 1);
     return name;
 }

@@ -16,6 +16,8 @@ names, argument meaning and (silent) error behaviour:
   _get_property_list (:185-197)                        `get_property_list()`
   _process (:285-341)                                  `_process(delta, camera, time)`: per-frame uniforms
   (the draw itself: Godot renderer)                    `render(camera, depth, out, rect, stream)`
+  far mode's BoxMesh (:1-3,56-58,98-101,300-321)       `render_proxy*`, `proxy_box_size`; `draw` = the current mode's draw
+  (several nodes in one frame: Godot renderer)         `draw_atmospheres(nodes, camera, depth, scene_rgba)`: back to front
 
 The fragment work runs only on the GPU: `render` raises if libatmo_hip.so or a gfx950 device is missing.
 """
@@ -507,7 +509,7 @@ class PlanetAtmosphere:
             return tuple(float(x) for x in s.global_position)
         return tuple(float(x) for x in s)
 
-    def _set_mode(self, mode: int):  # planet_atmosphere.gd:261-282 (mesh swap is rasteriser-only)
+    def _set_mode(self, mode: int):  # planet_atmosphere.gd:261-282 (the mesh swap: `draw` picks the quad or the BoxMesh by _mode)
         if mode == self._mode:
             return
         self._mode = mode
@@ -602,6 +604,61 @@ class PlanetAtmosphere:
         N.check(self._ctx, rc)
         return scene_rgba
 
+    # ---- the far-mode draw: the BoxMesh proxy (include/atmo_scene.h) ---------------------------------------------------------------
+    def proxy_box_size(self, camera=None) -> float:
+        """Edge of the far mode's BoxMesh: the reference's atmo_clip_distance (planet_atmosphere.gd:300-321), 1.75 (R + H + camera near) 1.1."""
+        cam_near = 0.1 if camera is None else camera.near
+        return 1.75 * (self._planet_radius + self._atmosphere_height + cam_near) * SWITCH_MARGIN_RATIO
+
+    def _proxy_call(self, fn, camera, depth, target, rect, stream, time, box_size):
+        frame = self.make_frame(camera, time, rect)
+        if stream is None:
+            stream = _torch_stream(depth)
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        self._bake_if_needed(stream)
+        nf = _to_native_frame(frame)
+        model = (C.c_float * 16)(*[float(x) for x in col_major(self.global_transform)])
+        size = self.proxy_box_size(camera) if box_size is None else float(box_size)
+        rc = fn(self._ctx, C.byref(nf), model, C.c_float(size), C.c_void_p(depth.data_ptr()), C.c_void_p(target.data_ptr()), C.c_void_p(stream or 0))
+        N.check(self._ctx, rc)
+
+    def render_proxy(self, camera, depth, out=None, rect=None, stream=None, time: float = 0.0, box_size: float | None = None):
+        """`render` through the far mode's BoxMesh (default edge: proxy_box_size(camera)) centred on global_transform: only the box's front-face
+        fragments that pass the depth test are shaded and written (atmo_render_proxy); every other pixel of `out` is left as it was."""
+        import torch
+
+        x0, y0, x1, y1 = rect if rect is not None else (0, 0, camera.width, camera.height)
+        if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
+                and tuple(depth.shape) == (camera.height, camera.width)):
+            raise TypeError("depth must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w)")
+        if out is None:
+            out = torch.zeros((y1 - y0, x1 - x0, 4), dtype=torch.float32, device=depth.device)
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (y1 - y0, x1 - x0, 4)):
+            raise ValueError("out must be a contiguous CUDA float32 tensor of shape (rect_h, rect_w, 4)")
+        self._proxy_call(self._lib.atmo_render_proxy, camera, depth, out, rect, stream, time, box_size)
+        return out
+
+    def render_proxy_composite(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0, box_size: float | None = None):
+        """`render_composite` through the far mode's BoxMesh (atmo_render_proxy_composite).  Returns `scene_rgba`."""
+        import torch
+
+        if not (isinstance(scene_rgba, torch.Tensor) and scene_rgba.is_cuda and scene_rgba.dtype == torch.float32
+                and scene_rgba.is_contiguous() and tuple(scene_rgba.shape) == (camera.height, camera.width, 4)):
+            raise ValueError("scene_rgba must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w, 4)")
+        if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
+                and tuple(depth.shape) == (camera.height, camera.width)):
+            raise TypeError("depth must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w)")
+        self._proxy_call(self._lib.atmo_render_proxy_composite, camera, depth, scene_rgba, rect, stream, time, box_size)
+        return scene_rgba
+
+    def draw(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0):
+        """The draw Godot makes for this node in its current mode (set by `_process`): near mode the fullscreen quad (`render_composite`), far mode
+        the BoxMesh of the reference's size (`render_proxy_composite`).  Returns `scene_rgba`."""
+        if self._mode == MODE_NEAR:
+            return self.render_composite(camera, depth, scene_rgba, rect=rect, stream=stream, time=time)
+        return self.render_proxy_composite(camera, depth, scene_rgba, rect=rect, stream=stream, time=time)
+
     def render_raw(self, frame: dict, depth_ptr: int, out_ptr: int, stream: int = 0):
         """`render` on raw device addresses (what a non-torch host would call)."""
         self._bake_if_needed(stream)
@@ -679,3 +736,26 @@ class PlanetAtmosphere:
         n, ms = C.c_int(0), C.c_double(0.0)
         N.check(self._ctx, self._lib.atmo_get_timing(self._ctx, C.byref(n), C.byref(ms)))
         return n.value, ms.value
+
+
+def _torch_stream(tensor) -> int:
+    import torch
+
+    return torch.cuda.current_stream(tensor.device).cuda_stream
+
+
+def draw_order(nodes, camera) -> list:
+    """The order Godot draws alpha-blended instances of equal render priority in: back to front by the distance from the camera to the centre of
+    each instance's AABB, farthest first (engine behaviour: the transparent render list's depth sort).  For both meshes of a PlanetAtmosphere that
+    centre is the node's origin (the BoxMesh and the near-mode quad are centred on it).  Stable for equal distances."""
+    cam_pos = np.asarray(camera.inv_view, dtype=np.float64)[:3, 3]
+    dist = [float(np.linalg.norm(np.asarray(n.global_transform, dtype=np.float64)[:3, 3] - cam_pos)) for n in nodes]
+    return [nodes[i] for i in sorted(range(len(nodes)), key=lambda i: -dist[i])]
+
+
+def draw_atmospheres(nodes, camera, depth, scene_rgba, stream=None, time: float = 0.0):
+    """Draws several PlanetAtmosphere nodes into one frame as Godot does: each node's draw for its current mode (`PlanetAtmosphere.draw`: the
+    fullscreen quad near, the BoxMesh far), composited over `scene_rgba` in place, back to front (`draw_order`).  Returns `scene_rgba`."""
+    for node in draw_order(list(nodes), camera):
+        node.draw(camera, depth, scene_rgba, stream=stream, time=time)
+    return scene_rgba

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define ATMO_ABI_VERSION 4
+#define ATMO_ABI_VERSION 5   /* 5: include/atmo_scene.h (atmo_render_proxy*); AtmoFrame and every call here as in 4 */
 
 typedef struct AtmoContext AtmoContext;
 
