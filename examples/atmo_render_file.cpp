@@ -4,17 +4,21 @@
 //
 //   hipcc -O2 -I include examples/atmo_render_file.cpp -L godot_atmosphere_shader_amd -latmo_hip \
 //         -Wl,-rpath,$PWD/godot_atmosphere_shader_amd -o atmo_render_file
-//   ./atmo_render_file <frame.bin> <depth.bin> <out.bin> <planet_radius> <atmosphere_height> <u_density> <view_steps>
+//   ./atmo_render_file <frame.bin> <depth.bin> <out.bin> <planet_radius> <atmosphere_height> <u_density> <view_steps> [--target rgba16f|rgba8]
 //
 // frame.bin = one AtmoFrame struct; depth.bin = viewport_h*viewport_w floats; out.bin = rect RGBA float4.
 // tests/test_gpu_parity.py::test_native_host_matches_python_binding checks the bytes against the Python path.
+// --target (include/atmo_target.h): the draw stores RGBA16F (8 bytes per pixel) or RGBA8_UNORM (4) instead, as into a renderer's own colour buffer;
+// out.bin then holds those pixels, tightly packed (tests/test_target_gpu.py::test_native_host_draws_into_a_packed_target).
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "atmo.h"
+#include "atmo_target.h"
 
 #define CHECK_ATMO(call)                                                                       \
     do {                                                                                       \
@@ -42,8 +46,13 @@ static bool read_file(const char *path, void *dst, size_t bytes) {
 }
 
 int main(int argc, char **argv) {
-    if (argc != 8) {
-        std::fprintf(stderr, "usage: %s frame.bin depth.bin out.bin planet_radius atmosphere_height u_density view_steps\n", argv[0]);
+    int format = ATMO_TARGET_RGBA32F;
+    if (argc == 10 && std::strcmp(argv[8], "--target") == 0) {
+        if (std::strcmp(argv[9], "rgba16f") == 0) format = ATMO_TARGET_RGBA16F;
+        else if (std::strcmp(argv[9], "rgba8") == 0) format = ATMO_TARGET_RGBA8_UNORM;
+        else { std::fprintf(stderr, "--target: rgba16f or rgba8\n"); return 2; }
+    } else if (argc != 8) {
+        std::fprintf(stderr, "usage: %s frame.bin depth.bin out.bin planet_radius atmosphere_height u_density view_steps [--target rgba16f|rgba8]\n", argv[0]);
         return 2;
     }
     AtmoContext *ctx = nullptr;
@@ -68,18 +77,27 @@ int main(int argc, char **argv) {
     CHECK_ATMO(atmo_bake_optical_depth(ctx, nullptr));  // replaces OpticalDepthBaker's SubViewport round trip
 
     const size_t rect_pix = (size_t)(frame.x1 - frame.x0) * (frame.y1 - frame.y0);
-    float *d_depth = nullptr, *d_rgba = nullptr;
+    // a host detects packed targets by the query, not by the ABI version (which they did not change)
+    const size_t pixel_bytes = (size_t)atmo_target_pixel_bytes(format);
+    if (pixel_bytes == 0) { std::fprintf(stderr, "this libatmo_hip does not draw into target format %d\n", format); return 1; }
+    float *d_depth = nullptr;
+    void *d_rgba = nullptr;
     CHECK_HIP(hipMalloc((void **)&d_depth, npix * sizeof(float)));
-    CHECK_HIP(hipMalloc((void **)&d_rgba, rect_pix * 4 * sizeof(float)));
+    CHECK_HIP(hipMalloc(&d_rgba, rect_pix * pixel_bytes));
     CHECK_HIP(hipMemcpy(d_depth, depth.data(), npix * sizeof(float), hipMemcpyHostToDevice));
-    CHECK_ATMO(atmo_render(ctx, &frame, d_depth, d_rgba, nullptr));
+    if (format == ATMO_TARGET_RGBA32F) {
+        CHECK_ATMO(atmo_render(ctx, &frame, d_depth, (float *)d_rgba, nullptr));
+    } else {
+        const AtmoTarget target = {d_rgba, format, /*row_pitch_bytes: tight*/ 0};
+        CHECK_ATMO(atmo_render_target(ctx, &frame, d_depth, &target, /*composite*/ 0, nullptr));
+    }
     CHECK_HIP(hipDeviceSynchronize());
-    std::vector<float> rgba(rect_pix * 4);
-    CHECK_HIP(hipMemcpy(rgba.data(), d_rgba, rgba.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<unsigned char> rgba(rect_pix * pixel_bytes);
+    CHECK_HIP(hipMemcpy(rgba.data(), d_rgba, rgba.size(), hipMemcpyDeviceToHost));
     FILE *f = std::fopen(argv[3], "wb");
-    if (!f || std::fwrite(rgba.data(), sizeof(float), rgba.size(), f) != rgba.size()) { std::fprintf(stderr, "cannot write %s\n", argv[3]); return 1; }
+    if (!f || std::fwrite(rgba.data(), 1, rgba.size(), f) != rgba.size()) { std::fprintf(stderr, "cannot write %s\n", argv[3]); return 1; }
     std::fclose(f);
-    std::printf("atmo_render: %zu pixels shaded\n", rect_pix);
+    std::printf("%s: %zu pixels shaded, %zu bytes each\n", format == ATMO_TARGET_RGBA32F ? "atmo_render" : "atmo_render_target", rect_pix, pixel_bytes);
     (void)hipFree(d_depth);
     (void)hipFree(d_rgba);
     CHECK_ATMO(atmo_destroy(ctx));

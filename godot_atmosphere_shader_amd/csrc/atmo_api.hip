@@ -8,6 +8,7 @@
 #include "../../include/atmo.h"
 #include "../../include/atmo_debug.h"
 #include "../../include/atmo_scene.h"
+#include "../../include/atmo_target.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 
@@ -1290,8 +1291,10 @@ int atmo_read_optical_depth(AtmoContext *ctx, float *lut_host, uint8_t *rgba8_ho
     return ATMO_OK;
 }
 
+// tc != nullptr: a packed colour target (atmo_render_target): rgba_dev is its pixels (checked by the caller), the launches are the KF_TARGET kernels';
+// pitch_px > 0: pixels per output row (an RGBA32F target with a pitch)
 static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream, bool composite,
-                       const uint32_t *tiles_dev = nullptr, int n_tiles = 0, int n_heavy = 0);
+                       const uint32_t *tiles_dev = nullptr, int n_tiles = 0, int n_heavy = 0, const atmo::TargetConsts *tc = nullptr, int pitch_px = 0);
 
 int atmo_render(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream) {
     return render_impl(ctx, frame, depth_dev, rgba_dev, stream, false);
@@ -1481,7 +1484,7 @@ static int note_draw_stream(AtmoContext *ctx, hipStream_t s, hipEvent_t *marker)
 }
 
 static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream, bool composite,
-                       const uint32_t *tiles_dev, int n_tiles, int n_heavy) {
+                       const uint32_t *tiles_dev, int n_tiles, int n_heavy, const atmo::TargetConsts *tc, int pitch_px) {
     if (!ctx) return ATMO_E_ARG;
     if (!frame) return fail(ctx, ATMO_E_ARG, "atmo_render: null frame");
     if (frame->viewport_w < 1 || frame->viewport_h < 1 || frame->viewport_w > 65536 || frame->viewport_h > 65536)
@@ -1491,7 +1494,7 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
         return fail(ctx, ATMO_E_ARG, "atmo_render: rect outside the viewport");
     if (frame->x0 == frame->x1 || frame->y0 == frame->y1) return ATMO_OK;  // empty rect: nothing to shade
     if (!depth_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, "atmo_render: null device pointer");
-    if ((reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, "atmo_render: rgba_dev must be 16-byte aligned");
+    if (!tc && (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, "atmo_render: rgba_dev must be 16-byte aligned");
     if (!(ctx->flags & (atmo::KF_LIGHT_DIRECT | atmo::KF_LITE)) && !(ctx->lut.ptr && ctx->lut4.ptr))
         return fail(ctx, ATMO_E_STATE, "atmo_render: u_optical_depth_texture not set (call atmo_bake_optical_depth or atmo_set_texture)");
     if ((ctx->flags & atmo::KF_CLOUDS) && !ctx->shape.ptr)
@@ -1515,6 +1518,12 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
         rc.composite = 1;
         rc.store_discards = 0;
     }
+    if (pitch_px > 0) rc.out_pitch = pitch_px;
+    if (tc) rc.out = nullptr;   // the KF_TARGET kernels address tc->pixels, rows tc->pitch_bytes apart
+    // the launches of this draw: the float kernels, or their packed-target twins
+    auto launch = [tc](int lflags, int lsplit, const atmo::RenderConsts &lrc, hipStream_t ls, int blocks) {
+        return tc ? atmo::launch_render_target(lflags, lsplit, lrc, *tc, ls, blocks) : atmo::launch_render(lflags, lsplit, lrc, ls, blocks);
+    };
     hipStream_t s = (hipStream_t)stream;
     { const int rc0 = tex_order(ctx, s); if (rc0 != ATMO_OK) return rc0; }  // texture updated on another stream
     int split = 1, flags = 0;
@@ -1762,18 +1771,18 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
         atmo::RenderConsts rc2 = rc;
         rc2.tile_order = order2;                       // two half-height tiles per heavy tile, heaviest first
         rc2.cost_rows_halved = 1;                      // ... whose costs belong to the one-lane grid's tile (only this launch: ADVICE r5)
-        HIP_TRY(ctx, atmo::launch_render(flags, 2, rc2, ctx->split_stream, 2 * heavy));
+        HIP_TRY(ctx, launch(flags, 2, rc2, ctx->split_stream, 2 * heavy));
         if (total_tiles - heavy > 0) {
             rc.tile_order += heavy;                    // the rest of the order, one lane per ray
-            HIP_TRY(ctx, atmo::launch_render(flags, split, rc, s, total_tiles - heavy));
+            HIP_TRY(ctx, launch(flags, split, rc, s, total_tiles - heavy));
         }
         { const int rc0 = order_after_stream(ctx, s, ctx->split_stream); if (rc0 != ATMO_OK) return rc0; }   // join
         ctx->split_draws += 1;
         ctx->split_tiles_last = (unsigned)heavy;
     } else {
-        HIP_TRY(ctx, atmo::launch_render(launch_flags, split, rc, s, tiles_dev ? n_tiles : 0));
+        HIP_TRY(ctx, launch(launch_flags, split, rc, s, tiles_dev ? n_tiles : 0));
     }
-    ctx->last_flags = flags;
+    ctx->last_flags = tc ? (flags | atmo::KF_TARGET) : flags;
     if (fb_record) {
         // Sort on the side stream as soon as this draw is done (the sort also clears the costs for the next recording).
         // order[write] was last read by draws enqueued on `s` before this one, so the event orders the write too.
@@ -2154,9 +2163,9 @@ static int proxy_family(AtmoContext *ctx, const char *who, const AtmoFrame *fram
 }
 
 static int proxy_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev, float *rgba_dev,
-                      void *stream, bool composite) {
+                      void *stream, bool composite, const atmo::TargetConsts *tc = nullptr, int pitch_px = 0) {   // tc, pitch_px: as render_impl's
     if (!ctx) return ATMO_E_ARG;
-    const char *who = composite ? "atmo_render_proxy_composite" : "atmo_render_proxy";
+    const char *who = (tc || pitch_px) ? "atmo_render_proxy_target" : composite ? "atmo_render_proxy_composite" : "atmo_render_proxy";
     if (!frame || !model_matrix) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null frame or model_matrix");
     if (!(box_size > 0.0f) || !std::isfinite(box_size)) return fail(ctx, ATMO_E_ARG, std::string(who) + ": box_size must be positive and finite");
     if (frame->viewport_w < 1 || frame->viewport_h < 1 || frame->viewport_w > 65536 || frame->viewport_h > 65536)
@@ -2164,7 +2173,7 @@ static int proxy_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *mod
     if (frame->x0 < 0 || frame->y0 < 0 || frame->x1 > frame->viewport_w || frame->y1 > frame->viewport_h || frame->x0 > frame->x1 || frame->y0 > frame->y1)
         return fail(ctx, ATMO_E_ARG, std::string(who) + ": rect outside the viewport");
     if (!depth_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null device pointer");
-    if ((reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, std::string(who) + ": rgba_dev must be 16-byte aligned");
+    if (!tc && (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, std::string(who) + ": rgba_dev must be 16-byte aligned");
     if (!(ctx->flags & (atmo::KF_LIGHT_DIRECT | atmo::KF_LITE)) && !(ctx->lut.ptr && ctx->lut4.ptr))
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": u_optical_depth_texture not set (call atmo_bake_optical_depth or atmo_set_texture)");
     if ((ctx->flags & atmo::KF_CLOUDS) && !ctx->shape.ptr) return fail(ctx, ATMO_E_STATE, std::string(who) + ": u_cloud_shape_texture not set");
@@ -2188,14 +2197,17 @@ static int proxy_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *mod
         rc.composite = 1;
         rc.store_discards = 0;
     }
+    if (pitch_px > 0) rc.out_pitch = pitch_px;
+    if (tc) rc.out = nullptr;
     rc.x0 = rect[0]; rc.y0 = rect[1]; rc.x1 = rect[2]; rc.y1 = rect[3];
     rc.gx0 = lod ? rect[0] & ~1 : rect[0];
     rc.gy0 = lod ? rect[1] & ~1 : rect[1];
     rc.tiles_x = gx;
     hipStream_t s = (hipStream_t)stream;
     { const int rc0 = tex_order(ctx, s); if (rc0 != ATMO_OK) return rc0; }
-    HIP_TRY(ctx, atmo::launch_render_proxy(flags, rc, pc, s));
-    ctx->last_flags = flags | atmo::KF_PROXY;
+    if (tc) HIP_TRY(ctx, atmo::launch_render_proxy_target(flags, rc, pc, *tc, s));
+    else HIP_TRY(ctx, atmo::launch_render_proxy(flags, rc, pc, s));
+    ctx->last_flags = flags | atmo::KF_PROXY | (tc ? atmo::KF_TARGET : 0);
     ctx->last_split = 1;
     hipEvent_t marker = nullptr;
     return note_draw_stream(ctx, s, &marker);
@@ -2209,6 +2221,85 @@ int atmo_render_proxy(AtmoContext *ctx, const AtmoFrame *frame, const float *mod
 int atmo_render_proxy_composite(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev,
                                 float *scene_rgba_dev, void *stream) {
     return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, scene_rgba_dev, stream, true);
+}
+
+// ---- packed colour targets (include/atmo_target.h) ----------------------------------------------------------------------------------------
+int atmo_target_pixel_bytes(int format) {
+    switch (format) {
+    case ATMO_TARGET_RGBA32F: return 16;
+    case ATMO_TARGET_RGBA16F: return 8;
+    case ATMO_TARGET_RGBA8_UNORM: return 4;
+    default: return 0;
+    }
+}
+
+// The argument checks of both target draws (everything that needs no device, in front of everything that does): on success *pitch_out = the row pitch
+// in bytes (the tight pitch for row_pitch_bytes == 0).
+static int target_check(AtmoContext *ctx, const char *who, const AtmoFrame *frame, const AtmoTarget *target, bool composite, int *pitch_out) {
+    if (!frame) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null frame");
+    if (!target) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null target");
+    const int px = atmo_target_pixel_bytes(target->format);
+    if (px == 0) return fail(ctx, ATMO_E_ARG, std::string(who) + ": unknown target format " + std::to_string(target->format));
+    if (!target->pixels) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null target pixels");
+    if ((reinterpret_cast<uintptr_t>(target->pixels) & (uintptr_t)(px - 1)) != 0)
+        return fail(ctx, ATMO_E_ARG, std::string(who) + ": target pixels must be aligned to the pixel size (" + std::to_string(px) + " bytes)");
+    if (frame->viewport_w < 1 || frame->viewport_h < 1 || frame->viewport_w > 65536 || frame->viewport_h > 65536)
+        return fail(ctx, ATMO_E_ARG, std::string(who) + ": bad viewport size");
+    if (frame->x0 < 0 || frame->y0 < 0 || frame->x1 > frame->viewport_w || frame->y1 > frame->viewport_h || frame->x0 > frame->x1 || frame->y0 > frame->y1)
+        return fail(ctx, ATMO_E_ARG, std::string(who) + ": rect outside the viewport");
+    const long long row_bytes = (long long)(composite ? frame->viewport_w : frame->x1 - frame->x0) * px;
+    long long pitch = target->row_pitch_bytes;
+    if (pitch == 0) pitch = row_bytes;
+    if (pitch < row_bytes || pitch % px != 0)
+        return fail(ctx, ATMO_E_ARG, std::string(who) + ": row_pitch_bytes must be 0, or at least the row's bytes (" + std::to_string(row_bytes) +
+                                         ") and a multiple of the pixel size (" + std::to_string(px) + ")");
+    *pitch_out = (int)pitch;   // (row_bytes <= 65536 * 16 and pitch is an int32: no overflow)
+    return ATMO_OK;
+}
+
+// The packed formats are drawn by the default forms' kernels only (target_family_supported); RGBA32F by the float kernels, whatever the mode.
+static int target_family(AtmoContext *ctx, const char *who, const AtmoFrame *frame) {
+    int flags = 0, split = 1;
+    launch_shape(ctx, frame, &flags, &split, nullptr);
+    if (!atmo::target_family_supported(flags, split))
+        return fail(ctx, ATMO_E_STATE, std::string(who) + ": no RGBA16F / RGBA8 kernel for this context's mode (packed targets exist for the default forms: "
+                                                          "atmo_set_precision 1, up to 32 view steps, one lane per ray); RGBA32F targets work in every mode");
+    return ATMO_OK;
+}
+
+int atmo_render_target(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, const AtmoTarget *target, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    int pitch = 0;
+    { const int rc0 = target_check(ctx, "atmo_render_target", frame, target, composite != 0, &pitch); if (rc0 != ATMO_OK) return rc0; }
+    if (target->format == ATMO_TARGET_RGBA32F)   // the float kernels themselves: a pitch in whole pixels is all they need
+        return render_impl(ctx, frame, depth_dev, (float *)target->pixels, stream, composite != 0, nullptr, 0, 0, nullptr, pitch / 16);
+    { const int rc0 = target_family(ctx, "atmo_render_target", frame); if (rc0 != ATMO_OK) return rc0; }
+    const atmo::TargetConsts tc = {target->pixels, pitch, target->format};
+    return render_impl(ctx, frame, depth_dev, (float *)target->pixels, stream, composite != 0, nullptr, 0, 0, &tc, 0);
+}
+
+int atmo_render_proxy_target(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev,
+                             const AtmoTarget *target, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    int pitch = 0;
+    { const int rc0 = target_check(ctx, "atmo_render_proxy_target", frame, target, composite != 0, &pitch); if (rc0 != ATMO_OK) return rc0; }
+    if (target->format == ATMO_TARGET_RGBA32F)
+        return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, (float *)target->pixels, stream, composite != 0, nullptr, pitch / 16);
+    const atmo::TargetConsts tc = {target->pixels, pitch, target->format};   // (proxy_impl refuses the modes without a proxy kernel: the same set)
+    return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, (float *)target->pixels, stream, composite != 0, &tc, 0);
+}
+
+// atmo_debug.h: the kernels' store_target<format> on caller-supplied DEVICE arrays -- dst[i] = encode(src[i]), or, composite, encode(blend(src[i], decode(dst[i])))
+int atmo_debug_store_target(AtmoContext *ctx, int format, int composite, const float *src_rgba_f32_dev, void *dst_dev, size_t n_pixels, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const int px = atmo_target_pixel_bytes(format);
+    if (px == 0) return fail(ctx, ATMO_E_ARG, "atmo_debug_store_target: unknown target format");
+    if (!src_rgba_f32_dev || !dst_dev || n_pixels > ((size_t)1 << 31)) return fail(ctx, ATMO_E_ARG, "atmo_debug_store_target: null pointer or more than 2^31 pixels");
+    if ((reinterpret_cast<uintptr_t>(src_rgba_f32_dev) & 15u) != 0 || (reinterpret_cast<uintptr_t>(dst_dev) & (uintptr_t)(px - 1)) != 0)
+        return fail(ctx, ATMO_E_ARG, "atmo_debug_store_target: src must be 16-byte aligned, dst aligned to the pixel size");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, atmo::launch_store_target(format, composite != 0, src_rgba_f32_dev, dst_dev, n_pixels, (hipStream_t)stream));
+    return ATMO_OK;
 }
 
 int atmo_debug_proxy_launch_rect(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, int *rect_out, int *tiles_out) {

@@ -126,7 +126,10 @@ enum KernelFlags : int { KF_CLOUDS = 1, KF_CLOUD_LIGHT_RM = 2, KF_LIGHT_DIRECT =
                           KF_GEO = 256 /* the block -> tile map is the geometric order's closed form (RenderConsts::geo_rows): a twin of the plain direct-light kernel, so that
                                           the draws that do not use it keep their preamble to the byte (the lookup compiled in cost a still camera 0.6 %) */,
                           KF_PROXY = 512 /* the far-mode BoxMesh draw (atmo_render_proxy, include/atmo_scene.h): shade_pixel first evaluates the proxy fragment test
-                                            (ProxyConsts); its own kernel (atmo_render_proxy_kernel), so the kernels of atmo_render stay what they were */ };
+                                            (ProxyConsts); its own kernel (atmo_render_proxy_kernel), so the kernels of atmo_render stay what they were */,
+                          KF_TARGET = 1024 /* a packed colour target (atmo_render_target, include/atmo_target.h): shade_pixel's stores and its blend go through
+                                              store_target<FMT> on TargetConsts instead of RenderConsts::out; kernels of their own (atmo_render_target_kernel,
+                                              atmo_render_proxy_target_kernel), for the same reason */ };
 
 // The far-mode draw's proxy (planet_atmosphere.gd:300-321: a BoxMesh of edge box_size centred on the node, rasterised with back-face culling, near / far
 // clipping and Godot 4.3's reverse-Z GREATER_OR_EQUAL depth test).  Pixel (nx, ny) of the existing prologue's NDC: its segment from the near plane (z = 1) to
@@ -139,10 +142,28 @@ struct ProxyConsts {
     float half;      // [host] box_size / 2
 };
 
+// A packed colour target (include/atmo_target.h): where and how the kernels of the KF_TARGET family store.  A kernel argument of its own, behind
+// RenderConsts (and ProxyConsts), so that the float kernels' argument layout -- and with it their code -- stays what it was.  RenderConsts::out is not read
+// by these kernels; out_x0 / out_y0 / composite / store_discards mean what they mean to the float kernels.
+enum TargetFormat : int { TF_RGBA32F = 0, TF_RGBA16F = 1, TF_RGBA8_UNORM = 2 };   // == AtmoTargetFormat
+struct TargetConsts {
+    void *pixels;          // the pixel (out_x0, out_y0) maps to
+    int32_t pitch_bytes;   // bytes from one row to the next
+    int32_t format;        // TF_RGBA16F or TF_RGBA8_UNORM (RGBA32F targets are drawn by the float kernels: a pitch in whole pixels is all they need);
+                           // uniform, read only where a pixel is addressed and stored
+};
+
 hipError_t launch_render(int flags, int split, const RenderConsts &rc, hipStream_t stream, int tile_list_blocks = 0);  // > 0: rc.tile_order lists that many tiles of the rect's grid
 // the proxy draws: one lane per ray, row-major grid of the rect in rc; flags = a draw's family without KF_PROXY (proxy_family_supported)
 bool proxy_family_supported(int flags);
 hipError_t launch_render_proxy(int flags, const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream);
+// the packed-target draws: the float draws' launches (grid, tile order, cost feedback, tile lists for the heavy-tile split) with the KF_TARGET kernels.
+// flags without KF_TARGET / KF_PROXY; target_family_supported says which (flags, split) exist.
+bool target_family_supported(int flags, int split);
+hipError_t launch_render_target(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream, int tile_list_blocks = 0);
+hipError_t launch_render_proxy_target(int flags, const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, hipStream_t stream);
+// store_target<format> over n pixels: dst[i] = encode(src[i]), or encode(blend(src[i], decode(dst[i]))) when composite (atmo_debug_store_target)
+hipError_t launch_store_target(int format, int composite, const float *src_rgba, void *dst, size_t n, hipStream_t stream);
 hipError_t launch_bake(const BakeConsts &bc, hipStream_t stream);
 hipError_t launch_tile_order(uint32_t *cost, uint32_t *order, int tiles_x, int tiles_y, int rx, int ry, uint32_t *tmp1, uint32_t *tmp2,
                              uint32_t *scratch, hipStream_t stream, uint32_t *order2 = nullptr, uint32_t *class_totals = nullptr);

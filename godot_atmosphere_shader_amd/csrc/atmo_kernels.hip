@@ -1938,8 +1938,81 @@ __device__ __forceinline__ bool proxy_fragment_passes(const ProxyConsts &pc, con
     return z_hi >= rc.depth[(size_t)py * rc.w + px];
 }
 
+// ---- packed colour targets (include/atmo_target.h; the numerical contract is stated there and restated in numpy by targets.py) ----------------
+// The store and the blend of a render kernel as a function of a compile-time format: encode(src), or decode(dst) -> the float composite's unfused
+// fp32 blend -> encode.  RGBA16F: binary16 round-to-nearest-even with subnormals (v_cvt_pk_f16_f32; NOT the round-toward-zero pack), overflow to
+// infinity; a NaN becomes THE quiet NaN 0x7e00 (the sign and payload of a NaN born in the blend -- inf * 0 -- differ between machines, the stored bits
+// shall not).  RGBA8_UNORM: rint(clamp(x, 0, 1) * 255) ties to even, NaN -> 0 (fmaxf returns its number), bytes R, G, B, A; decoded byte / 255.0f as an
+// IEEE division.  Plain vector stores of 16 / 8 / 4 bytes per lane.
+__device__ __forceinline__ uint32_t half_bits_rne(float x) {
+    const _Float16 h = (_Float16)x;
+    uint16_t b;
+    __builtin_memcpy(&b, &h, 2);
+    return x != x ? 0x7e00u : (uint32_t)b;
+}
+__device__ __forceinline__ float half_bits_to_float(uint32_t b) {
+    const uint16_t u = (uint16_t)b;
+    _Float16 h;
+    __builtin_memcpy(&h, &u, 2);
+    return (float)h;
+}
+__device__ __forceinline__ uint32_t unorm8_rne(float x) {
+#pragma clang fp contract(off)
+    const float c = fminf(fmaxf(x, 0.0f), 1.0f);
+    return (uint32_t)__builtin_rintf(c * 255.0f);
+}
+template <int FMT>
+__device__ __forceinline__ float4 target_decode(const void *p) {
+    if constexpr (FMT == TF_RGBA16F) {
+        const uint2 w = *(const uint2 *)p;
+        return make_float4(half_bits_to_float(w.x & 0xffffu), half_bits_to_float(w.x >> 16), half_bits_to_float(w.y & 0xffffu), half_bits_to_float(w.y >> 16));
+    } else if constexpr (FMT == TF_RGBA8_UNORM) {
+        const uint32_t w = *(const uint32_t *)p;
+        return make_float4(ieee_div((float)(w & 255u), 255.0f), ieee_div((float)((w >> 8) & 255u), 255.0f), ieee_div((float)((w >> 16) & 255u), 255.0f),
+                           ieee_div((float)(w >> 24), 255.0f));
+    } else {
+        return *(const float4 *)p;
+    }
+}
+template <int FMT>
+__device__ __forceinline__ void target_encode(void *p, const float4 &v) {
+    if constexpr (FMT == TF_RGBA16F) {
+        *(uint2 *)p = make_uint2(half_bits_rne(v.x) | (half_bits_rne(v.y) << 16), half_bits_rne(v.z) | (half_bits_rne(v.w) << 16));
+    } else if constexpr (FMT == TF_RGBA8_UNORM) {
+        *(uint32_t *)p = unorm8_rne(v.x) | (unorm8_rne(v.y) << 8) | (unorm8_rne(v.z) << 16) | (unorm8_rne(v.w) << 24);
+    } else {
+        *(float4 *)p = v;
+    }
+}
+template <int FMT>
+__device__ __forceinline__ void store_target(void *p, const float4 &src, const bool composite) {
+    float4 o = src;
+    if (composite) {
+        // the blend of shade_pixel's float epilogue, expression for expression (blend_mix: SRC_ALPHA, ONE_MINUS_SRC_ALPHA; alpha ONE, ONE_MINUS_SRC_ALPHA)
+#pragma clang fp contract(off)
+        const float4 dst = target_decode<FMT>(p);
+        const float ia = 1.0f - src.w;
+        o.x = src.x * src.w + dst.x * ia;
+        o.y = src.y * src.w + dst.y * ia;
+        o.z = src.z * src.w + dst.z * ia;
+        o.w = src.w + dst.w * ia;
+    }
+    target_encode<FMT>(p, o);
+}
+// the format as the uniform run-time field it is in the KF_TARGET kernels: one scalar branch behind the march
+__device__ __forceinline__ void store_target_rt(const int format, void *p, const float4 &src, const bool composite) {
+    if (format == TF_RGBA16F) store_target<TF_RGBA16F>(p, src, composite);
+    else store_target<TF_RGBA8_UNORM>(p, src, composite);
+}
+// a discarded fragment of a plain draw: (0, 0, 0, 0) is all-zero bits in both packed formats
+__device__ __forceinline__ void store_target_zero_rt(const int format, void *p) {
+    if (format == TF_RGBA16F) *(uint2 *)p = make_uint2(0u, 0u);
+    else *(uint32_t *)p = 0u;
+}
+
 template <int FLAGS, int LSTEPS, int SPLIT>
-__device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int tile_x, const int tile_y, const ProxyConsts *pc = nullptr) {
+__device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int tile_x, const int tile_y, const ProxyConsts *pc = nullptr,
+                                            const TargetConsts *tc = nullptr) {
     constexpr bool CLOUDS = (FLAGS & KF_CLOUDS) != 0;
     constexpr bool RM = (FLAGS & KF_CLOUD_LIGHT_RM) != 0;
     constexpr bool DIRECT = (FLAGS & KF_LIGHT_DIRECT) != 0;
@@ -1949,6 +2022,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     constexpr bool ATMO_REF = (FLAGS & KF_ATMO_REF) != 0;
     constexpr bool VIEWPOS = (FLAGS & KF_VIEW_POS) != 0;
     constexpr bool PROXY = (FLAGS & KF_PROXY) != 0;
+    constexpr bool TARGET = (FLAGS & KF_TARGET) != 0;
+    static_assert(!TARGET || (!VIEWPOS && !ATMO_REF && (SPLIT == 1 || (FLAGS & KF_CUBE_LOD) != 0)),
+                  "packed targets: the default forms; two lanes per ray only as the heavy-tile form of the declared-sampler cloud kernels");
     static_assert(!VIEWPOS || (!LITE && !ATMO_REF && SPLIT == 1), "KF_VIEW_POS: the fast v2 march, one lane per ray");
     static_assert(!PROXY || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0), "proxy draws: the default forms, one lane per ray, row-major");
     constexpr bool DIET = !DIRECT && !((FLAGS & KF_CLOUDS) && (FLAGS & KF_CLOUD_LIGHT_RM));
@@ -2003,7 +2079,12 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
             if (!pass) return;
         }
     }
-    float4 *out = rc.out + (size_t)(py - rc.out_y0) * (size_t)rc.out_pitch + (px - rc.out_x0);
+    float4 *out = nullptr;
+    char *tout = nullptr;   // KF_TARGET: the pixel's bytes in the packed target (8 per pixel RGBA16F, 4 RGBA8), rows pitch_bytes apart
+    if constexpr (TARGET)
+        tout = (char *)tc->pixels + (size_t)(py - rc.out_y0) * (size_t)tc->pitch_bytes + ((size_t)(px - rc.out_x0) << (tc->format == TF_RGBA16F ? 3 : 2));
+    else
+        out = rc.out + (size_t)(py - rc.out_y0) * (size_t)rc.out_pitch + (px - rc.out_x0);
 
     // --- sure-miss test in front of the exact prologue (round 3) ----------------------------------------
     // A ray from the view-space origin along v misses the shell iff (c.v)^2 < (|c|^2 - R^2) |v|^2 (that is h < 0 in ray_sphere,
@@ -2024,7 +2105,10 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
         const float cv = rc.center[0] * ax + rc.center[1] * ay + rc.center[2] * az;
         const float vv = ax * ax + ay * ay + az * az;
         if (cv * cv < rc.miss_k * vv) {
-            if (rc.store_discards && half == 0 && !helper) *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (rc.store_discards && half == 0 && !helper) {
+                if constexpr (TARGET) store_target_zero_rt(tc->format, tout);
+                else *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
             return;
         }
     }
@@ -2059,7 +2143,10 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     const float2 rs_atmo = hit_radius<DIET>(sh, rc.atmosphere_radius);
 
     if (rs_atmo.x == rs_atmo.y) {  // discard: nothing reaches the blend stage
-        if (rc.store_discards && half == 0 && !helper) *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (rc.store_discards && half == 0 && !helper) {
+            if constexpr (TARGET) store_target_zero_rt(tc->format, tout);
+            else *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
         return;
     }
     const float t_begin = fmaxf(rs_atmo.x, 0.0f);
@@ -2131,6 +2218,14 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                 }
             }
         }
+    }
+    if constexpr (TARGET) {
+        // the same fp32 ALBEDO / ALPHA, encoded (and blended) per the target's format; not by the second lane of a split ray nor by a helper, as below.
+        // The exchange registers stay reserved across it: the decode / encode arithmetic needs temporaries, and no instruction outside the exchange
+        // blocks may write those registers anywhere in a declared-sampler kernel (tools/check_quad_regs.py)
+        if (!(SPLIT == 2 && half) && !helper) store_target_rt(tc->format, tout, rgba, rc.composite != 0);
+        if constexpr (LOD) quad_regs_keep(qregs);
+        return;
     }
     if constexpr (LOD) quad_regs_keep(qregs);
     if (SPLIT == 2 && half) return;  // lane 0 of the pair holds the ray's result
@@ -2206,7 +2301,7 @@ constexpr bool render_sgpr_cap80(int flags) {
 #define ATMO_TRACE_ENTRY const uint64_t trace_entry = __builtin_amdgcn_s_memrealtime();
 #define ATMO_SHADE_TRACED                                                                                                          \
     const uint64_t trace_t0 = __builtin_amdgcn_s_memrealtime();                                                                    \
-    shade_pixel<FLAGS, LSTEPS, SPLIT>(rc, (int)tile_x, (int)tile_y);                                                               \
+    shade_pixel<FLAGS, LSTEPS, SPLIT>(rc, (int)tile_x, (int)tile_y ATMO_SHADE_EXTRA);                                              \
     if (rc.wave_trace != nullptr && (threadIdx.x & 63) == 0) {                                                                     \
         const uint32_t slot = (blockIdx.y * gridDim.x + blockIdx.x) * (TILE_W * TILE_H / 64) + (threadIdx.x >> 6);                 \
         unsigned long long *w = rc.wave_trace + 4ull * slot;                                                                       \
@@ -2217,8 +2312,9 @@ constexpr bool render_sgpr_cap80(int flags) {
     }
 #else
 #define ATMO_TRACE_ENTRY
-#define ATMO_SHADE_TRACED shade_pixel<FLAGS, LSTEPS, SPLIT>(rc, (int)tile_x, (int)tile_y);
+#define ATMO_SHADE_TRACED shade_pixel<FLAGS, LSTEPS, SPLIT>(rc, (int)tile_x, (int)tile_y ATMO_SHADE_EXTRA);
 #endif
+#define ATMO_SHADE_EXTRA   // further arguments of shade_pixel in the body below: none in the float kernels, the target in atmo_render_target_kernel
 // The geometric tile order (RenderConsts::geo_rows; cloudless kernels): block b shades the b-th tile of "the tiles that can shade, row-major, then the others,
 // row-major".  Uniform: scalar ALU and scalar loads from the kernel-argument segment only (a hint per 256 blocks, then one or two steps of a binary search).
 __device__ __forceinline__ uint32_t geo_tile(const RenderConsts &rc, uint32_t b) {
@@ -2294,6 +2390,39 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
 __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) __attribute__((amdgpu_num_sgpr(ATMO_SGPR_CAP_VALUE))) void atmo_render_kernel_s80(const RenderConsts rc) {
     ATMO_RENDER_KERNEL_BODY
+}
+
+// The packed-target draws (KF_TARGET; atmo_render_target / atmo_render_proxy_target, include/atmo_target.h): the bodies of the two kernels above with the
+// target as a second (third) kernel argument, which shade_pixel's stores and blend go through (store_target).  Kernels of their own names, so that the float
+// kernels keep their code to the byte and tests/test_host_logic.py still finds ONE headline kernel.
+#undef ATMO_SHADE_EXTRA
+#define ATMO_SHADE_EXTRA , nullptr, &tc
+#ifndef ATMO_LOOP_PAD_TARGET       // s_nop at the head of both twins ...
+#define ATMO_LOOP_PAD_TARGET 4
+#endif
+#ifndef ATMO_LOOP_PAD_TARGET_GEO   // ... and more of them in the geometric-order twin, on top of ATMO_LOOP_PAD_GEO
+#define ATMO_LOOP_PAD_TARGET_GEO 5
+#endif
+#define ATMO_TARGET_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_TARGET)
+#define ATMO_TARGET_GEO_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_TARGET_GEO)
+template <int FLAGS, int LSTEPS, int SPLIT = 1>
+__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_target_kernel(const RenderConsts rc, const TargetConsts tc) {
+    static_assert((FLAGS & KF_TARGET) != 0, "target kernels carry KF_TARGET");
+    // the headline kernel's twins <KF_TARGET | KF_LIGHT_DIRECT [| KF_GEO], 8, 1>: their view loop on ITS fast position, 12 bytes into a 32-byte block, as
+    // the float kernels' (march_atmosphere; tools/loop_phase.py reads all four, tests/test_target_host.py holds these two there)
+    if constexpr ((FLAGS & ~KF_GEO) == (KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8 && SPLIT == 1)
+        asm volatile(".rept " ATMO_TARGET_PAD_STR "\n\ts_nop 0\n\t.endr");
+    if constexpr (FLAGS == (KF_TARGET | KF_LIGHT_DIRECT | KF_GEO) && LSTEPS == 8 && SPLIT == 1)
+        asm volatile(".rept " ATMO_TARGET_GEO_PAD_STR "\n\ts_nop 0\n\t.endr");
+    ATMO_RENDER_KERNEL_BODY
+}
+#undef ATMO_SHADE_EXTRA
+#define ATMO_SHADE_EXTRA
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_proxy_target_kernel(const RenderConsts rc, const ProxyConsts pc,
+                                                                                                      const TargetConsts tc) {
+    static_assert((FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0, "proxy target kernels carry KF_PROXY | KF_TARGET");
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, &pc, &tc);
 }
 
 // Stable counting sort of the tiles by the cost a recording draw measured, heaviest class first; clears the costs for
@@ -2951,13 +3080,127 @@ bool proxy_family_supported(int flags) {
     }
 }
 
+// ---- packed-target launchers: the families of the proxy draws (what a default context selects), the geometric-order twin of the direct-light kernel, and
+// the two-lanes-per-ray form of the two declared-sampler cloud kernels that render_impl draws a frame's heavy tiles with
+template <int FLAGS, int LSTEPS, int SPLIT>
+static hipError_t launch_ts(const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream) {
+    int gx, gy;
+    render_grid(rc, SPLIT, &gx, &gy);
+    if (gx != rc.tiles_x) return hipErrorInvalidValue;
+    dim3 grid(gx, gy);
+    if (g_launch_blocks > 0) {
+        if (rc.tile_order == nullptr) return hipErrorInvalidValue;
+        grid = dim3(g_launch_blocks, 1);
+    }
+    hipLaunchKernelGGL((atmo_render_target_kernel<FLAGS | KF_TARGET, LSTEPS, SPLIT>), grid, dim3(TILE_W * TILE_H), 0, stream, rc, tc);
+    return hipGetLastError();
+}
+template <int FLAGS>
+static hipError_t launch_ts_direct(const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream) {   // 8 light steps unrolled, as launch_direct
+    return rc.light_steps == 8 ? launch_ts<FLAGS, 8, 1>(rc, tc, stream) : launch_ts<FLAGS, 0, 1>(rc, tc, stream);
+}
+template <int FLAGS>
+static hipError_t launch_ts_split(const RenderConsts &rc, const TargetConsts &tc, int split, hipStream_t stream) {
+    return split == 2 ? launch_ts<FLAGS, 0, 2>(rc, tc, stream) : launch_ts<FLAGS, 0, 1>(rc, tc, stream);
+}
+static hipError_t launch_render_target_grid(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream) {
+    if (!target_family_supported(flags & ~KF_GEO, split)) return hipErrorInvalidValue;
+    switch (flags) {
+    case 0: return launch_ts<0, 0, 1>(rc, tc, stream);
+    case KF_LIGHT_DIRECT: return launch_ts_direct<KF_LIGHT_DIRECT>(rc, tc, stream);
+    case KF_LIGHT_DIRECT | KF_GEO: return launch_ts_direct<KF_LIGHT_DIRECT | KF_GEO>(rc, tc, stream);
+    case KF_PRECISE | KF_CLOUDS: return launch_ts<KF_PRECISE | KF_CLOUDS, 0, 1>(rc, tc, stream);
+    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_ts<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0, 1>(rc, tc, stream);
+    case KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_ts_direct<KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, tc, stream);
+    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT: return launch_ts_direct<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, tc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: return launch_ts_split<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS>(rc, tc, split, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_ts_split<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM>(rc, tc, split, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_ts_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, tc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
+        return launch_ts_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, tc, stream);
+    case KF_PRECISE | KF_LITE: return launch_ts<KF_PRECISE | KF_LITE, 0, 1>(rc, tc, stream);
+    case KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_ts<KF_PRECISE | KF_LITE | KF_CLOUDS, 0, 1>(rc, tc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_ts<KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS, 0, 1>(rc, tc, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+hipError_t launch_render_target(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream, int tile_list_blocks) {
+    if (tc.format != TF_RGBA16F && tc.format != TF_RGBA8_UNORM) return hipErrorInvalidValue;
+    g_launch_blocks = tile_list_blocks;
+    const hipError_t e = launch_render_target_grid(flags, split, rc, tc, stream);
+    g_launch_blocks = 0;
+    return e;
+}
+bool target_family_supported(int flags, int split) {
+    if (split == 2) return flags == (KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS) || flags == (KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM);
+    return split == 1 && proxy_family_supported(flags);
+}
+template <int FLAGS, int LSTEPS>
+static hipError_t launch_pt(const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, hipStream_t stream) {
+    int gx, gy;
+    render_grid(rc, 1, &gx, &gy);
+    if (gx != rc.tiles_x || gx < 1 || gy < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((atmo_render_proxy_target_kernel<FLAGS | KF_PROXY | KF_TARGET, LSTEPS>), dim3(gx, gy), dim3(TILE_W * TILE_H), 0, stream, rc, pc, tc);
+    return hipGetLastError();
+}
+template <int FLAGS>
+static hipError_t launch_pt_direct(const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, hipStream_t stream) {
+    return rc.light_steps == 8 ? launch_pt<FLAGS, 8>(rc, pc, tc, stream) : launch_pt<FLAGS, 0>(rc, pc, tc, stream);
+}
+hipError_t launch_render_proxy_target(int flags, const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, hipStream_t stream) {
+    if (tc.format != TF_RGBA16F && tc.format != TF_RGBA8_UNORM) return hipErrorInvalidValue;
+    switch (flags) {
+    case 0: return launch_pt<0, 0>(rc, pc, tc, stream);
+    case KF_LIGHT_DIRECT: return launch_pt_direct<KF_LIGHT_DIRECT>(rc, pc, tc, stream);
+    case KF_PRECISE | KF_CLOUDS: return launch_pt<KF_PRECISE | KF_CLOUDS, 0>(rc, pc, tc, stream);
+    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_pt<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, pc, tc, stream);
+    case KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_pt_direct<KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, pc, tc, stream);
+    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT: return launch_pt_direct<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, pc, tc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: return launch_pt<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS, 0>(rc, pc, tc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_pt<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, pc, tc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_pt_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, pc, tc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
+        return launch_pt_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, pc, tc, stream);
+    case KF_PRECISE | KF_LITE: return launch_pt<KF_PRECISE | KF_LITE, 0>(rc, pc, tc, stream);
+    case KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_pt<KF_PRECISE | KF_LITE | KF_CLOUDS, 0>(rc, pc, tc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_pt<KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS, 0>(rc, pc, tc, stream);
+    default: return hipErrorInvalidValue;   // (the host asks proxy_family_supported first)
+    }
+}
+
+// store_target<FMT> on caller-supplied arrays (atmo_debug_store_target): the encode and the blend on chosen values, one pixel per lane
+template <int FMT>
+__global__ __launch_bounds__(256) void atmo_store_target_kernel(const float4 *__restrict__ src, void *dst, size_t n, int composite) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr size_t BYTES = FMT == TF_RGBA16F ? 8 : (FMT == TF_RGBA8_UNORM ? 4 : 16);
+    store_target<FMT>((char *)dst + i * BYTES, src[i], composite != 0);
+}
+hipError_t launch_store_target(int format, int composite, const float *src_rgba, void *dst, size_t n, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (n > ((size_t)1 << 31)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    const float4 *src = (const float4 *)src_rgba;
+    switch (format) {
+    case TF_RGBA32F: hipLaunchKernelGGL(atmo_store_target_kernel<TF_RGBA32F>, grid, block, 0, stream, src, dst, n, composite); break;
+    case TF_RGBA16F: hipLaunchKernelGGL(atmo_store_target_kernel<TF_RGBA16F>, grid, block, 0, stream, src, dst, n, composite); break;
+    case TF_RGBA8_UNORM: hipLaunchKernelGGL(atmo_store_target_kernel<TF_RGBA8_UNORM>, grid, block, 0, stream, src, dst, n, composite); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 const char *render_kernel_name(int flags, int light_steps, int split) {
     // demangled template name as rocprofv3 prints it: atmo_render_kernel<FLAGS, LSTEPS, SPLIT>; atmo_render_proxy_kernel<FLAGS, LSTEPS> for KF_PROXY
     static thread_local char name[64];
     const bool v2_precise = (flags & KF_ATMO_REF) != 0;  // its light march is a run-time loop
     const int lsteps = ((flags & KF_LIGHT_DIRECT) && light_steps == 8 && !v2_precise && !(flags & KF_VIEW_POS)) ? 8 : 0;
     if (flags & KF_PROXY) {
-        snprintf(name, sizeof(name), "atmo_render_proxy_kernel<%d, %d>", flags, lsteps);
+        snprintf(name, sizeof(name), "atmo_render_proxy%s_kernel<%d, %d>", (flags & KF_TARGET) ? "_target" : "", flags, lsteps);
+        return name;
+    }
+    if (flags & KF_TARGET) {
+        snprintf(name, sizeof(name), "atmo_render_target_kernel<%d, %d, %d>", flags, lsteps, split == 2 ? 2 : 1);
         return name;
     }
     snprintf(name, sizeof(name), "atmo_render_kernel%s<%d, %d, %d>", render_sgpr_cap80(flags) ? "_s80" : "", flags, lsteps, split == 2 ? 2 : 1);

@@ -543,12 +543,14 @@ class PlanetAtmosphere:
             sun = (0.0, 0.0, 0.0)
         return make_frame(camera, self.global_transform, sun, time, rect)
 
-    def render(self, camera, depth, out=None, rect=None, stream=None, time: float = 0.0):
+    def render(self, camera, depth, out=None, rect=None, stream=None, time: float = 0.0, target=None):
         """One draw: shades `rect` (default: whole viewport) of the camera's viewport.
 
         depth: CUDA float32 tensor (H, W), Godot reversed-Z depth.  out: CUDA float32 tensor
         (rect_h, rect_w, 4), allocated when None.  Work is enqueued on `stream` (a torch stream, a raw
-        hipStream_t int, or None for torch's current stream).  Returns `out`."""
+        hipStream_t int, or None for torch's current stream).  Returns `out`.
+        `out` may also be a float16 (RGBA16F) or uint8 (RGBA8_UNORM) tensor, and its rows may be further apart than a row (a row pitch): the draw then
+        stores in that format (atmo_render_target; godot_atmosphere_shader_amd.targets states the encoding).  target="rgba16f" | "rgba8" allocates one."""
         import torch
 
         frame = self.make_frame(camera, time, rect)
@@ -558,15 +560,22 @@ class PlanetAtmosphere:
         if tuple(depth.shape) != (camera.height, camera.width):
             raise ValueError("depth must have shape (viewport_h, viewport_w)")
         if out is None:
-            out = torch.empty((y1 - y0, x1 - x0, 4), dtype=torch.float32, device=depth.device)
-        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (y1 - y0, x1 - x0, 4)):
-            raise ValueError("out must be a contiguous CUDA float32 tensor of shape (rect_h, rect_w, 4)")
+            out = _new_target(y1 - y0, x1 - x0, target, depth.device, zero=False)
+        tgt = _colour_target(out, y1 - y0, x1 - x0, "out")
         if stream is None:
             stream = torch.cuda.current_stream(depth.device).cuda_stream
         elif hasattr(stream, "cuda_stream"):
             stream = stream.cuda_stream
-        self.render_raw(frame, depth.data_ptr(), out.data_ptr(), stream)
+        if tgt is not None:
+            self._target_call(_to_native_frame(frame), depth, tgt, 0, stream)
+        else:
+            self.render_raw(frame, depth.data_ptr(), out.data_ptr(), stream)
         return out
+
+    def _target_call(self, native_frame, depth, tgt, composite: int, stream):
+        self._bake_if_needed(stream)
+        rc = self._lib.atmo_render_target(self._ctx, C.byref(native_frame), C.c_void_p(depth.data_ptr()), C.byref(tgt), int(composite), C.c_void_p(stream or 0))
+        N.check(self._ctx, rc)
 
     def prepare_frame(self, camera, time: float = 0.0, rect=None) -> N.AtmoFrame:
         """The native per-frame argument block for `render_prepared` (build once per camera pose)."""
@@ -583,13 +592,13 @@ class PlanetAtmosphere:
     def render_composite(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0):
         """The draw including the renderer's blend stage: shades `rect` and alpha-blends the result over
         `scene_rgba` (CUDA float32 (H, W, 4), the scene colour buffer) in place, as Godot's blend_mix does with
-        ALBEDO/ALPHA; discarded fragments leave the scene untouched.  Returns `scene_rgba`."""
+        ALBEDO/ALPHA; discarded fragments leave the scene untouched.  Returns `scene_rgba`.
+        A float16 / uint8 `scene_rgba` (RGBA16F / RGBA8_UNORM, optionally with a row pitch) is blended in its own format: decoded, blended in fp32,
+        encoded once (atmo_render_target)."""
         import torch
 
         frame = self.make_frame(camera, time, rect)
-        if not (isinstance(scene_rgba, torch.Tensor) and scene_rgba.is_cuda and scene_rgba.dtype == torch.float32
-                and scene_rgba.is_contiguous() and tuple(scene_rgba.shape) == (camera.height, camera.width, 4)):
-            raise ValueError("scene_rgba must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w, 4)")
+        tgt = _colour_target(scene_rgba, camera.height, camera.width, "scene_rgba")
         if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
                 and tuple(depth.shape) == (camera.height, camera.width)):
             raise TypeError("depth must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w)")
@@ -599,6 +608,9 @@ class PlanetAtmosphere:
             stream = stream.cuda_stream
         self._bake_if_needed(stream)
         nf = _to_native_frame(frame)
+        if tgt is not None:
+            self._target_call(nf, depth, tgt, 1, stream)
+            return scene_rgba
         rc = self._lib.atmo_render_composite(self._ctx, C.byref(nf), C.c_void_p(depth.data_ptr()),
                                              C.c_void_p(scene_rgba.data_ptr()), C.c_void_p(stream or 0))
         N.check(self._ctx, rc)
@@ -610,7 +622,7 @@ class PlanetAtmosphere:
         cam_near = 0.1 if camera is None else camera.near
         return 1.75 * (self._planet_radius + self._atmosphere_height + cam_near) * SWITCH_MARGIN_RATIO
 
-    def _proxy_call(self, fn, camera, depth, target, rect, stream, time, box_size):
+    def _proxy_call(self, fn, camera, depth, target, rect, stream, time, box_size, tgt=None, composite=0):
         frame = self.make_frame(camera, time, rect)
         if stream is None:
             stream = _torch_stream(depth)
@@ -620,12 +632,17 @@ class PlanetAtmosphere:
         nf = _to_native_frame(frame)
         model = (C.c_float * 16)(*[float(x) for x in col_major(self.global_transform)])
         size = self.proxy_box_size(camera) if box_size is None else float(box_size)
-        rc = fn(self._ctx, C.byref(nf), model, C.c_float(size), C.c_void_p(depth.data_ptr()), C.c_void_p(target.data_ptr()), C.c_void_p(stream or 0))
+        if tgt is not None:   # a packed or pitched colour tensor (_colour_target): atmo_render_proxy_target
+            rc = self._lib.atmo_render_proxy_target(self._ctx, C.byref(nf), model, C.c_float(size), C.c_void_p(depth.data_ptr()), C.byref(tgt), int(composite),
+                                                    C.c_void_p(stream or 0))
+        else:
+            rc = fn(self._ctx, C.byref(nf), model, C.c_float(size), C.c_void_p(depth.data_ptr()), C.c_void_p(target.data_ptr()), C.c_void_p(stream or 0))
         N.check(self._ctx, rc)
 
-    def render_proxy(self, camera, depth, out=None, rect=None, stream=None, time: float = 0.0, box_size: float | None = None):
+    def render_proxy(self, camera, depth, out=None, rect=None, stream=None, time: float = 0.0, box_size: float | None = None, target=None):
         """`render` through the far mode's BoxMesh (default edge: proxy_box_size(camera)) centred on global_transform: only the box's front-face
-        fragments that pass the depth test are shaded and written (atmo_render_proxy); every other pixel of `out` is left as it was."""
+        fragments that pass the depth test are shaded and written (atmo_render_proxy); every other pixel of `out` is left as it was.
+        `out` / `target`: as `render` (float16 / uint8 tensors, a row pitch: atmo_render_proxy_target)."""
         import torch
 
         x0, y0, x1, y1 = rect if rect is not None else (0, 0, camera.width, camera.height)
@@ -633,28 +650,26 @@ class PlanetAtmosphere:
                 and tuple(depth.shape) == (camera.height, camera.width)):
             raise TypeError("depth must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w)")
         if out is None:
-            out = torch.zeros((y1 - y0, x1 - x0, 4), dtype=torch.float32, device=depth.device)
-        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (y1 - y0, x1 - x0, 4)):
-            raise ValueError("out must be a contiguous CUDA float32 tensor of shape (rect_h, rect_w, 4)")
-        self._proxy_call(self._lib.atmo_render_proxy, camera, depth, out, rect, stream, time, box_size)
+            out = _new_target(y1 - y0, x1 - x0, target, depth.device, zero=True)
+        tgt = _colour_target(out, y1 - y0, x1 - x0, "out")
+        self._proxy_call(self._lib.atmo_render_proxy, camera, depth, out, rect, stream, time, box_size, tgt, 0)
         return out
 
     def render_proxy_composite(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0, box_size: float | None = None):
-        """`render_composite` through the far mode's BoxMesh (atmo_render_proxy_composite).  Returns `scene_rgba`."""
+        """`render_composite` through the far mode's BoxMesh (atmo_render_proxy_composite; a float16 / uint8 / pitched `scene_rgba`:
+        atmo_render_proxy_target).  Returns `scene_rgba`."""
         import torch
 
-        if not (isinstance(scene_rgba, torch.Tensor) and scene_rgba.is_cuda and scene_rgba.dtype == torch.float32
-                and scene_rgba.is_contiguous() and tuple(scene_rgba.shape) == (camera.height, camera.width, 4)):
-            raise ValueError("scene_rgba must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w, 4)")
+        tgt = _colour_target(scene_rgba, camera.height, camera.width, "scene_rgba")
         if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
                 and tuple(depth.shape) == (camera.height, camera.width)):
             raise TypeError("depth must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w)")
-        self._proxy_call(self._lib.atmo_render_proxy_composite, camera, depth, scene_rgba, rect, stream, time, box_size)
+        self._proxy_call(self._lib.atmo_render_proxy_composite, camera, depth, scene_rgba, rect, stream, time, box_size, tgt, 1)
         return scene_rgba
 
     def draw(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0):
         """The draw Godot makes for this node in its current mode (set by `_process`): near mode the fullscreen quad (`render_composite`), far mode
-        the BoxMesh of the reference's size (`render_proxy_composite`).  Returns `scene_rgba`."""
+        the BoxMesh of the reference's size (`render_proxy_composite`).  Returns `scene_rgba` (float32, float16 or uint8; a row pitch is taken from its row stride)."""
         if self._mode == MODE_NEAR:
             return self.render_composite(camera, depth, scene_rgba, rect=rect, stream=stream, time=time)
         return self.render_proxy_composite(camera, depth, scene_rgba, rect=rect, stream=stream, time=time)
@@ -738,6 +753,34 @@ class PlanetAtmosphere:
         return n.value, ms.value
 
 
+def _colour_target(t, rows: int, cols: int, what: str):
+    """How a colour tensor is drawn into: None for a contiguous float32 (rows, cols, 4) tensor -- the float entry points --, else the N.AtmoTarget
+    of a float16 (RGBA16F), uint8 (RGBA8_UNORM) or float32 tensor whose pixels are contiguous and whose rows may be further apart (the row pitch
+    is the tensor's row stride): include/atmo_target.h."""
+    import torch
+
+    from . import targets as T
+
+    fmts = {torch.float32: T.RGBA32F, torch.float16: T.RGBA16F, torch.uint8: T.RGBA8}
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in fmts and tuple(t.shape) == (rows, cols, 4)):
+        raise ValueError(f"{what} must be a CUDA float32, float16 or uint8 tensor of shape ({rows}, {cols}, 4)")
+    if t.dtype == torch.float32 and t.is_contiguous():
+        return None
+    if not (t.stride(2) == 1 and t.stride(1) == 4 and (rows == 1 or t.stride(0) >= 4 * cols)):
+        raise ValueError(f"{what}: the pixels of a row must be contiguous and the row stride at least a row (a row pitch is the only stride supported)")
+    return N.AtmoTarget(t.data_ptr(), fmts[t.dtype], (t.stride(0) if rows > 1 else 4 * cols) * t.element_size())
+
+
+def _new_target(rows: int, cols: int, target, device, zero: bool):
+    """The tensor a draw allocates: float32, or the packed format named by target="rgba16f" | "rgba8"."""
+    import torch
+
+    from . import targets as T
+
+    dtype = {T.RGBA32F: torch.float32, T.RGBA16F: torch.float16, T.RGBA8: torch.uint8}[T.format_id(target) if target is not None else T.RGBA32F]
+    return (torch.zeros if zero else torch.empty)((rows, cols, 4), dtype=dtype, device=device)
+
+
 def _torch_stream(tensor) -> int:
     import torch
 
@@ -755,7 +798,8 @@ def draw_order(nodes, camera) -> list:
 
 def draw_atmospheres(nodes, camera, depth, scene_rgba, stream=None, time: float = 0.0):
     """Draws several PlanetAtmosphere nodes into one frame as Godot does: each node's draw for its current mode (`PlanetAtmosphere.draw`: the
-    fullscreen quad near, the BoxMesh far), composited over `scene_rgba` in place, back to front (`draw_order`).  Returns `scene_rgba`."""
+    fullscreen quad near, the BoxMesh far), composited over `scene_rgba` in place, back to front (`draw_order`).  Returns `scene_rgba`, which may be the renderer's own RGBA16F / RGBA8_UNORM buffer
+    (a float16 / uint8 tensor, optionally with a row pitch): every node then blends in that format."""
     for node in draw_order(list(nodes), camera):
         node.draw(camera, depth, scene_rgba, stream=stream, time=time)
     return scene_rgba

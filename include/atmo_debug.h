@@ -111,6 +111,12 @@ int atmo_debug_frame_constants(AtmoContext *ctx, const AtmoFrame *frame, int cub
  * rect; x0 == x1 when nothing is left), *tiles_out = the workgroup tiles of its grid (0: no launch). */
 int atmo_debug_proxy_launch_rect(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, int *rect_out, int *tiles_out);
 
+/* Diagnostics (no reference counterpart): the render kernels' store_target<format> (include/atmo_target.h: the encode, and the composite's decode / blend /
+ * encode) on caller-supplied DEVICE arrays, so that the contract can be tested on chosen values rather than on what a scene happens to produce:
+ * dst[i] = encode(src[i]) for composite == 0, encode(blend(src[i], decode(dst[i]))) otherwise; src = n_pixels x 4 floats (16-byte aligned), dst = n_pixels
+ * pixels of `format` (AtmoTargetFormat; RGBA32F included).  Enqueues one kernel on `stream`. */
+int atmo_debug_store_target(AtmoContext *ctx, int format, int composite, const float *src_rgba_f32_dev, void *dst_dev, size_t n_pixels, void *stream);
+
 #ifdef ATMO_WAVE_TRACE
 /* Diagnostic builds only (-DATMO_WAVE_TRACE: tools/wave_timeline.py, tools/rmq_stats.py; the shipped library does not export it): copies the wave
  * trace of the last draw -- 4 x uint64 per wave: start, end (s_memrealtime, 100 MHz), HW_ID, XCC_ID | preamble ticks << 8 -- to the host and

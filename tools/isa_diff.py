@@ -1,0 +1,47 @@
+#!/usr/bin/env python3
+"""Per-symbol diff of the render kernels of two builds of libatmo_hip.so (no GPU needed): every kernel whose name matches the pattern is disassembled from
+both libraries with llvm-objdump, branch targets and addresses stripped to offsets from the kernel's own start, and compared instruction for instruction.
+
+    python tools/isa_diff.py OLD.so NEW.so [symbol regex, default "atmo_render_kernel|atmo_render_proxy_kernel"]
+
+Prints one line per symbol that differs or exists in one build only, and a summary; exit status 1 when an OLD symbol is missing from or differs in NEW."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from loop_phase import LLVM, device_code_object
+
+
+def kernels(lib, pattern, tmp, tag):
+    co = device_code_object(lib, os.path.join(tmp, tag + ".co"))
+    syms = subprocess.run([f"{LLVM}/llvm-readelf", "-sW", co], check=True, capture_output=True, text=True).stdout
+    names = sorted({l.split()[-1] for l in syms.splitlines() if " FUNC " in l and re.search(pattern, l.split()[-1])})
+    out = {}
+    for name in names:
+        dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", f"--disassemble-symbols={name}", co], check=True, capture_output=True, text=True).stdout
+        # "  <instruction>   // <address>: <raw words>": keep the text and the raw encoding (relative branches encode offsets, so they compare as they are)
+        out[name] = [(m.group(1).strip(), m.group(3).strip()) for m in re.finditer(r"^\s+(\S[^\n]*?)\s+// ([0-9A-F]{12}):([^\n]*)", dis, re.M)]
+    return out
+
+
+if __name__ == "__main__":
+    old_lib, new_lib = sys.argv[1], sys.argv[2]
+    pattern = sys.argv[3] if len(sys.argv) > 3 else r"atmo_render_kernel|atmo_render_proxy_kernel"
+    with tempfile.TemporaryDirectory(prefix="isadiff_") as tmp:
+        old, new = kernels(old_lib, pattern, tmp, "old"), kernels(new_lib, pattern, tmp, "new")
+    bad = 0
+    for name in sorted(old):
+        if name not in new:
+            print(f"MISSING in new: {name}")
+            bad += 1
+        elif old[name] != new[name]:
+            first = next((i for i, (a, b) in enumerate(zip(old[name], new[name])) if a != b), min(len(old[name]), len(new[name])))
+            print(f"DIFFERS: {name}: {len(old[name])} -> {len(new[name])} instructions, first difference at instruction {first}")
+            bad += 1
+    added = sorted(set(new) - set(old))
+    print(f"{len(old)} kernels in the old build, {len(old) - bad} identical in the new one (text and encoding), {bad} differ or are missing; "
+          f"{len(added)} matching kernels only in the new build")
+    sys.exit(1 if bad else 0)
