@@ -29,14 +29,18 @@ DEBUG_SYMBOLS = (
     "atmo_set_lane_split", "atmo_debug_motion_px", "atmo_get_feedback_stats", "atmo_set_timing", "atmo_get_timing", "atmo_host_layout_cubemap", "atmo_host_layout_shape",
     "atmo_host_layout_lut", "atmo_host_cubemap_mip", "atmo_read_texture_layout", "atmo_selftest_exact_math", "atmo_debug_marched_optical_depth", "atmo_debug_log2_cr", "atmo_kernel_name", "atmo_build_id",
     "atmo_get_host_wait_stats", "atmo_get_split_stats", "atmo_debug_create_host_only", "atmo_debug_frame_constants", "atmo_debug_proxy_launch_rect",
-    "atmo_debug_store_target",
+    "atmo_debug_store_target", "atmo_debug_views_layout",
 )
 # every symbol include/atmo_scene.h declares: drawing several atmospheres into one frame (the far-mode BoxMesh draw)
 SCENE_SYMBOLS = ("atmo_render_proxy", "atmo_render_proxy_composite")
 # every symbol include/atmo_target.h declares: the same draws into a renderer's colour buffer (RGBA16F / RGBA8_UNORM / RGBA32F, with a row pitch).
 # The ABI version stays 5: a host detects the feature by these symbols and atmo_target_pixel_bytes(format) != 0.
 TARGET_SYMBOLS = ("atmo_target_pixel_bytes", "atmo_render_target", "atmo_render_proxy_target")
-EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS
+# every symbol include/atmo_views.h declares: several views of one planet in one launch (stereo eyes, split screen, probe faces).  The ABI version stays 5:
+# a host detects the feature by the symbol.
+VIEWS_SYMBOLS = ("atmo_render_views",)
+MAX_VIEWS = 8
+EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 
 
@@ -61,6 +65,14 @@ class AtmoTarget(C.Structure):
         ("pixels", C.c_void_p),
         ("format", C.c_int32),
         ("row_pitch_bytes", C.c_int32),
+    ]
+
+
+class AtmoView(C.Structure):
+    _fields_ = [
+        ("frame", AtmoFrame),
+        ("depth_dev", C.c_void_p),
+        ("rgba_dev", C.c_void_p),
     ]
 
 
@@ -140,6 +152,8 @@ def load() -> C.CDLL:
         "atmo_render_target": (ip, [vp, C.POINTER(AtmoFrame), vp, C.POINTER(AtmoTarget), ip, vp]),
         "atmo_render_proxy_target": (ip, [vp, C.POINTER(AtmoFrame), fp, C.c_float, vp, C.POINTER(AtmoTarget), ip, vp]),
         "atmo_debug_store_target": (ip, [vp, ip, ip, vp, vp, C.c_size_t, vp]),
+        "atmo_render_views": (ip, [vp, C.POINTER(AtmoView), ip, ip, vp]),
+        "atmo_debug_views_layout": (ip, [vp, C.POINTER(AtmoView), ip, C.POINTER(ip), C.POINTER(ip)]),
     }
     # ATMO_HIP_LIB names an A/B build (tools/ab_build_commit.sh: possibly an OLDER commit's library): entry points it lacks are skipped
     # (callers of those guard with hasattr) and its ABI version is not held against it.  The in-tree library must match exactly.

@@ -9,6 +9,7 @@
 #include "../../include/atmo_debug.h"
 #include "../../include/atmo_scene.h"
 #include "../../include/atmo_target.h"
+#include "../../include/atmo_views.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 
@@ -220,6 +221,28 @@ struct AtmoContext {
     DeviceBuffer wave_trace;                           // diagnostic build only
     size_t wave_trace_waves = 0;
 #endif
+    // atmo_render_views (include/atmo_views.h): the per-view RenderConsts of a batch travel host -> device through a ring of slots -- pinned host memory
+    // the stream-ordered copy reads, the device table the kernel reads, an event behind the launch.  A slot is reused only once its event has happened, so
+    // a host may run VIEWS_RING batches ahead (on any streams) before a call waits.
+    static constexpr int VIEWS_RING = 16;
+    struct ViewsSlot {
+        atmo::RenderConsts *host = nullptr;   // pinned: ATMO_MAX_VIEWS entries (a part of views_host)
+        atmo::RenderConsts *dev = nullptr;    // the same on the device (a part of views_dev)
+        hipEvent_t done = nullptr;            // recorded behind the launch that reads `dev`
+        bool in_flight = false;
+    } views_ring[VIEWS_RING];
+    atmo::RenderConsts *views_host = nullptr; // one pinned allocation and one device allocation for the whole ring, made by the first batch
+    DeviceBuffer views_dev;
+    unsigned views_next = 0;
+    unsigned views_ring_waits = 0;            // how often a call had to wait for a slot (all VIEWS_RING batches before it still in flight)
+    // ... and their ONE feedback state, separate from fb[] (it never recycles those), keyed by the batch's signature: stream (views_fb.draw_stream),
+    // kernel family, n_views and each view's grid.  Of FeedbackState it uses the cost buffer, the two orders, the events and the counters.
+    FeedbackState views_fb;
+    int views_key_flags = -1, views_key_n = 0, views_key_grid[8][2] = {{0}};
+    AtmoFrame views_prev[8];                  // each view's previous frame: its screen-space motion (feedback_motion_px)
+    float views_motion_px[8] = {0};
+    bool views_have_prev = false;
+    bool views_drop_pending = false;          // the sort in flight was recorded before a camera move: not to be used
     int timing = 0;          // 0 off; k >= 1: bracket every k-th launch with HIP events
     int launch_counter = 0;
     int timed_launches = 0;
@@ -527,6 +550,68 @@ void launch_shape(const AtmoContext *ctx, const AtmoFrame *frame, int *flags_out
     *split_out = split;
     if (lod_out) *lod_out = lod;
 }
+
+// ---- what every draw entry point does before it launches (render_impl, atmo_render_views) ------------------------------------------------
+// The frame's own checks: viewport size and rect.  *empty: the rect holds no pixel (the caller returns ATMO_OK without looking at the pointers).
+int check_frame(AtmoContext *ctx, const std::string &who, const AtmoFrame *frame, bool *empty) {
+    if (!frame) return fail(ctx, ATMO_E_ARG, who + ": null frame");
+    if (frame->viewport_w < 1 || frame->viewport_h < 1 || frame->viewport_w > 65536 || frame->viewport_h > 65536)
+        return fail(ctx, ATMO_E_ARG, who + ": bad viewport size");
+    if (frame->x0 < 0 || frame->y0 < 0 || frame->x1 > frame->viewport_w || frame->y1 > frame->viewport_h ||
+        frame->x0 > frame->x1 || frame->y0 > frame->y1)
+        return fail(ctx, ATMO_E_ARG, who + ": rect outside the viewport");
+    *empty = frame->x0 == frame->x1 || frame->y0 == frame->y1;
+    return ATMO_OK;
+}
+int check_draw_pointers(AtmoContext *ctx, const std::string &who, const float *depth_dev, const float *rgba_dev, bool float4_target) {
+    if (!depth_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": null device pointer");
+    if (float4_target && (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, who + ": rgba_dev must be 16-byte aligned");
+    return ATMO_OK;
+}
+int check_draw_textures(AtmoContext *ctx, const std::string &who) {
+    if (!(ctx->flags & (atmo::KF_LIGHT_DIRECT | atmo::KF_LITE)) && !(ctx->lut.ptr && ctx->lut4.ptr))
+        return fail(ctx, ATMO_E_STATE, who + ": u_optical_depth_texture not set (call atmo_bake_optical_depth or atmo_set_texture)");
+    if ((ctx->flags & atmo::KF_CLOUDS) && !ctx->shape.ptr)
+        return fail(ctx, ATMO_E_STATE, who + ": u_cloud_shape_texture not set");
+    return ATMO_OK;
+}
+// The frame a draw evaluates: the caller's, or `fixed` = the caller's with the engine's negated INV_VIEW_MATRIX origin undone (main:118-125)
+const AtmoFrame *draw_frame(const AtmoContext *ctx, const AtmoFrame *frame, AtmoFrame &fixed) {
+    if (!ctx->host_double_precision) return frame;
+    fixed = *frame;
+    fixed.inv_view_matrix[12] *= -1.0f;
+    fixed.inv_view_matrix[13] *= -1.0f;
+    fixed.inv_view_matrix[14] *= -1.0f;
+    return &fixed;
+}
+// The launch constants of a draw of `frame` (as draw_frame returns it): fill_consts, and the composite's addressing
+void draw_consts(const AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, bool composite, atmo::RenderConsts &rc) {
+    fill_consts(ctx, frame, depth_dev, rgba_dev, rc);
+    if (composite) {  // the target is the whole scene colour buffer, addressed by absolute pixel
+        rc.out_pitch = frame->viewport_w;
+        rc.out_x0 = 0;
+        rc.out_y0 = 0;
+        rc.composite = 1;
+        rc.store_discards = 0;
+    }
+}
+// The kernel family and launch shape of a draw (launch_shape), refused where the context demands a sampler it cannot have; under the declared sampler
+// (*lod) the launch grid starts on an even pixel: draw_grid_origin
+int draw_family(AtmoContext *ctx, const AtmoFrame *frame, int *flags, int *split, bool *lod) {
+    const char *why_not = nullptr;
+    (void)resolve_sampler_lod(ctx, &why_not);
+    if (ctx->sampler_lod == 1 && why_not) return fail(ctx, ATMO_E_STATE, why_not);
+    launch_shape(ctx, frame, flags, split, lod);
+    return ATMO_OK;
+}
+void draw_grid_origin(const AtmoFrame *frame, bool lod, atmo::RenderConsts &rc) {
+    if (lod) {
+        // the 2 x 2 quads are the viewport's: the grid starts on an even pixel, pixels in front of the rect are helper lanes
+        rc.gx0 = frame->x0 & ~1;
+        rc.gy0 = frame->y0 & ~1;
+    }
+}
+constexpr float FB_STILL_PX = 0.5f;   // pixels per frame below which a camera counts as still (tile feedback)
 
 // Reads back finished timing pairs.  only_completed: keep the pairs whose second event has not happened yet
 // (used to bound `pending` without blocking); otherwise wait for every pair.
@@ -908,6 +993,20 @@ int atmo_destroy(AtmoContext *ctx) {
         if (f.class_totals) (void)hipHostFree(f.class_totals);
         dev_free(f.cost);
     }
+    {
+        AtmoContext::FeedbackState &f = ctx->views_fb;
+        if (f.ev_draw) (void)hipEventDestroy(f.ev_draw);
+        for (int k = 0; k < 2; ++k) {
+            if (f.ev_order[k]) (void)hipEventDestroy(f.ev_order[k]);
+            dev_free(f.order[k]);
+        }
+        dev_free(f.cost);
+    }
+    for (AtmoContext::ViewsSlot &v : ctx->views_ring) {
+        if (v.done) { (void)hipEventSynchronize(v.done); (void)hipEventDestroy(v.done); }
+    }
+    if (ctx->views_host) (void)hipHostFree(ctx->views_host);
+    dev_free(ctx->views_dev);
     dev_free(ctx->fb_scratch);
     delete ctx;
     return ATMO_OK;
@@ -1486,38 +1585,20 @@ static int note_draw_stream(AtmoContext *ctx, hipStream_t s, hipEvent_t *marker)
 static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream, bool composite,
                        const uint32_t *tiles_dev, int n_tiles, int n_heavy, const atmo::TargetConsts *tc, int pitch_px) {
     if (!ctx) return ATMO_E_ARG;
-    if (!frame) return fail(ctx, ATMO_E_ARG, "atmo_render: null frame");
-    if (frame->viewport_w < 1 || frame->viewport_h < 1 || frame->viewport_w > 65536 || frame->viewport_h > 65536)
-        return fail(ctx, ATMO_E_ARG, "atmo_render: bad viewport size");
-    if (frame->x0 < 0 || frame->y0 < 0 || frame->x1 > frame->viewport_w || frame->y1 > frame->viewport_h ||
-        frame->x0 > frame->x1 || frame->y0 > frame->y1)
-        return fail(ctx, ATMO_E_ARG, "atmo_render: rect outside the viewport");
-    if (frame->x0 == frame->x1 || frame->y0 == frame->y1) return ATMO_OK;  // empty rect: nothing to shade
-    if (!depth_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, "atmo_render: null device pointer");
-    if (!tc && (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, "atmo_render: rgba_dev must be 16-byte aligned");
-    if (!(ctx->flags & (atmo::KF_LIGHT_DIRECT | atmo::KF_LITE)) && !(ctx->lut.ptr && ctx->lut4.ptr))
-        return fail(ctx, ATMO_E_STATE, "atmo_render: u_optical_depth_texture not set (call atmo_bake_optical_depth or atmo_set_texture)");
-    if ((ctx->flags & atmo::KF_CLOUDS) && !ctx->shape.ptr)
-        return fail(ctx, ATMO_E_STATE, "atmo_render: u_cloud_shape_texture not set");
+    {
+        bool empty = false;
+        const int rc0 = check_frame(ctx, "atmo_render", frame, &empty);
+        if (rc0 != ATMO_OK) return rc0;
+        if (empty) return ATMO_OK;  // empty rect: nothing to shade
+    }
+    { const int rc0 = check_draw_pointers(ctx, "atmo_render", depth_dev, rgba_dev, !tc); if (rc0 != ATMO_OK) return rc0; }
+    { const int rc0 = check_draw_textures(ctx, "atmo_render"); if (rc0 != ATMO_OK) return rc0; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
     atmo::RenderConsts rc;
     AtmoFrame fixed;
-    if (ctx->host_double_precision) {  // main:118-125: undo the engine's negated INV_VIEW_MATRIX origin
-        fixed = *frame;
-        fixed.inv_view_matrix[12] *= -1.0f;
-        fixed.inv_view_matrix[13] *= -1.0f;
-        fixed.inv_view_matrix[14] *= -1.0f;
-        frame = &fixed;
-    }
-    fill_consts(ctx, frame, depth_dev, rgba_dev, rc);
-    if (composite) {  // the target is the whole scene colour buffer, addressed by absolute pixel
-        rc.out_pitch = frame->viewport_w;
-        rc.out_x0 = 0;
-        rc.out_y0 = 0;
-        rc.composite = 1;
-        rc.store_discards = 0;
-    }
+    frame = draw_frame(ctx, frame, fixed);
+    draw_consts(ctx, frame, depth_dev, rgba_dev, composite, rc);
     if (pitch_px > 0) rc.out_pitch = pitch_px;
     if (tc) rc.out = nullptr;   // the KF_TARGET kernels address tc->pixels, rows tc->pitch_bytes apart
     // the launches of this draw: the float kernels, or their packed-target twins
@@ -1528,16 +1609,10 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
     { const int rc0 = tex_order(ctx, s); if (rc0 != ATMO_OK) return rc0; }  // texture updated on another stream
     int split = 1, flags = 0;
     {   // the coverage cubemap's sampler: as declared (implicit LOD) when a mip chain is bound
-        const char *why_not = nullptr;
-        (void)resolve_sampler_lod(ctx, &why_not);
-        if (ctx->sampler_lod == 1 && why_not) return fail(ctx, ATMO_E_STATE, why_not);
         bool lod = false;
-        launch_shape(ctx, frame, &flags, &split, &lod);
-        if (lod) {
-            // the 2 x 2 quads are the viewport's: the grid starts on an even pixel, pixels in front of the rect are helper lanes
-            rc.gx0 = frame->x0 & ~1;
-            rc.gy0 = frame->y0 & ~1;
-        }
+        const int rc0 = draw_family(ctx, frame, &flags, &split, &lod);
+        if (rc0 != ATMO_OK) return rc0;
+        draw_grid_origin(frame, lod, rc);
     }
     int gx = 0, gy = 0;
     atmo::render_grid(rc, split, &gx, &gy);
@@ -1568,7 +1643,7 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
     // the camera moves; and an order whose reach the motion has outrun is not used (row-major instead).
     // reach beyond which an order says nothing about the frame it would be used on: 160 px for the in-stream sort (a frame of lag),
     // 48 px for the side-stream sort (four to six frames of lag: measured, recording every 2nd frame without a usable order costs 1-2 %)
-    constexpr float FB_STILL_PX = 0.5f, FB_MAX_REACH_PX = 160.0f, FB_MAX_REACH_SIDE_PX = 48.0f, FB_INSTREAM_PX = 3.0f, FB_INSTREAM_LONG_PX = 8.0f;
+    constexpr float FB_MAX_REACH_PX = 160.0f, FB_MAX_REACH_SIDE_PX = 48.0f, FB_INSTREAM_PX = 3.0f, FB_INSTREAM_LONG_PX = 8.0f;
     int dil_rx = 0, dil_ry = 0;
     float reach_px = 0.0f;
     if (fb) {
@@ -1858,6 +1933,12 @@ int atmo_set_tile_feedback(AtmoContext *ctx, int mode) {
         f.used = false;
         f.n = 0;
     }
+    {   // ... and the batches' (atmo_render_views)
+        AtmoContext::FeedbackState &f = ctx->views_fb;
+        if (f.used && (f.n > 0 || f.pending)) f.dirty = true;
+        f.used = false;
+        f.n = 0;
+    }
     ctx->fb_budget = 8;
     return ATMO_OK;
 }
@@ -1871,6 +1952,7 @@ int atmo_get_feedback_stats(AtmoContext *ctx, int *states, unsigned *ordered_dra
     if (!ctx) return ATMO_E_ARG;
     int n = 0;
     for (const AtmoContext::FeedbackState &f : ctx->fb) n += f.used ? 1 : 0;
+    n += ctx->views_fb.used ? 1 : 0;   // the batches' state (atmo_render_views)
     if (states) *states = n;
     if (ordered_draws) *ordered_draws = ctx->fb_ordered_draws;
     if (sorts) *sorts = ctx->fb_sorts;
@@ -2151,11 +2233,8 @@ static int proxy_setup(AtmoContext *ctx, const char *who, const AtmoFrame *f, co
 
 // The family a proxy draw of this context uses, or ATMO_E_STATE when there is no proxy kernel for its mode (proxy_family_supported).
 static int proxy_family(AtmoContext *ctx, const char *who, const AtmoFrame *frame, int *flags, bool *lod) {
-    const char *why_not = nullptr;
-    (void)resolve_sampler_lod(ctx, &why_not);
-    if (ctx->sampler_lod == 1 && why_not) return fail(ctx, ATMO_E_STATE, why_not);
     int split = 1;
-    launch_shape(ctx, frame, flags, &split, lod);
+    { const int rc0 = draw_family(ctx, frame, flags, &split, lod); if (rc0 != ATMO_OK) return rc0; }
     if (split != 1 || !atmo::proxy_family_supported(*flags))
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": no proxy kernel for this context's mode (proxy draws exist for the default forms: atmo_set_precision 1, "
                                                           "up to 32 view steps, one lane per ray)");
@@ -2320,6 +2399,276 @@ int atmo_debug_proxy_launch_rect(AtmoContext *ctx, const AtmoFrame *frame, const
     { const int rc0 = proxy_setup(ctx, who, &fixed, model_matrix, box_size, lod, pc, rect_out, &gx, &gy); if (rc0 != ATMO_OK) return rc0; }
     *tiles_out = gx * gy;
     return ATMO_OK;
+}
+
+// ---- several views in one launch (include/atmo_views.h) -------------------------------------------------------------------------------------
+namespace {
+struct ViewsLayout {
+    int flags = 0;
+    bool lod = false;
+    int n_drawn = 0;                              // views with a non-empty rect
+    bool empty[ATMO_MAX_VIEWS];
+    int gx0[ATMO_MAX_VIEWS], gy0[ATMO_MAX_VIEWS];  // each view's grid origin (its rect's, rounded down to even under the declared sampler)
+    int gx[ATMO_MAX_VIEWS], gy[ATMO_MAX_VIEWS];    // ... and its tile grid (0 x 0 for an empty view)
+    uint32_t first_block[ATMO_MAX_VIEWS + 1];      // prefix of gx * gy; entries behind n_views repeat the total
+};
+
+// Everything about a batch that needs no device: the count, every view's frame checks, the family (ATMO_E_STATE where no multi-view kernel exists), and
+// the concatenated launch.  Shared by atmo_render_views and atmo_debug_views_layout.
+int views_layout(AtmoContext *ctx, const char *who, const AtmoView *views, int n_views, ViewsLayout &L) {
+    if (n_views < 0 || n_views > ATMO_MAX_VIEWS)
+        return fail(ctx, ATMO_E_ARG, std::string(who) + ": n_views must be 0 .. " + std::to_string(ATMO_MAX_VIEWS));
+    if (n_views == 0) {   // nothing to draw, whatever the context's mode
+        for (uint32_t &f : L.first_block) f = 0;
+        return ATMO_OK;
+    }
+    if (!views) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null views");
+    for (int i = 0; i < n_views; ++i) {
+        const int rc0 = check_frame(ctx, std::string(who) + ": view " + std::to_string(i), &views[i].frame, &L.empty[i]);
+        if (rc0 != ATMO_OK) return rc0;
+        if (!L.empty[i]) L.n_drawn += 1;
+    }
+    int split = 1;
+    { const int rc0 = draw_family(ctx, &views[0].frame, &L.flags, &split, &L.lod); if (rc0 != ATMO_OK) return rc0; }
+    if (split != 1 || !atmo::views_family_supported(L.flags))
+        return fail(ctx, ATMO_E_STATE, std::string(who) + ": no multi-view kernel for this context's mode (they exist for the default forms: atmo_set_precision 1, "
+                                                          "up to 32 view steps, one lane per ray)");
+    int tw = 0, th = 0;
+    atmo::render_tile_size(1, &tw, &th);
+    uint64_t total = 0;
+    for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) {
+        L.first_block[i] = (uint32_t)total;
+        if (i >= n_views) continue;
+        const AtmoFrame &f = views[i].frame;
+        L.gx0[i] = L.lod ? f.x0 & ~1 : f.x0;
+        L.gy0[i] = L.lod ? f.y0 & ~1 : f.y0;
+        L.gx[i] = L.empty[i] ? 0 : (f.x1 - L.gx0[i] + tw - 1) / tw;   // == atmo::render_grid of the view's constants
+        L.gy[i] = L.empty[i] ? 0 : (f.y1 - L.gy0[i] + th - 1) / th;
+        total += (uint64_t)L.gx[i] * (uint64_t)L.gy[i];
+    }
+    if (total > 0x7fffffffull) return fail(ctx, ATMO_E_ARG, std::string(who) + ": more than 2^31 tiles in one batch");
+    return ATMO_OK;
+}
+
+// The batches' feedback state, keyed by (stream, family, n_views, every view's grid): re-keyed -- ordered behind whatever used its buffers before, on
+// the device -- when the signature changes.  *out stays null when the context has feedback off for this batch.
+int views_feedback_state(AtmoContext *ctx, const ViewsLayout &L, int n_views, hipStream_t s, AtmoContext::FeedbackState **out) {
+    *out = nullptr;
+    AtmoContext::FeedbackState &f = ctx->views_fb;
+    bool same = f.used && f.draw_stream == s && ctx->views_key_flags == L.flags && ctx->views_key_n == n_views;
+    for (int i = 0; same && i < n_views; ++i) same = ctx->views_key_grid[i][0] == L.gx[i] && ctx->views_key_grid[i][1] == L.gy[i];
+    if (same) { *out = &f; return ATMO_OK; }
+    if (!ctx->fb_stream) {
+        int lo = 0, hi = 0;  // numerically lower = higher priority
+        HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
+        HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->fb_stream, hipStreamNonBlocking, hi));
+    }
+    { const int rc0 = dev_reserve(ctx, ctx->fb_scratch, atmo::tile_order_scratch_bytes()); if (rc0 != ATMO_OK) return rc0; }
+    if (f.used || f.dirty || f.pending || f.n > 0) {
+        const int rc0 = feedback_quiesce(ctx, f, s);
+        if (rc0 != ATMO_OK) return rc0;
+    }
+    const size_t bytes = (size_t)L.first_block[ATMO_MAX_VIEWS] * sizeof(uint32_t);
+    int rc1 = dev_reserve(ctx, f.cost, bytes);
+    for (int k = 0; k < 2 && rc1 == ATMO_OK; ++k) rc1 = dev_reserve(ctx, f.order[k], bytes);
+    if (rc1 != ATMO_OK) { f.used = false; return rc1; }
+    if (!f.ev_draw) {
+        HIP_TRY(ctx, hipEventCreateWithFlags(&f.ev_draw, hipEventDisableTiming));
+        for (int k = 0; k < 2; ++k) HIP_TRY(ctx, hipEventCreateWithFlags(&f.ev_order[k], hipEventDisableTiming));
+    }
+    HIP_TRY(ctx, hipMemsetAsync(f.cost.ptr, 0, bytes, s));
+    f.used = true;
+    f.draw_stream = s;
+    f.n = 0;
+    f.last_record = 0;
+    f.active = -1;
+    f.write = 0;
+    f.pending = false;
+    ctx->views_key_flags = L.flags;
+    ctx->views_key_n = n_views;
+    for (int i = 0; i < n_views; ++i) { ctx->views_key_grid[i][0] = L.gx[i]; ctx->views_key_grid[i][1] = L.gy[i]; }
+    ctx->views_have_prev = false;
+    ctx->views_drop_pending = false;
+    for (float &m : ctx->views_motion_px) m = 0.0f;
+    *out = &f;
+    return ATMO_OK;
+}
+}  // namespace
+
+int atmo_debug_views_layout(AtmoContext *ctx, const AtmoView *views, int n_views, int *first_block, int *grid) {
+    if (!ctx) return ATMO_E_ARG;
+    if (!first_block || !grid) return fail(ctx, ATMO_E_ARG, "atmo_debug_views_layout: null output");
+    ViewsLayout L;
+    { const int rc0 = views_layout(ctx, "atmo_debug_views_layout", views, n_views, L); if (rc0 != ATMO_OK) return rc0; }
+    for (int i = 0; i <= n_views; ++i) first_block[i] = (int)L.first_block[i];
+    for (int i = 0; i < n_views; ++i) { grid[2 * i] = L.gx[i]; grid[2 * i + 1] = L.gy[i]; }
+    return ATMO_OK;
+}
+
+int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_views";
+    ViewsLayout L;
+    { const int rc0 = views_layout(ctx, who, views, n_views, L); if (rc0 != ATMO_OK) return rc0; }
+    // the bytes every view writes: [lo, hi) -- plain: its own tight float4 array; composite: rows y0 .. y1 of its scene buffer, from pixel x0 of the first
+    // to pixel x1 of the last.  Pairwise disjoint, or the views would race (they run concurrently, in no order).
+    uintptr_t lo[ATMO_MAX_VIEWS], hi[ATMO_MAX_VIEWS];
+    for (int i = 0; i < n_views; ++i) {
+        if (L.empty[i]) continue;
+        const AtmoView &v = views[i];
+        { const int rc0 = check_draw_pointers(ctx, std::string(who) + ": view " + std::to_string(i), v.depth_dev, v.rgba_dev, true); if (rc0 != ATMO_OK) return rc0; }
+        const AtmoFrame &f = v.frame;
+        const uintptr_t base = reinterpret_cast<uintptr_t>(v.rgba_dev);
+        if (composite) {
+            lo[i] = base + ((uintptr_t)f.y0 * (uintptr_t)f.viewport_w + (uintptr_t)f.x0) * 16u;
+            hi[i] = base + ((uintptr_t)(f.y1 - 1) * (uintptr_t)f.viewport_w + (uintptr_t)f.x1) * 16u;
+        } else {
+            lo[i] = base;
+            hi[i] = base + (uintptr_t)(f.y1 - f.y0) * (uintptr_t)(f.x1 - f.x0) * 16u;
+        }
+        for (int j = 0; j < i; ++j)
+            if (!L.empty[j] && lo[i] < hi[j] && lo[j] < hi[i])
+                return fail(ctx, ATMO_E_ARG, std::string(who) + ": views " + std::to_string(j) + " and " + std::to_string(i) + " write overlapping memory");
+    }
+    if (L.n_drawn == 0) return ATMO_OK;   // n_views == 0, or every rect empty: nothing to shade
+    { const int rc0 = check_draw_textures(ctx, who); if (rc0 != ATMO_OK) return rc0; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    {   // the table the kernel reads is the context's and the next batch overwrites it: a replayed graph would shade with another batch's constants
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
+            return fail(ctx, ATMO_E_STATE, "atmo_render_views cannot be captured into a HIP graph (context-owned per-view constants); capture atmo_render per view instead");
+    }
+    // a staging slot: the oldest of the ring.  Its event lies behind the launch that read it; only a host VIEWS_RING batches ahead of the device waits here
+    static_assert(ATMO_MAX_VIEWS == atmo::MAX_VIEWS, "the header's view count is the kernels'");
+    if (!ctx->views_host || !ctx->views_dev.ptr) {
+        const size_t ring_bytes = (size_t)AtmoContext::VIEWS_RING * ATMO_MAX_VIEWS * sizeof(atmo::RenderConsts);
+        if (!ctx->views_host) {
+            void *p = nullptr;
+            HIP_TRY(ctx, hipHostMalloc(&p, ring_bytes, hipHostMallocDefault));
+            ctx->views_host = (atmo::RenderConsts *)p;
+        }
+        { const int rc0 = dev_reserve(ctx, ctx->views_dev, ring_bytes); if (rc0 != ATMO_OK) return rc0; }
+        for (int k = 0; k < AtmoContext::VIEWS_RING; ++k) {
+            ctx->views_ring[k].host = ctx->views_host + (size_t)k * ATMO_MAX_VIEWS;
+            ctx->views_ring[k].dev = (atmo::RenderConsts *)ctx->views_dev.ptr + (size_t)k * ATMO_MAX_VIEWS;
+        }
+    }
+    AtmoContext::ViewsSlot &slot = ctx->views_ring[ctx->views_next % AtmoContext::VIEWS_RING];
+    if (!slot.done) HIP_TRY(ctx, hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    if (slot.in_flight) {
+        if (hipEventQuery(slot.done) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->views_ring_waits += 1;
+            HIP_TRY(ctx, hipEventSynchronize(slot.done));
+        }
+        slot.in_flight = false;
+    }
+    AtmoFrame fixed[ATMO_MAX_VIEWS];
+    const AtmoFrame *frames[ATMO_MAX_VIEWS];
+    int first = -1;
+    for (int i = 0; i < n_views; ++i) {
+        atmo::RenderConsts &rc = slot.host[i];
+        if (L.empty[i]) { std::memset(&rc, 0, sizeof(rc)); frames[i] = &views[i].frame; continue; }
+        frames[i] = draw_frame(ctx, &views[i].frame, fixed[i]);
+        draw_consts(ctx, frames[i], views[i].depth_dev, views[i].rgba_dev, composite != 0, rc);
+        draw_grid_origin(frames[i], L.lod, rc);
+        rc.tiles_x = L.gx[i];
+        if (first < 0) first = i;
+    }
+    { const int rc0 = tex_order(ctx, s); if (rc0 != ATMO_OK) return rc0; }  // texture updated on another stream
+    atmo::ViewsConsts vc;
+    std::memset(&vc, 0, sizeof(vc));
+    for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) vc.first_block[i] = L.first_block[i];
+    const uint32_t total = L.first_block[ATMO_MAX_VIEWS];
+    // One tile order over all views, learnt as render_impl learns a single draw's on a still camera: the first two batches of a signature are not
+    // measured, the next four record, then every fb_period-th; the sort runs beside the draws on the side stream and its order is picked up once a
+    // host-side event query says it is complete.  While any view moves, the batch is neither ordered nor recorded (no dilation per view: atmo_views.h).
+    bool feedback = ctx->env_feedback >= 0 ? ctx->env_feedback != 0 : ctx->tile_feedback != 0;
+    if (total < 512u) feedback = false;   // tiny launches: nothing to schedule
+    AtmoContext::FeedbackState *fb = nullptr;
+    bool fb_record = false;
+    if (feedback) {
+        const int rc1 = views_feedback_state(ctx, L, n_views, s, &fb);
+        if (rc1 != ATMO_OK) return rc1;
+    }
+    if (fb) {
+        bool moving = false;
+        for (int i = 0; i < n_views; ++i) {
+            if (L.empty[i]) continue;
+            if (ctx->views_have_prev) {
+                const float m = feedback_motion_px(*frames[i], ctx->views_prev[i], ctx->p.u_planet_radius + ctx->p.u_atmosphere_height,
+                                                   (L.flags & atmo::KF_CLOUDS) != 0);
+                ctx->views_motion_px[i] = std::fmax(m, 0.75f * ctx->views_motion_px[i]);  // peak hold: one still frame does not end a camera move
+                if (ctx->views_motion_px[i] < 0.01f) ctx->views_motion_px[i] = 0.0f;
+            }
+            ctx->views_prev[i] = *frames[i];
+            moving = moving || ctx->views_motion_px[i] > FB_STILL_PX;
+        }
+        ctx->views_have_prev = true;
+        if (fb->pending) {
+            if (moving) ctx->views_drop_pending = true;   // sorted from a picture that has moved on since
+            if (hipEventQuery(fb->ev_order[fb->write]) == hipSuccess) {
+                if (!ctx->views_drop_pending) { fb->active = fb->write; fb->write ^= 1; }
+                fb->pending = false;
+                ctx->views_drop_pending = false;
+            } else {
+                (void)hipGetLastError();  // hipErrorNotReady is an answer, not an error
+            }
+        }
+        if (moving) {
+            fb->active = -1;
+        } else {
+            if (fb->active >= 0) {
+                vc.order = (const uint32_t *)fb->order[fb->active].ptr;
+                ctx->fb_ordered_draws += 1;
+            }
+            fb_record = !fb->pending && fb->n >= 2 && (fb->n < 6 || fb->n - fb->last_record >= ctx->fb_period);
+            if (fb_record) vc.cost = (uint32_t *)fb->cost.ptr;
+        }
+    }
+    struct EventPair {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~EventPair() {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } ev;
+    const bool timed = ctx->timing > 0 && (ctx->launch_counter % ctx->timing) == 0;
+    if (timed) {
+        if (ctx->pending.size() >= 64) drain_timing(ctx, /*only_completed=*/true);
+        HIP_TRY(ctx, hipEventCreate(&ev.e0));
+        HIP_TRY(ctx, hipEventCreate(&ev.e1));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(slot.dev, slot.host, (size_t)n_views * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
+    if (timed) HIP_TRY(ctx, hipEventRecord(ev.e0, s));   // the bracket is the one launch's
+    HIP_TRY(ctx, atmo::launch_render_views(L.flags, slot.host[first].light_steps, slot.dev, vc, s));
+    if (timed) {
+        HIP_TRY(ctx, hipEventRecord(ev.e1, s));
+        ctx->pending.emplace_back(ev.e0, ev.e1);
+        ev.e0 = ev.e1 = nullptr;  // ownership moved
+    }
+    HIP_TRY(ctx, hipEventRecord(slot.done, s));
+    slot.in_flight = true;
+    ctx->views_next += 1;
+    ctx->last_flags = L.flags | atmo::KF_VIEWS;
+    ctx->last_split = 1;
+    if (fb_record) {
+        // as render_impl: order[write] was last read by batches enqueued on `s` before this one, so the event orders the write too
+        HIP_TRY(ctx, hipEventRecord(fb->ev_draw, s));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->fb_stream, fb->ev_draw, 0));
+        HIP_TRY(ctx, atmo::launch_tile_order((uint32_t *)fb->cost.ptr, (uint32_t *)fb->order[fb->write].ptr, (int)total, 1, 0, 0, nullptr, nullptr,
+                                             (uint32_t *)ctx->fb_scratch.ptr, ctx->fb_stream, nullptr, nullptr));
+        HIP_TRY(ctx, hipEventRecord(fb->ev_order[fb->write], ctx->fb_stream));
+        fb->pending = true;
+        ctx->views_drop_pending = false;
+        fb->last_record = fb->n;
+        ctx->fb_sorts += 1;
+    }
+    if (fb) fb->n += 1;
+    ctx->launch_counter += 1;
+    hipEvent_t marker = nullptr;
+    return note_draw_stream(ctx, s, &marker);
 }
 
 }  // extern "C"

@@ -129,7 +129,10 @@ enum KernelFlags : int { KF_CLOUDS = 1, KF_CLOUD_LIGHT_RM = 2, KF_LIGHT_DIRECT =
                                             (ProxyConsts); its own kernel (atmo_render_proxy_kernel), so the kernels of atmo_render stay what they were */,
                           KF_TARGET = 1024 /* a packed colour target (atmo_render_target, include/atmo_target.h): shade_pixel's stores and its blend go through
                                               store_target<FMT> on TargetConsts instead of RenderConsts::out; kernels of their own (atmo_render_target_kernel,
-                                              atmo_render_proxy_target_kernel), for the same reason */ };
+                                              atmo_render_proxy_target_kernel), for the same reason */,
+                          KF_VIEWS = 2048 /* several views in one launch (atmo_render_views, include/atmo_views.h): the block index runs over the concatenation of all
+                                             views' tiles and shade_pixel reads the view's RenderConsts from a device table (ViewsConsts); a kernel of its own
+                                             (atmo_render_views_kernel), for the same reason */ };
 
 // The far-mode draw's proxy (planet_atmosphere.gd:300-321: a BoxMesh of edge box_size centred on the node, rasterised with back-face culling, near / far
 // clipping and Godot 4.3's reverse-Z GREATER_OR_EQUAL depth test).  Pixel (nx, ny) of the existing prologue's NDC: its segment from the near plane (z = 1) to
@@ -153,10 +156,25 @@ struct TargetConsts {
                            // uniform, read only where a pixel is addressed and stored
 };
 
+// Several views in one launch (include/atmo_views.h).  The per-view RenderConsts live in a device table (the kernel's first argument: a const __restrict__
+// pointer, indexed by a wave-uniform view number, so every field still arrives through scalar loads); this is what the launch itself needs.  The grid is
+// one-dimensional over the concatenation of the views' tiles: global tile t belongs to the view v with first_block[v] <= t < first_block[v + 1] and is that
+// view's tile t - first_block[v], row-major in its own grid (RenderConsts::tiles_x).
+constexpr int MAX_VIEWS = 8;   // == ATMO_MAX_VIEWS
+struct ViewsConsts {
+    uint32_t first_block[MAX_VIEWS + 1];   // prefix of the views' tile counts (an empty view adds nothing); entries behind n_views repeat the total
+    const uint32_t *order;                 // null => global tile = block index (view-major, row-major inside a view); else the global tile each block shades
+    uint32_t *cost;                        // null => no feedback; else per GLOBAL tile the longest wave's duration in shader cycles (atomicMax)
+};
+
 hipError_t launch_render(int flags, int split, const RenderConsts &rc, hipStream_t stream, int tile_list_blocks = 0);  // > 0: rc.tile_order lists that many tiles of the rect's grid
 // the proxy draws: one lane per ray, row-major grid of the rect in rc; flags = a draw's family without KF_PROXY (proxy_family_supported)
 bool proxy_family_supported(int flags);
 hipError_t launch_render_proxy(int flags, const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream);
+// the multi-view draws: one lane per ray; flags = a draw's family without KF_VIEWS (views_family_supported: the proxy draws' list); table_dev holds one
+// RenderConsts per view (light_steps is the context's: the same in all of them); total_blocks = vc.first_block[MAX_VIEWS]
+bool views_family_supported(int flags);
+hipError_t launch_render_views(int flags, int light_steps, const RenderConsts *table_dev, const ViewsConsts &vc, hipStream_t stream);
 // the packed-target draws: the float draws' launches (grid, tile order, cost feedback, tile lists for the heavy-tile split) with the KF_TARGET kernels.
 // flags without KF_TARGET / KF_PROXY; target_family_supported says which (flags, split) exist.
 bool target_family_supported(int flags, int split);

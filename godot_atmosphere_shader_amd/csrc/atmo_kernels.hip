@@ -2027,6 +2027,8 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                   "packed targets: the default forms; two lanes per ray only as the heavy-tile form of the declared-sampler cloud kernels");
     static_assert(!VIEWPOS || (!LITE && !ATMO_REF && SPLIT == 1), "KF_VIEW_POS: the fast v2 march, one lane per ray");
     static_assert(!PROXY || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0), "proxy draws: the default forms, one lane per ray, row-major");
+    static_assert((FLAGS & KF_VIEWS) == 0 || (!VIEWPOS && !ATMO_REF && !PROXY && !TARGET && SPLIT == 1 && (FLAGS & KF_GEO) == 0),
+                  "multi-view draws: the default forms, one lane per ray, float targets");
     constexpr bool DIET = !DIRECT && !((FLAGS & KF_CLOUDS) && (FLAGS & KF_CLOUD_LIGHT_RM));
     constexpr bool FASTMISS = (ATMO_FAST_MISS_MASK >> ((DIRECT ? 1 : 0) + (CLOUDS ? 2 : 0) + (LITE ? 4 : 0))) & 1;
     static_assert(!LOD || (CLOUDS && PRECISE), "implicit cubemap LOD: precise cloud kernels");
@@ -2385,6 +2387,46 @@ template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_proxy_kernel(const RenderConsts rc, const ProxyConsts pc) {
     static_assert((FLAGS & KF_PROXY) != 0, "proxy kernels carry KF_PROXY");
     shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, &pc);
+}
+// Several views in one launch (KF_VIEWS; atmo_render_views, include/atmo_views.h).  The grid is one-dimensional over the concatenation of all views' tiles:
+// block b shades global tile order[b] (one heaviest-first order over ALL views: the heavy tiles of every view first, the cheap tiles of all of them fill one
+// common drain), or b itself without an order (view-major, row-major inside a view).  The view is found among at most eight prefix values with scalar
+// compares, and its RenderConsts are `table[view]` in device memory: the index is wave-uniform and the pointer a read-only __restrict__ kernel argument, so
+// shade_pixel's reads of the constants stay scalar loads (SGPRs), as they are from the kernel-argument segment in atmo_render_kernel -- no per-lane copy of
+// the struct (round 4: a copy with the dynamically indexed rm_tap[i] becomes a 1.2 KB stack frame).  Costs are recorded per GLOBAL tile, as
+// ATMO_RENDER_KERNEL_BODY records them.  A kernel of its own, so that atmo_render's kernels keep their code to the byte.
+// VGPRs: every kernel of the family stays on the occupancy step of its atmo_render twin (profiles/views/README.md holds the table).  The level-0 cloud
+// kernels without raymarched light need the bound spelled out: their twins fit 62 VGPRs (eight waves per SIMD) under the common bound of six, these came
+// out at 68 (seven) without it.
+#ifndef ATMO_LOOP_PAD_VIEWS   // s_nop at the head of <KF_VIEWS | KF_LIGHT_DIRECT, 8>
+#define ATMO_LOOP_PAD_VIEWS 5
+#endif
+#define ATMO_VIEWS_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_VIEWS)
+constexpr int views_min_waves(int flags) {
+    return ((flags & KF_CLOUDS) && !(flags & (KF_CLOUD_LIGHT_RM | KF_CUBE_LOD))) ? 8 : render_min_waves(flags);
+}
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_kernel(const RenderConsts *__restrict__ table, const ViewsConsts vc) {
+    static_assert((FLAGS & KF_VIEWS) != 0, "multi-view kernels carry KF_VIEWS");
+    // the headline kernel's twin <KF_VIEWS | KF_LIGHT_DIRECT, 8>: its view loop on ITS fast position, 12 bytes into a 32-byte block, as the float kernel's
+    // (march_atmosphere; tools/loop_phase.py reads it, tests/test_views_host.py holds it there)
+    if constexpr (FLAGS == (KF_VIEWS | KF_LIGHT_DIRECT) && LSTEPS == 8) asm volatile(".rept " ATMO_VIEWS_PAD_STR "\n\ts_nop 0\n\t.endr");
+    uint32_t tile = blockIdx.x;
+    if (vc.order != nullptr) tile = vc.order[tile];
+    uint32_t view = 0;   // the last view whose first block is <= tile (empty views share their successor's first block and are stepped over)
+#pragma unroll
+    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vc.first_block[i] ? 1u : 0u;
+    view = __builtin_amdgcn_readfirstlane(view);
+    const RenderConsts &rc = table[view];
+    const uint32_t local = tile - vc.first_block[view];
+    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
+    uint64_t t0 = 0;
+    if (vc.cost != nullptr) t0 = __builtin_amdgcn_s_memtime();
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y);
+    if (vc.cost != nullptr && (threadIdx.x & 63) == 0) {
+        const uint64_t dt = __builtin_amdgcn_s_memtime() - t0;
+        atomicMax(&vc.cost[tile], (uint32_t)(dt > 0xffffffffull ? 0xffffffffull : dt));
+    }
 }
 // the same kernel under an 80-SGPR cap (8 waves per SIMD), for the families render_sgpr_cap80 names (none in the shipped build)
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
@@ -3080,6 +3122,38 @@ bool proxy_family_supported(int flags) {
     }
 }
 
+// ---- multi-view launchers: the proxy draws' families (what a default context selects), one lane per ray
+template <int FLAGS, int LSTEPS>
+static hipError_t launch_v(const RenderConsts *table, const ViewsConsts &vc, hipStream_t stream) {
+    const uint32_t total = vc.first_block[MAX_VIEWS];
+    if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((atmo_render_views_kernel<FLAGS | KF_VIEWS, LSTEPS>), dim3(total), dim3(TILE_W * TILE_H), 0, stream, table, vc);
+    return hipGetLastError();
+}
+hipError_t launch_render_views(int flags, int light_steps, const RenderConsts *table, const ViewsConsts &vc, hipStream_t stream) {
+#define ATMO_V_CASE(F) case (F): return launch_v<(F), 0>(table, vc, stream);
+#define ATMO_V_CASE_DIRECT(F) case (F): return light_steps == 8 ? launch_v<(F), 8>(table, vc, stream) : launch_v<(F), 0>(table, vc, stream);   // 8 light steps unrolled, as launch_direct
+    switch (flags) {
+        ATMO_V_CASE(0)
+        ATMO_V_CASE_DIRECT(KF_LIGHT_DIRECT)
+        ATMO_V_CASE(KF_PRECISE | KF_CLOUDS)
+        ATMO_V_CASE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
+        ATMO_V_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
+        ATMO_V_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
+        ATMO_V_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)
+        ATMO_V_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
+        ATMO_V_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
+        ATMO_V_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
+        ATMO_V_CASE(KF_PRECISE | KF_LITE)
+        ATMO_V_CASE(KF_PRECISE | KF_LITE | KF_CLOUDS)
+        ATMO_V_CASE(KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS)
+    default: return hipErrorInvalidValue;   // (the host asks views_family_supported first)
+    }
+#undef ATMO_V_CASE
+#undef ATMO_V_CASE_DIRECT
+}
+bool views_family_supported(int flags) { return proxy_family_supported(flags); }   // exactly the proxy draw's list
+
 // ---- packed-target launchers: the families of the proxy draws (what a default context selects), the geometric-order twin of the direct-light kernel, and
 // the two-lanes-per-ray form of the two declared-sampler cloud kernels that render_impl draws a frame's heavy tiles with
 template <int FLAGS, int LSTEPS, int SPLIT>
@@ -3197,6 +3271,10 @@ const char *render_kernel_name(int flags, int light_steps, int split) {
     const int lsteps = ((flags & KF_LIGHT_DIRECT) && light_steps == 8 && !v2_precise && !(flags & KF_VIEW_POS)) ? 8 : 0;
     if (flags & KF_PROXY) {
         snprintf(name, sizeof(name), "atmo_render_proxy%s_kernel<%d, %d>", (flags & KF_TARGET) ? "_target" : "", flags, lsteps);
+        return name;
+    }
+    if (flags & KF_VIEWS) {
+        snprintf(name, sizeof(name), "atmo_render_views_kernel<%d, %d>", flags, lsteps);
         return name;
     }
     if (flags & KF_TARGET) {

@@ -111,6 +111,14 @@ int atmo_debug_frame_constants(AtmoContext *ctx, const AtmoFrame *frame, int cub
  * rect; x0 == x1 when nothing is left), *tiles_out = the workgroup tiles of its grid (0: no launch). */
 int atmo_debug_proxy_launch_rect(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, int *rect_out, int *tiles_out);
 
+/* The launch a batch (include/atmo_views.h, atmo_render_views) of this context would make -- host arithmetic only, so it works on a host-only context:
+ * grid[2 i], grid[2 i + 1] = view i's tile grid (columns, rows of 16 x 8 pixel tiles from its grid origin: the rect's x0, y0, rounded down to even under
+ * the declared sampler; 0 x 0 for an empty rect), first_block[i] = the first block of view i in the one-dimensional launch over the concatenation of all
+ * views' tiles, first_block[n_views] = the launch's block count.  The argument and mode checks are atmo_render_views's (ATMO_E_ARG / ATMO_E_STATE);
+ * the device pointers of the views are not looked at. */
+struct AtmoView;
+int atmo_debug_views_layout(AtmoContext *ctx, const struct AtmoView *views, int n_views, int *first_block /* n_views + 1 */, int *grid /* 2 per view */);
+
 /* Diagnostics (no reference counterpart): the render kernels' store_target<format> (include/atmo_target.h: the encode, and the composite's decode / blend /
  * encode) on caller-supplied DEVICE arrays, so that the contract can be tested on chosen values rather than on what a scene happens to produce:
  * dst[i] = encode(src[i]) for composite == 0, encode(blend(src[i], decode(dst[i]))) otherwise; src = n_pixels x 4 floats (16-byte aligned), dst = n_pixels

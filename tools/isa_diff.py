@@ -4,7 +4,9 @@ both libraries with llvm-objdump, branch targets and addresses stripped to offse
 
     python tools/isa_diff.py OLD.so NEW.so [symbol regex, default "atmo_render_kernel|atmo_render_proxy_kernel"]
 
-Prints one line per symbol that differs or exists in one build only, and a summary; exit status 1 when an OLD symbol is missing from or differs in NEW."""
+Prints one line per symbol that differs or exists in one build only, and a summary; exit status 1 when an OLD symbol is missing from or differs in NEW.
+The literal of an `s_add_u32` / `s_addc_u32` that follows an `s_getpc_b64` is a PC-relative address (of a constant table elsewhere in the code object): it
+moves whenever a kernel is added in front of the table, and is not compared -- such kernels are counted as identical, and how many there were is said."""
 import os
 import re
 import subprocess
@@ -32,16 +34,31 @@ if __name__ == "__main__":
     pattern = sys.argv[3] if len(sys.argv) > 3 else r"atmo_render_kernel|atmo_render_proxy_kernel"
     with tempfile.TemporaryDirectory(prefix="isadiff_") as tmp:
         old, new = kernels(old_lib, pattern, tmp, "old"), kernels(new_lib, pattern, tmp, "new")
-    bad = 0
+    def strip_pcrel(ins):
+        """The instruction list with the literals of the address arithmetic behind s_getpc_b64 (text and encoding) blanked."""
+        out, window = [], 0
+        for text, raw in ins:
+            if text.startswith("s_getpc_b64"):
+                window = 4
+            elif window > 0 and re.match(r"s_addc?_u32 s\d+, s\d+, (0x[0-9a-f]+|-?\d+)$", text):
+                text, raw = text.rsplit(",", 1)[0] + ", <pc-relative>", raw.split()[0] if raw.split() else raw
+            window -= 1
+            out.append((text, raw))
+        return out
+
+    bad = moved = 0
     for name in sorted(old):
         if name not in new:
             print(f"MISSING in new: {name}")
             bad += 1
+        elif old[name] != new[name] and strip_pcrel(old[name]) == strip_pcrel(new[name]):
+            moved += 1
         elif old[name] != new[name]:
             first = next((i for i, (a, b) in enumerate(zip(old[name], new[name])) if a != b), min(len(old[name]), len(new[name])))
             print(f"DIFFERS: {name}: {len(old[name])} -> {len(new[name])} instructions, first difference at instruction {first}")
             bad += 1
     added = sorted(set(new) - set(old))
-    print(f"{len(old)} kernels in the old build, {len(old) - bad} identical in the new one (text and encoding), {bad} differ or are missing; "
+    print(f"{len(old)} kernels in the old build, {len(old) - bad} identical in the new one (text and encoding; {moved} of them up to a PC-relative constant), "
+          f"{bad} differ or are missing; "
           f"{len(added)} matching kernels only in the new build")
     sys.exit(1 if bad else 0)
