@@ -40,7 +40,10 @@ TARGET_SYMBOLS = ("atmo_target_pixel_bytes", "atmo_render_target", "atmo_render_
 # a host detects the feature by the symbol.
 VIEWS_SYMBOLS = ("atmo_render_views",)
 MAX_VIEWS = 8
-EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS
+# every symbol include/atmo_views_target.h declares: the same batch into packed and pitched colour targets (RGBA16F / RGBA8_UNORM / RGBA32F per view).
+# The ABI version stays 5: a host detects the feature by the symbol.
+VIEWS_TARGET_SYMBOLS = ("atmo_render_views_target",)
+EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 
 
@@ -73,6 +76,14 @@ class AtmoView(C.Structure):
         ("frame", AtmoFrame),
         ("depth_dev", C.c_void_p),
         ("rgba_dev", C.c_void_p),
+    ]
+
+
+class AtmoViewTarget(C.Structure):
+    _fields_ = [
+        ("frame", AtmoFrame),
+        ("depth_dev", C.c_void_p),
+        ("target", AtmoTarget),
     ]
 
 
@@ -154,6 +165,7 @@ def load() -> C.CDLL:
         "atmo_debug_store_target": (ip, [vp, ip, ip, vp, vp, C.c_size_t, vp]),
         "atmo_render_views": (ip, [vp, C.POINTER(AtmoView), ip, ip, vp]),
         "atmo_debug_views_layout": (ip, [vp, C.POINTER(AtmoView), ip, C.POINTER(ip), C.POINTER(ip)]),
+        "atmo_render_views_target": (ip, [vp, C.POINTER(AtmoViewTarget), ip, ip, vp]),
     }
     # ATMO_HIP_LIB names an A/B build (tools/ab_build_commit.sh: possibly an OLDER commit's library): entry points it lacks are skipped
     # (callers of those guard with hasattr) and its ABI version is not held against it.  The in-tree library must match exactly.

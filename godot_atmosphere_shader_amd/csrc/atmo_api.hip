@@ -10,6 +10,7 @@
 #include "../../include/atmo_scene.h"
 #include "../../include/atmo_target.h"
 #include "../../include/atmo_views.h"
+#include "../../include/atmo_views_target.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 
@@ -2405,6 +2406,7 @@ int atmo_debug_proxy_launch_rect(AtmoContext *ctx, const AtmoFrame *frame, const
 namespace {
 struct ViewsLayout {
     int flags = 0;
+    int family = 0;                               // the kernel family the batch launches: flags | KF_VIEWS [| KF_TARGET] (a part of the feedback signature)
     bool lod = false;
     int n_drawn = 0;                              // views with a non-empty rect
     bool empty[ATMO_MAX_VIEWS];
@@ -2413,33 +2415,49 @@ struct ViewsLayout {
     uint32_t first_block[ATMO_MAX_VIEWS + 1];      // prefix of gx * gy; entries behind n_views repeat the total
 };
 
-// Everything about a batch that needs no device: the count, every view's frame checks, the family (ATMO_E_STATE where no multi-view kernel exists), and
-// the concatenated launch.  Shared by atmo_render_views and atmo_debug_views_layout.
-int views_layout(AtmoContext *ctx, const char *who, const AtmoView *views, int n_views, ViewsLayout &L) {
+// What a batch entry point hands on about one view, whichever structure it came in (AtmoView, AtmoViewTarget).
+struct ViewArg {
+    const AtmoFrame *frame = nullptr;
+    const float *depth = nullptr;
+    void *pixels = nullptr;                 // as the single draw's: plain -- the rect's first pixel; composite -- the viewport's
+    int pitch_px = 0;                       // float targets: pixels from one row to the next, 0 = the draw's own (tight)
+    atmo::TargetConsts tc = {nullptr, 0, 0};   // packed targets (RGBA16F / RGBA8_UNORM)
+};
+
+// The first half of what a batch needs no device for: the count and every view's frame checks.  *done: n_views == 0, nothing to draw whatever the
+// context's mode.
+int views_check_frames(AtmoContext *ctx, const char *who, bool have_views, const ViewArg *args, int n_views, ViewsLayout &L, bool *done) {
+    *done = false;
     if (n_views < 0 || n_views > ATMO_MAX_VIEWS)
         return fail(ctx, ATMO_E_ARG, std::string(who) + ": n_views must be 0 .. " + std::to_string(ATMO_MAX_VIEWS));
     if (n_views == 0) {   // nothing to draw, whatever the context's mode
         for (uint32_t &f : L.first_block) f = 0;
+        *done = true;
         return ATMO_OK;
     }
-    if (!views) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null views");
+    if (!have_views) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null views");
     for (int i = 0; i < n_views; ++i) {
-        const int rc0 = check_frame(ctx, std::string(who) + ": view " + std::to_string(i), &views[i].frame, &L.empty[i]);
+        const int rc0 = check_frame(ctx, std::string(who) + ": view " + std::to_string(i), args[i].frame, &L.empty[i]);
         if (rc0 != ATMO_OK) return rc0;
         if (!L.empty[i]) L.n_drawn += 1;
     }
+    return ATMO_OK;
+}
+// The second half: the family (ATMO_E_STATE where no multi-view kernel exists; `packed`: the KF_VIEWS | KF_TARGET kernels) and the concatenated launch.
+int views_family_grid(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, bool packed, ViewsLayout &L) {
     int split = 1;
-    { const int rc0 = draw_family(ctx, &views[0].frame, &L.flags, &split, &L.lod); if (rc0 != ATMO_OK) return rc0; }
-    if (split != 1 || !atmo::views_family_supported(L.flags))
+    { const int rc0 = draw_family(ctx, args[0].frame, &L.flags, &split, &L.lod); if (rc0 != ATMO_OK) return rc0; }
+    if (split != 1 || !(packed ? atmo::views_target_family_supported(L.flags) : atmo::views_family_supported(L.flags)))
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": no multi-view kernel for this context's mode (they exist for the default forms: atmo_set_precision 1, "
                                                           "up to 32 view steps, one lane per ray)");
+    L.family = L.flags | atmo::KF_VIEWS | (packed ? atmo::KF_TARGET : 0);
     int tw = 0, th = 0;
     atmo::render_tile_size(1, &tw, &th);
     uint64_t total = 0;
     for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) {
         L.first_block[i] = (uint32_t)total;
         if (i >= n_views) continue;
-        const AtmoFrame &f = views[i].frame;
+        const AtmoFrame &f = *args[i].frame;
         L.gx0[i] = L.lod ? f.x0 & ~1 : f.x0;
         L.gy0[i] = L.lod ? f.y0 & ~1 : f.y0;
         L.gx[i] = L.empty[i] ? 0 : (f.x1 - L.gx0[i] + tw - 1) / tw;   // == atmo::render_grid of the view's constants
@@ -2449,13 +2467,24 @@ int views_layout(AtmoContext *ctx, const char *who, const AtmoView *views, int n
     if (total > 0x7fffffffull) return fail(ctx, ATMO_E_ARG, std::string(who) + ": more than 2^31 tiles in one batch");
     return ATMO_OK;
 }
+// Both halves, for the float batch (atmo_render_views, atmo_debug_views_layout): args[i] = views[i]'s frame, depth and output.
+int views_layout(AtmoContext *ctx, const char *who, const AtmoView *views, int n_views, ViewArg *args, ViewsLayout &L) {
+    for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) {
+        args[i].frame = &views[i].frame;
+        args[i].depth = views[i].depth_dev;
+        args[i].pixels = views[i].rgba_dev;
+    }
+    bool done = false;
+    { const int rc0 = views_check_frames(ctx, who, views != nullptr, args, n_views, L, &done); if (rc0 != ATMO_OK || done) return rc0; }
+    return views_family_grid(ctx, who, args, n_views, false, L);
+}
 
 // The batches' feedback state, keyed by (stream, family, n_views, every view's grid): re-keyed -- ordered behind whatever used its buffers before, on
 // the device -- when the signature changes.  *out stays null when the context has feedback off for this batch.
 int views_feedback_state(AtmoContext *ctx, const ViewsLayout &L, int n_views, hipStream_t s, AtmoContext::FeedbackState **out) {
     *out = nullptr;
     AtmoContext::FeedbackState &f = ctx->views_fb;
-    bool same = f.used && f.draw_stream == s && ctx->views_key_flags == L.flags && ctx->views_key_n == n_views;
+    bool same = f.used && f.draw_stream == s && ctx->views_key_flags == L.family && ctx->views_key_n == n_views;
     for (int i = 0; same && i < n_views; ++i) same = ctx->views_key_grid[i][0] == L.gx[i] && ctx->views_key_grid[i][1] == L.gy[i];
     if (same) { *out = &f; return ATMO_OK; }
     if (!ctx->fb_stream) {
@@ -2484,7 +2513,7 @@ int views_feedback_state(AtmoContext *ctx, const ViewsLayout &L, int n_views, hi
     f.active = -1;
     f.write = 0;
     f.pending = false;
-    ctx->views_key_flags = L.flags;
+    ctx->views_key_flags = L.family;
     ctx->views_key_n = n_views;
     for (int i = 0; i < n_views; ++i) { ctx->views_key_grid[i][0] = L.gx[i]; ctx->views_key_grid[i][1] = L.gy[i]; }
     ctx->views_have_prev = false;
@@ -2493,43 +2522,9 @@ int views_feedback_state(AtmoContext *ctx, const ViewsLayout &L, int n_views, hi
     *out = &f;
     return ATMO_OK;
 }
-}  // namespace
-
-int atmo_debug_views_layout(AtmoContext *ctx, const AtmoView *views, int n_views, int *first_block, int *grid) {
-    if (!ctx) return ATMO_E_ARG;
-    if (!first_block || !grid) return fail(ctx, ATMO_E_ARG, "atmo_debug_views_layout: null output");
-    ViewsLayout L;
-    { const int rc0 = views_layout(ctx, "atmo_debug_views_layout", views, n_views, L); if (rc0 != ATMO_OK) return rc0; }
-    for (int i = 0; i <= n_views; ++i) first_block[i] = (int)L.first_block[i];
-    for (int i = 0; i < n_views; ++i) { grid[2 * i] = L.gx[i]; grid[2 * i + 1] = L.gy[i]; }
-    return ATMO_OK;
-}
-
-int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int composite, void *stream) {
-    if (!ctx) return ATMO_E_ARG;
-    const char *who = "atmo_render_views";
-    ViewsLayout L;
-    { const int rc0 = views_layout(ctx, who, views, n_views, L); if (rc0 != ATMO_OK) return rc0; }
-    // the bytes every view writes: [lo, hi) -- plain: its own tight float4 array; composite: rows y0 .. y1 of its scene buffer, from pixel x0 of the first
-    // to pixel x1 of the last.  Pairwise disjoint, or the views would race (they run concurrently, in no order).
-    uintptr_t lo[ATMO_MAX_VIEWS], hi[ATMO_MAX_VIEWS];
-    for (int i = 0; i < n_views; ++i) {
-        if (L.empty[i]) continue;
-        const AtmoView &v = views[i];
-        { const int rc0 = check_draw_pointers(ctx, std::string(who) + ": view " + std::to_string(i), v.depth_dev, v.rgba_dev, true); if (rc0 != ATMO_OK) return rc0; }
-        const AtmoFrame &f = v.frame;
-        const uintptr_t base = reinterpret_cast<uintptr_t>(v.rgba_dev);
-        if (composite) {
-            lo[i] = base + ((uintptr_t)f.y0 * (uintptr_t)f.viewport_w + (uintptr_t)f.x0) * 16u;
-            hi[i] = base + ((uintptr_t)(f.y1 - 1) * (uintptr_t)f.viewport_w + (uintptr_t)f.x1) * 16u;
-        } else {
-            lo[i] = base;
-            hi[i] = base + (uintptr_t)(f.y1 - f.y0) * (uintptr_t)(f.x1 - f.x0) * 16u;
-        }
-        for (int j = 0; j < i; ++j)
-            if (!L.empty[j] && lo[i] < hi[j] && lo[j] < hi[i])
-                return fail(ctx, ATMO_E_ARG, std::string(who) + ": views " + std::to_string(j) + " and " + std::to_string(i) + " write overlapping memory");
-    }
+// Everything a batch does once its arguments stand: the staging slot, the per-view constants, the tile order and its feedback, the ONE launch.  Shared by
+// atmo_render_views (packed == false: the float kernels, args[i].pitch_px) and atmo_render_views_target (packed: the KF_VIEWS | KF_TARGET kernels, args[i].tc).
+int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, int composite, bool packed, const ViewsLayout &L, void *stream) {
     if (L.n_drawn == 0) return ATMO_OK;   // n_views == 0, or every rect empty: nothing to shade
     { const int rc0 = check_draw_textures(ctx, who); if (rc0 != ATMO_OK) return rc0; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2537,7 +2532,7 @@ int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int 
     {   // the table the kernel reads is the context's and the next batch overwrites it: a replayed graph would shade with another batch's constants
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-            return fail(ctx, ATMO_E_STATE, "atmo_render_views cannot be captured into a HIP graph (context-owned per-view constants); capture atmo_render per view instead");
+            return fail(ctx, ATMO_E_STATE, std::string(who) + " cannot be captured into a HIP graph (context-owned per-view constants); capture atmo_render per view instead");
     }
     // a staging slot: the oldest of the ring.  Its event lies behind the launch that read it; only a host VIEWS_RING batches ahead of the device waits here
     static_assert(ATMO_MAX_VIEWS == atmo::MAX_VIEWS, "the header's view count is the kernels'");
@@ -2569,16 +2564,20 @@ int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int 
     int first = -1;
     for (int i = 0; i < n_views; ++i) {
         atmo::RenderConsts &rc = slot.host[i];
-        if (L.empty[i]) { std::memset(&rc, 0, sizeof(rc)); frames[i] = &views[i].frame; continue; }
-        frames[i] = draw_frame(ctx, &views[i].frame, fixed[i]);
-        draw_consts(ctx, frames[i], views[i].depth_dev, views[i].rgba_dev, composite != 0, rc);
+        if (L.empty[i]) { std::memset(&rc, 0, sizeof(rc)); frames[i] = args[i].frame; continue; }
+        frames[i] = draw_frame(ctx, args[i].frame, fixed[i]);
+        draw_consts(ctx, frames[i], args[i].depth, (float *)args[i].pixels, composite != 0, rc);
+        if (args[i].pitch_px > 0) rc.out_pitch = args[i].pitch_px;
+        if (packed) rc.out = nullptr;   // the KF_TARGET kernels address tc.pixels, rows tc.pitch_bytes apart
         draw_grid_origin(frames[i], L.lod, rc);
         rc.tiles_x = L.gx[i];
         if (first < 0) first = i;
     }
     { const int rc0 = tex_order(ctx, s); if (rc0 != ATMO_OK) return rc0; }  // texture updated on another stream
-    atmo::ViewsConsts vc;
-    std::memset(&vc, 0, sizeof(vc));
+    atmo::ViewsTargetConsts vtc;   // (its targets are read by the packed kernels only)
+    std::memset(&vtc, 0, sizeof(vtc));
+    atmo::ViewsConsts &vc = vtc.v;
+    for (int i = 0; packed && i < n_views; ++i) if (!L.empty[i]) vtc.target[i] = args[i].tc;
     for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) vc.first_block[i] = L.first_block[i];
     const uint32_t total = L.first_block[ATMO_MAX_VIEWS];
     // One tile order over all views, learnt as render_impl learns a single draw's on a still camera: the first two batches of a signature are not
@@ -2642,7 +2641,8 @@ int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int 
     }
     HIP_TRY(ctx, hipMemcpyAsync(slot.dev, slot.host, (size_t)n_views * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
     if (timed) HIP_TRY(ctx, hipEventRecord(ev.e0, s));   // the bracket is the one launch's
-    HIP_TRY(ctx, atmo::launch_render_views(L.flags, slot.host[first].light_steps, slot.dev, vc, s));
+    if (packed) HIP_TRY(ctx, atmo::launch_render_views_target(L.flags, slot.host[first].light_steps, slot.dev, vtc, s));
+    else HIP_TRY(ctx, atmo::launch_render_views(L.flags, slot.host[first].light_steps, slot.dev, vc, s));
     if (timed) {
         HIP_TRY(ctx, hipEventRecord(ev.e1, s));
         ctx->pending.emplace_back(ev.e0, ev.e1);
@@ -2651,7 +2651,7 @@ int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int 
     HIP_TRY(ctx, hipEventRecord(slot.done, s));
     slot.in_flight = true;
     ctx->views_next += 1;
-    ctx->last_flags = L.flags | atmo::KF_VIEWS;
+    ctx->last_flags = L.family;
     ctx->last_split = 1;
     if (fb_record) {
         // as render_impl: order[write] was last read by batches enqueued on `s` before this one, so the event orders the write too
@@ -2669,6 +2669,106 @@ int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int 
     ctx->launch_counter += 1;
     hipEvent_t marker = nullptr;
     return note_draw_stream(ctx, s, &marker);
+}
+
+}  // namespace
+
+int atmo_debug_views_layout(AtmoContext *ctx, const AtmoView *views, int n_views, int *first_block, int *grid) {
+    if (!ctx) return ATMO_E_ARG;
+    if (!first_block || !grid) return fail(ctx, ATMO_E_ARG, "atmo_debug_views_layout: null output");
+    ViewsLayout L;
+    ViewArg args[ATMO_MAX_VIEWS];
+    { const int rc0 = views_layout(ctx, "atmo_debug_views_layout", views, n_views, args, L); if (rc0 != ATMO_OK) return rc0; }
+    for (int i = 0; i <= n_views; ++i) first_block[i] = (int)L.first_block[i];
+    for (int i = 0; i < n_views; ++i) { grid[2 * i] = L.gx[i]; grid[2 * i + 1] = L.gy[i]; }
+    return ATMO_OK;
+}
+
+int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_views";
+    ViewsLayout L;
+    ViewArg args[ATMO_MAX_VIEWS];
+    { const int rc0 = views_layout(ctx, who, views, n_views, args, L); if (rc0 != ATMO_OK) return rc0; }
+    // the bytes every view writes: [lo, hi) -- plain: its own tight float4 array; composite: rows y0 .. y1 of its scene buffer, from pixel x0 of the first
+    // to pixel x1 of the last.  Pairwise disjoint, or the views would race (they run concurrently, in no order).
+    uintptr_t lo[ATMO_MAX_VIEWS], hi[ATMO_MAX_VIEWS];
+    for (int i = 0; i < n_views; ++i) {
+        if (L.empty[i]) continue;
+        const AtmoView &v = views[i];
+        { const int rc0 = check_draw_pointers(ctx, std::string(who) + ": view " + std::to_string(i), v.depth_dev, v.rgba_dev, true); if (rc0 != ATMO_OK) return rc0; }
+        const AtmoFrame &f = v.frame;
+        const uintptr_t base = reinterpret_cast<uintptr_t>(v.rgba_dev);
+        if (composite) {
+            lo[i] = base + ((uintptr_t)f.y0 * (uintptr_t)f.viewport_w + (uintptr_t)f.x0) * 16u;
+            hi[i] = base + ((uintptr_t)(f.y1 - 1) * (uintptr_t)f.viewport_w + (uintptr_t)f.x1) * 16u;
+        } else {
+            lo[i] = base;
+            hi[i] = base + (uintptr_t)(f.y1 - f.y0) * (uintptr_t)(f.x1 - f.x0) * 16u;
+        }
+        for (int j = 0; j < i; ++j)
+            if (!L.empty[j] && lo[i] < hi[j] && lo[j] < hi[i])
+                return fail(ctx, ATMO_E_ARG, std::string(who) + ": views " + std::to_string(j) + " and " + std::to_string(i) + " write overlapping memory");
+    }
+    return views_enqueue(ctx, who, args, n_views, composite, false, L, stream);
+}
+
+// include/atmo_views_target.h: the batch into packed and pitched colour targets.  All argument checks (ATMO_E_ARG) in front of the mode check (ATMO_E_STATE),
+// both in front of anything that touches a device.
+int atmo_render_views_target(AtmoContext *ctx, const AtmoViewTarget *views, int n_views, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_views_target";
+    ViewsLayout L;
+    ViewArg args[ATMO_MAX_VIEWS];
+    for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) {
+        args[i].frame = &views[i].frame;
+        args[i].depth = views[i].depth_dev;
+        args[i].pixels = views[i].target.pixels;
+    }
+    {
+        bool done = false;
+        const int rc0 = views_check_frames(ctx, who, views != nullptr, args, n_views, L, &done);
+        if (rc0 != ATMO_OK || done) return rc0;
+    }
+    // per view: atmo_render_target's checks; one format per batch; and the bytes it writes -- `rows` rows of `row_bytes`, `pitch` apart, from `base`
+    int format = -1;
+    uintptr_t base[ATMO_MAX_VIEWS];
+    long long rows[ATMO_MAX_VIEWS], row_bytes[ATMO_MAX_VIEWS], pitch[ATMO_MAX_VIEWS];
+    for (int i = 0; i < n_views; ++i) {
+        if (L.empty[i]) continue;   // skipped: its pointers and its target are not looked at
+        const AtmoViewTarget &v = views[i];
+        const std::string who_i = std::string(who) + ": view " + std::to_string(i);
+        int p = 0;
+        { const int rc0 = target_check(ctx, who_i.c_str(), &v.frame, &v.target, composite != 0, &p); if (rc0 != ATMO_OK) return rc0; }
+        { const int rc0 = check_draw_pointers(ctx, who_i, v.depth_dev, (const float *)v.target.pixels, false); if (rc0 != ATMO_OK) return rc0; }
+        if (format >= 0 && v.target.format != format)
+            return fail(ctx, ATMO_E_ARG, who_i + ": target format " + std::to_string(v.target.format) + " differs from the batch's (" + std::to_string(format) +
+                                             "): one format per batch");
+        format = v.target.format;
+        const AtmoFrame &f = v.frame;
+        const long long px = atmo_target_pixel_bytes(format);
+        pitch[i] = p;
+        rows[i] = f.y1 - f.y0;
+        row_bytes[i] = (long long)(f.x1 - f.x0) * px;
+        base[i] = reinterpret_cast<uintptr_t>(v.target.pixels) + (composite ? (uintptr_t)((long long)f.y0 * p + (long long)f.x0 * px) : (uintptr_t)0);
+        args[i].pitch_px = format == ATMO_TARGET_RGBA32F ? p / 16 : 0;
+        args[i].tc = {v.target.pixels, p, v.target.format};
+        for (int j = 0; j < i; ++j) {
+            if (L.empty[j]) continue;
+            const int a = base[j] <= base[i] ? j : i, b = a == j ? i : j;   // A: the view of lower base
+            // (a) the byte ranges [base, base + (rows - 1) * pitch + row_bytes) are disjoint
+            if (base[a] + (uintptr_t)((rows[a] - 1) * pitch[a] + row_bytes[a]) <= base[b]) continue;
+            // (b) one pitch P: B starts behind A's last row, or in the gap of A's rows and ends inside it (rows of one image, side by side)
+            if (pitch[a] == pitch[b]) {
+                const uintptr_t d = base[b] - base[a], P = (uintptr_t)pitch[a], q = d / P, r = d % P;
+                if (q >= (uintptr_t)rows[a] || (r >= (uintptr_t)row_bytes[a] && r + (uintptr_t)row_bytes[b] <= P)) continue;
+            }
+            return fail(ctx, ATMO_E_ARG, std::string(who) + ": views " + std::to_string(j) + " and " + std::to_string(i) + " write overlapping memory");
+        }
+    }
+    const bool packed = format == ATMO_TARGET_RGBA16F || format == ATMO_TARGET_RGBA8_UNORM;
+    { const int rc0 = views_family_grid(ctx, who, args, n_views, packed, L); if (rc0 != ATMO_OK) return rc0; }
+    return views_enqueue(ctx, who, args, n_views, composite, packed, L, stream);
 }
 
 }  // extern "C"

@@ -132,7 +132,8 @@ enum KernelFlags : int { KF_CLOUDS = 1, KF_CLOUD_LIGHT_RM = 2, KF_LIGHT_DIRECT =
                                               atmo_render_proxy_target_kernel), for the same reason */,
                           KF_VIEWS = 2048 /* several views in one launch (atmo_render_views, include/atmo_views.h): the block index runs over the concatenation of all
                                              views' tiles and shade_pixel reads the view's RenderConsts from a device table (ViewsConsts); a kernel of its own
-                                             (atmo_render_views_kernel), for the same reason */ };
+                                             (atmo_render_views_kernel), for the same reason; with KF_TARGET: the same into packed colour targets, one
+                                             TargetConsts per view (atmo_render_views_target_kernel, include/atmo_views_target.h) */ };
 
 // The far-mode draw's proxy (planet_atmosphere.gd:300-321: a BoxMesh of edge box_size centred on the node, rasterised with back-face culling, near / far
 // clipping and Godot 4.3's reverse-Z GREATER_OR_EQUAL depth test).  Pixel (nx, ny) of the existing prologue's NDC: its segment from the near plane (z = 1) to
@@ -166,6 +167,12 @@ struct ViewsConsts {
     const uint32_t *order;                 // null => global tile = block index (view-major, row-major inside a view); else the global tile each block shades
     uint32_t *cost;                        // null => no feedback; else per GLOBAL tile the longest wave's duration in shader cycles (atomicMax)
 };
+// ... and where every view of a batch into packed colour targets stores (atmo_render_views_target): the eight TargetConsts by value in the kernel-argument
+// segment, indexed by the same wave-uniform view number, so they too arrive through scalar loads and the staging ring carries RenderConsts only.
+struct ViewsTargetConsts {
+    ViewsConsts v;
+    TargetConsts target[MAX_VIEWS];        // entries of empty views and behind n_views are zero: no tile maps to them
+};
 
 hipError_t launch_render(int flags, int split, const RenderConsts &rc, hipStream_t stream, int tile_list_blocks = 0);  // > 0: rc.tile_order lists that many tiles of the rect's grid
 // the proxy draws: one lane per ray, row-major grid of the rect in rc; flags = a draw's family without KF_PROXY (proxy_family_supported)
@@ -175,6 +182,11 @@ hipError_t launch_render_proxy(int flags, const RenderConsts &rc, const ProxyCon
 // RenderConsts per view (light_steps is the context's: the same in all of them); total_blocks = vc.first_block[MAX_VIEWS]
 bool views_family_supported(int flags);
 hipError_t launch_render_views(int flags, int light_steps, const RenderConsts *table_dev, const ViewsConsts &vc, hipStream_t stream);
+// the multi-view draws into packed colour targets (atmo_render_views_target, include/atmo_views_target.h): the same launch with the KF_VIEWS | KF_TARGET
+// kernels; vtc.target[v] is view v's target, every non-empty view in the one format vtc.target[first non-empty].format (RGBA16F or RGBA8_UNORM: RGBA32F
+// batches are launch_render_views with the pitch in RenderConsts::out_pitch)
+bool views_target_family_supported(int flags);
+hipError_t launch_render_views_target(int flags, int light_steps, const RenderConsts *table_dev, const ViewsTargetConsts &vtc, hipStream_t stream);
 // the packed-target draws: the float draws' launches (grid, tile order, cost feedback, tile lists for the heavy-tile split) with the KF_TARGET kernels.
 // flags without KF_TARGET / KF_PROXY; target_family_supported says which (flags, split) exist.
 bool target_family_supported(int flags, int split);

@@ -2027,8 +2027,8 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                   "packed targets: the default forms; two lanes per ray only as the heavy-tile form of the declared-sampler cloud kernels");
     static_assert(!VIEWPOS || (!LITE && !ATMO_REF && SPLIT == 1), "KF_VIEW_POS: the fast v2 march, one lane per ray");
     static_assert(!PROXY || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0), "proxy draws: the default forms, one lane per ray, row-major");
-    static_assert((FLAGS & KF_VIEWS) == 0 || (!VIEWPOS && !ATMO_REF && !PROXY && !TARGET && SPLIT == 1 && (FLAGS & KF_GEO) == 0),
-                  "multi-view draws: the default forms, one lane per ray, float targets");
+    static_assert((FLAGS & KF_VIEWS) == 0 || (!VIEWPOS && !ATMO_REF && !PROXY && SPLIT == 1 && (FLAGS & KF_GEO) == 0),
+                  "multi-view draws: the default forms, one lane per ray, float or packed targets (KF_VIEWS | KF_TARGET: atmo_render_views_target_kernel)");
     constexpr bool DIET = !DIRECT && !((FLAGS & KF_CLOUDS) && (FLAGS & KF_CLOUD_LIGHT_RM));
     constexpr bool FASTMISS = (ATMO_FAST_MISS_MASK >> ((DIRECT ? 1 : 0) + (CLOUDS ? 2 : 0) + (LITE ? 4 : 0))) & 1;
     static_assert(!LOD || (CLOUDS && PRECISE), "implicit cubemap LOD: precise cloud kernels");
@@ -2465,6 +2465,40 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render
                                                                                                       const TargetConsts tc) {
     static_assert((FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0, "proxy target kernels carry KF_PROXY | KF_TARGET");
     shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, &pc, &tc);
+}
+// Several views in one launch into packed colour targets (KF_VIEWS | KF_TARGET; atmo_render_views_target, include/atmo_views_target.h): the body of
+// atmo_render_views_kernel -- tile lookup, view lookup by scalar compares, table[view], cost recording per global tile -- with the view's TargetConsts handed
+// to shade_pixel.  The eight TargetConsts sit by value in the kernel-argument segment and are indexed by the same wave-uniform view number: scalar loads, no
+// per-lane copy, and the staging ring still carries RenderConsts only.  A kernel of its own name (neither atmo_render_views_kernel< nor
+// atmo_render_target_kernel is a substring of it), so that every other kernel keeps its code to the byte.  VGPRs: launch bounds as the float batch's
+// (views_min_waves); profiles/views/README.md holds the table against the float-batch twins.
+#ifndef ATMO_LOOP_PAD_VIEWS_TARGET   // s_nop at the head of <KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8>
+#define ATMO_LOOP_PAD_VIEWS_TARGET 5
+#endif
+#define ATMO_VIEWS_TARGET_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_VIEWS_TARGET)
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_target_kernel(const RenderConsts *__restrict__ table,
+                                                                                                         const ViewsTargetConsts vtc) {
+    static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_TARGET) != 0, "multi-view target kernels carry KF_VIEWS | KF_TARGET");
+    // the headline kernel's twin <KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8>: its view loop on ITS fast position, 12 bytes into a 32-byte block, as the
+    // other twins' (march_atmosphere; tools/loop_phase.py reads it, tests/test_views_target_host.py holds it there)
+    if constexpr (FLAGS == (KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8) asm volatile(".rept " ATMO_VIEWS_TARGET_PAD_STR "\n\ts_nop 0\n\t.endr");
+    uint32_t tile = blockIdx.x;
+    if (vtc.v.order != nullptr) tile = vtc.v.order[tile];
+    uint32_t view = 0;   // as atmo_render_views_kernel: the last view whose first block is <= tile
+#pragma unroll
+    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vtc.v.first_block[i] ? 1u : 0u;
+    view = __builtin_amdgcn_readfirstlane(view);
+    const RenderConsts &rc = table[view];
+    const uint32_t local = tile - vtc.v.first_block[view];
+    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
+    uint64_t t0 = 0;
+    if (vtc.v.cost != nullptr) t0 = __builtin_amdgcn_s_memtime();
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, nullptr, &vtc.target[view]);
+    if (vtc.v.cost != nullptr && (threadIdx.x & 63) == 0) {
+        const uint64_t dt = __builtin_amdgcn_s_memtime() - t0;
+        atomicMax(&vtc.v.cost[tile], (uint32_t)(dt > 0xffffffffull ? 0xffffffffull : dt));
+    }
 }
 
 // Stable counting sort of the tiles by the cost a recording draw measured, heaviest class first; clears the costs for
@@ -3242,6 +3276,46 @@ hipError_t launch_render_proxy_target(int flags, const RenderConsts &rc, const P
     }
 }
 
+// ---- multi-view launchers into packed colour targets: the float batch's families, one lane per ray
+template <int FLAGS, int LSTEPS>
+static hipError_t launch_vt(const RenderConsts *table, const ViewsTargetConsts &vtc, hipStream_t stream) {
+    const uint32_t total = vtc.v.first_block[MAX_VIEWS];
+    if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((atmo_render_views_target_kernel<FLAGS | KF_VIEWS | KF_TARGET, LSTEPS>), dim3(total), dim3(TILE_W * TILE_H), 0, stream, table, vtc);
+    return hipGetLastError();
+}
+hipError_t launch_render_views_target(int flags, int light_steps, const RenderConsts *table, const ViewsTargetConsts &vtc, hipStream_t stream) {
+    // one format per batch, and every view that owns tiles has a target
+    int format = -1;
+    for (int i = 0; i < MAX_VIEWS; ++i) {
+        if (vtc.v.first_block[i + 1] == vtc.v.first_block[i]) continue;
+        const TargetConsts &t = vtc.target[i];
+        if (t.pixels == nullptr || (t.format != TF_RGBA16F && t.format != TF_RGBA8_UNORM) || (format >= 0 && t.format != format)) return hipErrorInvalidValue;
+        format = t.format;
+    }
+#define ATMO_VT_CASE(F) case (F): return launch_vt<(F), 0>(table, vtc, stream);
+#define ATMO_VT_CASE_DIRECT(F) case (F): return light_steps == 8 ? launch_vt<(F), 8>(table, vtc, stream) : launch_vt<(F), 0>(table, vtc, stream);   // as launch_render_views
+    switch (flags) {
+        ATMO_VT_CASE(0)
+        ATMO_VT_CASE_DIRECT(KF_LIGHT_DIRECT)
+        ATMO_VT_CASE(KF_PRECISE | KF_CLOUDS)
+        ATMO_VT_CASE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
+        ATMO_VT_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
+        ATMO_VT_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
+        ATMO_VT_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)
+        ATMO_VT_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
+        ATMO_VT_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
+        ATMO_VT_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
+        ATMO_VT_CASE(KF_PRECISE | KF_LITE)
+        ATMO_VT_CASE(KF_PRECISE | KF_LITE | KF_CLOUDS)
+        ATMO_VT_CASE(KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS)
+    default: return hipErrorInvalidValue;   // (the host asks views_target_family_supported first)
+    }
+#undef ATMO_VT_CASE
+#undef ATMO_VT_CASE_DIRECT
+}
+bool views_target_family_supported(int flags) { return views_family_supported(flags) && target_family_supported(flags, 1); }   // the two lists' intersection: the same list
+
 // store_target<FMT> on caller-supplied arrays (atmo_debug_store_target): the encode and the blend on chosen values, one pixel per lane
 template <int FMT>
 __global__ __launch_bounds__(256) void atmo_store_target_kernel(const float4 *__restrict__ src, void *dst, size_t n, int composite) {
@@ -3274,7 +3348,7 @@ const char *render_kernel_name(int flags, int light_steps, int split) {
         return name;
     }
     if (flags & KF_VIEWS) {
-        snprintf(name, sizeof(name), "atmo_render_views_kernel<%d, %d>", flags, lsteps);
+        snprintf(name, sizeof(name), "atmo_render_views%s_kernel<%d, %d>", (flags & KF_TARGET) ? "_target" : "", flags, lsteps);
         return name;
     }
     if (flags & KF_TARGET) {

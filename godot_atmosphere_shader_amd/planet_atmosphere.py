@@ -635,12 +635,34 @@ class PlanetAtmosphere:
         rc = self._lib.atmo_render_views(self._ctx, views, int(n_views), int(bool(composite)), C.c_void_p(stream or 0))
         N.check(self._ctx, rc)
 
-    def render_views(self, cameras, depths, outs=None, rects=None, composite: bool = False, stream=None, time: float = 0.0):
+    def prepare_views_target(self, cameras, depth_ptrs, targets, rects=None, time: float = 0.0):
+        """The native argument block of `render_views_target_prepared`: one N.AtmoViewTarget per camera; targets[i] is an N.AtmoTarget (pixels, format,
+        row pitch in bytes) addressed as `atmo_render_target` addresses it."""
+        n = len(cameras)
+        if not (len(depth_ptrs) == n and len(targets) == n and (rects is None or len(rects) == n)):
+            raise ValueError("cameras, depths, targets and rects must have one entry per view")
+        views = (N.AtmoViewTarget * max(n, 1))()
+        for i, cam in enumerate(cameras):
+            views[i].frame = _to_native_frame(self.make_frame(cam, time, rects[i] if rects is not None else None))
+            views[i].depth_dev = depth_ptrs[i]
+            views[i].target = targets[i]
+        return views
+
+    def render_views_target_prepared(self, views, n_views: int, composite: bool = False, stream: int = 0):
+        """Enqueue one batch from `prepare_views_target` (atmo_render_views_target): one ctypes call, one launch for all views."""
+        self._bake_if_needed(stream)
+        rc = self._lib.atmo_render_views_target(self._ctx, views, int(n_views), int(bool(composite)), C.c_void_p(stream or 0))
+        N.check(self._ctx, rc)
+
+    def render_views(self, cameras, depths, outs=None, rects=None, composite: bool = False, stream=None, time: float = 0.0, target=None):
         """Several views of this planet in ONE launch (atmo_render_views): the two eyes of a stereo pass, a split screen, probe faces -- up to
         N.MAX_VIEWS.  View i is bit for bit `render(cameras[i], depths[i], outs[i], rects[i])` -- or, with composite=True,
         `render_composite(cameras[i], depths[i], outs[i], rects[i])`, where outs[i] is view i's (H_i, W_i, 4) scene buffer, blended in place --;
-        viewport sizes and rects may differ between views.  The tensors are checked as those calls check theirs (contiguous CUDA float32); outs=None
-        allocates the plain outputs.  The tensors the views write must not overlap.  One native call; returns the list of output tensors."""
+        viewport sizes and rects may differ between views.  The tensors are checked as those calls check theirs; outs=None allocates the plain
+        outputs.  The tensors the views write must not overlap.  One native call; returns the list of output tensors.
+        outs[i] may also be float16 (RGBA16F) or uint8 (RGBA8_UNORM) tensors, and their rows may be further apart than a row (a row pitch: the two
+        halves of one double-wide image, say): the batch then stores or blends in that format (atmo_render_views_target; one format per batch).
+        target="rgba16f" | "rgba8" allocates such outputs."""
         import torch
 
         n = len(cameras)
@@ -651,6 +673,7 @@ class PlanetAtmosphere:
         if composite and outs is None:
             raise ValueError("composite=True blends into the views' scene buffers: pass them as outs")
         outs = list(outs) if outs is not None else [None] * n
+        tgts = [None] * n
         for i, (cam, depth) in enumerate(zip(cameras, depths)):
             if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()):
                 raise TypeError(f"view {i}: depth must be a contiguous CUDA float32 tensor")
@@ -659,19 +682,22 @@ class PlanetAtmosphere:
             x0, y0, x1, y1 = rects[i] if rects is not None and rects[i] is not None else (0, 0, cam.width, cam.height)
             rows, cols = (cam.height, cam.width) if composite else (y1 - y0, x1 - x0)
             if outs[i] is None:
-                outs[i] = torch.empty((rows, cols, 4), dtype=torch.float32, device=depth.device)
-            o = outs[i]
-            if not (isinstance(o, torch.Tensor) and o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == (rows, cols, 4)):
-                raise ValueError(f"view {i}: {'scene_rgba' if composite else 'out'} must be a contiguous CUDA float32 tensor of shape ({rows}, {cols}, 4) "
-                                 "(packed colour targets are not part of render_views)")
+                outs[i] = _new_target(rows, cols, target, depth.device, zero=False)
+            # a contiguous float32 tensor (None), or the N.AtmoTarget of a float16 / uint8 / pitched one
+            tgts[i] = _colour_target(outs[i], rows, cols, f"view {i}: {'scene_rgba' if composite else 'out'}")
         if n == 0:
             return outs
         if stream is None:
             stream = torch.cuda.current_stream(depths[0].device).cuda_stream
         elif hasattr(stream, "cuda_stream"):
             stream = stream.cuda_stream
-        views = self.prepare_views(cameras, [d.data_ptr() for d in depths], [o.data_ptr() for o in outs], rects, time)
-        self.render_views_prepared(views, n, composite, stream)
+        if all(t is None for t in tgts):
+            views = self.prepare_views(cameras, [d.data_ptr() for d in depths], [o.data_ptr() for o in outs], rects, time)
+            self.render_views_prepared(views, n, composite, stream)
+        else:
+            tgts = [t if t is not None else N.AtmoTarget(o.data_ptr(), N.TARGET_RGBA32F, 0) for t, o in zip(tgts, outs)]
+            views = self.prepare_views_target(cameras, [d.data_ptr() for d in depths], tgts, rects, time)
+            self.render_views_target_prepared(views, n, composite, stream)
         return outs
 
     # ---- the far-mode draw: the BoxMesh proxy (include/atmo_scene.h) ---------------------------------------------------------------

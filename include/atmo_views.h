@@ -57,8 +57,9 @@
  * views of the 8-step baked-LUT atmosphere without clouds (15-25 us draws): +9 % at 1920 x 1080, +11 % at 1280 x 720 -- the batch's copy of the per-view
  * constants and its event are not amortised by two such draws (eight are: 0.82).
  *
- * WHAT COMES NEXT (not part of this header): packed colour targets (atmo_target.h: RGBA16F / RGBA8 / a row pitch) per view, proxy (far-mode) views,
- * motion-aware orders per view.
+ * PACKED AND PITCHED COLOUR TARGETS per view (RGBA16F / RGBA8 / a row pitch, and with the pitch the side-by-side halves of one image): atmo_views_target.h.
+ *
+ * WHAT COMES NEXT (not part of this header): proxy (far-mode) views, motion-aware orders per view.
  */
 #ifndef ATMO_VIEWS_H
 #define ATMO_VIEWS_H
