@@ -29,7 +29,7 @@ DEBUG_SYMBOLS = (
     "atmo_set_lane_split", "atmo_debug_motion_px", "atmo_get_feedback_stats", "atmo_set_timing", "atmo_get_timing", "atmo_host_layout_cubemap", "atmo_host_layout_shape",
     "atmo_host_layout_lut", "atmo_host_cubemap_mip", "atmo_read_texture_layout", "atmo_selftest_exact_math", "atmo_debug_marched_optical_depth", "atmo_debug_log2_cr", "atmo_kernel_name", "atmo_build_id",
     "atmo_get_host_wait_stats", "atmo_get_split_stats", "atmo_debug_create_host_only", "atmo_debug_frame_constants", "atmo_debug_proxy_launch_rect",
-    "atmo_debug_store_target", "atmo_debug_views_layout",
+    "atmo_debug_store_target", "atmo_debug_views_layout", "atmo_debug_tile_order", "atmo_debug_heavy_tile_count",
 )
 # every symbol include/atmo_scene.h declares: drawing several atmospheres into one frame (the far-mode BoxMesh draw)
 SCENE_SYMBOLS = ("atmo_render_proxy", "atmo_render_proxy_composite")
@@ -166,6 +166,8 @@ def load() -> C.CDLL:
         "atmo_render_views": (ip, [vp, C.POINTER(AtmoView), ip, ip, vp]),
         "atmo_debug_views_layout": (ip, [vp, C.POINTER(AtmoView), ip, C.POINTER(ip), C.POINTER(ip)]),
         "atmo_render_views_target": (ip, [vp, C.POINTER(AtmoViewTarget), ip, ip, vp]),
+        "atmo_debug_tile_order": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, C.POINTER(ip)]),
+        "atmo_debug_heavy_tile_count": (ip, [vp, ip, ip, C.c_float, C.c_float, ip]),
     }
     # ATMO_HIP_LIB names an A/B build (tools/ab_build_commit.sh: possibly an OLDER commit's library): entry points it lacks are skipped
     # (callers of those guard with hasattr) and its ABI version is not held against it.  The in-tree library must match exactly.

@@ -495,7 +495,8 @@ int resolve_sampler_lod(const AtmoContext *ctx, const char **why_not) {
 // A cloud frame at 1920x1080 is as long as its heaviest wavefront (all 64 rays in dense cloud: 0.36 of the 0.42 ms of clouds_high_rm; a
 // wave issues one instruction every ~5 cycles however empty the SIMD is) -- those tiles are drawn with two lanes per ray, which halves
 // exactly that, for 13-29 % more work on them; at 3840x2160 the same waves are a quarter of the draw and nothing is split.
-//   totals[k]: tiles in cost class k (half octaves of the wave duration in shader cycles, 0 = heaviest: tile_cost_class);
+//   totals[k]: tiles in cost class k (TILE_ORDER_PER_OCTAVE equal parts of every octave of the wave duration in shader cycles -- quarter octaves in the
+//   shipped 64-class build, half octaves in a 32-class one -- 0 = heaviest: tile_cost_class); a class counts with the middle of its range, the last with 0;
 //   the draw's duration is estimated from the same numbers: sum of wave lifetimes / resident waves (2 waves per tile; SIMDs x waves per SIMD).
 int heavy_tile_count(const uint32_t *totals, int n_tiles, float ratio, float trigger, int resident_waves) {
     double life[atmo::TILE_ORDER_CLASSES], sum = 0.0;
@@ -2036,6 +2037,43 @@ int atmo_debug_log2_cr(AtmoContext *ctx, int n, const float *x, float *out) {
     (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(ctx, e, "atmo_debug_log2_cr");
     return ATMO_OK;
+}
+
+// The feedback path's sort on the caller's costs.  Every device buffer is fresh and filled with 0xFFFFFFFF before the launch (the scratch and the dilation
+// temporaries included), so an entry the kernels never write comes back as that value instead of as whatever an earlier sort left there.
+int atmo_debug_tile_order(AtmoContext *ctx, const uint32_t *cost, int tiles_x, int tiles_y, int rx, int ry, uint32_t *order_out, uint32_t *order2_out,
+                          uint32_t *class_totals_out, uint32_t *cost_after_out, int *n_classes_out) {
+    if (!ctx) return ATMO_E_ARG;
+    if (!cost || !order_out) return fail(ctx, ATMO_E_ARG, "atmo_debug_tile_order: cost and order_out must not be NULL");
+    if (tiles_x < 1 || tiles_y < 1 || (long long)tiles_x * tiles_y > (1ll << 22))
+        return fail(ctx, ATMO_E_ARG, "atmo_debug_tile_order: the grid must be at least 1 x 1 and hold at most 2^22 tiles");
+    if (rx < 0 || ry < 0 || rx > 64 || ry > 64) return fail(ctx, ATMO_E_ARG, "atmo_debug_tile_order: dilation radii are 0 .. 64 tiles");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    constexpr size_t NC = atmo::TILE_ORDER_CLASSES;
+    const size_t n = (size_t)tiles_x * (size_t)tiles_y, scratch_words = atmo::tile_order_scratch_bytes() / sizeof(uint32_t);
+    // one allocation: cost | order | order2 | tmp1 | tmp2 | class totals | scratch
+    const size_t words = 6 * n + NC + scratch_words;
+    uint32_t *d = nullptr;
+    HIP_TRY(ctx, hipMalloc(&d, words * sizeof(uint32_t)));
+    uint32_t *d_cost = d, *d_order = d + n, *d_order2 = d + 2 * n, *d_tmp1 = d + 4 * n, *d_tmp2 = d + 5 * n, *d_totals = d + 6 * n, *d_scratch = d_totals + NC;
+    hipError_t e = hipMemset(d, 0xFF, words * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(d_cost, cost, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = atmo::launch_tile_order(d_cost, d_order, tiles_x, tiles_y, rx, ry, d_tmp1, d_tmp2, d_scratch, nullptr,
+                                                     order2_out ? d_order2 : nullptr, class_totals_out ? d_totals : nullptr);
+    if (e == hipSuccess) e = hipMemcpy(order_out, d_order, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && order2_out) e = hipMemcpy(order2_out, d_order2, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && class_totals_out) e = hipMemcpy(class_totals_out, d_totals, NC * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && cost_after_out) e = hipMemcpy(cost_after_out, d_cost, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return hip_fail(ctx, e, "atmo_debug_tile_order");
+    if (n_classes_out) *n_classes_out = (int)NC;
+    return ATMO_OK;
+}
+
+int atmo_debug_heavy_tile_count(const uint32_t *class_totals, int n_classes, int n_tiles, float ratio, float trigger, int resident_waves) {
+    if (!class_totals || n_classes != atmo::TILE_ORDER_CLASSES || n_tiles < 0 || resident_waves < 1)
+        return -fail(nullptr, ATMO_E_ARG, "atmo_debug_heavy_tile_count: bad argument (NULL totals, a class count other than the build's, n_tiles < 0 or resident_waves < 1)");
+    return heavy_tile_count(class_totals, n_tiles, ratio, trigger, resident_waves);
 }
 
 const char *atmo_kernel_name(AtmoContext *ctx) {

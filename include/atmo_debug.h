@@ -125,6 +125,22 @@ int atmo_debug_views_layout(AtmoContext *ctx, const struct AtmoView *views, int 
  * pixels of `format` (AtmoTargetFormat; RGBA32F included).  Enqueues one kernel on `stream`. */
 int atmo_debug_store_target(AtmoContext *ctx, int format, int composite, const float *src_rgba_f32_dev, void *dst_dev, size_t n_pixels, void *stream);
 
+/* Diagnostics (no reference counterpart): the library's tile-order sort (launch_tile_order, exactly the call the feedback path makes) on the caller's costs.
+ * All pointers are HOST memory.  cost: tiles_x * tiles_y values, row-major (n = their product, at most 2^22).  rx, ry: dilation radii in tiles (0 .. 64).
+ * order_out: n entries.  order2_out (may be NULL): 2 n.  class_totals_out (may be NULL): *n_classes_out entries.
+ * cost_after_out (may be NULL): the cost map as the sort leaves it, n entries.  n_classes_out (may be NULL): the build's class count (32 or 64).
+ * A NULL order2_out / class_totals_out reaches the sort as NULL (the view batch's form).  Every device buffer the sort sees is fresh and holds 0xFFFFFFFF
+ * in every word before the launch, so an entry the kernels do not write comes back as 0xFFFFFFFF.  A bad argument writes nothing. */
+int atmo_debug_tile_order(AtmoContext *ctx, const uint32_t *cost, int tiles_x, int tiles_y, int rx, int ry, uint32_t *order_out, uint32_t *order2_out,
+                          uint32_t *class_totals_out, uint32_t *cost_after_out, int *n_classes_out);
+
+/* heavy_tile_count as the draw path calls it (how many leading tiles of a sorted order go to the two-lanes-per-ray kernels); needs no device and no context.
+ * class_totals: n_classes entries, class 0 the heaviest.  Returns the count (>= 0); a bad argument -- NULL totals, n_classes other than the build's, n_tiles < 0,
+ * resident_waves < 1 -- returns -ATMO_E_ARG (a count cannot be negative; every other entry point returns a positive ATMO_E_*) and leaves a message for
+ * atmo_last_error_string(NULL).  That is the slot a failed atmo_create writes, one per thread: read it on the calling thread, before that thread's next
+ * atmo_create or call of this function. */
+int atmo_debug_heavy_tile_count(const uint32_t *class_totals, int n_classes, int n_tiles, float ratio, float trigger, int resident_waves);
+
 #ifdef ATMO_WAVE_TRACE
 /* Diagnostic builds only (-DATMO_WAVE_TRACE: tools/wave_timeline.py, tools/rmq_stats.py; the shipped library does not export it): copies the wave
  * trace of the last draw -- 4 x uint64 per wave: start, end (s_memrealtime, 100 MHz), HW_ID, XCC_ID | preamble ticks << 8 -- to the host and
