@@ -20,10 +20,10 @@ sanitize:           # ASan + UBSan run of the CPU oracle's tests
 
                     # (the loop-placement tests read the SHIPPED -O3 library's layout; this -O1 -g build's is another: deselected, as on the parent commit they failed here)
 sanitize-host:      # ASan + UBSan over the HOST side of libatmo_hip.so (uniform table, per-frame constants, layout helpers, argument checks,
-                    # the motion estimate, the packed-target checks, the multi-view checks and layout) driven by the no-GPU tests; the device code is built as always (no GPU sanitizers on this pool)
+                    # the motion estimate, the tile-order feedback's policy, the packed-target checks, the multi-view checks and layout) driven by the no-GPU tests; the device code is built as always (no GPU sanitizers on this pool)
 	set -e; out=$$(python -m godot_atmosphere_shader_amd.build --sanitize | tail -1); lib=$${out%% *}; rt=$${out##* }; \
 	LD_PRELOAD=$$rt ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=print_stacktrace=1 ATMO_HIP_LIB=$$lib \
-	    python -m pytest tests/test_host_logic.py tests/test_target_host.py tests/test_views_host.py -q -m "not gpu" -k "not whole_quad and not bench and not loop_position and not fast_position and not in_sgprs"
+	    python -m pytest tests/test_host_logic.py tests/test_target_host.py tests/test_views_host.py tests/test_feedback_plan_host.py -q -m "not gpu" -k "not whole_quad and not bench and not loop_position and not fast_position and not in_sgprs"
 
 clean:
 	rm -f godot_atmosphere_shader_amd/libatmo_hip*.so oracle/*.so tools/valu_peak

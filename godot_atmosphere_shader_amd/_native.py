@@ -29,7 +29,7 @@ DEBUG_SYMBOLS = (
     "atmo_set_lane_split", "atmo_debug_motion_px", "atmo_get_feedback_stats", "atmo_set_timing", "atmo_get_timing", "atmo_host_layout_cubemap", "atmo_host_layout_shape",
     "atmo_host_layout_lut", "atmo_host_cubemap_mip", "atmo_read_texture_layout", "atmo_selftest_exact_math", "atmo_debug_marched_optical_depth", "atmo_debug_log2_cr", "atmo_kernel_name", "atmo_build_id",
     "atmo_get_host_wait_stats", "atmo_get_split_stats", "atmo_debug_create_host_only", "atmo_debug_frame_constants", "atmo_debug_proxy_launch_rect",
-    "atmo_debug_store_target", "atmo_debug_views_layout", "atmo_debug_tile_order", "atmo_debug_heavy_tile_count",
+    "atmo_debug_store_target", "atmo_debug_views_layout", "atmo_debug_tile_order", "atmo_debug_heavy_tile_count", "atmo_debug_feedback_plan",
 )
 # every symbol include/atmo_scene.h declares: drawing several atmospheres into one frame (the far-mode BoxMesh draw)
 SCENE_SYMBOLS = ("atmo_render_proxy", "atmo_render_proxy_composite")
@@ -84,6 +84,22 @@ class AtmoViewTarget(C.Structure):
         ("frame", AtmoFrame),
         ("depth_dev", C.c_void_p),
         ("target", AtmoTarget),
+    ]
+
+
+class AtmoFeedbackPlanIn(C.Structure):   # include/atmo_debug.h
+    _fields_ = [
+        ("fb_period", C.c_uint32), ("moving_period", C.c_uint32), ("reach_scale", C.c_float), ("instream", C.c_int32), ("axis_windows", C.c_int32),
+        ("cloud_steps", C.c_int32), ("flags", C.c_int32), ("tile_h", C.c_int32), ("batch", C.c_int32), ("n", C.c_uint32), ("last_record", C.c_uint32),
+        ("pending", C.c_int32), ("active", C.c_int32), ("order_born", C.c_uint32), ("order_reach_px", C.c_float), ("is_last_n", C.c_uint32),
+        ("motion_px", C.c_float), ("sil_px", C.c_float * 2),
+    ]
+
+
+class AtmoFeedbackPlanOut(C.Structure):   # include/atmo_debug.h
+    _fields_ = [
+        ("order", C.c_int32), ("record", C.c_int32), ("sort_side", C.c_int32), ("sort_instream", C.c_int32), ("dil_rx", C.c_int32), ("dil_ry", C.c_int32),
+        ("reach_px", C.c_float), ("invalidate_active", C.c_int32),
     ]
 
 
@@ -168,6 +184,7 @@ def load() -> C.CDLL:
         "atmo_render_views_target": (ip, [vp, C.POINTER(AtmoViewTarget), ip, ip, vp]),
         "atmo_debug_tile_order": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, C.POINTER(ip)]),
         "atmo_debug_heavy_tile_count": (ip, [vp, ip, ip, C.c_float, C.c_float, ip]),
+        "atmo_debug_feedback_plan": (ip, [C.POINTER(AtmoFeedbackPlanIn), C.POINTER(AtmoFeedbackPlanOut)]),
     }
     # ATMO_HIP_LIB names an A/B build (tools/ab_build_commit.sh: possibly an OLDER commit's library): entry points it lacks are skipped
     # (callers of those guard with hasattr) and its ABI version is not held against it.  The in-tree library must match exactly.

@@ -13,6 +13,7 @@
 #include "../../include/atmo_views_target.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
+#include "atmo_feedback_plan.h"
 
 #include <array>
 #include <cmath>
@@ -161,6 +162,7 @@ struct AtmoContext {
         int active = -1;               // order[active] is complete and in use; -1: row-major order
         int write = 0;                 // order[write] is what the next / pending sort writes
         bool pending = false;          // a sort is in flight on fb_stream
+        bool drop_pending = false;     // (view batches) the sort in flight was recorded before a camera move: not to be used
         hipEvent_t ev_draw = nullptr, ev_order[2] = {nullptr, nullptr};
         unsigned long long last_use = 0;
         bool dirty = false;            // released by atmo_set_tile_feedback with work possibly in flight: quiesced when the slot is taken again
@@ -239,11 +241,11 @@ struct AtmoContext {
     // ... and their ONE feedback state, separate from fb[] (it never recycles those), keyed by the batch's signature: stream (views_fb.draw_stream),
     // kernel family, n_views and each view's grid.  Of FeedbackState it uses the cost buffer, the two orders, the events and the counters.
     FeedbackState views_fb;
-    int views_key_flags = -1, views_key_n = 0, views_key_grid[8][2] = {{0}};
-    AtmoFrame views_prev[8];                  // each view's previous frame: its screen-space motion (feedback_motion_px)
-    float views_motion_px[8] = {0};
-    bool views_have_prev = false;
-    bool views_drop_pending = false;          // the sort in flight was recorded before a camera move: not to be used
+    struct ViewsFeedbackKey {
+        int flags = -1, n = 0, grid[8][2] = {{0}};   // the signature (with views_fb.draw_stream)
+        AtmoFrame prev[8];                    // each view's previous frame: its screen-space motion (feedback_motion_px)
+        float motion_px[8] = {0};
+    } views_key;                              // (views_fb.have_prev: prev[] holds the last batch's frames)
     int timing = 0;          // 0 off; k >= 1: bracket every k-th launch with HIP events
     int launch_counter = 0;
     int timed_launches = 0;
@@ -268,6 +270,8 @@ int hip_fail(AtmoContext *ctx, hipError_t e, const char *what) {
         hipError_t e_ = (call);                              \
         if (e_ != hipSuccess) return hip_fail(ctx, e_, #call); \
     } while (0)
+
+#define ATMO_TRY(call) do { const int rc_ = (call); if (rc_ != ATMO_OK) return rc_; } while (0)   // the same for a call that returns ATMO_*
 
 int dev_alloc(AtmoContext *ctx, DeviceBuffer &b, size_t bytes) {
     if (b.ptr && b.bytes == bytes) return ATMO_OK;
@@ -586,8 +590,10 @@ const AtmoFrame *draw_frame(const AtmoContext *ctx, const AtmoFrame *frame, Atmo
     fixed.inv_view_matrix[14] *= -1.0f;
     return &fixed;
 }
-// The launch constants of a draw of `frame` (as draw_frame returns it): fill_consts, and the composite's addressing
-void draw_consts(const AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, bool composite, atmo::RenderConsts &rc) {
+// The launch constants of a draw of `frame` (as draw_frame returns it): fill_consts, the composite's addressing, a float target's row pitch in pixels
+// (pitch_px > 0), a packed target (the KF_TARGET kernels address TargetConsts::pixels, rows pitch_bytes apart)
+void draw_consts(const AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, bool composite, int pitch_px, bool packed,
+                 atmo::RenderConsts &rc) {
     fill_consts(ctx, frame, depth_dev, rgba_dev, rc);
     if (composite) {  // the target is the whole scene colour buffer, addressed by absolute pixel
         rc.out_pitch = frame->viewport_w;
@@ -596,6 +602,8 @@ void draw_consts(const AtmoContext *ctx, const AtmoFrame *frame, const float *de
         rc.composite = 1;
         rc.store_discards = 0;
     }
+    if (pitch_px > 0) rc.out_pitch = pitch_px;
+    if (packed) rc.out = nullptr;
 }
 // The kernel family and launch shape of a draw (launch_shape), refused where the context demands a sampler it cannot have; under the declared sampler
 // (*lod) the launch grid starts on an even pixel: draw_grid_origin
@@ -613,8 +621,6 @@ void draw_grid_origin(const AtmoFrame *frame, bool lod, atmo::RenderConsts &rc) 
         rc.gy0 = frame->y0 & ~1;
     }
 }
-constexpr float FB_STILL_PX = 0.5f;   // pixels per frame below which a camera counts as still (tile feedback)
-
 // Reads back finished timing pairs.  only_completed: keep the pairs whose second event has not happened yet
 // (used to bound `pending` without blocking); otherwise wait for every pair.
 void drain_timing(AtmoContext *ctx, bool only_completed = false) {
@@ -764,16 +770,60 @@ int order_after_draws_on(AtmoContext *ctx, hipStream_t waiter, hipStream_t drawn
 // order) once work enqueued on `new_stream` from now on runs: stream-side waits, the host does not block.  Only needed when the slot is
 // recycled for another key.  (A buffer that has to GROW is freed, and hipFree waits for the device by itself.)
 int feedback_quiesce(AtmoContext *ctx, AtmoContext::FeedbackState &f, hipStream_t new_stream) {
-    if (f.pending && ctx->fb_stream) {
-        const int rc0 = order_after_stream(ctx, new_stream, ctx->fb_stream);
-        if (rc0 != ATMO_OK) return rc0;
-    }
-    if ((f.n > 0 || f.dirty) && f.draw_stream != new_stream) {
-        const int rc0 = order_after_draws_on(ctx, new_stream, f.draw_stream);
-        if (rc0 != ATMO_OK) return rc0;
-    }
+    if (f.pending && ctx->fb_stream) ATMO_TRY(order_after_stream(ctx, new_stream, ctx->fb_stream));
+    if ((f.n > 0 || f.dirty) && f.draw_stream != new_stream) ATMO_TRY(order_after_draws_on(ctx, new_stream, f.draw_stream));
     f.pending = false;
     f.dirty = false;
+    return ATMO_OK;
+}
+
+// Is `s` recording into a HIP graph?  (A failed query counts as yes: nothing that a capture forbids is done.)
+bool stream_is_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
+}
+
+// Starts feedback state `f` over for a key of n_tiles tiles drawn on stream s -- what a single draw's state (feedback_state) and the batches'
+// (views_feedback_state) share: the sort stream and its scratch on first use, `f` ordered behind whatever used its buffers before (on the device),
+// the buffers, the events, the cost map cleared on the draw stream, the counters reset.  draw_tables: also what only single draws use -- the dilation
+// scratch, the in-stream order and the heavy-tile split's tables.
+int feedback_state_start(AtmoContext *ctx, AtmoContext::FeedbackState &f, hipStream_t s, size_t n_tiles, bool draw_tables) {
+    if (!ctx->fb_stream) {
+        int lo = 0, hi = 0;  // numerically lower = higher priority
+        HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
+        HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->fb_stream, hipStreamNonBlocking, hi));
+    }
+    ATMO_TRY(dev_reserve(ctx, ctx->fb_scratch, atmo::tile_order_scratch_bytes()));
+    // a recycled slot, one released by atmo_set_tile_feedback while its draws / sort may still have been in flight, a re-keyed batch state: ordered
+    // behind whatever used it before (nothing is enqueued for a slot that was never used); growing a buffer frees it, which waits for the device
+    ATMO_TRY(feedback_quiesce(ctx, f, s));
+    const size_t bytes = n_tiles * sizeof(uint32_t);
+    int rc1 = dev_reserve(ctx, f.cost, bytes);
+    for (int k = 0; k < 2 && rc1 == ATMO_OK; ++k) rc1 = dev_reserve(ctx, f.order[k], bytes);
+    if (draw_tables) {
+        for (int k = 0; k < 2 && rc1 == ATMO_OK; ++k) rc1 = dev_reserve(ctx, f.dil[k], bytes);
+        if (rc1 == ATMO_OK) rc1 = dev_reserve(ctx, f.is_order, bytes);
+        if (rc1 == ATMO_OK) rc1 = dev_reserve(ctx, f.is_scratch, atmo::tile_order_scratch_bytes());
+        for (int k = 0; k < 2 && rc1 == ATMO_OK; ++k) rc1 = dev_reserve(ctx, f.order2[k], 2 * bytes);
+        if (rc1 == ATMO_OK) rc1 = dev_reserve(ctx, f.is_order2, 2 * bytes);
+        if (rc1 == ATMO_OK && !f.class_totals) {
+            void *p = nullptr;
+            HIP_TRY(ctx, hipHostMalloc(&p, 3 * atmo::TILE_ORDER_CLASSES * sizeof(uint32_t), hipHostMallocDefault));
+            f.class_totals = (uint32_t *)p;
+        }
+        if (rc1 == ATMO_OK) std::memset(f.class_totals, 0, 3 * atmo::TILE_ORDER_CLASSES * sizeof(uint32_t));
+    }
+    if (rc1 != ATMO_OK) { f.used = false; return rc1; }
+    if (!f.ev_draw) {
+        HIP_TRY(ctx, hipEventCreateWithFlags(&f.ev_draw, hipEventDisableTiming));
+        for (int k = 0; k < 2; ++k) HIP_TRY(ctx, hipEventCreateWithFlags(&f.ev_order[k], hipEventDisableTiming));
+    }
+    HIP_TRY(ctx, hipMemsetAsync(f.cost.ptr, 0, bytes, s));
+    f.used = true;
+    f.draw_stream = s;
+    f.n = 0; f.last_record = 0; f.is_last_n = ~0u;
+    f.active = -1; f.write = 0; f.pending = false; f.drop_pending = false;
+    f.have_prev = false; f.motion_px = 0.0f;
     return ATMO_OK;
 }
 
@@ -794,61 +844,116 @@ int feedback_state(AtmoContext *ctx, int gx, int gy, int split, hipStream_t s, A
         if (!f.used) { if (!slot) slot = &f; }
         else if (!lru || f.last_use < lru->last_use) lru = &f;
     }
-    if (!ctx->fb_stream) {
-        int lo = 0, hi = 0;  // numerically lower = higher priority
-        HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->fb_stream, hipStreamNonBlocking, hi));
-        const int rc0 = dev_reserve(ctx, ctx->fb_scratch, atmo::tile_order_scratch_bytes());
-        if (rc0 != ATMO_OK) return rc0;
-    }
     if (!slot) {
         if (ctx->fb_budget <= 0) return ATMO_OK;  // no feedback for this draw
         ctx->fb_budget -= 1;
         ctx->fb_recycled += 1;
         slot = lru;
-        const int rc0 = feedback_quiesce(ctx, *slot, s);
-        if (rc0 != ATMO_OK) return rc0;
     }
-    if (slot->dirty) {  // released by atmo_set_tile_feedback while its draws / sort may still have been in flight
-        const int rc0 = feedback_quiesce(ctx, *slot, s);
-        if (rc0 != ATMO_OK) return rc0;
-    }
-    AtmoContext::FeedbackState &f = *slot;
-    const size_t bytes = (size_t)gx * gy * sizeof(uint32_t);
-    // (a slot taken here is ordered behind whatever used it before; growing a buffer frees it, which waits for the device)
-    int rc1 = dev_reserve(ctx, f.cost, bytes);
-    for (int k = 0; k < 2 && rc1 == ATMO_OK; ++k) rc1 = dev_reserve(ctx, f.order[k], bytes);
-    for (int k = 0; k < 2 && rc1 == ATMO_OK; ++k) rc1 = dev_reserve(ctx, f.dil[k], bytes);
-    if (rc1 == ATMO_OK) rc1 = dev_reserve(ctx, f.is_order, bytes);
-    if (rc1 == ATMO_OK) rc1 = dev_reserve(ctx, f.is_scratch, atmo::tile_order_scratch_bytes());
-    for (int k = 0; k < 2 && rc1 == ATMO_OK; ++k) rc1 = dev_reserve(ctx, f.order2[k], 2 * bytes);
-    if (rc1 == ATMO_OK) rc1 = dev_reserve(ctx, f.is_order2, 2 * bytes);
-    if (rc1 == ATMO_OK && !f.class_totals) {
-        void *p = nullptr;
-        HIP_TRY(ctx, hipHostMalloc(&p, 3 * atmo::TILE_ORDER_CLASSES * sizeof(uint32_t), hipHostMallocDefault));
-        f.class_totals = (uint32_t *)p;
-    }
-    if (rc1 == ATMO_OK) std::memset(f.class_totals, 0, 3 * atmo::TILE_ORDER_CLASSES * sizeof(uint32_t));
-    if (rc1 != ATMO_OK) { f.used = false; return rc1; }
-    if (!f.ev_draw) {
-        HIP_TRY(ctx, hipEventCreateWithFlags(&f.ev_draw, hipEventDisableTiming));
-        for (int k = 0; k < 2; ++k) HIP_TRY(ctx, hipEventCreateWithFlags(&f.ev_order[k], hipEventDisableTiming));
-    }
-    HIP_TRY(ctx, hipMemsetAsync(f.cost.ptr, 0, bytes, s));
-    f.used = true;
-    f.tiles_x = gx; f.tiles_y = gy; f.split = split;
-    f.draw_stream = s;
-    f.n = 0;
-    f.last_record = 0;
-    f.active = -1;
-    f.write = 0;
-    f.pending = false;
-    f.have_prev = false;
-    f.motion_px = 0.0f;
-    f.is_last_n = ~0u;
-    f.last_use = ctx->fb_clock;
-    *out = &f;
+    ATMO_TRY(feedback_state_start(ctx, *slot, s, (size_t)gx * gy, true));
+    slot->tiles_x = gx; slot->tiles_y = gy; slot->split = split;
+    slot->last_use = ctx->fb_clock;
+    *out = slot;
     return ATMO_OK;
+}
+
+// The poll of a pending side-stream sort: once a host-side event query says it is complete, its order becomes the one in use -- no stream-side wait
+// needed, and no draw ever waits for a sort.  drop: (view batches) the picture has moved on since that sort's costs were recorded, its order is not
+// to be used when it arrives.
+void feedback_poll(AtmoContext::FeedbackState &f, bool drop) {
+    if (!f.pending) return;
+    if (drop) f.drop_pending = true;
+    if (hipEventQuery(f.ev_order[f.write]) == hipSuccess) {
+        if (!f.drop_pending) { f.active = f.write; f.write ^= 1; }
+        f.pending = false; f.drop_pending = false;
+    } else (void)hipGetLastError();  // hipErrorNotReady is an answer, not an error: keep it out of the launch checks that follow
+}
+
+// The policy's input for a draw of state `f` as it stands (after the motion update and feedback_poll): feedback_plan, csrc/atmo_feedback_plan.h
+AtmoFeedbackPlanIn feedback_plan_input(const AtmoContext *ctx, const AtmoContext::FeedbackState &f, int flags, int tile_h, bool batch, float motion_px) {
+    const int a = f.active;
+    return {ctx->fb_period, ctx->moving_period, ctx->env_reach_scale, ctx->instream, ctx->fb_axis_windows, ctx->cloud_steps, flags, tile_h, batch ? 1 : 0,
+            f.n, f.last_record, f.pending ? 1 : 0, a, a >= 0 ? f.order_born[a] : 0u, a >= 0 ? f.order_reach_px[a] : 0.0f, f.is_last_n,
+            motion_px, {f.sil_px[0], f.sil_px[1]}};   // (in the order of include/atmo_debug.h)
+}
+
+// What `plan` names of state `f`: returns the order the draw uses (null: row-major) with its lane-split twin and class totals (a batch has neither: null),
+// *cost = the map a recording draw writes.  (Side stream: the host has seen this sort's event; in-stream: read without waiting -- at worst last frame's.)
+const uint32_t *feedback_apply(AtmoContext *ctx, AtmoContext::FeedbackState &f, const AtmoFeedbackPlanOut &plan, uint32_t **cost, const uint32_t **order2,
+                               const uint32_t **class_totals) {
+    const uint32_t *order = nullptr;
+    if (plan.order != atmo::FB_ORDER_NONE) {
+        const int k = plan.order == atmo::FB_ORDER_INSTREAM ? 2 : f.active;
+        order = (const uint32_t *)(k == 2 ? f.is_order : f.order[k]).ptr;
+        if (order2) *order2 = (const uint32_t *)(k == 2 ? f.is_order2 : f.order2[k]).ptr;
+        if (class_totals) *class_totals = f.class_totals + k * atmo::TILE_ORDER_CLASSES;
+        ctx->fb_ordered_draws += 1;
+    }
+    if (plan.record) *cost = (uint32_t *)f.cost.ptr;
+    if (plan.invalidate_active) f.active = -1;
+    return order;
+}
+
+// Enqueues the sort of f.cost (gx x gy tiles, dilated by rx x ry) into slot k of `f` -- 0, 1: order[k], the side-stream sort's; 2: is_order, the
+// in-stream sort's; with the slot's order2 and class totals where the state has them (a batch state has neither, nor a dilation scratch: null) --
+// on stream s with the block-histogram scratch x.  The sort also clears the costs for the next recording.
+int feedback_sort(AtmoContext *ctx, AtmoContext::FeedbackState &f, int k, int gx, int gy, int rx, int ry, hipStream_t s, const DeviceBuffer &x) {
+    const DeviceBuffer &order = k == 2 ? f.is_order : f.order[k], &order2 = k == 2 ? f.is_order2 : f.order2[k];
+    HIP_TRY(ctx, atmo::launch_tile_order((uint32_t *)f.cost.ptr, (uint32_t *)order.ptr, gx, gy, rx, ry, (uint32_t *)f.dil[0].ptr, (uint32_t *)f.dil[1].ptr,
+                                         (uint32_t *)x.ptr, s, (uint32_t *)order2.ptr, f.class_totals ? f.class_totals + k * atmo::TILE_ORDER_CLASSES : nullptr));
+    ctx->fb_sorts += 1;
+    return ATMO_OK;
+}
+
+// The side-stream sort behind a recording draw on `s`: as soon as that draw is done, beside the draws that follow.  order[write] was last read by
+// draws enqueued on `s` before this one, so the event orders the write too.
+int feedback_sort_side(AtmoContext *ctx, AtmoContext::FeedbackState &f, int gx, int gy, const AtmoFeedbackPlanOut &plan, hipStream_t s) {
+    HIP_TRY(ctx, hipEventRecord(f.ev_draw, s));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->fb_stream, f.ev_draw, 0));
+    ATMO_TRY(feedback_sort(ctx, f, f.write, gx, gy, plan.dil_rx, plan.dil_ry, ctx->fb_stream, ctx->fb_scratch));
+    f.order_reach_px[f.write] = plan.reach_px; f.order_born[f.write] = f.n;
+    HIP_TRY(ctx, hipEventRecord(f.ev_order[f.write], ctx->fb_stream));
+    f.pending = true; f.drop_pending = false; f.last_record = f.n;
+    return ATMO_OK;
+}
+
+// Kernel timing (atmo_set_timing): a pair of HIP events around every k-th counted launch, owned by the bracket until timing_end hands it to
+// ctx->pending (no error path leaks it).  timing_open decides and creates; timing_begin, timing_end record where the caller wants the bracket.
+struct TimingBracket {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool timed = false;
+    ~TimingBracket() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+int timing_open(AtmoContext *ctx, TimingBracket &t) {
+    t.timed = ctx->timing > 0 && (ctx->launch_counter % ctx->timing) == 0;
+    if (!t.timed) return ATMO_OK;
+    if (ctx->pending.size() >= 64) drain_timing(ctx, /*only_completed=*/true);  // a long loop with timing left on stays bounded
+    HIP_TRY(ctx, hipEventCreate(&t.e0));
+    HIP_TRY(ctx, hipEventCreate(&t.e1));
+    return ATMO_OK;
+}
+int timing_begin(AtmoContext *ctx, TimingBracket &t, hipStream_t s) {
+    if (t.timed) HIP_TRY(ctx, hipEventRecord(t.e0, s));
+    return ATMO_OK;
+}
+int timing_end(AtmoContext *ctx, TimingBracket &t, hipStream_t s) {
+    if (!t.timed) return ATMO_OK;
+    HIP_TRY(ctx, hipEventRecord(t.e1, s));
+    ctx->pending.emplace_back(t.e0, t.e1);
+    t.e0 = t.e1 = nullptr;  // ownership moved
+    return ATMO_OK;
+}
+
+// Does this family have a lane-split form whose frames are bit-identical to the one-lane kernel's?  Only the two BASELINE cloud kernels under the
+// declared sampler (atmo_kernels.hip: march_clouds<.., SPLIT = 2, LOD>); by itself the library uses the raymarched-light kernel's only (the kernel
+// without it gains only from eight GPUs on and loses 21 % at two -- profiles/round5/band_balance.txt -- so it takes part only when forced,
+// ATMO_HEAVY_SPLIT=2).
+bool two_lane_form(const AtmoContext *ctx, int flags) {
+    const int lod_cloud = atmo::KF_CUBE_LOD | atmo::KF_PRECISE | atmo::KF_CLOUDS;
+    return ctx->heavy_split == 2 ? (flags & ~atmo::KF_CLOUD_LIGHT_RM) == lod_cloud : flags == (lod_cloud | atmo::KF_CLOUD_LIGHT_RM);
 }
 
 }  // namespace
@@ -900,7 +1005,7 @@ static void init_variant(AtmoContext *ctx, int device, int variant, int view_ste
 
 int atmo_create(int device, int variant, int view_steps, int cloud_steps, int light_mode, int light_steps,
                 AtmoContext **out) {
-    { const int rc0 = check_create_args(variant, view_steps, cloud_steps, light_mode, light_steps, out); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(check_create_args(variant, view_steps, cloud_steps, light_mode, light_steps, out));
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n <= 0)
@@ -981,7 +1086,8 @@ int atmo_destroy(AtmoContext *ctx) {
         (void)hipStreamSynchronize(ctx->split_stream);
         (void)hipStreamDestroy(ctx->split_stream);
     }
-    for (AtmoContext::FeedbackState &f : ctx->fb) {
+    for (int i = 0; i <= AtmoContext::FB_SLOTS; ++i) {   // the single draws' states and the batches' (which holds fewer buffers: the others are null)
+        AtmoContext::FeedbackState &f = i < AtmoContext::FB_SLOTS ? ctx->fb[i] : ctx->views_fb;
         if (f.ev_draw) (void)hipEventDestroy(f.ev_draw);
         for (int k = 0; k < 2; ++k) {
             if (f.ev_order[k]) (void)hipEventDestroy(f.ev_order[k]);
@@ -993,15 +1099,6 @@ int atmo_destroy(AtmoContext *ctx) {
         dev_free(f.is_order2);
         for (int k = 0; k < 2; ++k) dev_free(f.order2[k]);
         if (f.class_totals) (void)hipHostFree(f.class_totals);
-        dev_free(f.cost);
-    }
-    {
-        AtmoContext::FeedbackState &f = ctx->views_fb;
-        if (f.ev_draw) (void)hipEventDestroy(f.ev_draw);
-        for (int k = 0; k < 2; ++k) {
-            if (f.ev_order[k]) (void)hipEventDestroy(f.ev_order[k]);
-            dev_free(f.order[k]);
-        }
         dev_free(f.cost);
     }
     for (AtmoContext::ViewsSlot &v : ctx->views_ring) {
@@ -1097,10 +1194,7 @@ static int tex_begin_update(AtmoContext *ctx, hipStream_t s) {
         ctx->device_syncs += 1;
         HIP_TRY(ctx, hipDeviceSynchronize());
     } else {
-        for (const AtmoContext::DrawStream &d : ctx->draw_streams) {
-            const int rc0 = order_after_draws(ctx, s, d);
-            if (rc0 != ATMO_OK) return rc0;
-        }
+        for (const AtmoContext::DrawStream &d : ctx->draw_streams) ATMO_TRY(order_after_draws(ctx, s, d));
     }
     // every earlier draw of this context is in front of the update now; later ones wait for tex_event (tex_order).  The streams stay
     // remembered with their markers: the feedback states and tile-list copies that drew on them are handed on behind those markers
@@ -1146,14 +1240,13 @@ int atmo_set_texture(AtmoContext *ctx, const char *name, int kind, int w, int h,
     }
     if (std::strcmp(name, "u_blue_noise_texture") == 0) {
         if (!data) {
-            const int rc0 = tex_begin_update(ctx, s);
-            if (rc0 != ATMO_OK) return rc0;
+            ATMO_TRY(tex_begin_update(ctx, s));
             HIP_TRY(ctx, hipMemsetAsync(ctx->blue.ptr, 0, 256 * 256, s));
             return tex_updated(ctx, s);
         }
         if (kind != ATMO_TEX_2D_R8) return fail(ctx, ATMO_E_ARG, "u_blue_noise_texture must be ATMO_TEX_2D_R8");
         if (w != 256 || h != 256) return fail(ctx, ATMO_E_ARG, "u_blue_noise_texture must be 256x256 (indexed & 0xff, main:169)");
-        { const int rc0 = tex_begin_update(ctx, s); if (rc0 != ATMO_OK) return rc0; }
+        ATMO_TRY(tex_begin_update(ctx, s));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->blue.ptr, data, 256 * 256, ck, s));
         return tex_updated(ctx, s);
     }
@@ -1259,7 +1352,7 @@ int atmo_read_texture_layout(AtmoContext *ctx, const char *name, void *out_host,
     if (!b->ptr) return ATMO_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    { const int rc0 = tex_order(ctx, s); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(tex_order(ctx, s));
     HIP_TRY(ctx, hipMemcpyAsync(out_host, b->ptr, b->bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     return ATMO_OK;
@@ -1348,7 +1441,7 @@ int atmo_bake_optical_depth(AtmoContext *ctx, void *stream) {
     if (!ctx) return ATMO_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int w = 256, h = 256;  // optical_depth_baker.gd:24
-    { const int rc0 = tex_begin_update(ctx, (hipStream_t)stream); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(tex_begin_update(ctx, (hipStream_t)stream));
     if (ctx->lut_w != w || ctx->lut_h != h || !ctx->lut.ptr || !ctx->lut4.ptr) {
         const int rc = lut_alloc(ctx, w, h);  // a size change waits for the device (hipFree)
         if (rc != ATMO_OK) return rc;
@@ -1372,7 +1465,7 @@ int atmo_read_optical_depth(AtmoContext *ctx, float *lut_host, uint8_t *rgba8_ho
     if (capacity_texels < n) return fail(ctx, ATMO_E_ARG, "atmo_read_optical_depth: buffer too small (atmo_get_texture_size gives w x h)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    { const int rc0 = tex_order(ctx, s); if (rc0 != ATMO_OK) return rc0; }  // a bake on another stream
+    ATMO_TRY(tex_order(ctx, s));  // a bake on another stream
     std::vector<float> tmp, padded((size_t)(ctx->lut_w + 2) * (ctx->lut_h + 2));
     float *dst = lut_host;
     if (!dst) { tmp.resize(n); dst = tmp.data(); }
@@ -1525,8 +1618,7 @@ int atmo_measure_tile_costs(AtmoContext *ctx, const AtmoFrame *frame, const floa
     const size_t bytes = (size_t)gx * gy * sizeof(uint32_t);
     hipStream_t s = (hipStream_t)stream;
     if (ctx->measure_buf.bytes < bytes) {  // grow-only; every earlier measurement waited for its own copy-out before it returned (below)
-        const int rc0 = dev_alloc(ctx, ctx->measure_buf, bytes);
-        if (rc0 != ATMO_OK) return rc0;
+        ATMO_TRY(dev_alloc(ctx, ctx->measure_buf, bytes));
     }
     uint32_t *d = (uint32_t *)ctx->measure_buf.ptr;
     hipError_t e = hipMemsetAsync(d, 0, bytes, s);
@@ -1572,9 +1664,7 @@ static int note_draw_stream(AtmoContext *ctx, hipStream_t s, hipEvent_t *marker)
     ds->last_use = ++ctx->draw_stream_clock;
     const bool home = s == ctx->tex_stream;   // the stream of the last texture update (the null stream before the first)
     if (ctx->draw_events && (!home || ctx->draw_events == 2)) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        const bool capturing = hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
-        if (!capturing) {   // (a draw inside a graph capture gets no marker: replays are the caller's to order)
+        if (!stream_is_capturing(s)) {   // (a draw inside a graph capture gets no marker: replays are the caller's to order)
             if (!ds->last_draw) HIP_TRY(ctx, hipEventCreateWithFlags(&ds->last_draw, hipEventDisableTiming));
             HIP_TRY(ctx, hipEventRecord(ds->last_draw, s));
             ds->recorded = true;
@@ -1584,162 +1674,151 @@ static int note_draw_stream(AtmoContext *ctx, hipStream_t s, hipEvent_t *marker)
     return ATMO_OK;
 }
 
+// Every draw's bookkeeping: what atmo_kernel_name reports, the accepted launches atmo_set_timing counts (proxy draws: not timed, not counted), the marker
+static int finish_draw(AtmoContext *ctx, hipStream_t s, int family, int split, bool counted, hipEvent_t *marker) {
+    ctx->last_flags = family;
+    ctx->last_split = split;
+    if (counted) ctx->launch_counter += 1;
+    return note_draw_stream(ctx, s, marker);
+}
+
+// A launch of a single draw: the float kernels, or (tc) their packed-target twins
+static hipError_t launch_draw(const atmo::TargetConsts *tc, int flags, int split, const atmo::RenderConsts &rc, hipStream_t s, int blocks) {
+    return tc ? atmo::launch_render_target(flags, split, rc, *tc, s, blocks) : atmo::launch_render(flags, split, rc, s, blocks);
+}
+
+// A single draw's feedback state (null where feedback_state leaves it null) with the camera's motion taken in and the pending sort polled
+static int feedback_begin(AtmoContext *ctx, const AtmoFrame *frame, int gx, int gy, int split, hipStream_t s, AtmoContext::FeedbackState **out) {
+    ATMO_TRY(feedback_state(ctx, gx, gy, split, s, out));
+    AtmoContext::FeedbackState *fb = *out;
+    if (!fb) return ATMO_OK;
+    if (fb->have_prev) {
+        float sil[2] = {0.0f, 0.0f};
+        const float m = feedback_motion_px(*frame, fb->prev_frame, ctx->p.u_planet_radius + ctx->p.u_atmosphere_height,
+                                           (ctx->flags & atmo::KF_CLOUDS) != 0, sil);
+        fb->motion_px = std::fmax(m, 0.75f * fb->motion_px);  // peak hold: one still frame does not end a camera move
+        if (fb->motion_px < 0.01f) fb->motion_px = 0.0f;
+        for (int k = 0; k < 2; ++k) fb->sil_px[k] = std::fmax(sil[k], 0.75f * fb->sil_px[k]);
+    }
+    fb->prev_frame = *frame;
+    fb->have_prev = true;
+    feedback_poll(*fb, false);
+    return ATMO_OK;
+}
+
+// atmo_render_tiles: rc.tile_order = the bounded copy of the caller's tile list; *order2 = the lane-split launch's list of its leading *n_heavy tiles.
+// The list is the caller's: an index beyond the grid must shade nothing (include/atmo.h) -- and must not be turned into addresses.  The
+// render kernels' preamble is not the place (one scalar compare-and-branch there costs the headline kernel 10 %:
+// profiles/round5/ab_tile_bound.txt), so a copy of the list is bounded on the device in front of the draw: out-of-range entries
+// become the first tile BELOW the viewport, whose lanes all leave at the kernel's own bounds test.  One copy per draw stream
+// (stream order protects it from the next tile-list draw on that stream); a fifth stream takes over the least recently used copy,
+// ordered behind its last reader on the device.
+static int bound_tile_list(AtmoContext *ctx, const AtmoFrame *frame, atmo::RenderConsts &rc, hipStream_t s, int flags, int split, int gx, int gy,
+                           const uint32_t *tiles_dev, int n_tiles, int *n_heavy, const uint32_t **order2) {
+    AtmoContext::TileListBuf *tl = nullptr;
+    ctx->tile_list_clock += 1;
+    for (AtmoContext::TileListBuf &t : ctx->tile_lists) if (!tl && t.used && t.stream == s) tl = &t;
+    for (AtmoContext::TileListBuf &t : ctx->tile_lists) if (!tl && !t.used) tl = &t;
+    if (!tl) {
+        tl = &ctx->tile_lists[0];
+        for (AtmoContext::TileListBuf &t : ctx->tile_lists) if (t.last_use < tl->last_use) tl = &t;
+        ATMO_TRY(order_after_draws_on(ctx, s, tl->stream));  // its last reader: a draw on that stream
+    }
+    tl->used = true;
+    tl->stream = s;
+    tl->last_use = ctx->tile_list_clock;
+    // the leading n_heavy tiles on two lanes per ray (atmo_render_tiles_split): only where that form exists and is the same bits (as for whole frames)
+    if (split != 1 || !two_lane_form(ctx, flags) || !ctx->heavy_split) *n_heavy = 0;
+    ATMO_TRY(dev_reserve(ctx, tl->buf, ((size_t)n_tiles + 2 * (size_t)*n_heavy) * sizeof(uint32_t)));
+    int tw = 0, th = 0;
+    atmo::render_tile_size(split, &tw, &th);                                         // pixels per tile of this launch
+    const uint32_t below = (uint32_t)((frame->viewport_h - rc.gy0 + th - 1) / th);   // the first tile row that starts below the viewport's last row
+    const int th2 = th / 2 > 0 ? th / 2 : 1;
+    const uint32_t below2 = (uint32_t)((frame->viewport_h - rc.gy0 + th2 - 1) / th2);
+    uint32_t *list2 = (uint32_t *)tl->buf.ptr + n_tiles;
+    HIP_TRY(ctx, atmo::launch_tile_list_bound(tiles_dev, (uint32_t *)tl->buf.ptr, n_tiles, (uint32_t)gx * (uint32_t)gy, below * (uint32_t)gx, s,
+                                              list2, *n_heavy, gx, below2 * (uint32_t)gx));
+    rc.tile_order = (const uint32_t *)tl->buf.ptr;
+    if (*n_heavy > 0) *order2 = list2;
+    return ATMO_OK;
+}
+
+// Heavy tiles on two lanes per ray, beside the rest of the draw (round 5; a family with two_lane_form): the leading `heavy` tiles of the order on the
+// split stream, the other total_tiles - heavy on `s`, forked and joined on the device.
+// Measured (profiles/round5/ab_heavy_tile_split.txt): it pays where a draw is as long as its heaviest wavefront -- clouds_high_rm at
+// 1280x720 -28 %, from the limb -42..-44 % at 1280x720 and 1920x1080, the night side -33 % -- and costs 9 % where the draw is bound by
+// throughput (1920x1080 pose P_space, where the lane-split kernel on EVERY tile is 43 % slower; 3840x2160), which the trigger keeps out;
+// the kernel without raymarched light never gains (its heaviest wave is a fifth as long): not split unless forced (ATMO_HEAVY_SPLIT=2).
+static int launch_heavy_split(AtmoContext *ctx, const atmo::TargetConsts *tc, int flags, int split, atmo::RenderConsts &rc, hipStream_t s,
+                              const uint32_t *order2, int heavy, int total_tiles) {
+    if (!ctx->split_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->split_stream, hipStreamNonBlocking));
+    ATMO_TRY(order_after_stream(ctx, ctx->split_stream, s));   // fork: behind everything the draw is behind
+    atmo::RenderConsts rc2 = rc;
+    rc2.tile_order = order2;                       // two half-height tiles per heavy tile, heaviest first
+    rc2.cost_rows_halved = 1;                      // ... whose costs belong to the one-lane grid's tile (only this launch: ADVICE r5)
+    HIP_TRY(ctx, launch_draw(tc, flags, 2, rc2, ctx->split_stream, 2 * heavy));
+    if (total_tiles - heavy > 0) {
+        rc.tile_order += heavy;                    // the rest of the order, one lane per ray
+        HIP_TRY(ctx, launch_draw(tc, flags, split, rc, s, total_tiles - heavy));
+    }
+    ATMO_TRY(order_after_stream(ctx, s, ctx->split_stream));   // join
+    ctx->split_draws += 1;
+    ctx->split_tiles_last = (unsigned)heavy;
+    return ATMO_OK;
+}
+
 static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream, bool composite,
                        const uint32_t *tiles_dev, int n_tiles, int n_heavy, const atmo::TargetConsts *tc, int pitch_px) {
+    // 1. checks
     if (!ctx) return ATMO_E_ARG;
-    {
-        bool empty = false;
-        const int rc0 = check_frame(ctx, "atmo_render", frame, &empty);
-        if (rc0 != ATMO_OK) return rc0;
-        if (empty) return ATMO_OK;  // empty rect: nothing to shade
-    }
-    { const int rc0 = check_draw_pointers(ctx, "atmo_render", depth_dev, rgba_dev, !tc); if (rc0 != ATMO_OK) return rc0; }
-    { const int rc0 = check_draw_textures(ctx, "atmo_render"); if (rc0 != ATMO_OK) return rc0; }
+    bool empty = false;
+    ATMO_TRY(check_frame(ctx, "atmo_render", frame, &empty));
+    if (empty) return ATMO_OK;  // empty rect: nothing to shade
+    ATMO_TRY(check_draw_pointers(ctx, "atmo_render", depth_dev, rgba_dev, !tc));
+    ATMO_TRY(check_draw_textures(ctx, "atmo_render"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
+    // 2. constants
     atmo::RenderConsts rc;
     AtmoFrame fixed;
     frame = draw_frame(ctx, frame, fixed);
-    draw_consts(ctx, frame, depth_dev, rgba_dev, composite, rc);
-    if (pitch_px > 0) rc.out_pitch = pitch_px;
-    if (tc) rc.out = nullptr;   // the KF_TARGET kernels address tc->pixels, rows tc->pitch_bytes apart
-    // the launches of this draw: the float kernels, or their packed-target twins
-    auto launch = [tc](int lflags, int lsplit, const atmo::RenderConsts &lrc, hipStream_t ls, int blocks) {
-        return tc ? atmo::launch_render_target(lflags, lsplit, lrc, *tc, ls, blocks) : atmo::launch_render(lflags, lsplit, lrc, ls, blocks);
-    };
+    draw_consts(ctx, frame, depth_dev, rgba_dev, composite, pitch_px, tc != nullptr, rc);
     hipStream_t s = (hipStream_t)stream;
-    { const int rc0 = tex_order(ctx, s); if (rc0 != ATMO_OK) return rc0; }  // texture updated on another stream
+    ATMO_TRY(tex_order(ctx, s));  // texture updated on another stream
+
+    // 3. family and grid
     int split = 1, flags = 0;
     {   // the coverage cubemap's sampler: as declared (implicit LOD) when a mip chain is bound
         bool lod = false;
-        const int rc0 = draw_family(ctx, frame, &flags, &split, &lod);
-        if (rc0 != ATMO_OK) return rc0;
+        ATMO_TRY(draw_family(ctx, frame, &flags, &split, &lod));
         draw_grid_origin(frame, lod, rc);
     }
     int gx = 0, gy = 0;
     atmo::render_grid(rc, split, &gx, &gy);
     rc.tiles_x = gx;
+    const int tile_h = (rc.y1 - rc.y0 + gy - 1) / gy;  // pixel rows per tile of this launch (8, or 4 with two lanes per ray)
+
+    // 4. feedback state, motion and poll
     // default (-1): on for every variant since the sort no longer costs the draws anything (profiles/round2/ab_tile_feedback.txt)
     bool feedback = ctx->env_feedback >= 0 ? ctx->env_feedback != 0 : ctx->tile_feedback != 0;
     if (ctx->measure_cost) feedback = false;  // a measuring draw: plain row-major launch that records into the caller's buffer
     if (tiles_dev) feedback = false;          // a tile-list draw: the caller's order
     if (feedback && (long long)gx * gy < 512) feedback = false;  // tiny launches: nothing to schedule
     const bool geo_policy = feedback;   // (also inside a graph capture: the geometric order enqueues nothing of its own)
-    if (feedback) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) feedback = false;  // no side-stream work inside a graph
-    }
-    // Every fb_period-th draw records the wave durations per tile; a sort on the side stream turns them into the next
-    // order, which later draws pick up once a host-side event query says it is complete: no draw ever waits for a sort.
-    bool fb_record = false, fb_instream = false;
+    if (feedback && stream_is_capturing(s)) feedback = false;  // no side-stream work inside a graph
     AtmoContext::FeedbackState *fb = nullptr;
+    if (feedback) ATMO_TRY(feedback_begin(ctx, frame, gx, gy, split, s, &fb));
+
+    // 5. plan (csrc/atmo_feedback_plan.h), and the order it names
+    AtmoFeedbackPlanOut plan = {atmo::FB_ORDER_NONE, 0, 0, 0, 0, 0, 0.0f, 0};
     const uint32_t *order2 = nullptr, *class_totals = nullptr;   // of the order in use (heavy tiles on two lanes per ray)
-    if (feedback) {
-        const int rc1 = feedback_state(ctx, gx, gy, split, s, &fb);
-        if (rc1 != ATMO_OK) return rc1;
-    }
-    // A moving camera (planet_atmosphere.gd:285-341 writes new matrices every frame; demo/avatar.gd, demo/mouse_look.gd): an order
-    // is used fb_lag frames after the costs it was sorted from were measured.  The host predicts how far the picture's features
-    // move in that time; the sort dilates the cost map by that distance, so a tile counts as cheap only if everything within
-    // reach of it was cheap (atmo_tile_dilate_kernel); costs are recorded every 2nd draw instead of every fb_period-th while
-    // the camera moves; and an order whose reach the motion has outrun is not used (row-major instead).
-    // reach beyond which an order says nothing about the frame it would be used on: 160 px for the in-stream sort (a frame of lag),
-    // 48 px for the side-stream sort (four to six frames of lag: measured, recording every 2nd frame without a usable order costs 1-2 %)
-    constexpr float FB_MAX_REACH_PX = 160.0f, FB_MAX_REACH_SIDE_PX = 48.0f, FB_INSTREAM_PX = 3.0f, FB_INSTREAM_LONG_PX = 8.0f;
-    int dil_rx = 0, dil_ry = 0;
-    float reach_px = 0.0f;
     if (fb) {
-        if (fb->have_prev) {
-            float sil[2] = {0.0f, 0.0f};
-            const float m = feedback_motion_px(*frame, fb->prev_frame, ctx->p.u_planet_radius + ctx->p.u_atmosphere_height,
-                                               (ctx->flags & atmo::KF_CLOUDS) != 0, sil);
-            fb->motion_px = std::fmax(m, 0.75f * fb->motion_px);  // peak hold: one still frame does not end a camera move
-            if (fb->motion_px < 0.01f) fb->motion_px = 0.0f;
-            for (int k = 0; k < 2; ++k) fb->sil_px[k] = std::fmax(sil[k], 0.75f * fb->sil_px[k]);
-        }
-        fb->prev_frame = *frame;
-        fb->have_prev = true;
-        const bool moving = fb->motion_px > FB_STILL_PX;
-        const unsigned period = moving ? (ctx->fb_period < ctx->moving_period ? ctx->fb_period : ctx->moving_period) : ctx->fb_period;
-        // what an order sorted now would have to cover: it is in use from ~2 frames after its recording draw until the next takes over
-        const float want_reach = moving ? fb->motion_px * (float)(period + 4u) * ctx->env_reach_scale : 0.0f;
-        // nothing measured now says anything about the frame it would order -- or the frames are so short (the baked-LUT atmosphere
-        // without clouds: 20-50 us, +3 % from the order at best) that recording and sorting every other frame costs more than it brings
-        const bool short_frames = !(flags & (atmo::KF_CLOUDS | atmo::KF_LIGHT_DIRECT));
-        const bool too_fast = want_reach > FB_MAX_REACH_SIDE_PX || (moving && short_frames);
-        if (fb->pending) {
-            if (hipEventQuery(fb->ev_order[fb->write]) == hipSuccess) {
-                fb->active = fb->write;  // complete: no stream-side wait needed
-                fb->write ^= 1;
-                fb->pending = false;
-            } else {
-                (void)hipGetLastError();  // hipErrorNotReady is an answer, not an error: keep it out of the launch checks below
-            }
-        }
-        // In-stream mode: while the camera moves by more than a few pixels per frame, the kernels whose cost map is worth it
-        // (raymarched cloud light: the heaviest tiles cost 10x the mean, frames of 0.4-1.3 ms, +48 % from the order on a still
-        // camera) sort on the DRAW stream, right behind every draw.  The next draw is then ordered by this frame's costs -- one
-        // frame of lag instead of four to six, so the dilation stays at a tile or two and the order keeps its meaning -- at the
-        // price of ~10 us of sort kernels on the critical path per frame.  Measured (profiles/round3/ab_tile_feedback_motion.txt):
-        // clouds_high_rm panning 1 degree per frame +20 % in-stream against +7 % with the side-stream sort, but 35 % against 37 %
-        // at 0.1 degree per frame; clouds_high (0.18 ms frames, +7 % at best) loses 7 % in-stream: side stream only.
-        // one frame of lag and one of margin -- of the silhouette's motion when the window is taken from it (below)
-        const float is_reach = (ctx->fb_axis_windows ? std::fmax(fb->sil_px[0], fb->sil_px[1]) : fb->motion_px) * 2.0f * ctx->env_reach_scale;
-        // Which kernels: raymarched cloud light from 3 px per frame; since round 4 (per-axis windows) also the other 64-step cloud kernels in
-        // the precise mode (0.2 ms frames: +10..13 % where the side-stream order had nothing left, measured from 8 px per frame; at 1.4 px per
-        // frame the side stream is 2-3 points better).  Shorter frames (`clouds`, the fast cloud mode: 0.12-0.16 ms) are neutral in-stream
-        // (-0.4..+3 %) and stay on the side stream; the cloudless direct-light kernel LOSES 9-12 % in-stream under a pan (ATMO_FB_INSTREAM=2).
-        const bool is_rm = (flags & atmo::KF_CLOUD_LIGHT_RM) != 0;
-        const bool is_long = (flags & atmo::KF_CLOUDS) && (flags & atmo::KF_PRECISE) && ctx->cloud_steps >= 64;
-        const bool is_kernel = ctx->instream == 2 ? (flags & (atmo::KF_CLOUDS | atmo::KF_LIGHT_DIRECT)) != 0 : (is_rm || (is_long && ctx->fb_axis_windows));
-        const float is_px = is_rm ? FB_INSTREAM_PX : FB_INSTREAM_LONG_PX;
-        fb_instream = ctx->instream && fb->motion_px >= is_px && is_kernel && !fb->pending && is_reach <= FB_MAX_REACH_PX;
-        const int tile_h = (rc.y1 - rc.y0 + gy - 1) / gy;  // pixel rows per tile of this launch (8, or 4 with two lanes per ray)
-        if (fb_instream) {
-            if (fb->is_last_n + 1u == fb->n) {  // the sort behind the previous draw of this key wrote is_order
-                rc.tile_order = (const uint32_t *)fb->is_order.ptr;
-                order2 = (const uint32_t *)fb->is_order2.ptr;
-                class_totals = fb->class_totals + 2 * atmo::TILE_ORDER_CLASSES;   // (read without waiting: at worst last frame's, or none yet)
-                ctx->fb_ordered_draws += 1;
-            }
-            rc.tile_cost = (uint32_t *)fb->cost.ptr;
-            reach_px = is_reach;
-            dil_rx = (int)std::ceil(reach_px / 16.0f);
-            dil_ry = (int)std::ceil(reach_px / (float)(tile_h > 0 ? tile_h : 8));
-            if (ctx->fb_axis_windows) {
-                // Round 4: the window per screen axis, from the motion of the planet's SILHOUETTE alone (two frames of it, one tile at least).  The
-                // expensive tiles of these kernels sit on the limb, which an orbit leaves where it is while the surface points behind motion_px sweep
-                // across the disc: the isotropic window (7 x 13 tiles at 1 degree of orbit per frame) buried the ranking of exactly those tiles, and
-                // a pan needs nothing vertically (profiles/round4/ab_tile_feedback_motion.txt).
-                dil_rx = (int)std::ceil(2.0f * fb->sil_px[0] * ctx->env_reach_scale / 16.0f);
-                dil_ry = (int)std::ceil(2.0f * fb->sil_px[1] * ctx->env_reach_scale / (float)(tile_h > 0 ? tile_h : 8));
-                dil_rx = dil_rx < 1 ? 1 : (dil_rx > 10 ? 10 : dil_rx);
-                dil_ry = dil_ry < 1 ? 1 : (dil_ry > 10 ? 10 : dil_ry);
-            }
-            fb->active = -1;  // whatever the side stream sorted last belongs to an older picture
-        } else {
-            if (fb->active >= 0) {
-                // still conservative?  features have moved about motion_px * (frames since the costs were measured)
-                const float moved = fb->motion_px * (float)(fb->n - fb->order_born[fb->active]);
-                if (moved <= fb->order_reach_px[fb->active] + 8.0f) {
-                    rc.tile_order = (const uint32_t *)fb->order[fb->active].ptr;
-                    order2 = (const uint32_t *)fb->order2[fb->active].ptr;
-                    class_totals = fb->class_totals + fb->active * atmo::TILE_ORDER_CLASSES;   // complete: the host has seen this sort's event
-                    ctx->fb_ordered_draws += 1;
-                }
-            }
-            // the first two draws of a key are not measured (cold clocks and caches rank the tiles poorly); the next four
-            // record back to back (the order settles in a few frames), then every period-th
-            fb_record = !too_fast && !fb->pending && fb->n >= 2 && (fb->n < 6 || fb->n - fb->last_record >= period);
-            if (fb_record) {
-                rc.tile_cost = (uint32_t *)fb->cost.ptr;
-                reach_px = want_reach;
-                dil_rx = reach_px > 0.0f ? (int)std::ceil(reach_px / 16.0f) : 0;
-                dil_ry = reach_px > 0.0f ? (int)std::ceil(reach_px / (float)(tile_h > 0 ? tile_h : 8)) : 0;
-            }
-        }
+        plan = atmo::feedback_plan(feedback_plan_input(ctx, *fb, flags, tile_h, false, fb->motion_px));
+        rc.tile_order = feedback_apply(ctx, *fb, plan, &rc.tile_cost, &order2, &class_totals);
     }
     if (ctx->measure_cost) rc.tile_cost = ctx->measure_cost;
+
+    // 6. geometric order
     // The direct-light cloudless kernels seen from outside the shell, when the learnt order has nothing for this draw -- a camera that moves too fast for it (a pan:
     // the silhouette slides a tile per frame), the first draws of a key, a draw inside a graph capture: the order is a closed form of the camera
     // (RenderConsts::geo_rows), looked up by the kernel's preamble.  That lookup costs every wave ~9 dependent scalar loads (+5 us on a 1920x1080 draw), which the
@@ -1747,22 +1826,14 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
     // camera loses 6 %, and the 20-50 us LUT kernels lose under every motion).
     int launch_flags = flags;
     if (geo_policy && ctx->geo_order && rc.tile_order == nullptr && flags == atmo::KF_LIGHT_DIRECT && rc.miss_k > 0.0f && split == 1) {
-        geo_order_fill(ctx, rc, gx, gy, (rc.y1 - rc.y0 + gy - 1) / gy);
+        geo_order_fill(ctx, rc, gx, gy, tile_h);
         if (rc.geo_rows > 0) {
             launch_flags |= atmo::KF_GEO;   // the twin kernel whose preamble looks the tile up (the plain kernel's preamble stays what it was)
             ctx->geo_draws += 1;
             ctx->fb_ordered_draws += 1;
         }
     }
-    // kernel timing brackets the draw kernel alone (the tile-order kernel runs beside the previous draw).  The event pair
-    // is owned by a guard until it is handed to ctx->pending, so no error path leaks it.
-    struct EventPair {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~EventPair() {
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
-    } ev;
+    TimingBracket timing;   // kernel timing brackets the draw kernel alone (the tile-order kernel runs beside the previous draw)
 #ifdef ATMO_WAVE_TRACE
     {
         const size_t waves = (size_t)gx * gy * 4;  // upper bound for every tile height
@@ -1775,123 +1846,37 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
         rc.wave_trace = (unsigned long long *)ctx->wave_trace.ptr;
     }
 #endif
-    if (tiles_dev) {   // (before anything is created or enqueued for this draw)
-        // the bounded copy of the list lives in a context-owned buffer that a later, longer list frees and reallocates -- a graph that had
-        // recorded this draw would replay on freed memory (and an allocation fails inside a global-mode capture anyway): refused, stated in atmo.h
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-            return fail(ctx, ATMO_E_STATE, "tile-list draws cannot be captured into a HIP graph (context-owned list buffer); capture atmo_render instead");
-    }
-    const bool timed = ctx->timing > 0 && (ctx->launch_counter % ctx->timing) == 0;
-    if (timed) {
-        if (ctx->pending.size() >= 64) drain_timing(ctx, /*only_completed=*/true);  // a long loop with timing left on stays bounded
-        HIP_TRY(ctx, hipEventCreate(&ev.e0));
-        HIP_TRY(ctx, hipEventCreate(&ev.e1));
-        HIP_TRY(ctx, hipEventRecord(ev.e0, s));
-    }
-    if (tiles_dev) {
-        // The list is the caller's: an index beyond the grid must shade nothing (include/atmo.h) -- and must not be turned into addresses.  The
-        // render kernels' preamble is not the place (one scalar compare-and-branch there costs the headline kernel 10 %:
-        // profiles/round5/ab_tile_bound.txt), so a copy of the list is bounded on the device in front of the draw: out-of-range entries
-        // become the first tile BELOW the viewport, whose lanes all leave at the kernel's own bounds test.  One copy per draw stream
-        // (stream order protects it from the next tile-list draw on that stream); a fifth stream takes over the least recently used copy,
-        // ordered behind its last reader on the device.
-        AtmoContext::TileListBuf *tl = nullptr;
-        ctx->tile_list_clock += 1;
-        for (AtmoContext::TileListBuf &t : ctx->tile_lists) if (!tl && t.used && t.stream == s) tl = &t;
-        for (AtmoContext::TileListBuf &t : ctx->tile_lists) if (!tl && !t.used) tl = &t;
-        if (!tl) {
-            tl = &ctx->tile_lists[0];
-            for (AtmoContext::TileListBuf &t : ctx->tile_lists) if (t.last_use < tl->last_use) tl = &t;
-            const int rc0 = order_after_draws_on(ctx, s, tl->stream);  // its last reader: a draw on that stream
-            if (rc0 != ATMO_OK) return rc0;
-        }
-        tl->used = true;
-        tl->stream = s;
-        tl->last_use = ctx->tile_list_clock;
-        // the leading n_heavy tiles on two lanes per ray (atmo_render_tiles_split): only where that form exists and is the same bits
-        // (as for whole frames: the raymarched-light kernel; the kernel without it gains only from eight GPUs on and loses 21 % at two --
-        //  profiles/round5/band_balance.txt -- so it takes part only when forced, ATMO_HEAVY_SPLIT=2)
-        const int lod_cloud0 = atmo::KF_CUBE_LOD | atmo::KF_PRECISE | atmo::KF_CLOUDS;
-        const bool form = ctx->heavy_split == 2 ? (flags & ~atmo::KF_CLOUD_LIGHT_RM) == lod_cloud0 : flags == (lod_cloud0 | atmo::KF_CLOUD_LIGHT_RM);
-        if (split != 1 || !form || !ctx->heavy_split) n_heavy = 0;
-        { const int rc0 = dev_reserve(ctx, tl->buf, ((size_t)n_tiles + 2 * (size_t)n_heavy) * sizeof(uint32_t)); if (rc0 != ATMO_OK) return rc0; }
-        int tw = 0, th = 0;
-        atmo::render_tile_size(split, &tw, &th);                                         // pixels per tile of this launch
-        const uint32_t below = (uint32_t)((frame->viewport_h - rc.gy0 + th - 1) / th);   // the first tile row that starts below the viewport's last row
-        const int th2 = th / 2 > 0 ? th / 2 : 1;
-        const uint32_t below2 = (uint32_t)((frame->viewport_h - rc.gy0 + th2 - 1) / th2);
-        uint32_t *list2 = (uint32_t *)tl->buf.ptr + n_tiles;
-        HIP_TRY(ctx, atmo::launch_tile_list_bound(tiles_dev, (uint32_t *)tl->buf.ptr, n_tiles, (uint32_t)gx * (uint32_t)gy, below * (uint32_t)gx, s,
-                                                  list2, n_heavy, gx, below2 * (uint32_t)gx));
-        rc.tile_order = (const uint32_t *)tl->buf.ptr;
-        if (n_heavy > 0) order2 = list2;
-    }
-    // Heavy tiles on two lanes per ray, beside the rest of the draw (round 5).  Only the two BASELINE cloud kernels under the declared sampler have
-    // the lane-split form whose frames are bit-identical to the one-lane kernel's (atmo_kernels.hip: march_clouds<.., SPLIT = 2, LOD>).
-    // Measured (profiles/round5/ab_heavy_tile_split.txt): it pays where a draw is as long as its heaviest wavefront -- clouds_high_rm at
-    // 1280x720 -28 %, from the limb -42..-44 % at 1280x720 and 1920x1080, the night side -33 % -- and costs 9 % where the draw is bound by
-    // throughput (1920x1080 pose P_space, where the lane-split kernel on EVERY tile is 43 % slower; 3840x2160), which the trigger keeps out;
-    // the kernel without raymarched light never gains (its heaviest wave is a fifth as long): not split unless forced (ATMO_HEAVY_SPLIT=2).
+    // the bounded copy of a tile list lives in a context-owned buffer that a later, longer list frees and reallocates -- a graph that had
+    // recorded this draw would replay on freed memory (and an allocation fails inside a global-mode capture anyway): refused, stated in atmo.h
+    // (before anything is created or enqueued for this draw)
+    if (tiles_dev && stream_is_capturing(s))
+        return fail(ctx, ATMO_E_STATE, "tile-list draws cannot be captured into a HIP graph (context-owned list buffer); capture atmo_render instead");
+    ATMO_TRY(timing_open(ctx, timing));
+    ATMO_TRY(timing_begin(ctx, timing, s));
+
+    // 7. tile-list bounding
+    if (tiles_dev) ATMO_TRY(bound_tile_list(ctx, frame, rc, s, flags, split, gx, gy, tiles_dev, n_tiles, &n_heavy, &order2));
+
+    // 8. launch: plain, or the heavy tiles on two lanes per ray beside the rest (launch_heavy_split)
     int heavy = 0;
-    const int lod_cloud = atmo::KF_CUBE_LOD | atmo::KF_PRECISE | atmo::KF_CLOUDS;
-    const bool split_form = ctx->heavy_split == 2 ? (flags & ~atmo::KF_CLOUD_LIGHT_RM) == lod_cloud : flags == (lod_cloud | atmo::KF_CLOUD_LIGHT_RM);
-    if (ctx->heavy_split && order2 && class_totals && rc.tile_order && !tiles_dev && split == 1 && split_form)
+    if (ctx->heavy_split && order2 && class_totals && rc.tile_order && !tiles_dev && split == 1 && two_lane_form(ctx, flags))
         heavy = heavy_tile_count(class_totals, gx * gy, ctx->heavy_split_ratio,
-                                 ctx->heavy_split == 2 ? 0.0f : (fb_instream ? ctx->heavy_split_trigger_moving : ctx->heavy_split_trigger),
+                                 ctx->heavy_split == 2 ? 0.0f : (plan.sort_instream ? ctx->heavy_split_trigger_moving : ctx->heavy_split_trigger),
                                  1024 * 6);   // both declared-sampler cloud kernels hold six waves per SIMD
     if (tiles_dev) heavy = n_heavy;   // a tile-list draw: the caller says how many of its leading tiles are heavy (atmo_render_tiles_split)
-    const int total_tiles = tiles_dev ? n_tiles : gx * gy;
-    if (heavy > 0) {
-        if (!ctx->split_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->split_stream, hipStreamNonBlocking));
-        { const int rc0 = order_after_stream(ctx, ctx->split_stream, s); if (rc0 != ATMO_OK) return rc0; }   // fork: behind everything the draw is behind
-        atmo::RenderConsts rc2 = rc;
-        rc2.tile_order = order2;                       // two half-height tiles per heavy tile, heaviest first
-        rc2.cost_rows_halved = 1;                      // ... whose costs belong to the one-lane grid's tile (only this launch: ADVICE r5)
-        HIP_TRY(ctx, launch(flags, 2, rc2, ctx->split_stream, 2 * heavy));
-        if (total_tiles - heavy > 0) {
-            rc.tile_order += heavy;                    // the rest of the order, one lane per ray
-            HIP_TRY(ctx, launch(flags, split, rc, s, total_tiles - heavy));
-        }
-        { const int rc0 = order_after_stream(ctx, s, ctx->split_stream); if (rc0 != ATMO_OK) return rc0; }   // join
-        ctx->split_draws += 1;
-        ctx->split_tiles_last = (unsigned)heavy;
-    } else {
-        HIP_TRY(ctx, launch(launch_flags, split, rc, s, tiles_dev ? n_tiles : 0));
-    }
-    ctx->last_flags = tc ? (flags | atmo::KF_TARGET) : flags;
-    if (fb_record) {
-        // Sort on the side stream as soon as this draw is done (the sort also clears the costs for the next recording).
-        // order[write] was last read by draws enqueued on `s` before this one, so the event orders the write too.
-        HIP_TRY(ctx, hipEventRecord(fb->ev_draw, s));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->fb_stream, fb->ev_draw, 0));
-        HIP_TRY(ctx, atmo::launch_tile_order((uint32_t *)fb->cost.ptr, (uint32_t *)fb->order[fb->write].ptr, gx, gy, dil_rx, dil_ry,
-                                             (uint32_t *)fb->dil[0].ptr, (uint32_t *)fb->dil[1].ptr, (uint32_t *)ctx->fb_scratch.ptr, ctx->fb_stream,
-                                             (uint32_t *)fb->order2[fb->write].ptr, fb->class_totals + fb->write * atmo::TILE_ORDER_CLASSES));
-        fb->order_reach_px[fb->write] = reach_px;
-        fb->order_born[fb->write] = fb->n;
-        HIP_TRY(ctx, hipEventRecord(fb->ev_order[fb->write], ctx->fb_stream));
-        fb->pending = true;
-        fb->last_record = fb->n;
-        ctx->fb_sorts += 1;
-    }
+    if (heavy > 0) ATMO_TRY(launch_heavy_split(ctx, tc, flags, split, rc, s, order2, heavy, tiles_dev ? n_tiles : gx * gy));
+    else HIP_TRY(ctx, launch_draw(tc, launch_flags, split, rc, s, tiles_dev ? n_tiles : 0));
+
+    // 9. sorts, 10. bookkeeping
+    if (plan.sort_side) ATMO_TRY(feedback_sort_side(ctx, *fb, gx, gy, plan, s));
     if (fb) fb->n += 1;
     hipEvent_t marker = nullptr;   // the draw stream's marker, when this draw recorded one (re-recorded behind the in-stream sort below)
-    { const int rc0 = note_draw_stream(ctx, s, &marker); if (rc0 != ATMO_OK) return rc0; }
-    ctx->last_split = split;
-    ctx->launch_counter += 1;  // counted only once the launch was accepted
-    if (timed) {
-        HIP_TRY(ctx, hipEventRecord(ev.e1, s));
-        ctx->pending.emplace_back(ev.e0, ev.e1);
-        ev.e0 = ev.e1 = nullptr;  // ownership moved
-    }
-    if (fb_instream) {  // behind the draw (and behind the timing bracket, which is the draw kernel's alone)
-        HIP_TRY(ctx, atmo::launch_tile_order((uint32_t *)fb->cost.ptr, (uint32_t *)fb->is_order.ptr, gx, gy, dil_rx, dil_ry,
-                                             (uint32_t *)fb->dil[0].ptr, (uint32_t *)fb->dil[1].ptr, (uint32_t *)fb->is_scratch.ptr, s,
-                                             (uint32_t *)fb->is_order2.ptr, fb->class_totals + 2 * atmo::TILE_ORDER_CLASSES));
+    ATMO_TRY(finish_draw(ctx, s, tc ? (flags | atmo::KF_TARGET) : flags, split, true, &marker));   // (atmo_kernel_name: the family without KF_GEO)
+    ATMO_TRY(timing_end(ctx, timing, s));
+    if (plan.sort_instream) {  // behind the draw (and behind the timing bracket, which is the draw kernel's alone)
+        ATMO_TRY(feedback_sort(ctx, *fb, 2, gx, gy, plan.dil_rx, plan.dil_ry, s, fb->is_scratch));
         fb->is_last_n = fb->n - 1;
         fb->last_record = fb->n - 1;
-        ctx->fb_sorts += 1;
         // that sort reads and writes the feedback state (cost, is_order, dil[], class_totals) on this stream BEHIND the marker recorded above,
         // and whoever takes the state over (feedback_quiesce, order_after_draws_on: a recycled slot, a key handed to another stream) waits for the
         // marker only -- so the marker goes behind the sort (the stream handle is alive: we are inside the caller's draw call)
@@ -1930,14 +1915,9 @@ int atmo_set_tile_feedback(AtmoContext *ctx, int mode) {
     ctx->tile_feedback = mode;
     // restart every feedback state at its next launch.  Buffers are kept and nothing waits here: a slot whose draws or sort may still be
     // in flight is marked dirty, and whoever takes it next is ordered behind that work on the device (feedback_state -> feedback_quiesce)
-    for (AtmoContext::FeedbackState &f : ctx->fb) {
+    for (int i = 0; i <= AtmoContext::FB_SLOTS; ++i) {   // ... and the batches' (atmo_render_views)
+        AtmoContext::FeedbackState &f = i < AtmoContext::FB_SLOTS ? ctx->fb[i] : ctx->views_fb;
         if (f.used && (f.n > 0 || f.pending)) f.dirty = true;   // (f.pending stays: the quiesce orders the new owner behind the sort stream)
-        f.used = false;
-        f.n = 0;
-    }
-    {   // ... and the batches' (atmo_render_views)
-        AtmoContext::FeedbackState &f = ctx->views_fb;
-        if (f.used && (f.n > 0 || f.pending)) f.dirty = true;
         f.used = false;
         f.n = 0;
     }
@@ -1948,6 +1928,12 @@ int atmo_set_tile_feedback(AtmoContext *ctx, int mode) {
 float atmo_debug_motion_px(const AtmoFrame *a, const AtmoFrame *b, float radius, int surface_points) {
     if (!a || !b) return -1.0f;
     return feedback_motion_px(*a, *b, radius, surface_points != 0);
+}
+
+int atmo_debug_feedback_plan(const AtmoFeedbackPlanIn *in, AtmoFeedbackPlanOut *out) {
+    if (!in || !out) return fail(nullptr, ATMO_E_ARG, "atmo_debug_feedback_plan: null argument");
+    *out = atmo::feedback_plan(*in);
+    return ATMO_OK;
 }
 
 int atmo_get_feedback_stats(AtmoContext *ctx, int *states, unsigned *ordered_draws, unsigned *sorts, unsigned *recycled) {
@@ -2105,7 +2091,7 @@ int atmo_get_host_wait_stats(AtmoContext *ctx, unsigned *device_syncs) {
 
 // ---- the host side without a device (atmo_debug.h): for the CPU test suite and the sanitizer build ----------------------------------
 int atmo_debug_create_host_only(int variant, int view_steps, int cloud_steps, int light_mode, int light_steps, AtmoContext **out) {
-    { const int rc0 = check_create_args(variant, view_steps, cloud_steps, light_mode, light_steps, out); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(check_create_args(variant, view_steps, cloud_steps, light_mode, light_steps, out));
     AtmoContext *ctx = new (std::nothrow) AtmoContext();
     if (!ctx) return fail(nullptr, ATMO_E_ARG, "atmo_debug_create_host_only: out of host memory");
     init_variant(ctx, /*device: none*/ -1, variant, view_steps, cloud_steps, light_mode, light_steps);
@@ -2119,10 +2105,9 @@ int atmo_debug_frame_constants(AtmoContext *ctx, const AtmoFrame *frame, int cub
     if (cube_n < 0 || cube_n > 4096) return fail(ctx, ATMO_E_ARG, "atmo_debug_frame_constants: bad cubemap size");
     const int saved_n = ctx->cube_n;
     ctx->cube_n = cube_n;  // the level-0 certificate's constant depends on the face size; no texture needs to be bound for it
-    AtmoFrame fixed = *frame;
-    if (ctx->host_double_precision) for (int k = 12; k < 15; ++k) fixed.inv_view_matrix[k] *= -1.0f;
+    AtmoFrame fixed;
     atmo::RenderConsts rc;
-    fill_consts(ctx, &fixed, nullptr, nullptr, rc);
+    fill_consts(ctx, draw_frame(ctx, frame, fixed), nullptr, nullptr, rc);
     ctx->cube_n = saved_n;
     std::vector<float> v;
     auto put = [&](const float *p, int n) { v.insert(v.end(), p, p + n); };
@@ -2273,7 +2258,7 @@ static int proxy_setup(AtmoContext *ctx, const char *who, const AtmoFrame *f, co
 // The family a proxy draw of this context uses, or ATMO_E_STATE when there is no proxy kernel for its mode (proxy_family_supported).
 static int proxy_family(AtmoContext *ctx, const char *who, const AtmoFrame *frame, int *flags, bool *lod) {
     int split = 1;
-    { const int rc0 = draw_family(ctx, frame, flags, &split, lod); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(draw_family(ctx, frame, flags, &split, lod));
     if (split != 1 || !atmo::proxy_family_supported(*flags))
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": no proxy kernel for this context's mode (proxy draws exist for the default forms: atmo_set_precision 1, "
                                                           "up to 32 view steps, one lane per ray)");
@@ -2286,49 +2271,34 @@ static int proxy_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *mod
     const char *who = (tc || pitch_px) ? "atmo_render_proxy_target" : composite ? "atmo_render_proxy_composite" : "atmo_render_proxy";
     if (!frame || !model_matrix) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null frame or model_matrix");
     if (!(box_size > 0.0f) || !std::isfinite(box_size)) return fail(ctx, ATMO_E_ARG, std::string(who) + ": box_size must be positive and finite");
-    if (frame->viewport_w < 1 || frame->viewport_h < 1 || frame->viewport_w > 65536 || frame->viewport_h > 65536)
-        return fail(ctx, ATMO_E_ARG, std::string(who) + ": bad viewport size");
-    if (frame->x0 < 0 || frame->y0 < 0 || frame->x1 > frame->viewport_w || frame->y1 > frame->viewport_h || frame->x0 > frame->x1 || frame->y0 > frame->y1)
-        return fail(ctx, ATMO_E_ARG, std::string(who) + ": rect outside the viewport");
-    if (!depth_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null device pointer");
-    if (!tc && (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, std::string(who) + ": rgba_dev must be 16-byte aligned");
-    if (!(ctx->flags & (atmo::KF_LIGHT_DIRECT | atmo::KF_LITE)) && !(ctx->lut.ptr && ctx->lut4.ptr))
-        return fail(ctx, ATMO_E_STATE, std::string(who) + ": u_optical_depth_texture not set (call atmo_bake_optical_depth or atmo_set_texture)");
-    if ((ctx->flags & atmo::KF_CLOUDS) && !ctx->shape.ptr) return fail(ctx, ATMO_E_STATE, std::string(who) + ": u_cloud_shape_texture not set");
+    bool empty = false;
+    ATMO_TRY(check_frame(ctx, who, frame, &empty));
+    // (unlike render_impl, the pointers, the textures and the mode are checked in front of the empty rect's ATMO_OK)
+    ATMO_TRY(check_draw_pointers(ctx, who, depth_dev, rgba_dev, !tc));
+    ATMO_TRY(check_draw_textures(ctx, who));
     int flags = 0;
     bool lod = false;
-    { const int rc0 = proxy_family(ctx, who, frame, &flags, &lod); if (rc0 != ATMO_OK) return rc0; }
-    if (frame->x0 == frame->x1 || frame->y0 == frame->y1) return ATMO_OK;
-    AtmoFrame fixed = *frame;
-    if (ctx->host_double_precision) for (int k = 12; k < 15; ++k) fixed.inv_view_matrix[k] *= -1.0f;   // as render_impl (main:118-125)
+    ATMO_TRY(proxy_family(ctx, who, frame, &flags, &lod));
+    if (empty) return ATMO_OK;
+    AtmoFrame fixed;
+    frame = draw_frame(ctx, frame, fixed);
     atmo::ProxyConsts pc;
     int rect[4], gx = 0, gy = 0;
-    { const int rc0 = proxy_setup(ctx, who, &fixed, model_matrix, box_size, lod, pc, rect, &gx, &gy); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(proxy_setup(ctx, who, frame, model_matrix, box_size, lod, pc, rect, &gx, &gy));
     if (gx == 0 || gy == 0) return ATMO_OK;   // nothing of the box is on this rect between the planes: no launch
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     atmo::RenderConsts rc;
-    fill_consts(ctx, &fixed, depth_dev, rgba_dev, rc);   // the output stays addressed by the FRAME's rect (plain) or the viewport (composite)
-    if (composite) {
-        rc.out_pitch = fixed.viewport_w;
-        rc.out_x0 = 0;
-        rc.out_y0 = 0;
-        rc.composite = 1;
-        rc.store_discards = 0;
-    }
-    if (pitch_px > 0) rc.out_pitch = pitch_px;
-    if (tc) rc.out = nullptr;
+    draw_consts(ctx, frame, depth_dev, rgba_dev, composite, pitch_px, tc != nullptr, rc);   // the output stays addressed by the FRAME's rect (plain) or the viewport (composite)
     rc.x0 = rect[0]; rc.y0 = rect[1]; rc.x1 = rect[2]; rc.y1 = rect[3];
     rc.gx0 = lod ? rect[0] & ~1 : rect[0];
     rc.gy0 = lod ? rect[1] & ~1 : rect[1];
     rc.tiles_x = gx;
     hipStream_t s = (hipStream_t)stream;
-    { const int rc0 = tex_order(ctx, s); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(tex_order(ctx, s));
     if (tc) HIP_TRY(ctx, atmo::launch_render_proxy_target(flags, rc, pc, *tc, s));
     else HIP_TRY(ctx, atmo::launch_render_proxy(flags, rc, pc, s));
-    ctx->last_flags = flags | atmo::KF_PROXY | (tc ? atmo::KF_TARGET : 0);
-    ctx->last_split = 1;
     hipEvent_t marker = nullptr;
-    return note_draw_stream(ctx, s, &marker);
+    return finish_draw(ctx, s, flags | atmo::KF_PROXY | (tc ? atmo::KF_TARGET : 0), 1, false, &marker);
 }
 
 int atmo_render_proxy(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev, float *rgba_dev,
@@ -2361,10 +2331,8 @@ static int target_check(AtmoContext *ctx, const char *who, const AtmoFrame *fram
     if (!target->pixels) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null target pixels");
     if ((reinterpret_cast<uintptr_t>(target->pixels) & (uintptr_t)(px - 1)) != 0)
         return fail(ctx, ATMO_E_ARG, std::string(who) + ": target pixels must be aligned to the pixel size (" + std::to_string(px) + " bytes)");
-    if (frame->viewport_w < 1 || frame->viewport_h < 1 || frame->viewport_w > 65536 || frame->viewport_h > 65536)
-        return fail(ctx, ATMO_E_ARG, std::string(who) + ": bad viewport size");
-    if (frame->x0 < 0 || frame->y0 < 0 || frame->x1 > frame->viewport_w || frame->y1 > frame->viewport_h || frame->x0 > frame->x1 || frame->y0 > frame->y1)
-        return fail(ctx, ATMO_E_ARG, std::string(who) + ": rect outside the viewport");
+    bool empty = false;   // (an empty rect is the draw's to return ATMO_OK for, behind its own checks)
+    ATMO_TRY(check_frame(ctx, who, frame, &empty));
     const long long row_bytes = (long long)(composite ? frame->viewport_w : frame->x1 - frame->x0) * px;
     long long pitch = target->row_pitch_bytes;
     if (pitch == 0) pitch = row_bytes;
@@ -2388,10 +2356,10 @@ static int target_family(AtmoContext *ctx, const char *who, const AtmoFrame *fra
 int atmo_render_target(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, const AtmoTarget *target, int composite, void *stream) {
     if (!ctx) return ATMO_E_ARG;
     int pitch = 0;
-    { const int rc0 = target_check(ctx, "atmo_render_target", frame, target, composite != 0, &pitch); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(target_check(ctx, "atmo_render_target", frame, target, composite != 0, &pitch));
     if (target->format == ATMO_TARGET_RGBA32F)   // the float kernels themselves: a pitch in whole pixels is all they need
         return render_impl(ctx, frame, depth_dev, (float *)target->pixels, stream, composite != 0, nullptr, 0, 0, nullptr, pitch / 16);
-    { const int rc0 = target_family(ctx, "atmo_render_target", frame); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(target_family(ctx, "atmo_render_target", frame));
     const atmo::TargetConsts tc = {target->pixels, pitch, target->format};
     return render_impl(ctx, frame, depth_dev, (float *)target->pixels, stream, composite != 0, nullptr, 0, 0, &tc, 0);
 }
@@ -2400,7 +2368,7 @@ int atmo_render_proxy_target(AtmoContext *ctx, const AtmoFrame *frame, const flo
                              const AtmoTarget *target, int composite, void *stream) {
     if (!ctx) return ATMO_E_ARG;
     int pitch = 0;
-    { const int rc0 = target_check(ctx, "atmo_render_proxy_target", frame, target, composite != 0, &pitch); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(target_check(ctx, "atmo_render_proxy_target", frame, target, composite != 0, &pitch));
     if (target->format == ATMO_TARGET_RGBA32F)
         return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, (float *)target->pixels, stream, composite != 0, nullptr, pitch / 16);
     const atmo::TargetConsts tc = {target->pixels, pitch, target->format};   // (proxy_impl refuses the modes without a proxy kernel: the same set)
@@ -2425,17 +2393,18 @@ int atmo_debug_proxy_launch_rect(AtmoContext *ctx, const AtmoFrame *frame, const
     const char *who = "atmo_debug_proxy_launch_rect";
     if (!frame || !model_matrix || !rect_out || !tiles_out) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null argument");
     if (!(box_size > 0.0f) || !std::isfinite(box_size)) return fail(ctx, ATMO_E_ARG, std::string(who) + ": box_size must be positive and finite");
+    // (not check_frame: this entry point has no 65 536 viewport cap and one message for both failures -- the set of accepted arguments would change)
     if (frame->viewport_w < 1 || frame->viewport_h < 1 || frame->x0 < 0 || frame->y0 < 0 || frame->x1 > frame->viewport_w ||
         frame->y1 > frame->viewport_h || frame->x0 > frame->x1 || frame->y0 > frame->y1)
         return fail(ctx, ATMO_E_ARG, std::string(who) + ": bad viewport or rect");
     int flags = 0, split = 1;
     bool lod = false;
     launch_shape(ctx, frame, &flags, &split, &lod);   // the grid origin: even under the declared sampler
-    AtmoFrame fixed = *frame;
-    if (ctx->host_double_precision) for (int k = 12; k < 15; ++k) fixed.inv_view_matrix[k] *= -1.0f;
+    AtmoFrame fixed;
+    frame = draw_frame(ctx, frame, fixed);
     atmo::ProxyConsts pc;
     int gx = 0, gy = 0;
-    { const int rc0 = proxy_setup(ctx, who, &fixed, model_matrix, box_size, lod, pc, rect_out, &gx, &gy); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(proxy_setup(ctx, who, frame, model_matrix, box_size, lod, pc, rect_out, &gx, &gy));
     *tiles_out = gx * gy;
     return ATMO_OK;
 }
@@ -2475,8 +2444,7 @@ int views_check_frames(AtmoContext *ctx, const char *who, bool have_views, const
     }
     if (!have_views) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null views");
     for (int i = 0; i < n_views; ++i) {
-        const int rc0 = check_frame(ctx, std::string(who) + ": view " + std::to_string(i), args[i].frame, &L.empty[i]);
-        if (rc0 != ATMO_OK) return rc0;
+        ATMO_TRY(check_frame(ctx, std::string(who) + ": view " + std::to_string(i), args[i].frame, &L.empty[i]));
         if (!L.empty[i]) L.n_drawn += 1;
     }
     return ATMO_OK;
@@ -2484,7 +2452,7 @@ int views_check_frames(AtmoContext *ctx, const char *who, bool have_views, const
 // The second half: the family (ATMO_E_STATE where no multi-view kernel exists; `packed`: the KF_VIEWS | KF_TARGET kernels) and the concatenated launch.
 int views_family_grid(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, bool packed, ViewsLayout &L) {
     int split = 1;
-    { const int rc0 = draw_family(ctx, args[0].frame, &L.flags, &split, &L.lod); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(draw_family(ctx, args[0].frame, &L.flags, &split, &L.lod));
     if (split != 1 || !(packed ? atmo::views_target_family_supported(L.flags) : atmo::views_family_supported(L.flags)))
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": no multi-view kernel for this context's mode (they exist for the default forms: atmo_set_precision 1, "
                                                           "up to 32 view steps, one lane per ray)");
@@ -2518,61 +2486,44 @@ int views_layout(AtmoContext *ctx, const char *who, const AtmoView *views, int n
 }
 
 // The batches' feedback state, keyed by (stream, family, n_views, every view's grid): re-keyed -- ordered behind whatever used its buffers before, on
-// the device -- when the signature changes.  *out stays null when the context has feedback off for this batch.
+// the device -- when the signature changes (feedback_state_start).
 int views_feedback_state(AtmoContext *ctx, const ViewsLayout &L, int n_views, hipStream_t s, AtmoContext::FeedbackState **out) {
-    *out = nullptr;
     AtmoContext::FeedbackState &f = ctx->views_fb;
-    bool same = f.used && f.draw_stream == s && ctx->views_key_flags == L.family && ctx->views_key_n == n_views;
-    for (int i = 0; same && i < n_views; ++i) same = ctx->views_key_grid[i][0] == L.gx[i] && ctx->views_key_grid[i][1] == L.gy[i];
-    if (same) { *out = &f; return ATMO_OK; }
-    if (!ctx->fb_stream) {
-        int lo = 0, hi = 0;  // numerically lower = higher priority
-        HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->fb_stream, hipStreamNonBlocking, hi));
-    }
-    { const int rc0 = dev_reserve(ctx, ctx->fb_scratch, atmo::tile_order_scratch_bytes()); if (rc0 != ATMO_OK) return rc0; }
-    if (f.used || f.dirty || f.pending || f.n > 0) {
-        const int rc0 = feedback_quiesce(ctx, f, s);
-        if (rc0 != ATMO_OK) return rc0;
-    }
-    const size_t bytes = (size_t)L.first_block[ATMO_MAX_VIEWS] * sizeof(uint32_t);
-    int rc1 = dev_reserve(ctx, f.cost, bytes);
-    for (int k = 0; k < 2 && rc1 == ATMO_OK; ++k) rc1 = dev_reserve(ctx, f.order[k], bytes);
-    if (rc1 != ATMO_OK) { f.used = false; return rc1; }
-    if (!f.ev_draw) {
-        HIP_TRY(ctx, hipEventCreateWithFlags(&f.ev_draw, hipEventDisableTiming));
-        for (int k = 0; k < 2; ++k) HIP_TRY(ctx, hipEventCreateWithFlags(&f.ev_order[k], hipEventDisableTiming));
-    }
-    HIP_TRY(ctx, hipMemsetAsync(f.cost.ptr, 0, bytes, s));
-    f.used = true;
-    f.draw_stream = s;
-    f.n = 0;
-    f.last_record = 0;
-    f.active = -1;
-    f.write = 0;
-    f.pending = false;
-    ctx->views_key_flags = L.family;
-    ctx->views_key_n = n_views;
-    for (int i = 0; i < n_views; ++i) { ctx->views_key_grid[i][0] = L.gx[i]; ctx->views_key_grid[i][1] = L.gy[i]; }
-    ctx->views_have_prev = false;
-    ctx->views_drop_pending = false;
-    for (float &m : ctx->views_motion_px) m = 0.0f;
+    AtmoContext::ViewsFeedbackKey &key = ctx->views_key;
     *out = &f;
+    bool same = f.used && f.draw_stream == s && key.flags == L.family && key.n == n_views;
+    for (int i = 0; same && i < n_views; ++i) same = key.grid[i][0] == L.gx[i] && key.grid[i][1] == L.gy[i];
+    if (same) return ATMO_OK;
+    ATMO_TRY(feedback_state_start(ctx, f, s, L.first_block[ATMO_MAX_VIEWS], false));
+    key.flags = L.family;
+    key.n = n_views;
+    for (int i = 0; i < n_views; ++i) { key.grid[i][0] = L.gx[i]; key.grid[i][1] = L.gy[i]; }
+    for (float &m : key.motion_px) m = 0.0f;
     return ATMO_OK;
 }
-// Everything a batch does once its arguments stand: the staging slot, the per-view constants, the tile order and its feedback, the ONE launch.  Shared by
-// atmo_render_views (packed == false: the float kernels, args[i].pitch_px) and atmo_render_views_target (packed: the KF_VIEWS | KF_TARGET kernels, args[i].tc).
-int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, int composite, bool packed, const ViewsLayout &L, void *stream) {
-    if (L.n_drawn == 0) return ATMO_OK;   // n_views == 0, or every rect empty: nothing to shade
-    { const int rc0 = check_draw_textures(ctx, who); if (rc0 != ATMO_OK) return rc0; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    {   // the table the kernel reads is the context's and the next batch overwrites it: a replayed graph would shade with another batch's constants
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-            return fail(ctx, ATMO_E_STATE, std::string(who) + " cannot be captured into a HIP graph (context-owned per-view constants); capture atmo_render per view instead");
+// ... with every view's motion taken in (the fastest view's, in pixels per frame: *motion_px) and the pending sort polled: what feedback_plan decides on
+static int views_feedback_begin(AtmoContext *ctx, const ViewsLayout &L, int n_views, const AtmoFrame *const *frames, hipStream_t s,
+                         AtmoContext::FeedbackState **out, float *motion_px) {
+    ATMO_TRY(views_feedback_state(ctx, L, n_views, s, out));
+    AtmoContext::ViewsFeedbackKey &key = ctx->views_key;
+    *motion_px = 0.0f;
+    for (int i = 0; i < n_views; ++i) {
+        if (L.empty[i]) continue;
+        if ((*out)->have_prev) {
+            const float m = feedback_motion_px(*frames[i], key.prev[i], ctx->p.u_planet_radius + ctx->p.u_atmosphere_height, (L.flags & atmo::KF_CLOUDS) != 0);
+            key.motion_px[i] = std::fmax(m, 0.75f * key.motion_px[i]);  // peak hold: one still frame does not end a camera move
+            if (key.motion_px[i] < 0.01f) key.motion_px[i] = 0.0f;
+        }
+        key.prev[i] = *frames[i];
+        *motion_px = std::fmax(*motion_px, key.motion_px[i]);
     }
-    // a staging slot: the oldest of the ring.  Its event lies behind the launch that read it; only a host VIEWS_RING batches ahead of the device waits here
+    (*out)->have_prev = true;
+    feedback_poll(**out, *motion_px > atmo::FB_STILL_PX);   // (moving: the sort in flight was made from a picture that has moved on since)
+    return ATMO_OK;
+}
+// A staging slot for a batch's per-view constants: the oldest of the ring.  Its event lies behind the launch that read it; only a host VIEWS_RING batches
+// ahead of the device waits here
+static int views_ring_slot(AtmoContext *ctx, AtmoContext::ViewsSlot **out) {
     static_assert(ATMO_MAX_VIEWS == atmo::MAX_VIEWS, "the header's view count is the kernels'");
     if (!ctx->views_host || !ctx->views_dev.ptr) {
         const size_t ring_bytes = (size_t)AtmoContext::VIEWS_RING * ATMO_MAX_VIEWS * sizeof(atmo::RenderConsts);
@@ -2581,7 +2532,7 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_
             HIP_TRY(ctx, hipHostMalloc(&p, ring_bytes, hipHostMallocDefault));
             ctx->views_host = (atmo::RenderConsts *)p;
         }
-        { const int rc0 = dev_reserve(ctx, ctx->views_dev, ring_bytes); if (rc0 != ATMO_OK) return rc0; }
+        ATMO_TRY(dev_reserve(ctx, ctx->views_dev, ring_bytes));
         for (int k = 0; k < AtmoContext::VIEWS_RING; ++k) {
             ctx->views_ring[k].host = ctx->views_host + (size_t)k * ATMO_MAX_VIEWS;
             ctx->views_ring[k].dev = (atmo::RenderConsts *)ctx->views_dev.ptr + (size_t)k * ATMO_MAX_VIEWS;
@@ -2597,116 +2548,66 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_
         }
         slot.in_flight = false;
     }
+    *out = &slot;
+    return ATMO_OK;
+}
+// Everything a batch does once its arguments stand: the staging slot, the per-view constants, the tile order and its feedback, the ONE launch.  Shared by
+// atmo_render_views (packed == false: the float kernels, args[i].pitch_px) and atmo_render_views_target (packed: the KF_VIEWS | KF_TARGET kernels, args[i].tc).
+int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, int composite, bool packed, const ViewsLayout &L, void *stream) {
+    if (L.n_drawn == 0) return ATMO_OK;   // n_views == 0, or every rect empty: nothing to shade
+    ATMO_TRY(check_draw_textures(ctx, who));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    // the table the kernel reads is the context's and the next batch overwrites it: a replayed graph would shade with another batch's constants
+    if (stream_is_capturing(s))
+        return fail(ctx, ATMO_E_STATE, std::string(who) + " cannot be captured into a HIP graph (context-owned per-view constants); capture atmo_render per view instead");
+    AtmoContext::ViewsSlot *slot = nullptr;
+    ATMO_TRY(views_ring_slot(ctx, &slot));
     AtmoFrame fixed[ATMO_MAX_VIEWS];
     const AtmoFrame *frames[ATMO_MAX_VIEWS];
     int first = -1;
     for (int i = 0; i < n_views; ++i) {
-        atmo::RenderConsts &rc = slot.host[i];
+        atmo::RenderConsts &rc = slot->host[i];
         if (L.empty[i]) { std::memset(&rc, 0, sizeof(rc)); frames[i] = args[i].frame; continue; }
         frames[i] = draw_frame(ctx, args[i].frame, fixed[i]);
-        draw_consts(ctx, frames[i], args[i].depth, (float *)args[i].pixels, composite != 0, rc);
-        if (args[i].pitch_px > 0) rc.out_pitch = args[i].pitch_px;
-        if (packed) rc.out = nullptr;   // the KF_TARGET kernels address tc.pixels, rows tc.pitch_bytes apart
+        draw_consts(ctx, frames[i], args[i].depth, (float *)args[i].pixels, composite != 0, args[i].pitch_px, packed, rc);
         draw_grid_origin(frames[i], L.lod, rc);
         rc.tiles_x = L.gx[i];
         if (first < 0) first = i;
     }
-    { const int rc0 = tex_order(ctx, s); if (rc0 != ATMO_OK) return rc0; }  // texture updated on another stream
+    ATMO_TRY(tex_order(ctx, s));  // texture updated on another stream
     atmo::ViewsTargetConsts vtc;   // (its targets are read by the packed kernels only)
     std::memset(&vtc, 0, sizeof(vtc));
     atmo::ViewsConsts &vc = vtc.v;
     for (int i = 0; packed && i < n_views; ++i) if (!L.empty[i]) vtc.target[i] = args[i].tc;
     for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) vc.first_block[i] = L.first_block[i];
     const uint32_t total = L.first_block[ATMO_MAX_VIEWS];
-    // One tile order over all views, learnt as render_impl learns a single draw's on a still camera: the first two batches of a signature are not
-    // measured, the next four record, then every fb_period-th; the sort runs beside the draws on the side stream and its order is picked up once a
-    // host-side event query says it is complete.  While any view moves, the batch is neither ordered nor recorded (no dilation per view: atmo_views.h).
+    // One tile order over all views, learnt as render_impl learns a single draw's on a still camera: feedback_plan's batch form
     bool feedback = ctx->env_feedback >= 0 ? ctx->env_feedback != 0 : ctx->tile_feedback != 0;
     if (total < 512u) feedback = false;   // tiny launches: nothing to schedule
     AtmoContext::FeedbackState *fb = nullptr;
-    bool fb_record = false;
+    AtmoFeedbackPlanOut plan = {atmo::FB_ORDER_NONE, 0, 0, 0, 0, 0, 0.0f, 0};
     if (feedback) {
-        const int rc1 = views_feedback_state(ctx, L, n_views, s, &fb);
-        if (rc1 != ATMO_OK) return rc1;
+        float motion_px = 0.0f;
+        ATMO_TRY(views_feedback_begin(ctx, L, n_views, frames, s, &fb, &motion_px));
+        // (batch form: decided as for motion 0 or not at all, so views_fb's sil_px / is_last_n / order_reach_px, which no batch maintains, are never reached)
+        plan = atmo::feedback_plan(feedback_plan_input(ctx, *fb, L.flags, 8, true, motion_px));
+        vc.order = feedback_apply(ctx, *fb, plan, &vc.cost, nullptr, nullptr);
     }
-    if (fb) {
-        bool moving = false;
-        for (int i = 0; i < n_views; ++i) {
-            if (L.empty[i]) continue;
-            if (ctx->views_have_prev) {
-                const float m = feedback_motion_px(*frames[i], ctx->views_prev[i], ctx->p.u_planet_radius + ctx->p.u_atmosphere_height,
-                                                   (L.flags & atmo::KF_CLOUDS) != 0);
-                ctx->views_motion_px[i] = std::fmax(m, 0.75f * ctx->views_motion_px[i]);  // peak hold: one still frame does not end a camera move
-                if (ctx->views_motion_px[i] < 0.01f) ctx->views_motion_px[i] = 0.0f;
-            }
-            ctx->views_prev[i] = *frames[i];
-            moving = moving || ctx->views_motion_px[i] > FB_STILL_PX;
-        }
-        ctx->views_have_prev = true;
-        if (fb->pending) {
-            if (moving) ctx->views_drop_pending = true;   // sorted from a picture that has moved on since
-            if (hipEventQuery(fb->ev_order[fb->write]) == hipSuccess) {
-                if (!ctx->views_drop_pending) { fb->active = fb->write; fb->write ^= 1; }
-                fb->pending = false;
-                ctx->views_drop_pending = false;
-            } else {
-                (void)hipGetLastError();  // hipErrorNotReady is an answer, not an error
-            }
-        }
-        if (moving) {
-            fb->active = -1;
-        } else {
-            if (fb->active >= 0) {
-                vc.order = (const uint32_t *)fb->order[fb->active].ptr;
-                ctx->fb_ordered_draws += 1;
-            }
-            fb_record = !fb->pending && fb->n >= 2 && (fb->n < 6 || fb->n - fb->last_record >= ctx->fb_period);
-            if (fb_record) vc.cost = (uint32_t *)fb->cost.ptr;
-        }
-    }
-    struct EventPair {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~EventPair() {
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
-    } ev;
-    const bool timed = ctx->timing > 0 && (ctx->launch_counter % ctx->timing) == 0;
-    if (timed) {
-        if (ctx->pending.size() >= 64) drain_timing(ctx, /*only_completed=*/true);
-        HIP_TRY(ctx, hipEventCreate(&ev.e0));
-        HIP_TRY(ctx, hipEventCreate(&ev.e1));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(slot.dev, slot.host, (size_t)n_views * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
-    if (timed) HIP_TRY(ctx, hipEventRecord(ev.e0, s));   // the bracket is the one launch's
-    if (packed) HIP_TRY(ctx, atmo::launch_render_views_target(L.flags, slot.host[first].light_steps, slot.dev, vtc, s));
-    else HIP_TRY(ctx, atmo::launch_render_views(L.flags, slot.host[first].light_steps, slot.dev, vc, s));
-    if (timed) {
-        HIP_TRY(ctx, hipEventRecord(ev.e1, s));
-        ctx->pending.emplace_back(ev.e0, ev.e1);
-        ev.e0 = ev.e1 = nullptr;  // ownership moved
-    }
-    HIP_TRY(ctx, hipEventRecord(slot.done, s));
-    slot.in_flight = true;
+    TimingBracket timing;
+    ATMO_TRY(timing_open(ctx, timing));
+    HIP_TRY(ctx, hipMemcpyAsync(slot->dev, slot->host, (size_t)n_views * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
+    ATMO_TRY(timing_begin(ctx, timing, s));   // the bracket is the one launch's
+    if (packed) HIP_TRY(ctx, atmo::launch_render_views_target(L.flags, slot->host[first].light_steps, slot->dev, vtc, s));
+    else HIP_TRY(ctx, atmo::launch_render_views(L.flags, slot->host[first].light_steps, slot->dev, vc, s));
+    ATMO_TRY(timing_end(ctx, timing, s));
+    HIP_TRY(ctx, hipEventRecord(slot->done, s));
+    slot->in_flight = true;
     ctx->views_next += 1;
-    ctx->last_flags = L.family;
-    ctx->last_split = 1;
-    if (fb_record) {
-        // as render_impl: order[write] was last read by batches enqueued on `s` before this one, so the event orders the write too
-        HIP_TRY(ctx, hipEventRecord(fb->ev_draw, s));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->fb_stream, fb->ev_draw, 0));
-        HIP_TRY(ctx, atmo::launch_tile_order((uint32_t *)fb->cost.ptr, (uint32_t *)fb->order[fb->write].ptr, (int)total, 1, 0, 0, nullptr, nullptr,
-                                             (uint32_t *)ctx->fb_scratch.ptr, ctx->fb_stream, nullptr, nullptr));
-        HIP_TRY(ctx, hipEventRecord(fb->ev_order[fb->write], ctx->fb_stream));
-        fb->pending = true;
-        ctx->views_drop_pending = false;
-        fb->last_record = fb->n;
-        ctx->fb_sorts += 1;
-    }
+    if (plan.sort_side) ATMO_TRY(feedback_sort_side(ctx, *fb, (int)total, 1, plan, s));
     if (fb) fb->n += 1;
-    ctx->launch_counter += 1;
     hipEvent_t marker = nullptr;
-    return note_draw_stream(ctx, s, &marker);
+    return finish_draw(ctx, s, L.family, 1, true, &marker);
 }
 
 }  // namespace
@@ -2716,7 +2617,7 @@ int atmo_debug_views_layout(AtmoContext *ctx, const AtmoView *views, int n_views
     if (!first_block || !grid) return fail(ctx, ATMO_E_ARG, "atmo_debug_views_layout: null output");
     ViewsLayout L;
     ViewArg args[ATMO_MAX_VIEWS];
-    { const int rc0 = views_layout(ctx, "atmo_debug_views_layout", views, n_views, args, L); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(views_layout(ctx, "atmo_debug_views_layout", views, n_views, args, L));
     for (int i = 0; i <= n_views; ++i) first_block[i] = (int)L.first_block[i];
     for (int i = 0; i < n_views; ++i) { grid[2 * i] = L.gx[i]; grid[2 * i + 1] = L.gy[i]; }
     return ATMO_OK;
@@ -2727,14 +2628,14 @@ int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int 
     const char *who = "atmo_render_views";
     ViewsLayout L;
     ViewArg args[ATMO_MAX_VIEWS];
-    { const int rc0 = views_layout(ctx, who, views, n_views, args, L); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(views_layout(ctx, who, views, n_views, args, L));
     // the bytes every view writes: [lo, hi) -- plain: its own tight float4 array; composite: rows y0 .. y1 of its scene buffer, from pixel x0 of the first
     // to pixel x1 of the last.  Pairwise disjoint, or the views would race (they run concurrently, in no order).
     uintptr_t lo[ATMO_MAX_VIEWS], hi[ATMO_MAX_VIEWS];
     for (int i = 0; i < n_views; ++i) {
         if (L.empty[i]) continue;
         const AtmoView &v = views[i];
-        { const int rc0 = check_draw_pointers(ctx, std::string(who) + ": view " + std::to_string(i), v.depth_dev, v.rgba_dev, true); if (rc0 != ATMO_OK) return rc0; }
+        ATMO_TRY(check_draw_pointers(ctx, std::string(who) + ": view " + std::to_string(i), v.depth_dev, v.rgba_dev, true));
         const AtmoFrame &f = v.frame;
         const uintptr_t base = reinterpret_cast<uintptr_t>(v.rgba_dev);
         if (composite) {
@@ -2777,8 +2678,8 @@ int atmo_render_views_target(AtmoContext *ctx, const AtmoViewTarget *views, int 
         const AtmoViewTarget &v = views[i];
         const std::string who_i = std::string(who) + ": view " + std::to_string(i);
         int p = 0;
-        { const int rc0 = target_check(ctx, who_i.c_str(), &v.frame, &v.target, composite != 0, &p); if (rc0 != ATMO_OK) return rc0; }
-        { const int rc0 = check_draw_pointers(ctx, who_i, v.depth_dev, (const float *)v.target.pixels, false); if (rc0 != ATMO_OK) return rc0; }
+        ATMO_TRY(target_check(ctx, who_i.c_str(), &v.frame, &v.target, composite != 0, &p));
+        ATMO_TRY(check_draw_pointers(ctx, who_i, v.depth_dev, (const float *)v.target.pixels, false));
         if (format >= 0 && v.target.format != format)
             return fail(ctx, ATMO_E_ARG, who_i + ": target format " + std::to_string(v.target.format) + " differs from the batch's (" + std::to_string(format) +
                                              "): one format per batch");
@@ -2805,7 +2706,7 @@ int atmo_render_views_target(AtmoContext *ctx, const AtmoViewTarget *views, int 
         }
     }
     const bool packed = format == ATMO_TARGET_RGBA16F || format == ATMO_TARGET_RGBA8_UNORM;
-    { const int rc0 = views_family_grid(ctx, who, args, n_views, packed, L); if (rc0 != ATMO_OK) return rc0; }
+    ATMO_TRY(views_family_grid(ctx, who, args, n_views, packed, L));
     return views_enqueue(ctx, who, args, n_views, composite, packed, L, stream);
 }
 

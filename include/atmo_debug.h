@@ -141,6 +141,34 @@ int atmo_debug_tile_order(AtmoContext *ctx, const uint32_t *cost, int tiles_x, i
  * atmo_create or call of this function. */
 int atmo_debug_heavy_tile_count(const uint32_t *class_totals, int n_classes, int n_tiles, float ratio, float trigger, int resident_waves);
 
+/* The tile-order feedback's policy as the draw path evaluates it (csrc/atmo_feedback_plan.h: feedback_plan, the function atmo_render and atmo_render_views
+ * call, not a copy); needs no device and no context.  In: the context's knobs, the launch and a snapshot of the feedback state's counters as they stand
+ * after the motion update and the poll of the pending sort.  Out: what the draw does. */
+typedef struct AtmoFeedbackPlanIn {
+    uint32_t fb_period, moving_period;        /* ATMO_TILE_FEEDBACK_PERIOD (8), ATMO_FB_MOVING_PERIOD (2) */
+    float reach_scale;                        /* ATMO_FB_REACH_SCALE (1) */
+    int32_t instream, axis_windows;           /* ATMO_FB_INSTREAM (1), ATMO_FB_AXIS_WINDOWS (1) */
+    int32_t cloud_steps;                      /* the context's */
+    int32_t flags;                            /* the kernel family: 1 clouds, 2 raymarched cloud light, 4 direct light, 16 precise (csrc/atmo_device.h: KernelFlags) */
+    int32_t tile_h;                           /* pixel rows per tile of the launch: 8, or 4 with two lanes per ray */
+    int32_t batch;                            /* != 0: a view batch -- no in-stream sort, no dilation; moving: neither ordered nor recorded */
+    uint32_t n, last_record;                  /* draws of the key so far; n of the last recording draw */
+    int32_t pending, active;                  /* a side-stream sort is in flight; the complete order's slot, -1: none */
+    uint32_t order_born;                      /* of order[active] (not read when active < 0): n of the draw it was sorted from ... */
+    float order_reach_px;                     /* ... and the motion it covers */
+    uint32_t is_last_n;                       /* n of the draw behind which the last in-stream sort ran (0xFFFFFFFF: none) */
+    float motion_px, sil_px[2];               /* pixels per frame: the picture's features (a batch: its fastest view's); the silhouette per screen axis */
+} AtmoFeedbackPlanIn;
+typedef struct AtmoFeedbackPlanOut {
+    int32_t order;                            /* the order the draw uses: 0 none (row-major), 1 the side-stream sort's slot `active`, 2 the in-stream sort's */
+    int32_t record;                           /* the draw records tile costs */
+    int32_t sort_side, sort_instream;         /* the sort that follows the draw: on the side stream, on the draw stream */
+    int32_t dil_rx, dil_ry;                   /* that sort's dilation window, in tiles */
+    float reach_px;                           /* the motion the sorted order covers */
+    int32_t invalidate_active;                /* the side-stream order belongs to an older picture: active = -1 */
+} AtmoFeedbackPlanOut;
+int atmo_debug_feedback_plan(const AtmoFeedbackPlanIn *in, AtmoFeedbackPlanOut *out);   /* ATMO_E_ARG for a NULL argument */
+
 #ifdef ATMO_WAVE_TRACE
 /* Diagnostic builds only (-DATMO_WAVE_TRACE: tools/wave_timeline.py, tools/rmq_stats.py; the shipped library does not export it): copies the wave
  * trace of the last draw -- 4 x uint64 per wave: start, end (s_memrealtime, 100 MHz), HW_ID, XCC_ID | preamble ticks << 8 -- to the host and

@@ -1565,6 +1565,55 @@ def test_moving_camera_sequence_is_identical_with_feedback_on_and_off():
         off.close()
 
 
+def _feedback_counters(node):
+    st = node.feedback_stats()
+    return st["states"], st["ordered_draws"], st["sorts"], st["recycled"]
+
+
+@pytest.mark.parametrize("batch", [False, True], ids=["draws", "batches"])
+@pytest.mark.parametrize("config_name", ["no_clouds_32_lut", "clouds_high"])
+def test_tile_feedback_counters_are_exact_when_every_sort_is_seen_complete(config_name, batch):
+    """24 draws (or batches of two views) of one still pose on a fresh context, the device synchronised after each: every pending sort is seen complete by
+    the next draw, so the policy's counters are exact -- the draws n = 2, 3, 4, 5 record, then every 8th (13, 21): six sorts; the order of draw 2's costs
+    is in use from draw 3 on: 21 ordered draws; one state, nothing recycled.  (640 x 360: 1800 tiles per view, above the 512 below which nothing is
+    scheduled; no direct light, so no geometric order counts as well.)  The pictures are the feedback-off context's."""
+    tex, params = demo_textures(), demo_params()
+    w, h = 640, 360
+    cams = [S.Camera.from_pose(w, h, "P_space")] + ([S.Camera.from_pose(w, h, "P_limb")] if batch else [])
+    depths = [torch.from_numpy(S.depth_ground_sphere(c)).cuda() for c in cams]
+    on, off = make_node(config_name, tex, params, tile_feedback=1), make_node(config_name, tex, params, tile_feedback=0)
+    want = off.render_views(cams, depths) if batch else [off.render(cams[0], depths[0])]
+    assert _feedback_counters(on) == (0, 0, 0, 0)
+    for n in range(24):
+        got = on.render_views(cams, depths) if batch else [on.render(cams[0], depths[0])]
+        torch.cuda.synchronize()
+        assert all(torch.equal(g, w_) for g, w_ in zip(got, want)), n
+        assert _feedback_counters(on) == (1, max(0, n - 2), sum(n >= k for k in (2, 3, 4, 5, 13, 21)), 0), n
+    assert _feedback_counters(on) == (1, 21, 6, 0)
+    assert _feedback_counters(off) == (0, 0, 0, 0)
+    on.close()
+    off.close()
+
+
+def test_a_batch_with_a_moving_view_is_neither_ordered_nor_recorded():
+    """Two views, the first panning by 1 degree (about 5 pixels at 640 x 360) per frame, for 12 frames: no sort, no ordered draw; the pictures are the
+    feedback-off context's."""
+    import bench
+
+    tex, params = demo_textures(), demo_params()
+    w, h = 640, 360
+    still = S.Camera.from_pose(w, h, "P_limb")
+    on, off = make_node("clouds_high", tex, params, tile_feedback=1), make_node("clouds_high", tex, params, tile_feedback=0)
+    for k, cam in enumerate(bench.motion_cameras(S, w, h, ("pan", 1.0), 12)):
+        depths = [bench.depth_ground_sphere_torch(torch, S, c, torch.device("cuda")) for c in (cam, still)]
+        got, want = on.render_views([cam, still], depths), off.render_views([cam, still], depths)
+        torch.cuda.synchronize()
+        assert all(torch.equal(g, w_) for g, w_ in zip(got, want)), k
+        assert _feedback_counters(on) == (1, 0, 0, 0), k
+    on.close()
+    off.close()
+
+
 def test_geometric_tile_order_draws_every_tile_exactly_once():
     """Round 6: the direct-light cloudless kernels, seen from outside the atmosphere shell, take their tile order from the camera in closed form where the learnt
     order has nothing for a draw (RenderConsts::geo_rows: the tiles that can shade first, the others behind them) -- a map from the block index to the tile that must
