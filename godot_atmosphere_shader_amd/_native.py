@@ -29,7 +29,7 @@ DEBUG_SYMBOLS = (
     "atmo_set_lane_split", "atmo_debug_motion_px", "atmo_get_feedback_stats", "atmo_set_timing", "atmo_get_timing", "atmo_host_layout_cubemap", "atmo_host_layout_shape",
     "atmo_host_layout_lut", "atmo_host_cubemap_mip", "atmo_read_texture_layout", "atmo_selftest_exact_math", "atmo_debug_marched_optical_depth", "atmo_debug_log2_cr", "atmo_kernel_name", "atmo_build_id",
     "atmo_get_host_wait_stats", "atmo_get_split_stats", "atmo_debug_create_host_only", "atmo_debug_frame_constants", "atmo_debug_proxy_launch_rect",
-    "atmo_debug_store_target", "atmo_debug_views_layout", "atmo_debug_tile_order", "atmo_debug_heavy_tile_count", "atmo_debug_feedback_plan",
+    "atmo_debug_store_target", "atmo_debug_views_layout", "atmo_debug_views_proxy_layout", "atmo_debug_tile_order", "atmo_debug_heavy_tile_count", "atmo_debug_feedback_plan",
 )
 # every symbol include/atmo_scene.h declares: drawing several atmospheres into one frame (the far-mode BoxMesh draw)
 SCENE_SYMBOLS = ("atmo_render_proxy", "atmo_render_proxy_composite")
@@ -43,7 +43,10 @@ MAX_VIEWS = 8
 # every symbol include/atmo_views_target.h declares: the same batch into packed and pitched colour targets (RGBA16F / RGBA8_UNORM / RGBA32F per view).
 # The ABI version stays 5: a host detects the feature by the symbol.
 VIEWS_TARGET_SYMBOLS = ("atmo_render_views_target",)
-EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_TARGET_SYMBOLS
+# every symbol include/atmo_views_proxy.h declares: the far-mode (proxy) form of both batches -- several views of one planet's BoxMesh proxy in one launch.
+# The ABI version stays 5: a host detects the feature by the symbols.
+VIEWS_PROXY_SYMBOLS = ("atmo_render_views_proxy", "atmo_render_views_proxy_target")
+EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 
 
@@ -182,6 +185,9 @@ def load() -> C.CDLL:
         "atmo_render_views": (ip, [vp, C.POINTER(AtmoView), ip, ip, vp]),
         "atmo_debug_views_layout": (ip, [vp, C.POINTER(AtmoView), ip, C.POINTER(ip), C.POINTER(ip)]),
         "atmo_render_views_target": (ip, [vp, C.POINTER(AtmoViewTarget), ip, ip, vp]),
+        "atmo_render_views_proxy": (ip, [vp, C.POINTER(AtmoView), ip, fp, C.c_float, ip, vp]),
+        "atmo_render_views_proxy_target": (ip, [vp, C.POINTER(AtmoViewTarget), ip, fp, C.c_float, ip, vp]),
+        "atmo_debug_views_proxy_layout": (ip, [vp, C.POINTER(AtmoView), ip, fp, C.c_float, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]),
         "atmo_debug_tile_order": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, C.POINTER(ip)]),
         "atmo_debug_heavy_tile_count": (ip, [vp, ip, ip, C.c_float, C.c_float, ip]),
         "atmo_debug_feedback_plan": (ip, [C.POINTER(AtmoFeedbackPlanIn), C.POINTER(AtmoFeedbackPlanOut)]),

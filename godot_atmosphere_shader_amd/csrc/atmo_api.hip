@@ -11,6 +11,7 @@
 #include "../../include/atmo_target.h"
 #include "../../include/atmo_views.h"
 #include "../../include/atmo_views_target.h"
+#include "../../include/atmo_views_proxy.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -2610,27 +2611,10 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_
     return finish_draw(ctx, s, L.family, 1, true, &marker);
 }
 
-}  // namespace
-
-int atmo_debug_views_layout(AtmoContext *ctx, const AtmoView *views, int n_views, int *first_block, int *grid) {
-    if (!ctx) return ATMO_E_ARG;
-    if (!first_block || !grid) return fail(ctx, ATMO_E_ARG, "atmo_debug_views_layout: null output");
-    ViewsLayout L;
-    ViewArg args[ATMO_MAX_VIEWS];
-    ATMO_TRY(views_layout(ctx, "atmo_debug_views_layout", views, n_views, args, L));
-    for (int i = 0; i <= n_views; ++i) first_block[i] = (int)L.first_block[i];
-    for (int i = 0; i < n_views; ++i) { grid[2 * i] = L.gx[i]; grid[2 * i + 1] = L.gy[i]; }
-    return ATMO_OK;
-}
-
-int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int composite, void *stream) {
-    if (!ctx) return ATMO_E_ARG;
-    const char *who = "atmo_render_views";
-    ViewsLayout L;
-    ViewArg args[ATMO_MAX_VIEWS];
-    ATMO_TRY(views_layout(ctx, who, views, n_views, args, L));
-    // the bytes every view writes: [lo, hi) -- plain: its own tight float4 array; composite: rows y0 .. y1 of its scene buffer, from pixel x0 of the first
-    // to pixel x1 of the last.  Pairwise disjoint, or the views would race (they run concurrently, in no order).
+// The float batches' per-view pointer checks and their overlap rule (atmo_render_views, atmo_render_views_proxy), behind views_check_frames.
+// The bytes every view writes: [lo, hi) -- plain: its own tight float4 array; composite: rows y0 .. y1 of its scene buffer, from pixel x0 of the first
+// to pixel x1 of the last.  Pairwise disjoint, or the views would race (they run concurrently, in no order).
+int views_float_outputs(AtmoContext *ctx, const char *who, const AtmoView *views, int n_views, int composite, const ViewsLayout &L) {
     uintptr_t lo[ATMO_MAX_VIEWS], hi[ATMO_MAX_VIEWS];
     for (int i = 0; i < n_views; ++i) {
         if (L.empty[i]) continue;
@@ -2649,27 +2633,23 @@ int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int 
             if (!L.empty[j] && lo[i] < hi[j] && lo[j] < hi[i])
                 return fail(ctx, ATMO_E_ARG, std::string(who) + ": views " + std::to_string(j) + " and " + std::to_string(i) + " write overlapping memory");
     }
-    return views_enqueue(ctx, who, args, n_views, composite, false, L, stream);
+    return ATMO_OK;
 }
-
-// include/atmo_views_target.h: the batch into packed and pitched colour targets.  All argument checks (ATMO_E_ARG) in front of the mode check (ATMO_E_STATE),
-// both in front of anything that touches a device.
-int atmo_render_views_target(AtmoContext *ctx, const AtmoViewTarget *views, int n_views, int composite, void *stream) {
-    if (!ctx) return ATMO_E_ARG;
-    const char *who = "atmo_render_views_target";
-    ViewsLayout L;
-    ViewArg args[ATMO_MAX_VIEWS];
+// The target batches' argument checks (atmo_render_views_target, atmo_render_views_proxy_target): the count and every view's frame (views_check_frames;
+// *done as there), then per view atmo_render_target's checks, one format per batch, and the overlap rule of include/atmo_views_target.h on the bytes it
+// writes -- `rows` rows of `row_bytes`, `pitch` apart, from `base`.  Fills args; *packed: the batch's format is RGBA16F or RGBA8_UNORM.
+int views_target_outputs(AtmoContext *ctx, const char *who, const AtmoViewTarget *views, int n_views, int composite, ViewArg *args, ViewsLayout &L,
+                         bool *done, bool *packed) {
     for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) {
         args[i].frame = &views[i].frame;
         args[i].depth = views[i].depth_dev;
         args[i].pixels = views[i].target.pixels;
     }
+    *packed = false;
     {
-        bool done = false;
-        const int rc0 = views_check_frames(ctx, who, views != nullptr, args, n_views, L, &done);
-        if (rc0 != ATMO_OK || done) return rc0;
+        const int rc0 = views_check_frames(ctx, who, views != nullptr, args, n_views, L, done);
+        if (rc0 != ATMO_OK || *done) return rc0;
     }
-    // per view: atmo_render_target's checks; one format per batch; and the bytes it writes -- `rows` rows of `row_bytes`, `pitch` apart, from `base`
     int format = -1;
     uintptr_t base[ATMO_MAX_VIEWS];
     long long rows[ATMO_MAX_VIEWS], row_bytes[ATMO_MAX_VIEWS], pitch[ATMO_MAX_VIEWS];
@@ -2705,11 +2685,189 @@ int atmo_render_views_target(AtmoContext *ctx, const AtmoViewTarget *views, int 
             return fail(ctx, ATMO_E_ARG, std::string(who) + ": views " + std::to_string(j) + " and " + std::to_string(i) + " write overlapping memory");
         }
     }
-    const bool packed = format == ATMO_TARGET_RGBA16F || format == ATMO_TARGET_RGBA8_UNORM;
+    *packed = format == ATMO_TARGET_RGBA16F || format == ATMO_TARGET_RGBA8_UNORM;
+    return ATMO_OK;
+}
+
+// ---- several far-mode (proxy) views in one launch (include/atmo_views_proxy.h) ---------------------------------------------------------------
+// The launch of a proxy batch: proxy_setup per non-empty view -- its ProxyConsts, its cut rectangle (the box's screen rectangle inside the view's rect) and
+// that rectangle's tile grid, exactly the single proxy draw's -- and the prefix of those grids.  A view without a tile (an empty rect; the box behind the
+// camera, beyond the far plane, off the rect) adds nothing.
+struct ViewsProxyLayout {
+    atmo::ProxyConsts pc[ATMO_MAX_VIEWS];
+    int rect[ATMO_MAX_VIEWS][4];
+    int gx[ATMO_MAX_VIEWS], gy[ATMO_MAX_VIEWS];
+    uint32_t first_block[ATMO_MAX_VIEWS + 1];   // prefix of gx * gy; entries behind n_views repeat the total
+    AtmoFrame fixed[ATMO_MAX_VIEWS];
+    const AtmoFrame *frames[ATMO_MAX_VIEWS];     // the frames the kernels see (draw_frame): args[i].frame or &fixed[i]
+};
+int views_proxy_checks(AtmoContext *ctx, const char *who, const float *model_matrix, float box_size) {
+    if (!model_matrix) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null model_matrix");
+    if (!(box_size > 0.0f) || !std::isfinite(box_size)) return fail(ctx, ATMO_E_ARG, std::string(who) + ": box_size must be positive and finite");
+    return ATMO_OK;
+}
+// Behind every argument check that needs no matrix arithmetic: the mode (ATMO_E_STATE, proxy_family: the one list both families share), then the boxes.
+int views_proxy_layout(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, const float *model_matrix, float box_size, ViewsLayout &L,
+                       ViewsProxyLayout &P) {
+    ATMO_TRY(proxy_family(ctx, who, args[0].frame, &L.flags, &L.lod));
+    uint64_t total = 0;
+    for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) {
+        P.first_block[i] = (uint32_t)total;
+        if (i >= ATMO_MAX_VIEWS) break;
+        P.gx[i] = P.gy[i] = 0;
+        std::memset(&P.pc[i], 0, sizeof(P.pc[i]));
+        P.frames[i] = nullptr;
+        for (int k = 0; k < 4; ++k) P.rect[i][k] = 0;
+        if (i >= n_views) continue;
+        const AtmoFrame &f = *args[i].frame;
+        P.rect[i][0] = P.rect[i][2] = f.x0;
+        P.rect[i][1] = P.rect[i][3] = f.y0;
+        if (L.empty[i]) continue;
+        P.frames[i] = draw_frame(ctx, args[i].frame, P.fixed[i]);
+        const std::string who_i = std::string(who) + ": view " + std::to_string(i);
+        ATMO_TRY(proxy_setup(ctx, who_i.c_str(), P.frames[i], model_matrix, box_size, L.lod, P.pc[i], P.rect[i], &P.gx[i], &P.gy[i]));
+        total += (uint64_t)P.gx[i] * (uint64_t)P.gy[i];
+    }
+    if (total > 0x7fffffffull) return fail(ctx, ATMO_E_ARG, std::string(who) + ": more than 2^31 tiles in one batch");
+    return ATMO_OK;
+}
+// views_enqueue's sibling for the proxy batches: the staging slot, the per-view constants with the CUT rectangle as the launch rectangle (the output stays
+// addressed by the frame's rect or the viewport, as proxy_impl fills it), the ONE launch.  No tile order, no feedback state, not timed and not counted, as
+// the single proxy draw.
+int views_proxy_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, int composite, bool packed, const ViewsLayout &L,
+                        const ViewsProxyLayout &P, void *stream) {
+    if (P.first_block[ATMO_MAX_VIEWS] == 0) return ATMO_OK;   // no view has a tile: no launch, no staging slot
+    ATMO_TRY(check_draw_textures(ctx, who));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s))   // as views_enqueue: the table is the context's and the next batch overwrites it
+        return fail(ctx, ATMO_E_STATE, std::string(who) + " cannot be captured into a HIP graph (context-owned per-view constants); capture atmo_render_proxy per view instead");
+    AtmoContext::ViewsSlot *slot = nullptr;
+    ATMO_TRY(views_ring_slot(ctx, &slot));
+    atmo::ViewsProxyTargetConsts vptc;   // (its targets are read by the packed kernels only)
+    std::memset(&vptc, 0, sizeof(vptc));
+    int first = -1;
+    for (int i = 0; i < n_views; ++i) {
+        atmo::RenderConsts &rc = slot->host[i];
+        if (P.gx[i] == 0 || P.gy[i] == 0) { std::memset(&rc, 0, sizeof(rc)); continue; }
+        draw_consts(ctx, P.frames[i], args[i].depth, (float *)args[i].pixels, composite != 0, args[i].pitch_px, packed, rc);
+        const int *rect = P.rect[i];
+        rc.x0 = rect[0]; rc.y0 = rect[1]; rc.x1 = rect[2]; rc.y1 = rect[3];
+        rc.gx0 = L.lod ? rect[0] & ~1 : rect[0];
+        rc.gy0 = L.lod ? rect[1] & ~1 : rect[1];
+        rc.tiles_x = P.gx[i];
+        vptc.p.proxy[i] = P.pc[i];
+        if (packed) vptc.target[i] = args[i].tc;
+        if (first < 0) first = i;
+    }
+    for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) vptc.p.first_block[i] = P.first_block[i];
+    ATMO_TRY(tex_order(ctx, s));  // texture updated on another stream
+    HIP_TRY(ctx, hipMemcpyAsync(slot->dev, slot->host, (size_t)n_views * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
+    if (packed) HIP_TRY(ctx, atmo::launch_render_views_proxy_target(L.flags, slot->host[first].light_steps, slot->dev, vptc, s));
+    else HIP_TRY(ctx, atmo::launch_render_views_proxy(L.flags, slot->host[first].light_steps, slot->dev, vptc.p, s));
+    HIP_TRY(ctx, hipEventRecord(slot->done, s));
+    slot->in_flight = true;
+    ctx->views_next += 1;
+    hipEvent_t marker = nullptr;
+    return finish_draw(ctx, s, L.flags | atmo::KF_VIEWS | atmo::KF_PROXY | (packed ? atmo::KF_TARGET : 0), 1, false, &marker);
+}
+}  // namespace
+
+int atmo_debug_views_layout(AtmoContext *ctx, const AtmoView *views, int n_views, int *first_block, int *grid) {
+    if (!ctx) return ATMO_E_ARG;
+    if (!first_block || !grid) return fail(ctx, ATMO_E_ARG, "atmo_debug_views_layout: null output");
+    ViewsLayout L;
+    ViewArg args[ATMO_MAX_VIEWS];
+    ATMO_TRY(views_layout(ctx, "atmo_debug_views_layout", views, n_views, args, L));
+    for (int i = 0; i <= n_views; ++i) first_block[i] = (int)L.first_block[i];
+    for (int i = 0; i < n_views; ++i) { grid[2 * i] = L.gx[i]; grid[2 * i + 1] = L.gy[i]; }
+    return ATMO_OK;
+}
+
+int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_views";
+    ViewsLayout L;
+    ViewArg args[ATMO_MAX_VIEWS];
+    ATMO_TRY(views_layout(ctx, who, views, n_views, args, L));
+    ATMO_TRY(views_float_outputs(ctx, who, views, n_views, composite, L));
+    return views_enqueue(ctx, who, args, n_views, composite, false, L, stream);
+}
+
+// include/atmo_views_target.h: the batch into packed and pitched colour targets.  All argument checks (ATMO_E_ARG) in front of the mode check (ATMO_E_STATE),
+// both in front of anything that touches a device.
+int atmo_render_views_target(AtmoContext *ctx, const AtmoViewTarget *views, int n_views, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_views_target";
+    ViewsLayout L;
+    ViewArg args[ATMO_MAX_VIEWS];
+    bool done = false, packed = false;
+    ATMO_TRY(views_target_outputs(ctx, who, views, n_views, composite, args, L, &done, &packed));
+    if (done) return ATMO_OK;
     ATMO_TRY(views_family_grid(ctx, who, args, n_views, packed, L));
     return views_enqueue(ctx, who, args, n_views, composite, packed, L, stream);
 }
 
+// include/atmo_views_proxy.h: the far-mode (proxy) batches.  Argument checks that need no matrix arithmetic (ATMO_E_ARG) in front of the mode check
+// (ATMO_E_STATE), a singular matrix behind it (as atmo_render_proxy), all in front of anything that touches a device.
+int atmo_render_views_proxy(AtmoContext *ctx, const AtmoView *views, int n_views, const float *model_matrix, float box_size, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_views_proxy";
+    ViewsLayout L;
+    ViewArg args[ATMO_MAX_VIEWS];
+    for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) {
+        args[i].frame = &views[i].frame;
+        args[i].depth = views[i].depth_dev;
+        args[i].pixels = views[i].rgba_dev;
+    }
+    bool done = false;
+    ATMO_TRY(views_check_frames(ctx, who, views != nullptr, args, n_views, L, &done));
+    ATMO_TRY(views_proxy_checks(ctx, who, model_matrix, box_size));
+    if (done) return ATMO_OK;
+    ATMO_TRY(views_float_outputs(ctx, who, views, n_views, composite, L));
+    ViewsProxyLayout P;
+    ATMO_TRY(views_proxy_layout(ctx, who, args, n_views, model_matrix, box_size, L, P));
+    return views_proxy_enqueue(ctx, who, args, n_views, composite, false, L, P, stream);
+}
+
+int atmo_render_views_proxy_target(AtmoContext *ctx, const AtmoViewTarget *views, int n_views, const float *model_matrix, float box_size, int composite,
+                                   void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_views_proxy_target";
+    ViewsLayout L;
+    ViewArg args[ATMO_MAX_VIEWS];
+    bool done = false, packed = false;
+    ATMO_TRY(views_target_outputs(ctx, who, views, n_views, composite, args, L, &done, &packed));
+    ATMO_TRY(views_proxy_checks(ctx, who, model_matrix, box_size));
+    if (done) return ATMO_OK;
+    ViewsProxyLayout P;
+    ATMO_TRY(views_proxy_layout(ctx, who, args, n_views, model_matrix, box_size, L, P));
+    return views_proxy_enqueue(ctx, who, args, n_views, composite, packed, L, P, stream);
+}
+
+// atmo_debug.h: the launch of a proxy batch as the host computes it; host-only contexts work, the pointers are not looked at
+int atmo_debug_views_proxy_layout(AtmoContext *ctx, const AtmoView *views, int n_views, const float *model_matrix, float box_size, int *first_block,
+                                  int *grid, int *rects) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_debug_views_proxy_layout";
+    if (!first_block || !grid || !rects) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null output");
+    ViewsLayout L;
+    ViewArg args[ATMO_MAX_VIEWS];
+    for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) args[i].frame = &views[i].frame;
+    bool done = false;
+    ATMO_TRY(views_check_frames(ctx, who, views != nullptr, args, n_views, L, &done));
+    ATMO_TRY(views_proxy_checks(ctx, who, model_matrix, box_size));
+    if (done) { first_block[0] = 0; return ATMO_OK; }
+    ViewsProxyLayout P;
+    ATMO_TRY(views_proxy_layout(ctx, who, args, n_views, model_matrix, box_size, L, P));
+    for (int i = 0; i <= n_views; ++i) first_block[i] = (int)P.first_block[i];
+    for (int i = 0; i < n_views; ++i) {
+        grid[2 * i] = P.gx[i];
+        grid[2 * i + 1] = P.gy[i];
+        for (int k = 0; k < 4; ++k) rects[4 * i + k] = P.rect[i][k];
+    }
+    return ATMO_OK;
+}
 }  // extern "C"
 
 #ifdef ATMO_WAVE_TRACE

@@ -173,6 +173,18 @@ struct ViewsTargetConsts {
     ViewsConsts v;
     TargetConsts target[MAX_VIEWS];        // entries of empty views and behind n_views are zero: no tile maps to them
 };
+// Several far-mode (proxy) views in one launch (atmo_render_views_proxy, include/atmo_views_proxy.h): the launch of ViewsConsts without a tile order or
+// cost recording -- every view's grid is the box's screen rectangle and changes every frame, as the single proxy draw's -- and each view's ProxyConsts
+// (one box, eight cameras: K differs per view).  By value in the kernel-argument segment and indexed by the wave-uniform view number, as
+// ViewsTargetConsts::target: scalar loads.  table[v] carries the CUT rectangle (x0 .. y1, gx0, gy0, tiles_x); the output stays addressed by the frame's.
+struct ViewsProxyConsts {
+    uint32_t first_block[MAX_VIEWS + 1];   // prefix of the views' tile counts (a view without a tile adds nothing); entries behind n_views repeat the total
+    ProxyConsts proxy[MAX_VIEWS];          // entries of views without a tile and behind n_views are zero: no tile maps to them
+};
+struct ViewsProxyTargetConsts {
+    ViewsProxyConsts p;
+    TargetConsts target[MAX_VIEWS];        // as ViewsTargetConsts::target
+};
 
 hipError_t launch_render(int flags, int split, const RenderConsts &rc, hipStream_t stream, int tile_list_blocks = 0);  // > 0: rc.tile_order lists that many tiles of the rect's grid
 // the proxy draws: one lane per ray, row-major grid of the rect in rc; flags = a draw's family without KF_PROXY (proxy_family_supported)
@@ -187,6 +199,12 @@ hipError_t launch_render_views(int flags, int light_steps, const RenderConsts *t
 // batches are launch_render_views with the pitch in RenderConsts::out_pitch)
 bool views_target_family_supported(int flags);
 hipError_t launch_render_views_target(int flags, int light_steps, const RenderConsts *table_dev, const ViewsTargetConsts &vtc, hipStream_t stream);
+// the multi-view proxy draws (atmo_render_views_proxy[_target], include/atmo_views_proxy.h): the KF_VIEWS | KF_PROXY [| KF_TARGET] kernels over the
+// concatenation of every view's cut rectangle's grid, view-major and row-major; the same list of families
+bool views_proxy_family_supported(int flags);
+hipError_t launch_render_views_proxy(int flags, int light_steps, const RenderConsts *table_dev, const ViewsProxyConsts &vpc, hipStream_t stream);
+bool views_proxy_target_family_supported(int flags);
+hipError_t launch_render_views_proxy_target(int flags, int light_steps, const RenderConsts *table_dev, const ViewsProxyTargetConsts &vptc, hipStream_t stream);
 // the packed-target draws: the float draws' launches (grid, tile order, cost feedback, tile lists for the heavy-tile split) with the KF_TARGET kernels.
 // flags without KF_TARGET / KF_PROXY; target_family_supported says which (flags, split) exist.
 bool target_family_supported(int flags, int split);

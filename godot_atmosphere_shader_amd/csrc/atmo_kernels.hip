@@ -2027,7 +2027,7 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                   "packed targets: the default forms; two lanes per ray only as the heavy-tile form of the declared-sampler cloud kernels");
     static_assert(!VIEWPOS || (!LITE && !ATMO_REF && SPLIT == 1), "KF_VIEW_POS: the fast v2 march, one lane per ray");
     static_assert(!PROXY || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0), "proxy draws: the default forms, one lane per ray, row-major");
-    static_assert((FLAGS & KF_VIEWS) == 0 || (!VIEWPOS && !ATMO_REF && !PROXY && SPLIT == 1 && (FLAGS & KF_GEO) == 0),
+    static_assert((FLAGS & KF_VIEWS) == 0 || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0),
                   "multi-view draws: the default forms, one lane per ray, float or packed targets (KF_VIEWS | KF_TARGET: atmo_render_views_target_kernel)");
     constexpr bool DIET = !DIRECT && !((FLAGS & KF_CLOUDS) && (FLAGS & KF_CLOUD_LIGHT_RM));
     constexpr bool FASTMISS = (ATMO_FAST_MISS_MASK >> ((DIRECT ? 1 : 0) + (CLOUDS ? 2 : 0) + (LITE ? 4 : 0))) & 1;
@@ -2499,6 +2499,42 @@ __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_r
         const uint64_t dt = __builtin_amdgcn_s_memtime() - t0;
         atomicMax(&vtc.v.cost[tile], (uint32_t)(dt > 0xffffffffull ? 0xffffffffull : dt));
     }
+}
+// Several far-mode (proxy) views in one launch (KF_VIEWS | KF_PROXY [| KF_TARGET]; atmo_render_views_proxy[_target], include/atmo_views_proxy.h): the view
+// lookup of atmo_render_views_kernel in front of the proxy draw's shade_pixel.  table[view] carries the view's CUT rectangle -- the box's screen rectangle
+// inside its rect, as proxy_setup computes it per view -- so a block is a tile of that rectangle; there is no tile order and no cost recording (the grids
+// change every frame, as the single proxy draw's).  The eight ProxyConsts, and the eight TargetConsts of the packed form, sit by value in the
+// kernel-argument segment and are indexed by the wave-uniform view number: scalar loads, as ViewsTargetConsts::target.  Kernels of their own names (no
+// older kernel's name is a substring of them), so that every other kernel keeps its code to the byte.  Launch bounds as the float batch's (views_min_waves);
+// no loop padding: like the single proxy kernels, the headline family's twins sit where the compiler puts them (profiles/views/README.md "Proxy batches").
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_proxy_kernel(const RenderConsts *__restrict__ table,
+                                                                                                        const ViewsProxyConsts vpc) {
+    static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) == 0, "multi-view proxy kernels carry KF_VIEWS | KF_PROXY");
+    const uint32_t tile = blockIdx.x;
+    uint32_t view = 0;   // as atmo_render_views_kernel: the last view whose first block is <= tile
+#pragma unroll
+    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vpc.first_block[i] ? 1u : 0u;
+    view = __builtin_amdgcn_readfirstlane(view);
+    const RenderConsts &rc = table[view];
+    const uint32_t local = tile - vpc.first_block[view];
+    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, &vpc.proxy[view]);
+}
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_proxy_target_kernel(const RenderConsts *__restrict__ table,
+                                                                                                               const ViewsProxyTargetConsts vptc) {
+    static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0,
+                  "multi-view proxy target kernels carry KF_VIEWS | KF_PROXY | KF_TARGET");
+    const uint32_t tile = blockIdx.x;
+    uint32_t view = 0;
+#pragma unroll
+    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vptc.p.first_block[i] ? 1u : 0u;
+    view = __builtin_amdgcn_readfirstlane(view);
+    const RenderConsts &rc = table[view];
+    const uint32_t local = tile - vptc.p.first_block[view];
+    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, &vptc.p.proxy[view], &vptc.target[view]);
 }
 
 // Stable counting sort of the tiles by the cost a recording draw measured, heaviest class first; clears the costs for
@@ -3316,6 +3352,68 @@ hipError_t launch_render_views_target(int flags, int light_steps, const RenderCo
 }
 bool views_target_family_supported(int flags) { return views_family_supported(flags) && target_family_supported(flags, 1); }   // the two lists' intersection: the same list
 
+// ---- multi-view proxy launchers (float and packed): the same families, one lane per ray, no tile order
+template <int FLAGS, int LSTEPS>
+static hipError_t launch_vp(const RenderConsts *table, const ViewsProxyConsts &vpc, hipStream_t stream) {
+    const uint32_t total = vpc.first_block[MAX_VIEWS];
+    if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((atmo_render_views_proxy_kernel<FLAGS | KF_VIEWS | KF_PROXY, LSTEPS>), dim3(total), dim3(TILE_W * TILE_H), 0, stream, table, vpc);
+    return hipGetLastError();
+}
+template <int FLAGS, int LSTEPS>
+static hipError_t launch_vpt(const RenderConsts *table, const ViewsProxyTargetConsts &vptc, hipStream_t stream) {
+    const uint32_t total = vptc.p.first_block[MAX_VIEWS];
+    if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((atmo_render_views_proxy_target_kernel<FLAGS | KF_VIEWS | KF_PROXY | KF_TARGET, LSTEPS>), dim3(total), dim3(TILE_W * TILE_H), 0, stream,
+                       table, vptc);
+    return hipGetLastError();
+}
+#define ATMO_VP_FAMILIES                                                          \
+    ATMO_VP_CASE(0)                                                               \
+    ATMO_VP_CASE_DIRECT(KF_LIGHT_DIRECT)                                          \
+    ATMO_VP_CASE(KF_PRECISE | KF_CLOUDS)                                          \
+    ATMO_VP_CASE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)                      \
+    ATMO_VP_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)                 \
+    ATMO_VP_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT) \
+    ATMO_VP_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)                            \
+    ATMO_VP_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)        \
+    ATMO_VP_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)   \
+    ATMO_VP_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT) \
+    ATMO_VP_CASE(KF_PRECISE | KF_LITE)                                            \
+    ATMO_VP_CASE(KF_PRECISE | KF_LITE | KF_CLOUDS)                                \
+    ATMO_VP_CASE(KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS)
+hipError_t launch_render_views_proxy(int flags, int light_steps, const RenderConsts *table, const ViewsProxyConsts &vpc, hipStream_t stream) {
+#define ATMO_VP_CASE(F) case (F): return launch_vp<(F), 0>(table, vpc, stream);
+#define ATMO_VP_CASE_DIRECT(F) case (F): return light_steps == 8 ? launch_vp<(F), 8>(table, vpc, stream) : launch_vp<(F), 0>(table, vpc, stream);   // as launch_render_views
+    switch (flags) {
+        ATMO_VP_FAMILIES
+    default: return hipErrorInvalidValue;   // (the host asks views_proxy_family_supported first)
+    }
+#undef ATMO_VP_CASE
+#undef ATMO_VP_CASE_DIRECT
+}
+bool views_proxy_family_supported(int flags) { return proxy_family_supported(flags); }
+hipError_t launch_render_views_proxy_target(int flags, int light_steps, const RenderConsts *table, const ViewsProxyTargetConsts &vptc, hipStream_t stream) {
+    // one format per batch, and every view that owns tiles has a target
+    int format = -1;
+    for (int i = 0; i < MAX_VIEWS; ++i) {
+        if (vptc.p.first_block[i + 1] == vptc.p.first_block[i]) continue;
+        const TargetConsts &t = vptc.target[i];
+        if (t.pixels == nullptr || (t.format != TF_RGBA16F && t.format != TF_RGBA8_UNORM) || (format >= 0 && t.format != format)) return hipErrorInvalidValue;
+        format = t.format;
+    }
+#define ATMO_VP_CASE(F) case (F): return launch_vpt<(F), 0>(table, vptc, stream);
+#define ATMO_VP_CASE_DIRECT(F) case (F): return light_steps == 8 ? launch_vpt<(F), 8>(table, vptc, stream) : launch_vpt<(F), 0>(table, vptc, stream);
+    switch (flags) {
+        ATMO_VP_FAMILIES
+    default: return hipErrorInvalidValue;   // (the host asks views_proxy_target_family_supported first)
+    }
+#undef ATMO_VP_CASE
+#undef ATMO_VP_CASE_DIRECT
+}
+#undef ATMO_VP_FAMILIES
+bool views_proxy_target_family_supported(int flags) { return proxy_family_supported(flags); }
+
 // store_target<FMT> on caller-supplied arrays (atmo_debug_store_target): the encode and the blend on chosen values, one pixel per lane
 template <int FMT>
 __global__ __launch_bounds__(256) void atmo_store_target_kernel(const float4 *__restrict__ src, void *dst, size_t n, int composite) {
@@ -3343,6 +3441,10 @@ const char *render_kernel_name(int flags, int light_steps, int split) {
     static thread_local char name[64];
     const bool v2_precise = (flags & KF_ATMO_REF) != 0;  // its light march is a run-time loop
     const int lsteps = ((flags & KF_LIGHT_DIRECT) && light_steps == 8 && !v2_precise && !(flags & KF_VIEW_POS)) ? 8 : 0;
+    if ((flags & KF_VIEWS) && (flags & KF_PROXY)) {
+        snprintf(name, sizeof(name), "atmo_render_views_proxy%s_kernel<%d, %d>", (flags & KF_TARGET) ? "_target" : "", flags, lsteps);
+        return name;
+    }
     if (flags & KF_PROXY) {
         snprintf(name, sizeof(name), "atmo_render_proxy%s_kernel<%d, %d>", (flags & KF_TARGET) ? "_target" : "", flags, lsteps);
         return name;

@@ -663,6 +663,10 @@ class PlanetAtmosphere:
         outs[i] may also be float16 (RGBA16F) or uint8 (RGBA8_UNORM) tensors, and their rows may be further apart than a row (a row pitch: the two
         halves of one double-wide image, say): the batch then stores or blends in that format (atmo_render_views_target; one format per batch).
         target="rgba16f" | "rgba8" allocates such outputs."""
+        return self._render_views(cameras, depths, outs, rects, composite, stream, time, target, None)
+
+    def _render_views(self, cameras, depths, outs, rects, composite, stream, time, target, proxy):
+        """`render_views` (proxy None) and `render_views_proxy` (proxy = (model, box_size): zero-filled allocations, the proxy entry points)."""
         import torch
 
         n = len(cameras)
@@ -682,7 +686,7 @@ class PlanetAtmosphere:
             x0, y0, x1, y1 = rects[i] if rects is not None and rects[i] is not None else (0, 0, cam.width, cam.height)
             rows, cols = (cam.height, cam.width) if composite else (y1 - y0, x1 - x0)
             if outs[i] is None:
-                outs[i] = _new_target(rows, cols, target, depth.device, zero=False)
+                outs[i] = _new_target(rows, cols, target, depth.device, zero=proxy is not None)
             # a contiguous float32 tensor (None), or the N.AtmoTarget of a float16 / uint8 / pitched one
             tgts[i] = _colour_target(outs[i], rows, cols, f"view {i}: {'scene_rgba' if composite else 'out'}")
         if n == 0:
@@ -693,12 +697,54 @@ class PlanetAtmosphere:
             stream = stream.cuda_stream
         if all(t is None for t in tgts):
             views = self.prepare_views(cameras, [d.data_ptr() for d in depths], [o.data_ptr() for o in outs], rects, time)
-            self.render_views_prepared(views, n, composite, stream)
+            if proxy is not None:
+                self.render_views_proxy_prepared(views, n, proxy[0], proxy[1], composite, stream)
+            else:
+                self.render_views_prepared(views, n, composite, stream)
         else:
             tgts = [t if t is not None else N.AtmoTarget(o.data_ptr(), N.TARGET_RGBA32F, 0) for t, o in zip(tgts, outs)]
             views = self.prepare_views_target(cameras, [d.data_ptr() for d in depths], tgts, rects, time)
-            self.render_views_target_prepared(views, n, composite, stream)
+            if proxy is not None:
+                self.render_views_proxy_target_prepared(views, n, proxy[0], proxy[1], composite, stream)
+            else:
+                self.render_views_target_prepared(views, n, composite, stream)
         return outs
+
+    # ---- several far-mode views in one launch (include/atmo_views_proxy.h) -----------------------------------------------------------
+    def proxy_model(self):
+        """The native model matrix of the proxy draws: global_transform, column-major."""
+        return (C.c_float * 16)(*[float(x) for x in col_major(self.global_transform)])
+
+    def render_views_proxy_prepared(self, views, n_views: int, model, box_size: float, composite: bool = False, stream: int = 0):
+        """Enqueue one far-mode batch from `prepare_views` (atmo_render_views_proxy): `model` from `proxy_model`, one launch for all views."""
+        self._bake_if_needed(stream)
+        rc = self._lib.atmo_render_views_proxy(self._ctx, views, int(n_views), model, C.c_float(box_size), int(bool(composite)), C.c_void_p(stream or 0))
+        N.check(self._ctx, rc)
+
+    def render_views_proxy_target_prepared(self, views, n_views: int, model, box_size: float, composite: bool = False, stream: int = 0):
+        """Enqueue one far-mode batch from `prepare_views_target` (atmo_render_views_proxy_target)."""
+        self._bake_if_needed(stream)
+        rc = self._lib.atmo_render_views_proxy_target(self._ctx, views, int(n_views), model, C.c_float(box_size), int(bool(composite)),
+                                                      C.c_void_p(stream or 0))
+        N.check(self._ctx, rc)
+
+    def render_views_proxy(self, cameras, depths, outs=None, rects=None, composite: bool = False, stream=None, time: float = 0.0,
+                           box_size: float | None = None, target=None):
+        """`render_views` through the far mode's BoxMesh: several views of this planet's proxy in ONE launch (atmo_render_views_proxy).  View i is bit
+        for bit `render_proxy(cameras[i], depths[i], outs[i], rects[i], box_size=box_size)` -- or, with composite=True, `render_proxy_composite` --:
+        only the box's passing front-face fragments are written.  One box per batch: edge `box_size` (default proxy_box_size(cameras[0])) centred on
+        global_transform.  outs=None allocates zero-filled outputs, as `render_proxy` does; float16 / uint8 / pitched tensors go through
+        atmo_render_views_proxy_target (one format per batch)."""
+        if box_size is None:
+            box_size = self.proxy_box_size(cameras[0] if len(cameras) else None)
+        return self._render_views(cameras, depths, outs, rects, composite, stream, time, target, (self.proxy_model(), float(box_size)))
+
+    def draw_views(self, cameras, depths, scene_rgbas, rects=None, stream=None, time: float = 0.0):
+        """`draw` for several views in one launch: near mode `render_views(..., composite=True)`, far mode `render_views_proxy(..., composite=True)`
+        with the BoxMesh of the reference's size.  Returns the list of scene buffers."""
+        if self._mode == MODE_NEAR:
+            return self.render_views(cameras, depths, scene_rgbas, rects=rects, composite=True, stream=stream, time=time)
+        return self.render_views_proxy(cameras, depths, scene_rgbas, rects=rects, composite=True, stream=stream, time=time)
 
     # ---- the far-mode draw: the BoxMesh proxy (include/atmo_scene.h) ---------------------------------------------------------------
     def proxy_box_size(self, camera=None) -> float:

@@ -119,6 +119,14 @@ int atmo_debug_proxy_launch_rect(AtmoContext *ctx, const AtmoFrame *frame, const
 struct AtmoView;
 int atmo_debug_views_layout(AtmoContext *ctx, const struct AtmoView *views, int n_views, int *first_block /* n_views + 1 */, int *grid /* 2 per view */);
 
+/* The launch a proxy batch (include/atmo_views_proxy.h, atmo_render_views_proxy) of this context would make -- host geometry only, so it works on a host-only
+ * context: rects[4 i .. 4 i + 3] = x0, y0, x1, y1 of the pixels view i's part of the launch covers (atmo_debug_proxy_launch_rect of that view alone; the empty
+ * rectangle x0, y0, x0, y0 of its frame for a view whose rect is empty), grid[2 i], grid[2 i + 1] = that rectangle's tile grid (0 x 0: the view has no
+ * tile), first_block[i] = the first block of view i in the one-dimensional launch, first_block[n_views] = the launch's block count.  The argument and mode
+ * checks are atmo_render_views_proxy's (ATMO_E_ARG / ATMO_E_STATE); the device pointers of the views are not looked at. */
+int atmo_debug_views_proxy_layout(AtmoContext *ctx, const struct AtmoView *views, int n_views, const float *model_matrix, float box_size,
+                                  int *first_block /* n_views + 1 */, int *grid /* 2 per view */, int *rects /* 4 per view */);
+
 /* Diagnostics (no reference counterpart): the render kernels' store_target<format> (include/atmo_target.h: the encode, and the composite's decode / blend /
  * encode) on caller-supplied DEVICE arrays, so that the contract can be tested on chosen values rather than on what a scene happens to produce:
  * dst[i] = encode(src[i]) for composite == 0, encode(blend(src[i], decode(dst[i]))) otherwise; src = n_pixels x 4 floats (16-byte aligned), dst = n_pixels

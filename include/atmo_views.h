@@ -59,7 +59,7 @@
  *
  * PACKED AND PITCHED COLOUR TARGETS per view (RGBA16F / RGBA8 / a row pitch, and with the pitch the side-by-side halves of one image): atmo_views_target.h.
  *
- * WHAT COMES NEXT (not part of this header): proxy (far-mode) views, motion-aware orders per view.
+ * WHAT COMES NEXT (not part of this header): motion-aware orders per view.  Far-mode (proxy) views are atmo_views_proxy.h.
  */
 #ifndef ATMO_VIEWS_H
 #define ATMO_VIEWS_H

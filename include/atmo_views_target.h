@@ -56,7 +56,8 @@
  * of the 8-step baked-LUT atmosphere without clouds (25 us draws): +6.0 %, which is as much as either arm's own spread there (5-7 %) -- the batch's copy of
  * the per-view constants and its event are not amortised by two such draws (eight 1280 x 720 views are: 0.79).
  *
- * WHAT COMES NEXT (not part of this header): proxy (far-mode) views, motion-aware orders per view, the heavy-tile lane split for batches.
+ * WHAT COMES NEXT (not part of this header): motion-aware orders per view, the heavy-tile lane split for batches.  Far-mode (proxy) views of both batches are
+ * atmo_views_proxy.h.
  */
 #ifndef ATMO_VIEWS_TARGET_H
 #define ATMO_VIEWS_TARGET_H
