@@ -4,11 +4,12 @@
 //
 //   hipcc -O2 -I include examples/atmo_render_file.cpp -L godot_atmosphere_shader_amd -latmo_hip \
 //         -Wl,-rpath,$PWD/godot_atmosphere_shader_amd -o atmo_render_file
-//   ./atmo_render_file <frame.bin> <depth.bin> <out.bin> <planet_radius> <atmosphere_height> <u_density> <view_steps> [--target rgba16f|rgba8]
+//   ./atmo_render_file <frame.bin> <depth.bin> <out.bin> <planet_radius> <atmosphere_height> <u_density> <view_steps> [--target rgba16f|rgba8|rgba8_srgb|bgra8|bgra8_srgb|a2b10g10r10]
 //
 // frame.bin = one AtmoFrame struct; depth.bin = viewport_h*viewport_w floats; out.bin = rect RGBA float4.
 // tests/test_gpu_parity.py::test_native_host_matches_python_binding checks the bytes against the Python path.
-// --target (include/atmo_target.h): the draw stores RGBA16F (8 bytes per pixel) or RGBA8_UNORM (4) instead, as into a renderer's own colour buffer;
+// --target (include/atmo_target.h): the draw stores RGBA16F (8 bytes per pixel), or RGBA8_UNORM / RGBA8_SRGB / BGRA8_UNORM / BGRA8_SRGB /
+// A2B10G10R10_UNORM (4), instead, as into a renderer's own colour buffer;
 // out.bin then holds those pixels, tightly packed (tests/test_target_gpu.py::test_native_host_draws_into_a_packed_target).
 #include <hip/hip_runtime_api.h>
 
@@ -50,9 +51,13 @@ int main(int argc, char **argv) {
     if (argc == 10 && std::strcmp(argv[8], "--target") == 0) {
         if (std::strcmp(argv[9], "rgba16f") == 0) format = ATMO_TARGET_RGBA16F;
         else if (std::strcmp(argv[9], "rgba8") == 0) format = ATMO_TARGET_RGBA8_UNORM;
-        else { std::fprintf(stderr, "--target: rgba16f or rgba8\n"); return 2; }
+        else if (std::strcmp(argv[9], "rgba8_srgb") == 0) format = ATMO_TARGET_RGBA8_SRGB;
+        else if (std::strcmp(argv[9], "bgra8") == 0) format = ATMO_TARGET_BGRA8_UNORM;
+        else if (std::strcmp(argv[9], "bgra8_srgb") == 0) format = ATMO_TARGET_BGRA8_SRGB;
+        else if (std::strcmp(argv[9], "a2b10g10r10") == 0) format = ATMO_TARGET_A2B10G10R10_UNORM;
+        else { std::fprintf(stderr, "--target: rgba16f, rgba8, rgba8_srgb, bgra8, bgra8_srgb or a2b10g10r10\n"); return 2; }
     } else if (argc != 8) {
-        std::fprintf(stderr, "usage: %s frame.bin depth.bin out.bin planet_radius atmosphere_height u_density view_steps [--target rgba16f|rgba8]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s frame.bin depth.bin out.bin planet_radius atmosphere_height u_density view_steps [--target rgba16f|rgba8|rgba8_srgb|bgra8|bgra8_srgb|a2b10g10r10]\n", argv[0]);
         return 2;
     }
     AtmoContext *ctx = nullptr;

@@ -33,7 +33,8 @@ DEBUG_SYMBOLS = (
 )
 # every symbol include/atmo_scene.h declares: drawing several atmospheres into one frame (the far-mode BoxMesh draw)
 SCENE_SYMBOLS = ("atmo_render_proxy", "atmo_render_proxy_composite")
-# every symbol include/atmo_target.h declares: the same draws into a renderer's colour buffer (RGBA16F / RGBA8_UNORM / RGBA32F, with a row pitch).
+# every symbol include/atmo_target.h declares: the same draws into a renderer's colour buffer (RGBA32F, RGBA16F, RGBA8_UNORM / _SRGB, BGRA8_UNORM / _SRGB,
+# A2B10G10R10_UNORM, with a row pitch).
 # The ABI version stays 5: a host detects the feature by these symbols and atmo_target_pixel_bytes(format) != 0.
 TARGET_SYMBOLS = ("atmo_target_pixel_bytes", "atmo_render_target", "atmo_render_proxy_target")
 # every symbol include/atmo_views.h declares: several views of one planet in one launch (stereo eyes, split screen, probe faces).  The ABI version stays 5:
@@ -48,6 +49,7 @@ VIEWS_TARGET_SYMBOLS = ("atmo_render_views_target",)
 VIEWS_PROXY_SYMBOLS = ("atmo_render_views_proxy", "atmo_render_views_proxy_target")
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
+TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
 
 
 class AtmoFrame(C.Structure):

@@ -15,6 +15,7 @@
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
+#include "atmo_srgb_tables.h"
 
 #include <array>
 #include <cmath>
@@ -2313,12 +2314,24 @@ int atmo_render_proxy_composite(AtmoContext *ctx, const AtmoFrame *frame, const 
 }
 
 // ---- packed colour targets (include/atmo_target.h) ----------------------------------------------------------------------------------------
+// (the sRGB tables the kernels carry: 256 entries each, THRESH[0] the filler 0.0, DECODE[0] = 0.0 and DECODE[255] = 1.0 -- a truncated header fails here)
+static constexpr uint32_t k_srgb_thresh_bits[] = {ATMO_SRGB_THRESH_BITS}, k_srgb_decode_bits[] = {ATMO_SRGB_DECODE_BITS};
+static_assert(sizeof(k_srgb_thresh_bits) == 1024 && sizeof(k_srgb_decode_bits) == 1024 && k_srgb_thresh_bits[0] == 0u && k_srgb_decode_bits[0] == 0u &&
+                  k_srgb_decode_bits[255] == 0x3f800000u,
+              "atmo_srgb_tables.h");
+static_assert((int)ATMO_TARGET_RGBA8_SRGB == (int)atmo::TF_RGBA8_SRGB && (int)ATMO_TARGET_BGRA8_UNORM == (int)atmo::TF_BGRA8_UNORM &&
+                  (int)ATMO_TARGET_BGRA8_SRGB == (int)atmo::TF_BGRA8_SRGB && (int)ATMO_TARGET_A2B10G10R10_UNORM == (int)atmo::TF_A2B10G10R10_UNORM,
+              "TargetFormat == AtmoTargetFormat");
 int atmo_target_pixel_bytes(int format) {
     switch (format) {
     case ATMO_TARGET_RGBA32F: return 16;
     case ATMO_TARGET_RGBA16F: return 8;
-    case ATMO_TARGET_RGBA8_UNORM: return 4;
-    default: return 0;
+    case ATMO_TARGET_RGBA8_UNORM:
+    case ATMO_TARGET_RGBA8_SRGB:
+    case ATMO_TARGET_BGRA8_UNORM:
+    case ATMO_TARGET_BGRA8_SRGB:
+    case ATMO_TARGET_A2B10G10R10_UNORM: return 4;
+    default: return 0;   // 3 .. 15 and everything from 20 up: unknown
     }
 }
 
@@ -2349,7 +2362,7 @@ static int target_family(AtmoContext *ctx, const char *who, const AtmoFrame *fra
     int flags = 0, split = 1;
     launch_shape(ctx, frame, &flags, &split, nullptr);
     if (!atmo::target_family_supported(flags, split))
-        return fail(ctx, ATMO_E_STATE, std::string(who) + ": no RGBA16F / RGBA8 kernel for this context's mode (packed targets exist for the default forms: "
+        return fail(ctx, ATMO_E_STATE, std::string(who) + ": no RGBA16F / RGBA8 kernel for this context's mode (packed targets, every format but RGBA32F, exist for the default forms: "
                                                           "atmo_set_precision 1, up to 32 view steps, one lane per ray); RGBA32F targets work in every mode");
     return ATMO_OK;
 }
@@ -2637,7 +2650,7 @@ int views_float_outputs(AtmoContext *ctx, const char *who, const AtmoView *views
 }
 // The target batches' argument checks (atmo_render_views_target, atmo_render_views_proxy_target): the count and every view's frame (views_check_frames;
 // *done as there), then per view atmo_render_target's checks, one format per batch, and the overlap rule of include/atmo_views_target.h on the bytes it
-// writes -- `rows` rows of `row_bytes`, `pitch` apart, from `base`.  Fills args; *packed: the batch's format is RGBA16F or RGBA8_UNORM.
+// writes -- `rows` rows of `row_bytes`, `pitch` apart, from `base`.  Fills args; *packed: the batch's format is not RGBA32F.
 int views_target_outputs(AtmoContext *ctx, const char *who, const AtmoViewTarget *views, int n_views, int composite, ViewArg *args, ViewsLayout &L,
                          bool *done, bool *packed) {
     for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) {
@@ -2685,7 +2698,7 @@ int views_target_outputs(AtmoContext *ctx, const char *who, const AtmoViewTarget
             return fail(ctx, ATMO_E_ARG, std::string(who) + ": views " + std::to_string(j) + " and " + std::to_string(i) + " write overlapping memory");
         }
     }
-    *packed = format == ATMO_TARGET_RGBA16F || format == ATMO_TARGET_RGBA8_UNORM;
+    *packed = atmo::target_format_packed(format);
     return ATMO_OK;
 }
 

@@ -149,11 +149,14 @@ struct ProxyConsts {
 // A packed colour target (include/atmo_target.h): where and how the kernels of the KF_TARGET family store.  A kernel argument of its own, behind
 // RenderConsts (and ProxyConsts), so that the float kernels' argument layout -- and with it their code -- stays what it was.  RenderConsts::out is not read
 // by these kernels; out_x0 / out_y0 / composite / store_discards mean what they mean to the float kernels.
-enum TargetFormat : int { TF_RGBA32F = 0, TF_RGBA16F = 1, TF_RGBA8_UNORM = 2 };   // == AtmoTargetFormat
+enum TargetFormat : int { TF_RGBA32F = 0, TF_RGBA16F = 1, TF_RGBA8_UNORM = 2,
+                          TF_RGBA8_SRGB = 16, TF_BGRA8_UNORM = 17, TF_BGRA8_SRGB = 18, TF_A2B10G10R10_UNORM = 19 };   // == AtmoTargetFormat
+// the formats the KF_TARGET kernels store: everything but RGBA32F; 8 bytes a pixel for RGBA16F, 4 for every other one
+inline bool target_format_packed(int format) { return format == TF_RGBA16F || format == TF_RGBA8_UNORM || (format >= TF_RGBA8_SRGB && format <= TF_A2B10G10R10_UNORM); }
 struct TargetConsts {
     void *pixels;          // the pixel (out_x0, out_y0) maps to
     int32_t pitch_bytes;   // bytes from one row to the next
-    int32_t format;        // TF_RGBA16F or TF_RGBA8_UNORM (RGBA32F targets are drawn by the float kernels: a pitch in whole pixels is all they need);
+    int32_t format;        // a packed format (RGBA32F targets are drawn by the float kernels: a pitch in whole pixels is all they need);
                            // uniform, read only where a pixel is addressed and stored
 };
 

@@ -26,6 +26,7 @@
 //   optical_depth.gdshader:17-31,45-68                  LUT bake                 -> atmo_bake_kernel
 #include "atmo_device.h"
 #include "atmo_layout.h"
+#include "atmo_srgb_tables.h"
 
 #include <cstdio>
 
@@ -1961,6 +1962,35 @@ __device__ __forceinline__ uint32_t unorm8_rne(float x) {
     const float c = fminf(fmaxf(x, 0.0f), 1.0f);
     return (uint32_t)__builtin_rintf(c * 255.0f);
 }
+// UNORM fields of 10 and 2 bits (A2B10G10R10): the same rule with 1023 and 3
+template <int MAXV>
+__device__ __forceinline__ uint32_t unorm_rne(float x) {
+#pragma clang fp contract(off)
+    const float c = fminf(fmaxf(x, 0.0f), 1.0f);
+    return (uint32_t)__builtin_rintf(c * (float)MAXV);
+}
+// sRGB (RGBA8_SRGB, BGRA8_SRGB): the two tables of atmo_srgb_tables.h are the contract.  Read-only device globals, 2 KB, read with per-lane loads.
+// g_srgb_thresh has a 257th entry, +inf, so that [code + 1] is a load for every code.
+__device__ const uint32_t g_srgb_thresh[257] = {ATMO_SRGB_THRESH_BITS 0x7f800000u};
+__device__ const uint32_t g_srgb_decode[256] = {ATMO_SRGB_DECODE_BITS};
+__device__ __forceinline__ float srgb8_decode(uint32_t byte) { return __uint_as_float(g_srgb_decode[byte]); }
+// code(x) = #{k in 1 .. 255 : x >= THRESH[k]}, NaN -> 0, without a loop: a guess g = rint(255 E(c)) from the fast log2 / exp2, then one step down or
+// up against THRESH[g] and THRESH[g + 1].  The guess is E evaluated in fp32 with v_log_f32 / v_exp_f32 (1 ulp each): the exponent's error is below
+// 2^-20 for c >= 0.0031308 (|log2 c| < 8.4), so 255 E is off by less than 0.001 of a code and g is the table's code or its neighbour; the step makes it the
+// table's whatever the guess's last bits do.  (tests/test_target_formats_gpu.py holds every threshold, its neighbours and a 2^-16 grid to the table.)
+__device__ __forceinline__ uint32_t srgb8_encode(float x) {
+#pragma clang fp contract(off)
+    const float c = fminf(fmaxf(x, 0.0f), 1.0f);   // NaN -> 0 (fmaxf returns its number)
+    const float curve = 1.055f * __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(c) * (1.0f / 2.4f)) - 0.055f;
+    const float e = c <= 0.0031308f ? 12.92f * c : curve;
+    const int g = min(max((int)__builtin_rintf(255.0f * e), 0), 255);
+    const float t0 = __uint_as_float(g_srgb_thresh[g]), t1 = __uint_as_float(g_srgb_thresh[g + 1]);   // THRESH[0] = 0 <= c < +inf = [256]
+    return (uint32_t)(g - (c < t0 ? 1 : 0) + (c >= t1 ? 1 : 0));
+}
+// The formats as three properties: BGRA = RGBA with bytes 0 and 2 exchanged; sRGB = R, G, B through the tables, A as UNORM8.
+template <int FMT> constexpr bool tf_bgra = FMT == TF_BGRA8_UNORM || FMT == TF_BGRA8_SRGB;
+template <int FMT> constexpr bool tf_srgb = FMT == TF_RGBA8_SRGB || FMT == TF_BGRA8_SRGB;
+template <int FMT> constexpr bool tf_bytes4 = FMT == TF_RGBA8_UNORM || FMT == TF_RGBA8_SRGB || FMT == TF_BGRA8_UNORM || FMT == TF_BGRA8_SRGB;
 template <int FMT>
 __device__ __forceinline__ float4 target_decode(const void *p) {
     if constexpr (FMT == TF_RGBA16F) {
@@ -1970,6 +2000,17 @@ __device__ __forceinline__ float4 target_decode(const void *p) {
         const uint32_t w = *(const uint32_t *)p;
         return make_float4(ieee_div((float)(w & 255u), 255.0f), ieee_div((float)((w >> 8) & 255u), 255.0f), ieee_div((float)((w >> 16) & 255u), 255.0f),
                            ieee_div((float)(w >> 24), 255.0f));
+    } else if constexpr (tf_bytes4<FMT>) {
+        const uint32_t w = *(const uint32_t *)p;
+        const uint32_t b0 = w & 255u, b1 = (w >> 8) & 255u, b2 = (w >> 16) & 255u;
+        const uint32_t r = tf_bgra<FMT> ? b2 : b0, b = tf_bgra<FMT> ? b0 : b2;
+        const float a = ieee_div((float)(w >> 24), 255.0f);
+        if constexpr (tf_srgb<FMT>) return make_float4(srgb8_decode(r), srgb8_decode(b1), srgb8_decode(b), a);
+        else return make_float4(ieee_div((float)r, 255.0f), ieee_div((float)b1, 255.0f), ieee_div((float)b, 255.0f), a);
+    } else if constexpr (FMT == TF_A2B10G10R10_UNORM) {
+        const uint32_t w = *(const uint32_t *)p;
+        return make_float4(ieee_div((float)(w & 1023u), 1023.0f), ieee_div((float)((w >> 10) & 1023u), 1023.0f), ieee_div((float)((w >> 20) & 1023u), 1023.0f),
+                           ieee_div((float)(w >> 30), 3.0f));
     } else {
         return *(const float4 *)p;
     }
@@ -1980,6 +2021,12 @@ __device__ __forceinline__ void target_encode(void *p, const float4 &v) {
         *(uint2 *)p = make_uint2(half_bits_rne(v.x) | (half_bits_rne(v.y) << 16), half_bits_rne(v.z) | (half_bits_rne(v.w) << 16));
     } else if constexpr (FMT == TF_RGBA8_UNORM) {
         *(uint32_t *)p = unorm8_rne(v.x) | (unorm8_rne(v.y) << 8) | (unorm8_rne(v.z) << 16) | (unorm8_rne(v.w) << 24);
+    } else if constexpr (tf_bytes4<FMT>) {
+        const float c0 = tf_bgra<FMT> ? v.z : v.x, c2 = tf_bgra<FMT> ? v.x : v.z;
+        if constexpr (tf_srgb<FMT>) *(uint32_t *)p = srgb8_encode(c0) | (srgb8_encode(v.y) << 8) | (srgb8_encode(c2) << 16) | (unorm8_rne(v.w) << 24);
+        else *(uint32_t *)p = unorm8_rne(c0) | (unorm8_rne(v.y) << 8) | (unorm8_rne(c2) << 16) | (unorm8_rne(v.w) << 24);
+    } else if constexpr (FMT == TF_A2B10G10R10_UNORM) {
+        *(uint32_t *)p = unorm_rne<1023>(v.x) | (unorm_rne<1023>(v.y) << 10) | (unorm_rne<1023>(v.z) << 20) | (unorm_rne<3>(v.w) << 30);
     } else {
         *(float4 *)p = v;
     }
@@ -1999,12 +2046,23 @@ __device__ __forceinline__ void store_target(void *p, const float4 &src, const b
     }
     target_encode<FMT>(p, o);
 }
-// the format as the uniform run-time field it is in the KF_TARGET kernels: one scalar branch behind the march
+// the format as the uniform run-time field it is in the KF_TARGET kernels: one scalar branch chain behind the march, RGBA16F and RGBA8_UNORM first.
+// The four newer formats are told apart on an opaque copy of the field (an empty asm on its SGPR: no instruction): one chain over all seven values is
+// lowered as a binary search that starts at 16 and lays the two older formats' code out behind the newer ones'; this way their two tests and their
+// blocks stay where they were, right behind the march.
 __device__ __forceinline__ void store_target_rt(const int format, void *p, const float4 &src, const bool composite) {
     if (format == TF_RGBA16F) store_target<TF_RGBA16F>(p, src, composite);
-    else store_target<TF_RGBA8_UNORM>(p, src, composite);
+    else if (format == TF_RGBA8_UNORM) store_target<TF_RGBA8_UNORM>(p, src, composite);
+    else {
+        int newer = format;
+        asm volatile("" : "+s"(newer));
+        if (newer == TF_RGBA8_SRGB) store_target<TF_RGBA8_SRGB>(p, src, composite);
+        else if (newer == TF_BGRA8_SRGB) store_target<TF_BGRA8_SRGB>(p, src, composite);
+        else if (newer == TF_BGRA8_UNORM) store_target<TF_BGRA8_UNORM>(p, src, composite);
+        else store_target<TF_A2B10G10R10_UNORM>(p, src, composite);
+    }
 }
-// a discarded fragment of a plain draw: (0, 0, 0, 0) is all-zero bits in both packed formats
+// a discarded fragment of a plain draw: (0, 0, 0, 0) is all-zero bits in every packed format (sRGB code 0 is 0.0), 8 bytes of them in RGBA16F, else 4
 __device__ __forceinline__ void store_target_zero_rt(const int format, void *p) {
     if (format == TF_RGBA16F) *(uint2 *)p = make_uint2(0u, 0u);
     else *(uint32_t *)p = 0u;
@@ -3269,7 +3327,7 @@ static hipError_t launch_render_target_grid(int flags, int split, const RenderCo
     }
 }
 hipError_t launch_render_target(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream, int tile_list_blocks) {
-    if (tc.format != TF_RGBA16F && tc.format != TF_RGBA8_UNORM) return hipErrorInvalidValue;
+    if (!target_format_packed(tc.format)) return hipErrorInvalidValue;
     g_launch_blocks = tile_list_blocks;
     const hipError_t e = launch_render_target_grid(flags, split, rc, tc, stream);
     g_launch_blocks = 0;
@@ -3292,7 +3350,7 @@ static hipError_t launch_pt_direct(const RenderConsts &rc, const ProxyConsts &pc
     return rc.light_steps == 8 ? launch_pt<FLAGS, 8>(rc, pc, tc, stream) : launch_pt<FLAGS, 0>(rc, pc, tc, stream);
 }
 hipError_t launch_render_proxy_target(int flags, const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, hipStream_t stream) {
-    if (tc.format != TF_RGBA16F && tc.format != TF_RGBA8_UNORM) return hipErrorInvalidValue;
+    if (!target_format_packed(tc.format)) return hipErrorInvalidValue;
     switch (flags) {
     case 0: return launch_pt<0, 0>(rc, pc, tc, stream);
     case KF_LIGHT_DIRECT: return launch_pt_direct<KF_LIGHT_DIRECT>(rc, pc, tc, stream);
@@ -3326,7 +3384,7 @@ hipError_t launch_render_views_target(int flags, int light_steps, const RenderCo
     for (int i = 0; i < MAX_VIEWS; ++i) {
         if (vtc.v.first_block[i + 1] == vtc.v.first_block[i]) continue;
         const TargetConsts &t = vtc.target[i];
-        if (t.pixels == nullptr || (t.format != TF_RGBA16F && t.format != TF_RGBA8_UNORM) || (format >= 0 && t.format != format)) return hipErrorInvalidValue;
+        if (t.pixels == nullptr || !target_format_packed(t.format) || (format >= 0 && t.format != format)) return hipErrorInvalidValue;
         format = t.format;
     }
 #define ATMO_VT_CASE(F) case (F): return launch_vt<(F), 0>(table, vtc, stream);
@@ -3399,7 +3457,7 @@ hipError_t launch_render_views_proxy_target(int flags, int light_steps, const Re
     for (int i = 0; i < MAX_VIEWS; ++i) {
         if (vptc.p.first_block[i + 1] == vptc.p.first_block[i]) continue;
         const TargetConsts &t = vptc.target[i];
-        if (t.pixels == nullptr || (t.format != TF_RGBA16F && t.format != TF_RGBA8_UNORM) || (format >= 0 && t.format != format)) return hipErrorInvalidValue;
+        if (t.pixels == nullptr || !target_format_packed(t.format) || (format >= 0 && t.format != format)) return hipErrorInvalidValue;
         format = t.format;
     }
 #define ATMO_VP_CASE(F) case (F): return launch_vpt<(F), 0>(table, vptc, stream);
@@ -3419,7 +3477,7 @@ template <int FMT>
 __global__ __launch_bounds__(256) void atmo_store_target_kernel(const float4 *__restrict__ src, void *dst, size_t n, int composite) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    constexpr size_t BYTES = FMT == TF_RGBA16F ? 8 : (FMT == TF_RGBA8_UNORM ? 4 : 16);
+    constexpr size_t BYTES = FMT == TF_RGBA32F ? 16 : (FMT == TF_RGBA16F ? 8 : 4);
     store_target<FMT>((char *)dst + i * BYTES, src[i], composite != 0);
 }
 hipError_t launch_store_target(int format, int composite, const float *src_rgba, void *dst, size_t n, hipStream_t stream) {
@@ -3431,6 +3489,10 @@ hipError_t launch_store_target(int format, int composite, const float *src_rgba,
     case TF_RGBA32F: hipLaunchKernelGGL(atmo_store_target_kernel<TF_RGBA32F>, grid, block, 0, stream, src, dst, n, composite); break;
     case TF_RGBA16F: hipLaunchKernelGGL(atmo_store_target_kernel<TF_RGBA16F>, grid, block, 0, stream, src, dst, n, composite); break;
     case TF_RGBA8_UNORM: hipLaunchKernelGGL(atmo_store_target_kernel<TF_RGBA8_UNORM>, grid, block, 0, stream, src, dst, n, composite); break;
+    case TF_RGBA8_SRGB: hipLaunchKernelGGL(atmo_store_target_kernel<TF_RGBA8_SRGB>, grid, block, 0, stream, src, dst, n, composite); break;
+    case TF_BGRA8_UNORM: hipLaunchKernelGGL(atmo_store_target_kernel<TF_BGRA8_UNORM>, grid, block, 0, stream, src, dst, n, composite); break;
+    case TF_BGRA8_SRGB: hipLaunchKernelGGL(atmo_store_target_kernel<TF_BGRA8_SRGB>, grid, block, 0, stream, src, dst, n, composite); break;
+    case TF_A2B10G10R10_UNORM: hipLaunchKernelGGL(atmo_store_target_kernel<TF_A2B10G10R10_UNORM>, grid, block, 0, stream, src, dst, n, composite); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -550,7 +550,9 @@ class PlanetAtmosphere:
         (rect_h, rect_w, 4), allocated when None.  Work is enqueued on `stream` (a torch stream, a raw
         hipStream_t int, or None for torch's current stream).  Returns `out`.
         `out` may also be a float16 (RGBA16F) or uint8 (RGBA8_UNORM) tensor, and its rows may be further apart than a row (a row pitch): the draw then
-        stores in that format (atmo_render_target; godot_atmosphere_shader_amd.targets states the encoding).  target="rgba16f" | "rgba8" allocates one."""
+        stores in that format (atmo_render_target; godot_atmosphere_shader_amd.targets states the encoding).  target="rgba16f" | "rgba8" allocates one.
+        A uint8 tensor means RGBA8_UNORM; target="rgba8_srgb" | "bgra8" | "bgra8_srgb" | "a2b10g10r10" next to `out` says that its bytes are that format's
+        instead, and alone allocates such a tensor.  A name that contradicts the tensor's dtype raises ValueError."""
         import torch
 
         frame = self.make_frame(camera, time, rect)
@@ -561,7 +563,7 @@ class PlanetAtmosphere:
             raise ValueError("depth must have shape (viewport_h, viewport_w)")
         if out is None:
             out = _new_target(y1 - y0, x1 - x0, target, depth.device, zero=False)
-        tgt = _colour_target(out, y1 - y0, x1 - x0, "out")
+        tgt = _colour_target(out, y1 - y0, x1 - x0, "out", target)
         if stream is None:
             stream = torch.cuda.current_stream(depth.device).cuda_stream
         elif hasattr(stream, "cuda_stream"):
@@ -589,16 +591,16 @@ class PlanetAtmosphere:
                                    C.c_void_p(stream or 0))
         N.check(self._ctx, rc)
 
-    def render_composite(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0):
+    def render_composite(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0, target=None):
         """The draw including the renderer's blend stage: shades `rect` and alpha-blends the result over
         `scene_rgba` (CUDA float32 (H, W, 4), the scene colour buffer) in place, as Godot's blend_mix does with
         ALBEDO/ALPHA; discarded fragments leave the scene untouched.  Returns `scene_rgba`.
         A float16 / uint8 `scene_rgba` (RGBA16F / RGBA8_UNORM, optionally with a row pitch) is blended in its own format: decoded, blended in fp32,
-        encoded once (atmo_render_target)."""
+        encoded once (atmo_render_target).  `target` names the format of a uint8 buffer that is not RGBA8_UNORM, as in `render`."""
         import torch
 
         frame = self.make_frame(camera, time, rect)
-        tgt = _colour_target(scene_rgba, camera.height, camera.width, "scene_rgba")
+        tgt = _colour_target(scene_rgba, camera.height, camera.width, "scene_rgba", target)
         if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
                 and tuple(depth.shape) == (camera.height, camera.width)):
             raise TypeError("depth must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w)")
@@ -662,7 +664,8 @@ class PlanetAtmosphere:
         outputs.  The tensors the views write must not overlap.  One native call; returns the list of output tensors.
         outs[i] may also be float16 (RGBA16F) or uint8 (RGBA8_UNORM) tensors, and their rows may be further apart than a row (a row pitch: the two
         halves of one double-wide image, say): the batch then stores or blends in that format (atmo_render_views_target; one format per batch).
-        target="rgba16f" | "rgba8" allocates such outputs."""
+        target="rgba16f" | "rgba8" allocates such outputs; target="rgba8_srgb" | "bgra8" | "bgra8_srgb" | "a2b10g10r10" names the format of uint8 outs, or
+        allocates them, as in `render`."""
         return self._render_views(cameras, depths, outs, rects, composite, stream, time, target, None)
 
     def _render_views(self, cameras, depths, outs, rects, composite, stream, time, target, proxy):
@@ -688,7 +691,7 @@ class PlanetAtmosphere:
             if outs[i] is None:
                 outs[i] = _new_target(rows, cols, target, depth.device, zero=proxy is not None)
             # a contiguous float32 tensor (None), or the N.AtmoTarget of a float16 / uint8 / pitched one
-            tgts[i] = _colour_target(outs[i], rows, cols, f"view {i}: {'scene_rgba' if composite else 'out'}")
+            tgts[i] = _colour_target(outs[i], rows, cols, f"view {i}: {'scene_rgba' if composite else 'out'}", target)
         if n == 0:
             return outs
         if stream is None:
@@ -739,12 +742,12 @@ class PlanetAtmosphere:
             box_size = self.proxy_box_size(cameras[0] if len(cameras) else None)
         return self._render_views(cameras, depths, outs, rects, composite, stream, time, target, (self.proxy_model(), float(box_size)))
 
-    def draw_views(self, cameras, depths, scene_rgbas, rects=None, stream=None, time: float = 0.0):
+    def draw_views(self, cameras, depths, scene_rgbas, rects=None, stream=None, time: float = 0.0, target=None):
         """`draw` for several views in one launch: near mode `render_views(..., composite=True)`, far mode `render_views_proxy(..., composite=True)`
         with the BoxMesh of the reference's size.  Returns the list of scene buffers."""
         if self._mode == MODE_NEAR:
-            return self.render_views(cameras, depths, scene_rgbas, rects=rects, composite=True, stream=stream, time=time)
-        return self.render_views_proxy(cameras, depths, scene_rgbas, rects=rects, composite=True, stream=stream, time=time)
+            return self.render_views(cameras, depths, scene_rgbas, rects=rects, composite=True, stream=stream, time=time, target=target)
+        return self.render_views_proxy(cameras, depths, scene_rgbas, rects=rects, composite=True, stream=stream, time=time, target=target)
 
     # ---- the far-mode draw: the BoxMesh proxy (include/atmo_scene.h) ---------------------------------------------------------------
     def proxy_box_size(self, camera=None) -> float:
@@ -781,28 +784,29 @@ class PlanetAtmosphere:
             raise TypeError("depth must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w)")
         if out is None:
             out = _new_target(y1 - y0, x1 - x0, target, depth.device, zero=True)
-        tgt = _colour_target(out, y1 - y0, x1 - x0, "out")
+        tgt = _colour_target(out, y1 - y0, x1 - x0, "out", target)
         self._proxy_call(self._lib.atmo_render_proxy, camera, depth, out, rect, stream, time, box_size, tgt, 0)
         return out
 
-    def render_proxy_composite(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0, box_size: float | None = None):
+    def render_proxy_composite(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0, box_size: float | None = None, target=None):
         """`render_composite` through the far mode's BoxMesh (atmo_render_proxy_composite; a float16 / uint8 / pitched `scene_rgba`:
-        atmo_render_proxy_target).  Returns `scene_rgba`."""
+        atmo_render_proxy_target; `target`: as `render_composite`).  Returns `scene_rgba`."""
         import torch
 
-        tgt = _colour_target(scene_rgba, camera.height, camera.width, "scene_rgba")
+        tgt = _colour_target(scene_rgba, camera.height, camera.width, "scene_rgba", target)
         if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
                 and tuple(depth.shape) == (camera.height, camera.width)):
             raise TypeError("depth must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w)")
         self._proxy_call(self._lib.atmo_render_proxy_composite, camera, depth, scene_rgba, rect, stream, time, box_size, tgt, 1)
         return scene_rgba
 
-    def draw(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0):
+    def draw(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0, target=None):
         """The draw Godot makes for this node in its current mode (set by `_process`): near mode the fullscreen quad (`render_composite`), far mode
-        the BoxMesh of the reference's size (`render_proxy_composite`).  Returns `scene_rgba` (float32, float16 or uint8; a row pitch is taken from its row stride)."""
+        the BoxMesh of the reference's size (`render_proxy_composite`).  Returns `scene_rgba` (float32, float16 or uint8; a row pitch is taken from its row stride;
+        `target` names the format of a uint8 buffer that is not RGBA8_UNORM)."""
         if self._mode == MODE_NEAR:
-            return self.render_composite(camera, depth, scene_rgba, rect=rect, stream=stream, time=time)
-        return self.render_proxy_composite(camera, depth, scene_rgba, rect=rect, stream=stream, time=time)
+            return self.render_composite(camera, depth, scene_rgba, rect=rect, stream=stream, time=time, target=target)
+        return self.render_proxy_composite(camera, depth, scene_rgba, rect=rect, stream=stream, time=time, target=target)
 
     def render_raw(self, frame: dict, depth_ptr: int, out_ptr: int, stream: int = 0):
         """`render` on raw device addresses (what a non-torch host would call)."""
@@ -883,10 +887,12 @@ class PlanetAtmosphere:
         return n.value, ms.value
 
 
-def _colour_target(t, rows: int, cols: int, what: str):
+def _colour_target(t, rows: int, cols: int, what: str, target=None):
     """How a colour tensor is drawn into: None for a contiguous float32 (rows, cols, 4) tensor -- the float entry points --, else the N.AtmoTarget
     of a float16 (RGBA16F), uint8 (RGBA8_UNORM) or float32 tensor whose pixels are contiguous and whose rows may be further apart (the row pitch
-    is the tensor's row stride): include/atmo_target.h."""
+    is the tensor's row stride): include/atmo_target.h.  `target` names the format of the tensor's bits where the dtype does not say it: a uint8
+    tensor is RGBA8_UNORM unless target="rgba8_srgb" | "bgra8" | "bgra8_srgb" | "a2b10g10r10" (the bytes as they lie in memory); a name that
+    contradicts the dtype is a ValueError."""
     import torch
 
     from . import targets as T
@@ -894,20 +900,27 @@ def _colour_target(t, rows: int, cols: int, what: str):
     fmts = {torch.float32: T.RGBA32F, torch.float16: T.RGBA16F, torch.uint8: T.RGBA8}
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in fmts and tuple(t.shape) == (rows, cols, 4)):
         raise ValueError(f"{what} must be a CUDA float32, float16 or uint8 tensor of shape ({rows}, {cols}, 4)")
-    if t.dtype == torch.float32 and t.is_contiguous():
+    fmt = fmts[t.dtype]
+    if target is not None:
+        fmt = T.format_id(target)
+        if np.dtype(T.DTYPES[fmt]).name != str(t.dtype).replace("torch.", ""):
+            raise ValueError(f"{what}: target={target!r} is a {np.dtype(T.DTYPES[fmt]).name} format, the tensor is {t.dtype}")
+    if fmt == T.RGBA32F and t.is_contiguous():
         return None
     if not (t.stride(2) == 1 and t.stride(1) == 4 and (rows == 1 or t.stride(0) >= 4 * cols)):
         raise ValueError(f"{what}: the pixels of a row must be contiguous and the row stride at least a row (a row pitch is the only stride supported)")
-    return N.AtmoTarget(t.data_ptr(), fmts[t.dtype], (t.stride(0) if rows > 1 else 4 * cols) * t.element_size())
+    return N.AtmoTarget(t.data_ptr(), fmt, (t.stride(0) if rows > 1 else 4 * cols) * t.element_size())
 
 
 def _new_target(rows: int, cols: int, target, device, zero: bool):
-    """The tensor a draw allocates: float32, or the packed format named by target="rgba16f" | "rgba8"."""
+    """The tensor a draw allocates: float32, or the packed format named by target="rgba16f" | "rgba8" | "rgba8_srgb" | "bgra8" | "bgra8_srgb" |
+    "a2b10g10r10" (uint8 (rows, cols, 4) for all but the first: the bytes as they lie in memory)."""
     import torch
 
     from . import targets as T
 
-    dtype = {T.RGBA32F: torch.float32, T.RGBA16F: torch.float16, T.RGBA8: torch.uint8}[T.format_id(target) if target is not None else T.RGBA32F]
+    np_dtype = T.DTYPES[T.format_id(target) if target is not None else T.RGBA32F]
+    dtype = {np.float32: torch.float32, np.float16: torch.float16, np.uint8: torch.uint8}[np_dtype]
     return (torch.zeros if zero else torch.empty)((rows, cols, 4), dtype=dtype, device=device)
 
 
@@ -926,10 +939,12 @@ def draw_order(nodes, camera) -> list:
     return [nodes[i] for i in sorted(range(len(nodes)), key=lambda i: -dist[i])]
 
 
-def draw_atmospheres(nodes, camera, depth, scene_rgba, stream=None, time: float = 0.0):
+def draw_atmospheres(nodes, camera, depth, scene_rgba, stream=None, time: float = 0.0, target=None):
     """Draws several PlanetAtmosphere nodes into one frame as Godot does: each node's draw for its current mode (`PlanetAtmosphere.draw`: the
     fullscreen quad near, the BoxMesh far), composited over `scene_rgba` in place, back to front (`draw_order`).  Returns `scene_rgba`, which may be the renderer's own RGBA16F / RGBA8_UNORM buffer
-    (a float16 / uint8 tensor, optionally with a row pitch): every node then blends in that format."""
+    (a float16 / uint8 tensor, optionally with a row pitch): every node then blends in that format.  `target` names the format of a uint8 buffer that is not
+    RGBA8_UNORM ("rgba8_srgb", "bgra8", "bgra8_srgb", "a2b10g10r10")."""
+    kw = {} if target is None else {"target": target}
     for node in draw_order(list(nodes), camera):
-        node.draw(camera, depth, scene_rgba, stream=stream, time=time)
+        node.draw(camera, depth, scene_rgba, stream=stream, time=time, **kw)
     return scene_rgba
