@@ -375,3 +375,76 @@ def test_new_formats_need_the_default_forms(mode):
                     assert lib.atmo_render_views_proxy_target(ctx, v, 2, m, C.c_float(10.0), composite, None) == N.ATMO_E_STATE
     finally:
         lib.atmo_destroy(ctx)
+
+
+# ---- the code bracket of a tolerance (tests/test_target_formats_kernels_gpu.py holds the kernels' frames to the CPU oracle with it) ------------------
+
+def stored_fields(buf, fmt):
+    """The stored codes of (..., 4) bytes of a format 16 .. 19 in R, G, B, A order, as int64: the bytes un-swizzled, or the word's 10- / 2-bit fields."""
+    b = np.ascontiguousarray(buf, dtype=np.uint8)
+    if T.format_id(fmt) == T.A2B10G10R10:
+        w = b.view("<u4")[..., 0].astype(np.int64)
+        return np.stack([w & 1023, (w >> 10) & 1023, (w >> 20) & 1023, w >> 30], axis=-1)
+    return (b[..., [2, 1, 0, 3]] if T.format_id(fmt) in (T.BGRA8, T.BGRA8_SRGB) else b).astype(np.int64)
+
+
+def code_bracket(o, fmt, tol):
+    """(code(lo), code(hi)) for lo, hi = o -/+ tol * max(1, |o|), per field: code = targets.encode of that field (sRGB through SRGB_THRESH, UNORM with 255 /
+    1023 / 3).  Every code function is monotone (non-decreasing) in its fp32 argument, and rounding lo and hi to fp32 is monotone too, so an fp32 x within the
+    tolerance of o has code(lo) <= code(x) <= code(hi): the bracket carries no quantisation term."""
+    o = np.asarray(o, dtype=np.float64)
+    m = tol * np.maximum(1.0, np.abs(o))
+    return stored_fields(T.encode(o - m, fmt), fmt), stored_fields(T.encode(o + m, fmt), fmt)
+
+
+def _bracket_sources():
+    th = T.SRGB_THRESH[1:]
+    grid = (np.arange(2 ** 17 + 1, dtype=np.float64) * 2.0 ** -16 - 0.5).astype(f32)           # [-0.5, 1.5] in steps of 2^-16, exact in fp32
+    return np.concatenate([th, np.nextafter(th, f32(-1.0)), np.nextafter(th, f32(2.0)), grid]).astype(f32)
+
+
+@pytest.mark.parametrize("fmt", NEW)
+def test_code_bracket_is_monotone_and_collapses_away_from_thresholds(fmt):
+    """code_bracket at common.TOL on every sRGB threshold with its fp32 neighbours and on a 2^-16 grid of [-0.5, 1.5], the same value in all four fields:
+    values within the tolerance encode inside the bracket; the bracket is one code wherever no threshold of the field lies within the tolerance (and never
+    more than two codes: 2 TOL max(1, |o|) is below the narrowest code, 1 / 3295 at the foot of the sRGB curve and 1 / 1023 in a 10-bit field)."""
+    from common import TOL
+
+    o = _bracket_sources()
+    lo, hi = code_bracket(np.stack([o] * 4, axis=-1), fmt, TOL)
+    assert lo.shape == hi.shape == (o.size, 4) and np.all(lo <= hi) and np.all(hi - lo <= 1)
+    m = TOL * np.maximum(1.0, np.abs(o.astype(np.float64)))
+    rng = np.random.default_rng(5)
+    for frac in (-1.0, -0.999, -0.5, 0.0, 0.5, 0.999, 1.0, None):
+        d = rng.uniform(-1.0, 1.0, size=o.size) if frac is None else frac
+        x64 = o.astype(np.float64) + d * m
+        x = x64.astype(f32)
+        # only fp32 values that do lie within the tolerance (the rounding of o + d m may step outside by half an ulp at d = +/-1)
+        inside = np.abs(x.astype(np.float64) - o.astype(np.float64)) <= m
+        assert inside.mean() > 0.4, frac
+        c = stored_fields(T.encode(np.stack([x] * 4, axis=-1), fmt), fmt)
+        assert np.all((lo <= c)[inside]) and np.all((c <= hi)[inside]), (fmt, frac)
+    # the endpoints themselves
+    assert np.array_equal(stored_fields(T.encode(np.stack([o.astype(np.float64) - m] * 4, axis=-1), fmt), fmt), lo)
+    # away from thresholds: one code.  The thresholds of a field, as reals: SRGB_THRESH[k], or (k + 0.5) / N of a UNORM field (the fp32 product's own rounding
+    # moves a UNORM threshold by less than 2^-22, allowed for below)
+    srgb = T.format_id(fmt) in (T.RGBA8_SRGB, T.BGRA8_SRGB)
+    tens = T.format_id(fmt) == T.A2B10G10R10
+    for field in range(4):
+        if srgb and field < 3:
+            edges = T.SRGB_THRESH[1:].astype(np.float64)
+        else:
+            n = (3 if field == 3 else 1023) if tens else 255
+            edges = (np.arange(n) + 0.5) / n
+        i = np.clip(np.searchsorted(edges, o.astype(np.float64)), 1, edges.size - 1)
+        dist = np.minimum(np.abs(o - edges[i - 1]), np.abs(o - edges[i]))
+        away = dist > m + 2.0 ** -20
+        assert away.mean() > 0.7, (fmt, field, away.mean())
+        assert np.array_equal(lo[away, field], hi[away, field]), (fmt, field)
+        wide = float((lo[:, field] != hi[:, field]).mean())
+        print(f"{fmt} field {field}: the bracket holds two codes for {wide:.4f} of the sources")
+        assert (lo[:, field] != hi[:, field]).any()              # ... and two next to one: the sources do straddle thresholds
+    # known answers (SRGB_THRESH[188] = D(187.5 / 255) = 0.49991 lies between 0.4999 and 0.5001; alpha 0.5 * 255 = 127.5 between 127.47 and 127.53)
+    assert [x.tolist() for x in code_bracket([[0.5, 0.0, 1.0, 0.5]], "rgba8_srgb", 1e-4)] == [[[187, 0, 255, 127]], [[188, 0, 255, 128]]]
+    assert [x.tolist() for x in code_bracket([[0.5, 0.0, 2.0, 0.5]], "a2b10g10r10", 1e-4)] == [[[511, 0, 1023, 1]], [[512, 0, 1023, 2]]]
+    assert stored_fields(np.array([[1, 2, 3, 4]], dtype=np.uint8), "bgra8").tolist() == [[3, 2, 1, 4]]

@@ -20,9 +20,10 @@ KF_VIEWS = 2048
 GUARD = 64                       # sentinel pixels in front of and behind every buffer
 PAD = 7                          # sentinel pixels behind every row of a pitched buffer
 FORMATS = ("rgba16f", "rgba8")
-BITS = {"rgba16f": np.uint16, "rgba8": np.uint8, "rgba32f": np.uint32}
-SENTINEL = {"rgba16f": 0x5A5A, "rgba8": 0xA5, "rgba32f": 0x7FC5A5A5}     # (0x7FC5A5A5: a NaN pattern no kernel produces)
-PX_BYTES = {"rgba16f": 8, "rgba8": 4, "rgba32f": 16}
+BYTE_FORMATS = ("rgba8", "rgba8_srgb", "bgra8", "bgra8_srgb", "a2b10g10r10")     # uint8 tensors, four bytes a pixel as they lie in memory
+BITS = {"rgba16f": np.uint16, "rgba32f": np.uint32, **{f: np.uint8 for f in BYTE_FORMATS}}
+SENTINEL = {"rgba16f": 0x5A5A, "rgba32f": 0x7FC5A5A5, **{f: 0xA5 for f in BYTE_FORMATS}}     # (0x7FC5A5A5: a NaN pattern no kernel produces)
+PX_BYTES = {"rgba16f": 8, "rgba32f": 16, **{f: 4 for f in BYTE_FORMATS}}
 
 
 class Buf:
@@ -58,7 +59,7 @@ class Buf:
 def _random_dst(shape, fmt, seed):
     """Pseudo-random destination bits: every finite half pattern / every byte / finite floats with alphas in [0, 1] are drawn from."""
     rng = np.random.default_rng(seed)
-    if fmt == "rgba8":
+    if fmt in BYTE_FORMATS:
         return rng.integers(0, 256, size=shape, dtype=np.uint8)
     if fmt == "rgba32f":
         a = rng.uniform(-0.25, 2.0, size=shape).astype(np.float32)
