@@ -2257,14 +2257,23 @@ static int proxy_setup(AtmoContext *ctx, const char *who, const AtmoFrame *f, co
     return ATMO_OK;
 }
 
-// The family a proxy draw of this context uses, or ATMO_E_STATE when there is no proxy kernel for its mode (proxy_family_supported).
+// The family a proxy draw of this context uses, or ATMO_E_STATE when there is no proxy kernel for its mode (default_family_supported).
 static int proxy_family(AtmoContext *ctx, const char *who, const AtmoFrame *frame, int *flags, bool *lod) {
     int split = 1;
     ATMO_TRY(draw_family(ctx, frame, flags, &split, lod));
-    if (split != 1 || !atmo::proxy_family_supported(*flags))
+    if (split != 1 || !atmo::default_family_supported(*flags))
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": no proxy kernel for this context's mode (proxy draws exist for the default forms: atmo_set_precision 1, "
                                                           "up to 32 view steps, one lane per ray)");
     return ATMO_OK;
+}
+
+// A proxy launch shades the CUT rectangle (proxy_setup's rect, gx tiles a row): the launch rectangle and grid origin of rc, whose output stays addressed as
+// draw_consts left it.  The grid origin: the rect's, rounded down to even under the declared sampler.
+static void proxy_cut_rect(const int *rect, bool lod, int gx, atmo::RenderConsts &rc) {
+    rc.x0 = rect[0]; rc.y0 = rect[1]; rc.x1 = rect[2]; rc.y1 = rect[3];
+    rc.gx0 = lod ? rect[0] & ~1 : rect[0];
+    rc.gy0 = lod ? rect[1] & ~1 : rect[1];
+    rc.tiles_x = gx;
 }
 
 static int proxy_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev, float *rgba_dev,
@@ -2291,10 +2300,7 @@ static int proxy_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *mod
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     atmo::RenderConsts rc;
     draw_consts(ctx, frame, depth_dev, rgba_dev, composite, pitch_px, tc != nullptr, rc);   // the output stays addressed by the FRAME's rect (plain) or the viewport (composite)
-    rc.x0 = rect[0]; rc.y0 = rect[1]; rc.x1 = rect[2]; rc.y1 = rect[3];
-    rc.gx0 = lod ? rect[0] & ~1 : rect[0];
-    rc.gy0 = lod ? rect[1] & ~1 : rect[1];
-    rc.tiles_x = gx;
+    proxy_cut_rect(rect, lod, gx, rc);
     hipStream_t s = (hipStream_t)stream;
     ATMO_TRY(tex_order(ctx, s));
     if (tc) HIP_TRY(ctx, atmo::launch_render_proxy_target(flags, rc, pc, *tc, s));
@@ -2445,6 +2451,15 @@ struct ViewArg {
     atmo::TargetConsts tc = {nullptr, 0, 0};   // packed targets (RGBA16F / RGBA8_UNORM)
 };
 
+// The float batches' views (AtmoView) as ViewArg: frame, depth and output; no pitch, no packed target.  Null views or a bad count: views_check_frames' to refuse.
+void view_args(const AtmoView *views, int n_views, ViewArg *args) {
+    for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) {
+        args[i].frame = &views[i].frame;
+        args[i].depth = views[i].depth_dev;
+        args[i].pixels = views[i].rgba_dev;
+    }
+}
+
 // The first half of what a batch needs no device for: the count and every view's frame checks.  *done: n_views == 0, nothing to draw whatever the
 // context's mode.
 int views_check_frames(AtmoContext *ctx, const char *who, bool have_views, const ViewArg *args, int n_views, ViewsLayout &L, bool *done) {
@@ -2467,7 +2482,7 @@ int views_check_frames(AtmoContext *ctx, const char *who, bool have_views, const
 int views_family_grid(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, bool packed, ViewsLayout &L) {
     int split = 1;
     ATMO_TRY(draw_family(ctx, args[0].frame, &L.flags, &split, &L.lod));
-    if (split != 1 || !(packed ? atmo::views_target_family_supported(L.flags) : atmo::views_family_supported(L.flags)))
+    if (split != 1 || !atmo::default_family_supported(L.flags))
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": no multi-view kernel for this context's mode (they exist for the default forms: atmo_set_precision 1, "
                                                           "up to 32 view steps, one lane per ray)");
     L.family = L.flags | atmo::KF_VIEWS | (packed ? atmo::KF_TARGET : 0);
@@ -2489,11 +2504,7 @@ int views_family_grid(AtmoContext *ctx, const char *who, const ViewArg *args, in
 }
 // Both halves, for the float batch (atmo_render_views, atmo_debug_views_layout): args[i] = views[i]'s frame, depth and output.
 int views_layout(AtmoContext *ctx, const char *who, const AtmoView *views, int n_views, ViewArg *args, ViewsLayout &L) {
-    for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) {
-        args[i].frame = &views[i].frame;
-        args[i].depth = views[i].depth_dev;
-        args[i].pixels = views[i].rgba_dev;
-    }
+    view_args(views, n_views, args);
     bool done = false;
     { const int rc0 = views_check_frames(ctx, who, views != nullptr, args, n_views, L, &done); if (rc0 != ATMO_OK || done) return rc0; }
     return views_family_grid(ctx, who, args, n_views, false, L);
@@ -2565,6 +2576,13 @@ static int views_ring_slot(AtmoContext *ctx, AtmoContext::ViewsSlot **out) {
     *out = &slot;
     return ATMO_OK;
 }
+// ... and the end of its use: behind the launch that reads it on stream s; the next batch takes the next slot
+static int views_ring_slot_used(AtmoContext *ctx, AtmoContext::ViewsSlot *slot, hipStream_t s) {
+    HIP_TRY(ctx, hipEventRecord(slot->done, s));
+    slot->in_flight = true;
+    ctx->views_next += 1;
+    return ATMO_OK;
+}
 // Everything a batch does once its arguments stand: the staging slot, the per-view constants, the tile order and its feedback, the ONE launch.  Shared by
 // atmo_render_views (packed == false: the float kernels, args[i].pitch_px) and atmo_render_views_target (packed: the KF_VIEWS | KF_TARGET kernels, args[i].tc).
 int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, int composite, bool packed, const ViewsLayout &L, void *stream) {
@@ -2615,9 +2633,7 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_
     if (packed) HIP_TRY(ctx, atmo::launch_render_views_target(L.flags, slot->host[first].light_steps, slot->dev, vtc, s));
     else HIP_TRY(ctx, atmo::launch_render_views(L.flags, slot->host[first].light_steps, slot->dev, vc, s));
     ATMO_TRY(timing_end(ctx, timing, s));
-    HIP_TRY(ctx, hipEventRecord(slot->done, s));
-    slot->in_flight = true;
-    ctx->views_next += 1;
+    ATMO_TRY(views_ring_slot_used(ctx, slot, s));
     if (plan.sort_side) ATMO_TRY(feedback_sort_side(ctx, *fb, (int)total, 1, plan, s));
     if (fb) fb->n += 1;
     hipEvent_t marker = nullptr;
@@ -2764,11 +2780,7 @@ int views_proxy_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, 
         atmo::RenderConsts &rc = slot->host[i];
         if (P.gx[i] == 0 || P.gy[i] == 0) { std::memset(&rc, 0, sizeof(rc)); continue; }
         draw_consts(ctx, P.frames[i], args[i].depth, (float *)args[i].pixels, composite != 0, args[i].pitch_px, packed, rc);
-        const int *rect = P.rect[i];
-        rc.x0 = rect[0]; rc.y0 = rect[1]; rc.x1 = rect[2]; rc.y1 = rect[3];
-        rc.gx0 = L.lod ? rect[0] & ~1 : rect[0];
-        rc.gy0 = L.lod ? rect[1] & ~1 : rect[1];
-        rc.tiles_x = P.gx[i];
+        proxy_cut_rect(P.rect[i], L.lod, P.gx[i], rc);
         vptc.p.proxy[i] = P.pc[i];
         if (packed) vptc.target[i] = args[i].tc;
         if (first < 0) first = i;
@@ -2778,9 +2790,7 @@ int views_proxy_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, 
     HIP_TRY(ctx, hipMemcpyAsync(slot->dev, slot->host, (size_t)n_views * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
     if (packed) HIP_TRY(ctx, atmo::launch_render_views_proxy_target(L.flags, slot->host[first].light_steps, slot->dev, vptc, s));
     else HIP_TRY(ctx, atmo::launch_render_views_proxy(L.flags, slot->host[first].light_steps, slot->dev, vptc.p, s));
-    HIP_TRY(ctx, hipEventRecord(slot->done, s));
-    slot->in_flight = true;
-    ctx->views_next += 1;
+    ATMO_TRY(views_ring_slot_used(ctx, slot, s));
     hipEvent_t marker = nullptr;
     return finish_draw(ctx, s, L.flags | atmo::KF_VIEWS | atmo::KF_PROXY | (packed ? atmo::KF_TARGET : 0), 1, false, &marker);
 }
@@ -2828,11 +2838,7 @@ int atmo_render_views_proxy(AtmoContext *ctx, const AtmoView *views, int n_views
     const char *who = "atmo_render_views_proxy";
     ViewsLayout L;
     ViewArg args[ATMO_MAX_VIEWS];
-    for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) {
-        args[i].frame = &views[i].frame;
-        args[i].depth = views[i].depth_dev;
-        args[i].pixels = views[i].rgba_dev;
-    }
+    view_args(views, n_views, args);
     bool done = false;
     ATMO_TRY(views_check_frames(ctx, who, views != nullptr, args, n_views, L, &done));
     ATMO_TRY(views_proxy_checks(ctx, who, model_matrix, box_size));
@@ -2866,7 +2872,7 @@ int atmo_debug_views_proxy_layout(AtmoContext *ctx, const AtmoView *views, int n
     if (!first_block || !grid || !rects) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null output");
     ViewsLayout L;
     ViewArg args[ATMO_MAX_VIEWS];
-    for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) args[i].frame = &views[i].frame;
+    view_args(views, n_views, args);   // (the frames are all this looks at)
     bool done = false;
     ATMO_TRY(views_check_frames(ctx, who, views != nullptr, args, n_views, L, &done));
     ATMO_TRY(views_proxy_checks(ctx, who, model_matrix, box_size));

@@ -190,26 +190,28 @@ struct ViewsProxyTargetConsts {
 };
 
 hipError_t launch_render(int flags, int split, const RenderConsts &rc, hipStream_t stream, int tile_list_blocks = 0);  // > 0: rc.tile_order lists that many tiles of the rect's grid
-// the proxy draws: one lane per ray, row-major grid of the rect in rc; flags = a draw's family without KF_PROXY (proxy_family_supported)
-bool proxy_family_supported(int flags);
+// Every launcher below draws the DEFAULT-FORM families (what a default context selects: one lane per ray, the precise cloud and v1 forms, up to 32 view
+// steps) and no other.  The list stands once, ATMO_DEFAULT_FAMILIES in atmo_kernels.hip: default_family_supported and launch_default_family are made from it.
+//   a new family:       one line at the end of that list; every launcher below then has it
+//   a new entry point:  its kernel, and one launch_default_family call whose lambda names that kernel and its family bits
+// flags = a draw's family WITHOUT the entry point's own bits (KF_PROXY, KF_VIEWS, KF_TARGET), which the launcher adds.
+bool default_family_supported(int flags);
+// the proxy draws: one lane per ray, row-major grid of the rect in rc
 hipError_t launch_render_proxy(int flags, const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream);
-// the multi-view draws: one lane per ray; flags = a draw's family without KF_VIEWS (views_family_supported: the proxy draws' list); table_dev holds one
-// RenderConsts per view (light_steps is the context's: the same in all of them); total_blocks = vc.first_block[MAX_VIEWS]
-bool views_family_supported(int flags);
+// the multi-view draws: one lane per ray; table_dev holds one RenderConsts per view (light_steps is the context's: the same in all of them);
+// total_blocks = vc.first_block[MAX_VIEWS]
 hipError_t launch_render_views(int flags, int light_steps, const RenderConsts *table_dev, const ViewsConsts &vc, hipStream_t stream);
 // the multi-view draws into packed colour targets (atmo_render_views_target, include/atmo_views_target.h): the same launch with the KF_VIEWS | KF_TARGET
-// kernels; vtc.target[v] is view v's target, every non-empty view in the one format vtc.target[first non-empty].format (RGBA16F or RGBA8_UNORM: RGBA32F
-// batches are launch_render_views with the pitch in RenderConsts::out_pitch)
-bool views_target_family_supported(int flags);
+// kernels; vtc.target[v] is view v's target, every non-empty view in the one packed format vtc.target[first non-empty].format (RGBA32F batches are
+// launch_render_views with the pitch in RenderConsts::out_pitch)
 hipError_t launch_render_views_target(int flags, int light_steps, const RenderConsts *table_dev, const ViewsTargetConsts &vtc, hipStream_t stream);
 // the multi-view proxy draws (atmo_render_views_proxy[_target], include/atmo_views_proxy.h): the KF_VIEWS | KF_PROXY [| KF_TARGET] kernels over the
-// concatenation of every view's cut rectangle's grid, view-major and row-major; the same list of families
-bool views_proxy_family_supported(int flags);
+// concatenation of every view's cut rectangle's grid, view-major and row-major
 hipError_t launch_render_views_proxy(int flags, int light_steps, const RenderConsts *table_dev, const ViewsProxyConsts &vpc, hipStream_t stream);
-bool views_proxy_target_family_supported(int flags);
 hipError_t launch_render_views_proxy_target(int flags, int light_steps, const RenderConsts *table_dev, const ViewsProxyTargetConsts &vptc, hipStream_t stream);
 // the packed-target draws: the float draws' launches (grid, tile order, cost feedback, tile lists for the heavy-tile split) with the KF_TARGET kernels.
-// flags without KF_TARGET / KF_PROXY; target_family_supported says which (flags, split) exist.
+// target_family_supported says which (flags, split) exist: the default families with split 1 and the two declared-sampler cloud families with split 2;
+// launch_render_target also takes KF_LIGHT_DIRECT | KF_GEO (the geometric-order twin; ask target_family_supported without KF_GEO).
 bool target_family_supported(int flags, int split);
 hipError_t launch_render_target(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream, int tile_list_blocks = 0);
 hipError_t launch_render_proxy_target(int flags, const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, hipStream_t stream);

@@ -29,6 +29,7 @@
 #include "atmo_srgb_tables.h"
 
 #include <cstdio>
+#include <type_traits>
 
 namespace atmo {
 
@@ -3088,389 +3089,256 @@ void render_grid(const RenderConsts &rc, int split, int *tiles_x, int *tiles_y) 
     *tiles_y = (rc.y1 - rc.gy0 + th - 1) / th;
 }
 
-// Blocks of the launch in flight: 0 = the whole grid of the rect; n > 0 = a tile-list draw (atmo_render_tiles): n blocks, block b shades
-// tile rc.tile_order[b] of that grid.  (A plain variable instead of a parameter threaded through the 80-case dispatch below; the host API
-// is single-threaded per context and sets it around one launch_render call.)
-static thread_local int g_launch_blocks = 0;
-
-template <int FLAGS, int LSTEPS, int SPLIT>
-static hipError_t launch_s(const RenderConsts &rc, hipStream_t stream) {
+// A draw's launch over the tile grid of the rect in rc: blocks = 0 launches the whole grid; blocks = n > 0 is a tile-list draw (atmo_render_tiles): n blocks,
+// block b shades tile rc.tile_order[b] of that grid.  `more`: the kernel's arguments behind rc.
+template <class Kernel, class... More>
+static hipError_t launch_tiles(Kernel kernel, int split, const RenderConsts &rc, int blocks, hipStream_t stream, const More &...more) {
     int gx, gy;
-    render_grid(rc, SPLIT, &gx, &gy);
+    render_grid(rc, split, &gx, &gy);
     if (gx != rc.tiles_x) return hipErrorInvalidValue;
     dim3 grid(gx, gy);
-    if (g_launch_blocks > 0) {
+    if (blocks > 0) {
         if (rc.tile_order == nullptr) return hipErrorInvalidValue;
-        grid = dim3(g_launch_blocks, 1);
+        grid = dim3(blocks, 1);
     }
-    if constexpr (render_sgpr_cap80(FLAGS))
-        hipLaunchKernelGGL((atmo_render_kernel_s80<FLAGS, LSTEPS, SPLIT>), grid, dim3(TILE_W * TILE_H), 0, stream, rc);
-    else
-        hipLaunchKernelGGL((atmo_render_kernel<FLAGS, LSTEPS, SPLIT>), grid, dim3(TILE_W * TILE_H), 0, stream, rc);
+    hipLaunchKernelGGL(kernel, grid, dim3(TILE_W * TILE_H), 0, stream, rc, more...);
+    return hipGetLastError();
+}
+// ... a proxy draw's: one lane per ray, the whole grid, which has a tile
+template <class Kernel, class... More>
+static hipError_t launch_rect(Kernel kernel, const RenderConsts &rc, hipStream_t stream, const More &...more) {
+    int gx, gy;
+    render_grid(rc, 1, &gx, &gy);
+    if (gx != rc.tiles_x || gx < 1 || gy < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, dim3(gx, gy), dim3(TILE_W * TILE_H), 0, stream, rc, more...);
+    return hipGetLastError();
+}
+// ... and a view batch's: one block per tile of the concatenation of the views' grids (first_block[MAX_VIEWS] of them); consts: the kernel's argument behind
+// the table
+template <class Kernel, class Consts>
+static hipError_t launch_batch(Kernel kernel, const uint32_t *first_block, const RenderConsts *table, const Consts &consts, hipStream_t stream) {
+    const uint32_t total = first_block[MAX_VIEWS];
+    if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, dim3(total), dim3(TILE_W * TILE_H), 0, stream, table, consts);
     return hipGetLastError();
 }
 
+template <int FLAGS, int LSTEPS, int SPLIT>
+static hipError_t launch_s(const RenderConsts &rc, hipStream_t stream, int blocks) {
+    if constexpr (render_sgpr_cap80(FLAGS)) return launch_tiles(atmo_render_kernel_s80<FLAGS, LSTEPS, SPLIT>, SPLIT, rc, blocks, stream);
+    else return launch_tiles(atmo_render_kernel<FLAGS, LSTEPS, SPLIT>, SPLIT, rc, blocks, stream);
+}
+
 template <int FLAGS, int LSTEPS>
-static hipError_t launch_t(const RenderConsts &rc, int split, hipStream_t stream) {
-    return split == 2 ? launch_s<FLAGS, LSTEPS, 2>(rc, stream) : launch_s<FLAGS, LSTEPS, 1>(rc, stream);
+static hipError_t launch_t(const RenderConsts &rc, int split, hipStream_t stream, int blocks) {
+    return split == 2 ? launch_s<FLAGS, LSTEPS, 2>(rc, stream, blocks) : launch_s<FLAGS, LSTEPS, 1>(rc, stream, blocks);
 }
 
 // direct light mode: 8 light steps (BASELINE's "32 view x 8 light") has an unrolled instantiation
 template <int FLAGS>
-static hipError_t launch_direct(const RenderConsts &rc, int split, hipStream_t stream) {
-    return rc.light_steps == 8 ? launch_t<FLAGS, 8>(rc, split, stream) : launch_t<FLAGS, 0>(rc, split, stream);
+static hipError_t launch_direct(const RenderConsts &rc, int split, hipStream_t stream, int blocks) {
+    return rc.light_steps == 8 ? launch_t<FLAGS, 8>(rc, split, stream, blocks) : launch_t<FLAGS, 0>(rc, split, stream, blocks);
 }
 
-static hipError_t launch_render_grid(int flags, int split, const RenderConsts &rc, hipStream_t stream);
+// The float draws (atmo_render, atmo_render_tiles): every form a context can select, the precision-0 / 2 and long-march (KF_VIEW_POS) ones included, so this
+// dispatch keeps a case list of its own.  tile_list_blocks: launch_tiles' blocks.
 hipError_t launch_render(int flags, int split, const RenderConsts &rc, hipStream_t stream, int tile_list_blocks) {
-    g_launch_blocks = tile_list_blocks;
-    const hipError_t e = launch_render_grid(flags, split, rc, stream);
-    g_launch_blocks = 0;
-    return e;
-}
-static hipError_t launch_render_grid(int flags, int split, const RenderConsts &rc, hipStream_t stream) {
     switch (flags) {
-    case 0: return launch_t<0, 0>(rc, split, stream);
-    case KF_LIGHT_DIRECT: return launch_direct<KF_LIGHT_DIRECT>(rc, split, stream);
+    case 0: return launch_t<0, 0>(rc, split, stream, tile_list_blocks);
+    case KF_LIGHT_DIRECT: return launch_direct<KF_LIGHT_DIRECT>(rc, split, stream, tile_list_blocks);
     case KF_LIGHT_DIRECT | KF_GEO:   // (one lane per ray; render_impl has filled rc.geo_rows)
-        return rc.light_steps == 8 ? launch_s<KF_LIGHT_DIRECT | KF_GEO, 8, 1>(rc, stream) : launch_s<KF_LIGHT_DIRECT | KF_GEO, 0, 1>(rc, stream);
-    case KF_CLOUDS: return launch_t<KF_CLOUDS, 0>(rc, split, stream);
-    case KF_CLOUDS | KF_LIGHT_DIRECT: return launch_direct<KF_CLOUDS | KF_LIGHT_DIRECT>(rc, split, stream);
-    case KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_t<KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, split, stream);
-    case KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT: return launch_direct<KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, split, stream);
-    case KF_LITE: return launch_t<KF_LITE, 0>(rc, split, stream);
-    case KF_LITE | KF_CLOUDS: return launch_t<KF_LITE | KF_CLOUDS, 0>(rc, split, stream);
+        return rc.light_steps == 8 ? launch_s<KF_LIGHT_DIRECT | KF_GEO, 8, 1>(rc, stream, tile_list_blocks) : launch_s<KF_LIGHT_DIRECT | KF_GEO, 0, 1>(rc, stream, tile_list_blocks);
+    case KF_CLOUDS: return launch_t<KF_CLOUDS, 0>(rc, split, stream, tile_list_blocks);
+    case KF_CLOUDS | KF_LIGHT_DIRECT: return launch_direct<KF_CLOUDS | KF_LIGHT_DIRECT>(rc, split, stream, tile_list_blocks);
+    case KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_t<KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, split, stream, tile_list_blocks);
+    case KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT: return launch_direct<KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, split, stream, tile_list_blocks);
+    case KF_LITE: return launch_t<KF_LITE, 0>(rc, split, stream, tile_list_blocks);
+    case KF_LITE | KF_CLOUDS: return launch_t<KF_LITE | KF_CLOUDS, 0>(rc, split, stream, tile_list_blocks);
     // the v2 atmosphere in the reference's operation order (atmo_set_precision 2), one lane per ray, run-time light-step loop
-    case KF_ATMO_REF: return launch_s<KF_ATMO_REF, 0, 1>(rc, stream);
-    case KF_ATMO_REF | KF_LIGHT_DIRECT: return launch_s<KF_ATMO_REF | KF_LIGHT_DIRECT, 0, 1>(rc, stream);
-    case KF_ATMO_REF | KF_PRECISE | KF_CLOUDS: return launch_s<KF_ATMO_REF | KF_PRECISE | KF_CLOUDS, 0, 1>(rc, stream);
-    case KF_ATMO_REF | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_s<KF_ATMO_REF | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT, 0, 1>(rc, stream);
-    case KF_ATMO_REF | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_s<KF_ATMO_REF | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0, 1>(rc, stream);
+    case KF_ATMO_REF: return launch_s<KF_ATMO_REF, 0, 1>(rc, stream, tile_list_blocks);
+    case KF_ATMO_REF | KF_LIGHT_DIRECT: return launch_s<KF_ATMO_REF | KF_LIGHT_DIRECT, 0, 1>(rc, stream, tile_list_blocks);
+    case KF_ATMO_REF | KF_PRECISE | KF_CLOUDS: return launch_s<KF_ATMO_REF | KF_PRECISE | KF_CLOUDS, 0, 1>(rc, stream, tile_list_blocks);
+    case KF_ATMO_REF | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_s<KF_ATMO_REF | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT, 0, 1>(rc, stream, tile_list_blocks);
+    case KF_ATMO_REF | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_s<KF_ATMO_REF | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0, 1>(rc, stream, tile_list_blocks);
     case KF_ATMO_REF | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
-        return launch_s<KF_ATMO_REF | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT, 0, 1>(rc, stream);
+        return launch_s<KF_ATMO_REF | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT, 0, 1>(rc, stream, tile_list_blocks);
     // ... under the declared cubemap sampler
-    case KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: return launch_s<KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS, 0, 1>(rc, stream);
+    case KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: return launch_s<KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS, 0, 1>(rc, stream, tile_list_blocks);
     case KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM:
-        return launch_s<KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0, 1>(rc, stream);
+        return launch_s<KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0, 1>(rc, stream, tile_list_blocks);
     case KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT:
-        return launch_s<KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT, 0, 1>(rc, stream);
+        return launch_s<KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT, 0, 1>(rc, stream, tile_list_blocks);
     case KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
-        return launch_s<KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT, 0, 1>(rc, stream);
+        return launch_s<KF_ATMO_REF | KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT, 0, 1>(rc, stream, tile_list_blocks);
     // precise cloud density (atmo_set_precision 1, the default of the cloud variants)
-    case KF_PRECISE | KF_CLOUDS: return launch_t<KF_PRECISE | KF_CLOUDS, 0>(rc, split, stream);
-    case KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_direct<KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, split, stream);
-    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_t<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, split, stream);
+    case KF_PRECISE | KF_CLOUDS: return launch_t<KF_PRECISE | KF_CLOUDS, 0>(rc, split, stream, tile_list_blocks);
+    case KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_direct<KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, split, stream, tile_list_blocks);
+    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_t<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, split, stream, tile_list_blocks);
     case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
-        return launch_direct<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, split, stream);
-    case KF_PRECISE | KF_LITE: return launch_t<KF_PRECISE | KF_LITE, 0>(rc, split, stream);
-    case KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_t<KF_PRECISE | KF_LITE | KF_CLOUDS, 0>(rc, split, stream);
+        return launch_direct<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, split, stream, tile_list_blocks);
+    case KF_PRECISE | KF_LITE: return launch_t<KF_PRECISE | KF_LITE, 0>(rc, split, stream, tile_list_blocks);
+    case KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_t<KF_PRECISE | KF_LITE | KF_CLOUDS, 0>(rc, split, stream, tile_list_blocks);
     // implicit cubemap LOD (atmo_set_sampler_lod 1): precise cloud kernels, one lane per ray
     // (split == 2: the cloud march on two lanes per ray -- what the host draws a frame's heavy tiles with, bit-identical to the one-lane form)
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: return launch_t<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS, 0>(rc, split, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_t<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, split, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_s<KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS, 0, 1>(rc, stream);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: return launch_t<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS, 0>(rc, split, stream, tile_list_blocks);
+    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_t<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, split, stream, tile_list_blocks);
+    case KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_s<KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS, 0, 1>(rc, stream, tile_list_blocks);
     // ... and with the direct light march of the atmosphere (one lane per ray; the two-lanes-per-ray launch shape has no LOD form)
     case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT:
-        return rc.light_steps == 8 ? launch_s<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT, 8, 1>(rc, stream)
-                                   : launch_s<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT, 0, 1>(rc, stream);
+        return rc.light_steps == 8 ? launch_s<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT, 8, 1>(rc, stream, tile_list_blocks)
+                                   : launch_s<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT, 0, 1>(rc, stream, tile_list_blocks);
     case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
-        return rc.light_steps == 8 ? launch_s<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT, 8, 1>(rc, stream)
-                                   : launch_s<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT, 0, 1>(rc, stream);
+        return rc.light_steps == 8 ? launch_s<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT, 8, 1>(rc, stream, tile_list_blocks)
+                                   : launch_s<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT, 0, 1>(rc, stream, tile_list_blocks);
     default: break;
     }
     // more than 32 view steps (KF_VIEW_POS, set by the host): the fast v2 march with the reference's position accumulation; one lane per ray,
     // run-time light-step loop
     if (flags & KF_VIEW_POS) {
         switch (flags & ~KF_VIEW_POS) {
-#define ATMO_VP_CASE(F) case (F): return launch_s<(F) | KF_VIEW_POS, 0, 1>(rc, stream);
-            ATMO_VP_CASE(0)
-            ATMO_VP_CASE(KF_LIGHT_DIRECT)
-            ATMO_VP_CASE(KF_CLOUDS)
-            ATMO_VP_CASE(KF_CLOUDS | KF_LIGHT_DIRECT)
-            ATMO_VP_CASE(KF_CLOUDS | KF_CLOUD_LIGHT_RM)
-            ATMO_VP_CASE(KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
-            ATMO_VP_CASE(KF_PRECISE | KF_CLOUDS)
-            ATMO_VP_CASE(KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
-            ATMO_VP_CASE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
-            ATMO_VP_CASE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
-            ATMO_VP_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)
-            ATMO_VP_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
-            ATMO_VP_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
-            ATMO_VP_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
-#undef ATMO_VP_CASE
+#define ATMO_VIEW_POS_CASE(F) case (F): return launch_s<(F) | KF_VIEW_POS, 0, 1>(rc, stream, tile_list_blocks);
+            ATMO_VIEW_POS_CASE(0)
+            ATMO_VIEW_POS_CASE(KF_LIGHT_DIRECT)
+            ATMO_VIEW_POS_CASE(KF_CLOUDS)
+            ATMO_VIEW_POS_CASE(KF_CLOUDS | KF_LIGHT_DIRECT)
+            ATMO_VIEW_POS_CASE(KF_CLOUDS | KF_CLOUD_LIGHT_RM)
+            ATMO_VIEW_POS_CASE(KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
+            ATMO_VIEW_POS_CASE(KF_PRECISE | KF_CLOUDS)
+            ATMO_VIEW_POS_CASE(KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
+            ATMO_VIEW_POS_CASE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
+            ATMO_VIEW_POS_CASE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
+            ATMO_VIEW_POS_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)
+            ATMO_VIEW_POS_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
+            ATMO_VIEW_POS_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
+            ATMO_VIEW_POS_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
+#undef ATMO_VIEW_POS_CASE
         default: break;
         }
     }
     return hipErrorInvalidValue;
 }
 
-// The families a proxy draw exists for (atmo_render_proxy): what a default context selects -- one lane per ray, the precise cloud and v1 forms, up to
-// 32 view steps.  Precision 0 and 2, long view marches (KF_VIEW_POS) and lane split have no proxy kernel: the host refuses those draws (ATMO_E_STATE).
-template <int FLAGS, int LSTEPS>
-static hipError_t launch_p(const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream) {
-    int gx, gy;
-    render_grid(rc, 1, &gx, &gy);
-    if (gx != rc.tiles_x || gx < 1 || gy < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((atmo_render_proxy_kernel<FLAGS | KF_PROXY, LSTEPS>), dim3(gx, gy), dim3(TILE_W * TILE_H), 0, stream, rc, pc);
-    return hipGetLastError();
-}
-template <int FLAGS>
-static hipError_t launch_p_direct(const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream) {   // 8 light steps unrolled, as launch_direct
-    return rc.light_steps == 8 ? launch_p<FLAGS, 8>(rc, pc, stream) : launch_p<FLAGS, 0>(rc, pc, stream);
-}
-hipError_t launch_render_proxy(int flags, const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream) {
+// ---- the default-form families: what a default context selects -- one lane per ray, the precise cloud and v1 forms, up to 32 view steps.  The proxy draws,
+// the view batches, the packed-target draws and their combinations exist for these and no other: precision 0 and 2, long view marches (KF_VIEW_POS) and lane
+// split have no such kernel, and the host refuses those draws (ATMO_E_STATE).  ONE(F): one kernel; TWIN(F): a direct-light family, which also has the unrolled
+// LSTEPS == 8 instantiation (as launch_direct).  GEO_TWIN(F) is not one of the thirteen: the geometric-order twin of the direct-light family, which only the
+// single packed-target draw has (launch_render_target); it stands here because the kernels are placed in the code object in the order of this list (LSTEPS 8
+// before 0), and the loops' positions with them: add a family at the end.
+#define ATMO_DEFAULT_FAMILIES(ONE, TWIN, GEO_TWIN)                              \
+    ONE(0)                                                                      \
+    TWIN(KF_LIGHT_DIRECT)                                                       \
+    GEO_TWIN(KF_LIGHT_DIRECT | KF_GEO)                                          \
+    ONE(KF_PRECISE | KF_CLOUDS)                                                 \
+    ONE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)                             \
+    TWIN(KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)                              \
+    TWIN(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)          \
+    ONE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)                                   \
+    ONE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)               \
+    TWIN(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)                \
+    TWIN(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT) \
+    ONE(KF_PRECISE | KF_LITE)                                                   \
+    ONE(KF_PRECISE | KF_LITE | KF_CLOUDS)                                       \
+    ONE(KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS)
+#define ATMO_FAMILY_LISTED(F) case (F):
+#define ATMO_FAMILY_SKIPPED(F)
+bool default_family_supported(int flags) {
     switch (flags) {
-    case 0: return launch_p<0, 0>(rc, pc, stream);
-    case KF_LIGHT_DIRECT: return launch_p_direct<KF_LIGHT_DIRECT>(rc, pc, stream);
-    case KF_PRECISE | KF_CLOUDS: return launch_p<KF_PRECISE | KF_CLOUDS, 0>(rc, pc, stream);
-    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_p<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, pc, stream);
-    case KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_p_direct<KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, pc, stream);
-    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT: return launch_p_direct<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, pc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: return launch_p<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS, 0>(rc, pc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_p<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, pc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_p_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, pc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
-        return launch_p_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, pc, stream);
-    case KF_PRECISE | KF_LITE: return launch_p<KF_PRECISE | KF_LITE, 0>(rc, pc, stream);
-    case KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_p<KF_PRECISE | KF_LITE | KF_CLOUDS, 0>(rc, pc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_p<KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS, 0>(rc, pc, stream);
-    default: return hipErrorInvalidValue;   // (the host asks proxy_family_supported first)
-    }
-}
-bool proxy_family_supported(int flags) {
-    switch (flags) {
-    case 0: case KF_LIGHT_DIRECT:
-    case KF_PRECISE | KF_CLOUDS: case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM:
-    case KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM:
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
-    case KF_PRECISE | KF_LITE: case KF_PRECISE | KF_LITE | KF_CLOUDS: case KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS:
+        ATMO_DEFAULT_FAMILIES(ATMO_FAMILY_LISTED, ATMO_FAMILY_LISTED, ATMO_FAMILY_SKIPPED)
         return true;
     default: return false;
     }
 }
-
-// ---- multi-view launchers: the proxy draws' families (what a default context selects), one lane per ray
-template <int FLAGS, int LSTEPS>
-static hipError_t launch_v(const RenderConsts *table, const ViewsConsts &vc, hipStream_t stream) {
-    const uint32_t total = vc.first_block[MAX_VIEWS];
-    if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((atmo_render_views_kernel<FLAGS | KF_VIEWS, LSTEPS>), dim3(total), dim3(TILE_W * TILE_H), 0, stream, table, vc);
-    return hipGetLastError();
+// (flags, light_steps) -> launch(FLAGS, LSTEPS), both std::integral_constant: every entry point below is this with its own kernel and family bits.
+// hipErrorInvalidValue for a family that is not listed (the host asks default_family_supported / target_family_supported first).
+template <int N>
+using int_c = std::integral_constant<int, N>;
+template <bool WITH_GEO_TWIN = false, class Launch>
+static hipError_t launch_default_family(int flags, int light_steps, Launch &&launch) {
+#define ATMO_FAMILY_ONE(F) case (F): return launch(int_c<(F)>{}, int_c<0>{});
+#define ATMO_FAMILY_8_OR_0(F) light_steps == 8 ? launch(int_c<(F)>{}, int_c<8>{}) : launch(int_c<(F)>{}, int_c<0>{})
+#define ATMO_FAMILY_TWIN(F) case (F): return ATMO_FAMILY_8_OR_0(F);
+#define ATMO_FAMILY_GEO_TWIN(F) case (F): if constexpr (WITH_GEO_TWIN) return ATMO_FAMILY_8_OR_0(F); else break;
+    switch (flags) {
+        ATMO_DEFAULT_FAMILIES(ATMO_FAMILY_ONE, ATMO_FAMILY_TWIN, ATMO_FAMILY_GEO_TWIN)
+    default: break;
+    }
+    return hipErrorInvalidValue;
+#undef ATMO_FAMILY_ONE
+#undef ATMO_FAMILY_8_OR_0
+#undef ATMO_FAMILY_TWIN
+#undef ATMO_FAMILY_GEO_TWIN
 }
+#undef ATMO_FAMILY_LISTED
+#undef ATMO_FAMILY_SKIPPED
+#undef ATMO_DEFAULT_FAMILIES
+
+// one packed format per batch, and every view that owns tiles has a target
+static bool batch_targets_valid(const uint32_t *first_block, const TargetConsts *target) {
+    int format = -1;
+    for (int i = 0; i < MAX_VIEWS; ++i) {
+        if (first_block[i + 1] == first_block[i]) continue;
+        const TargetConsts &t = target[i];
+        if (t.pixels == nullptr || !target_format_packed(t.format) || (format >= 0 && t.format != format)) return false;
+        format = t.format;
+    }
+    return true;
+}
+
+// the proxy draws (atmo_render_proxy)
+hipError_t launch_render_proxy(int flags, const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream) {
+    return launch_default_family(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_rect(atmo_render_proxy_kernel<F | KF_PROXY, L>, rc, stream, pc);
+    });
+}
+// the view batches
 hipError_t launch_render_views(int flags, int light_steps, const RenderConsts *table, const ViewsConsts &vc, hipStream_t stream) {
-#define ATMO_V_CASE(F) case (F): return launch_v<(F), 0>(table, vc, stream);
-#define ATMO_V_CASE_DIRECT(F) case (F): return light_steps == 8 ? launch_v<(F), 8>(table, vc, stream) : launch_v<(F), 0>(table, vc, stream);   // 8 light steps unrolled, as launch_direct
-    switch (flags) {
-        ATMO_V_CASE(0)
-        ATMO_V_CASE_DIRECT(KF_LIGHT_DIRECT)
-        ATMO_V_CASE(KF_PRECISE | KF_CLOUDS)
-        ATMO_V_CASE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
-        ATMO_V_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
-        ATMO_V_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
-        ATMO_V_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)
-        ATMO_V_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
-        ATMO_V_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
-        ATMO_V_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
-        ATMO_V_CASE(KF_PRECISE | KF_LITE)
-        ATMO_V_CASE(KF_PRECISE | KF_LITE | KF_CLOUDS)
-        ATMO_V_CASE(KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS)
-    default: return hipErrorInvalidValue;   // (the host asks views_family_supported first)
-    }
-#undef ATMO_V_CASE
-#undef ATMO_V_CASE_DIRECT
+    return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_batch(atmo_render_views_kernel<F | KF_VIEWS, L>, vc.first_block, table, vc, stream);
+    });
 }
-bool views_family_supported(int flags) { return proxy_family_supported(flags); }   // exactly the proxy draw's list
 
-// ---- packed-target launchers: the families of the proxy draws (what a default context selects), the geometric-order twin of the direct-light kernel, and
-// the two-lanes-per-ray form of the two declared-sampler cloud kernels that render_impl draws a frame's heavy tiles with
-template <int FLAGS, int LSTEPS, int SPLIT>
-static hipError_t launch_ts(const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream) {
-    int gx, gy;
-    render_grid(rc, SPLIT, &gx, &gy);
-    if (gx != rc.tiles_x) return hipErrorInvalidValue;
-    dim3 grid(gx, gy);
-    if (g_launch_blocks > 0) {
-        if (rc.tile_order == nullptr) return hipErrorInvalidValue;
-        grid = dim3(g_launch_blocks, 1);
-    }
-    hipLaunchKernelGGL((atmo_render_target_kernel<FLAGS | KF_TARGET, LSTEPS, SPLIT>), grid, dim3(TILE_W * TILE_H), 0, stream, rc, tc);
-    return hipGetLastError();
-}
-template <int FLAGS>
-static hipError_t launch_ts_direct(const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream) {   // 8 light steps unrolled, as launch_direct
-    return rc.light_steps == 8 ? launch_ts<FLAGS, 8, 1>(rc, tc, stream) : launch_ts<FLAGS, 0, 1>(rc, tc, stream);
-}
-template <int FLAGS>
-static hipError_t launch_ts_split(const RenderConsts &rc, const TargetConsts &tc, int split, hipStream_t stream) {
-    return split == 2 ? launch_ts<FLAGS, 0, 2>(rc, tc, stream) : launch_ts<FLAGS, 0, 1>(rc, tc, stream);
-}
-static hipError_t launch_render_target_grid(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream) {
-    if (!target_family_supported(flags & ~KF_GEO, split)) return hipErrorInvalidValue;
-    switch (flags) {
-    case 0: return launch_ts<0, 0, 1>(rc, tc, stream);
-    case KF_LIGHT_DIRECT: return launch_ts_direct<KF_LIGHT_DIRECT>(rc, tc, stream);
-    case KF_LIGHT_DIRECT | KF_GEO: return launch_ts_direct<KF_LIGHT_DIRECT | KF_GEO>(rc, tc, stream);
-    case KF_PRECISE | KF_CLOUDS: return launch_ts<KF_PRECISE | KF_CLOUDS, 0, 1>(rc, tc, stream);
-    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_ts<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0, 1>(rc, tc, stream);
-    case KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_ts_direct<KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, tc, stream);
-    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT: return launch_ts_direct<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, tc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: return launch_ts_split<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS>(rc, tc, split, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_ts_split<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM>(rc, tc, split, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_ts_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, tc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
-        return launch_ts_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, tc, stream);
-    case KF_PRECISE | KF_LITE: return launch_ts<KF_PRECISE | KF_LITE, 0, 1>(rc, tc, stream);
-    case KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_ts<KF_PRECISE | KF_LITE | KF_CLOUDS, 0, 1>(rc, tc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_ts<KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS, 0, 1>(rc, tc, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-hipError_t launch_render_target(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream, int tile_list_blocks) {
-    if (!target_format_packed(tc.format)) return hipErrorInvalidValue;
-    g_launch_blocks = tile_list_blocks;
-    const hipError_t e = launch_render_target_grid(flags, split, rc, tc, stream);
-    g_launch_blocks = 0;
-    return e;
+// the packed-target draws: the float draws' launch (launch_tiles) over the default families, and two forms more that render_impl draws with: the
+// geometric-order twin of the direct-light kernel, and the two-lanes-per-ray form of the two declared-sampler cloud kernels (a frame's heavy tiles)
+constexpr bool target_family_has_split(int flags) {
+    return flags == (KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS) || flags == (KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM);
 }
 bool target_family_supported(int flags, int split) {
-    if (split == 2) return flags == (KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS) || flags == (KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM);
-    return split == 1 && proxy_family_supported(flags);
+    return split == 2 ? target_family_has_split(flags) : split == 1 && default_family_supported(flags);
 }
-template <int FLAGS, int LSTEPS>
-static hipError_t launch_pt(const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, hipStream_t stream) {
-    int gx, gy;
-    render_grid(rc, 1, &gx, &gy);
-    if (gx != rc.tiles_x || gx < 1 || gy < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((atmo_render_proxy_target_kernel<FLAGS | KF_PROXY | KF_TARGET, LSTEPS>), dim3(gx, gy), dim3(TILE_W * TILE_H), 0, stream, rc, pc, tc);
-    return hipGetLastError();
-}
-template <int FLAGS>
-static hipError_t launch_pt_direct(const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, hipStream_t stream) {
-    return rc.light_steps == 8 ? launch_pt<FLAGS, 8>(rc, pc, tc, stream) : launch_pt<FLAGS, 0>(rc, pc, tc, stream);
+hipError_t launch_render_target(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream, int tile_list_blocks) {
+    if (!target_format_packed(tc.format) || !target_family_supported(flags & ~KF_GEO, split)) return hipErrorInvalidValue;
+    return launch_default_family<true>(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        if constexpr (target_family_has_split(F)) {
+            if (split == 2) return launch_tiles(atmo_render_target_kernel<F | KF_TARGET, L, 2>, 2, rc, tile_list_blocks, stream, tc);
+        }
+        return launch_tiles(atmo_render_target_kernel<F | KF_TARGET, L, 1>, 1, rc, tile_list_blocks, stream, tc);
+    });
 }
 hipError_t launch_render_proxy_target(int flags, const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, hipStream_t stream) {
     if (!target_format_packed(tc.format)) return hipErrorInvalidValue;
-    switch (flags) {
-    case 0: return launch_pt<0, 0>(rc, pc, tc, stream);
-    case KF_LIGHT_DIRECT: return launch_pt_direct<KF_LIGHT_DIRECT>(rc, pc, tc, stream);
-    case KF_PRECISE | KF_CLOUDS: return launch_pt<KF_PRECISE | KF_CLOUDS, 0>(rc, pc, tc, stream);
-    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_pt<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, pc, tc, stream);
-    case KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_pt_direct<KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, pc, tc, stream);
-    case KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT: return launch_pt_direct<KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, pc, tc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS: return launch_pt<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS, 0>(rc, pc, tc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM: return launch_pt<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM, 0>(rc, pc, tc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT: return launch_pt_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT>(rc, pc, tc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT:
-        return launch_pt_direct<KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT>(rc, pc, tc, stream);
-    case KF_PRECISE | KF_LITE: return launch_pt<KF_PRECISE | KF_LITE, 0>(rc, pc, tc, stream);
-    case KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_pt<KF_PRECISE | KF_LITE | KF_CLOUDS, 0>(rc, pc, tc, stream);
-    case KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS: return launch_pt<KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS, 0>(rc, pc, tc, stream);
-    default: return hipErrorInvalidValue;   // (the host asks proxy_family_supported first)
-    }
-}
-
-// ---- multi-view launchers into packed colour targets: the float batch's families, one lane per ray
-template <int FLAGS, int LSTEPS>
-static hipError_t launch_vt(const RenderConsts *table, const ViewsTargetConsts &vtc, hipStream_t stream) {
-    const uint32_t total = vtc.v.first_block[MAX_VIEWS];
-    if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((atmo_render_views_target_kernel<FLAGS | KF_VIEWS | KF_TARGET, LSTEPS>), dim3(total), dim3(TILE_W * TILE_H), 0, stream, table, vtc);
-    return hipGetLastError();
+    return launch_default_family(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_rect(atmo_render_proxy_target_kernel<F | KF_PROXY | KF_TARGET, L>, rc, stream, pc, tc);
+    });
 }
 hipError_t launch_render_views_target(int flags, int light_steps, const RenderConsts *table, const ViewsTargetConsts &vtc, hipStream_t stream) {
-    // one format per batch, and every view that owns tiles has a target
-    int format = -1;
-    for (int i = 0; i < MAX_VIEWS; ++i) {
-        if (vtc.v.first_block[i + 1] == vtc.v.first_block[i]) continue;
-        const TargetConsts &t = vtc.target[i];
-        if (t.pixels == nullptr || !target_format_packed(t.format) || (format >= 0 && t.format != format)) return hipErrorInvalidValue;
-        format = t.format;
-    }
-#define ATMO_VT_CASE(F) case (F): return launch_vt<(F), 0>(table, vtc, stream);
-#define ATMO_VT_CASE_DIRECT(F) case (F): return light_steps == 8 ? launch_vt<(F), 8>(table, vtc, stream) : launch_vt<(F), 0>(table, vtc, stream);   // as launch_render_views
-    switch (flags) {
-        ATMO_VT_CASE(0)
-        ATMO_VT_CASE_DIRECT(KF_LIGHT_DIRECT)
-        ATMO_VT_CASE(KF_PRECISE | KF_CLOUDS)
-        ATMO_VT_CASE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
-        ATMO_VT_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
-        ATMO_VT_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
-        ATMO_VT_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)
-        ATMO_VT_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)
-        ATMO_VT_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)
-        ATMO_VT_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT)
-        ATMO_VT_CASE(KF_PRECISE | KF_LITE)
-        ATMO_VT_CASE(KF_PRECISE | KF_LITE | KF_CLOUDS)
-        ATMO_VT_CASE(KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS)
-    default: return hipErrorInvalidValue;   // (the host asks views_target_family_supported first)
-    }
-#undef ATMO_VT_CASE
-#undef ATMO_VT_CASE_DIRECT
+    if (!batch_targets_valid(vtc.v.first_block, vtc.target)) return hipErrorInvalidValue;
+    return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_batch(atmo_render_views_target_kernel<F | KF_VIEWS | KF_TARGET, L>, vtc.v.first_block, table, vtc, stream);
+    });
 }
-bool views_target_family_supported(int flags) { return views_family_supported(flags) && target_family_supported(flags, 1); }   // the two lists' intersection: the same list
 
-// ---- multi-view proxy launchers (float and packed): the same families, one lane per ray, no tile order
-template <int FLAGS, int LSTEPS>
-static hipError_t launch_vp(const RenderConsts *table, const ViewsProxyConsts &vpc, hipStream_t stream) {
-    const uint32_t total = vpc.first_block[MAX_VIEWS];
-    if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((atmo_render_views_proxy_kernel<FLAGS | KF_VIEWS | KF_PROXY, LSTEPS>), dim3(total), dim3(TILE_W * TILE_H), 0, stream, table, vpc);
-    return hipGetLastError();
-}
-template <int FLAGS, int LSTEPS>
-static hipError_t launch_vpt(const RenderConsts *table, const ViewsProxyTargetConsts &vptc, hipStream_t stream) {
-    const uint32_t total = vptc.p.first_block[MAX_VIEWS];
-    if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((atmo_render_views_proxy_target_kernel<FLAGS | KF_VIEWS | KF_PROXY | KF_TARGET, LSTEPS>), dim3(total), dim3(TILE_W * TILE_H), 0, stream,
-                       table, vptc);
-    return hipGetLastError();
-}
-#define ATMO_VP_FAMILIES                                                          \
-    ATMO_VP_CASE(0)                                                               \
-    ATMO_VP_CASE_DIRECT(KF_LIGHT_DIRECT)                                          \
-    ATMO_VP_CASE(KF_PRECISE | KF_CLOUDS)                                          \
-    ATMO_VP_CASE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)                      \
-    ATMO_VP_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)                 \
-    ATMO_VP_CASE_DIRECT(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT) \
-    ATMO_VP_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)                            \
-    ATMO_VP_CASE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)        \
-    ATMO_VP_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_LIGHT_DIRECT)   \
-    ATMO_VP_CASE_DIRECT(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT) \
-    ATMO_VP_CASE(KF_PRECISE | KF_LITE)                                            \
-    ATMO_VP_CASE(KF_PRECISE | KF_LITE | KF_CLOUDS)                                \
-    ATMO_VP_CASE(KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS)
+// the proxy view batches (float and packed): no tile order
 hipError_t launch_render_views_proxy(int flags, int light_steps, const RenderConsts *table, const ViewsProxyConsts &vpc, hipStream_t stream) {
-#define ATMO_VP_CASE(F) case (F): return launch_vp<(F), 0>(table, vpc, stream);
-#define ATMO_VP_CASE_DIRECT(F) case (F): return light_steps == 8 ? launch_vp<(F), 8>(table, vpc, stream) : launch_vp<(F), 0>(table, vpc, stream);   // as launch_render_views
-    switch (flags) {
-        ATMO_VP_FAMILIES
-    default: return hipErrorInvalidValue;   // (the host asks views_proxy_family_supported first)
-    }
-#undef ATMO_VP_CASE
-#undef ATMO_VP_CASE_DIRECT
+    return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_batch(atmo_render_views_proxy_kernel<F | KF_VIEWS | KF_PROXY, L>, vpc.first_block, table, vpc, stream);
+    });
 }
-bool views_proxy_family_supported(int flags) { return proxy_family_supported(flags); }
 hipError_t launch_render_views_proxy_target(int flags, int light_steps, const RenderConsts *table, const ViewsProxyTargetConsts &vptc, hipStream_t stream) {
-    // one format per batch, and every view that owns tiles has a target
-    int format = -1;
-    for (int i = 0; i < MAX_VIEWS; ++i) {
-        if (vptc.p.first_block[i + 1] == vptc.p.first_block[i]) continue;
-        const TargetConsts &t = vptc.target[i];
-        if (t.pixels == nullptr || !target_format_packed(t.format) || (format >= 0 && t.format != format)) return hipErrorInvalidValue;
-        format = t.format;
-    }
-#define ATMO_VP_CASE(F) case (F): return launch_vpt<(F), 0>(table, vptc, stream);
-#define ATMO_VP_CASE_DIRECT(F) case (F): return light_steps == 8 ? launch_vpt<(F), 8>(table, vptc, stream) : launch_vpt<(F), 0>(table, vptc, stream);
-    switch (flags) {
-        ATMO_VP_FAMILIES
-    default: return hipErrorInvalidValue;   // (the host asks views_proxy_target_family_supported first)
-    }
-#undef ATMO_VP_CASE
-#undef ATMO_VP_CASE_DIRECT
+    if (!batch_targets_valid(vptc.p.first_block, vptc.target)) return hipErrorInvalidValue;
+    return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_batch(atmo_render_views_proxy_target_kernel<F | KF_VIEWS | KF_PROXY | KF_TARGET, L>, vptc.p.first_block, table, vptc, stream);
+    });
 }
-#undef ATMO_VP_FAMILIES
-bool views_proxy_target_family_supported(int flags) { return proxy_family_supported(flags); }
 
 // store_target<FMT> on caller-supplied arrays (atmo_debug_store_target): the encode and the blend on chosen values, one pixel per lane
 template <int FMT>

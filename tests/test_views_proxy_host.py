@@ -408,3 +408,46 @@ def test_views_proxy_kernels_keep_their_constants_in_sgprs():
             m = re.search(r"(\d+) VGPRs \((\d+) waves; proxy twin (\d+), batch twin (\d+)\)", ln)
             assert m and int(m.group(2)) == waves(int(m.group(1))), ln
             assert int(m.group(2)) >= min(waves(int(m.group(3))), waves(int(m.group(4)))), ln
+
+
+def test_every_default_form_entry_point_has_the_same_families():
+    """The proxy draws, the view batches, the packed-target draws and their combinations are all launched from ONE list of families (ATMO_DEFAULT_FAMILIES in
+    csrc/atmo_kernels.hip): the thirteen default forms, five of them with the unrolled LSTEPS == 8 twin -- 18 (FLAGS, LSTEPS) pairs.  Read back from the
+    library as built: each of the six kernels exists for exactly those pairs under its own family bits, and atmo_render_target_kernel for those with
+    SPLIT 1, the KF_GEO twin of the direct-light family and the SPLIT 2 form of the two declared-sampler cloud families, and nothing else."""
+    from godot_atmosphere_shader_amd.build import build_native
+
+    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
+        pytest.skip("llvm-readelf of the ROCm toolchain not found")
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import loop_phase
+    finally:
+        sys.path.pop(0)
+    import tempfile
+
+    CLOUDS, RM, DIRECT, LITE, PRECISE, LOD, GEO, PROXY, TARGET, VIEWS = 1, 2, 4, 8, 16, 32, 256, 512, 1024, 2048   # KernelFlags (csrc/atmo_device.h)
+    plain = [0, PRECISE | CLOUDS, PRECISE | CLOUDS | RM, LOD | PRECISE | CLOUDS, LOD | PRECISE | CLOUDS | RM, PRECISE | LITE, PRECISE | LITE | CLOUDS,
+             LOD | PRECISE | LITE | CLOUDS]
+    direct = [DIRECT, PRECISE | CLOUDS | DIRECT, PRECISE | CLOUDS | RM | DIRECT, LOD | PRECISE | CLOUDS | DIRECT, LOD | PRECISE | CLOUDS | RM | DIRECT]
+    want = {(f, 0) for f in plain + direct} | {(f, 8) for f in direct}
+    assert len(plain) + len(direct) == 13 and len(want) == 18
+
+    with tempfile.TemporaryDirectory(prefix="families_") as tmp:
+        co = loop_phase.device_code_object(build_native(), os.path.join(tmp, "dev.co"))
+        syms = subprocess.run([f"{loop_phase.LLVM}/llvm-readelf", "-sW", co], check=True, capture_output=True, text=True).stdout
+    found = {}
+    for line in syms.splitlines():
+        m = re.search(r"\d+(atmo_render_[a-z_]*kernel)ILi(\d+)ELi(\d+)E(?:Li(\d+)E)?E", line.split()[-1]) if " FUNC " in line else None
+        if m:
+            found.setdefault(m.group(1), set()).add(tuple(int(g) for g in m.groups()[1:] if g is not None))
+    for kernel, bits in (("atmo_render_proxy_kernel", PROXY), ("atmo_render_views_kernel", VIEWS), ("atmo_render_proxy_target_kernel", PROXY | TARGET),
+                         ("atmo_render_views_target_kernel", VIEWS | TARGET), ("atmo_render_views_proxy_kernel", VIEWS | PROXY),
+                         ("atmo_render_views_proxy_target_kernel", VIEWS | PROXY | TARGET)):
+        got = found[kernel]
+        assert all(f & (PROXY | TARGET | VIEWS | GEO) == bits for f, _ in got), (kernel, sorted(got))
+        assert {(f & ~bits, l) for f, l in got} == want, (kernel, sorted(got))
+    got = found["atmo_render_target_kernel"]
+    assert all(f & (PROXY | TARGET | VIEWS) == TARGET for f, _, _ in got), sorted(got)
+    want_target = {(f, l, 1) for f, l in want} | {(DIRECT | GEO, 8, 1), (DIRECT | GEO, 0, 1)} | {(LOD | PRECISE | CLOUDS, 0, 2), (LOD | PRECISE | CLOUDS | RM, 0, 2)}
+    assert {(f & ~TARGET, l, s) for f, l, s in got} == want_target, sorted(got)
