@@ -203,6 +203,22 @@ def _to_native_frame(frame: dict) -> N.AtmoFrame:
     return f
 
 
+# The C entry point of one draw, by (through the far mode's box proxy?, into an N.AtmoTarget -- a packed or pitched tensor --?): (plain, composite).
+# The float entry points end (..., depth, rgba, stream), the *_target ones (..., depth, &target, composite, stream); the proxy ones take
+# (model, box_size) behind the frame.  `PlanetAtmosphere._render_one` builds the call from the row; a new entry point is a new row.
+_SINGLE_DRAWS = {
+    (False, False): ("atmo_render", "atmo_render_composite"),
+    (False, True): ("atmo_render_target", "atmo_render_target"),
+    (True, False): ("atmo_render_proxy", "atmo_render_proxy_composite"),
+    (True, True): ("atmo_render_proxy_target", "atmo_render_proxy_target"),
+}
+# ... and of a view batch, by the same key: all four take (views, n, [model, box_size,] composite, stream) (`PlanetAtmosphere._enqueue_views`)
+_BATCH_DRAWS = {
+    (False, False): "atmo_render_views", (False, True): "atmo_render_views_target",
+    (True, False): "atmo_render_views_proxy", (True, True): "atmo_render_views_proxy_target",
+}
+
+
 class PlanetAtmosphere:
     """See module docstring.  One instance owns one AtmoContext on one GPU."""
 
@@ -517,12 +533,8 @@ class PlanetAtmosphere:
 
     def _process(self, delta: float = 0.0, camera=None, time: float | None = None):
         """planet_atmosphere.gd:285-341: near/far switch and the per-frame uniforms."""
-        cam_pos = np.zeros(3)
-        cam_near = 0.1
-        if camera is not None:
-            cam_pos = np.asarray(camera.inv_view)[:3, 3]
-            cam_near = camera.near
-        atmo_clip_distance = 1.75 * (self._planet_radius + self._atmosphere_height + cam_near) * SWITCH_MARGIN_RATIO
+        cam_pos = np.zeros(3) if camera is None else np.asarray(camera.inv_view)[:3, 3]
+        atmo_clip_distance = self.proxy_box_size(camera)
         d = float(np.linalg.norm(np.asarray(self.global_transform)[:3, 3] - cam_pos))
         self._set_mode(MODE_NEAR if (d < atmo_clip_distance or self.force_fullscreen) else MODE_FAR)
 
@@ -550,34 +562,30 @@ class PlanetAtmosphere:
         (rect_h, rect_w, 4), allocated when None.  Work is enqueued on `stream` (a torch stream, a raw
         hipStream_t int, or None for torch's current stream).  Returns `out`.
         `out` may also be a float16 (RGBA16F) or uint8 (RGBA8_UNORM) tensor, and its rows may be further apart than a row (a row pitch): the draw then
-        stores in that format (atmo_render_target; godot_atmosphere_shader_amd.targets states the encoding).  target="rgba16f" | "rgba8" allocates one.
-        A uint8 tensor means RGBA8_UNORM; target="rgba8_srgb" | "bgra8" | "bgra8_srgb" | "a2b10g10r10" next to `out` says that its bytes are that format's
-        instead, and alone allocates such a tensor.  A name that contradicts the tensor's dtype raises ValueError."""
-        import torch
+        stores in that format (atmo_render_target; godot_atmosphere_shader_amd.targets states the encoding).  `target` names a packed format
+        (`_new_target` lists the names): alone it allocates such a tensor, next to a uint8 `out` it says that its bytes are that format's instead of
+        RGBA8_UNORM's (`_colour_target`).  A name that contradicts the tensor's dtype raises ValueError."""
+        return self._render_one(camera, depth, out, rect, stream, time, target, False, None, split_depth_errors=True)
 
+    def _render_one(self, camera, depth, colour, rect, stream, time, target, composite, proxy, split_depth_errors=False):
+        """The four single draws: `composite` blends into the whole viewport's buffer, else `colour` holds the rect (allocated when None);
+        `proxy` is None or `_proxy`'s (model, box_size): zero-filled allocations, the proxy entry points."""
         frame = self.make_frame(camera, time, rect)
         x0, y0, x1, y1 = frame["rect"]
-        if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()):
-            raise TypeError("depth must be a contiguous CUDA float32 tensor")
-        if tuple(depth.shape) != (camera.height, camera.width):
-            raise ValueError("depth must have shape (viewport_h, viewport_w)")
-        if out is None:
-            out = _new_target(y1 - y0, x1 - x0, target, depth.device, zero=False)
-        tgt = _colour_target(out, y1 - y0, x1 - x0, "out", target)
-        if stream is None:
-            stream = torch.cuda.current_stream(depth.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        if tgt is not None:
-            self._target_call(_to_native_frame(frame), depth, tgt, 0, stream)
-        else:
-            self.render_raw(frame, depth.data_ptr(), out.data_ptr(), stream)
-        return out
-
-    def _target_call(self, native_frame, depth, tgt, composite: int, stream):
+        _check_depth(depth, camera, split=split_depth_errors)
+        rows, cols = (camera.height, camera.width) if composite else (y1 - y0, x1 - x0)
+        if colour is None and not composite:
+            colour = _new_target(rows, cols, target, depth.device, zero=proxy is not None)
+        # a contiguous float32 tensor (None), or the N.AtmoTarget of a float16 / uint8 / pitched one
+        tgt = _colour_target(colour, rows, cols, "scene_rgba" if composite else "out", target)
+        stream = _stream_handle(stream, depth)
         self._bake_if_needed(stream)
-        rc = self._lib.atmo_render_target(self._ctx, C.byref(native_frame), C.c_void_p(depth.data_ptr()), C.byref(tgt), int(composite), C.c_void_p(stream or 0))
-        N.check(self._ctx, rc)
+        nf = _to_native_frame(frame)
+        fn = getattr(self._lib, _SINGLE_DRAWS[proxy is not None, tgt is not None][bool(composite)])
+        box = () if proxy is None else (proxy[0], C.c_float(proxy[1]))
+        where = (C.c_void_p(colour.data_ptr()),) if tgt is None else (C.byref(tgt), int(composite))
+        N.check(self._ctx, fn(self._ctx, C.byref(nf), *box, C.c_void_p(depth.data_ptr()), *where, C.c_void_p(stream or 0)))
+        return colour
 
     def prepare_frame(self, camera, time: float = 0.0, rect=None) -> N.AtmoFrame:
         """The native per-frame argument block for `render_prepared` (build once per camera pose)."""
@@ -597,64 +605,42 @@ class PlanetAtmosphere:
         ALBEDO/ALPHA; discarded fragments leave the scene untouched.  Returns `scene_rgba`.
         A float16 / uint8 `scene_rgba` (RGBA16F / RGBA8_UNORM, optionally with a row pitch) is blended in its own format: decoded, blended in fp32,
         encoded once (atmo_render_target).  `target` names the format of a uint8 buffer that is not RGBA8_UNORM, as in `render`."""
-        import torch
-
-        frame = self.make_frame(camera, time, rect)
-        tgt = _colour_target(scene_rgba, camera.height, camera.width, "scene_rgba", target)
-        if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
-                and tuple(depth.shape) == (camera.height, camera.width)):
-            raise TypeError("depth must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w)")
-        if stream is None:
-            stream = torch.cuda.current_stream(depth.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        self._bake_if_needed(stream)
-        nf = _to_native_frame(frame)
-        if tgt is not None:
-            self._target_call(nf, depth, tgt, 1, stream)
-            return scene_rgba
-        rc = self._lib.atmo_render_composite(self._ctx, C.byref(nf), C.c_void_p(depth.data_ptr()),
-                                             C.c_void_p(scene_rgba.data_ptr()), C.c_void_p(stream or 0))
-        N.check(self._ctx, rc)
-        return scene_rgba
+        return self._render_one(camera, depth, scene_rgba, rect, stream, time, target, True, None)
 
     # ---- several views in one launch (include/atmo_views.h) ------------------------------------------------------------------------
     def prepare_views(self, cameras, depth_ptrs, out_ptrs, rects=None, time: float = 0.0):
         """The native argument block of `render_views_prepared`: one N.AtmoView per camera, on raw device addresses."""
-        n = len(cameras)
-        if not (len(depth_ptrs) == n and len(out_ptrs) == n and (rects is None or len(rects) == n)):
-            raise ValueError("cameras, depths, outs and rects must have one entry per view")
-        views = (N.AtmoView * max(n, 1))()
-        for i, cam in enumerate(cameras):
-            views[i].frame = _to_native_frame(self.make_frame(cam, time, rects[i] if rects is not None else None))
-            views[i].depth_dev = depth_ptrs[i]
-            views[i].rgba_dev = out_ptrs[i]
-        return views
+        return self._prepare_views(N.AtmoView, cameras, depth_ptrs, out_ptrs, rects, time)
 
     def render_views_prepared(self, views, n_views: int, composite: bool = False, stream: int = 0):
         """Enqueue one batch from `prepare_views`: one ctypes call, one launch for all views."""
-        self._bake_if_needed(stream)
-        rc = self._lib.atmo_render_views(self._ctx, views, int(n_views), int(bool(composite)), C.c_void_p(stream or 0))
-        N.check(self._ctx, rc)
+        self._enqueue_views(self._lib.atmo_render_views, views, n_views, None, composite, stream)
 
     def prepare_views_target(self, cameras, depth_ptrs, targets, rects=None, time: float = 0.0):
         """The native argument block of `render_views_target_prepared`: one N.AtmoViewTarget per camera; targets[i] is an N.AtmoTarget (pixels, format,
         row pitch in bytes) addressed as `atmo_render_target` addresses it."""
-        n = len(cameras)
-        if not (len(depth_ptrs) == n and len(targets) == n and (rects is None or len(rects) == n)):
-            raise ValueError("cameras, depths, targets and rects must have one entry per view")
-        views = (N.AtmoViewTarget * max(n, 1))()
-        for i, cam in enumerate(cameras):
-            views[i].frame = _to_native_frame(self.make_frame(cam, time, rects[i] if rects is not None else None))
-            views[i].depth_dev = depth_ptrs[i]
-            views[i].target = targets[i]
-        return views
+        return self._prepare_views(N.AtmoViewTarget, cameras, depth_ptrs, targets, rects, time)
 
     def render_views_target_prepared(self, views, n_views: int, composite: bool = False, stream: int = 0):
         """Enqueue one batch from `prepare_views_target` (atmo_render_views_target): one ctypes call, one launch for all views."""
+        self._enqueue_views(self._lib.atmo_render_views_target, views, n_views, None, composite, stream)
+
+    def _prepare_views(self, struct, cameras, depth_ptrs, colours, rects, time):
+        field, name = ("rgba_dev", "outs") if struct is N.AtmoView else ("target", "targets")
+        n = len(cameras)
+        if not (len(depth_ptrs) == n and len(colours) == n and (rects is None or len(rects) == n)):
+            raise ValueError(f"cameras, depths, {name} and rects must have one entry per view")
+        views = (struct * max(n, 1))()
+        for i, cam in enumerate(cameras):
+            views[i].frame = _to_native_frame(self.make_frame(cam, time, rects[i] if rects is not None else None))
+            views[i].depth_dev = depth_ptrs[i]
+            setattr(views[i], field, colours[i])
+        return views
+
+    def _enqueue_views(self, fn, views, n_views, proxy, composite, stream):
         self._bake_if_needed(stream)
-        rc = self._lib.atmo_render_views_target(self._ctx, views, int(n_views), int(bool(composite)), C.c_void_p(stream or 0))
-        N.check(self._ctx, rc)
+        box = () if proxy is None else (proxy[0], C.c_float(proxy[1]))
+        N.check(self._ctx, fn(self._ctx, views, int(n_views), *box, int(bool(composite)), C.c_void_p(stream or 0)))
 
     def render_views(self, cameras, depths, outs=None, rects=None, composite: bool = False, stream=None, time: float = 0.0, target=None):
         """Several views of this planet in ONE launch (atmo_render_views): the two eyes of a stereo pass, a split screen, probe faces -- up to
@@ -664,14 +650,11 @@ class PlanetAtmosphere:
         outputs.  The tensors the views write must not overlap.  One native call; returns the list of output tensors.
         outs[i] may also be float16 (RGBA16F) or uint8 (RGBA8_UNORM) tensors, and their rows may be further apart than a row (a row pitch: the two
         halves of one double-wide image, say): the batch then stores or blends in that format (atmo_render_views_target; one format per batch).
-        target="rgba16f" | "rgba8" allocates such outputs; target="rgba8_srgb" | "bgra8" | "bgra8_srgb" | "a2b10g10r10" names the format of uint8 outs, or
-        allocates them, as in `render`."""
+        `target` allocates such outputs, or names the format of uint8 outs, as in `render`."""
         return self._render_views(cameras, depths, outs, rects, composite, stream, time, target, None)
 
     def _render_views(self, cameras, depths, outs, rects, composite, stream, time, target, proxy):
-        """`render_views` (proxy None) and `render_views_proxy` (proxy = (model, box_size): zero-filled allocations, the proxy entry points)."""
-        import torch
-
+        """`render_views` (proxy None) and `render_views_proxy` (proxy = `_proxy`'s (model, box_size): zero-filled allocations, the proxy entry points)."""
         n = len(cameras)
         if n > N.MAX_VIEWS:
             raise ValueError(f"at most {N.MAX_VIEWS} views per batch")
@@ -682,10 +665,7 @@ class PlanetAtmosphere:
         outs = list(outs) if outs is not None else [None] * n
         tgts = [None] * n
         for i, (cam, depth) in enumerate(zip(cameras, depths)):
-            if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()):
-                raise TypeError(f"view {i}: depth must be a contiguous CUDA float32 tensor")
-            if tuple(depth.shape) != (cam.height, cam.width):
-                raise ValueError(f"view {i}: depth must have shape (viewport_h, viewport_w)")
+            _check_depth(depth, cam, f"view {i}: ", split=True)
             x0, y0, x1, y1 = rects[i] if rects is not None and rects[i] is not None else (0, 0, cam.width, cam.height)
             rows, cols = (cam.height, cam.width) if composite else (y1 - y0, x1 - x0)
             if outs[i] is None:
@@ -694,23 +674,15 @@ class PlanetAtmosphere:
             tgts[i] = _colour_target(outs[i], rows, cols, f"view {i}: {'scene_rgba' if composite else 'out'}", target)
         if n == 0:
             return outs
-        if stream is None:
-            stream = torch.cuda.current_stream(depths[0].device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        if all(t is None for t in tgts):
-            views = self.prepare_views(cameras, [d.data_ptr() for d in depths], [o.data_ptr() for o in outs], rects, time)
-            if proxy is not None:
-                self.render_views_proxy_prepared(views, n, proxy[0], proxy[1], composite, stream)
-            else:
-                self.render_views_prepared(views, n, composite, stream)
-        else:
+        stream = _stream_handle(stream, depths[0])
+        depth_ptrs = [d.data_ptr() for d in depths]
+        packed = any(t is not None for t in tgts)
+        if packed:   # one batch, one struct: a contiguous float32 tensor among pitched ones is an RGBA32F target without a pitch
             tgts = [t if t is not None else N.AtmoTarget(o.data_ptr(), N.TARGET_RGBA32F, 0) for t, o in zip(tgts, outs)]
-            views = self.prepare_views_target(cameras, [d.data_ptr() for d in depths], tgts, rects, time)
-            if proxy is not None:
-                self.render_views_proxy_target_prepared(views, n, proxy[0], proxy[1], composite, stream)
-            else:
-                self.render_views_target_prepared(views, n, composite, stream)
+            views = self.prepare_views_target(cameras, depth_ptrs, tgts, rects, time)
+        else:
+            views = self.prepare_views(cameras, depth_ptrs, [o.data_ptr() for o in outs], rects, time)
+        self._enqueue_views(getattr(self._lib, _BATCH_DRAWS[proxy is not None, packed]), views, n, proxy, composite, stream)
         return outs
 
     # ---- several far-mode views in one launch (include/atmo_views_proxy.h) -----------------------------------------------------------
@@ -720,16 +692,11 @@ class PlanetAtmosphere:
 
     def render_views_proxy_prepared(self, views, n_views: int, model, box_size: float, composite: bool = False, stream: int = 0):
         """Enqueue one far-mode batch from `prepare_views` (atmo_render_views_proxy): `model` from `proxy_model`, one launch for all views."""
-        self._bake_if_needed(stream)
-        rc = self._lib.atmo_render_views_proxy(self._ctx, views, int(n_views), model, C.c_float(box_size), int(bool(composite)), C.c_void_p(stream or 0))
-        N.check(self._ctx, rc)
+        self._enqueue_views(self._lib.atmo_render_views_proxy, views, n_views, (model, box_size), composite, stream)
 
     def render_views_proxy_target_prepared(self, views, n_views: int, model, box_size: float, composite: bool = False, stream: int = 0):
         """Enqueue one far-mode batch from `prepare_views_target` (atmo_render_views_proxy_target)."""
-        self._bake_if_needed(stream)
-        rc = self._lib.atmo_render_views_proxy_target(self._ctx, views, int(n_views), model, C.c_float(box_size), int(bool(composite)),
-                                                      C.c_void_p(stream or 0))
-        N.check(self._ctx, rc)
+        self._enqueue_views(self._lib.atmo_render_views_proxy_target, views, n_views, (model, box_size), composite, stream)
 
     def render_views_proxy(self, cameras, depths, outs=None, rects=None, composite: bool = False, stream=None, time: float = 0.0,
                            box_size: float | None = None, target=None):
@@ -738,9 +705,8 @@ class PlanetAtmosphere:
         only the box's passing front-face fragments are written.  One box per batch: edge `box_size` (default proxy_box_size(cameras[0])) centred on
         global_transform.  outs=None allocates zero-filled outputs, as `render_proxy` does; float16 / uint8 / pitched tensors go through
         atmo_render_views_proxy_target (one format per batch)."""
-        if box_size is None:
-            box_size = self.proxy_box_size(cameras[0] if len(cameras) else None)
-        return self._render_views(cameras, depths, outs, rects, composite, stream, time, target, (self.proxy_model(), float(box_size)))
+        proxy = self._proxy(cameras[0] if len(cameras) else None, box_size)
+        return self._render_views(cameras, depths, outs, rects, composite, stream, time, target, proxy)
 
     def draw_views(self, cameras, depths, scene_rgbas, rects=None, stream=None, time: float = 0.0, target=None):
         """`draw` for several views in one launch: near mode `render_views(..., composite=True)`, far mode `render_views_proxy(..., composite=True)`
@@ -755,50 +721,20 @@ class PlanetAtmosphere:
         cam_near = 0.1 if camera is None else camera.near
         return 1.75 * (self._planet_radius + self._atmosphere_height + cam_near) * SWITCH_MARGIN_RATIO
 
-    def _proxy_call(self, fn, camera, depth, target, rect, stream, time, box_size, tgt=None, composite=0):
-        frame = self.make_frame(camera, time, rect)
-        if stream is None:
-            stream = _torch_stream(depth)
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        self._bake_if_needed(stream)
-        nf = _to_native_frame(frame)
-        model = (C.c_float * 16)(*[float(x) for x in col_major(self.global_transform)])
-        size = self.proxy_box_size(camera) if box_size is None else float(box_size)
-        if tgt is not None:   # a packed or pitched colour tensor (_colour_target): atmo_render_proxy_target
-            rc = self._lib.atmo_render_proxy_target(self._ctx, C.byref(nf), model, C.c_float(size), C.c_void_p(depth.data_ptr()), C.byref(tgt), int(composite),
-                                                    C.c_void_p(stream or 0))
-        else:
-            rc = fn(self._ctx, C.byref(nf), model, C.c_float(size), C.c_void_p(depth.data_ptr()), C.c_void_p(target.data_ptr()), C.c_void_p(stream or 0))
-        N.check(self._ctx, rc)
+    def _proxy(self, camera, box_size):
+        """What the proxy entry points take beside a plain draw's arguments: (model matrix, the box's edge -- default proxy_box_size(camera))."""
+        return self.proxy_model(), self.proxy_box_size(camera) if box_size is None else float(box_size)
 
     def render_proxy(self, camera, depth, out=None, rect=None, stream=None, time: float = 0.0, box_size: float | None = None, target=None):
         """`render` through the far mode's BoxMesh (default edge: proxy_box_size(camera)) centred on global_transform: only the box's front-face
-        fragments that pass the depth test are shaded and written (atmo_render_proxy); every other pixel of `out` is left as it was.
-        `out` / `target`: as `render` (float16 / uint8 tensors, a row pitch: atmo_render_proxy_target)."""
-        import torch
-
-        x0, y0, x1, y1 = rect if rect is not None else (0, 0, camera.width, camera.height)
-        if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
-                and tuple(depth.shape) == (camera.height, camera.width)):
-            raise TypeError("depth must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w)")
-        if out is None:
-            out = _new_target(y1 - y0, x1 - x0, target, depth.device, zero=True)
-        tgt = _colour_target(out, y1 - y0, x1 - x0, "out", target)
-        self._proxy_call(self._lib.atmo_render_proxy, camera, depth, out, rect, stream, time, box_size, tgt, 0)
-        return out
+        fragments that pass the depth test are shaded and written (atmo_render_proxy); every other pixel of `out` is left as it was (an `out` allocated
+        here is zero-filled).  `out` / `target`: as `render` (float16 / uint8 tensors, a row pitch: atmo_render_proxy_target)."""
+        return self._render_one(camera, depth, out, rect, stream, time, target, False, self._proxy(camera, box_size))
 
     def render_proxy_composite(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0, box_size: float | None = None, target=None):
         """`render_composite` through the far mode's BoxMesh (atmo_render_proxy_composite; a float16 / uint8 / pitched `scene_rgba`:
         atmo_render_proxy_target; `target`: as `render_composite`).  Returns `scene_rgba`."""
-        import torch
-
-        tgt = _colour_target(scene_rgba, camera.height, camera.width, "scene_rgba", target)
-        if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
-                and tuple(depth.shape) == (camera.height, camera.width)):
-            raise TypeError("depth must be a contiguous CUDA float32 tensor of shape (viewport_h, viewport_w)")
-        self._proxy_call(self._lib.atmo_render_proxy_composite, camera, depth, scene_rgba, rect, stream, time, box_size, tgt, 1)
-        return scene_rgba
+        return self._render_one(camera, depth, scene_rgba, rect, stream, time, target, True, self._proxy(camera, box_size))
 
     def draw(self, camera, depth, scene_rgba, rect=None, stream=None, time: float = 0.0, target=None):
         """The draw Godot makes for this node in its current mode (set by `_process`): near mode the fullscreen quad (`render_composite`), far mode
@@ -832,8 +768,7 @@ class PlanetAtmosphere:
     def measure_tile_costs(self, camera, depth, rect=None, stream=None, time: float = 0.0):
         """One draw through atmo_measure_tile_costs: ((tiles_y, tiles_x) uint32 costs -- every tile's longest wavefront in shader cycles --,
         tile_w, tile_h).  sharding.lpt_strips deals them to the GPUs of a node."""
-        rows = self.measure_row_costs(camera, depth, rect=rect, stream=stream, time=time)
-        del rows
+        self.measure_row_costs(camera, depth, rect=rect, stream=stream, time=time)
         return self._last_tile_costs, self._last_tile_size[0], self._last_tile_size[1]
 
     def measure_row_costs(self, camera, depth, rect=None, stream=None, time: float = 0.0):
@@ -845,10 +780,7 @@ class PlanetAtmosphere:
         frame = self.make_frame(camera, time, rect)
         x0, y0, x1, y1 = frame["rect"]
         nf = _to_native_frame(frame)
-        if stream is None:
-            stream = torch.cuda.current_stream(depth.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
+        stream = _stream_handle(stream, depth)
         self._bake_if_needed(stream)
         scratch = torch.empty((y1 - y0, x1 - x0, 4), dtype=torch.float32, device=depth.device)
         gx, gy, tw, th = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
@@ -891,8 +823,8 @@ def _colour_target(t, rows: int, cols: int, what: str, target=None):
     """How a colour tensor is drawn into: None for a contiguous float32 (rows, cols, 4) tensor -- the float entry points --, else the N.AtmoTarget
     of a float16 (RGBA16F), uint8 (RGBA8_UNORM) or float32 tensor whose pixels are contiguous and whose rows may be further apart (the row pitch
     is the tensor's row stride): include/atmo_target.h.  `target` names the format of the tensor's bits where the dtype does not say it: a uint8
-    tensor is RGBA8_UNORM unless target="rgba8_srgb" | "bgra8" | "bgra8_srgb" | "a2b10g10r10" (the bytes as they lie in memory); a name that
-    contradicts the dtype is a ValueError."""
+    tensor is RGBA8_UNORM unless `target` is another 4-byte format of `_new_target`'s list (the bytes as they lie in memory); a name that contradicts
+    the dtype is a ValueError."""
     import torch
 
     from . import targets as T
@@ -914,7 +846,8 @@ def _colour_target(t, rows: int, cols: int, what: str, target=None):
 
 def _new_target(rows: int, cols: int, target, device, zero: bool):
     """The tensor a draw allocates: float32, or the packed format named by target="rgba16f" | "rgba8" | "rgba8_srgb" | "bgra8" | "bgra8_srgb" |
-    "a2b10g10r10" (uint8 (rows, cols, 4) for all but the first: the bytes as they lie in memory)."""
+    "a2b10g10r10" (uint8 (rows, cols, 4) for all but the first: the bytes as they lie in memory).  This is THE list of target names of every draw
+    method: targets.FORMATS holds it, and a new format is one line there (plus its DTYPES / PIXEL_BYTES entries)."""
     import torch
 
     from . import targets as T
@@ -924,10 +857,26 @@ def _new_target(rows: int, cols: int, target, device, zero: bool):
     return (torch.zeros if zero else torch.empty)((rows, cols, 4), dtype=dtype, device=device)
 
 
-def _torch_stream(tensor) -> int:
+def _stream_handle(stream, tensor) -> int:
+    """The hipStream_t behind a draw's `stream` argument: a torch stream's, a raw handle as it is, None = torch's current stream on the tensor's device."""
+    if stream is None:
+        import torch
+
+        return torch.cuda.current_stream(tensor.device).cuda_stream
+    return getattr(stream, "cuda_stream", stream)
+
+
+def _check_depth(depth, camera, prefix: str = "", split: bool = False):
+    """A depth buffer is a contiguous CUDA float32 (viewport_h, viewport_w) tensor.  split: `render` and the view batches raise TypeError for the tensor's
+    kind and ValueError for its shape; the other single draws raise one TypeError that names both (kept as it was: NOTES.md)."""
     import torch
 
-    return torch.cuda.current_stream(tensor.device).cuda_stream
+    kind = "depth must be a contiguous CUDA float32 tensor"
+    both = kind + " of shape (viewport_h, viewport_w)"
+    if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()):
+        raise TypeError(prefix + (kind if split else both))
+    if tuple(depth.shape) != (camera.height, camera.width):
+        raise ValueError(prefix + "depth must have shape (viewport_h, viewport_w)") if split else TypeError(prefix + both)
 
 
 def draw_order(nodes, camera) -> list:
@@ -943,7 +892,7 @@ def draw_atmospheres(nodes, camera, depth, scene_rgba, stream=None, time: float 
     """Draws several PlanetAtmosphere nodes into one frame as Godot does: each node's draw for its current mode (`PlanetAtmosphere.draw`: the
     fullscreen quad near, the BoxMesh far), composited over `scene_rgba` in place, back to front (`draw_order`).  Returns `scene_rgba`, which may be the renderer's own RGBA16F / RGBA8_UNORM buffer
     (a float16 / uint8 tensor, optionally with a row pitch): every node then blends in that format.  `target` names the format of a uint8 buffer that is not
-    RGBA8_UNORM ("rgba8_srgb", "bgra8", "bgra8_srgb", "a2b10g10r10")."""
+    RGBA8_UNORM, as in `PlanetAtmosphere.render`."""
     kw = {} if target is None else {"target": target}
     for node in draw_order(list(nodes), camera):
         node.draw(camera, depth, scene_rgba, stream=stream, time=time, **kw)
