@@ -136,11 +136,19 @@ __device__ __forceinline__ float exact_div_uniform(float a, float c, float rc) {
 // Sure-miss test in front of the exact prologue (shade_pixel).  ATMO_FAST_MISS_MASK: bit (direct + 2 clouds + 4 lite) = that kernel
 // family uses it (a measured choice per family, like the prologue diet: profiles/round3/ab_fast_miss.txt).
 #ifndef ATMO_FAST_MISS_MASK
-#define ATMO_FAST_MISS_MASK 0x05  // baked-LUT atmosphere with and without clouds: -1.4 % / -0.7 %; the direct-light kernels lose 11 % (!), v1 1.5 %
+#define ATMO_FAST_MISS_MASK 0x05  // baked-LUT atmosphere with and without clouds: -1.4 % / -0.7 %; v1 loses 1.5 %.  The direct-light kernels (bit 1): round 3's
+                                  // "-11 %" was the view loop pushed off its fast position; with the loop held there the test still costs the headline
+                                  // draw +1.1 % at every one of the eight positions' best (profiles/direct_diet/sweep_variants.txt: b, ab against a) -- off
 #endif
 // Both forms give the same bits; which one a kernel variant uses is a measured choice (profiles/round2/ab_prologue.txt:
-// the short forms gain 3-4 % on the baked-LUT atmosphere kernels and cost the direct-light and the raymarched-cloud-light
-// kernels 2-3 % at 1920x1080 although they execute fewer instructions -- see the note at atmo_render_kernel).
+// the short forms gain 3-4 % on the baked-LUT atmosphere kernels; the raymarched-cloud-light kernels measured 2-3 % slower with them
+// at 1920x1080 and keep the long forms).  The cloudless direct-light kernels measured "2-3 % slower" too in round 2 -- an artefact: the
+// shorter prologue moved their view loop off its fast position (march_atmosphere).  Swept over all eight positions the short forms
+// gain 2.4 % there (profiles/direct_diet/sweep_variants.txt, variant a), and ATMO_DIRECT_PROLOGUE_DIET = 1 gives them to every
+// DIRECT && !CLOUDS kernel; 0 is the long form, for A/B builds.
+#ifndef ATMO_DIRECT_PROLOGUE_DIET   // the cloudless direct-light kernels take the short forms too
+#define ATMO_DIRECT_PROLOGUE_DIET 1
+#endif
 template <bool DIET = true>
 __device__ __forceinline__ float prologue_sqrt(float x) { return DIET ? exact_sqrt(x) : ieee_sqrt(x); }
 template <bool DIET = true>
@@ -1070,7 +1078,21 @@ __device__ __forceinline__ float cube_sample_lod_quad(const RenderConsts &rc, fl
 struct LightMarchConsts {
     float ninv_h, c1, dens2, ratm2, inv_light_steps;
     int light_steps;
+    float dens2_8;   // dens2 / 8, exact (ATMO_LIGHT_FOLD)
 };
+// ATMO_LIGHT_FOLD (the 8-step form; 0 = the arithmetic as first written, for A/B builds): scalings by exact powers of two folded into constants, the
+// same bits with three instructions fewer per view step (profiles/direct_diet/: -2.1 % on the headline draw).
+//   >= 1  lstep = ray_len / 8 is exact, so RN(lstep * (bdot + bdot)) = RN(ray_len * bdot) / 4 and RN(lstep * lstep) = RN(ray_len * ray_len) / 64: with
+//         m = ray_len * bdot and l2 = ray_len^2 the FMAs fma(j^2 / 64, l2, fma(j / 4, m, r2)) round the very same real numbers (j / 4 and j^2 / 64 are
+//         exact in binary), and RN(RN(acc * ray_len) * (dens2 / 8)) = RN(RN(acc * lstep) * dens2).  Scaling by 2^k commutes with rounding unless a
+//         result is subnormal: ray_len is 0 or at least an ulp of sq or bdot, so on a planet of radius >= 1e-7 l2 and m are normal or 0; on smaller
+//         ones a subnormal l2 or m is below 2^-126 against half an ulp of r2 >= R^2 and both forms add nothing (tests/test_direct_diet_fold.py; on the
+//         device tests/test_direct_diet_gpu.py, radius 2^-45).  acc * ray_len is subnormal only for a sun_od below 1e-37 * dens2.
+//   >= 2  no fmaxf(hh, 0) in front of the root: hh < 0 gives a NaN root, fminf(NaN, NaN) = NaN, and the fmaxf(., 0) behind it returns 0 for a NaN --
+//         ray_len = 0 as from the clamped form's sq = 0 (min(0, -bdot) clamped at 0).  hh = -0.0 cannot come out of a difference rounded to nearest.
+#ifndef ATMO_LIGHT_FOLD
+#define ATMO_LIGHT_FOLD 2
+#endif
 template <int LSTEPS>
 __device__ __forceinline__ float sun_od_direct(const LightMarchConsts &k, float r2, float bdot, float y3) {
 #pragma clang fp contract(fast)
@@ -1079,17 +1101,19 @@ __device__ __forceinline__ float sun_od_direct(const LightMarchConsts &k, float 
     // chord from the sample to the outer sphere along the sun direction, then a left Riemann sum.
     // x1 - max(x0, 0) with x0 = -b - sq, x1 = sq - b  ==  min(x1 - x0, x1) = min(2 sq, sq - b)
     const float hh = ratm2 - (r2 - bdot * bdot);
-    const float sq = hw_sqrt(fmaxf(hh, 0.0f));
+    const float sq = hw_sqrt((ATMO_LIGHT_FOLD >= 2 && LSTEPS == 8) ? hh : fmaxf(hh, 0.0f));
     // inside the outer sphere the forward exit distance is >= 0; hh < 0 (rounding at the shell) gives sq = 0 and
     // min(0, -b), which the max folds to the reference's 0
     const float ray_len = fmaxf(fminf(sq + sq, sq - bdot), 0.0f);
     const float lstep = ray_len * inv_light_steps;
     float acc = y3;  // sample 0 sits on the view sample itself
     if (LSTEPS == 8) {
-        const float lb = lstep * (bdot + bdot), l2 = lstep * lstep;
+        constexpr bool FOLD = ATMO_LIGHT_FOLD != 0;
+        const float lb = FOLD ? ray_len * bdot : lstep * (bdot + bdot), l2 = FOLD ? ray_len * ray_len : lstep * lstep;
+        constexpr float kb = FOLD ? 0.25f : 1.0f, k2 = FOLD ? 0.015625f : 1.0f;
         float q[8], rr[8];
 #pragma unroll
-        for (int j = 1; j < 8; ++j) q[j] = fmaf((float)(j * j), l2, fmaf((float)j, lb, r2));
+        for (int j = 1; j < 8; ++j) q[j] = fmaf((float)(j * j) * k2, l2, fmaf((float)j * kb, lb, r2));
         asm volatile("v_sqrt_f32 %0, %7\n\tv_sqrt_f32 %1, %8\n\tv_sqrt_f32 %2, %9\n\tv_sqrt_f32 %3, %10\n\t"
                      "v_sqrt_f32 %4, %11\n\tv_sqrt_f32 %5, %12\n\tv_sqrt_f32 %6, %13\n\ts_nop 0"
                      : "=&v"(rr[1]), "=&v"(rr[2]), "=&v"(rr[3]), "=&v"(rr[4]), "=&v"(rr[5]), "=&v"(rr[6]), "=&v"(rr[7])
@@ -1099,6 +1123,7 @@ __device__ __forceinline__ float sun_od_direct(const LightMarchConsts &k, float 
             const float yy = sat(fmaf(rr[j], ninv_h, c1));
             acc = fmaf(yy * yy, yy, acc);
         }
+        if (FOLD) return acc * ray_len * k.dens2_8;
     } else if (LSTEPS > 0) {
         // |o + j*l*sun|^2 = r2 + j*(l*2b) + j^2*(l*l), |sun| = 1: two FMAs per sample
         const float lb = lstep * (bdot + bdot), l2 = lstep * lstep;
@@ -1155,7 +1180,7 @@ __device__ __forceinline__ float4 march_atmosphere(const RenderConsts &rc, V3 di
     const float ratm2 = rc.atmosphere_radius * rc.atmosphere_radius;
     const int light_steps = LSTEPS > 0 ? LSTEPS : rc.light_steps;
     const float inv_light_steps = LSTEPS > 0 ? 1.0f / (float)(LSTEPS > 0 ? LSTEPS : 1) : hw_rcp((float)light_steps);
-    const LightMarchConsts lmc = {ninv_h, c1, dens2, ratm2, inv_light_steps, light_steps};
+    const LightMarchConsts lmc = {ninv_h, c1, dens2, ratm2, inv_light_steps, light_steps, dens2 * 0.125f};
     const float half_w = 0.5f * (float)rc.lut_w, x_off = half_w - 0.5f;
     const float lut_hf = (float)rc.lut_h, y_off = lut_hf - 0.5f;
 
@@ -1170,8 +1195,10 @@ __device__ __forceinline__ float4 march_atmosphere(const RenderConsts &rc, V3 di
     float lr = 0.0f, lg = 0.0f, lb = 0.0f, view_od = 0.0f;
 
     // WHERE THIS LOOP SITS IN THE INSTRUCTION STREAM IS PART OF THE HEADLINE KERNEL'S SPEED (round 6, profiles/round6/ab_loop_phase.txt).  In <4, 8, 1> the loop
-    // is 436 bytes, and the draw takes 0.0865 ms when its first instruction -- the target of the backward branch -- lies 12 bytes into a 32-byte block, 0.094-0.096 ms
-    // (+8.5 ... +11 %) at each of the other seven 4-byte positions; shifted by 32 bytes it is fast again.  Instructions inserted INSIDE the loop behind its first one
+    // was 436 bytes (81 VALU instructions), and the draw took 0.0865 ms when its first instruction -- the target of the backward branch -- lay 12 bytes into a 32-byte
+    // block, 0.094-0.096 ms (+8.5 ... +11 %) at each of the other seven 4-byte positions; shifted by 32 bytes it was fast again.  With ATMO_LIGHT_FOLD it is 428 bytes
+    // (78 VALU instructions) and fast at 4, 12, 20 and 28 bytes into the block, 7-9 % slower at 0, 8, 16 and 24 (profiles/direct_diet/: tools/phase_sweep.py times all
+    // eight); every twin is held at 12 (0.0821 ms; 4 bytes in measured 0.0818).  Instructions inserted INSIDE the loop behind its first one
     // cost their issue slot and nothing else, a 2 x unrolled body has no fast position at all, the LUT kernels' and the cloud kernels' loops do not care.  It is what
     // made rounds 2-5's "any scalar instruction in the preamble costs 8-10 %" and "an 80-SGPR cap (8 waves per SIMD) loses 8 %" -- both moved this loop by 4 bytes
     // (at the right position the capped build is exactly as fast as this one: the eighth wave buys nothing).  tests/test_host_logic.py holds the position
@@ -2088,7 +2115,8 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     static_assert(!PROXY || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0), "proxy draws: the default forms, one lane per ray, row-major");
     static_assert((FLAGS & KF_VIEWS) == 0 || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0),
                   "multi-view draws: the default forms, one lane per ray, float or packed targets (KF_VIEWS | KF_TARGET: atmo_render_views_target_kernel)");
-    constexpr bool DIET = !DIRECT && !((FLAGS & KF_CLOUDS) && (FLAGS & KF_CLOUD_LIGHT_RM));
+    // the short exact prologue: every kernel but cloud + direct-light and raymarched cloud light (prologue_sqrt)
+    constexpr bool DIET = (!DIRECT || (ATMO_DIRECT_PROLOGUE_DIET && !CLOUDS)) && !((FLAGS & KF_CLOUDS) && (FLAGS & KF_CLOUD_LIGHT_RM));
     constexpr bool FASTMISS = (ATMO_FAST_MISS_MASK >> ((DIRECT ? 1 : 0) + (CLOUDS ? 2 : 0) + (LITE ? 4 : 0))) & 1;
     static_assert(!LOD || (CLOUDS && PRECISE), "implicit cubemap LOD: precise cloud kernels");
     static_assert(!(LOD && SPLIT == 2) || (!ATMO_REF && !VIEWPOS && !LITE && !DIRECT), "two lanes per ray under the declared sampler: the two BASELINE cloud kernels");
@@ -2398,7 +2426,7 @@ __device__ __forceinline__ uint32_t geo_tile(const RenderConsts &rc, uint32_t b)
     return lo * tx + (o < first ? o : o + len);
 }
 #ifndef ATMO_LOOP_PAD_GEO   // s_nop in front of shade_pixel in the twin kernels <4 | KF_GEO, 8, 1>: puts their view loop 12 bytes into a 32-byte block
-#define ATMO_LOOP_PAD_GEO 6
+#define ATMO_LOOP_PAD_GEO 5
 #endif
 #define ATMO_GEO_STR2(x) #x
 #define ATMO_GEO_STR(x) ATMO_GEO_STR2(x)
@@ -2458,7 +2486,7 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render
 // kernels without raymarched light need the bound spelled out: their twins fit 62 VGPRs (eight waves per SIMD) under the common bound of six, these came
 // out at 68 (seven) without it.
 #ifndef ATMO_LOOP_PAD_VIEWS   // s_nop at the head of <KF_VIEWS | KF_LIGHT_DIRECT, 8>
-#define ATMO_LOOP_PAD_VIEWS 5
+#define ATMO_LOOP_PAD_VIEWS 3
 #endif
 #define ATMO_VIEWS_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_VIEWS)
 constexpr int views_min_waves(int flags) {
@@ -2499,10 +2527,10 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) __attribute__((a
 #undef ATMO_SHADE_EXTRA
 #define ATMO_SHADE_EXTRA , nullptr, &tc
 #ifndef ATMO_LOOP_PAD_TARGET       // s_nop at the head of both twins ...
-#define ATMO_LOOP_PAD_TARGET 4
+#define ATMO_LOOP_PAD_TARGET 3
 #endif
 #ifndef ATMO_LOOP_PAD_TARGET_GEO   // ... and more of them in the geometric-order twin, on top of ATMO_LOOP_PAD_GEO
-#define ATMO_LOOP_PAD_TARGET_GEO 5
+#define ATMO_LOOP_PAD_TARGET_GEO 6
 #endif
 #define ATMO_TARGET_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_TARGET)
 #define ATMO_TARGET_GEO_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_TARGET_GEO)
@@ -2532,7 +2560,7 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render
 // atmo_render_target_kernel is a substring of it), so that every other kernel keeps its code to the byte.  VGPRs: launch bounds as the float batch's
 // (views_min_waves); profiles/views/README.md holds the table against the float-batch twins.
 #ifndef ATMO_LOOP_PAD_VIEWS_TARGET   // s_nop at the head of <KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8>
-#define ATMO_LOOP_PAD_VIEWS_TARGET 5
+#define ATMO_LOOP_PAD_VIEWS_TARGET 3
 #endif
 #define ATMO_VIEWS_TARGET_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_VIEWS_TARGET)
 template <int FLAGS, int LSTEPS>
@@ -3007,6 +3035,7 @@ __global__ __launch_bounds__(256) void atmo_light_probe_kernel(const float *__re
     k.ninv_h = -inv_h;
     k.c1 = fmaf(planet_radius, inv_h, 1.0f);
     k.dens2 = density * density;
+    k.dens2_8 = k.dens2 * 0.125f;
     const float ratm = planet_radius + atmosphere_height;
     k.ratm2 = ratm * ratm;
     k.light_steps = light_steps;
