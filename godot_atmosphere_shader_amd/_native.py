@@ -47,6 +47,10 @@ VIEWS_TARGET_SYMBOLS = ("atmo_render_views_target",)
 # every symbol include/atmo_views_proxy.h declares: the far-mode (proxy) form of both batches -- several views of one planet's BoxMesh proxy in one launch.
 # The ABI version stays 5: a host detects the feature by the symbols.
 VIEWS_PROXY_SYMBOLS = ("atmo_render_views_proxy", "atmo_render_views_proxy_target")
+# every symbol include/atmo_planets.h declares: a frame's far planets -- several contexts -- in as few launches as blending allows.  The ABI version stays
+# 5 and EXPORTED_SYMBOLS stays the union of the seven older headers' tuples (NOTES.md): a host detects the feature by these symbols.
+PLANETS_SYMBOLS = ("atmo_render_planets", "atmo_plan_planets")
+MAX_PLANET_DRAWS = 64
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -87,6 +91,17 @@ class AtmoView(C.Structure):
 class AtmoViewTarget(C.Structure):
     _fields_ = [
         ("frame", AtmoFrame),
+        ("depth_dev", C.c_void_p),
+        ("target", AtmoTarget),
+    ]
+
+
+class AtmoPlanetDraw(C.Structure):   # include/atmo_planets.h
+    _fields_ = [
+        ("ctx", C.c_void_p),
+        ("frame", AtmoFrame),
+        ("model_matrix", C.c_float * 16),
+        ("box_size", C.c_float),
         ("depth_dev", C.c_void_p),
         ("target", AtmoTarget),
     ]
@@ -190,6 +205,8 @@ def load() -> C.CDLL:
         "atmo_render_views_proxy": (ip, [vp, C.POINTER(AtmoView), ip, fp, C.c_float, ip, vp]),
         "atmo_render_views_proxy_target": (ip, [vp, C.POINTER(AtmoViewTarget), ip, fp, C.c_float, ip, vp]),
         "atmo_debug_views_proxy_layout": (ip, [vp, C.POINTER(AtmoView), ip, fp, C.c_float, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]),
+        "atmo_render_planets": (ip, [C.POINTER(AtmoPlanetDraw), ip, vp]),
+        "atmo_plan_planets": (ip, [C.POINTER(AtmoPlanetDraw), ip, C.POINTER(ip), C.POINTER(ip)]),
         "atmo_debug_tile_order": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, C.POINTER(ip)]),
         "atmo_debug_heavy_tile_count": (ip, [vp, ip, ip, C.c_float, C.c_float, ip]),
         "atmo_debug_feedback_plan": (ip, [C.POINTER(AtmoFeedbackPlanIn), C.POINTER(AtmoFeedbackPlanOut)]),

@@ -12,9 +12,11 @@
 #include "../../include/atmo_views.h"
 #include "../../include/atmo_views_target.h"
 #include "../../include/atmo_views_proxy.h"
+#include "../../include/atmo_planets.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
+#include "atmo_planets_plan.h"
 #include "atmo_srgb_tables.h"
 
 #include <array>
@@ -2703,14 +2705,8 @@ int views_target_outputs(AtmoContext *ctx, const char *who, const AtmoViewTarget
         args[i].tc = {v.target.pixels, p, v.target.format};
         for (int j = 0; j < i; ++j) {
             if (L.empty[j]) continue;
-            const int a = base[j] <= base[i] ? j : i, b = a == j ? i : j;   // A: the view of lower base
-            // (a) the byte ranges [base, base + (rows - 1) * pitch + row_bytes) are disjoint
-            if (base[a] + (uintptr_t)((rows[a] - 1) * pitch[a] + row_bytes[a]) <= base[b]) continue;
-            // (b) one pitch P: B starts behind A's last row, or in the gap of A's rows and ends inside it (rows of one image, side by side)
-            if (pitch[a] == pitch[b]) {
-                const uintptr_t d = base[b] - base[a], P = (uintptr_t)pitch[a], q = d / P, r = d % P;
-                if (q >= (uintptr_t)rows[a] || (r >= (uintptr_t)row_bytes[a] && r + (uintptr_t)row_bytes[b] <= P)) continue;
-            }
+            // rules (a) and (b): the pair test atmo_render_planets plans with (atmo_planets_plan.h)
+            if (atmo::footprints_disjoint({(uint64_t)base[j], rows[j], row_bytes[j], pitch[j]}, {(uint64_t)base[i], rows[i], row_bytes[i], pitch[i]})) continue;
             return fail(ctx, ATMO_E_ARG, std::string(who) + ": views " + std::to_string(j) + " and " + std::to_string(i) + " write overlapping memory");
         }
     }
@@ -2884,6 +2880,130 @@ int atmo_debug_views_proxy_layout(AtmoContext *ctx, const AtmoView *views, int n
         grid[2 * i] = P.gx[i];
         grid[2 * i + 1] = P.gy[i];
         for (int k = 0; k < 4; ++k) rects[4 * i + k] = P.rect[i][k];
+    }
+    return ATMO_OK;
+}
+
+// ---- a frame's far planets in as few launches as blending allows (include/atmo_planets.h) ------------------------------------------------------------
+namespace {
+// What the checks leave of a call: per draw the single proxy draw's launch (proxy_setup: the box's constants, the cut rectangle and its tile grid, on the
+// frame the kernels see), its family and its target; and the plan (atmo_planets_plan.h).
+struct PlanetsLayout {
+    int flags[ATMO_MAX_PLANET_DRAWS];
+    bool lod[ATMO_MAX_PLANET_DRAWS];
+    int pitch[ATMO_MAX_PLANET_DRAWS];                 // the row pitch in effect, bytes
+    atmo::ProxyConsts pc[ATMO_MAX_PLANET_DRAWS];
+    int rect[ATMO_MAX_PLANET_DRAWS][4];
+    int gx[ATMO_MAX_PLANET_DRAWS], gy[ATMO_MAX_PLANET_DRAWS];
+    AtmoFrame fixed[ATMO_MAX_PLANET_DRAWS];
+    const AtmoFrame *frames[ATMO_MAX_PLANET_DRAWS];   // draw_frame: &draws[i].frame or &fixed[i]
+    int launch_of[ATMO_MAX_PLANET_DRAWS];
+    int n_launches = 0;
+};
+static_assert(ATMO_MAX_PLANET_DRAWS == atmo::PLANETS_MAX_DRAWS, "the header's draw count is the planner's");
+
+// Every check that needs no device, then the plan.  Messages that name a draw are stored on that draw's context.
+int planets_layout(const char *who, const AtmoPlanetDraw *draws, int n, PlanetsLayout &L) {
+    L.n_launches = 0;
+    if (n < 0 || n > ATMO_MAX_PLANET_DRAWS)   // (a negative count claims no entry: draws[0] is not looked at)
+        return fail(n > 0 && draws ? draws[0].ctx : nullptr, ATMO_E_ARG, std::string(who) + ": n_draws must be 0 .. " + std::to_string(ATMO_MAX_PLANET_DRAWS));
+    if (n == 0) return ATMO_OK;
+    if (!draws) return fail(nullptr, ATMO_E_ARG, std::string(who) + ": null draws");
+    auto name = [who](int i) { return std::string(who) + ": draw " + std::to_string(i); };
+    for (int i = 0; i < n; ++i) {
+        if (!draws[i].ctx) return fail(nullptr, ATMO_E_ARG, name(i) + ": null ctx");
+        if (draws[i].ctx->device != draws[0].ctx->device)
+            return fail(draws[i].ctx, ATMO_E_ARG, name(i) + ": its context is on another device than draw 0's (one device per call)");
+    }
+    bool empty[ATMO_MAX_PLANET_DRAWS];
+    for (int i = 0; i < n; ++i) {   // atmo_render_proxy_target's argument checks that need no matrix arithmetic
+        const AtmoPlanetDraw &d = draws[i];
+        const std::string who_i = name(i);
+        ATMO_TRY(target_check(d.ctx, who_i.c_str(), &d.frame, &d.target, true, &L.pitch[i]));
+        if (!(d.box_size > 0.0f) || !std::isfinite(d.box_size)) return fail(d.ctx, ATMO_E_ARG, who_i + ": box_size must be positive and finite");
+        ATMO_TRY(check_frame(d.ctx, who_i, &d.frame, &empty[i]));
+        ATMO_TRY(check_draw_pointers(d.ctx, who_i, d.depth_dev, (const float *)d.target.pixels, d.target.format == ATMO_TARGET_RGBA32F));
+    }
+    for (int i = 0; i < n; ++i) ATMO_TRY(proxy_family(draws[i].ctx, name(i).c_str(), &draws[i].frame, &L.flags[i], &L.lod[i]));   // the mode: ATMO_E_STATE
+    atmo::PlanetPlanIn in[ATMO_MAX_PLANET_DRAWS];
+    for (int i = 0; i < n; ++i) {
+        const AtmoPlanetDraw &d = draws[i];
+        L.gx[i] = L.gy[i] = 0;
+        L.frames[i] = draw_frame(d.ctx, &d.frame, L.fixed[i]);
+        std::memset(&in[i], 0, sizeof(in[i]));
+        if (empty[i]) continue;
+        ATMO_TRY(proxy_setup(d.ctx, name(i).c_str(), L.frames[i], d.model_matrix, d.box_size, L.lod[i], L.pc[i], L.rect[i], &L.gx[i], &L.gy[i]));
+        if (L.gx[i] == 0 || L.gy[i] == 0) continue;
+        const int64_t px = atmo_target_pixel_bytes(d.target.format);
+        const int *r = L.rect[i];
+        in[i].has_tile = 1;
+        in[i].fp = {(uint64_t)reinterpret_cast<uintptr_t>(d.target.pixels) + (uint64_t)((int64_t)r[1] * L.pitch[i] + (int64_t)r[0] * px), r[3] - r[1],
+                    (r[2] - r[0]) * px, L.pitch[i]};
+        // the family key (the device is the call's): the flags, the LSTEPS twin launch_default_family picks -- the direct-light families have the unrolled
+        // 8-step form --, and the kernel that stores the target: the float one, or the packed one with its format (one format per packed launch)
+        const uint64_t twin = ((L.flags[i] & atmo::KF_LIGHT_DIRECT) && d.ctx->light_steps == 8) ? 1u : 0u;
+        const uint64_t store = atmo::target_format_packed(d.target.format) ? (uint64_t)d.target.format + 1u : 0u;
+        in[i].key = (uint64_t)(uint32_t)L.flags[i] | twin << 32 | store << 40;
+    }
+    atmo::planets_plan(in, n, ATMO_MAX_VIEWS, L.launch_of, nullptr, &L.n_launches);
+    return ATMO_OK;
+}
+}  // namespace
+
+int atmo_plan_planets(const AtmoPlanetDraw *draws, int n_draws, int *launch_of, int *n_launches) {
+    PlanetsLayout L;
+    ATMO_TRY(planets_layout("atmo_plan_planets", draws, n_draws, L));
+    for (int i = 0; launch_of && i < n_draws; ++i) launch_of[i] = L.launch_of[i];
+    if (n_launches) *n_launches = L.n_launches;
+    return ATMO_OK;
+}
+
+// Launch by launch, in the plan's order, each as views_proxy_enqueue issues a proxy batch -- but every table entry from its own draw's context.
+int atmo_render_planets(const AtmoPlanetDraw *draws, int n_draws, void *stream) {
+    const char *who = "atmo_render_planets";
+    PlanetsLayout L;
+    ATMO_TRY(planets_layout(who, draws, n_draws, L));
+    for (int i = 0; i < n_draws; ++i) ATMO_TRY(check_draw_textures(draws[i].ctx, std::string(who) + ": draw " + std::to_string(i)));   // as the single draw: tile or not
+    if (L.n_launches == 0) return ATMO_OK;   // no draw has a tile: no launch, no staging slot
+    AtmoContext *ctx0 = draws[0].ctx;
+    HIP_TRY(ctx0, hipSetDevice(ctx0->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s))   // as views_proxy_enqueue: the tables are context-owned and later batches overwrite them
+        return fail(ctx0, ATMO_E_STATE, std::string(who) + " cannot be captured into a HIP graph (context-owned per-draw constants); capture atmo_render_proxy_target per draw instead");
+    for (int launch = 0; launch < L.n_launches; ++launch) {
+        int member[ATMO_MAX_VIEWS], n = 0;
+        for (int i = 0; i < n_draws; ++i) if (L.launch_of[i] == launch) member[n++] = i;   // (the plan: 1 .. ATMO_MAX_VIEWS draws of one key, each with a tile)
+        AtmoContext *first = draws[member[0]].ctx;
+        const bool packed = atmo::target_format_packed(draws[member[0]].target.format);
+        AtmoContext::ViewsSlot *slot = nullptr;
+        ATMO_TRY(views_ring_slot(first, &slot));
+        atmo::ViewsProxyTargetConsts vptc;   // (its targets are read by the packed kernels only)
+        std::memset(&vptc, 0, sizeof(vptc));
+        uint32_t total = 0;
+        for (int k = 0; k <= ATMO_MAX_VIEWS; ++k) {
+            vptc.p.first_block[k] = total;
+            if (k >= n) continue;
+            const int i = member[k];
+            const AtmoPlanetDraw &d = draws[i];
+            atmo::RenderConsts &rc = slot->host[k];
+            draw_consts(d.ctx, L.frames[i], d.depth_dev, (float *)d.target.pixels, true, packed ? 0 : L.pitch[i] / 16, packed, rc);
+            proxy_cut_rect(L.rect[i], L.lod[i], L.gx[i], rc);
+            vptc.p.proxy[k] = L.pc[i];
+            if (packed) vptc.target[k] = {d.target.pixels, L.pitch[i], d.target.format};
+            total += (uint32_t)L.gx[i] * (uint32_t)L.gy[i];   // (at most 2^25 tiles a draw: the sum of eight fits)
+        }
+        auto distinct = [&](int k) { for (int j = 0; j < k; ++j) if (draws[member[j]].ctx == draws[member[k]].ctx) return false; return true; };
+        for (int k = 0; k < n; ++k) if (distinct(k)) ATMO_TRY(tex_order(draws[member[k]].ctx, s));   // a texture updated on another stream
+        const int family = L.flags[member[0]];
+        HIP_TRY(first, hipMemcpyAsync(slot->dev, slot->host, (size_t)n * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
+        if (packed) HIP_TRY(first, atmo::launch_render_views_proxy_target(family, slot->host[0].light_steps, slot->dev, vptc, s));
+        else HIP_TRY(first, atmo::launch_render_views_proxy(family, slot->host[0].light_steps, slot->dev, vptc.p, s));
+        ATMO_TRY(views_ring_slot_used(first, slot, s));
+        for (int k = 0; k < n; ++k) {
+            if (!distinct(k)) continue;
+            hipEvent_t marker = nullptr;
+            ATMO_TRY(finish_draw(draws[member[k]].ctx, s, family | atmo::KF_VIEWS | atmo::KF_PROXY | (packed ? atmo::KF_TARGET : 0), 1, false, &marker));
+        }
     }
     return ATMO_OK;
 }

@@ -18,6 +18,7 @@ names, argument meaning and (silent) error behaviour:
   (the draw itself: Godot renderer)                    `render(camera, depth, out, rect, stream)`
   far mode's BoxMesh (:1-3,56-58,98-101,300-321)       `render_proxy*`, `proxy_box_size`; `draw` = the current mode's draw
   (several nodes in one frame: Godot renderer)         `draw_atmospheres(nodes, camera, depth, scene_rgba)`: back to front
+  (the same, far nodes batched: include/atmo_planets.h) `draw_atmospheres_batched(...)`, `render_planets(draws)`
 
 The fragment work runs only on the GPU: `render` raises if libatmo_hip.so or a gfx950 device is missing.
 """
@@ -896,4 +897,87 @@ def draw_atmospheres(nodes, camera, depth, scene_rgba, stream=None, time: float 
     kw = {} if target is None else {"target": target}
     for node in draw_order(list(nodes), camera):
         node.draw(camera, depth, scene_rgba, stream=stream, time=time, **kw)
+    return scene_rgba
+
+
+def prepare_planets(draws, time: float = 0.0):
+    """The native argument block of `render_planets_prepared` / `plan_planets`: one N.AtmoPlanetDraw per (node, camera, depth, scene_rgba, rect, box_size,
+    target) entry, the tensors checked as `PlanetAtmosphere.render_proxy_composite` checks them."""
+    draws = list(draws)
+    if len(draws) > N.MAX_PLANET_DRAWS:
+        raise ValueError(f"at most {N.MAX_PLANET_DRAWS} draws per call")
+    arr = (N.AtmoPlanetDraw * max(len(draws), 1))()
+    for i, (node, camera, depth, scene_rgba, rect, box_size, target) in enumerate(draws):
+        _check_depth(depth, camera, f"draw {i}: ")
+        tgt = _colour_target(scene_rgba, camera.height, camera.width, f"draw {i}: scene_rgba", target)
+        model, size = node._proxy(camera, box_size)
+        d = arr[i]
+        d.ctx = node._ctx
+        d.frame = _to_native_frame(node.make_frame(camera, time, rect))
+        d.model_matrix = model
+        d.box_size = size
+        d.depth_dev = depth.data_ptr()
+        d.target = tgt if tgt is not None else N.AtmoTarget(scene_rgba.data_ptr(), N.TARGET_RGBA32F, 0)
+    return arr
+
+
+def _check_planets(rc: int, arr, n: int, who: bytes) -> None:
+    if rc != N.ATMO_OK:   # the message lies on the context of the draw it names, on the first draw's, or in the slot without a context
+        lib = N.load()
+        msgs = [lib.atmo_last_error_string(arr[i].ctx) for i in range(n) if arr[i].ctx] + [lib.atmo_last_error_string(None)]
+        named = [m.decode() for m in msgs if m and m.startswith(who)]
+        raise N.AtmoError(rc, named[0] if named else "")
+
+
+def plan_planets(draws, time: float = 0.0):
+    """atmo_plan_planets: (launch_of, n_launches) -- for every entry of `draws` the launch of `render_planets` that holds it, or -1 when its box leaves
+    no tile on its rect.  Nothing is enqueued."""
+    draws = list(draws)
+    arr = prepare_planets(draws, time)
+    launch_of, n_launches = (C.c_int * max(len(draws), 1))(), C.c_int(0)
+    _check_planets(N.load().atmo_plan_planets(arr, len(draws), launch_of, C.byref(n_launches)), arr, len(draws), b"atmo_plan_planets")
+    return list(launch_of)[:len(draws)], n_launches.value
+
+
+def render_planets_prepared(arr, n_draws: int, stream: int = 0):
+    """Enqueue one frame's far planets from `prepare_planets`: one ctypes call."""
+    _check_planets(N.load().atmo_render_planets(arr, int(n_draws), C.c_void_p(stream or 0)), arr, int(n_draws), b"atmo_render_planets")
+
+
+def render_planets(draws, stream=None, time: float = 0.0):
+    """Several far-mode planets blended into their scene buffers in LIST ORDER by ONE native call (atmo_render_planets, include/atmo_planets.h): draws
+    that cannot touch on screen share a launch, draws that may keep their order.  `draws` is a list of (node, camera, depth, scene_rgba, rect, box_size,
+    target); entry i is bit for bit `node.render_proxy_composite(camera, depth, scene_rgba, rect=rect, box_size=box_size, target=target)` issued in that
+    order: rect None is the whole viewport, box_size None is `node.proxy_box_size(camera)`, scene_rgba a float32, float16 or uint8 tensor with an
+    optional row pitch, `target` the format name of a uint8 buffer that is not RGBA8_UNORM.  A node may appear more than once (stereo).  Bakes each
+    node's optical depth first if that is pending.  At most N.MAX_PLANET_DRAWS entries."""
+    draws = list(draws)
+    if not draws:
+        return
+    arr = prepare_planets(draws, time)
+    handle = _stream_handle(stream, draws[0][2])
+    for d in draws:
+        d[0]._bake_if_needed(handle)
+    render_planets_prepared(arr, len(draws), handle)
+
+
+def draw_atmospheres_batched(nodes, camera, depth, scene_rgba, stream=None, time: float = 0.0, target=None):
+    """`draw_atmospheres` with the far nodes batched: the same order (`draw_order`), the same bytes, but every maximal run of far-mode nodes in that
+    order goes through ONE `render_planets` call -- planets that do not overlap on screen share a launch -- and a near-mode node, whose fullscreen
+    draw touches everything, is its own `node.draw` between the runs.  Returns `scene_rgba`."""
+    kw = {} if target is None else {"target": target}
+    run = []
+
+    def flush():
+        if run:
+            render_planets([(n, camera, depth, scene_rgba, None, None, target) for n in run], stream=stream, time=time)
+            run.clear()
+
+    for node in draw_order(list(nodes), camera):
+        if node._mode == MODE_FAR:
+            run.append(node)
+            continue
+        flush()
+        node.draw(camera, depth, scene_rgba, stream=stream, time=time, **kw)
+    flush()
     return scene_rgba
