@@ -30,6 +30,7 @@ DEBUG_SYMBOLS = (
     "atmo_host_layout_lut", "atmo_host_cubemap_mip", "atmo_read_texture_layout", "atmo_selftest_exact_math", "atmo_debug_marched_optical_depth", "atmo_debug_log2_cr", "atmo_kernel_name", "atmo_build_id",
     "atmo_get_host_wait_stats", "atmo_get_split_stats", "atmo_debug_create_host_only", "atmo_debug_frame_constants", "atmo_debug_proxy_launch_rect",
     "atmo_debug_store_target", "atmo_debug_views_layout", "atmo_debug_views_proxy_layout", "atmo_debug_tile_order", "atmo_debug_heavy_tile_count", "atmo_debug_feedback_plan",
+    "atmo_debug_decode_depth",
 )
 # every symbol include/atmo_scene.h declares: drawing several atmospheres into one frame (the far-mode BoxMesh draw)
 SCENE_SYMBOLS = ("atmo_render_proxy", "atmo_render_proxy_composite")
@@ -51,6 +52,12 @@ VIEWS_PROXY_SYMBOLS = ("atmo_render_views_proxy", "atmo_render_views_proxy_targe
 # 5 and EXPORTED_SYMBOLS stays the union of the seven older headers' tuples (NOTES.md): a host detects the feature by these symbols.
 PLANETS_SYMBOLS = ("atmo_render_planets", "atmo_plan_planets")
 MAX_PLANET_DRAWS = 64
+# every symbol include/atmo_depth.h declares: the target draws with the depth buffer in its own format (D32_SFLOAT, D16_UNORM, X8_D24_UNORM) and row pitch.
+# The ABI version stays 5 and the tuple stands beside EXPORTED_SYMBOLS, as PLANETS_SYMBOLS (NOTES.md): a host detects the feature by these symbols and
+# atmo_depth_texel_bytes(format) != 0.
+DEPTH_SYMBOLS = ("atmo_depth_texel_bytes", "atmo_render_depth_target", "atmo_render_proxy_depth_target", "atmo_render_views_depth_target",
+                 "atmo_render_views_proxy_depth_target")
+DEPTH_D32_SFLOAT, DEPTH_D16_UNORM, DEPTH_X8_D24_UNORM = range(3)
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -92,6 +99,22 @@ class AtmoViewTarget(C.Structure):
     _fields_ = [
         ("frame", AtmoFrame),
         ("depth_dev", C.c_void_p),
+        ("target", AtmoTarget),
+    ]
+
+
+class AtmoDepth(C.Structure):   # include/atmo_depth.h
+    _fields_ = [
+        ("texels", C.c_void_p),
+        ("format", C.c_int32),
+        ("row_pitch_bytes", C.c_int32),
+    ]
+
+
+class AtmoViewDepthTarget(C.Structure):   # include/atmo_depth.h
+    _fields_ = [
+        ("frame", AtmoFrame),
+        ("depth", AtmoDepth),
         ("target", AtmoTarget),
     ]
 
@@ -207,6 +230,12 @@ def load() -> C.CDLL:
         "atmo_debug_views_proxy_layout": (ip, [vp, C.POINTER(AtmoView), ip, fp, C.c_float, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]),
         "atmo_render_planets": (ip, [C.POINTER(AtmoPlanetDraw), ip, vp]),
         "atmo_plan_planets": (ip, [C.POINTER(AtmoPlanetDraw), ip, C.POINTER(ip), C.POINTER(ip)]),
+        "atmo_depth_texel_bytes": (ip, [ip]),
+        "atmo_render_depth_target": (ip, [vp, C.POINTER(AtmoFrame), C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), ip, vp]),
+        "atmo_render_proxy_depth_target": (ip, [vp, C.POINTER(AtmoFrame), fp, C.c_float, C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), ip, vp]),
+        "atmo_render_views_depth_target": (ip, [vp, C.POINTER(AtmoViewDepthTarget), ip, ip, vp]),
+        "atmo_render_views_proxy_depth_target": (ip, [vp, C.POINTER(AtmoViewDepthTarget), ip, fp, C.c_float, ip, vp]),
+        "atmo_debug_decode_depth": (ip, [ip, vp, vp, C.c_size_t, vp]),
         "atmo_debug_tile_order": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, C.POINTER(ip)]),
         "atmo_debug_heavy_tile_count": (ip, [vp, ip, ip, C.c_float, C.c_float, ip]),
         "atmo_debug_feedback_plan": (ip, [C.POINTER(AtmoFeedbackPlanIn), C.POINTER(AtmoFeedbackPlanOut)]),

@@ -17,7 +17,8 @@ SOURCES = ["atmo_api.hip", "atmo_kernels.hip"]
 HEADERS = ["atmo_device.h", "atmo_layout.h", "atmo_feedback_plan.h", "atmo_planets_plan.h", "atmo_srgb_tables.h", os.path.join("..", "..", "include", "atmo.h"), os.path.join("..", "..", "include", "atmo_debug.h"),
            os.path.join("..", "..", "include", "atmo_scene.h"), os.path.join("..", "..", "include", "atmo_target.h"),
            os.path.join("..", "..", "include", "atmo_views.h"), os.path.join("..", "..", "include", "atmo_views_target.h"),
-           os.path.join("..", "..", "include", "atmo_views_proxy.h"), os.path.join("..", "..", "include", "atmo_planets.h")]
+           os.path.join("..", "..", "include", "atmo_views_proxy.h"), os.path.join("..", "..", "include", "atmo_planets.h"),
+           os.path.join("..", "..", "include", "atmo_depth.h")]
 
 # -ffp-contract=off: the kernels and the host-side per-frame constants must round exactly like a scalar
 # fp32 evaluation of the shader wherever control flow or the ill-conditioned cloud chain is involved;

@@ -13,6 +13,7 @@
 #include "../../include/atmo_views_target.h"
 #include "../../include/atmo_views_proxy.h"
 #include "../../include/atmo_planets.h"
+#include "../../include/atmo_depth.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -576,6 +577,28 @@ int check_frame(AtmoContext *ctx, const std::string &who, const AtmoFrame *frame
 int check_draw_pointers(AtmoContext *ctx, const std::string &who, const float *depth_dev, const float *rgba_dev, bool float4_target) {
     if (!depth_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": null device pointer");
     if (float4_target && (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, who + ": rgba_dev must be 16-byte aligned");
+    return ATMO_OK;
+}
+// ... and of a depth source (include/atmo_depth.h), where the draws of atmo_depth.h have it in place of the depth_dev null check: w x h = the viewport.
+// On success *out = what the KF_DEPTH kernels read (the tight pitch for row_pitch_bytes == 0).
+static_assert((int)ATMO_DEPTH_D32_SFLOAT == (int)atmo::DF_D32_SFLOAT && (int)ATMO_DEPTH_D16_UNORM == (int)atmo::DF_D16_UNORM &&
+                  (int)ATMO_DEPTH_X8_D24_UNORM == (int)atmo::DF_X8_D24_UNORM,
+              "DepthFormat == AtmoDepthFormat");
+int depth_check(AtmoContext *ctx, const std::string &who, const AtmoDepth *depth, int w, int h, atmo::DepthConsts *out) {
+    (void)h;
+    if (!depth) return fail(ctx, ATMO_E_ARG, who + ": null depth");
+    const int tb = atmo::depth_texel_bytes(depth->format);
+    if (tb == 0) return fail(ctx, ATMO_E_ARG, who + ": unknown depth format " + std::to_string(depth->format));
+    if (!depth->texels) return fail(ctx, ATMO_E_ARG, who + ": null depth texels");
+    if ((reinterpret_cast<uintptr_t>(depth->texels) & (uintptr_t)(tb - 1)) != 0)
+        return fail(ctx, ATMO_E_ARG, who + ": depth texels must be aligned to the texel size (" + std::to_string(tb) + " bytes)");
+    const long long row_bytes = (long long)w * tb;
+    long long pitch = depth->row_pitch_bytes;
+    if (pitch == 0) pitch = row_bytes;
+    if (pitch < row_bytes || pitch % tb != 0)
+        return fail(ctx, ATMO_E_ARG, who + ": depth row_pitch_bytes must be 0, or at least the viewport row's bytes (" + std::to_string(row_bytes) +
+                                         ") and a multiple of the texel size (" + std::to_string(tb) + ")");
+    *out = {depth->texels, (int32_t)pitch, depth->format};   // (row_bytes <= 65536 * 4 and pitch is an int32: no overflow)
     return ATMO_OK;
 }
 int check_draw_textures(AtmoContext *ctx, const std::string &who) {
@@ -1492,7 +1515,8 @@ int atmo_read_optical_depth(AtmoContext *ctx, float *lut_host, uint8_t *rgba8_ho
 // tc != nullptr: a packed colour target (atmo_render_target): rgba_dev is its pixels (checked by the caller), the launches are the KF_TARGET kernels';
 // pitch_px > 0: pixels per output row (an RGBA32F target with a pitch)
 static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream, bool composite,
-                       const uint32_t *tiles_dev = nullptr, int n_tiles = 0, int n_heavy = 0, const atmo::TargetConsts *tc = nullptr, int pitch_px = 0);
+                       const uint32_t *tiles_dev = nullptr, int n_tiles = 0, int n_heavy = 0, const atmo::TargetConsts *tc = nullptr, int pitch_px = 0,
+                       bool depth_source = false, const AtmoDepth *depth = nullptr);
 
 int atmo_render(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream) {
     return render_impl(ctx, frame, depth_dev, rgba_dev, stream, false);
@@ -1687,7 +1711,9 @@ static int finish_draw(AtmoContext *ctx, hipStream_t s, int family, int split, b
 }
 
 // A launch of a single draw: the float kernels, or (tc) their packed-target twins
-static hipError_t launch_draw(const atmo::TargetConsts *tc, int flags, int split, const atmo::RenderConsts &rc, hipStream_t s, int blocks) {
+static hipError_t launch_draw(const atmo::TargetConsts *tc, int flags, int split, const atmo::RenderConsts &rc, hipStream_t s, int blocks,
+                              const atmo::DepthConsts *dc = nullptr) {   // dc (with tc): the depth-source twins of those (include/atmo_depth.h)
+    if (dc) return tc ? atmo::launch_render_depth_target(flags, split, rc, *tc, *dc, s, blocks) : hipErrorInvalidValue;
     return tc ? atmo::launch_render_target(flags, split, rc, *tc, s, blocks) : atmo::launch_render(flags, split, rc, s, blocks);
 }
 
@@ -1754,16 +1780,16 @@ static int bound_tile_list(AtmoContext *ctx, const AtmoFrame *frame, atmo::Rende
 // throughput (1920x1080 pose P_space, where the lane-split kernel on EVERY tile is 43 % slower; 3840x2160), which the trigger keeps out;
 // the kernel without raymarched light never gains (its heaviest wave is a fifth as long): not split unless forced (ATMO_HEAVY_SPLIT=2).
 static int launch_heavy_split(AtmoContext *ctx, const atmo::TargetConsts *tc, int flags, int split, atmo::RenderConsts &rc, hipStream_t s,
-                              const uint32_t *order2, int heavy, int total_tiles) {
+                              const uint32_t *order2, int heavy, int total_tiles, const atmo::DepthConsts *dc = nullptr) {
     if (!ctx->split_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->split_stream, hipStreamNonBlocking));
     ATMO_TRY(order_after_stream(ctx, ctx->split_stream, s));   // fork: behind everything the draw is behind
     atmo::RenderConsts rc2 = rc;
     rc2.tile_order = order2;                       // two half-height tiles per heavy tile, heaviest first
     rc2.cost_rows_halved = 1;                      // ... whose costs belong to the one-lane grid's tile (only this launch: ADVICE r5)
-    HIP_TRY(ctx, launch_draw(tc, flags, 2, rc2, ctx->split_stream, 2 * heavy));
+    HIP_TRY(ctx, launch_draw(tc, flags, 2, rc2, ctx->split_stream, 2 * heavy, dc));
     if (total_tiles - heavy > 0) {
         rc.tile_order += heavy;                    // the rest of the order, one lane per ray
-        HIP_TRY(ctx, launch_draw(tc, flags, split, rc, s, total_tiles - heavy));
+        HIP_TRY(ctx, launch_draw(tc, flags, split, rc, s, total_tiles - heavy, dc));
     }
     ATMO_TRY(order_after_stream(ctx, s, ctx->split_stream));   // join
     ctx->split_draws += 1;
@@ -1772,13 +1798,21 @@ static int launch_heavy_split(AtmoContext *ctx, const atmo::TargetConsts *tc, in
 }
 
 static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream, bool composite,
-                       const uint32_t *tiles_dev, int n_tiles, int n_heavy, const atmo::TargetConsts *tc, int pitch_px) {
+                       const uint32_t *tiles_dev, int n_tiles, int n_heavy, const atmo::TargetConsts *tc, int pitch_px, bool depth_source,
+                       const AtmoDepth *depth) {   // depth_source: atmo_render_depth_target -- `depth` in place of depth_dev, tc set for every format
     // 1. checks
     if (!ctx) return ATMO_E_ARG;
     bool empty = false;
     ATMO_TRY(check_frame(ctx, "atmo_render", frame, &empty));
     if (empty) return ATMO_OK;  // empty rect: nothing to shade
-    ATMO_TRY(check_draw_pointers(ctx, "atmo_render", depth_dev, rgba_dev, !tc));
+    atmo::DepthConsts depth_consts = {nullptr, 0, 0};
+    const atmo::DepthConsts *dc = nullptr;
+    if (depth_source) {
+        ATMO_TRY(depth_check(ctx, "atmo_render_depth_target", depth, frame->viewport_w, frame->viewport_h, &depth_consts));
+        dc = &depth_consts;
+    } else {
+        ATMO_TRY(check_draw_pointers(ctx, "atmo_render", depth_dev, rgba_dev, !tc));
+    }
     ATMO_TRY(check_draw_textures(ctx, "atmo_render"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
@@ -1868,14 +1902,14 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
                                  ctx->heavy_split == 2 ? 0.0f : (plan.sort_instream ? ctx->heavy_split_trigger_moving : ctx->heavy_split_trigger),
                                  1024 * 6);   // both declared-sampler cloud kernels hold six waves per SIMD
     if (tiles_dev) heavy = n_heavy;   // a tile-list draw: the caller says how many of its leading tiles are heavy (atmo_render_tiles_split)
-    if (heavy > 0) ATMO_TRY(launch_heavy_split(ctx, tc, flags, split, rc, s, order2, heavy, tiles_dev ? n_tiles : gx * gy));
-    else HIP_TRY(ctx, launch_draw(tc, launch_flags, split, rc, s, tiles_dev ? n_tiles : 0));
+    if (heavy > 0) ATMO_TRY(launch_heavy_split(ctx, tc, flags, split, rc, s, order2, heavy, tiles_dev ? n_tiles : gx * gy, dc));
+    else HIP_TRY(ctx, launch_draw(tc, launch_flags, split, rc, s, tiles_dev ? n_tiles : 0, dc));
 
     // 9. sorts, 10. bookkeeping
     if (plan.sort_side) ATMO_TRY(feedback_sort_side(ctx, *fb, gx, gy, plan, s));
     if (fb) fb->n += 1;
     hipEvent_t marker = nullptr;   // the draw stream's marker, when this draw recorded one (re-recorded behind the in-stream sort below)
-    ATMO_TRY(finish_draw(ctx, s, tc ? (flags | atmo::KF_TARGET) : flags, split, true, &marker));   // (atmo_kernel_name: the family without KF_GEO)
+    ATMO_TRY(finish_draw(ctx, s, tc ? (flags | atmo::KF_TARGET | (dc ? atmo::KF_DEPTH : 0)) : flags, split, true, &marker));   // (atmo_kernel_name: the family without KF_GEO)
     ATMO_TRY(timing_end(ctx, timing, s));
     if (plan.sort_instream) {  // behind the draw (and behind the timing bracket, which is the draw kernel's alone)
         ATMO_TRY(feedback_sort(ctx, *fb, 2, gx, gy, plan.dil_rx, plan.dil_ry, s, fb->is_scratch));
@@ -2279,15 +2313,19 @@ static void proxy_cut_rect(const int *rect, bool lod, int gx, atmo::RenderConsts
 }
 
 static int proxy_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev, float *rgba_dev,
-                      void *stream, bool composite, const atmo::TargetConsts *tc = nullptr, int pitch_px = 0) {   // tc, pitch_px: as render_impl's
+                      void *stream, bool composite, const atmo::TargetConsts *tc = nullptr, int pitch_px = 0, bool depth_source = false,
+                      const AtmoDepth *depth = nullptr) {   // tc, pitch_px, depth_source, depth: as render_impl's
     if (!ctx) return ATMO_E_ARG;
-    const char *who = (tc || pitch_px) ? "atmo_render_proxy_target" : composite ? "atmo_render_proxy_composite" : "atmo_render_proxy";
+    const char *who = depth_source ? "atmo_render_proxy_depth_target"
+                                   : (tc || pitch_px) ? "atmo_render_proxy_target" : composite ? "atmo_render_proxy_composite" : "atmo_render_proxy";
     if (!frame || !model_matrix) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null frame or model_matrix");
     if (!(box_size > 0.0f) || !std::isfinite(box_size)) return fail(ctx, ATMO_E_ARG, std::string(who) + ": box_size must be positive and finite");
     bool empty = false;
     ATMO_TRY(check_frame(ctx, who, frame, &empty));
     // (unlike render_impl, the pointers, the textures and the mode are checked in front of the empty rect's ATMO_OK)
-    ATMO_TRY(check_draw_pointers(ctx, who, depth_dev, rgba_dev, !tc));
+    atmo::DepthConsts dc = {nullptr, 0, 0};
+    if (depth_source) ATMO_TRY(depth_check(ctx, who, depth, frame->viewport_w, frame->viewport_h, &dc));
+    else ATMO_TRY(check_draw_pointers(ctx, who, depth_dev, rgba_dev, !tc));
     ATMO_TRY(check_draw_textures(ctx, who));
     int flags = 0;
     bool lod = false;
@@ -2305,10 +2343,11 @@ static int proxy_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *mod
     proxy_cut_rect(rect, lod, gx, rc);
     hipStream_t s = (hipStream_t)stream;
     ATMO_TRY(tex_order(ctx, s));
-    if (tc) HIP_TRY(ctx, atmo::launch_render_proxy_target(flags, rc, pc, *tc, s));
+    if (depth_source) HIP_TRY(ctx, tc ? atmo::launch_render_proxy_depth_target(flags, rc, pc, *tc, dc, s) : hipErrorInvalidValue);
+    else if (tc) HIP_TRY(ctx, atmo::launch_render_proxy_target(flags, rc, pc, *tc, s));
     else HIP_TRY(ctx, atmo::launch_render_proxy(flags, rc, pc, s));
     hipEvent_t marker = nullptr;
-    return finish_draw(ctx, s, flags | atmo::KF_PROXY | (tc ? atmo::KF_TARGET : 0), 1, false, &marker);
+    return finish_draw(ctx, s, flags | atmo::KF_PROXY | (tc ? atmo::KF_TARGET : 0) | (depth_source ? atmo::KF_DEPTH : 0), 1, false, &marker);
 }
 
 int atmo_render_proxy(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev, float *rgba_dev,
@@ -2366,12 +2405,17 @@ static int target_check(AtmoContext *ctx, const char *who, const AtmoFrame *fram
 }
 
 // The packed formats are drawn by the default forms' kernels only (target_family_supported); RGBA32F by the float kernels, whatever the mode.
-static int target_family(AtmoContext *ctx, const char *who, const AtmoFrame *frame) {
+// depth_source: the caller is atmo_render_depth_target, whose kernels draw RGBA32F too -- no target format works in another mode there.
+static int target_family(AtmoContext *ctx, const char *who, const AtmoFrame *frame, bool depth_source = false) {
     int flags = 0, split = 1;
     launch_shape(ctx, frame, &flags, &split, nullptr);
-    if (!atmo::target_family_supported(flags, split))
+    if (!atmo::target_family_supported(flags, split)) {
+        if (depth_source)
+            return fail(ctx, ATMO_E_STATE, std::string(who) + ": no depth-source kernel for this context's mode (they exist for the default forms: atmo_set_precision 1, "
+                                                              "up to 32 view steps, one lane per ray), whatever the target format, RGBA32F included");
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": no RGBA16F / RGBA8 kernel for this context's mode (packed targets, every format but RGBA32F, exist for the default forms: "
                                                           "atmo_set_precision 1, up to 32 view steps, one lane per ray); RGBA32F targets work in every mode");
+    }
     return ATMO_OK;
 }
 
@@ -2395,6 +2439,36 @@ int atmo_render_proxy_target(AtmoContext *ctx, const AtmoFrame *frame, const flo
         return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, (float *)target->pixels, stream, composite != 0, nullptr, pitch / 16);
     const atmo::TargetConsts tc = {target->pixels, pitch, target->format};   // (proxy_impl refuses the modes without a proxy kernel: the same set)
     return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, (float *)target->pixels, stream, composite != 0, &tc, 0);
+}
+
+// ---- depth sources (include/atmo_depth.h): the two draws above with the depth buffer in its own format and pitch ------------------------------
+// Every target format, RGBA32F included, goes to the KF_DEPTH | KF_TARGET kernels (the default forms: target_family for all of them).
+int atmo_depth_texel_bytes(int format) { return atmo::depth_texel_bytes(format); }
+
+int atmo_render_depth_target(AtmoContext *ctx, const AtmoFrame *frame, const AtmoDepth *depth, const AtmoTarget *target, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    int pitch = 0;
+    ATMO_TRY(target_check(ctx, "atmo_render_depth_target", frame, target, composite != 0, &pitch));
+    ATMO_TRY(target_family(ctx, "atmo_render_depth_target", frame, true));
+    const atmo::TargetConsts tc = {target->pixels, pitch, target->format};
+    return render_impl(ctx, frame, nullptr, (float *)target->pixels, stream, composite != 0, nullptr, 0, 0, &tc, 0, true, depth);
+}
+
+int atmo_render_proxy_depth_target(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const AtmoDepth *depth,
+                                   const AtmoTarget *target, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    int pitch = 0;
+    ATMO_TRY(target_check(ctx, "atmo_render_proxy_depth_target", frame, target, composite != 0, &pitch));
+    const atmo::TargetConsts tc = {target->pixels, pitch, target->format};   // (proxy_impl refuses the modes without a proxy kernel: the same set)
+    return proxy_impl(ctx, frame, model_matrix, box_size, nullptr, (float *)target->pixels, stream, composite != 0, &tc, 0, true, depth);
+}
+
+// atmo_debug.h: the kernels' depth decode on a caller-supplied DEVICE array
+int atmo_debug_decode_depth(int format, const void *texels_dev, float *out_dev, size_t n, void *stream) {
+    const int tb = atmo::depth_texel_bytes(format);
+    if (tb == 0 || !texels_dev || !out_dev || n > ((size_t)1 << 31)) return ATMO_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(texels_dev) & (uintptr_t)(tb - 1)) != 0 || (reinterpret_cast<uintptr_t>(out_dev) & 3u) != 0) return ATMO_E_ARG;
+    return atmo::launch_decode_depth(format, texels_dev, out_dev, n, (hipStream_t)stream) == hipSuccess ? ATMO_OK : ATMO_E_HIP;
 }
 
 // atmo_debug.h: the kernels' store_target<format> on caller-supplied DEVICE arrays -- dst[i] = encode(src[i]), or, composite, encode(blend(src[i], decode(dst[i])))
@@ -2451,6 +2525,7 @@ struct ViewArg {
     void *pixels = nullptr;                 // as the single draw's: plain -- the rect's first pixel; composite -- the viewport's
     int pitch_px = 0;                       // float targets: pixels from one row to the next, 0 = the draw's own (tight)
     atmo::TargetConsts tc = {nullptr, 0, 0};   // packed targets (RGBA16F / RGBA8_UNORM)
+    atmo::DepthConsts dc = {nullptr, 0, 0};    // depth-source batches (include/atmo_depth.h): in place of `depth`, and tc for every target format
 };
 
 // The float batches' views (AtmoView) as ViewArg: frame, depth and output; no pitch, no packed target.  Null views or a bad count: views_check_frames' to refuse.
@@ -2587,7 +2662,9 @@ static int views_ring_slot_used(AtmoContext *ctx, AtmoContext::ViewsSlot *slot, 
 }
 // Everything a batch does once its arguments stand: the staging slot, the per-view constants, the tile order and its feedback, the ONE launch.  Shared by
 // atmo_render_views (packed == false: the float kernels, args[i].pitch_px) and atmo_render_views_target (packed: the KF_VIEWS | KF_TARGET kernels, args[i].tc).
-int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, int composite, bool packed, const ViewsLayout &L, void *stream) {
+// depth_source: atmo_render_views_depth_target (packed set whatever the format: the KF_DEPTH | KF_VIEWS | KF_TARGET kernels, args[i].tc and args[i].dc).
+int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, int composite, bool packed, const ViewsLayout &L, void *stream,
+                  bool depth_source = false) {
     if (L.n_drawn == 0) return ATMO_OK;   // n_views == 0, or every rect empty: nothing to shade
     ATMO_TRY(check_draw_textures(ctx, who));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2614,6 +2691,9 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_
     std::memset(&vtc, 0, sizeof(vtc));
     atmo::ViewsConsts &vc = vtc.v;
     for (int i = 0; packed && i < n_views; ++i) if (!L.empty[i]) vtc.target[i] = args[i].tc;
+    atmo::ViewsDepthConsts vdc;    // (read by the depth-source kernels only)
+    std::memset(&vdc, 0, sizeof(vdc));
+    for (int i = 0; depth_source && i < n_views; ++i) if (!L.empty[i]) vdc.depth[i] = args[i].dc;
     for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) vc.first_block[i] = L.first_block[i];
     const uint32_t total = L.first_block[ATMO_MAX_VIEWS];
     // One tile order over all views, learnt as render_impl learns a single draw's on a still camera: feedback_plan's batch form
@@ -2632,7 +2712,8 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_
     ATMO_TRY(timing_open(ctx, timing));
     HIP_TRY(ctx, hipMemcpyAsync(slot->dev, slot->host, (size_t)n_views * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
     ATMO_TRY(timing_begin(ctx, timing, s));   // the bracket is the one launch's
-    if (packed) HIP_TRY(ctx, atmo::launch_render_views_target(L.flags, slot->host[first].light_steps, slot->dev, vtc, s));
+    if (depth_source) HIP_TRY(ctx, atmo::launch_render_views_depth_target(L.flags, slot->host[first].light_steps, slot->dev, vtc, vdc, s));
+    else if (packed) HIP_TRY(ctx, atmo::launch_render_views_target(L.flags, slot->host[first].light_steps, slot->dev, vtc, s));
     else HIP_TRY(ctx, atmo::launch_render_views(L.flags, slot->host[first].light_steps, slot->dev, vc, s));
     ATMO_TRY(timing_end(ctx, timing, s));
     ATMO_TRY(views_ring_slot_used(ctx, slot, s));
@@ -2669,8 +2750,9 @@ int views_float_outputs(AtmoContext *ctx, const char *who, const AtmoView *views
 // The target batches' argument checks (atmo_render_views_target, atmo_render_views_proxy_target): the count and every view's frame (views_check_frames;
 // *done as there), then per view atmo_render_target's checks, one format per batch, and the overlap rule of include/atmo_views_target.h on the bytes it
 // writes -- `rows` rows of `row_bytes`, `pitch` apart, from `base`.  Fills args; *packed: the batch's format is not RGBA32F.
+// depths (atmo_depth.h's batches): view i's depth source, checked (depth_check, into args[i].dc) where the float batches have their depth_dev null check.
 int views_target_outputs(AtmoContext *ctx, const char *who, const AtmoViewTarget *views, int n_views, int composite, ViewArg *args, ViewsLayout &L,
-                         bool *done, bool *packed) {
+                         bool *done, bool *packed, const AtmoDepth *const *depths = nullptr) {
     for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) {
         args[i].frame = &views[i].frame;
         args[i].depth = views[i].depth_dev;
@@ -2690,7 +2772,8 @@ int views_target_outputs(AtmoContext *ctx, const char *who, const AtmoViewTarget
         const std::string who_i = std::string(who) + ": view " + std::to_string(i);
         int p = 0;
         ATMO_TRY(target_check(ctx, who_i.c_str(), &v.frame, &v.target, composite != 0, &p));
-        ATMO_TRY(check_draw_pointers(ctx, who_i, v.depth_dev, (const float *)v.target.pixels, false));
+        if (depths) ATMO_TRY(depth_check(ctx, who_i, depths[i], v.frame.viewport_w, v.frame.viewport_h, &args[i].dc));
+        else ATMO_TRY(check_draw_pointers(ctx, who_i, v.depth_dev, (const float *)v.target.pixels, false));
         if (format >= 0 && v.target.format != format)
             return fail(ctx, ATMO_E_ARG, who_i + ": target format " + std::to_string(v.target.format) + " differs from the batch's (" + std::to_string(format) +
                                              "): one format per batch");
@@ -2760,7 +2843,7 @@ int views_proxy_layout(AtmoContext *ctx, const char *who, const ViewArg *args, i
 // addressed by the frame's rect or the viewport, as proxy_impl fills it), the ONE launch.  No tile order, no feedback state, not timed and not counted, as
 // the single proxy draw.
 int views_proxy_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, int composite, bool packed, const ViewsLayout &L,
-                        const ViewsProxyLayout &P, void *stream) {
+                        const ViewsProxyLayout &P, void *stream, bool depth_source = false) {   // depth_source: as views_enqueue's
     if (P.first_block[ATMO_MAX_VIEWS] == 0) return ATMO_OK;   // no view has a tile: no launch, no staging slot
     ATMO_TRY(check_draw_textures(ctx, who));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2771,6 +2854,8 @@ int views_proxy_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, 
     ATMO_TRY(views_ring_slot(ctx, &slot));
     atmo::ViewsProxyTargetConsts vptc;   // (its targets are read by the packed kernels only)
     std::memset(&vptc, 0, sizeof(vptc));
+    atmo::ViewsDepthConsts vdc;          // (read by the depth-source kernels only)
+    std::memset(&vdc, 0, sizeof(vdc));
     int first = -1;
     for (int i = 0; i < n_views; ++i) {
         atmo::RenderConsts &rc = slot->host[i];
@@ -2779,16 +2864,18 @@ int views_proxy_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, 
         proxy_cut_rect(P.rect[i], L.lod, P.gx[i], rc);
         vptc.p.proxy[i] = P.pc[i];
         if (packed) vptc.target[i] = args[i].tc;
+        if (depth_source) vdc.depth[i] = args[i].dc;
         if (first < 0) first = i;
     }
     for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) vptc.p.first_block[i] = P.first_block[i];
     ATMO_TRY(tex_order(ctx, s));  // texture updated on another stream
     HIP_TRY(ctx, hipMemcpyAsync(slot->dev, slot->host, (size_t)n_views * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
-    if (packed) HIP_TRY(ctx, atmo::launch_render_views_proxy_target(L.flags, slot->host[first].light_steps, slot->dev, vptc, s));
+    if (depth_source) HIP_TRY(ctx, atmo::launch_render_views_proxy_depth_target(L.flags, slot->host[first].light_steps, slot->dev, vptc, vdc, s));
+    else if (packed) HIP_TRY(ctx, atmo::launch_render_views_proxy_target(L.flags, slot->host[first].light_steps, slot->dev, vptc, s));
     else HIP_TRY(ctx, atmo::launch_render_views_proxy(L.flags, slot->host[first].light_steps, slot->dev, vptc.p, s));
     ATMO_TRY(views_ring_slot_used(ctx, slot, s));
     hipEvent_t marker = nullptr;
-    return finish_draw(ctx, s, L.flags | atmo::KF_VIEWS | atmo::KF_PROXY | (packed ? atmo::KF_TARGET : 0), 1, false, &marker);
+    return finish_draw(ctx, s, L.flags | atmo::KF_VIEWS | atmo::KF_PROXY | (packed ? atmo::KF_TARGET : 0) | (depth_source ? atmo::KF_DEPTH : 0), 1, false, &marker);
 }
 }  // namespace
 
@@ -2858,6 +2945,58 @@ int atmo_render_views_proxy_target(AtmoContext *ctx, const AtmoViewTarget *views
     ViewsProxyLayout P;
     ATMO_TRY(views_proxy_layout(ctx, who, args, n_views, model_matrix, box_size, L, P));
     return views_proxy_enqueue(ctx, who, args, n_views, composite, packed, L, P, stream);
+}
+
+// include/atmo_depth.h: the two target batches with a depth source per view.  The views as AtmoViewTarget (views_target_outputs: the same checks in the
+// same order, the depth's where depth_dev's null check stands); every target format draws with the KF_DEPTH kernels, so `packed` is set for RGBA32F too and
+// the float target's pitch in pixels is not used.
+namespace {
+struct DepthViews {
+    AtmoViewTarget v[ATMO_MAX_VIEWS];
+    const AtmoDepth *depth[ATMO_MAX_VIEWS];
+    DepthViews(const AtmoViewDepthTarget *views, int n_views) {
+        for (int i = 0; i < ATMO_MAX_VIEWS; ++i) {
+            depth[i] = nullptr;
+            if (!views || i >= n_views) continue;
+            v[i].frame = views[i].frame;
+            v[i].depth_dev = nullptr;
+            v[i].target = views[i].target;
+            depth[i] = &views[i].depth;
+        }
+    }
+};
+}  // namespace
+
+int atmo_render_views_depth_target(AtmoContext *ctx, const AtmoViewDepthTarget *views, int n_views, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_views_depth_target";
+    ViewsLayout L;
+    ViewArg args[ATMO_MAX_VIEWS];
+    const DepthViews dv(views, n_views);
+    bool done = false, packed = false;
+    ATMO_TRY(views_target_outputs(ctx, who, views ? dv.v : nullptr, n_views, composite, args, L, &done, &packed, dv.depth));
+    if (done) return ATMO_OK;
+    for (ViewArg &a : args) a.pitch_px = 0;
+    ATMO_TRY(views_family_grid(ctx, who, args, n_views, true, L));
+    L.family |= atmo::KF_DEPTH;
+    return views_enqueue(ctx, who, args, n_views, composite, true, L, stream, true);
+}
+
+int atmo_render_views_proxy_depth_target(AtmoContext *ctx, const AtmoViewDepthTarget *views, int n_views, const float *model_matrix, float box_size,
+                                         int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_views_proxy_depth_target";
+    ViewsLayout L;
+    ViewArg args[ATMO_MAX_VIEWS];
+    const DepthViews dv(views, n_views);
+    bool done = false, packed = false;
+    ATMO_TRY(views_target_outputs(ctx, who, views ? dv.v : nullptr, n_views, composite, args, L, &done, &packed, dv.depth));
+    ATMO_TRY(views_proxy_checks(ctx, who, model_matrix, box_size));
+    if (done) return ATMO_OK;
+    for (ViewArg &a : args) a.pitch_px = 0;
+    ViewsProxyLayout P;
+    ATMO_TRY(views_proxy_layout(ctx, who, args, n_views, model_matrix, box_size, L, P));
+    return views_proxy_enqueue(ctx, who, args, n_views, composite, true, L, P, stream, true);
 }
 
 // atmo_debug.h: the launch of a proxy batch as the host computes it; host-only contexts work, the pointers are not looked at

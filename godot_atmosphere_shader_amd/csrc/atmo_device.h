@@ -133,7 +133,11 @@ enum KernelFlags : int { KF_CLOUDS = 1, KF_CLOUD_LIGHT_RM = 2, KF_LIGHT_DIRECT =
                           KF_VIEWS = 2048 /* several views in one launch (atmo_render_views, include/atmo_views.h): the block index runs over the concatenation of all
                                              views' tiles and shade_pixel reads the view's RenderConsts from a device table (ViewsConsts); a kernel of its own
                                              (atmo_render_views_kernel), for the same reason; with KF_TARGET: the same into packed colour targets, one
-                                             TargetConsts per view (atmo_render_views_target_kernel, include/atmo_views_target.h) */ };
+                                             TargetConsts per view (atmo_render_views_target_kernel, include/atmo_views_target.h) */,
+                          KF_DEPTH = 4096 /* the depth buffer in its own format and row pitch (atmo_render_depth_target, include/atmo_depth.h): shade_pixel's depth read
+                                             goes through load_depth on DepthConsts instead of RenderConsts::depth, and its stores take all seven target formats;
+                                             always with KF_TARGET, kernels of their own (atmo_render[_proxy|_views|_views_proxy]_depth_target_kernel), for the
+                                             same reason */ };
 
 // The far-mode draw's proxy (planet_atmosphere.gd:300-321: a BoxMesh of edge box_size centred on the node, rasterised with back-face culling, near / far
 // clipping and Godot 4.3's reverse-Z GREATER_OR_EQUAL depth test).  Pixel (nx, ny) of the existing prologue's NDC: its segment from the near plane (z = 1) to
@@ -158,6 +162,16 @@ struct TargetConsts {
     int32_t pitch_bytes;   // bytes from one row to the next
     int32_t format;        // a packed format (RGBA32F targets are drawn by the float kernels: a pitch in whole pixels is all they need);
                            // uniform, read only where a pixel is addressed and stored
+};
+
+// A depth source (include/atmo_depth.h): where and how the kernels of the KF_DEPTH family read the depth sample.  A kernel argument of its own, behind every
+// older one.  RenderConsts::depth is null in these draws and not read.
+enum DepthFormat : int { DF_D32_SFLOAT = 0, DF_D16_UNORM = 1, DF_X8_D24_UNORM = 2 };   // == AtmoDepthFormat
+inline int depth_texel_bytes(int format) { return format == DF_D16_UNORM ? 2 : (format == DF_D32_SFLOAT || format == DF_X8_D24_UNORM) ? 4 : 0; }
+struct DepthConsts {
+    const void *texels;    // the viewport's first texel
+    int32_t pitch_bytes;   // bytes from one row to the next
+    int32_t format;        // uniform, read only where the sample is loaded and decoded
 };
 
 // Several views in one launch (include/atmo_views.h).  The per-view RenderConsts live in a device table (the kernel's first argument: a const __restrict__
@@ -189,6 +203,12 @@ struct ViewsProxyTargetConsts {
     TargetConsts target[MAX_VIEWS];        // as ViewsTargetConsts::target
 };
 
+// ... and where every view of a depth-source batch reads its depth (atmo_render_views[_proxy]_depth_target): the eight DepthConsts by value in the
+// kernel-argument segment, a kernel argument of its own behind ViewsTargetConsts / ViewsProxyTargetConsts, indexed by the wave-uniform view number
+struct ViewsDepthConsts {
+    DepthConsts depth[MAX_VIEWS];          // entries of views without a tile and behind n_views are zero: no tile maps to them
+};
+
 hipError_t launch_render(int flags, int split, const RenderConsts &rc, hipStream_t stream, int tile_list_blocks = 0);  // > 0: rc.tile_order lists that many tiles of the rect's grid
 // Every launcher below draws the DEFAULT-FORM families (what a default context selects: one lane per ray, the precise cloud and v1 forms, up to 32 view
 // steps) and no other.  The list stands once, ATMO_DEFAULT_FAMILIES in atmo_kernels.hip: default_family_supported and launch_default_family are made from it.
@@ -215,6 +235,18 @@ hipError_t launch_render_views_proxy_target(int flags, int light_steps, const Re
 bool target_family_supported(int flags, int split);
 hipError_t launch_render_target(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, hipStream_t stream, int tile_list_blocks = 0);
 hipError_t launch_render_proxy_target(int flags, const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, hipStream_t stream);
+// the depth-source draws (include/atmo_depth.h): the four packed-target launches above with the KF_DEPTH | KF_TARGET kernels, which read the depth through
+// DepthConsts and store every target format, RGBA32F included.  (flags, split) as launch_render_target's: target_family_supported says which exist.
+hipError_t launch_render_depth_target(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, const DepthConsts &dc, hipStream_t stream,
+                                      int tile_list_blocks = 0);
+hipError_t launch_render_proxy_depth_target(int flags, const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, const DepthConsts &dc,
+                                            hipStream_t stream);
+hipError_t launch_render_views_depth_target(int flags, int light_steps, const RenderConsts *table_dev, const ViewsTargetConsts &vtc,
+                                            const ViewsDepthConsts &vdc, hipStream_t stream);
+hipError_t launch_render_views_proxy_depth_target(int flags, int light_steps, const RenderConsts *table_dev, const ViewsProxyTargetConsts &vptc,
+                                                  const ViewsDepthConsts &vdc, hipStream_t stream);
+// load_depth's decode over n texels of a caller's array: out[i] = decode(texels[i]) (atmo_debug_decode_depth)
+hipError_t launch_decode_depth(int format, const void *texels, float *out, size_t n, hipStream_t stream);
 // store_target<format> over n pixels: dst[i] = encode(src[i]), or encode(blend(src[i], decode(dst[i]))) when composite (atmo_debug_store_target)
 hipError_t launch_store_target(int format, int composite, const float *src_rgba, void *dst, size_t n, hipStream_t stream);
 hipError_t launch_bake(const BakeConsts &bc, hipStream_t stream);

@@ -1941,11 +1941,36 @@ __device__ __forceinline__ float2 march_clouds_rm_queue(const RenderConsts &rc, 
     return make_float2(rec.total_light, 1.0f - rec.one_minus_alpha);
 }
 
+// ---- depth sources (include/atmo_depth.h; the contract is restated in numpy by depth_formats.py) ------------------------------------------------
+// The depth sample of the KF_DEPTH kernels.  depth_decode: one texel at p in the uniform `format` -- D32_SFLOAT: the float, its bits untouched; D16_UNORM:
+// code / 65535.0f; X8_D24_UNORM: (word & 0xFFFFFF) / 16777215.0f, bits 24-31 ignored -- each ONE correctly rounded fp32 division of an exactly converted
+// integer (Vulkan's UNORM rule), so only the top code is 1.0 and only code 0 is 0.0.  One global_load_dword / global_load_ushort per lane behind a scalar
+// branch, and NOTHING ELSE behind it: the decode is straight-line code on the loaded word (the quotient is computed for D32_SFLOAT too and not
+// selected).  With the division inside a three-way branch the single-draw cloud kernels spilled 200-300 SGPRs to VGPR lanes -- hipcc then loads 48
+// dwords of RenderConsts in front of the branch and carries them across it -- and clouds_high drew 1.85x slower (profiles/depth/README.md;
+// tools/depth_resources.py counts the spills now).  Outside every fp contract(fast) region; atmo_debug_decode_depth runs this same function on a
+// caller's array.
+__device__ __forceinline__ float depth_decode(const int format, const void *p) {
+#pragma clang fp contract(off)
+    uint32_t raw;
+    if (format == DF_D16_UNORM) raw = *(const uint16_t *)p;
+    else raw = *(const uint32_t *)p;
+    const float q = ieee_div((float)(raw & 0xffffffu), format == DF_D16_UNORM ? 65535.0f : 16777215.0f);
+    return format == DF_D32_SFLOAT ? __uint_as_float(raw) : q;
+}
+// ... of viewport pixel (px, py): rows pitch_bytes apart from the viewport's first texel
+__device__ __forceinline__ float load_depth(const DepthConsts &dc, const int px, const int py) {
+    const char *p = (const char *)dc.texels + (size_t)py * (size_t)dc.pitch_bytes + ((size_t)px << (dc.format == DF_D16_UNORM ? 1 : 2));
+    return depth_decode(dc.format, p);
+}
+
 // The proxy fragment test of the far-mode draw (KF_PROXY; ProxyConsts states the geometry): true = pixel (px, py) is a fragment of the BoxMesh's
 // front face -- its near-to-far segment starts outside the closed box and enters it -- and that fragment passes the depth test.  The test is Godot 4.3's
 // for a spatial material with depth_draw_opaque and no depth_test_disabled under its reverse-Z forward renderers: GREATER_OR_EQUAL against the depth
 // buffer (engine behaviour, not in the reference tree).  Each face's half-space c0 + z c1 <= 0 bounds the segment's depth interval from one side.
-__device__ __forceinline__ bool proxy_fragment_passes(const ProxyConsts &pc, const RenderConsts &rc, const int px, const int py) {
+template <bool DEPTH = false>   // DEPTH: the depth buffer is *dc (KF_DEPTH) instead of rc.depth
+__device__ __forceinline__ bool proxy_fragment_passes(const ProxyConsts &pc, const RenderConsts &rc, const int px, const int py,
+                                                      const DepthConsts *dc = nullptr) {
     const float nx = pixel_coord<true>((float)px + 0.5f, rc.vw, rc.rcp_vw) * 2.0f - 1.0f;   // the prologue's NDC (the same bits as its pixel_coord)
     const float ny = pixel_coord<true>((float)py + 0.5f, rc.vh, rc.rcp_vh) * 2.0f - 1.0f;
     float a[4];
@@ -1964,7 +1989,8 @@ __device__ __forceinline__ bool proxy_fragment_passes(const ProxyConsts &pc, con
     }
     // covered: the segment meets the box (a non-empty interval) and its near end z = 1 is not inside it; the fragment's depth is the entry's, z_hi
     if (empty || z_lo > z_hi || !(z_hi < 1.0f)) return false;
-    return z_hi >= rc.depth[(size_t)py * rc.w + px];
+    if constexpr (DEPTH) return z_hi >= load_depth(*dc, px, py);
+    else return z_hi >= rc.depth[(size_t)py * rc.w + px];
 }
 
 // ---- packed colour targets (include/atmo_target.h; the numerical contract is stated there and restated in numpy by targets.py) ----------------
@@ -2095,10 +2121,21 @@ __device__ __forceinline__ void store_target_zero_rt(const int format, void *p) 
     if (format == TF_RGBA16F) *(uint2 *)p = make_uint2(0u, 0u);
     else *(uint32_t *)p = 0u;
 }
+// ... and the same two for the KF_DEPTH kernels, which store all seven formats: RGBA32F (16 bytes a pixel; store_target<TF_RGBA32F> is the float
+// epilogue's blend and a plain float4 store) beside the six packed ones.  A dispatch of their own: the older kernels inline store_target_rt as it stands.
+__device__ __forceinline__ int target_pixel_shift_all(const int format) { return format == TF_RGBA32F ? 4 : (format == TF_RGBA16F ? 3 : 2); }
+__device__ __forceinline__ void store_target_all_rt(const int format, void *p, const float4 &src, const bool composite) {
+    if (format == TF_RGBA32F) store_target<TF_RGBA32F>(p, src, composite);
+    else store_target_rt(format, p, src, composite);
+}
+__device__ __forceinline__ void store_target_zero_all_rt(const int format, void *p) {
+    if (format == TF_RGBA32F) *(float4 *)p = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    else store_target_zero_rt(format, p);
+}
 
 template <int FLAGS, int LSTEPS, int SPLIT>
 __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int tile_x, const int tile_y, const ProxyConsts *pc = nullptr,
-                                            const TargetConsts *tc = nullptr) {
+                                            const TargetConsts *tc = nullptr, const DepthConsts *dc = nullptr) {
     constexpr bool CLOUDS = (FLAGS & KF_CLOUDS) != 0;
     constexpr bool RM = (FLAGS & KF_CLOUD_LIGHT_RM) != 0;
     constexpr bool DIRECT = (FLAGS & KF_LIGHT_DIRECT) != 0;
@@ -2109,6 +2146,8 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     constexpr bool VIEWPOS = (FLAGS & KF_VIEW_POS) != 0;
     constexpr bool PROXY = (FLAGS & KF_PROXY) != 0;
     constexpr bool TARGET = (FLAGS & KF_TARGET) != 0;
+    constexpr bool DEPTH = (FLAGS & KF_DEPTH) != 0;   // the depth sample through load_depth(*dc), the stores in all seven target formats
+    static_assert(!DEPTH || TARGET, "depth sources: the target kernels' forms");
     static_assert(!TARGET || (!VIEWPOS && !ATMO_REF && (SPLIT == 1 || (FLAGS & KF_CUBE_LOD) != 0)),
                   "packed targets: the default forms; two lanes per ray only as the heavy-tile form of the declared-sampler cloud kernels");
     static_assert(!VIEWPOS || (!LITE && !ATMO_REF && SPLIT == 1), "KF_VIEW_POS: the fast v2 march, one lane per ray");
@@ -2159,7 +2198,7 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
         // discard store included).  Without the declared sampler a failing lane simply leaves.  With it, a failing pixel becomes a HELPER, like a pixel
         // outside the rect: it marches for its quad mates and stores nothing -- a partner's picture depends on that pixel's ray alone, so a passing pixel
         // is bit-identical to atmo_render's -- and a quad with no passing pixel leaves whole.
-        const bool pass = proxy_fragment_passes(*pc, rc, px, py);
+        const bool pass = proxy_fragment_passes<DEPTH>(*pc, rc, px, py, dc);
         if constexpr (LOD) {
             const unsigned long long drawn = __builtin_amdgcn_ballot_w64(pass && !helper);
             if (((drawn >> (lane & ~3)) & 0xFull) == 0) return;
@@ -2170,7 +2209,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     }
     float4 *out = nullptr;
     char *tout = nullptr;   // KF_TARGET: the pixel's bytes in the packed target (8 per pixel RGBA16F, 4 RGBA8), rows pitch_bytes apart
-    if constexpr (TARGET)
+    if constexpr (DEPTH)
+        tout = (char *)tc->pixels + (size_t)(py - rc.out_y0) * (size_t)tc->pitch_bytes + ((size_t)(px - rc.out_x0) << target_pixel_shift_all(tc->format));
+    else if constexpr (TARGET)
         tout = (char *)tc->pixels + (size_t)(py - rc.out_y0) * (size_t)tc->pitch_bytes + ((size_t)(px - rc.out_x0) << (tc->format == TF_RGBA16F ? 3 : 2));
     else
         out = rc.out + (size_t)(py - rc.out_y0) * (size_t)rc.out_pitch + (px - rc.out_x0);
@@ -2195,7 +2236,8 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
         const float vv = ax * ax + ay * ay + az * az;
         if (cv * cv < rc.miss_k * vv) {
             if (rc.store_discards && half == 0 && !helper) {
-                if constexpr (TARGET) store_target_zero_rt(tc->format, tout);
+                if constexpr (DEPTH) store_target_zero_all_rt(tc->format, tout);
+                else if constexpr (TARGET) store_target_zero_rt(tc->format, tout);
                 else *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
             return;
@@ -2203,7 +2245,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     }
 
     // --- exact prologue (main:128-169) -----------------------------------------------------------
-    const float nonlinear_depth = rc.depth[(size_t)py * rc.w + px];
+    float nonlinear_depth;
+    if constexpr (DEPTH) nonlinear_depth = load_depth(*dc, px, py);
+    else nonlinear_depth = rc.depth[(size_t)py * rc.w + px];
     const float uvx = pixel_coord<DIET>((float)px + 0.5f, rc.vw, rc.rcp_vw);
     const float uvy = pixel_coord<DIET>((float)py + 0.5f, rc.vh, rc.rcp_vh);
     const float nx = uvx * 2.0f - 1.0f, ny = uvy * 2.0f - 1.0f, nz = nonlinear_depth;
@@ -2233,7 +2277,8 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
 
     if (rs_atmo.x == rs_atmo.y) {  // discard: nothing reaches the blend stage
         if (rc.store_discards && half == 0 && !helper) {
-            if constexpr (TARGET) store_target_zero_rt(tc->format, tout);
+            if constexpr (DEPTH) store_target_zero_all_rt(tc->format, tout);
+            else if constexpr (TARGET) store_target_zero_rt(tc->format, tout);
             else *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
         return;
@@ -2312,7 +2357,10 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
         // the same fp32 ALBEDO / ALPHA, encoded (and blended) per the target's format; not by the second lane of a split ray nor by a helper, as below.
         // The exchange registers stay reserved across it: the decode / encode arithmetic needs temporaries, and no instruction outside the exchange
         // blocks may write those registers anywhere in a declared-sampler kernel (tools/check_quad_regs.py)
-        if (!(SPLIT == 2 && half) && !helper) store_target_rt(tc->format, tout, rgba, rc.composite != 0);
+        if (!(SPLIT == 2 && half) && !helper) {
+            if constexpr (DEPTH) store_target_all_rt(tc->format, tout, rgba, rc.composite != 0);
+            else store_target_rt(tc->format, tout, rgba, rc.composite != 0);
+        }
         if constexpr (LOD) quad_regs_keep(qregs);
         return;
     }
@@ -3397,9 +3445,15 @@ hipError_t launch_store_target(int format, int composite, const float *src_rgba,
 
 const char *render_kernel_name(int flags, int light_steps, int split) {
     // demangled template name as rocprofv3 prints it: atmo_render_kernel<FLAGS, LSTEPS, SPLIT>; atmo_render_proxy_kernel<FLAGS, LSTEPS> for KF_PROXY
-    static thread_local char name[64];
+    static thread_local char name[80];
     const bool v2_precise = (flags & KF_ATMO_REF) != 0;  // its light march is a run-time loop
     const int lsteps = ((flags & KF_LIGHT_DIRECT) && light_steps == 8 && !v2_precise && !(flags & KF_VIEW_POS)) ? 8 : 0;
+    if (flags & KF_DEPTH) {   // atmo_render[_views][_proxy]_depth_target_kernel<FLAGS, LSTEPS[, SPLIT]>
+        const char *views = (flags & KF_VIEWS) ? "_views" : "", *proxy = (flags & KF_PROXY) ? "_proxy" : "";
+        if (flags & (KF_VIEWS | KF_PROXY)) snprintf(name, sizeof(name), "atmo_render%s%s_depth_target_kernel<%d, %d>", views, proxy, flags, lsteps);
+        else snprintf(name, sizeof(name), "atmo_render_depth_target_kernel<%d, %d, %d>", flags, lsteps, split == 2 ? 2 : 1);
+        return name;
+    }
     if ((flags & KF_VIEWS) && (flags & KF_PROXY)) {
         snprintf(name, sizeof(name), "atmo_render_views_proxy%s_kernel<%d, %d>", (flags & KF_TARGET) ? "_target" : "", flags, lsteps);
         return name;
@@ -3436,6 +3490,152 @@ hipError_t launch_lut_footprints(const float *apron, int w, int h, float *out4, 
 hipError_t launch_bake(const BakeConsts &bc, hipStream_t stream) {
     dim3 grid((bc.w + 15) / 16, (bc.h + 15) / 16);
     hipLaunchKernelGGL(atmo_bake_kernel, grid, dim3(256), 0, stream, bc);
+    return hipGetLastError();
+}
+
+// ---- depth sources (KF_DEPTH; include/atmo_depth.h) -----------------------------------------------------------------------------------------
+// The four packed-target kernels once more, with the depth buffer in its own format and row pitch: the same bodies with a DepthConsts behind every older
+// argument (the batches: eight of them by value in the kernel-argument segment, indexed by the wave-uniform view number -- scalar loads, as
+// ViewsTargetConsts::target), which shade_pixel's depth read goes through (load_depth), and with stores in all seven target formats (a host with a D24
+// buffer and a float4 colour buffer has no other call).  Kernels of their own names (no older kernel's name is a substring of them, nor the reverse),
+// defined and instantiated behind everything else, so that every older kernel keeps its code and its place in the code object.
+#undef ATMO_SHADE_EXTRA
+#define ATMO_SHADE_EXTRA , nullptr, &tc, &dc
+#ifndef ATMO_LOOP_PAD_DEPTH         // s_nop at the head of the twins <KF_DEPTH | KF_TARGET | KF_LIGHT_DIRECT [| KF_GEO], 8, 1> ...
+#define ATMO_LOOP_PAD_DEPTH 2
+#endif
+#ifndef ATMO_LOOP_PAD_DEPTH_GEO     // ... and more of them in the geometric-order twin, on top of ATMO_LOOP_PAD_GEO
+#define ATMO_LOOP_PAD_DEPTH_GEO 2
+#endif
+#ifndef ATMO_LOOP_PAD_DEPTH_VIEWS   // ... and at the head of <KF_DEPTH | KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8>
+#define ATMO_LOOP_PAD_DEPTH_VIEWS 0   // (0: this twin's loop lands on 12 mod 32 by itself; the knob stands for the next change in front of it)
+#endif
+template <int FLAGS, int LSTEPS, int SPLIT = 1>
+__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_depth_target_kernel(const RenderConsts rc, const TargetConsts tc,
+                                                                                                      const DepthConsts dc) {
+    static_assert((FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0, "depth-source kernels carry KF_DEPTH | KF_TARGET");
+    // the headline kernel's twins: their view loop 12 bytes into a 32-byte block, as every twin's before them (march_atmosphere; tools/loop_phase.py reads
+    // them, tests/test_depth_host.py holds them there)
+    if constexpr ((FLAGS & ~KF_GEO) == (KF_DEPTH | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8 && SPLIT == 1)
+        asm volatile(".rept " ATMO_GEO_STR(ATMO_LOOP_PAD_DEPTH) "\n\ts_nop 0\n\t.endr");
+    if constexpr (FLAGS == (KF_DEPTH | KF_TARGET | KF_LIGHT_DIRECT | KF_GEO) && LSTEPS == 8 && SPLIT == 1)
+        asm volatile(".rept " ATMO_GEO_STR(ATMO_LOOP_PAD_DEPTH_GEO) "\n\ts_nop 0\n\t.endr");
+    ATMO_RENDER_KERNEL_BODY
+}
+#undef ATMO_SHADE_EXTRA
+#define ATMO_SHADE_EXTRA
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_proxy_depth_target_kernel(const RenderConsts rc, const ProxyConsts pc,
+                                                                                                            const TargetConsts tc, const DepthConsts dc) {
+    static_assert((FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0, "KF_DEPTH | KF_PROXY | KF_TARGET");
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, &pc, &tc, &dc);
+}
+// (the body of atmo_render_views_target_kernel)
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_depth_target_kernel(const RenderConsts *__restrict__ table,
+                                                                                                               const ViewsTargetConsts vtc,
+                                                                                                               const ViewsDepthConsts vdc) {
+    static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0, "KF_DEPTH | KF_VIEWS | KF_TARGET");
+    if constexpr (FLAGS == (KF_DEPTH | KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8)
+        asm volatile(".rept " ATMO_GEO_STR(ATMO_LOOP_PAD_DEPTH_VIEWS) "\n\ts_nop 0\n\t.endr");
+    uint32_t tile = blockIdx.x;
+    if (vtc.v.order != nullptr) tile = vtc.v.order[tile];
+    uint32_t view = 0;   // as atmo_render_views_kernel: the last view whose first block is <= tile
+#pragma unroll
+    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vtc.v.first_block[i] ? 1u : 0u;
+    view = __builtin_amdgcn_readfirstlane(view);
+    const RenderConsts &rc = table[view];
+    const uint32_t local = tile - vtc.v.first_block[view];
+    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
+    uint64_t t0 = 0;
+    if (vtc.v.cost != nullptr) t0 = __builtin_amdgcn_s_memtime();
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, nullptr, &vtc.target[view], &vdc.depth[view]);
+    if (vtc.v.cost != nullptr && (threadIdx.x & 63) == 0) {
+        const uint64_t dt = __builtin_amdgcn_s_memtime() - t0;
+        atomicMax(&vtc.v.cost[tile], (uint32_t)(dt > 0xffffffffull ? 0xffffffffull : dt));
+    }
+}
+// (the body of atmo_render_views_proxy_target_kernel; unpadded, as every proxy kernel)
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_proxy_depth_target_kernel(
+    const RenderConsts *__restrict__ table, const ViewsProxyTargetConsts vptc, const ViewsDepthConsts vdc) {
+    static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0,
+                  "KF_DEPTH | KF_VIEWS | KF_PROXY | KF_TARGET");
+    const uint32_t tile = blockIdx.x;
+    uint32_t view = 0;
+#pragma unroll
+    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vptc.p.first_block[i] ? 1u : 0u;
+    view = __builtin_amdgcn_readfirstlane(view);
+    const RenderConsts &rc = table[view];
+    const uint32_t local = tile - vptc.p.first_block[view];
+    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, &vptc.p.proxy[view], &vptc.target[view], &vdc.depth[view]);
+}
+
+// their launches: those of the four packed-target draws
+static bool target_format_known(int format) { return format == TF_RGBA32F || target_format_packed(format); }
+static bool depth_consts_valid(const DepthConsts &dc) { return dc.texels != nullptr && depth_texel_bytes(dc.format) != 0 && dc.pitch_bytes > 0; }
+// one target format per batch (any of the seven), and every view that owns tiles has a target and a depth source
+static bool batch_depth_targets_valid(const uint32_t *first_block, const TargetConsts *target, const DepthConsts *depth) {
+    int format = -1;
+    for (int i = 0; i < MAX_VIEWS; ++i) {
+        if (first_block[i + 1] == first_block[i]) continue;
+        const TargetConsts &t = target[i];
+        if (t.pixels == nullptr || !target_format_known(t.format) || (format >= 0 && t.format != format) || !depth_consts_valid(depth[i])) return false;
+        format = t.format;
+    }
+    return true;
+}
+template <class Kernel, class A, class B>
+static hipError_t launch_batch2(Kernel kernel, const uint32_t *first_block, const RenderConsts *table, const A &a, const B &b, hipStream_t stream) {
+    const uint32_t total = first_block[MAX_VIEWS];
+    if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, dim3(total), dim3(TILE_W * TILE_H), 0, stream, table, a, b);
+    return hipGetLastError();
+}
+hipError_t launch_render_depth_target(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, const DepthConsts &dc, hipStream_t stream,
+                                      int tile_list_blocks) {
+    if (!target_format_known(tc.format) || !depth_consts_valid(dc) || !target_family_supported(flags & ~KF_GEO, split)) return hipErrorInvalidValue;
+    return launch_default_family<true>(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        if constexpr (target_family_has_split(F)) {
+            if (split == 2) return launch_tiles(atmo_render_depth_target_kernel<F | KF_DEPTH | KF_TARGET, L, 2>, 2, rc, tile_list_blocks, stream, tc, dc);
+        }
+        return launch_tiles(atmo_render_depth_target_kernel<F | KF_DEPTH | KF_TARGET, L, 1>, 1, rc, tile_list_blocks, stream, tc, dc);
+    });
+}
+hipError_t launch_render_proxy_depth_target(int flags, const RenderConsts &rc, const ProxyConsts &pc, const TargetConsts &tc, const DepthConsts &dc,
+                                            hipStream_t stream) {
+    if (!target_format_known(tc.format) || !depth_consts_valid(dc)) return hipErrorInvalidValue;
+    return launch_default_family(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_rect(atmo_render_proxy_depth_target_kernel<F | KF_DEPTH | KF_PROXY | KF_TARGET, L>, rc, stream, pc, tc, dc);
+    });
+}
+hipError_t launch_render_views_depth_target(int flags, int light_steps, const RenderConsts *table, const ViewsTargetConsts &vtc, const ViewsDepthConsts &vdc,
+                                            hipStream_t stream) {
+    if (!batch_depth_targets_valid(vtc.v.first_block, vtc.target, vdc.depth)) return hipErrorInvalidValue;
+    return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_batch2(atmo_render_views_depth_target_kernel<F | KF_DEPTH | KF_VIEWS | KF_TARGET, L>, vtc.v.first_block, table, vtc, vdc, stream);
+    });
+}
+hipError_t launch_render_views_proxy_depth_target(int flags, int light_steps, const RenderConsts *table, const ViewsProxyTargetConsts &vptc,
+                                                  const ViewsDepthConsts &vdc, hipStream_t stream) {
+    if (!batch_depth_targets_valid(vptc.p.first_block, vptc.target, vdc.depth)) return hipErrorInvalidValue;
+    return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_batch2(atmo_render_views_proxy_depth_target_kernel<F | KF_DEPTH | KF_VIEWS | KF_PROXY | KF_TARGET, L>, vptc.p.first_block, table, vptc,
+                             vdc, stream);
+    });
+}
+
+// load_depth's decode on caller-supplied arrays (atmo_debug_decode_depth): one texel per lane, tightly packed
+__global__ __launch_bounds__(256) void atmo_decode_depth_kernel(int format, const void *texels, float *__restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = depth_decode(format, (const char *)texels + (i << (format == DF_D16_UNORM ? 1 : 2)));
+}
+hipError_t launch_decode_depth(int format, const void *texels, float *out, size_t n, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (n > ((size_t)1 << 31) || depth_texel_bytes(format) == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(atmo_decode_depth_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, format, texels, out, n);
     return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@ names, argument meaning and (silent) error behaviour:
   far mode's BoxMesh (:1-3,56-58,98-101,300-321)       `render_proxy*`, `proxy_box_size`; `draw` = the current mode's draw
   (several nodes in one frame: Godot renderer)         `draw_atmospheres(nodes, camera, depth, scene_rgba)`: back to front
   (the same, far nodes batched: include/atmo_planets.h) `draw_atmospheres_batched(...)`, `render_planets(draws)`
+  (the renderer's own depth buffer: include/atmo_depth.h) `depth_source(tensor)` in place of any draw's `depth`
 
 The fragment work runs only on the GPU: `render` raises if libatmo_hip.so or a gfx950 device is missing.
 """
@@ -204,20 +205,70 @@ def _to_native_frame(frame: dict) -> N.AtmoFrame:
     return f
 
 
-# The C entry point of one draw, by (through the far mode's box proxy?, into an N.AtmoTarget -- a packed or pitched tensor --?): (plain, composite).
-# The float entry points end (..., depth, rgba, stream), the *_target ones (..., depth, &target, composite, stream); the proxy ones take
-# (model, box_size) behind the frame.  `PlanetAtmosphere._render_one` builds the call from the row; a new entry point is a new row.
+# The C entry point of one draw, by (through the far mode's box proxy?, into an N.AtmoTarget -- a packed or pitched tensor --?, the depth a
+# `depth_source` -- an N.AtmoDepth --?): (plain, composite).
+# The float entry points end (..., depth, rgba, stream), the *_target ones (..., depth, &target, composite, stream), the *_depth_target ones the same with
+# &depth (every colour tensor is an N.AtmoTarget there: include/atmo_depth.h has no float4-only form); the proxy ones take (model, box_size) behind the
+# frame.  `PlanetAtmosphere._render_one` builds the call from the row; a new entry point is a new row.
 _SINGLE_DRAWS = {
-    (False, False): ("atmo_render", "atmo_render_composite"),
-    (False, True): ("atmo_render_target", "atmo_render_target"),
-    (True, False): ("atmo_render_proxy", "atmo_render_proxy_composite"),
-    (True, True): ("atmo_render_proxy_target", "atmo_render_proxy_target"),
+    (False, False, False): ("atmo_render", "atmo_render_composite"),
+    (False, True, False): ("atmo_render_target", "atmo_render_target"),
+    (True, False, False): ("atmo_render_proxy", "atmo_render_proxy_composite"),
+    (True, True, False): ("atmo_render_proxy_target", "atmo_render_proxy_target"),
+    (False, True, True): ("atmo_render_depth_target", "atmo_render_depth_target"),
+    (True, True, True): ("atmo_render_proxy_depth_target", "atmo_render_proxy_depth_target"),
 }
-# ... and of a view batch, by the same key: all four take (views, n, [model, box_size,] composite, stream) (`PlanetAtmosphere._enqueue_views`)
+# ... and of a view batch, by the same key: all six take (views, n, [model, box_size,] composite, stream) (`PlanetAtmosphere._enqueue_views`)
 _BATCH_DRAWS = {
-    (False, False): "atmo_render_views", (False, True): "atmo_render_views_target",
-    (True, False): "atmo_render_views_proxy", (True, True): "atmo_render_views_proxy_target",
+    (False, False, False): "atmo_render_views", (False, True, False): "atmo_render_views_target",
+    (True, False, False): "atmo_render_views_proxy", (True, True, False): "atmo_render_views_proxy_target",
+    (False, True, True): "atmo_render_views_depth_target", (True, True, True): "atmo_render_views_proxy_depth_target",
 }
+
+
+class DepthSource:
+    """A depth buffer in its own format and row pitch (include/atmo_depth.h), as `depth_source` returns it: `tensor`, `format` (the AtmoDepthFormat
+    value) and `pitch_bytes`.  Every draw method that takes `depth` takes one in its place."""
+
+    __slots__ = ("tensor", "format", "pitch_bytes")
+
+    def __init__(self, tensor, format, pitch_bytes):
+        self.tensor, self.format, self.pitch_bytes = tensor, format, pitch_bytes
+
+    @property
+    def device(self):
+        return self.tensor.device
+
+    def native(self, camera, prefix: str = "") -> N.AtmoDepth:
+        """The N.AtmoDepth of this buffer as `camera`'s viewport; ValueError where the shape is not (viewport_h, viewport_w)."""
+        if tuple(self.tensor.shape) != (camera.height, camera.width):
+            raise ValueError(prefix + "depth must have shape (viewport_h, viewport_w)")
+        return N.AtmoDepth(self.tensor.data_ptr(), self.format, self.pitch_bytes)
+
+
+def depth_source(tensor, format=None) -> DepthSource:
+    """Wraps a renderer's depth buffer for the draws of include/atmo_depth.h: a CUDA 2-D (viewport_h, viewport_w) tensor whose elements of a row are
+    contiguous and whose rows may be further apart than a row (a row pitch: a view of one half of a double-wide image, say).  The dtype says the format:
+    float32 is "d32f", int16 (or uint16) "d16", int32 "x8d24" (depth in bits 0-23 of each word, the top byte ignored; depth_formats states the decoding).
+    `format` names the format only where it must agree with the dtype; a mismatch raises ValueError."""
+    import torch
+
+    from . import depth_formats as D
+
+    fmts = {torch.float32: D.D32F, torch.int16: D.D16, torch.int32: D.X8D24}
+    if hasattr(torch, "uint16"):
+        fmts[torch.uint16] = D.D16
+    if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.dtype in fmts):
+        raise TypeError("a depth source must be a CUDA float32 (d32f), int16 / uint16 (d16) or int32 (x8d24) tensor")
+    fmt = fmts[tensor.dtype]
+    if format is not None and D.format_id(format) != fmt:
+        raise ValueError(f"format={format!r} does not agree with the tensor's dtype {tensor.dtype}, which is {D.NAMES[fmt]!r}")
+    if tensor.dim() != 2:
+        raise ValueError("a depth source must have shape (viewport_h, viewport_w)")
+    rows, cols = tensor.shape
+    if not ((cols == 1 or tensor.stride(1) == 1) and (rows == 1 or tensor.stride(0) >= cols)):
+        raise ValueError("a depth source: the texels of a row must be contiguous and the row stride at least a row (a row pitch is the only stride supported)")
+    return DepthSource(tensor, fmt, (tensor.stride(0) if rows > 1 else cols) * tensor.element_size())
 
 
 class PlanetAtmosphere:
@@ -559,7 +610,8 @@ class PlanetAtmosphere:
     def render(self, camera, depth, out=None, rect=None, stream=None, time: float = 0.0, target=None):
         """One draw: shades `rect` (default: whole viewport) of the camera's viewport.
 
-        depth: CUDA float32 tensor (H, W), Godot reversed-Z depth.  out: CUDA float32 tensor
+        depth: CUDA float32 tensor (H, W), Godot reversed-Z depth -- or a `depth_source(...)` of the renderer's own D32 / D16 / X8_D24 buffer, with a row
+        pitch if it has one (atmo_render_depth_target), here and in every other draw method.  out: CUDA float32 tensor
         (rect_h, rect_w, 4), allocated when None.  Work is enqueued on `stream` (a torch stream, a raw
         hipStream_t int, or None for torch's current stream).  Returns `out`.
         `out` may also be a float16 (RGBA16F) or uint8 (RGBA8_UNORM) tensor, and its rows may be further apart than a row (a row pitch): the draw then
@@ -573,19 +625,24 @@ class PlanetAtmosphere:
         `proxy` is None or `_proxy`'s (model, box_size): zero-filled allocations, the proxy entry points."""
         frame = self.make_frame(camera, time, rect)
         x0, y0, x1, y1 = frame["rect"]
-        _check_depth(depth, camera, split=split_depth_errors)
+        src = depth.native(camera) if isinstance(depth, DepthSource) else None   # (a plain tensor: today's path, checks and messages)
+        if src is None:
+            _check_depth(depth, camera, split=split_depth_errors)
         rows, cols = (camera.height, camera.width) if composite else (y1 - y0, x1 - x0)
         if colour is None and not composite:
             colour = _new_target(rows, cols, target, depth.device, zero=proxy is not None)
         # a contiguous float32 tensor (None), or the N.AtmoTarget of a float16 / uint8 / pitched one
         tgt = _colour_target(colour, rows, cols, "scene_rgba" if composite else "out", target)
+        if src is not None and tgt is None:   # the depth-source entry points take every colour tensor as an N.AtmoTarget
+            tgt = N.AtmoTarget(colour.data_ptr(), N.TARGET_RGBA32F, 0)
         stream = _stream_handle(stream, depth)
         self._bake_if_needed(stream)
         nf = _to_native_frame(frame)
-        fn = getattr(self._lib, _SINGLE_DRAWS[proxy is not None, tgt is not None][bool(composite)])
+        fn = getattr(self._lib, _SINGLE_DRAWS[proxy is not None, tgt is not None, src is not None][bool(composite)])
         box = () if proxy is None else (proxy[0], C.c_float(proxy[1]))
         where = (C.c_void_p(colour.data_ptr()),) if tgt is None else (C.byref(tgt), int(composite))
-        N.check(self._ctx, fn(self._ctx, C.byref(nf), *box, C.c_void_p(depth.data_ptr()), *where, C.c_void_p(stream or 0)))
+        depth_arg = C.c_void_p(depth.data_ptr()) if src is None else C.byref(src)
+        N.check(self._ctx, fn(self._ctx, C.byref(nf), *box, depth_arg, *where, C.c_void_p(stream or 0)))
         return colour
 
     def prepare_frame(self, camera, time: float = 0.0, rect=None) -> N.AtmoFrame:
@@ -626,15 +683,21 @@ class PlanetAtmosphere:
         """Enqueue one batch from `prepare_views_target` (atmo_render_views_target): one ctypes call, one launch for all views."""
         self._enqueue_views(self._lib.atmo_render_views_target, views, n_views, None, composite, stream)
 
+    def prepare_views_depth_target(self, cameras, depths, targets, rects=None, time: float = 0.0):
+        """The native argument block of the depth-source batches (atmo_render_views_depth_target, atmo_render_views_proxy_depth_target): one
+        N.AtmoViewDepthTarget per camera; depths[i] is an N.AtmoDepth, targets[i] an N.AtmoTarget."""
+        return self._prepare_views(N.AtmoViewDepthTarget, cameras, depths, targets, rects, time)
+
     def _prepare_views(self, struct, cameras, depth_ptrs, colours, rects, time):
         field, name = ("rgba_dev", "outs") if struct is N.AtmoView else ("target", "targets")
+        depth_field = "depth" if struct is N.AtmoViewDepthTarget else "depth_dev"
         n = len(cameras)
         if not (len(depth_ptrs) == n and len(colours) == n and (rects is None or len(rects) == n)):
             raise ValueError(f"cameras, depths, {name} and rects must have one entry per view")
         views = (struct * max(n, 1))()
         for i, cam in enumerate(cameras):
             views[i].frame = _to_native_frame(self.make_frame(cam, time, rects[i] if rects is not None else None))
-            views[i].depth_dev = depth_ptrs[i]
+            setattr(views[i], depth_field, depth_ptrs[i])
             setattr(views[i], field, colours[i])
         return views
 
@@ -665,8 +728,15 @@ class PlanetAtmosphere:
             raise ValueError("composite=True blends into the views' scene buffers: pass them as outs")
         outs = list(outs) if outs is not None else [None] * n
         tgts = [None] * n
+        sources = [isinstance(d, DepthSource) for d in depths]
+        if any(sources) and not all(sources):
+            raise TypeError("the depths of one batch are all tensors or all depth_source(...) objects")
+        srcs = [None] * n
         for i, (cam, depth) in enumerate(zip(cameras, depths)):
-            _check_depth(depth, cam, f"view {i}: ", split=True)
+            if sources[i]:
+                srcs[i] = depth.native(cam, f"view {i}: ")
+            else:
+                _check_depth(depth, cam, f"view {i}: ", split=True)
             x0, y0, x1, y1 = rects[i] if rects is not None and rects[i] is not None else (0, 0, cam.width, cam.height)
             rows, cols = (cam.height, cam.width) if composite else (y1 - y0, x1 - x0)
             if outs[i] is None:
@@ -676,14 +746,15 @@ class PlanetAtmosphere:
         if n == 0:
             return outs
         stream = _stream_handle(stream, depths[0])
-        depth_ptrs = [d.data_ptr() for d in depths]
-        packed = any(t is not None for t in tgts)
+        depth_ptrs = [d.data_ptr() for d in depths] if not sources[0] else srcs
+        packed = sources[0] or any(t is not None for t in tgts)   # (the depth-source batches take every colour tensor as an N.AtmoTarget)
         if packed:   # one batch, one struct: a contiguous float32 tensor among pitched ones is an RGBA32F target without a pitch
             tgts = [t if t is not None else N.AtmoTarget(o.data_ptr(), N.TARGET_RGBA32F, 0) for t, o in zip(tgts, outs)]
-            views = self.prepare_views_target(cameras, depth_ptrs, tgts, rects, time)
+            prepare = self.prepare_views_depth_target if sources[0] else self.prepare_views_target
+            views = prepare(cameras, depth_ptrs, tgts, rects, time)
         else:
             views = self.prepare_views(cameras, depth_ptrs, [o.data_ptr() for o in outs], rects, time)
-        self._enqueue_views(getattr(self._lib, _BATCH_DRAWS[proxy is not None, packed]), views, n, proxy, composite, stream)
+        self._enqueue_views(getattr(self._lib, _BATCH_DRAWS[proxy is not None, packed, sources[0]]), views, n, proxy, composite, stream)
         return outs
 
     # ---- several far-mode views in one launch (include/atmo_views_proxy.h) -----------------------------------------------------------
@@ -908,6 +979,8 @@ def prepare_planets(draws, time: float = 0.0):
         raise ValueError(f"at most {N.MAX_PLANET_DRAWS} draws per call")
     arr = (N.AtmoPlanetDraw * max(len(draws), 1))()
     for i, (node, camera, depth, scene_rgba, rect, box_size, target) in enumerate(draws):
+        if isinstance(depth, DepthSource):
+            raise TypeError(f"draw {i}: atmo_render_planets takes float depth tensors only (AtmoPlanetDraw holds a float pointer), not a depth_source")
         _check_depth(depth, camera, f"draw {i}: ")
         tgt = _colour_target(scene_rgba, camera.height, camera.width, f"draw {i}: scene_rgba", target)
         model, size = node._proxy(camera, box_size)
@@ -965,6 +1038,8 @@ def draw_atmospheres_batched(nodes, camera, depth, scene_rgba, stream=None, time
     """`draw_atmospheres` with the far nodes batched: the same order (`draw_order`), the same bytes, but every maximal run of far-mode nodes in that
     order goes through ONE `render_planets` call -- planets that do not overlap on screen share a launch -- and a near-mode node, whose fullscreen
     draw touches everything, is its own `node.draw` between the runs.  Returns `scene_rgba`."""
+    if isinstance(depth, DepthSource):
+        raise TypeError("draw_atmospheres_batched takes a float depth tensor only (atmo_render_planets), not a depth_source: use draw_atmospheres")
     kw = {} if target is None else {"target": target}
     run = []
 

@@ -133,6 +133,12 @@ int atmo_debug_views_proxy_layout(AtmoContext *ctx, const struct AtmoView *views
  * pixels of `format` (AtmoTargetFormat; RGBA32F included).  Enqueues one kernel on `stream`. */
 int atmo_debug_store_target(AtmoContext *ctx, int format, int composite, const float *src_rgba_f32_dev, void *dst_dev, size_t n_pixels, void *stream);
 
+/* Diagnostics (no reference counterpart): the render kernels' depth decode (include/atmo_depth.h: the device function their depth read goes through) on a
+ * caller-supplied DEVICE array, so that the contract can be tested on every code rather than on what a scene happens to hold: out_dev[i] =
+ * decode(texels_dev[i]) for n tightly packed texels of `format` (AtmoDepthFormat; texels aligned to the texel size, n <= 2^31).  Takes no context (it runs
+ * on the current device).  Enqueues one kernel on `stream`.  ATMO_E_ARG: unknown format, null or misaligned pointer, n too large. */
+int atmo_debug_decode_depth(int format, const void *texels_dev, float *out_dev, size_t n, void *stream);
+
 /* Diagnostics (no reference counterpart): the library's tile-order sort (launch_tile_order, exactly the call the feedback path makes) on the caller's costs.
  * All pointers are HOST memory.  cost: tiles_x * tiles_y values, row-major (n = their product, at most 2^22).  rx, ry: dilation radii in tiles (0 .. 64).
  * order_out: n entries.  order2_out (may be NULL): 2 n.  class_totals_out (may be NULL): *n_classes_out entries.

@@ -1,0 +1,330 @@
+"""CPU tests of the depth sources (include/atmo_depth.h): the numerical contract as godot_atmosphere_shader_amd/depth_formats.py states it, the header's
+symbol set and the binding, the capability query, the kernels the library was built with (families, resources, loop positions), and the argument checks of
+the four entry points on a host-only context.  (tests/test_depth_gpu.py holds the kernels to the statement bit for bit.)"""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from godot_atmosphere_shader_amd import depth_formats as D
+from godot_atmosphere_shader_amd import scene as S
+from godot_atmosphere_shader_amd.scene import col_major
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# include/atmo_depth.h: (format, code, the decoded fp32 bits)
+ANCHORS = [("d16", 1, 0x37800080), ("d16", 32768, 0x3F000080), ("d16", 65534, 0x3F7FFF00), ("d16", 65535, 0x3F800000),
+           ("x8d24", 1, 0x33800001), ("x8d24", 8388608, 0x3F000001), ("x8d24", 16777214, 0x3F7FFFFF), ("x8d24", 16777215, 0x3F800000)]
+
+
+# ---- the statement -----------------------------------------------------------------------------------------------------------------------------
+
+def test_decode_gives_the_headers_anchors():
+    for fmt, code, bits in ANCHORS:
+        got = D.decode(np.array([code], dtype=D.DTYPES[D.format_id(fmt)]), fmt)
+        assert got.dtype == np.float32 and int(got.view(np.uint32)[0]) == bits, (fmt, code, hex(int(got.view(np.uint32)[0])))
+    assert (D.D32F, D.D16, D.X8D24) == (0, 1, 2) and D.FORMATS == {"d32f": 0, "d16": 1, "x8d24": 2}
+    assert D.TEXEL_BYTES == {0: 4, 1: 2, 2: 4}
+    assert [np.dtype(D.DTYPES[f]).itemsize for f in (0, 1, 2)] == [4, 2, 4]
+    with pytest.raises(ValueError):
+        D.decode(np.zeros(4, dtype=np.uint16), "d24")
+    with pytest.raises(ValueError):
+        D.decode(np.zeros(4, dtype=np.uint8), "d16")
+
+
+def test_decode_is_the_float64_quotient_rounded_once():
+    """All 2^16 D16 codes; 2^20 random 24-bit codes with random top bytes, and the 2^12 codes at either end."""
+    codes = np.arange(65536, dtype=np.uint16)
+    got = D.decode(codes, "d16")
+    assert np.array_equal(got.view(np.uint32), (codes.astype(np.float64) / 65535.0).astype(np.float32).view(np.uint32))
+    assert np.array_equal(D.decode(codes.view(np.int16), "d16").view(np.uint32), got.view(np.uint32))      # an int16 carrier: the same bits
+    assert (got == 1.0).sum() == 1 and got[65535] == 1.0 and (got == 0.0).sum() == 1 and got[0] == 0.0 and np.all(np.diff(got) > 0)
+    rng = np.random.default_rng(24)
+    c24 = np.concatenate([rng.integers(0, 1 << 24, size=1 << 20, dtype=np.uint32), np.arange(4096, dtype=np.uint32),
+                          np.arange((1 << 24) - 4096, 1 << 24, dtype=np.uint32)])
+    words = c24 | (rng.integers(0, 256, size=c24.size, dtype=np.uint32) << 24)
+    assert (words >> 24).any()
+    got = D.decode(words, "x8d24")
+    assert np.array_equal(got.view(np.uint32), (c24.astype(np.float64) / 16777215.0).astype(np.float32).view(np.uint32))
+    assert np.array_equal(D.decode(words.view(np.int32), "x8d24").view(np.uint32), got.view(np.uint32))
+    assert np.all(got[c24 == 16777215] == 1.0) and np.all(got[c24 != 16777215] < 1.0) and np.all(got[c24 != 0] > 0.0)
+    # d32f: the bits themselves
+    bits = rng.integers(0, 1 << 32, size=4096, dtype=np.uint64).astype(np.uint32)
+    assert np.array_equal(D.decode(bits.view(np.float32), "d32f").view(np.uint32), bits)
+
+
+def test_quantise_then_decode_is_within_half_a_code():
+    rng = np.random.default_rng(5)
+    d = np.concatenate([rng.random(1 << 16, dtype=np.float32), np.array([0.0, 1.0, -0.25, 1.5, 0.5, 2.0 ** -30], dtype=np.float32)])
+    for fmt, top in (("d16", 65535), ("x8d24", 16777215)):
+        q = D.quantise(d, fmt)
+        assert q.dtype == D.DTYPES[D.format_id(fmt)] and int(q.max()) == top and int(q.min()) == 0
+        back = D.decode(q, fmt).astype(np.float64)
+        # half a code, plus the half-ulp of the one fp32 rounding of the quotient (values below 1: at most 2^-25)
+        assert np.all(np.abs(back - np.clip(d.astype(np.float64), 0.0, 1.0)) <= 0.5 / top + 2.0 ** -25), fmt
+    assert np.array_equal(D.quantise(d, "d32f").view(np.uint32), d.view(np.uint32))
+    assert D.quantise(np.float32(0.0), "x8d24") == 0 and D.quantise(np.float32(1.0), "x8d24") == 16777215
+
+
+# ---- the header and the binding ------------------------------------------------------------------------------------------------------------------
+
+def _functions(name):
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
+    return set(re.findall(r"\b(atmo_[a-z0-9_]+)\s*\(", header))
+
+
+def test_binding_exposes_the_depth_header():
+    from godot_atmosphere_shader_amd import _native as N
+    from godot_atmosphere_shader_amd.build import build_native
+
+    build_native()
+    lib = N.load()
+    assert _functions("atmo_depth.h") == set(N.DEPTH_SYMBOLS) == {"atmo_depth_texel_bytes", "atmo_render_depth_target", "atmo_render_proxy_depth_target",
+                                                                 "atmo_render_views_depth_target", "atmo_render_views_proxy_depth_target"}
+    for sym in N.DEPTH_SYMBOLS + ("atmo_debug_decode_depth",):
+        assert getattr(lib, sym) is not None
+    # a tuple of its own beside EXPORTED_SYMBOLS, which stays the union of the seven older headers' tuples; the feature is detected by symbol
+    assert not set(N.DEPTH_SYMBOLS) & set(N.EXPORTED_SYMBOLS)
+    assert N.EXPORTED_SYMBOLS == (N.CORE_SYMBOLS + N.DEBUG_SYMBOLS + N.SCENE_SYMBOLS + N.TARGET_SYMBOLS + N.VIEWS_SYMBOLS + N.VIEWS_PROXY_SYMBOLS +
+                                  N.VIEWS_TARGET_SYMBOLS)
+    assert "atmo_debug_decode_depth" in N.DEBUG_SYMBOLS and "atmo_debug_decode_depth" in _functions("atmo_debug.h")
+    assert len(N.CORE_SYMBOLS) == 22 and lib.atmo_abi_version() == N.ABI_VERSION == 5
+    assert [lib.atmo_depth_texel_bytes(f) for f in (N.DEPTH_D32_SFLOAT, N.DEPTH_D16_UNORM, N.DEPTH_X8_D24_UNORM)] == [4, 2, 4]
+    assert [lib.atmo_depth_texel_bytes(f) for f in (-1, 3)] == [0, 0]
+    assert (D.D32F, D.D16, D.X8D24) == (N.DEPTH_D32_SFLOAT, N.DEPTH_D16_UNORM, N.DEPTH_X8_D24_UNORM)
+    assert C.sizeof(N.AtmoDepth) == 16 and N.AtmoDepth.format.offset == 8 and N.AtmoDepth.row_pitch_bytes.offset == 12
+    assert C.sizeof(N.AtmoViewDepthTarget) == C.sizeof(N.AtmoFrame) + 4 + 32 and N.AtmoViewDepthTarget.depth.offset == C.sizeof(N.AtmoFrame) + 4
+    # the older headers do not know the new one
+    for name in ("atmo.h", "atmo_scene.h", "atmo_target.h", "atmo_views.h", "atmo_views_target.h", "atmo_views_proxy.h", "atmo_planets.h"):
+        assert "atmo_depth" not in open(os.path.join(ROOT, "include", name)).read(), name
+
+
+# ---- the kernels, read back from the library as built --------------------------------------------------------------------------------------------
+
+def _loop_phase():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import loop_phase
+    finally:
+        sys.path.pop(0)
+    return loop_phase
+
+
+def test_every_depth_kernel_exists_for_the_default_families():
+    """As tests/test_views_proxy_host.py::test_every_default_form_entry_point_has_the_same_families: each of the four depth-source kernels exists for
+    exactly the 18 (FLAGS, LSTEPS) pairs of ATMO_DEFAULT_FAMILIES under its own bits, atmo_render_depth_target_kernel with SPLIT 1 and also for the KF_GEO
+    twin of the direct-light family and the SPLIT 2 form of the two declared-sampler cloud families."""
+    from godot_atmosphere_shader_amd.build import build_native
+
+    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
+        pytest.skip("llvm-readelf of the ROCm toolchain not found")
+    loop_phase = _loop_phase()
+    import tempfile
+
+    CLOUDS, RM, DIRECT, LITE, PRECISE, LOD, GEO, PROXY, TARGET, VIEWS, DEPTH = 1, 2, 4, 8, 16, 32, 256, 512, 1024, 2048, 4096   # KernelFlags (csrc/atmo_device.h)
+    plain = [0, PRECISE | CLOUDS, PRECISE | CLOUDS | RM, LOD | PRECISE | CLOUDS, LOD | PRECISE | CLOUDS | RM, PRECISE | LITE, PRECISE | LITE | CLOUDS,
+             LOD | PRECISE | LITE | CLOUDS]
+    direct = [DIRECT, PRECISE | CLOUDS | DIRECT, PRECISE | CLOUDS | RM | DIRECT, LOD | PRECISE | CLOUDS | DIRECT, LOD | PRECISE | CLOUDS | RM | DIRECT]
+    want = {(f, 0) for f in plain + direct} | {(f, 8) for f in direct}
+    assert len(want) == 18
+    with tempfile.TemporaryDirectory(prefix="depth_families_") as tmp:
+        co = loop_phase.device_code_object(build_native(), os.path.join(tmp, "dev.co"))
+        syms = subprocess.run([f"{loop_phase.LLVM}/llvm-readelf", "-sW", co], check=True, capture_output=True, text=True).stdout
+    found, names = {}, set()
+    for line in syms.splitlines():
+        m = re.search(r"\d+(atmo_render_[a-z_]*kernel)ILi(\d+)ELi(\d+)E(?:Li(\d+)E)?E", line.split()[-1]) if " FUNC " in line else None
+        if m:
+            names.add(m.group(1))
+            found.setdefault(m.group(1), set()).add(tuple(int(g) for g in m.groups()[1:] if g is not None))
+    for kernel, bits in (("atmo_render_proxy_depth_target_kernel", PROXY), ("atmo_render_views_depth_target_kernel", VIEWS),
+                         ("atmo_render_views_proxy_depth_target_kernel", VIEWS | PROXY)):
+        got = found[kernel]
+        bits |= TARGET | DEPTH
+        assert all(f & (PROXY | TARGET | VIEWS | GEO | DEPTH) == bits for f, _ in got), (kernel, sorted(got))
+        assert {(f & ~bits, l) for f, l in got} == want, (kernel, sorted(got))
+    got = found["atmo_render_depth_target_kernel"]
+    assert all(f & (PROXY | TARGET | VIEWS | DEPTH) == TARGET | DEPTH for f, _, _ in got), sorted(got)
+    want_single = {(f, l, 1) for f, l in want} | {(DIRECT | GEO, 8, 1), (DIRECT | GEO, 0, 1)} | {(LOD | PRECISE | CLOUDS, 0, 2), (LOD | PRECISE | CLOUDS | RM, 0, 2)}
+    assert {(f & ~(TARGET | DEPTH), l, s) for f, l, s in got} == want_single, sorted(got)
+    # no kernel's name is a substring of another family's: a tool that selects kernels by name selects one family
+    new = {n for n in names if "depth" in n}
+    assert len(new) == 4
+    for n in new:
+        assert not any(o in n or n in o for o in names - {n}), n
+    # KF_DEPTH appears in these four families only
+    assert all(not (f[0] & DEPTH) for k, s in found.items() if k not in new for f in s)
+
+
+def test_depth_headline_twins_sit_at_the_fast_loop_position():
+    """As tests/test_target_host.py::test_target_headline_twins_sit_at_the_fast_loop_position: the direct-light headline twins of the depth-source family carry
+    the same view loop, and it starts 12 bytes into its 32-byte block (ATMO_LOOP_PAD_DEPTH, ATMO_LOOP_PAD_DEPTH_GEO, ATMO_LOOP_PAD_DEPTH_VIEWS)."""
+    from godot_atmosphere_shader_amd.build import build_native
+
+    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
+        pytest.skip("llvm-objdump of the ROCm toolchain not found")
+    loop_phase = _loop_phase()
+    lib = build_native()
+    for pattern, knob in (("atmo_render_depth_target_kernelILi5124ELi8ELi1E", "ATMO_LOOP_PAD_DEPTH"),
+                          ("atmo_render_depth_target_kernelILi5380ELi8ELi1E", "ATMO_LOOP_PAD_DEPTH_GEO"),
+                          ("atmo_render_views_depth_target_kernelILi7172ELi8E", "ATMO_LOOP_PAD_DEPTH_VIEWS")):
+        rows = loop_phase.view_loops(lib, pattern)
+        assert len(rows) == 1, (pattern, rows)
+        name, offset, phase, size = rows[0]
+        assert phase == loop_phase.FAST_PHASE, f"{name}: view loop {phase} bytes into its block (at +0x{offset:x}, {size} bytes): move {knob}"
+        assert size == loop_phase.view_loops(lib, "atmo_render_target_kernelILi1028ELi8ELi1E")[0][3]   # the packed-target twin's loop
+    # the older headline kernels stay where they were
+    for pattern in ("atmo_render_kernelILi4ELi8ELi1E", loop_phase.GEO_TWIN, "atmo_render_target_kernelILi1028ELi8ELi1E",
+                    "atmo_render_views_target_kernelILi3076ELi8E"):
+        rows = loop_phase.view_loops(lib, pattern)
+        assert len(rows) == 1 and rows[0][2] == loop_phase.FAST_PHASE, (pattern, rows)
+
+
+def test_depth_kernels_keep_their_constants_in_sgprs():
+    """tools/depth_resources.py: each of the 22 + 18 + 18 + 18 kernels has no stack frame, as many vector loads inside its loops as its packed-target twin
+    (the depth load sits in the prologue; no field of a DepthConsts arrives through a vector load) and a VGPR count on the twin's occupancy step or better."""
+    import shutil
+
+    if shutil.which("hipcc") is None:
+        pytest.skip("hipcc not found")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "depth_resources.py")], capture_output=True, text=True, timeout=900)
+    print(p.stdout)
+    assert p.returncode == 0, p.stdout + p.stderr
+    for family, n in (("atmo_render_depth_target_kernel<", 22), ("atmo_render_proxy_depth_target_kernel<", 18),
+                      ("atmo_render_views_depth_target_kernel<", 18), ("atmo_render_views_proxy_depth_target_kernel<", 18)):
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith(family)]
+        assert len(lines) == n and all(ln.endswith("ScratchSize 0: ok") for ln in lines), family
+        for ln in lines:
+            m = re.search(r"in loops (\d+) vector loads \(twin (\d+)\)", ln)
+            assert m and m.group(1) == m.group(2), ln
+
+
+# ---- argument checks through the C ABI, without a device -------------------------------------------------------------------------------------------
+
+def _frame(cam, rect=None):
+    from godot_atmosphere_shader_amd import _native as N
+
+    f = N.AtmoFrame()
+    f.inv_projection_matrix[:] = [float(x) for x in col_major(cam.inv_projection)]
+    f.inv_view_matrix[:] = [float(x) for x in col_major(cam.inv_view)]
+    f.viewport_w, f.viewport_h = cam.width, cam.height
+    f.x0, f.y0, f.x1, f.y1 = rect if rect is not None else (0, 0, cam.width, cam.height)
+    return f
+
+
+def _host_ctx(variant, light_mode, light_steps):
+    from godot_atmosphere_shader_amd import _native as N
+
+    ctx = C.c_void_p()
+    assert N.load().atmo_debug_create_host_only(variant, 0, 0, light_mode, light_steps, C.byref(ctx)) == N.ATMO_OK
+    return ctx
+
+
+def test_depth_entry_points_check_their_arguments_without_a_device():
+    """Null depth, null texels, format 3, D16 texels at an odd address, a pitch below the viewport's row or not a multiple of the texel: ATMO_E_ARG from
+    all four calls (the batches name the view), before anything touches a device.  A well-formed call on a host-only context fails too -- but not with
+    ATMO_E_ARG.  The target's own refusals come first, as in atmo_render_target."""
+    from godot_atmosphere_shader_amd import _native as N
+
+    lib = N.load()
+    ctx = _host_ctx(N.VARIANT_NO_CLOUDS, N.LIGHT_DIRECT, 8)
+    try:
+        cam = S.Camera(64, 36, (0.0, 0.0, 600.0), (0.0, 0.0, 0.0))
+        f = _frame(cam)
+        sub = _frame(cam, (8, 4, 40, 30))
+        m = (C.c_float * 16)(*[float(x) for x in col_major(np.eye(4))])
+        good_t = N.AtmoTarget(8192, N.TARGET_RGBA16F, 0)
+
+        def all_four(frame, depth, target=good_t, composite=0):
+            """The four return codes and messages; the batches carry the view under test as view 1 behind a well-formed view 0."""
+            d = C.byref(depth) if depth is not None else None
+            out = [(lib.atmo_render_depth_target(ctx, C.byref(frame), d, C.byref(target), composite, None), lib.atmo_last_error_string(ctx)),
+                   (lib.atmo_render_proxy_depth_target(ctx, C.byref(frame), m, C.c_float(10.0), d, C.byref(target), composite, None),
+                    lib.atmo_last_error_string(ctx))]
+            if depth is not None:   # (a view's depth is a member: it cannot be null)
+                views = (N.AtmoViewDepthTarget * 2)()
+                views[0].frame, views[0].depth, views[0].target = frame, N.AtmoDepth(4096, N.DEPTH_D32_SFLOAT, 0), N.AtmoTarget(1 << 20, target.format, 0)
+                views[1].frame, views[1].depth, views[1].target = frame, depth, N.AtmoTarget(2 << 20, target.format, target.row_pitch_bytes)
+                out.append((lib.atmo_render_views_depth_target(ctx, views, 2, composite, None), lib.atmo_last_error_string(ctx)))
+                out.append((lib.atmo_render_views_proxy_depth_target(ctx, views, 2, m, C.c_float(10.0), composite, None), lib.atmo_last_error_string(ctx)))
+            return out
+
+        def refused(frame, depth, word, **kw):
+            res = all_four(frame, depth, **kw)
+            assert [rc for rc, _ in res] == [N.ATMO_E_ARG] * len(res), res
+            assert all(word in msg for _, msg in res), res
+            assert all(b"view 1" in msg for _, msg in res[2:]), res
+            return True
+
+        def accepted(frame, depth, **kw):
+            res = all_four(frame, depth, **kw)
+            assert all(rc not in (N.ATMO_OK, N.ATMO_E_ARG) for rc, _ in res), res   # no device: never drawn, but the arguments are not blamed
+            return True
+
+        assert refused(f, None, b"null depth")
+        assert refused(f, N.AtmoDepth(None, N.DEPTH_D16_UNORM, 0), b"null depth texels")
+        assert refused(f, N.AtmoDepth(4096, 3, 0), b"unknown depth format 3")
+        assert refused(f, N.AtmoDepth(4096, -1, 0), b"unknown depth format")
+        for fmt, tb in ((N.DEPTH_D32_SFLOAT, 4), (N.DEPTH_D16_UNORM, 2), (N.DEPTH_X8_D24_UNORM, 4)):
+            assert refused(f, N.AtmoDepth(4096 + tb // 2, fmt, 0), b"aligned")                      # D16 at an odd address, D32 / X8_D24 at 2 mod 4
+            assert accepted(f, N.AtmoDepth(4096 + tb, fmt, 0))
+            assert refused(f, N.AtmoDepth(4096, fmt, 64 * tb - tb), b"row_pitch_bytes")             # below a viewport row
+            assert refused(f, N.AtmoDepth(4096, fmt, 65 * tb + 1), b"row_pitch_bytes")              # not a multiple of the texel
+            assert refused(f, N.AtmoDepth(4096, fmt, -64 * tb), b"row_pitch_bytes")
+            assert accepted(f, N.AtmoDepth(4096, fmt, 64 * tb)) and accepted(f, N.AtmoDepth(4096, fmt, 69 * tb), composite=1)
+            # the depth is the VIEWPORT's whatever the rect: a rect's width is not enough
+            assert refused(sub, N.AtmoDepth(4096, fmt, 32 * tb), b"row_pitch_bytes") and accepted(sub, N.AtmoDepth(4096, fmt, 64 * tb))
+        # every target format is taken, RGBA32F included
+        for tf in (N.TARGET_RGBA32F, N.TARGET_RGBA16F, N.TARGET_RGBA8_UNORM, N.TARGET_RGBA8_SRGB, N.TARGET_BGRA8_UNORM, N.TARGET_BGRA8_SRGB,
+                   N.TARGET_A2B10G10R10_UNORM):
+            assert accepted(f, N.AtmoDepth(4096, N.DEPTH_X8_D24_UNORM, 0), target=N.AtmoTarget(8192, tf, 0))
+        # the target's refusals stand in front of the depth's
+        res = all_four(f, N.AtmoDepth(None, 3, 0), target=N.AtmoTarget(8192, 3, 0))
+        assert all(rc == N.ATMO_E_ARG and b"target format" in msg for rc, msg in res), res
+        # an empty rect: ATMO_OK from the single draw whatever the depth, as atmo_render_target with a null depth_dev
+        empty = _frame(cam, (5, 5, 5, 9))
+        assert lib.atmo_render_depth_target(ctx, C.byref(empty), None, C.byref(good_t), 0, None) == N.ATMO_OK
+        assert lib.atmo_render_target(ctx, C.byref(empty), None, C.byref(good_t), 0, None) == N.ATMO_OK
+        # null context, null frame, null views
+        d = N.AtmoDepth(4096, N.DEPTH_D16_UNORM, 0)
+        assert lib.atmo_render_depth_target(None, C.byref(f), C.byref(d), C.byref(good_t), 0, None) == N.ATMO_E_ARG
+        assert lib.atmo_render_depth_target(ctx, None, C.byref(d), C.byref(good_t), 0, None) == N.ATMO_E_ARG
+        assert lib.atmo_render_views_depth_target(ctx, None, 2, 0, None) == N.ATMO_E_ARG
+        assert lib.atmo_render_views_depth_target(ctx, None, 0, 0, None) == N.ATMO_OK
+        assert lib.atmo_render_views_depth_target(ctx, None, 9, 0, None) == N.ATMO_E_ARG
+        # the debug decode: format, pointers, alignment
+        assert lib.atmo_debug_decode_depth(3, C.c_void_p(4096), C.c_void_p(8192), 16, None) == N.ATMO_E_ARG
+        assert lib.atmo_debug_decode_depth(N.DEPTH_D16_UNORM, None, C.c_void_p(8192), 16, None) == N.ATMO_E_ARG
+        assert lib.atmo_debug_decode_depth(N.DEPTH_D16_UNORM, C.c_void_p(4097), C.c_void_p(8192), 16, None) == N.ATMO_E_ARG
+        assert lib.atmo_debug_decode_depth(N.DEPTH_D16_UNORM, C.c_void_p(4096), None, 16, None) == N.ATMO_E_ARG
+    finally:
+        lib.atmo_destroy(ctx)
+
+
+def test_depth_sources_need_the_default_forms_on_a_host_only_context():
+    """precision 2: ATMO_E_STATE from the single draws for every target format, RGBA32F included (these calls draw it with kernels of their own)."""
+    from godot_atmosphere_shader_amd import _native as N
+
+    lib = N.load()
+    ctx = _host_ctx(N.VARIANT_NO_CLOUDS, N.LIGHT_DIRECT, 8)
+    try:
+        assert lib.atmo_set_precision(ctx, 2) == N.ATMO_OK
+        cam = S.Camera(64, 36, (0.0, 0.0, 600.0), (0.0, 0.0, 0.0))
+        f = _frame(cam)
+        m = (C.c_float * 16)(*[float(x) for x in col_major(np.eye(4))])
+        d = N.AtmoDepth(4096, N.DEPTH_X8_D24_UNORM, 0)
+        for tf in (N.TARGET_RGBA32F, N.TARGET_RGBA16F):
+            t = N.AtmoTarget(8192, tf, 0)
+            assert lib.atmo_render_depth_target(ctx, C.byref(f), C.byref(d), C.byref(t), 0, None) == N.ATMO_E_STATE
+            msg = lib.atmo_last_error_string(ctx)   # (not atmo_render_target's wording: no target format works in another mode here)
+            assert b"no depth-source kernel" in msg and b"RGBA32F included" in msg and b"work in every mode" not in msg, msg
+            assert lib.atmo_render_proxy_depth_target(ctx, C.byref(f), m, C.c_float(10.0), C.byref(d), C.byref(t), 1, None) == N.ATMO_E_STATE
+            views = (N.AtmoViewDepthTarget * 1)()
+            views[0].frame, views[0].depth, views[0].target = f, d, t
+            assert lib.atmo_render_views_depth_target(ctx, views, 1, 0, None) == N.ATMO_E_STATE
+            assert lib.atmo_render_views_proxy_depth_target(ctx, views, 1, m, C.c_float(10.0), 0, None) == N.ATMO_E_STATE
+    finally:
+        lib.atmo_destroy(ctx)

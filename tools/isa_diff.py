@@ -21,11 +21,16 @@ def kernels(lib, pattern, tmp, tag):
     co = device_code_object(lib, os.path.join(tmp, tag + ".co"))
     syms = subprocess.run([f"{LLVM}/llvm-readelf", "-sW", co], check=True, capture_output=True, text=True).stdout
     names = sorted({l.split()[-1] for l in syms.splitlines() if " FUNC " in l and re.search(pattern, l.split()[-1])})
+    # st_value and st_size of every kernel: what lies behind a symbol's size is not the kernel's (alignment and end-of-section s_nop padding, which
+    # llvm-objdump prints up to the next symbol -- 240 of them behind atmo_lut_footprint_kernel until another kernel was placed behind it)
+    extent = {l.split()[-1]: (int(l.split()[1], 16), int(l.split()[2])) for l in syms.splitlines() if " FUNC " in l}
     out = {}
     for name in names:
         dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", f"--disassemble-symbols={name}", co], check=True, capture_output=True, text=True).stdout
         # "  <instruction>   // <address>: <raw words>": keep the text and the raw encoding (relative branches encode offsets, so they compare as they are)
-        out[name] = [(m.group(1).strip(), m.group(3).strip()) for m in re.finditer(r"^\s+(\S[^\n]*?)\s+// ([0-9A-F]{12}):([^\n]*)", dis, re.M)]
+        start, size = extent[name]
+        ins = [(m.group(1).strip(), m.group(3).strip(), int(m.group(2), 16)) for m in re.finditer(r"^\s+(\S[^\n]*?)\s+// ([0-9A-F]{12}):([^\n]*)", dis, re.M)]
+        out[name] = [(text, raw) for text, raw, addr in ins if addr < start + size]
     return out
 
 
