@@ -1201,7 +1201,7 @@ __device__ __forceinline__ float4 march_atmosphere(const RenderConsts &rc, V3 di
     // eight); every twin is held at 12 (0.0821 ms; 4 bytes in measured 0.0818).  Instructions inserted INSIDE the loop behind its first one
     // cost their issue slot and nothing else, a 2 x unrolled body has no fast position at all, the LUT kernels' and the cloud kernels' loops do not care.  It is what
     // made rounds 2-5's "any scalar instruction in the preamble costs 8-10 %" and "an 80-SGPR cap (8 waves per SIMD) loses 8 %" -- both moved this loop by 4 bytes
-    // (at the right position the capped build is exactly as fast as this one: the eighth wave buys nothing).  tests/test_host_logic.py holds the position
+    // (at the right position the capped build is exactly as fast as this one: the eighth wave buys nothing).  tests/test_kernel_twins_host.py holds the position
     // (tools/loop_phase.py reads it from the built library); if a change to the code in front of the loop moves it, ATMO_LOOP_PAD = the number of s_nop that puts it back.
 #ifndef ATMO_LOOP_PAD
 #define ATMO_LOOP_PAD 0   // (the geometric tile order's first form in the preamble needed 1; with its hint tables the loop is back on 12 mod 32 by itself)
@@ -1948,7 +1948,7 @@ __device__ __forceinline__ float2 march_clouds_rm_queue(const RenderConsts &rc, 
 // branch, and NOTHING ELSE behind it: the decode is straight-line code on the loaded word (the quotient is computed for D32_SFLOAT too and not
 // selected).  With the division inside a three-way branch the single-draw cloud kernels spilled 200-300 SGPRs to VGPR lanes -- hipcc then loads 48
 // dwords of RenderConsts in front of the branch and carries them across it -- and clouds_high drew 1.85x slower (profiles/depth/README.md;
-// tools/depth_resources.py counts the spills now).  Outside every fp contract(fast) region; atmo_debug_decode_depth runs this same function on a
+// tools/twin_resources.py counts the spills now).  Outside every fp contract(fast) region; atmo_debug_decode_depth runs this same function on a
 // caller's array.
 __device__ __forceinline__ float depth_decode(const int format, const void *p) {
 #pragma clang fp contract(off)
@@ -2436,9 +2436,9 @@ constexpr bool render_sgpr_cap80(int flags) {
 // preamble, and these kernels are sensitive to exactly that: see the note inside).
 #ifdef ATMO_WAVE_TRACE
 #define ATMO_TRACE_ENTRY const uint64_t trace_entry = __builtin_amdgcn_s_memrealtime();
-#define ATMO_SHADE_TRACED                                                                                                          \
+#define ATMO_SHADE_TRACED(TARGET, DEPTH)                                                                                           \
     const uint64_t trace_t0 = __builtin_amdgcn_s_memrealtime();                                                                    \
-    shade_pixel<FLAGS, LSTEPS, SPLIT>(rc, (int)tile_x, (int)tile_y ATMO_SHADE_EXTRA);                                              \
+    shade_pixel<FLAGS, LSTEPS, SPLIT>(rc, (int)tile_x, (int)tile_y, nullptr, TARGET, DEPTH);                                       \
     if (rc.wave_trace != nullptr && (threadIdx.x & 63) == 0) {                                                                     \
         const uint32_t slot = (blockIdx.y * gridDim.x + blockIdx.x) * (TILE_W * TILE_H / 64) + (threadIdx.x >> 6);                 \
         unsigned long long *w = rc.wave_trace + 4ull * slot;                                                                       \
@@ -2449,9 +2449,8 @@ constexpr bool render_sgpr_cap80(int flags) {
     }
 #else
 #define ATMO_TRACE_ENTRY
-#define ATMO_SHADE_TRACED shade_pixel<FLAGS, LSTEPS, SPLIT>(rc, (int)tile_x, (int)tile_y ATMO_SHADE_EXTRA);
+#define ATMO_SHADE_TRACED(TARGET, DEPTH) shade_pixel<FLAGS, LSTEPS, SPLIT>(rc, (int)tile_x, (int)tile_y, nullptr, TARGET, DEPTH);
 #endif
-#define ATMO_SHADE_EXTRA   // further arguments of shade_pixel in the body below: none in the float kernels, the target in atmo_render_target_kernel
 // The geometric tile order (RenderConsts::geo_rows; cloudless kernels): block b shades the b-th tile of "the tiles that can shade, row-major, then the others,
 // row-major".  Uniform: scalar ALU and scalar loads from the kernel-argument segment only (a hint per 256 blocks, then one or two steps of a binary search).
 __device__ __forceinline__ uint32_t geo_tile(const RenderConsts &rc, uint32_t b) {
@@ -2476,28 +2475,30 @@ __device__ __forceinline__ uint32_t geo_tile(const RenderConsts &rc, uint32_t b)
 #ifndef ATMO_LOOP_PAD_GEO   // s_nop in front of shade_pixel in the twin kernels <4 | KF_GEO, 8, 1>: puts their view loop 12 bytes into a 32-byte block
 #define ATMO_LOOP_PAD_GEO 5
 #endif
-#define ATMO_GEO_STR2(x) #x
-#define ATMO_GEO_STR(x) ATMO_GEO_STR2(x)
-#define ATMO_GEO_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_GEO)
+// N s_nop in front of a kernel's code: what every ATMO_LOOP_PAD_* knob below counts (tools/phase_sweep.py sweeps them, tools/loop_phase.py names them)
+#define ATMO_PAD_STR2(x) #x
+#define ATMO_PAD_STR(x) ATMO_PAD_STR2(x)
+#define ATMO_HEAD_PAD(N) asm volatile(".rept " ATMO_PAD_STR(N) "\n\ts_nop 0\n\t.endr")
 // Keep this preamble exactly as it is for every variant.  Measured on the direct-light kernel (same loop ISA in all
 // three builds, profiles/round2/ab_direct_kernel.txt): this form 0.108-0.109 ms; a branch on tile_order in front of
 // the division 0.115 ms; NO preamble at all (blockIdx used directly) 0.115 ms as well.  Round 2 read that as "the scalar work in
 // front of the depth load helps"; round 6 found what it was: every one of those edits moved the direct-light kernel's view loop by a few bytes, and
 // that loop is 8.5-11 % slower at seven of its eight possible 4-byte positions (march_atmosphere; profiles/round6/ab_loop_phase.txt).  The preamble
-// itself is neutral; the POSITION is what must be kept (tests/test_host_logic.py::test_headline_view_loop_sits_at_its_fast_position).
-#define ATMO_RENDER_KERNEL_BODY                                                                                  \
+// itself is neutral; the POSITION is what must be kept (tests/test_kernel_twins_host.py::test_headline_twin_sits_at_the_fast_loop_position).
+// TARGET, DEPTH: shade_pixel's arguments behind the proxy (nullptr in the float kernels).
+#define ATMO_RENDER_KERNEL_BODY(TARGET, DEPTH)                                                                   \
     ATMO_TRACE_ENTRY                                                                                             \
     uint32_t tile = blockIdx.y * gridDim.x + blockIdx.x;                                                         \
     if constexpr ((FLAGS & KF_GEO) != 0) {   /* the twin kernels of the geometric order only: render_impl launches them with a table */ \
         tile = geo_tile(rc, tile);                                                                               \
         /* ... and their view loop on ITS fast position (march_atmosphere; tools/loop_phase.py reads both kernels) */ \
-        asm volatile(".rept " ATMO_GEO_PAD_STR "\n\ts_nop 0\n\t.endr");                                          \
+        ATMO_HEAD_PAD(ATMO_LOOP_PAD_GEO);                                                                        \
     }                                                                                                            \
     if (rc.tile_order != nullptr) tile = rc.tile_order[tile];                                                    \
     const uint32_t tile_y = tile / (uint32_t)rc.tiles_x, tile_x = tile - tile_y * (uint32_t)rc.tiles_x;          \
     uint64_t t0 = 0;                                                                                             \
     if (rc.tile_cost != nullptr) t0 = __builtin_amdgcn_s_memtime();                                              \
-    ATMO_SHADE_TRACED                                                                                            \
+    ATMO_SHADE_TRACED(TARGET, DEPTH)                                                                             \
     if (rc.tile_cost != nullptr && (threadIdx.x & 63) == 0) {                                                    \
         uint64_t dt = __builtin_amdgcn_s_memtime() - t0;                                                         \
         uint32_t cost_tile = tile;                                                                               \
@@ -2514,7 +2515,7 @@ __device__ __forceinline__ uint32_t geo_tile(const RenderConsts &rc, uint32_t b)
 
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
 __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_kernel(const RenderConsts rc) {
-    ATMO_RENDER_KERNEL_BODY
+    ATMO_RENDER_KERNEL_BODY(nullptr, nullptr)
 }
 // The far-mode proxy draw (KF_PROXY; atmo_render_proxy): the launch grid covers the box's screen rectangle only (the host clips it), row-major, no tile
 // order, no cost feedback -- its grid changes every frame.  A kernel of its own, so that atmo_render's kernels keep their code to the byte.
@@ -2536,65 +2537,61 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render
 #ifndef ATMO_LOOP_PAD_VIEWS   // s_nop at the head of <KF_VIEWS | KF_LIGHT_DIRECT, 8>
 #define ATMO_LOOP_PAD_VIEWS 3
 #endif
-#define ATMO_VIEWS_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_VIEWS)
 constexpr int views_min_waves(int flags) {
     return ((flags & KF_CLOUDS) && !(flags & (KF_CLOUD_LIGHT_RM | KF_CUBE_LOD))) ? 8 : render_min_waves(flags);
 }
+// The body of the six view-batch kernels, textually the same in all of them for the reason ATMO_RENDER_KERNEL_BODY is.  V: the kernel argument that holds
+// first_block (and, ORDERED = 1, the tile order and the cost map; the proxy batches have neither: 0); PROXY, TARGET, DEPTH: shade_pixel's arguments behind
+// the tile, each the view's entry of an array in the kernel-argument segment or nullptr.
+#define ATMO_VIEWS_ORDERED_0(...)
+#define ATMO_VIEWS_ORDERED_1(...) __VA_ARGS__
+#define ATMO_VIEWS_KERNEL_BODY(V, ORDERED, PROXY, TARGET, DEPTH)                                                                       \
+    uint32_t tile = blockIdx.x;                                                                                                        \
+    ATMO_VIEWS_ORDERED_##ORDERED(if (V.order != nullptr) tile = V.order[tile];)                                                        \
+    uint32_t view = 0; /* the last view whose first block is <= tile (empty views share their successor's first block and are stepped over) */ \
+    _Pragma("unroll") for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= V.first_block[i] ? 1u : 0u;                                  \
+    view = __builtin_amdgcn_readfirstlane(view);                                                                                       \
+    const RenderConsts &rc = table[view];                                                                                              \
+    const uint32_t local = tile - V.first_block[view];                                                                                 \
+    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;                              \
+    ATMO_VIEWS_ORDERED_##ORDERED(uint64_t t0 = 0; if (V.cost != nullptr) t0 = __builtin_amdgcn_s_memtime();)                           \
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, PROXY, TARGET, DEPTH);                                                 \
+    ATMO_VIEWS_ORDERED_##ORDERED(if (V.cost != nullptr && (threadIdx.x & 63) == 0) {                                                   \
+        const uint64_t dt = __builtin_amdgcn_s_memtime() - t0;                                                                         \
+        atomicMax(&V.cost[tile], (uint32_t)(dt > 0xffffffffull ? 0xffffffffull : dt));                                                 \
+    })
 template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_kernel(const RenderConsts *__restrict__ table, const ViewsConsts vc) {
     static_assert((FLAGS & KF_VIEWS) != 0, "multi-view kernels carry KF_VIEWS");
     // the headline kernel's twin <KF_VIEWS | KF_LIGHT_DIRECT, 8>: its view loop on ITS fast position, 12 bytes into a 32-byte block, as the float kernel's
-    // (march_atmosphere; tools/loop_phase.py reads it, tests/test_views_host.py holds it there)
-    if constexpr (FLAGS == (KF_VIEWS | KF_LIGHT_DIRECT) && LSTEPS == 8) asm volatile(".rept " ATMO_VIEWS_PAD_STR "\n\ts_nop 0\n\t.endr");
-    uint32_t tile = blockIdx.x;
-    if (vc.order != nullptr) tile = vc.order[tile];
-    uint32_t view = 0;   // the last view whose first block is <= tile (empty views share their successor's first block and are stepped over)
-#pragma unroll
-    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vc.first_block[i] ? 1u : 0u;
-    view = __builtin_amdgcn_readfirstlane(view);
-    const RenderConsts &rc = table[view];
-    const uint32_t local = tile - vc.first_block[view];
-    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
-    uint64_t t0 = 0;
-    if (vc.cost != nullptr) t0 = __builtin_amdgcn_s_memtime();
-    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y);
-    if (vc.cost != nullptr && (threadIdx.x & 63) == 0) {
-        const uint64_t dt = __builtin_amdgcn_s_memtime() - t0;
-        atomicMax(&vc.cost[tile], (uint32_t)(dt > 0xffffffffull ? 0xffffffffull : dt));
-    }
+    // (march_atmosphere; tools/loop_phase.py reads it, tests/test_kernel_twins_host.py holds it there)
+    if constexpr (FLAGS == (KF_VIEWS | KF_LIGHT_DIRECT) && LSTEPS == 8) ATMO_HEAD_PAD(ATMO_LOOP_PAD_VIEWS);
+    ATMO_VIEWS_KERNEL_BODY(vc, 1, nullptr, nullptr, nullptr)
 }
 // the same kernel under an 80-SGPR cap (8 waves per SIMD), for the families render_sgpr_cap80 names (none in the shipped build)
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
 __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) __attribute__((amdgpu_num_sgpr(ATMO_SGPR_CAP_VALUE))) void atmo_render_kernel_s80(const RenderConsts rc) {
-    ATMO_RENDER_KERNEL_BODY
+    ATMO_RENDER_KERNEL_BODY(nullptr, nullptr)
 }
 
 // The packed-target draws (KF_TARGET; atmo_render_target / atmo_render_proxy_target, include/atmo_target.h): the bodies of the two kernels above with the
 // target as a second (third) kernel argument, which shade_pixel's stores and blend go through (store_target).  Kernels of their own names, so that the float
-// kernels keep their code to the byte and tests/test_host_logic.py still finds ONE headline kernel.
-#undef ATMO_SHADE_EXTRA
-#define ATMO_SHADE_EXTRA , nullptr, &tc
+// kernels keep their code to the byte and tests/test_kernel_twins_host.py still finds ONE headline kernel.
 #ifndef ATMO_LOOP_PAD_TARGET       // s_nop at the head of both twins ...
 #define ATMO_LOOP_PAD_TARGET 3
 #endif
 #ifndef ATMO_LOOP_PAD_TARGET_GEO   // ... and more of them in the geometric-order twin, on top of ATMO_LOOP_PAD_GEO
 #define ATMO_LOOP_PAD_TARGET_GEO 6
 #endif
-#define ATMO_TARGET_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_TARGET)
-#define ATMO_TARGET_GEO_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_TARGET_GEO)
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
 __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_target_kernel(const RenderConsts rc, const TargetConsts tc) {
     static_assert((FLAGS & KF_TARGET) != 0, "target kernels carry KF_TARGET");
     // the headline kernel's twins <KF_TARGET | KF_LIGHT_DIRECT [| KF_GEO], 8, 1>: their view loop on ITS fast position, 12 bytes into a 32-byte block, as
-    // the float kernels' (march_atmosphere; tools/loop_phase.py reads all four, tests/test_target_host.py holds these two there)
-    if constexpr ((FLAGS & ~KF_GEO) == (KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8 && SPLIT == 1)
-        asm volatile(".rept " ATMO_TARGET_PAD_STR "\n\ts_nop 0\n\t.endr");
-    if constexpr (FLAGS == (KF_TARGET | KF_LIGHT_DIRECT | KF_GEO) && LSTEPS == 8 && SPLIT == 1)
-        asm volatile(".rept " ATMO_TARGET_GEO_PAD_STR "\n\ts_nop 0\n\t.endr");
-    ATMO_RENDER_KERNEL_BODY
+    // the float kernels' (march_atmosphere; tools/loop_phase.py reads all four, tests/test_kernel_twins_host.py holds these two there)
+    if constexpr ((FLAGS & ~KF_GEO) == (KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8 && SPLIT == 1) ATMO_HEAD_PAD(ATMO_LOOP_PAD_TARGET);
+    if constexpr (FLAGS == (KF_TARGET | KF_LIGHT_DIRECT | KF_GEO) && LSTEPS == 8 && SPLIT == 1) ATMO_HEAD_PAD(ATMO_LOOP_PAD_TARGET_GEO);
+    ATMO_RENDER_KERNEL_BODY(&tc, nullptr)
 }
-#undef ATMO_SHADE_EXTRA
-#define ATMO_SHADE_EXTRA
 template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_proxy_target_kernel(const RenderConsts rc, const ProxyConsts pc,
                                                                                                       const TargetConsts tc) {
@@ -2610,30 +2607,14 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render
 #ifndef ATMO_LOOP_PAD_VIEWS_TARGET   // s_nop at the head of <KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8>
 #define ATMO_LOOP_PAD_VIEWS_TARGET 3
 #endif
-#define ATMO_VIEWS_TARGET_PAD_STR ATMO_GEO_STR(ATMO_LOOP_PAD_VIEWS_TARGET)
 template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_target_kernel(const RenderConsts *__restrict__ table,
                                                                                                          const ViewsTargetConsts vtc) {
     static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_TARGET) != 0, "multi-view target kernels carry KF_VIEWS | KF_TARGET");
     // the headline kernel's twin <KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8>: its view loop on ITS fast position, 12 bytes into a 32-byte block, as the
-    // other twins' (march_atmosphere; tools/loop_phase.py reads it, tests/test_views_target_host.py holds it there)
-    if constexpr (FLAGS == (KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8) asm volatile(".rept " ATMO_VIEWS_TARGET_PAD_STR "\n\ts_nop 0\n\t.endr");
-    uint32_t tile = blockIdx.x;
-    if (vtc.v.order != nullptr) tile = vtc.v.order[tile];
-    uint32_t view = 0;   // as atmo_render_views_kernel: the last view whose first block is <= tile
-#pragma unroll
-    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vtc.v.first_block[i] ? 1u : 0u;
-    view = __builtin_amdgcn_readfirstlane(view);
-    const RenderConsts &rc = table[view];
-    const uint32_t local = tile - vtc.v.first_block[view];
-    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
-    uint64_t t0 = 0;
-    if (vtc.v.cost != nullptr) t0 = __builtin_amdgcn_s_memtime();
-    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, nullptr, &vtc.target[view]);
-    if (vtc.v.cost != nullptr && (threadIdx.x & 63) == 0) {
-        const uint64_t dt = __builtin_amdgcn_s_memtime() - t0;
-        atomicMax(&vtc.v.cost[tile], (uint32_t)(dt > 0xffffffffull ? 0xffffffffull : dt));
-    }
+    // other twins' (march_atmosphere; tools/loop_phase.py reads it, tests/test_kernel_twins_host.py holds it there)
+    if constexpr (FLAGS == (KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8) ATMO_HEAD_PAD(ATMO_LOOP_PAD_VIEWS_TARGET);
+    ATMO_VIEWS_KERNEL_BODY(vtc.v, 1, nullptr, &vtc.target[view], nullptr)
 }
 // Several far-mode (proxy) views in one launch (KF_VIEWS | KF_PROXY [| KF_TARGET]; atmo_render_views_proxy[_target], include/atmo_views_proxy.h): the view
 // lookup of atmo_render_views_kernel in front of the proxy draw's shade_pixel.  table[view] carries the view's CUT rectangle -- the box's screen rectangle
@@ -2646,30 +2627,14 @@ template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_proxy_kernel(const RenderConsts *__restrict__ table,
                                                                                                         const ViewsProxyConsts vpc) {
     static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) == 0, "multi-view proxy kernels carry KF_VIEWS | KF_PROXY");
-    const uint32_t tile = blockIdx.x;
-    uint32_t view = 0;   // as atmo_render_views_kernel: the last view whose first block is <= tile
-#pragma unroll
-    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vpc.first_block[i] ? 1u : 0u;
-    view = __builtin_amdgcn_readfirstlane(view);
-    const RenderConsts &rc = table[view];
-    const uint32_t local = tile - vpc.first_block[view];
-    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
-    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, &vpc.proxy[view]);
+    ATMO_VIEWS_KERNEL_BODY(vpc, 0, &vpc.proxy[view], nullptr, nullptr)
 }
 template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_proxy_target_kernel(const RenderConsts *__restrict__ table,
                                                                                                                const ViewsProxyTargetConsts vptc) {
     static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0,
                   "multi-view proxy target kernels carry KF_VIEWS | KF_PROXY | KF_TARGET");
-    const uint32_t tile = blockIdx.x;
-    uint32_t view = 0;
-#pragma unroll
-    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vptc.p.first_block[i] ? 1u : 0u;
-    view = __builtin_amdgcn_readfirstlane(view);
-    const RenderConsts &rc = table[view];
-    const uint32_t local = tile - vptc.p.first_block[view];
-    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
-    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, &vptc.p.proxy[view], &vptc.target[view]);
+    ATMO_VIEWS_KERNEL_BODY(vptc.p, 0, &vptc.p.proxy[view], &vptc.target[view], nullptr)
 }
 
 // Stable counting sort of the tiles by the cost a recording draw measured, heaviest class first; clears the costs for
@@ -3190,13 +3155,13 @@ static hipError_t launch_rect(Kernel kernel, const RenderConsts &rc, hipStream_t
     hipLaunchKernelGGL(kernel, dim3(gx, gy), dim3(TILE_W * TILE_H), 0, stream, rc, more...);
     return hipGetLastError();
 }
-// ... and a view batch's: one block per tile of the concatenation of the views' grids (first_block[MAX_VIEWS] of them); consts: the kernel's argument behind
+// ... and a view batch's: one block per tile of the concatenation of the views' grids (first_block[MAX_VIEWS] of them); consts: the kernel's arguments behind
 // the table
-template <class Kernel, class Consts>
-static hipError_t launch_batch(Kernel kernel, const uint32_t *first_block, const RenderConsts *table, const Consts &consts, hipStream_t stream) {
+template <class Kernel, class... Consts>
+static hipError_t launch_batch(Kernel kernel, const uint32_t *first_block, const RenderConsts *table, hipStream_t stream, const Consts &...consts) {
     const uint32_t total = first_block[MAX_VIEWS];
     if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kernel, dim3(total), dim3(TILE_W * TILE_H), 0, stream, table, consts);
+    hipLaunchKernelGGL(kernel, dim3(total), dim3(TILE_W * TILE_H), 0, stream, table, consts...);
     return hipGetLastError();
 }
 
@@ -3349,13 +3314,17 @@ static hipError_t launch_default_family(int flags, int light_steps, Launch &&lau
 #undef ATMO_FAMILY_SKIPPED
 #undef ATMO_DEFAULT_FAMILIES
 
-// one packed format per batch, and every view that owns tiles has a target
-static bool batch_targets_valid(const uint32_t *first_block, const TargetConsts *target) {
+static bool target_format_known(int format) { return format == TF_RGBA32F || target_format_packed(format); }
+static bool depth_consts_valid(const DepthConsts &dc) { return dc.texels != nullptr && depth_texel_bytes(dc.format) != 0 && dc.pitch_bytes > 0; }
+// one target format per batch, and every view that owns tiles has a target: a packed one, or with `depth` (the depth-source batches) any of the seven and
+// a depth source as well
+static bool batch_targets_valid(const uint32_t *first_block, const TargetConsts *target, const DepthConsts *depth = nullptr) {
     int format = -1;
     for (int i = 0; i < MAX_VIEWS; ++i) {
         if (first_block[i + 1] == first_block[i]) continue;
         const TargetConsts &t = target[i];
-        if (t.pixels == nullptr || !target_format_packed(t.format) || (format >= 0 && t.format != format)) return false;
+        if (t.pixels == nullptr || (format >= 0 && t.format != format)) return false;
+        if (depth != nullptr ? !target_format_known(t.format) || !depth_consts_valid(depth[i]) : !target_format_packed(t.format)) return false;
         format = t.format;
     }
     return true;
@@ -3370,7 +3339,7 @@ hipError_t launch_render_proxy(int flags, const RenderConsts &rc, const ProxyCon
 // the view batches
 hipError_t launch_render_views(int flags, int light_steps, const RenderConsts *table, const ViewsConsts &vc, hipStream_t stream) {
     return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
-        return launch_batch(atmo_render_views_kernel<F | KF_VIEWS, L>, vc.first_block, table, vc, stream);
+        return launch_batch(atmo_render_views_kernel<F | KF_VIEWS, L>, vc.first_block, table, stream, vc);
     });
 }
 
@@ -3400,20 +3369,20 @@ hipError_t launch_render_proxy_target(int flags, const RenderConsts &rc, const P
 hipError_t launch_render_views_target(int flags, int light_steps, const RenderConsts *table, const ViewsTargetConsts &vtc, hipStream_t stream) {
     if (!batch_targets_valid(vtc.v.first_block, vtc.target)) return hipErrorInvalidValue;
     return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
-        return launch_batch(atmo_render_views_target_kernel<F | KF_VIEWS | KF_TARGET, L>, vtc.v.first_block, table, vtc, stream);
+        return launch_batch(atmo_render_views_target_kernel<F | KF_VIEWS | KF_TARGET, L>, vtc.v.first_block, table, stream, vtc);
     });
 }
 
 // the proxy view batches (float and packed): no tile order
 hipError_t launch_render_views_proxy(int flags, int light_steps, const RenderConsts *table, const ViewsProxyConsts &vpc, hipStream_t stream) {
     return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
-        return launch_batch(atmo_render_views_proxy_kernel<F | KF_VIEWS | KF_PROXY, L>, vpc.first_block, table, vpc, stream);
+        return launch_batch(atmo_render_views_proxy_kernel<F | KF_VIEWS | KF_PROXY, L>, vpc.first_block, table, stream, vpc);
     });
 }
 hipError_t launch_render_views_proxy_target(int flags, int light_steps, const RenderConsts *table, const ViewsProxyTargetConsts &vptc, hipStream_t stream) {
     if (!batch_targets_valid(vptc.p.first_block, vptc.target)) return hipErrorInvalidValue;
     return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
-        return launch_batch(atmo_render_views_proxy_target_kernel<F | KF_VIEWS | KF_PROXY | KF_TARGET, L>, vptc.p.first_block, table, vptc, stream);
+        return launch_batch(atmo_render_views_proxy_target_kernel<F | KF_VIEWS | KF_PROXY | KF_TARGET, L>, vptc.p.first_block, table, stream, vptc);
     });
 }
 
@@ -3499,8 +3468,6 @@ hipError_t launch_bake(const BakeConsts &bc, hipStream_t stream) {
 // ViewsTargetConsts::target), which shade_pixel's depth read goes through (load_depth), and with stores in all seven target formats (a host with a D24
 // buffer and a float4 colour buffer has no other call).  Kernels of their own names (no older kernel's name is a substring of them, nor the reverse),
 // defined and instantiated behind everything else, so that every older kernel keeps its code and its place in the code object.
-#undef ATMO_SHADE_EXTRA
-#define ATMO_SHADE_EXTRA , nullptr, &tc, &dc
 #ifndef ATMO_LOOP_PAD_DEPTH         // s_nop at the head of the twins <KF_DEPTH | KF_TARGET | KF_LIGHT_DIRECT [| KF_GEO], 8, 1> ...
 #define ATMO_LOOP_PAD_DEPTH 2
 #endif
@@ -3515,84 +3482,35 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render
                                                                                                       const DepthConsts dc) {
     static_assert((FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0, "depth-source kernels carry KF_DEPTH | KF_TARGET");
     // the headline kernel's twins: their view loop 12 bytes into a 32-byte block, as every twin's before them (march_atmosphere; tools/loop_phase.py reads
-    // them, tests/test_depth_host.py holds them there)
-    if constexpr ((FLAGS & ~KF_GEO) == (KF_DEPTH | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8 && SPLIT == 1)
-        asm volatile(".rept " ATMO_GEO_STR(ATMO_LOOP_PAD_DEPTH) "\n\ts_nop 0\n\t.endr");
-    if constexpr (FLAGS == (KF_DEPTH | KF_TARGET | KF_LIGHT_DIRECT | KF_GEO) && LSTEPS == 8 && SPLIT == 1)
-        asm volatile(".rept " ATMO_GEO_STR(ATMO_LOOP_PAD_DEPTH_GEO) "\n\ts_nop 0\n\t.endr");
-    ATMO_RENDER_KERNEL_BODY
+    // them, tests/test_kernel_twins_host.py holds them there)
+    if constexpr ((FLAGS & ~KF_GEO) == (KF_DEPTH | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8 && SPLIT == 1) ATMO_HEAD_PAD(ATMO_LOOP_PAD_DEPTH);
+    if constexpr (FLAGS == (KF_DEPTH | KF_TARGET | KF_LIGHT_DIRECT | KF_GEO) && LSTEPS == 8 && SPLIT == 1) ATMO_HEAD_PAD(ATMO_LOOP_PAD_DEPTH_GEO);
+    ATMO_RENDER_KERNEL_BODY(&tc, &dc)
 }
-#undef ATMO_SHADE_EXTRA
-#define ATMO_SHADE_EXTRA
 template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_proxy_depth_target_kernel(const RenderConsts rc, const ProxyConsts pc,
                                                                                                             const TargetConsts tc, const DepthConsts dc) {
     static_assert((FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0, "KF_DEPTH | KF_PROXY | KF_TARGET");
     shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, &pc, &tc, &dc);
 }
-// (the body of atmo_render_views_target_kernel)
 template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_depth_target_kernel(const RenderConsts *__restrict__ table,
                                                                                                                const ViewsTargetConsts vtc,
                                                                                                                const ViewsDepthConsts vdc) {
     static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0, "KF_DEPTH | KF_VIEWS | KF_TARGET");
-    if constexpr (FLAGS == (KF_DEPTH | KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8)
-        asm volatile(".rept " ATMO_GEO_STR(ATMO_LOOP_PAD_DEPTH_VIEWS) "\n\ts_nop 0\n\t.endr");
-    uint32_t tile = blockIdx.x;
-    if (vtc.v.order != nullptr) tile = vtc.v.order[tile];
-    uint32_t view = 0;   // as atmo_render_views_kernel: the last view whose first block is <= tile
-#pragma unroll
-    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vtc.v.first_block[i] ? 1u : 0u;
-    view = __builtin_amdgcn_readfirstlane(view);
-    const RenderConsts &rc = table[view];
-    const uint32_t local = tile - vtc.v.first_block[view];
-    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
-    uint64_t t0 = 0;
-    if (vtc.v.cost != nullptr) t0 = __builtin_amdgcn_s_memtime();
-    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, nullptr, &vtc.target[view], &vdc.depth[view]);
-    if (vtc.v.cost != nullptr && (threadIdx.x & 63) == 0) {
-        const uint64_t dt = __builtin_amdgcn_s_memtime() - t0;
-        atomicMax(&vtc.v.cost[tile], (uint32_t)(dt > 0xffffffffull ? 0xffffffffull : dt));
-    }
+    if constexpr (FLAGS == (KF_DEPTH | KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8) ATMO_HEAD_PAD(ATMO_LOOP_PAD_DEPTH_VIEWS);
+    ATMO_VIEWS_KERNEL_BODY(vtc.v, 1, nullptr, &vtc.target[view], &vdc.depth[view])
 }
-// (the body of atmo_render_views_proxy_target_kernel; unpadded, as every proxy kernel)
+// (unpadded, as every proxy kernel)
 template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_proxy_depth_target_kernel(
     const RenderConsts *__restrict__ table, const ViewsProxyTargetConsts vptc, const ViewsDepthConsts vdc) {
     static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0,
                   "KF_DEPTH | KF_VIEWS | KF_PROXY | KF_TARGET");
-    const uint32_t tile = blockIdx.x;
-    uint32_t view = 0;
-#pragma unroll
-    for (int i = 1; i < MAX_VIEWS; ++i) view += tile >= vptc.p.first_block[i] ? 1u : 0u;
-    view = __builtin_amdgcn_readfirstlane(view);
-    const RenderConsts &rc = table[view];
-    const uint32_t local = tile - vptc.p.first_block[view];
-    const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;
-    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, &vptc.p.proxy[view], &vptc.target[view], &vdc.depth[view]);
+    ATMO_VIEWS_KERNEL_BODY(vptc.p, 0, &vptc.p.proxy[view], &vptc.target[view], &vdc.depth[view])
 }
 
 // their launches: those of the four packed-target draws
-static bool target_format_known(int format) { return format == TF_RGBA32F || target_format_packed(format); }
-static bool depth_consts_valid(const DepthConsts &dc) { return dc.texels != nullptr && depth_texel_bytes(dc.format) != 0 && dc.pitch_bytes > 0; }
-// one target format per batch (any of the seven), and every view that owns tiles has a target and a depth source
-static bool batch_depth_targets_valid(const uint32_t *first_block, const TargetConsts *target, const DepthConsts *depth) {
-    int format = -1;
-    for (int i = 0; i < MAX_VIEWS; ++i) {
-        if (first_block[i + 1] == first_block[i]) continue;
-        const TargetConsts &t = target[i];
-        if (t.pixels == nullptr || !target_format_known(t.format) || (format >= 0 && t.format != format) || !depth_consts_valid(depth[i])) return false;
-        format = t.format;
-    }
-    return true;
-}
-template <class Kernel, class A, class B>
-static hipError_t launch_batch2(Kernel kernel, const uint32_t *first_block, const RenderConsts *table, const A &a, const B &b, hipStream_t stream) {
-    const uint32_t total = first_block[MAX_VIEWS];
-    if (total < 1u || total > 0x7fffffffu || table == nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kernel, dim3(total), dim3(TILE_W * TILE_H), 0, stream, table, a, b);
-    return hipGetLastError();
-}
 hipError_t launch_render_depth_target(int flags, int split, const RenderConsts &rc, const TargetConsts &tc, const DepthConsts &dc, hipStream_t stream,
                                       int tile_list_blocks) {
     if (!target_format_known(tc.format) || !depth_consts_valid(dc) || !target_family_supported(flags & ~KF_GEO, split)) return hipErrorInvalidValue;
@@ -3612,17 +3530,17 @@ hipError_t launch_render_proxy_depth_target(int flags, const RenderConsts &rc, c
 }
 hipError_t launch_render_views_depth_target(int flags, int light_steps, const RenderConsts *table, const ViewsTargetConsts &vtc, const ViewsDepthConsts &vdc,
                                             hipStream_t stream) {
-    if (!batch_depth_targets_valid(vtc.v.first_block, vtc.target, vdc.depth)) return hipErrorInvalidValue;
+    if (!batch_targets_valid(vtc.v.first_block, vtc.target, vdc.depth)) return hipErrorInvalidValue;
     return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
-        return launch_batch2(atmo_render_views_depth_target_kernel<F | KF_DEPTH | KF_VIEWS | KF_TARGET, L>, vtc.v.first_block, table, vtc, vdc, stream);
+        return launch_batch(atmo_render_views_depth_target_kernel<F | KF_DEPTH | KF_VIEWS | KF_TARGET, L>, vtc.v.first_block, table, stream, vtc, vdc);
     });
 }
 hipError_t launch_render_views_proxy_depth_target(int flags, int light_steps, const RenderConsts *table, const ViewsProxyTargetConsts &vptc,
                                                   const ViewsDepthConsts &vdc, hipStream_t stream) {
-    if (!batch_depth_targets_valid(vptc.p.first_block, vptc.target, vdc.depth)) return hipErrorInvalidValue;
+    if (!batch_targets_valid(vptc.p.first_block, vptc.target, vdc.depth)) return hipErrorInvalidValue;
     return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
-        return launch_batch2(atmo_render_views_proxy_depth_target_kernel<F | KF_DEPTH | KF_VIEWS | KF_PROXY | KF_TARGET, L>, vptc.p.first_block, table, vptc,
-                             vdc, stream);
+        return launch_batch(atmo_render_views_proxy_depth_target_kernel<F | KF_DEPTH | KF_VIEWS | KF_PROXY | KF_TARGET, L>, vptc.p.first_block, table,
+                            stream, vptc, vdc);
     });
 }
 

@@ -1,5 +1,5 @@
 """CPU tests of the depth sources (include/atmo_depth.h): the numerical contract as godot_atmosphere_shader_amd/depth_formats.py states it, the header's
-symbol set and the binding, the capability query, the kernels the library was built with (families, resources, loop positions), and the argument checks of
+symbol set and the binding, the capability query, the kernels the library was built with (families; resources and loop positions: tests/test_kernel_twins_host.py), and the argument checks of
 the four entry points on a host-only context.  (tests/test_depth_gpu.py holds the kernels to the statement bit for bit.)"""
 import ctypes as C
 import os
@@ -159,47 +159,6 @@ def test_every_depth_kernel_exists_for_the_default_families():
     assert all(not (f[0] & DEPTH) for k, s in found.items() if k not in new for f in s)
 
 
-def test_depth_headline_twins_sit_at_the_fast_loop_position():
-    """As tests/test_target_host.py::test_target_headline_twins_sit_at_the_fast_loop_position: the direct-light headline twins of the depth-source family carry
-    the same view loop, and it starts 12 bytes into its 32-byte block (ATMO_LOOP_PAD_DEPTH, ATMO_LOOP_PAD_DEPTH_GEO, ATMO_LOOP_PAD_DEPTH_VIEWS)."""
-    from godot_atmosphere_shader_amd.build import build_native
-
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.skip("llvm-objdump of the ROCm toolchain not found")
-    loop_phase = _loop_phase()
-    lib = build_native()
-    for pattern, knob in (("atmo_render_depth_target_kernelILi5124ELi8ELi1E", "ATMO_LOOP_PAD_DEPTH"),
-                          ("atmo_render_depth_target_kernelILi5380ELi8ELi1E", "ATMO_LOOP_PAD_DEPTH_GEO"),
-                          ("atmo_render_views_depth_target_kernelILi7172ELi8E", "ATMO_LOOP_PAD_DEPTH_VIEWS")):
-        rows = loop_phase.view_loops(lib, pattern)
-        assert len(rows) == 1, (pattern, rows)
-        name, offset, phase, size = rows[0]
-        assert phase == loop_phase.FAST_PHASE, f"{name}: view loop {phase} bytes into its block (at +0x{offset:x}, {size} bytes): move {knob}"
-        assert size == loop_phase.view_loops(lib, "atmo_render_target_kernelILi1028ELi8ELi1E")[0][3]   # the packed-target twin's loop
-    # the older headline kernels stay where they were
-    for pattern in ("atmo_render_kernelILi4ELi8ELi1E", loop_phase.GEO_TWIN, "atmo_render_target_kernelILi1028ELi8ELi1E",
-                    "atmo_render_views_target_kernelILi3076ELi8E"):
-        rows = loop_phase.view_loops(lib, pattern)
-        assert len(rows) == 1 and rows[0][2] == loop_phase.FAST_PHASE, (pattern, rows)
-
-
-def test_depth_kernels_keep_their_constants_in_sgprs():
-    """tools/depth_resources.py: each of the 22 + 18 + 18 + 18 kernels has no stack frame, as many vector loads inside its loops as its packed-target twin
-    (the depth load sits in the prologue; no field of a DepthConsts arrives through a vector load) and a VGPR count on the twin's occupancy step or better."""
-    import shutil
-
-    if shutil.which("hipcc") is None:
-        pytest.skip("hipcc not found")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "depth_resources.py")], capture_output=True, text=True, timeout=900)
-    print(p.stdout)
-    assert p.returncode == 0, p.stdout + p.stderr
-    for family, n in (("atmo_render_depth_target_kernel<", 22), ("atmo_render_proxy_depth_target_kernel<", 18),
-                      ("atmo_render_views_depth_target_kernel<", 18), ("atmo_render_views_proxy_depth_target_kernel<", 18)):
-        lines = [ln for ln in p.stdout.splitlines() if ln.startswith(family)]
-        assert len(lines) == n and all(ln.endswith("ScratchSize 0: ok") for ln in lines), family
-        for ln in lines:
-            m = re.search(r"in loops (\d+) vector loads \(twin (\d+)\)", ln)
-            assert m and m.group(1) == m.group(2), ln
 
 
 # ---- argument checks through the C ABI, without a device -------------------------------------------------------------------------------------------

@@ -227,27 +227,3 @@ def test_blend_is_decode_blend_encode():
     weird = T.blend(np.array([[np.inf, -np.inf, 1.0, 0.0]], dtype=f32), np.array([[1.0, 1.0, np.inf, 1.0]], dtype=np.float16), 1).view(np.uint16)
     assert list(weird[0]) == [T.HALF_QNAN, T.HALF_QNAN, 0x7C00, 0x3C00]
     assert np.array_equal(T.blend(src, src.copy(), "rgba32f")[:, 3], src[:, 3] + src[:, 3] * (f32(1.0) - src[:, 3]))
-
-
-def test_target_headline_twins_sit_at_the_fast_loop_position():
-    """The RGBA16F / RGBA8 twins of the headline kernel, <KF_TARGET | KF_LIGHT_DIRECT [| KF_GEO], 8, 1>, carry the same 436-byte view loop; it is 8.5-11 % slower off
-    its position (tests/test_host_logic.py::test_headline_view_loop_sits_at_its_fast_position), so the twins are padded onto it too (ATMO_LOOP_PAD_TARGET[_GEO])."""
-    import sys as _sys
-
-    from godot_atmosphere_shader_amd.build import build_native
-
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.skip("llvm-objdump of the ROCm toolchain not found")
-    _sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import loop_phase
-    finally:
-        _sys.path.pop(0)
-    lib = build_native()
-    for pattern, knob in (("atmo_render_target_kernelILi1028ELi8ELi1E", "ATMO_LOOP_PAD_TARGET"), ("atmo_render_target_kernelILi1284ELi8ELi1E", "ATMO_LOOP_PAD_TARGET_GEO")):
-        rows = loop_phase.view_loops(lib, pattern)
-        assert len(rows) == 1, rows
-        name, offset, phase, size = rows[0]
-        assert phase == loop_phase.FAST_PHASE, f"{name}: view loop {phase} bytes into its block (at +0x{offset:x}, {size} bytes): move {knob}"
-    # and the float headline kernel is still found once by the substring the existing test uses: the new family has a name of its own
-    assert len(loop_phase.view_loops(lib, "atmo_render_kernelILi4ELi8ELi1E")) == 1

@@ -1,12 +1,12 @@
 """CPU tests of the multi-view draw (include/atmo_views.h): the header's symbol set and the binding, the argument and state checks of atmo_render_views on a
 host-only context (nothing touches a device), the concatenated launch atmo_debug_views_layout reports -- every tile of every non-empty view exactly
-once --, and the static properties of the new kernels (the headline twin's loop position; registers, stack and loads against the atmo_render twins).
+once.  (tests/test_kernel_twins_host.py holds the static properties of the kernels: the headline twin's loop position; registers, stack and loads
+against the atmo_render twins.)
 (tests/test_views_gpu.py holds the kernels to atmo_render's pictures bit for bit.)"""
 import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import pytest
 
@@ -229,37 +229,3 @@ def test_views_layout_partitions_the_launch(even_origin):
         assert lib.atmo_debug_views_layout(ctx, v, 1, None, g0) == N.ATMO_E_ARG
     finally:
         lib.atmo_destroy(ctx)
-
-
-def test_views_headline_twin_sits_at_the_fast_loop_position():
-    """<KF_VIEWS | KF_LIGHT_DIRECT, 8> carries the headline kernel's 436-byte view loop, which is 8.5-11 % slower off its position
-    (tests/test_host_logic.py::test_headline_view_loop_sits_at_its_fast_position): padded onto it (ATMO_LOOP_PAD_VIEWS)."""
-    from godot_atmosphere_shader_amd.build import build_native
-
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.skip("llvm-objdump of the ROCm toolchain not found")
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import loop_phase
-    finally:
-        sys.path.pop(0)
-    lib = build_native()
-    rows = loop_phase.view_loops(lib, "atmo_render_views_kernelILi2052ELi8E")
-    assert len(rows) == 1, rows
-    name, offset, phase, size = rows[0]
-    assert phase == loop_phase.FAST_PHASE, f"{name}: view loop {phase} bytes into its block (at +0x{offset:x}, {size} bytes): move ATMO_LOOP_PAD_VIEWS"
-    # the float headline kernel is still found once by the substring the existing test uses: the new family has a name of its own
-    assert len(loop_phase.view_loops(lib, "atmo_render_kernelILi4ELi8ELi1E")) == 1
-
-
-def test_views_kernels_keep_their_constants_in_sgprs():
-    """tools/views_resources.py: every multi-view kernel has no stack frame, as many vector loads inside its loops as its atmo_render twin (the texture
-    fetches: no constant arrives through a vector load) and a VGPR count on the twin's occupancy step or a better one."""
-    import shutil
-
-    if shutil.which("hipcc") is None:
-        pytest.skip("hipcc not found")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "views_resources.py")], capture_output=True, text=True, timeout=900)
-    print(p.stdout)
-    assert p.returncode == 0, p.stdout + p.stderr
-    assert p.stdout.count("atmo_render_views_kernel<") == 18 and "ScratchSize 0: ok" in p.stdout

@@ -1,7 +1,7 @@
 """CPU tests of the far-mode (proxy) view batches (include/atmo_views_proxy.h): the header's symbol set and the binding, every refusal of
 atmo_render_views_proxy and atmo_render_views_proxy_target on a host-only context (nothing touches a device), the launch layout the host computes
-(atmo_debug_views_proxy_layout) against the single proxy draw's launch rectangle and the float64 coverage of tests/proxy_geometry.py, and the static
-properties of the 36 new kernels (tools/views_proxy_resources.py).
+(atmo_debug_views_proxy_layout) against the single proxy draw's launch rectangle and the float64 coverage of tests/proxy_geometry.py, and the families
+the library was built with.  (tests/test_kernel_twins_host.py holds the static properties of the 36 kernels: tools/twin_resources.py.)
 (tests/test_views_proxy_gpu.py holds the kernels to the single proxy draws' bytes bit for bit.)"""
 import ctypes as C
 import os
@@ -386,28 +386,6 @@ def test_layout_is_the_single_draws_launch_per_view(variant):
     finally:
         lib.atmo_destroy(ctx)
 
-
-def test_views_proxy_kernels_keep_their_constants_in_sgprs():
-    """tools/views_proxy_resources.py: each of the 18 + 18 kernels has no stack frame, as many vector loads inside its loops as its single-proxy twin (the
-    texture fetches: no constant -- no field of a ProxyConsts or a TargetConsts -- arrives through a vector load) and a VGPR count on the occupancy step
-    of the lower of its two twins (the single proxy draw's kernel, the fullscreen batch's) or a better one."""
-    import shutil
-
-    if shutil.which("hipcc") is None:
-        pytest.skip("hipcc not found")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "views_proxy_resources.py")], capture_output=True, text=True, timeout=900)
-    print(p.stdout)
-    assert p.returncode == 0, p.stdout + p.stderr
-    waves = lambda vgprs: min(8, 512 // (((vgprs + 7) // 8) * 8))      # noqa: E731
-    for family in ("atmo_render_views_proxy_kernel<", "atmo_render_views_proxy_target_kernel<"):
-        lines = [ln for ln in p.stdout.splitlines() if ln.startswith(family)]
-        assert len(lines) == 18 and all(ln.endswith("ScratchSize 0: ok") for ln in lines), family
-        for ln in lines:
-            m = re.search(r"in loops (\d+) vector loads \(proxy twin (\d+)\)", ln)
-            assert m and m.group(1) == m.group(2), ln
-            m = re.search(r"(\d+) VGPRs \((\d+) waves; proxy twin (\d+), batch twin (\d+)\)", ln)
-            assert m and int(m.group(2)) == waves(int(m.group(1))), ln
-            assert int(m.group(2)) >= min(waves(int(m.group(3))), waves(int(m.group(4)))), ln
 
 
 def test_every_default_form_entry_point_has_the_same_families():

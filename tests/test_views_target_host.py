@@ -1,12 +1,11 @@
 """CPU tests of the multi-view draw into packed and pitched colour targets (include/atmo_views_target.h): the header's symbol set and the binding, every
-refusal of atmo_render_views_target on a host-only context (nothing touches a device), the overlap rule against a brute-force byte-set comparison, and the
-static properties of the new kernels (the headline twin's loop position; registers, stack and loads against the float-batch twins).
+refusal of atmo_render_views_target on a host-only context (nothing touches a device) and the overlap rule against a brute-force byte-set comparison.
+(tests/test_kernel_twins_host.py holds the static properties of the kernels: the headline twin's loop position; registers, stack and loads against the twins.)
 (tests/test_views_target_gpu.py holds the kernels to atmo_render_target's bytes bit for bit.)"""
 import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -327,46 +326,3 @@ def test_render_views_target_needs_the_default_forms(mode, fmt):
         assert lib.atmo_render_views_target(ctx, v, n, 0, None) == N.ATMO_E_ARG
     finally:
         lib.atmo_destroy(ctx)
-
-
-def test_views_target_headline_twin_sits_at_the_fast_loop_position():
-    """<KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8> carries the headline kernel's view loop, which is 8.5-11 % slower off its position: padded onto it
-    (ATMO_LOOP_PAD_VIEWS_TARGET).  The float headline kernel, its views twin and its target twins are each still found once, at theirs."""
-    from godot_atmosphere_shader_amd.build import build_native
-
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.skip("llvm-objdump of the ROCm toolchain not found")
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import loop_phase
-    finally:
-        sys.path.pop(0)
-    lib = build_native()
-    for pattern, knob in (("atmo_render_views_target_kernelILi3076ELi8E", "ATMO_LOOP_PAD_VIEWS_TARGET"), ("atmo_render_kernelILi4ELi8ELi1E", "ATMO_LOOP_PAD"),
-                          ("atmo_render_views_kernelILi2052ELi8E", "ATMO_LOOP_PAD_VIEWS"), ("atmo_render_target_kernelILi1028ELi8ELi1E", "ATMO_LOOP_PAD_TARGET"),
-                          ("atmo_render_target_kernelILi1284ELi8ELi1E", "ATMO_LOOP_PAD_TARGET_GEO")):
-        rows = loop_phase.view_loops(lib, pattern)
-        assert len(rows) == 1, (pattern, rows)
-        name, offset, phase, size = rows[0]
-        assert phase == loop_phase.FAST_PHASE, f"{name}: view loop {phase} bytes into its block (at +0x{offset:x}, {size} bytes): move {knob}"
-
-
-def test_views_target_kernels_keep_their_constants_in_sgprs():
-    """tools/views_target_resources.py: every kernel of the family has no stack frame, as many vector loads inside its loops as its float-batch twin (the
-    texture fetches: no constant, and no field of a TargetConsts, arrives through a vector load) and a VGPR count on the twin's occupancy step or a
-    better one."""
-    import shutil
-
-    if shutil.which("hipcc") is None:
-        pytest.skip("hipcc not found")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "views_target_resources.py")], capture_output=True, text=True, timeout=900)
-    print(p.stdout)
-    assert p.returncode == 0, p.stdout + p.stderr
-    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("atmo_render_views_target_kernel<")]
-    assert len(lines) == 18 and all(ln.endswith("ScratchSize 0: ok") for ln in lines)
-    for ln in lines:
-        m = re.search(r"in loops (\d+) vector loads \(twin (\d+)\)", ln)
-        assert m and m.group(1) == m.group(2), ln
-        m = re.search(r"(\d+) VGPRs \((\d+) waves; twin (\d+)\)", ln)
-        twin_waves = min(8, 512 // (((int(m.group(3)) + 7) // 8) * 8))
-        assert int(m.group(2)) >= twin_waves, ln

@@ -2,7 +2,7 @@
 """Where the view loop of the direct-light kernels sits in the instruction stream (round 6, profiles/round6/ab_loop_phase.txt): the draw is 8.5-11 % slower
 unless the loop's first instruction -- the target of its backward branch -- lies 12 bytes into a 32-byte block.
 
-    python tools/loop_phase.py [libatmo_hip.so] [kernel substring, default "atmo_render_kernelILi4ELi8ELi1E"]
+    python tools/loop_phase.py [libatmo_hip.so] [kernel substring, default: each of HEADLINE_TWINS]
 
 Prints, per matching kernel, the address of the loop header relative to the kernel's start, its offset in the 32-byte block, and the loop's size."""
 import os
@@ -51,9 +51,22 @@ def view_loops(lib, pattern="atmo_render_kernelILi4ELi8ELi1E"):
 
 
 GEO_TWIN = "atmo_render_kernelILi260ELi8ELi1E"   # <KF_LIGHT_DIRECT | KF_GEO, 8, 1>: the same loop behind the geometric order's lookup (ATMO_LOOP_PAD_GEO)
+# Every kernel that carries the headline kernel's view loop and is held on FAST_PHASE: (substring of its mangled name, the knob in atmo_kernels.hip that
+# moves it).  The float headline kernel first; tests/test_kernel_twins_host.py holds each of them there.  A new twin: one line here.
+HEADLINE_TWINS = (
+    ("atmo_render_kernelILi4ELi8ELi1E", "ATMO_LOOP_PAD"),
+    (GEO_TWIN, "ATMO_LOOP_PAD_GEO"),
+    ("atmo_render_views_kernelILi2052ELi8E", "ATMO_LOOP_PAD_VIEWS"),
+    ("atmo_render_target_kernelILi1028ELi8ELi1E", "ATMO_LOOP_PAD_TARGET"),
+    ("atmo_render_target_kernelILi1284ELi8ELi1E", "ATMO_LOOP_PAD_TARGET_GEO"),
+    ("atmo_render_views_target_kernelILi3076ELi8E", "ATMO_LOOP_PAD_VIEWS_TARGET"),
+    ("atmo_render_depth_target_kernelILi5124ELi8ELi1E", "ATMO_LOOP_PAD_DEPTH"),
+    ("atmo_render_depth_target_kernelILi5380ELi8ELi1E", "ATMO_LOOP_PAD_DEPTH_GEO"),
+    ("atmo_render_views_depth_target_kernelILi7172ELi8E", "ATMO_LOOP_PAD_DEPTH_VIEWS"),
+)
 
 
 if __name__ == "__main__":
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "godot_atmosphere_shader_amd", "libatmo_hip.so")
-    for name, off, phase, size in (view_loops(lib, sys.argv[2]) if len(sys.argv) > 2 else view_loops(lib) + view_loops(lib, GEO_TWIN)):
+    for name, off, phase, size in (view_loops(lib, sys.argv[2]) if len(sys.argv) > 2 else [row for pattern, _ in HEADLINE_TWINS for row in view_loops(lib, pattern)]):
         print(f"{name}: view loop at +0x{off:x}, {size} bytes, header {phase} bytes into its 32-byte block ({'the fast position' if phase == FAST_PHASE else 'a SLOW position'})")
