@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from common import CONFIGS, SAMPLERS, TOL, demo_frame, demo_params, demo_textures, has_clouds, kernel_flags, make_node, oracle_inputs
+import random_scenes as RS
 from godot_atmosphere_shader_amd import scene as S
 
 pytestmark = pytest.mark.gpu
@@ -366,102 +367,38 @@ def test_log2_cr_device_equals_oracle(oracle32):
     lib.atmo_destroy(ctx)
 
 
-def _random_scene(rng, k):
-    """Random planet / camera / shader parameters: exercises the code paths the demo scene does not."""
-    R = float(rng.choice([1.0, 10.0, 100.0, 637.1]))
-    H = R * float(rng.uniform(0.03, 0.25))
-    dens_target = float(rng.uniform(0.3, 3.0))  # vertical optical depth rho^2 * H / 4 of order one
-    params = demo_params(
-        u_planet_radius=R, u_atmosphere_height=H, u_density=float(np.sqrt(4.0 * dens_target / H)),
-        u_scattering_strength=float(rng.uniform(0.3, 3.0)),
-        u_scattering_wavelengths=(float(rng.uniform(600, 750)), float(rng.uniform(500, 580)), float(rng.uniform(400, 480))),
-        u_atmosphere_modulate=tuple(rng.uniform(0.5, 1.0, 3).tolist()),
-        u_atmosphere_ambient_color=tuple(rng.uniform(0.0, 0.01, 3).tolist()),
-        u_sphere_depth_factor=float(rng.choice([0.0, 0.35, 1.0])),
-        u_cloud_density_scale=float(rng.uniform(0.5, 60.0) / H * 8.0),
-        u_cloud_bottom=float(rng.uniform(0.05, 0.3)), u_cloud_top=float(rng.uniform(0.4, 0.9)),
-        u_cloud_blend=float(rng.uniform(0.0, 1.0)), u_cloud_shape_invert=float(rng.choice([0.0, 1.0])),
-        u_cloud_coverage_bias=float(rng.uniform(-0.2, 0.2)), u_cloud_shape_factor=float(rng.uniform(0.0, 1.0)),
-        u_cloud_shape_scale=float(rng.uniform(0.05, 0.4) * 100.0 / R),
-    )
-    a = float(rng.uniform(0, 2 * np.pi))
-    params["u_cloud_coverage_rotation"] = (np.cos(a), np.sin(a), -np.sin(a), np.cos(a))
-    # camera: somewhere between just above the ground and 3 radii out, looking roughly at the limb or the planet
-    alt = float(rng.choice([0.02 * H, 0.4 * H, 0.9 * H, 1.5 * H, 0.6 * R, 2.0 * R]))
-    d = rng.normal(size=3)
-    d /= np.linalg.norm(d)
-    eye = d * (R + alt)
-    tangent = np.cross(d, rng.normal(size=3))
-    tangent /= np.linalg.norm(tangent)
-    target = eye + tangent * R * 0.5 - d * R * float(rng.uniform(-0.1, 0.6))
-    sun = rng.normal(size=3)
-    sun = sun / np.linalg.norm(sun) * R * 50.0
-    w, h = [(96, 54), (80, 45), (64, 64), (113, 37)][k % 4]
-    cam = S.Camera(w, h, eye=eye, target=target, fovy_deg=float(rng.uniform(40, 90)), near=0.05 * H, far=20.0 * R)
-    return params, cam, tuple(sun.tolist())
-
-
-# Seeds 0-11, then (round 6) the four scenes of the 1 212-scene soak that exceeded 1e-4 in rounds 3-5 -- 442 / 658 / 890 carried a 24^3 shape volume whose
-# filter coordinates the kernels had fused (fma(p, n, -0.5): the same bits as the reference's rounded product only for power-of-two n), 1040 one ulp of
-# the declared sampler's lambda; profiles/round6/fuzz_four.txt -- and 20 more drawn from the 1 212 (np.random.default_rng(6).choice(arange(12, 1212), 20)).
-# ATMO_FUZZ_EXTRA=n: seeds 12 .. 12 + n - 1 as well, on demand (the soak: n = 1200); ATMO_FUZZ_FIRST=k: k .. k + n - 1 instead (fresh scenes).
-FUZZ_SEEDS = list(range(12)) + [442, 658, 890, 1040] + [159, 234, 406, 418, 449, 456, 521, 537, 546, 553, 624, 648, 766, 792, 816, 817, 826, 915, 1133, 1187]
-_FUZZ_FIRST = int(__import__("os").environ.get("ATMO_FUZZ_FIRST", "12"))
-FUZZ_SEEDS += [k for k in range(_FUZZ_FIRST, _FUZZ_FIRST + int(__import__("os").environ.get("ATMO_FUZZ_EXTRA", "0"))) if k not in FUZZ_SEEDS]
+# The random scenes themselves -- `_random_scene`, the six-variant table, the per-seed textures, the node -- live in tests/random_scenes.py, which needs
+# no GPU, so that tests/test_random_scenes_host.py can say on the oracle what each seed's frame holds and tests/test_draw_paths_random_gpu.py can send
+# the same scenes through every other draw path.  FUZZ_SEEDS (there, with its history): seeds 0-11, the four of the round-6 soak, 20 more of its 1 212,
+# and the replacements of the always-run seeds whose frames are empty.
+_random_scene = RS.random_scene
+FUZZ_SEEDS = RS.FUZZ_SEEDS
 
 
 @pytest.mark.parametrize("seed", FUZZ_SEEDS)
 def test_parity_random_scenes(oracle32, seed):
     """Random planets, cameras (inside/outside the atmosphere and the cloud layer), suns, step counts (incl. the
     run-time light-step path and 16/64 view steps), non-power-of-two shape textures and small cubemaps."""
-    from godot_atmosphere_shader_amd import PlanetAtmosphere, load_shader
-    from godot_atmosphere_shader_amd.planet_atmosphere import make_frame
-
     rng = np.random.default_rng(1000 + seed)
     params, cam, sun = _random_scene(rng, seed)
-    shape_n = [64, 32, 24, 48][seed % 4]          # 24 and 48 are not powers of two
-    cube_n = [256, 64, 17, 128][seed % 4]
-    tex = dict(blue_noise=S.make_blue_noise(seed + 1), shape=S.make_shape_texture(shape_n, seed=seed, cells=4),
-               cubemap=None if seed % 5 == 4 else S.make_coverage_cubemap(cube_n, seed=seed))
-    variants = [
-        ("planet_atmosphere_no_clouds", dict(view_steps=16), dict(view_steps=16)),
-        ("planet_atmosphere_no_clouds", dict(view_steps=64, light_steps=5), dict(view_steps=64, light_mode="direct", light_steps=5)),
-        ("planet_atmosphere_clouds", dict(view_steps=8, cloud_steps=8), dict(cloud_steps=8)),
-        ("planet_atmosphere_clouds_high_rm", dict(view_steps=8, cloud_steps=24, cloud_light_rm=1), dict(cloud_steps=24)),
-        ("planet_atmosphere_clouds_high", dict(view_steps=12, cloud_steps=64, light_steps=8), dict(view_steps=12, light_mode="direct", light_steps=8)),
-        ("planet_atmosphere_clouds_high_rm", dict(view_steps=8, cloud_steps=64, cloud_light_rm=1, light_steps=3), dict(light_mode="direct", light_steps=3)),
-    ]
-    shader, ocfg, kw = variants[seed % len(variants)]
-    depth = S.depth_ground_sphere(cam, radius=params["u_planet_radius"]) if seed % 3 else S.depth_far(cam)
+    tex = RS.textures(seed)          # 24^3 and 48^3 shape volumes, a 17-texel cubemap face: no powers of two; every fifth seed without a cubemap
+    shader, ocfg, kw = RS.variant_of(seed)
+    depth = RS.near_depth(seed, cam, params["u_planet_radius"])
     ref_order = bool(__import__("os").environ.get("ATMO_FUZZ_PRECISE"))  # ATMO_FUZZ_PRECISE=1: atmo_set_precision 2, tighter bars below
     cloudy = "cloud_steps" in ocfg and tex["cubemap"] is not None
     # the cubemap sampler: the library's default (as declared: linear-mipmap, implicit LOD; the oracle gets the chain and cube_lod=1) and,
     # stated, level 0 only -- every cloud scene under both
-    for lod in ((None, False) if cloudy else (None,)):
-        node = PlanetAtmosphere(blue_noise=tex["blue_noise"], precise_atmosphere=ref_order, cubemap_lod=lod, **kw)
-        node.custom_shader = load_shader(shader)
-        node.planet_radius, node.atmosphere_height, node.sun_path = params["u_planet_radius"], params["u_atmosphere_height"], sun
-        for k, v in params.items():
-            if k not in ("u_planet_radius", "u_atmosphere_height", "u_cloud_coverage_rotation", "u_world_to_model_matrix"):
-                node.set(f"shader_params/{k}", v)
-        node._process(0.0, cam, time=0.0)
-        node.set_shader_parameter("u_cloud_coverage_rotation", np.asarray(params["u_cloud_coverage_rotation"], dtype=np.float32))
-        node.set_shader_parameter("u_cloud_shape_texture", tex["shape"])
-        if tex["cubemap"] is not None:
-            node.set_shader_parameter("u_cloud_coverage_cubemap", tex["cubemap"])
+    assert RS.samplers(seed, tex) == ((None, False) if cloudy else (None,))
+    for lod in RS.samplers(seed, tex):
+        node = RS.make_node(params, tex, sun, cam, shader, kw, lod, precise_atmosphere=ref_order)
         got = _gpu_render(node, cam, depth)
         declared = cloudy and lod is None
         assert bool(int(node.kernel_name.split("<")[1].split(",")[0]) & 32) == declared, node.kernel_name
         lut = node.read_optical_depth() if "light_steps" not in ocfg else None
         node.close()
-        # the node took the colours as the inspector holds them (sRGB) and converted them on upload (`source_color`);
-        # the oracle works on linear colours
-        oparams = dict(params, u_atmosphere_modulate=tuple(S.srgb_to_linear(params["u_atmosphere_modulate"]).tolist()),
-                       u_atmosphere_ambient_color=tuple(S.srgb_to_linear(params["u_atmosphere_ambient_color"]).tolist()))
-        otex = dict(tex, optical_depth=lut)
-        if declared:
-            otex["cubemap"] = oracle32.cubemap_mip_chain(tex["cubemap"])
-        want, hits = oracle32.render(oparams, otex, dict(ocfg, cube_lod=1) if declared else ocfg, make_frame(cam, np.eye(4), sun), depth, nthreads=8)
+        # (RS.oracle_render: the node took the colours as the inspector holds them (sRGB) and converted them on upload (`source_color`);
+        # the oracle works on linear colours)
+        want, hits = RS.oracle_render(oracle32, params, tex, ocfg, declared, lut, cam, sun, depth)
         assert np.array_equal(np.all(got == 0.0, axis=-1), np.all(want == 0.0, axis=-1))
         finite = np.isfinite(want)
         assert np.array_equal(np.isfinite(got), finite)
