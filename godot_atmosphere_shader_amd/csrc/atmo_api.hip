@@ -2200,7 +2200,7 @@ static bool mat4_inverse_d(const double *m, double *inv) {   // Gauss-Jordan wit
 // The proxy's per-draw constants (atmo::ProxyConsts, built in double and rounded once) and the launch: the pixel rectangle of the box's part between the
 // near and the far plane, grown by one pixel and cut to the frame's rect, and its tile grid.  `f` is the frame as the kernels see it (DOUBLE_PRECISION
 // applied).  A covered pixel's fragment lies on a front face between the planes: every front face is clipped against the two planes in clip space
-// (0 <= z <= w: reverse-Z, linear along an edge), the vertices left are projected to pixel centres (the prologue's uv = (p + 0.5) / size).  *tiles = 0: nothing
+// (0 <= z <= w: reverse-Z, linear along an edge) and against the sides of the frame's rect, the vertices left are projected to pixel centres (the prologue's uv = (p + 0.5) / size).  *tiles = 0: nothing
 // to draw (behind the camera, beyond the far plane, off the rect).  Launch origin as render_impl's: even under the declared sampler.
 static int proxy_setup(AtmoContext *ctx, const char *who, const AtmoFrame *f, const float *model_matrix, float box_size, bool lod,
                        atmo::ProxyConsts &pc, int rect[4], int *tiles_x, int *tiles_y) {
@@ -2249,8 +2249,22 @@ static int proxy_setup(AtmoContext *ctx, const char *who, const AtmoFrame *f, co
             for (int r = 0; r < 4; ++r) q[r] = pv[0 * 4 + r] * mp[0] + pv[1 * 4 + r] * mp[1] + pv[2 * 4 + r] * mp[2] + pv[3 * 4 + r];
             poly.push_back(q);
         }
-        for (int pl = 0; pl < 2 && !poly.empty(); ++pl) {
-            auto g = [pl](const std::array<double, 4> &q) { return pl == 0 ? q[2] : q[3] - q[2]; };
+        // ... and then by the four sides of the rect's pixel CENTRES, x0 .. x1 - 1 by y0 .. y1 - 1, a hundredth of a pixel wider for the rounding here (w > 0
+        // between the planes; a side x_pixel >= a is x - (2 (a + 0.5) / W - 1) w >= 0): a face that runs off the screen would otherwise widen the rectangle by
+        // the part of its outline that no pixel of the rect sees
+        const double side[4] = {2.0 * ((double)f->x0 + 0.49) / W - 1.0, 2.0 * ((double)f->x1 - 0.49) / W - 1.0,
+                                2.0 * ((double)f->y0 + 0.49) / H - 1.0, 2.0 * ((double)f->y1 - 0.49) / H - 1.0};
+        for (int pl = 0; pl < 6 && !poly.empty(); ++pl) {
+            auto g = [pl, &side](const std::array<double, 4> &q) {
+                switch (pl) {
+                case 0: return q[2];
+                case 1: return q[3] - q[2];
+                case 2: return q[0] - side[0] * q[3];
+                case 3: return side[1] * q[3] - q[0];
+                case 4: return q[1] - side[2] * q[3];
+                default: return side[3] * q[3] - q[1];
+                }
+            };
             next.clear();
             for (size_t i = 0; i < poly.size(); ++i) {
                 const std::array<double, 4> &A = poly[i], &B = poly[(i + 1) % poly.size()];

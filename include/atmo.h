@@ -73,7 +73,10 @@ enum AtmoMemory { ATMO_MEM_HOST = 0, ATMO_MEM_DEVICE = 1 };
  * x0=y0=0, x1=viewport_w, y1=viewport_h).
  */
 typedef struct AtmoFrame {
-    float inv_projection_matrix[16]; /* INV_PROJECTION_MATRIX: (SCREEN_UV*2-1, depth, 1) -> view space */
+    float inv_projection_matrix[16]; /* INV_PROJECTION_MATRIX: (SCREEN_UV*2-1, depth, 1) -> view space.  Used as given, whatever the projection
+                                        (off-axis, jittered, infinite far plane, orthographic): the ray is normalize() of the UNDIVIDED xyz of that
+                                        product (main:131-142), so the sign and the scale convention of the inverse matter, and an orthographic
+                                        matrix yields the reference's depth-dependent rays from the camera's position. */
     float inv_view_matrix[16];       /* INV_VIEW_MATRIX */
     int32_t viewport_w, viewport_h;  /* VIEWPORT_SIZE */
     float planet_center_viewspace[3];/* varying v_planet_center_viewspace (atmosphere_vertex, main:101-102) */

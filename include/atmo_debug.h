@@ -107,7 +107,7 @@ int atmo_get_host_wait_stats(AtmoContext *ctx, unsigned *device_syncs);
 int atmo_debug_create_host_only(int variant, int view_steps, int cloud_steps, int light_mode, int light_steps, AtmoContext **out);
 int atmo_debug_frame_constants(AtmoContext *ctx, const AtmoFrame *frame, int cube_n, float *out, int capacity, int *count);
 /* The launch a proxy draw (include/atmo_scene.h) of this context would make -- host geometry only, so it works on a host-only context: rect_out[4] =
- * x0, y0, x1, y1 of the pixels the launch covers (the box's part between the near and the far plane, projected, grown by one pixel and cut to the frame's
+ * x0, y0, x1, y1 of the pixels the launch covers (the box's part between the near and the far plane and inside the frame's rect, projected, grown by one pixel and cut to the frame's
  * rect; x0 == x1 when nothing is left), *tiles_out = the workgroup tiles of its grid (0: no launch). */
 int atmo_debug_proxy_launch_rect(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, int *rect_out, int *tiles_out);
 

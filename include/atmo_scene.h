@@ -15,9 +15,10 @@
  * atmo_render_composite shade them -- the same bits --, every other pixel stores nothing.  A covered pixel whose ray then misses the shell is a
  * discarded fragment (stored as (0,0,0,0) by atmo_render_proxy unless atmo_set_target_cleared; never by the composite).  A reference quirk kept:
  * the box's half-edge 0.9625 (R + H + near) is smaller than R + H unless near > 0.039 (R + H), so seen face-on from far away the box cuts the rim
- * of the halo.
+ * of the halo.  The proxy draws assume a reverse-Z projection (depth 1 on the near plane, 0 on the far plane; the far plane may lie at infinity, and
+ * the projection may be off-axis or orthographic); a forward-Z matrix, which atmo_render accepts, is not supported by the proxy draws.
  *
- * Launch: only the box's screen rectangle (its part between the planes, projected, grown by one pixel, cut to frame->x0..y1), row-major, no tile
+ * Launch: only the box's screen rectangle (its part between the planes that the rect sees, projected, grown by one pixel, cut to frame->x0..y1), row-major, no tile
  * order or feedback state; no launch at all when nothing of the box is left (behind the camera, beyond the far plane, off the rect) -- ATMO_OK.
  * Nothing is allocated: a draw can be captured into a HIP graph like atmo_render.  Stream rules are atmo_render's.  The frame, the textures, the
  * uniforms and DOUBLE_PRECISION (atmo_set_host_double_precision) are used as by atmo_render.
