@@ -617,20 +617,48 @@ const AtmoFrame *draw_frame(const AtmoContext *ctx, const AtmoFrame *frame, Atmo
     fixed.inv_view_matrix[14] *= -1.0f;
     return &fixed;
 }
-// The launch constants of a draw of `frame` (as draw_frame returns it): fill_consts, the composite's addressing, a float target's row pitch in pixels
-// (pitch_px > 0), a packed target (the KF_TARGET kernels address TargetConsts::pixels, rows pitch_bytes apart)
-void draw_consts(const AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, bool composite, int pitch_px, bool packed,
-                 atmo::RenderConsts &rc) {
-    fill_consts(ctx, frame, depth_dev, rgba_dev, rc);
-    if (composite) {  // the target is the whole scene colour buffer, addressed by absolute pixel
+// ---- what a draw reads and writes: the ONE description behind every draw path ----------------------------------------------------------------
+// The depth -- a float array, or a depth source in its own format (include/atmo_depth.h) -- and the colour output -- float4 pixels with a pitch in
+// pixels, or a packed target (include/atmo_target.h) --, and which of the three kernel kinds that makes.  An entry point builds it once (float_surfaces,
+// target_surfaces, depth_target_surfaces; view_draw per view of a batch); the caller's AtmoTarget / AtmoDepth travel in it unchecked until target_check
+// and check_surfaces have run.  A depth source has no form without a target: SURF_DEPTH reads tc as SURF_PACKED does.
+enum SurfaceKind { SURF_FLOAT, SURF_PACKED, SURF_DEPTH };   // the float kernels; their KF_TARGET twins; the KF_DEPTH | KF_TARGET twins (every target format)
+struct DrawSurfaces {
+    SurfaceKind kind = SURF_FLOAT;
+    bool composite = false;                    // the output is the whole scene colour buffer, addressed by absolute pixel
+    const float *depth = nullptr;              // SURF_FLOAT, SURF_PACKED: the viewport's depth, floats
+    const AtmoDepth *depth_source = nullptr;   // SURF_DEPTH: the caller's, unchecked -- check_surfaces -> dc
+    const AtmoTarget *target = nullptr;        // target draws: the caller's, unchecked -- target_check -> kind, pixels, pitch_px, tc
+    void *pixels = nullptr;                    // as the single draw's: plain -- the rect's first pixel; composite -- the viewport's
+    int pitch_px = 0;                          // SURF_FLOAT: pixels from one row to the next, 0 = the draw's own (tight)
+    atmo::TargetConsts tc = {nullptr, 0, 0};   // SURF_PACKED, SURF_DEPTH
+    atmo::DepthConsts dc = {nullptr, 0, 0};    // SURF_DEPTH
+};
+DrawSurfaces float_surfaces(const float *depth_dev, float *rgba_dev, bool composite) { return {SURF_FLOAT, composite, depth_dev, nullptr, nullptr, rgba_dev}; }
+DrawSurfaces target_surfaces(const float *depth_dev, const AtmoTarget *target, bool composite) { return {SURF_FLOAT, composite, depth_dev, nullptr, target}; }
+DrawSurfaces depth_target_surfaces(const AtmoDepth *depth, const AtmoTarget *target, bool composite) { return {SURF_DEPTH, composite, nullptr, depth, target}; }
+// The depth's check of a draw of `frame`: the depth source's (into sf.dc), or the float draws' null and alignment checks
+int check_surfaces(AtmoContext *ctx, const std::string &who, const AtmoFrame *frame, DrawSurfaces &sf) {
+    if (sf.kind == SURF_DEPTH) return depth_check(ctx, who, sf.depth_source, frame->viewport_w, frame->viewport_h, &sf.dc);
+    return check_draw_pointers(ctx, who, sf.depth, (const float *)sf.pixels, sf.kind == SURF_FLOAT);
+}
+// The entry point's own family bits, as finish_draw and ViewsLayout::family carry them
+int surface_family_bits(SurfaceKind kind) {
+    return kind == SURF_DEPTH ? atmo::KF_TARGET | atmo::KF_DEPTH : kind == SURF_PACKED ? atmo::KF_TARGET : 0;
+}
+// The launch constants of a draw of `frame` (as draw_frame returns it): fill_consts, the composite's addressing, a float target's row pitch in pixels,
+// a packed target (the KF_TARGET kernels address TargetConsts::pixels, rows pitch_bytes apart)
+void draw_consts(const AtmoContext *ctx, const AtmoFrame *frame, const DrawSurfaces &sf, atmo::RenderConsts &rc) {
+    fill_consts(ctx, frame, sf.depth, (float *)sf.pixels, rc);
+    if (sf.composite) {  // the target is the whole scene colour buffer, addressed by absolute pixel
         rc.out_pitch = frame->viewport_w;
         rc.out_x0 = 0;
         rc.out_y0 = 0;
         rc.composite = 1;
         rc.store_discards = 0;
     }
-    if (pitch_px > 0) rc.out_pitch = pitch_px;
-    if (packed) rc.out = nullptr;
+    if (sf.pitch_px > 0) rc.out_pitch = sf.pitch_px;
+    if (sf.kind != SURF_FLOAT) rc.out = nullptr;
 }
 // The kernel family and launch shape of a draw (launch_shape), refused where the context demands a sampler it cannot have; under the declared sampler
 // (*lod) the launch grid starts on an even pixel: draw_grid_origin
@@ -1512,18 +1540,21 @@ int atmo_read_optical_depth(AtmoContext *ctx, float *lut_host, uint8_t *rgba8_ho
     return ATMO_OK;
 }
 
-// tc != nullptr: a packed colour target (atmo_render_target): rgba_dev is its pixels (checked by the caller), the launches are the KF_TARGET kernels';
-// pitch_px > 0: pixels per output row (an RGBA32F target with a pitch)
-static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream, bool composite,
-                       const uint32_t *tiles_dev = nullptr, int n_tiles = 0, int n_heavy = 0, const atmo::TargetConsts *tc = nullptr, int pitch_px = 0,
-                       bool depth_source = false, const AtmoDepth *depth = nullptr);
+// atmo_render_tiles[_split]: the caller's tile list -- n tiles of the rect's grid, the leading n_heavy of them on two lanes per ray; dev == nullptr: the whole grid
+struct TileList {
+    const uint32_t *dev;
+    int n, n_heavy;
+};
+static constexpr TileList WHOLE_GRID = {nullptr, 0, 0};
+// sf: the entry point's (a target's already through target_check, which the caller runs; the depth is checked here, behind the empty rect)
+static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, DrawSurfaces sf, TileList tiles, void *stream);
 
 int atmo_render(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream) {
-    return render_impl(ctx, frame, depth_dev, rgba_dev, stream, false);
+    return render_impl(ctx, frame, float_surfaces(depth_dev, rgba_dev, false), WHOLE_GRID, stream);
 }
 
 int atmo_render_composite(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *scene_rgba_dev, void *stream) {
-    return render_impl(ctx, frame, depth_dev, scene_rgba_dev, stream, true);
+    return render_impl(ctx, frame, float_surfaces(depth_dev, scene_rgba_dev, true), WHOLE_GRID, stream);
 }
 
 // The geometric tile order of a cloudless frame seen from outside the atmosphere shell (rc.miss_k > 0: the projection's ray directions do not depend on depth and
@@ -1605,7 +1636,7 @@ int atmo_render_tiles(AtmoContext *ctx, const AtmoFrame *frame, const float *dep
     if (!ctx) return ATMO_E_ARG;
     if (n_tiles < 0 || (n_tiles > 0 && !tiles_dev)) return fail(ctx, ATMO_E_ARG, "atmo_render_tiles: bad tile list");
     if (n_tiles == 0) return ATMO_OK;  // an empty share of the frame: nothing to shade
-    return render_impl(ctx, frame, depth_dev, rgba_dev, stream, false, tiles_dev, n_tiles);
+    return render_impl(ctx, frame, float_surfaces(depth_dev, rgba_dev, false), {tiles_dev, n_tiles, 0}, stream);
 }
 
 int atmo_render_tiles_split(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, const uint32_t *tiles_dev, int n_tiles,
@@ -1613,7 +1644,7 @@ int atmo_render_tiles_split(AtmoContext *ctx, const AtmoFrame *frame, const floa
     if (!ctx) return ATMO_E_ARG;
     if (n_tiles < 0 || (n_tiles > 0 && !tiles_dev) || n_heavy < 0 || n_heavy > n_tiles) return fail(ctx, ATMO_E_ARG, "atmo_render_tiles_split: bad tile list");
     if (n_tiles == 0) return ATMO_OK;
-    return render_impl(ctx, frame, depth_dev, rgba_dev, stream, false, tiles_dev, n_tiles, n_heavy);
+    return render_impl(ctx, frame, float_surfaces(depth_dev, rgba_dev, false), {tiles_dev, n_tiles, n_heavy}, stream);
 }
 
 int atmo_measure_tile_costs(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream,
@@ -1654,7 +1685,7 @@ int atmo_measure_tile_costs(AtmoContext *ctx, const AtmoFrame *frame, const floa
     if (e != hipSuccess) rc = hip_fail(ctx, e, "hipMemsetAsync");
     if (rc == ATMO_OK) {
         ctx->measure_cost = d;  // render_impl: record into this buffer, row-major order, no feedback bookkeeping
-        rc = render_impl(ctx, frame, depth_dev, rgba_dev, stream, false);
+        rc = render_impl(ctx, frame, float_surfaces(depth_dev, rgba_dev, false), WHOLE_GRID, stream);
         ctx->measure_cost = nullptr;
     }
     if (rc == ATMO_OK) {
@@ -1710,11 +1741,32 @@ static int finish_draw(AtmoContext *ctx, hipStream_t s, int family, int split, b
     return note_draw_stream(ctx, s, marker);
 }
 
-// A launch of a single draw: the float kernels, or (tc) their packed-target twins
-static hipError_t launch_draw(const atmo::TargetConsts *tc, int flags, int split, const atmo::RenderConsts &rc, hipStream_t s, int blocks,
-                              const atmo::DepthConsts *dc = nullptr) {   // dc (with tc): the depth-source twins of those (include/atmo_depth.h)
-    if (dc) return tc ? atmo::launch_render_depth_target(flags, split, rc, *tc, *dc, s, blocks) : hipErrorInvalidValue;
-    return tc ? atmo::launch_render_target(flags, split, rc, *tc, s, blocks) : atmo::launch_render(flags, split, rc, s, blocks);
+// ---- the surfaces' kind decides the launcher: one function per launch shape ----------------------------------------------------------------
+// A single draw over its tile grid (blocks > 0: rc.tile_order lists that many tiles)
+static hipError_t launch_draw(const DrawSurfaces &sf, int flags, int split, const atmo::RenderConsts &rc, hipStream_t s, int blocks) {
+    return sf.kind == SURF_DEPTH    ? atmo::launch_render_depth_target(flags, split, rc, sf.tc, sf.dc, s, blocks)
+           : sf.kind == SURF_PACKED ? atmo::launch_render_target(flags, split, rc, sf.tc, s, blocks)
+                                    : atmo::launch_render(flags, split, rc, s, blocks);
+}
+// A single proxy draw over its cut rectangle
+static hipError_t launch_proxy(const DrawSurfaces &sf, int flags, const atmo::RenderConsts &rc, const atmo::ProxyConsts &pc, hipStream_t s) {
+    return sf.kind == SURF_DEPTH    ? atmo::launch_render_proxy_depth_target(flags, rc, pc, sf.tc, sf.dc, s)
+           : sf.kind == SURF_PACKED ? atmo::launch_render_proxy_target(flags, rc, pc, sf.tc, s)
+                                    : atmo::launch_render_proxy(flags, rc, pc, s);
+}
+// A view batch (vtc.target is read by the packed kernels only, vdc by the depth-source kernels only)
+static hipError_t launch_views(SurfaceKind kind, int flags, int light_steps, const atmo::RenderConsts *table_dev, const atmo::ViewsTargetConsts &vtc,
+                               const atmo::ViewsDepthConsts &vdc, hipStream_t s) {
+    return kind == SURF_DEPTH    ? atmo::launch_render_views_depth_target(flags, light_steps, table_dev, vtc, vdc, s)
+           : kind == SURF_PACKED ? atmo::launch_render_views_target(flags, light_steps, table_dev, vtc, s)
+                                 : atmo::launch_render_views(flags, light_steps, table_dev, vtc.v, s);
+}
+// ... and a proxy batch
+static hipError_t launch_views_proxy(SurfaceKind kind, int flags, int light_steps, const atmo::RenderConsts *table_dev,
+                                     const atmo::ViewsProxyTargetConsts &vptc, const atmo::ViewsDepthConsts &vdc, hipStream_t s) {
+    return kind == SURF_DEPTH    ? atmo::launch_render_views_proxy_depth_target(flags, light_steps, table_dev, vptc, vdc, s)
+           : kind == SURF_PACKED ? atmo::launch_render_views_proxy_target(flags, light_steps, table_dev, vptc, s)
+                                 : atmo::launch_render_views_proxy(flags, light_steps, table_dev, vptc.p, s);
 }
 
 // A single draw's feedback state (null where feedback_state leaves it null) with the camera's motion taken in and the pending sort polled
@@ -1779,17 +1831,17 @@ static int bound_tile_list(AtmoContext *ctx, const AtmoFrame *frame, atmo::Rende
 // 1280x720 -28 %, from the limb -42..-44 % at 1280x720 and 1920x1080, the night side -33 % -- and costs 9 % where the draw is bound by
 // throughput (1920x1080 pose P_space, where the lane-split kernel on EVERY tile is 43 % slower; 3840x2160), which the trigger keeps out;
 // the kernel without raymarched light never gains (its heaviest wave is a fifth as long): not split unless forced (ATMO_HEAVY_SPLIT=2).
-static int launch_heavy_split(AtmoContext *ctx, const atmo::TargetConsts *tc, int flags, int split, atmo::RenderConsts &rc, hipStream_t s,
-                              const uint32_t *order2, int heavy, int total_tiles, const atmo::DepthConsts *dc = nullptr) {
+static int launch_heavy_split(AtmoContext *ctx, const DrawSurfaces &sf, int flags, int split, atmo::RenderConsts &rc, hipStream_t s,
+                              const uint32_t *order2, int heavy, int total_tiles) {
     if (!ctx->split_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->split_stream, hipStreamNonBlocking));
     ATMO_TRY(order_after_stream(ctx, ctx->split_stream, s));   // fork: behind everything the draw is behind
     atmo::RenderConsts rc2 = rc;
     rc2.tile_order = order2;                       // two half-height tiles per heavy tile, heaviest first
     rc2.cost_rows_halved = 1;                      // ... whose costs belong to the one-lane grid's tile (only this launch: ADVICE r5)
-    HIP_TRY(ctx, launch_draw(tc, flags, 2, rc2, ctx->split_stream, 2 * heavy, dc));
+    HIP_TRY(ctx, launch_draw(sf, flags, 2, rc2, ctx->split_stream, 2 * heavy));
     if (total_tiles - heavy > 0) {
         rc.tile_order += heavy;                    // the rest of the order, one lane per ray
-        HIP_TRY(ctx, launch_draw(tc, flags, split, rc, s, total_tiles - heavy, dc));
+        HIP_TRY(ctx, launch_draw(sf, flags, split, rc, s, total_tiles - heavy));
     }
     ATMO_TRY(order_after_stream(ctx, s, ctx->split_stream));   // join
     ctx->split_draws += 1;
@@ -1797,22 +1849,13 @@ static int launch_heavy_split(AtmoContext *ctx, const atmo::TargetConsts *tc, in
     return ATMO_OK;
 }
 
-static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream, bool composite,
-                       const uint32_t *tiles_dev, int n_tiles, int n_heavy, const atmo::TargetConsts *tc, int pitch_px, bool depth_source,
-                       const AtmoDepth *depth) {   // depth_source: atmo_render_depth_target -- `depth` in place of depth_dev, tc set for every format
-    // 1. checks
+static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, DrawSurfaces sf, TileList tiles, void *stream) {
+    // 1. checks (every message but the depth source's says atmo_render, whichever sibling called)
     if (!ctx) return ATMO_E_ARG;
     bool empty = false;
     ATMO_TRY(check_frame(ctx, "atmo_render", frame, &empty));
     if (empty) return ATMO_OK;  // empty rect: nothing to shade
-    atmo::DepthConsts depth_consts = {nullptr, 0, 0};
-    const atmo::DepthConsts *dc = nullptr;
-    if (depth_source) {
-        ATMO_TRY(depth_check(ctx, "atmo_render_depth_target", depth, frame->viewport_w, frame->viewport_h, &depth_consts));
-        dc = &depth_consts;
-    } else {
-        ATMO_TRY(check_draw_pointers(ctx, "atmo_render", depth_dev, rgba_dev, !tc));
-    }
+    ATMO_TRY(check_surfaces(ctx, sf.kind == SURF_DEPTH ? "atmo_render_depth_target" : "atmo_render", frame, sf));
     ATMO_TRY(check_draw_textures(ctx, "atmo_render"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
@@ -1820,7 +1863,7 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
     atmo::RenderConsts rc;
     AtmoFrame fixed;
     frame = draw_frame(ctx, frame, fixed);
-    draw_consts(ctx, frame, depth_dev, rgba_dev, composite, pitch_px, tc != nullptr, rc);
+    draw_consts(ctx, frame, sf, rc);
     hipStream_t s = (hipStream_t)stream;
     ATMO_TRY(tex_order(ctx, s));  // texture updated on another stream
 
@@ -1840,7 +1883,7 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
     // default (-1): on for every variant since the sort no longer costs the draws anything (profiles/round2/ab_tile_feedback.txt)
     bool feedback = ctx->env_feedback >= 0 ? ctx->env_feedback != 0 : ctx->tile_feedback != 0;
     if (ctx->measure_cost) feedback = false;  // a measuring draw: plain row-major launch that records into the caller's buffer
-    if (tiles_dev) feedback = false;          // a tile-list draw: the caller's order
+    if (tiles.dev) feedback = false;          // a tile-list draw: the caller's order
     if (feedback && (long long)gx * gy < 512) feedback = false;  // tiny launches: nothing to schedule
     const bool geo_policy = feedback;   // (also inside a graph capture: the geometric order enqueues nothing of its own)
     if (feedback && stream_is_capturing(s)) feedback = false;  // no side-stream work inside a graph
@@ -1887,29 +1930,29 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *de
     // the bounded copy of a tile list lives in a context-owned buffer that a later, longer list frees and reallocates -- a graph that had
     // recorded this draw would replay on freed memory (and an allocation fails inside a global-mode capture anyway): refused, stated in atmo.h
     // (before anything is created or enqueued for this draw)
-    if (tiles_dev && stream_is_capturing(s))
+    if (tiles.dev && stream_is_capturing(s))
         return fail(ctx, ATMO_E_STATE, "tile-list draws cannot be captured into a HIP graph (context-owned list buffer); capture atmo_render instead");
     ATMO_TRY(timing_open(ctx, timing));
     ATMO_TRY(timing_begin(ctx, timing, s));
 
     // 7. tile-list bounding
-    if (tiles_dev) ATMO_TRY(bound_tile_list(ctx, frame, rc, s, flags, split, gx, gy, tiles_dev, n_tiles, &n_heavy, &order2));
+    if (tiles.dev) ATMO_TRY(bound_tile_list(ctx, frame, rc, s, flags, split, gx, gy, tiles.dev, tiles.n, &tiles.n_heavy, &order2));
 
     // 8. launch: plain, or the heavy tiles on two lanes per ray beside the rest (launch_heavy_split)
     int heavy = 0;
-    if (ctx->heavy_split && order2 && class_totals && rc.tile_order && !tiles_dev && split == 1 && two_lane_form(ctx, flags))
+    if (ctx->heavy_split && order2 && class_totals && rc.tile_order && !tiles.dev && split == 1 && two_lane_form(ctx, flags))
         heavy = heavy_tile_count(class_totals, gx * gy, ctx->heavy_split_ratio,
                                  ctx->heavy_split == 2 ? 0.0f : (plan.sort_instream ? ctx->heavy_split_trigger_moving : ctx->heavy_split_trigger),
                                  1024 * 6);   // both declared-sampler cloud kernels hold six waves per SIMD
-    if (tiles_dev) heavy = n_heavy;   // a tile-list draw: the caller says how many of its leading tiles are heavy (atmo_render_tiles_split)
-    if (heavy > 0) ATMO_TRY(launch_heavy_split(ctx, tc, flags, split, rc, s, order2, heavy, tiles_dev ? n_tiles : gx * gy, dc));
-    else HIP_TRY(ctx, launch_draw(tc, launch_flags, split, rc, s, tiles_dev ? n_tiles : 0, dc));
+    if (tiles.dev) heavy = tiles.n_heavy;   // a tile-list draw: the caller says how many of its leading tiles are heavy (atmo_render_tiles_split)
+    if (heavy > 0) ATMO_TRY(launch_heavy_split(ctx, sf, flags, split, rc, s, order2, heavy, tiles.dev ? tiles.n : gx * gy));
+    else HIP_TRY(ctx, launch_draw(sf, launch_flags, split, rc, s, tiles.dev ? tiles.n : 0));
 
     // 9. sorts, 10. bookkeeping
     if (plan.sort_side) ATMO_TRY(feedback_sort_side(ctx, *fb, gx, gy, plan, s));
     if (fb) fb->n += 1;
     hipEvent_t marker = nullptr;   // the draw stream's marker, when this draw recorded one (re-recorded behind the in-stream sort below)
-    ATMO_TRY(finish_draw(ctx, s, tc ? (flags | atmo::KF_TARGET | (dc ? atmo::KF_DEPTH : 0)) : flags, split, true, &marker));   // (atmo_kernel_name: the family without KF_GEO)
+    ATMO_TRY(finish_draw(ctx, s, flags | surface_family_bits(sf.kind), split, true, &marker));   // (atmo_kernel_name: the family without KF_GEO)
     ATMO_TRY(timing_end(ctx, timing, s));
     if (plan.sort_instream) {  // behind the draw (and behind the timing bracket, which is the draw kernel's alone)
         ATMO_TRY(feedback_sort(ctx, *fb, 2, gx, gy, plan.dil_rx, plan.dil_ry, s, fb->is_scratch));
@@ -2326,20 +2369,15 @@ static void proxy_cut_rect(const int *rect, bool lod, int gx, atmo::RenderConsts
     rc.tiles_x = gx;
 }
 
-static int proxy_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev, float *rgba_dev,
-                      void *stream, bool composite, const atmo::TargetConsts *tc = nullptr, int pitch_px = 0, bool depth_source = false,
-                      const AtmoDepth *depth = nullptr) {   // tc, pitch_px, depth_source, depth: as render_impl's
+// who: the entry point, as its messages name it; sf: as render_impl's
+static int proxy_impl(AtmoContext *ctx, const char *who, const AtmoFrame *frame, const float *model_matrix, float box_size, DrawSurfaces sf, void *stream) {
     if (!ctx) return ATMO_E_ARG;
-    const char *who = depth_source ? "atmo_render_proxy_depth_target"
-                                   : (tc || pitch_px) ? "atmo_render_proxy_target" : composite ? "atmo_render_proxy_composite" : "atmo_render_proxy";
     if (!frame || !model_matrix) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null frame or model_matrix");
     if (!(box_size > 0.0f) || !std::isfinite(box_size)) return fail(ctx, ATMO_E_ARG, std::string(who) + ": box_size must be positive and finite");
     bool empty = false;
     ATMO_TRY(check_frame(ctx, who, frame, &empty));
     // (unlike render_impl, the pointers, the textures and the mode are checked in front of the empty rect's ATMO_OK)
-    atmo::DepthConsts dc = {nullptr, 0, 0};
-    if (depth_source) ATMO_TRY(depth_check(ctx, who, depth, frame->viewport_w, frame->viewport_h, &dc));
-    else ATMO_TRY(check_draw_pointers(ctx, who, depth_dev, rgba_dev, !tc));
+    ATMO_TRY(check_surfaces(ctx, who, frame, sf));
     ATMO_TRY(check_draw_textures(ctx, who));
     int flags = 0;
     bool lod = false;
@@ -2353,25 +2391,23 @@ static int proxy_impl(AtmoContext *ctx, const AtmoFrame *frame, const float *mod
     if (gx == 0 || gy == 0) return ATMO_OK;   // nothing of the box is on this rect between the planes: no launch
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     atmo::RenderConsts rc;
-    draw_consts(ctx, frame, depth_dev, rgba_dev, composite, pitch_px, tc != nullptr, rc);   // the output stays addressed by the FRAME's rect (plain) or the viewport (composite)
+    draw_consts(ctx, frame, sf, rc);   // the output stays addressed by the FRAME's rect (plain) or the viewport (composite)
     proxy_cut_rect(rect, lod, gx, rc);
     hipStream_t s = (hipStream_t)stream;
     ATMO_TRY(tex_order(ctx, s));
-    if (depth_source) HIP_TRY(ctx, tc ? atmo::launch_render_proxy_depth_target(flags, rc, pc, *tc, dc, s) : hipErrorInvalidValue);
-    else if (tc) HIP_TRY(ctx, atmo::launch_render_proxy_target(flags, rc, pc, *tc, s));
-    else HIP_TRY(ctx, atmo::launch_render_proxy(flags, rc, pc, s));
+    HIP_TRY(ctx, launch_proxy(sf, flags, rc, pc, s));
     hipEvent_t marker = nullptr;
-    return finish_draw(ctx, s, flags | atmo::KF_PROXY | (tc ? atmo::KF_TARGET : 0) | (depth_source ? atmo::KF_DEPTH : 0), 1, false, &marker);
+    return finish_draw(ctx, s, flags | atmo::KF_PROXY | surface_family_bits(sf.kind), 1, false, &marker);
 }
 
 int atmo_render_proxy(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev, float *rgba_dev,
                       void *stream) {
-    return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, rgba_dev, stream, false);
+    return proxy_impl(ctx, "atmo_render_proxy", frame, model_matrix, box_size, float_surfaces(depth_dev, rgba_dev, false), stream);
 }
 
 int atmo_render_proxy_composite(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev,
                                 float *scene_rgba_dev, void *stream) {
-    return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, scene_rgba_dev, stream, true);
+    return proxy_impl(ctx, "atmo_render_proxy_composite", frame, model_matrix, box_size, float_surfaces(depth_dev, scene_rgba_dev, true), stream);
 }
 
 // ---- packed colour targets (include/atmo_target.h) ----------------------------------------------------------------------------------------
@@ -2396,9 +2432,13 @@ int atmo_target_pixel_bytes(int format) {
     }
 }
 
-// The argument checks of both target draws (everything that needs no device, in front of everything that does): on success *pitch_out = the row pitch
-// in bytes (the tight pitch for row_pitch_bytes == 0).
-static int target_check(AtmoContext *ctx, const char *who, const AtmoFrame *frame, const AtmoTarget *target, bool composite, int *pitch_out) {
+// The argument checks of every target draw (everything that needs no device, in front of everything that does) on sf.target.  On success sf holds the
+// checked output: its pixels, TargetConsts with the row pitch in bytes in effect (the tight pitch for row_pitch_bytes == 0), and -- unless a depth source
+// has made it SURF_DEPTH -- its kind: RGBA32F is drawn by the float kernels themselves (a pitch in whole pixels is all they need), every other format
+// by the packed ones.
+static int target_check(AtmoContext *ctx, const char *who, const AtmoFrame *frame, DrawSurfaces &sf) {
+    const AtmoTarget *target = sf.target;
+    const bool composite = sf.composite;
     if (!frame) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null frame");
     if (!target) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null target");
     const int px = atmo_target_pixel_bytes(target->format);
@@ -2414,13 +2454,16 @@ static int target_check(AtmoContext *ctx, const char *who, const AtmoFrame *fram
     if (pitch < row_bytes || pitch % px != 0)
         return fail(ctx, ATMO_E_ARG, std::string(who) + ": row_pitch_bytes must be 0, or at least the row's bytes (" + std::to_string(row_bytes) +
                                          ") and a multiple of the pixel size (" + std::to_string(px) + ")");
-    *pitch_out = (int)pitch;   // (row_bytes <= 65536 * 16 and pitch is an int32: no overflow)
+    sf.pixels = target->pixels;
+    sf.tc = {target->pixels, (int32_t)pitch, target->format};   // (row_bytes <= 65536 * 16 and pitch is an int32: no overflow)
+    if (sf.kind != SURF_DEPTH) sf.kind = target->format == ATMO_TARGET_RGBA32F ? SURF_FLOAT : SURF_PACKED;
+    sf.pitch_px = sf.kind == SURF_FLOAT ? (int)pitch / 16 : 0;
     return ATMO_OK;
 }
 
 // The packed formats are drawn by the default forms' kernels only (target_family_supported); RGBA32F by the float kernels, whatever the mode.
 // depth_source: the caller is atmo_render_depth_target, whose kernels draw RGBA32F too -- no target format works in another mode there.
-static int target_family(AtmoContext *ctx, const char *who, const AtmoFrame *frame, bool depth_source = false) {
+static int target_family(AtmoContext *ctx, const char *who, const AtmoFrame *frame, bool depth_source) {
     int flags = 0, split = 1;
     launch_shape(ctx, frame, &flags, &split, nullptr);
     if (!atmo::target_family_supported(flags, split)) {
@@ -2435,24 +2478,21 @@ static int target_family(AtmoContext *ctx, const char *who, const AtmoFrame *fra
 
 int atmo_render_target(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, const AtmoTarget *target, int composite, void *stream) {
     if (!ctx) return ATMO_E_ARG;
-    int pitch = 0;
-    ATMO_TRY(target_check(ctx, "atmo_render_target", frame, target, composite != 0, &pitch));
-    if (target->format == ATMO_TARGET_RGBA32F)   // the float kernels themselves: a pitch in whole pixels is all they need
-        return render_impl(ctx, frame, depth_dev, (float *)target->pixels, stream, composite != 0, nullptr, 0, 0, nullptr, pitch / 16);
-    ATMO_TRY(target_family(ctx, "atmo_render_target", frame));
-    const atmo::TargetConsts tc = {target->pixels, pitch, target->format};
-    return render_impl(ctx, frame, depth_dev, (float *)target->pixels, stream, composite != 0, nullptr, 0, 0, &tc, 0);
+    DrawSurfaces sf = target_surfaces(depth_dev, target, composite != 0);
+    ATMO_TRY(target_check(ctx, "atmo_render_target", frame, sf));
+    if (sf.kind == SURF_PACKED) ATMO_TRY(target_family(ctx, "atmo_render_target", frame, false));
+    return render_impl(ctx, frame, sf, WHOLE_GRID, stream);
 }
 
 int atmo_render_proxy_target(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const float *depth_dev,
                              const AtmoTarget *target, int composite, void *stream) {
     if (!ctx) return ATMO_E_ARG;
-    int pitch = 0;
-    ATMO_TRY(target_check(ctx, "atmo_render_proxy_target", frame, target, composite != 0, &pitch));
-    if (target->format == ATMO_TARGET_RGBA32F)
-        return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, (float *)target->pixels, stream, composite != 0, nullptr, pitch / 16);
-    const atmo::TargetConsts tc = {target->pixels, pitch, target->format};   // (proxy_impl refuses the modes without a proxy kernel: the same set)
-    return proxy_impl(ctx, frame, model_matrix, box_size, depth_dev, (float *)target->pixels, stream, composite != 0, &tc, 0);
+    DrawSurfaces sf = target_surfaces(depth_dev, target, composite != 0);
+    ATMO_TRY(target_check(ctx, "atmo_render_proxy_target", frame, sf));
+    // (proxy_impl refuses the modes without a proxy kernel: the same set as the packed kernels'.)  An RGBA32F target whose row has no byte -- a rect
+    // without a column, plain, tight -- has always been named as the float draw it is handed on as: kept, the messages are the interface's
+    const char *who = (sf.kind == SURF_PACKED || sf.pitch_px) ? "atmo_render_proxy_target" : composite ? "atmo_render_proxy_composite" : "atmo_render_proxy";
+    return proxy_impl(ctx, who, frame, model_matrix, box_size, sf, stream);
 }
 
 // ---- depth sources (include/atmo_depth.h): the two draws above with the depth buffer in its own format and pitch ------------------------------
@@ -2461,20 +2501,18 @@ int atmo_depth_texel_bytes(int format) { return atmo::depth_texel_bytes(format);
 
 int atmo_render_depth_target(AtmoContext *ctx, const AtmoFrame *frame, const AtmoDepth *depth, const AtmoTarget *target, int composite, void *stream) {
     if (!ctx) return ATMO_E_ARG;
-    int pitch = 0;
-    ATMO_TRY(target_check(ctx, "atmo_render_depth_target", frame, target, composite != 0, &pitch));
+    DrawSurfaces sf = depth_target_surfaces(depth, target, composite != 0);
+    ATMO_TRY(target_check(ctx, "atmo_render_depth_target", frame, sf));
     ATMO_TRY(target_family(ctx, "atmo_render_depth_target", frame, true));
-    const atmo::TargetConsts tc = {target->pixels, pitch, target->format};
-    return render_impl(ctx, frame, nullptr, (float *)target->pixels, stream, composite != 0, nullptr, 0, 0, &tc, 0, true, depth);
+    return render_impl(ctx, frame, sf, WHOLE_GRID, stream);
 }
 
 int atmo_render_proxy_depth_target(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const AtmoDepth *depth,
                                    const AtmoTarget *target, int composite, void *stream) {
     if (!ctx) return ATMO_E_ARG;
-    int pitch = 0;
-    ATMO_TRY(target_check(ctx, "atmo_render_proxy_depth_target", frame, target, composite != 0, &pitch));
-    const atmo::TargetConsts tc = {target->pixels, pitch, target->format};   // (proxy_impl refuses the modes without a proxy kernel: the same set)
-    return proxy_impl(ctx, frame, model_matrix, box_size, nullptr, (float *)target->pixels, stream, composite != 0, &tc, 0, true, depth);
+    DrawSurfaces sf = depth_target_surfaces(depth, target, composite != 0);
+    ATMO_TRY(target_check(ctx, "atmo_render_proxy_depth_target", frame, sf));   // (proxy_impl refuses the modes without a proxy kernel: the same set)
+    return proxy_impl(ctx, "atmo_render_proxy_depth_target", frame, model_matrix, box_size, sf, stream);
 }
 
 // atmo_debug.h: the kernels' depth decode on a caller-supplied DEVICE array
@@ -2532,28 +2570,29 @@ struct ViewsLayout {
     uint32_t first_block[ATMO_MAX_VIEWS + 1];      // prefix of gx * gy; entries behind n_views repeat the total
 };
 
-// What a batch entry point hands on about one view, whichever structure it came in (AtmoView, AtmoViewTarget).
-struct ViewArg {
+// What a batch entry point hands on about one view: its frame and the single draw's description of what it reads and writes -- each public view
+// structure reduces to it (the target's and the depth source's still unchecked: views_target_outputs)
+struct ViewDraw {
     const AtmoFrame *frame = nullptr;
-    const float *depth = nullptr;
-    void *pixels = nullptr;                 // as the single draw's: plain -- the rect's first pixel; composite -- the viewport's
-    int pitch_px = 0;                       // float targets: pixels from one row to the next, 0 = the draw's own (tight)
-    atmo::TargetConsts tc = {nullptr, 0, 0};   // packed targets (RGBA16F / RGBA8_UNORM)
-    atmo::DepthConsts dc = {nullptr, 0, 0};    // depth-source batches (include/atmo_depth.h): in place of `depth`, and tc for every target format
+    DrawSurfaces sf;
 };
-
-// The float batches' views (AtmoView) as ViewArg: frame, depth and output; no pitch, no packed target.  Null views or a bad count: views_check_frames' to refuse.
-void view_args(const AtmoView *views, int n_views, ViewArg *args) {
-    for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) {
-        args[i].frame = &views[i].frame;
-        args[i].depth = views[i].depth_dev;
-        args[i].pixels = views[i].rgba_dev;
+extern "C++" {   // (overloads and a template: not for the C linkage block this stands in)
+ViewDraw view_draw(const AtmoView &v, bool composite) { return {&v.frame, float_surfaces(v.depth_dev, v.rgba_dev, composite)}; }
+ViewDraw view_draw(const AtmoViewTarget &v, bool composite) { return {&v.frame, target_surfaces(v.depth_dev, &v.target, composite)}; }
+ViewDraw view_draw(const AtmoViewDepthTarget &v, bool composite) { return {&v.frame, depth_target_surfaces(&v.depth, &v.target, composite)}; }
+// A batch's views, whichever structure they came in.  Null views or a bad count: views_check_frames' to refuse.
+template <class View>
+struct ViewDraws {
+    ViewDraw v[ATMO_MAX_VIEWS];
+    ViewDraws(const View *views, int n_views, int composite) {
+        for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) v[i] = view_draw(views[i], composite != 0);
     }
+};
 }
 
 // The first half of what a batch needs no device for: the count and every view's frame checks.  *done: n_views == 0, nothing to draw whatever the
 // context's mode.
-int views_check_frames(AtmoContext *ctx, const char *who, bool have_views, const ViewArg *args, int n_views, ViewsLayout &L, bool *done) {
+int views_check_frames(AtmoContext *ctx, const char *who, bool have_views, const ViewDraw *args, int n_views, ViewsLayout &L, bool *done) {
     *done = false;
     if (n_views < 0 || n_views > ATMO_MAX_VIEWS)
         return fail(ctx, ATMO_E_ARG, std::string(who) + ": n_views must be 0 .. " + std::to_string(ATMO_MAX_VIEWS));
@@ -2569,14 +2608,14 @@ int views_check_frames(AtmoContext *ctx, const char *who, bool have_views, const
     }
     return ATMO_OK;
 }
-// The second half: the family (ATMO_E_STATE where no multi-view kernel exists; `packed`: the KF_VIEWS | KF_TARGET kernels) and the concatenated launch.
-int views_family_grid(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, bool packed, ViewsLayout &L) {
+// The second half: the family (ATMO_E_STATE where no multi-view kernel exists; `kind`: the batch's surfaces) and the concatenated launch.
+int views_family_grid(AtmoContext *ctx, const char *who, const ViewDraw *args, int n_views, SurfaceKind kind, ViewsLayout &L) {
     int split = 1;
     ATMO_TRY(draw_family(ctx, args[0].frame, &L.flags, &split, &L.lod));
     if (split != 1 || !atmo::default_family_supported(L.flags))
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": no multi-view kernel for this context's mode (they exist for the default forms: atmo_set_precision 1, "
                                                           "up to 32 view steps, one lane per ray)");
-    L.family = L.flags | atmo::KF_VIEWS | (packed ? atmo::KF_TARGET : 0);
+    L.family = L.flags | atmo::KF_VIEWS | surface_family_bits(kind);
     int tw = 0, th = 0;
     atmo::render_tile_size(1, &tw, &th);
     uint64_t total = 0;
@@ -2593,12 +2632,11 @@ int views_family_grid(AtmoContext *ctx, const char *who, const ViewArg *args, in
     if (total > 0x7fffffffull) return fail(ctx, ATMO_E_ARG, std::string(who) + ": more than 2^31 tiles in one batch");
     return ATMO_OK;
 }
-// Both halves, for the float batch (atmo_render_views, atmo_debug_views_layout): args[i] = views[i]'s frame, depth and output.
-int views_layout(AtmoContext *ctx, const char *who, const AtmoView *views, int n_views, ViewArg *args, ViewsLayout &L) {
-    view_args(views, n_views, args);
+// Both halves, for the float batch (atmo_render_views, atmo_debug_views_layout)
+int views_layout(AtmoContext *ctx, const char *who, bool have_views, const ViewDraw *args, int n_views, ViewsLayout &L) {
     bool done = false;
-    { const int rc0 = views_check_frames(ctx, who, views != nullptr, args, n_views, L, &done); if (rc0 != ATMO_OK || done) return rc0; }
-    return views_family_grid(ctx, who, args, n_views, false, L);
+    { const int rc0 = views_check_frames(ctx, who, have_views, args, n_views, L, &done); if (rc0 != ATMO_OK || done) return rc0; }
+    return views_family_grid(ctx, who, args, n_views, SURF_FLOAT, L);
 }
 
 // The batches' feedback state, keyed by (stream, family, n_views, every view's grid): re-keyed -- ordered behind whatever used its buffers before, on
@@ -2675,10 +2713,8 @@ static int views_ring_slot_used(AtmoContext *ctx, AtmoContext::ViewsSlot *slot, 
     return ATMO_OK;
 }
 // Everything a batch does once its arguments stand: the staging slot, the per-view constants, the tile order and its feedback, the ONE launch.  Shared by
-// atmo_render_views (packed == false: the float kernels, args[i].pitch_px) and atmo_render_views_target (packed: the KF_VIEWS | KF_TARGET kernels, args[i].tc).
-// depth_source: atmo_render_views_depth_target (packed set whatever the format: the KF_DEPTH | KF_VIEWS | KF_TARGET kernels, args[i].tc and args[i].dc).
-int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, int composite, bool packed, const ViewsLayout &L, void *stream,
-                  bool depth_source = false) {
+// atmo_render_views, atmo_render_views_target and atmo_render_views_depth_target; kind: the batch's surfaces -- every non-empty view's
+int views_enqueue(AtmoContext *ctx, const char *who, const ViewDraw *args, int n_views, SurfaceKind kind, const ViewsLayout &L, void *stream) {
     if (L.n_drawn == 0) return ATMO_OK;   // n_views == 0, or every rect empty: nothing to shade
     ATMO_TRY(check_draw_textures(ctx, who));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2695,7 +2731,7 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_
         atmo::RenderConsts &rc = slot->host[i];
         if (L.empty[i]) { std::memset(&rc, 0, sizeof(rc)); frames[i] = args[i].frame; continue; }
         frames[i] = draw_frame(ctx, args[i].frame, fixed[i]);
-        draw_consts(ctx, frames[i], args[i].depth, (float *)args[i].pixels, composite != 0, args[i].pitch_px, packed, rc);
+        draw_consts(ctx, frames[i], args[i].sf, rc);
         draw_grid_origin(frames[i], L.lod, rc);
         rc.tiles_x = L.gx[i];
         if (first < 0) first = i;
@@ -2704,10 +2740,10 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_
     atmo::ViewsTargetConsts vtc;   // (its targets are read by the packed kernels only)
     std::memset(&vtc, 0, sizeof(vtc));
     atmo::ViewsConsts &vc = vtc.v;
-    for (int i = 0; packed && i < n_views; ++i) if (!L.empty[i]) vtc.target[i] = args[i].tc;
+    for (int i = 0; kind != SURF_FLOAT && i < n_views; ++i) if (!L.empty[i]) vtc.target[i] = args[i].sf.tc;
     atmo::ViewsDepthConsts vdc;    // (read by the depth-source kernels only)
     std::memset(&vdc, 0, sizeof(vdc));
-    for (int i = 0; depth_source && i < n_views; ++i) if (!L.empty[i]) vdc.depth[i] = args[i].dc;
+    for (int i = 0; kind == SURF_DEPTH && i < n_views; ++i) if (!L.empty[i]) vdc.depth[i] = args[i].sf.dc;
     for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) vc.first_block[i] = L.first_block[i];
     const uint32_t total = L.first_block[ATMO_MAX_VIEWS];
     // One tile order over all views, learnt as render_impl learns a single draw's on a still camera: feedback_plan's batch form
@@ -2726,9 +2762,7 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_
     ATMO_TRY(timing_open(ctx, timing));
     HIP_TRY(ctx, hipMemcpyAsync(slot->dev, slot->host, (size_t)n_views * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
     ATMO_TRY(timing_begin(ctx, timing, s));   // the bracket is the one launch's
-    if (depth_source) HIP_TRY(ctx, atmo::launch_render_views_depth_target(L.flags, slot->host[first].light_steps, slot->dev, vtc, vdc, s));
-    else if (packed) HIP_TRY(ctx, atmo::launch_render_views_target(L.flags, slot->host[first].light_steps, slot->dev, vtc, s));
-    else HIP_TRY(ctx, atmo::launch_render_views(L.flags, slot->host[first].light_steps, slot->dev, vc, s));
+    HIP_TRY(ctx, launch_views(kind, L.flags, slot->host[first].light_steps, slot->dev, vtc, vdc, s));
     ATMO_TRY(timing_end(ctx, timing, s));
     ATMO_TRY(views_ring_slot_used(ctx, slot, s));
     if (plan.sort_side) ATMO_TRY(feedback_sort_side(ctx, *fb, (int)total, 1, plan, s));
@@ -2740,15 +2774,14 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_
 // The float batches' per-view pointer checks and their overlap rule (atmo_render_views, atmo_render_views_proxy), behind views_check_frames.
 // The bytes every view writes: [lo, hi) -- plain: its own tight float4 array; composite: rows y0 .. y1 of its scene buffer, from pixel x0 of the first
 // to pixel x1 of the last.  Pairwise disjoint, or the views would race (they run concurrently, in no order).
-int views_float_outputs(AtmoContext *ctx, const char *who, const AtmoView *views, int n_views, int composite, const ViewsLayout &L) {
+int views_float_outputs(AtmoContext *ctx, const char *who, ViewDraw *args, int n_views, const ViewsLayout &L) {
     uintptr_t lo[ATMO_MAX_VIEWS], hi[ATMO_MAX_VIEWS];
     for (int i = 0; i < n_views; ++i) {
         if (L.empty[i]) continue;
-        const AtmoView &v = views[i];
-        ATMO_TRY(check_draw_pointers(ctx, std::string(who) + ": view " + std::to_string(i), v.depth_dev, v.rgba_dev, true));
-        const AtmoFrame &f = v.frame;
-        const uintptr_t base = reinterpret_cast<uintptr_t>(v.rgba_dev);
-        if (composite) {
+        ATMO_TRY(check_surfaces(ctx, std::string(who) + ": view " + std::to_string(i), args[i].frame, args[i].sf));
+        const AtmoFrame &f = *args[i].frame;
+        const uintptr_t base = reinterpret_cast<uintptr_t>(args[i].sf.pixels);
+        if (args[i].sf.composite) {
             lo[i] = base + ((uintptr_t)f.y0 * (uintptr_t)f.viewport_w + (uintptr_t)f.x0) * 16u;
             hi[i] = base + ((uintptr_t)(f.y1 - 1) * (uintptr_t)f.viewport_w + (uintptr_t)f.x1) * 16u;
         } else {
@@ -2763,18 +2796,12 @@ int views_float_outputs(AtmoContext *ctx, const char *who, const AtmoView *views
 }
 // The target batches' argument checks (atmo_render_views_target, atmo_render_views_proxy_target): the count and every view's frame (views_check_frames;
 // *done as there), then per view atmo_render_target's checks, one format per batch, and the overlap rule of include/atmo_views_target.h on the bytes it
-// writes -- `rows` rows of `row_bytes`, `pitch` apart, from `base`.  Fills args; *packed: the batch's format is not RGBA32F.
-// depths (atmo_depth.h's batches): view i's depth source, checked (depth_check, into args[i].dc) where the float batches have their depth_dev null check.
-int views_target_outputs(AtmoContext *ctx, const char *who, const AtmoViewTarget *views, int n_views, int composite, ViewArg *args, ViewsLayout &L,
-                         bool *done, bool *packed, const AtmoDepth *const *depths = nullptr) {
-    for (int i = 0; views && i < n_views && i < ATMO_MAX_VIEWS; ++i) {
-        args[i].frame = &views[i].frame;
-        args[i].depth = views[i].depth_dev;
-        args[i].pixels = views[i].target.pixels;
-    }
-    *packed = false;
+// writes -- `rows` rows of `row_bytes`, `pitch` apart, from `base`.  args[i].sf comes in with the caller's target and depth unchecked and leaves checked
+// (target_check; check_surfaces: the depth source's checks stand where the float depth's null check does).  *kind: the batch's surfaces.
+int views_target_outputs(AtmoContext *ctx, const char *who, bool have_views, ViewDraw *args, int n_views, ViewsLayout &L, bool *done, SurfaceKind *kind) {
+    *kind = SURF_FLOAT;
     {
-        const int rc0 = views_check_frames(ctx, who, views != nullptr, args, n_views, L, done);
+        const int rc0 = views_check_frames(ctx, who, have_views, args, n_views, L, done);
         if (rc0 != ATMO_OK || *done) return rc0;
     }
     int format = -1;
@@ -2782,24 +2809,21 @@ int views_target_outputs(AtmoContext *ctx, const char *who, const AtmoViewTarget
     long long rows[ATMO_MAX_VIEWS], row_bytes[ATMO_MAX_VIEWS], pitch[ATMO_MAX_VIEWS];
     for (int i = 0; i < n_views; ++i) {
         if (L.empty[i]) continue;   // skipped: its pointers and its target are not looked at
-        const AtmoViewTarget &v = views[i];
+        DrawSurfaces &sf = args[i].sf;
         const std::string who_i = std::string(who) + ": view " + std::to_string(i);
-        int p = 0;
-        ATMO_TRY(target_check(ctx, who_i.c_str(), &v.frame, &v.target, composite != 0, &p));
-        if (depths) ATMO_TRY(depth_check(ctx, who_i, depths[i], v.frame.viewport_w, v.frame.viewport_h, &args[i].dc));
-        else ATMO_TRY(check_draw_pointers(ctx, who_i, v.depth_dev, (const float *)v.target.pixels, false));
-        if (format >= 0 && v.target.format != format)
-            return fail(ctx, ATMO_E_ARG, who_i + ": target format " + std::to_string(v.target.format) + " differs from the batch's (" + std::to_string(format) +
+        ATMO_TRY(target_check(ctx, who_i.c_str(), args[i].frame, sf));
+        ATMO_TRY(check_surfaces(ctx, who_i, args[i].frame, sf));
+        if (format >= 0 && sf.tc.format != format)
+            return fail(ctx, ATMO_E_ARG, who_i + ": target format " + std::to_string(sf.tc.format) + " differs from the batch's (" + std::to_string(format) +
                                              "): one format per batch");
-        format = v.target.format;
-        const AtmoFrame &f = v.frame;
-        const long long px = atmo_target_pixel_bytes(format);
+        format = sf.tc.format;
+        *kind = sf.kind;
+        const AtmoFrame &f = *args[i].frame;
+        const long long px = atmo_target_pixel_bytes(format), p = sf.tc.pitch_bytes;
         pitch[i] = p;
         rows[i] = f.y1 - f.y0;
         row_bytes[i] = (long long)(f.x1 - f.x0) * px;
-        base[i] = reinterpret_cast<uintptr_t>(v.target.pixels) + (composite ? (uintptr_t)((long long)f.y0 * p + (long long)f.x0 * px) : (uintptr_t)0);
-        args[i].pitch_px = format == ATMO_TARGET_RGBA32F ? p / 16 : 0;
-        args[i].tc = {v.target.pixels, p, v.target.format};
+        base[i] = reinterpret_cast<uintptr_t>(sf.pixels) + (sf.composite ? (uintptr_t)(f.y0 * p + f.x0 * px) : (uintptr_t)0);
         for (int j = 0; j < i; ++j) {
             if (L.empty[j]) continue;
             // rules (a) and (b): the pair test atmo_render_planets plans with (atmo_planets_plan.h)
@@ -2807,7 +2831,6 @@ int views_target_outputs(AtmoContext *ctx, const char *who, const AtmoViewTarget
             return fail(ctx, ATMO_E_ARG, std::string(who) + ": views " + std::to_string(j) + " and " + std::to_string(i) + " write overlapping memory");
         }
     }
-    *packed = atmo::target_format_packed(format);
     return ATMO_OK;
 }
 
@@ -2829,7 +2852,7 @@ int views_proxy_checks(AtmoContext *ctx, const char *who, const float *model_mat
     return ATMO_OK;
 }
 // Behind every argument check that needs no matrix arithmetic: the mode (ATMO_E_STATE, proxy_family: the one list both families share), then the boxes.
-int views_proxy_layout(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, const float *model_matrix, float box_size, ViewsLayout &L,
+int views_proxy_layout(AtmoContext *ctx, const char *who, const ViewDraw *args, int n_views, const float *model_matrix, float box_size, ViewsLayout &L,
                        ViewsProxyLayout &P) {
     ATMO_TRY(proxy_family(ctx, who, args[0].frame, &L.flags, &L.lod));
     uint64_t total = 0;
@@ -2853,17 +2876,23 @@ int views_proxy_layout(AtmoContext *ctx, const char *who, const ViewArg *args, i
     if (total > 0x7fffffffull) return fail(ctx, ATMO_E_ARG, std::string(who) + ": more than 2^31 tiles in one batch");
     return ATMO_OK;
 }
-// views_enqueue's sibling for the proxy batches: the staging slot, the per-view constants with the CUT rectangle as the launch rectangle (the output stays
-// addressed by the frame's rect or the viewport, as proxy_impl fills it), the ONE launch.  No tile order, no feedback state, not timed and not counted, as
-// the single proxy draw.
-int views_proxy_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, int n_views, int composite, bool packed, const ViewsLayout &L,
-                        const ViewsProxyLayout &P, void *stream, bool depth_source = false) {   // depth_source: as views_enqueue's
-    if (P.first_block[ATMO_MAX_VIEWS] == 0) return ATMO_OK;   // no view has a tile: no launch, no staging slot
-    ATMO_TRY(check_draw_textures(ctx, who));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (stream_is_capturing(s))   // as views_enqueue: the table is the context's and the next batch overwrites it
-        return fail(ctx, ATMO_E_STATE, std::string(who) + " cannot be captured into a HIP graph (context-owned per-view constants); capture atmo_render_proxy per view instead");
+// ---- the ONE enqueue of a proxy batch: atmo_render_views_proxy*'s launch and every launch of atmo_render_planets -------------------------------------
+// An entry of the launch's table: whose draw it is, the frame as the kernels see it (draw_frame), its surfaces, and proxy_setup's results.
+struct ProxyBatchEntry {
+    AtmoContext *ctx;
+    const AtmoFrame *frame;
+    const DrawSurfaces *sf;
+    const atmo::ProxyConsts *pc;
+    const int *rect;   // the cut rectangle
+    int gx, gy;        // ... and its tile grid; 0 x 0: no tile -- a zero table row, nothing of the launch maps to it
+    bool lod;
+};
+// views_enqueue's sibling: the staging slot (the first entry's context's, which also holds a HIP error's message), the table with the CUT rectangle as each
+// entry's launch rectangle (the output stays addressed by the frame's rect or the viewport, as proxy_impl fills it), the ONE launch of `flags`' family and
+// of the surfaces' kind the entries with a tile share.  tex_order and finish_draw once per distinct context, in entry order.  No tile order, no feedback
+// state, not timed and not counted, as the single proxy draw.  The caller has checked the textures and the capture state and set the device.
+int proxy_batch_enqueue(const ProxyBatchEntry *e, int n, int flags, hipStream_t s) {
+    AtmoContext *ctx = e[0].ctx;
     AtmoContext::ViewsSlot *slot = nullptr;
     ATMO_TRY(views_ring_slot(ctx, &slot));
     atmo::ViewsProxyTargetConsts vptc;   // (its targets are read by the packed kernels only)
@@ -2871,25 +2900,45 @@ int views_proxy_enqueue(AtmoContext *ctx, const char *who, const ViewArg *args, 
     atmo::ViewsDepthConsts vdc;          // (read by the depth-source kernels only)
     std::memset(&vdc, 0, sizeof(vdc));
     int first = -1;
-    for (int i = 0; i < n_views; ++i) {
-        atmo::RenderConsts &rc = slot->host[i];
-        if (P.gx[i] == 0 || P.gy[i] == 0) { std::memset(&rc, 0, sizeof(rc)); continue; }
-        draw_consts(ctx, P.frames[i], args[i].depth, (float *)args[i].pixels, composite != 0, args[i].pitch_px, packed, rc);
-        proxy_cut_rect(P.rect[i], L.lod, P.gx[i], rc);
-        vptc.p.proxy[i] = P.pc[i];
-        if (packed) vptc.target[i] = args[i].tc;
-        if (depth_source) vdc.depth[i] = args[i].dc;
-        if (first < 0) first = i;
+    uint32_t total = 0;
+    for (int k = 0; k <= ATMO_MAX_VIEWS; ++k) {
+        vptc.p.first_block[k] = total;   // (entries behind n repeat the total)
+        if (k >= n) continue;
+        atmo::RenderConsts &rc = slot->host[k];
+        if (e[k].gx == 0 || e[k].gy == 0) { std::memset(&rc, 0, sizeof(rc)); continue; }
+        const DrawSurfaces &sf = *e[k].sf;
+        draw_consts(e[k].ctx, e[k].frame, sf, rc);
+        proxy_cut_rect(e[k].rect, e[k].lod, e[k].gx, rc);
+        vptc.p.proxy[k] = *e[k].pc;
+        if (sf.kind != SURF_FLOAT) vptc.target[k] = sf.tc;
+        if (sf.kind == SURF_DEPTH) vdc.depth[k] = sf.dc;
+        if (first < 0) first = k;
+        total += (uint32_t)e[k].gx * (uint32_t)e[k].gy;   // (the callers' layouts have bounded the sum)
     }
-    for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) vptc.p.first_block[i] = P.first_block[i];
-    ATMO_TRY(tex_order(ctx, s));  // texture updated on another stream
-    HIP_TRY(ctx, hipMemcpyAsync(slot->dev, slot->host, (size_t)n_views * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
-    if (depth_source) HIP_TRY(ctx, atmo::launch_render_views_proxy_depth_target(L.flags, slot->host[first].light_steps, slot->dev, vptc, vdc, s));
-    else if (packed) HIP_TRY(ctx, atmo::launch_render_views_proxy_target(L.flags, slot->host[first].light_steps, slot->dev, vptc, s));
-    else HIP_TRY(ctx, atmo::launch_render_views_proxy(L.flags, slot->host[first].light_steps, slot->dev, vptc.p, s));
+    const SurfaceKind kind = e[first].sf->kind;
+    auto distinct = [&](int k) { for (int j = 0; j < k; ++j) if (e[j].ctx == e[k].ctx) return false; return true; };
+    for (int k = 0; k < n; ++k) if (distinct(k)) ATMO_TRY(tex_order(e[k].ctx, s));   // a texture updated on another stream
+    HIP_TRY(ctx, hipMemcpyAsync(slot->dev, slot->host, (size_t)n * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, launch_views_proxy(kind, flags, slot->host[first].light_steps, slot->dev, vptc, vdc, s));
     ATMO_TRY(views_ring_slot_used(ctx, slot, s));
-    hipEvent_t marker = nullptr;
-    return finish_draw(ctx, s, L.flags | atmo::KF_VIEWS | atmo::KF_PROXY | (packed ? atmo::KF_TARGET : 0) | (depth_source ? atmo::KF_DEPTH : 0), 1, false, &marker);
+    for (int k = 0; k < n; ++k) {
+        if (!distinct(k)) continue;
+        hipEvent_t marker = nullptr;
+        ATMO_TRY(finish_draw(e[k].ctx, s, flags | atmo::KF_VIEWS | atmo::KF_PROXY | surface_family_bits(kind), 1, false, &marker));
+    }
+    return ATMO_OK;
+}
+// A view batch's: every view an entry of the one context (a view without a tile: its zero row; light_steps is the first view's that has one)
+int views_proxy_enqueue(AtmoContext *ctx, const char *who, const ViewDraw *args, int n_views, const ViewsLayout &L, const ViewsProxyLayout &P, void *stream) {
+    if (P.first_block[ATMO_MAX_VIEWS] == 0) return ATMO_OK;   // no view has a tile: no launch, no staging slot
+    ATMO_TRY(check_draw_textures(ctx, who));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s))   // as views_enqueue: the table is the context's and the next batch overwrites it
+        return fail(ctx, ATMO_E_STATE, std::string(who) + " cannot be captured into a HIP graph (context-owned per-view constants); capture atmo_render_proxy per view instead");
+    ProxyBatchEntry e[ATMO_MAX_VIEWS];
+    for (int i = 0; i < n_views; ++i) e[i] = {ctx, P.frames[i], &args[i].sf, &P.pc[i], P.rect[i], P.gx[i], P.gy[i], L.lod};
+    return proxy_batch_enqueue(e, n_views, L.flags, s);
 }
 }  // namespace
 
@@ -2897,8 +2946,8 @@ int atmo_debug_views_layout(AtmoContext *ctx, const AtmoView *views, int n_views
     if (!ctx) return ATMO_E_ARG;
     if (!first_block || !grid) return fail(ctx, ATMO_E_ARG, "atmo_debug_views_layout: null output");
     ViewsLayout L;
-    ViewArg args[ATMO_MAX_VIEWS];
-    ATMO_TRY(views_layout(ctx, "atmo_debug_views_layout", views, n_views, args, L));
+    const ViewDraws<AtmoView> args(views, n_views, 0);   // (the frames are all this looks at)
+    ATMO_TRY(views_layout(ctx, "atmo_debug_views_layout", views != nullptr, args.v, n_views, L));
     for (int i = 0; i <= n_views; ++i) first_block[i] = (int)L.first_block[i];
     for (int i = 0; i < n_views; ++i) { grid[2 * i] = L.gx[i]; grid[2 * i + 1] = L.gy[i]; }
     return ATMO_OK;
@@ -2908,24 +2957,32 @@ int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int 
     if (!ctx) return ATMO_E_ARG;
     const char *who = "atmo_render_views";
     ViewsLayout L;
-    ViewArg args[ATMO_MAX_VIEWS];
-    ATMO_TRY(views_layout(ctx, who, views, n_views, args, L));
-    ATMO_TRY(views_float_outputs(ctx, who, views, n_views, composite, L));
-    return views_enqueue(ctx, who, args, n_views, composite, false, L, stream);
+    ViewDraws<AtmoView> args(views, n_views, composite);
+    ATMO_TRY(views_layout(ctx, who, views != nullptr, args.v, n_views, L));
+    ATMO_TRY(views_float_outputs(ctx, who, args.v, n_views, L));
+    return views_enqueue(ctx, who, args.v, n_views, SURF_FLOAT, L, stream);
 }
 
-// include/atmo_views_target.h: the batch into packed and pitched colour targets.  All argument checks (ATMO_E_ARG) in front of the mode check (ATMO_E_STATE),
-// both in front of anything that touches a device.
-int atmo_render_views_target(AtmoContext *ctx, const AtmoViewTarget *views, int n_views, int composite, void *stream) {
+// include/atmo_views_target.h and include/atmo_depth.h: the batch into packed and pitched colour targets, with float depths or a depth source per view (whose
+// every target format draws with the KF_DEPTH kernels).  All argument checks (ATMO_E_ARG) in front of the mode check (ATMO_E_STATE), both in front of
+// anything that touches a device.
+extern "C++" template <class View>
+static int render_views_target(AtmoContext *ctx, const char *who, const View *views, int n_views, int composite, void *stream) {
     if (!ctx) return ATMO_E_ARG;
-    const char *who = "atmo_render_views_target";
     ViewsLayout L;
-    ViewArg args[ATMO_MAX_VIEWS];
-    bool done = false, packed = false;
-    ATMO_TRY(views_target_outputs(ctx, who, views, n_views, composite, args, L, &done, &packed));
+    ViewDraws<View> args(views, n_views, composite);
+    bool done = false;
+    SurfaceKind kind = SURF_FLOAT;
+    ATMO_TRY(views_target_outputs(ctx, who, views != nullptr, args.v, n_views, L, &done, &kind));
     if (done) return ATMO_OK;
-    ATMO_TRY(views_family_grid(ctx, who, args, n_views, packed, L));
-    return views_enqueue(ctx, who, args, n_views, composite, packed, L, stream);
+    ATMO_TRY(views_family_grid(ctx, who, args.v, n_views, kind, L));
+    return views_enqueue(ctx, who, args.v, n_views, kind, L, stream);
+}
+int atmo_render_views_target(AtmoContext *ctx, const AtmoViewTarget *views, int n_views, int composite, void *stream) {
+    return render_views_target(ctx, "atmo_render_views_target", views, n_views, composite, stream);
+}
+int atmo_render_views_depth_target(AtmoContext *ctx, const AtmoViewDepthTarget *views, int n_views, int composite, void *stream) {
+    return render_views_target(ctx, "atmo_render_views_depth_target", views, n_views, composite, stream);
 }
 
 // include/atmo_views_proxy.h: the far-mode (proxy) batches.  Argument checks that need no matrix arithmetic (ATMO_E_ARG) in front of the mode check
@@ -2934,83 +2991,40 @@ int atmo_render_views_proxy(AtmoContext *ctx, const AtmoView *views, int n_views
     if (!ctx) return ATMO_E_ARG;
     const char *who = "atmo_render_views_proxy";
     ViewsLayout L;
-    ViewArg args[ATMO_MAX_VIEWS];
-    view_args(views, n_views, args);
+    ViewDraws<AtmoView> args(views, n_views, composite);
     bool done = false;
-    ATMO_TRY(views_check_frames(ctx, who, views != nullptr, args, n_views, L, &done));
+    ATMO_TRY(views_check_frames(ctx, who, views != nullptr, args.v, n_views, L, &done));
     ATMO_TRY(views_proxy_checks(ctx, who, model_matrix, box_size));
     if (done) return ATMO_OK;
-    ATMO_TRY(views_float_outputs(ctx, who, views, n_views, composite, L));
+    ATMO_TRY(views_float_outputs(ctx, who, args.v, n_views, L));
     ViewsProxyLayout P;
-    ATMO_TRY(views_proxy_layout(ctx, who, args, n_views, model_matrix, box_size, L, P));
-    return views_proxy_enqueue(ctx, who, args, n_views, composite, false, L, P, stream);
+    ATMO_TRY(views_proxy_layout(ctx, who, args.v, n_views, model_matrix, box_size, L, P));
+    return views_proxy_enqueue(ctx, who, args.v, n_views, L, P, stream);
 }
 
+// ... into targets, with float depths or a depth source per view
+extern "C++" template <class View>
+static int render_views_proxy_target(AtmoContext *ctx, const char *who, const View *views, int n_views, const float *model_matrix, float box_size,
+                                     int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    ViewsLayout L;
+    ViewDraws<View> args(views, n_views, composite);
+    bool done = false;
+    SurfaceKind kind = SURF_FLOAT;
+    ATMO_TRY(views_target_outputs(ctx, who, views != nullptr, args.v, n_views, L, &done, &kind));
+    ATMO_TRY(views_proxy_checks(ctx, who, model_matrix, box_size));
+    if (done) return ATMO_OK;
+    ViewsProxyLayout P;
+    ATMO_TRY(views_proxy_layout(ctx, who, args.v, n_views, model_matrix, box_size, L, P));
+    return views_proxy_enqueue(ctx, who, args.v, n_views, L, P, stream);
+}
 int atmo_render_views_proxy_target(AtmoContext *ctx, const AtmoViewTarget *views, int n_views, const float *model_matrix, float box_size, int composite,
                                    void *stream) {
-    if (!ctx) return ATMO_E_ARG;
-    const char *who = "atmo_render_views_proxy_target";
-    ViewsLayout L;
-    ViewArg args[ATMO_MAX_VIEWS];
-    bool done = false, packed = false;
-    ATMO_TRY(views_target_outputs(ctx, who, views, n_views, composite, args, L, &done, &packed));
-    ATMO_TRY(views_proxy_checks(ctx, who, model_matrix, box_size));
-    if (done) return ATMO_OK;
-    ViewsProxyLayout P;
-    ATMO_TRY(views_proxy_layout(ctx, who, args, n_views, model_matrix, box_size, L, P));
-    return views_proxy_enqueue(ctx, who, args, n_views, composite, packed, L, P, stream);
+    return render_views_proxy_target(ctx, "atmo_render_views_proxy_target", views, n_views, model_matrix, box_size, composite, stream);
 }
-
-// include/atmo_depth.h: the two target batches with a depth source per view.  The views as AtmoViewTarget (views_target_outputs: the same checks in the
-// same order, the depth's where depth_dev's null check stands); every target format draws with the KF_DEPTH kernels, so `packed` is set for RGBA32F too and
-// the float target's pitch in pixels is not used.
-namespace {
-struct DepthViews {
-    AtmoViewTarget v[ATMO_MAX_VIEWS];
-    const AtmoDepth *depth[ATMO_MAX_VIEWS];
-    DepthViews(const AtmoViewDepthTarget *views, int n_views) {
-        for (int i = 0; i < ATMO_MAX_VIEWS; ++i) {
-            depth[i] = nullptr;
-            if (!views || i >= n_views) continue;
-            v[i].frame = views[i].frame;
-            v[i].depth_dev = nullptr;
-            v[i].target = views[i].target;
-            depth[i] = &views[i].depth;
-        }
-    }
-};
-}  // namespace
-
-int atmo_render_views_depth_target(AtmoContext *ctx, const AtmoViewDepthTarget *views, int n_views, int composite, void *stream) {
-    if (!ctx) return ATMO_E_ARG;
-    const char *who = "atmo_render_views_depth_target";
-    ViewsLayout L;
-    ViewArg args[ATMO_MAX_VIEWS];
-    const DepthViews dv(views, n_views);
-    bool done = false, packed = false;
-    ATMO_TRY(views_target_outputs(ctx, who, views ? dv.v : nullptr, n_views, composite, args, L, &done, &packed, dv.depth));
-    if (done) return ATMO_OK;
-    for (ViewArg &a : args) a.pitch_px = 0;
-    ATMO_TRY(views_family_grid(ctx, who, args, n_views, true, L));
-    L.family |= atmo::KF_DEPTH;
-    return views_enqueue(ctx, who, args, n_views, composite, true, L, stream, true);
-}
-
 int atmo_render_views_proxy_depth_target(AtmoContext *ctx, const AtmoViewDepthTarget *views, int n_views, const float *model_matrix, float box_size,
                                          int composite, void *stream) {
-    if (!ctx) return ATMO_E_ARG;
-    const char *who = "atmo_render_views_proxy_depth_target";
-    ViewsLayout L;
-    ViewArg args[ATMO_MAX_VIEWS];
-    const DepthViews dv(views, n_views);
-    bool done = false, packed = false;
-    ATMO_TRY(views_target_outputs(ctx, who, views ? dv.v : nullptr, n_views, composite, args, L, &done, &packed, dv.depth));
-    ATMO_TRY(views_proxy_checks(ctx, who, model_matrix, box_size));
-    if (done) return ATMO_OK;
-    for (ViewArg &a : args) a.pitch_px = 0;
-    ViewsProxyLayout P;
-    ATMO_TRY(views_proxy_layout(ctx, who, args, n_views, model_matrix, box_size, L, P));
-    return views_proxy_enqueue(ctx, who, args, n_views, composite, true, L, P, stream, true);
+    return render_views_proxy_target(ctx, "atmo_render_views_proxy_depth_target", views, n_views, model_matrix, box_size, composite, stream);
 }
 
 // atmo_debug.h: the launch of a proxy batch as the host computes it; host-only contexts work, the pointers are not looked at
@@ -3020,14 +3034,13 @@ int atmo_debug_views_proxy_layout(AtmoContext *ctx, const AtmoView *views, int n
     const char *who = "atmo_debug_views_proxy_layout";
     if (!first_block || !grid || !rects) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null output");
     ViewsLayout L;
-    ViewArg args[ATMO_MAX_VIEWS];
-    view_args(views, n_views, args);   // (the frames are all this looks at)
+    const ViewDraws<AtmoView> args(views, n_views, 0);   // (the frames are all this looks at)
     bool done = false;
-    ATMO_TRY(views_check_frames(ctx, who, views != nullptr, args, n_views, L, &done));
+    ATMO_TRY(views_check_frames(ctx, who, views != nullptr, args.v, n_views, L, &done));
     ATMO_TRY(views_proxy_checks(ctx, who, model_matrix, box_size));
     if (done) { first_block[0] = 0; return ATMO_OK; }
     ViewsProxyLayout P;
-    ATMO_TRY(views_proxy_layout(ctx, who, args, n_views, model_matrix, box_size, L, P));
+    ATMO_TRY(views_proxy_layout(ctx, who, args.v, n_views, model_matrix, box_size, L, P));
     for (int i = 0; i <= n_views; ++i) first_block[i] = (int)P.first_block[i];
     for (int i = 0; i < n_views; ++i) {
         grid[2 * i] = P.gx[i];
@@ -3044,7 +3057,7 @@ namespace {
 struct PlanetsLayout {
     int flags[ATMO_MAX_PLANET_DRAWS];
     bool lod[ATMO_MAX_PLANET_DRAWS];
-    int pitch[ATMO_MAX_PLANET_DRAWS];                 // the row pitch in effect, bytes
+    DrawSurfaces sf[ATMO_MAX_PLANET_DRAWS];           // composite into the draw's target: checked (tc.pitch_bytes: the row pitch in effect)
     atmo::ProxyConsts pc[ATMO_MAX_PLANET_DRAWS];
     int rect[ATMO_MAX_PLANET_DRAWS][4];
     int gx[ATMO_MAX_PLANET_DRAWS], gy[ATMO_MAX_PLANET_DRAWS];
@@ -3072,10 +3085,11 @@ int planets_layout(const char *who, const AtmoPlanetDraw *draws, int n, PlanetsL
     for (int i = 0; i < n; ++i) {   // atmo_render_proxy_target's argument checks that need no matrix arithmetic
         const AtmoPlanetDraw &d = draws[i];
         const std::string who_i = name(i);
-        ATMO_TRY(target_check(d.ctx, who_i.c_str(), &d.frame, &d.target, true, &L.pitch[i]));
+        L.sf[i] = target_surfaces(d.depth_dev, &d.target, true);
+        ATMO_TRY(target_check(d.ctx, who_i.c_str(), &d.frame, L.sf[i]));
         if (!(d.box_size > 0.0f) || !std::isfinite(d.box_size)) return fail(d.ctx, ATMO_E_ARG, who_i + ": box_size must be positive and finite");
         ATMO_TRY(check_frame(d.ctx, who_i, &d.frame, &empty[i]));
-        ATMO_TRY(check_draw_pointers(d.ctx, who_i, d.depth_dev, (const float *)d.target.pixels, d.target.format == ATMO_TARGET_RGBA32F));
+        ATMO_TRY(check_surfaces(d.ctx, who_i, &d.frame, L.sf[i]));
     }
     for (int i = 0; i < n; ++i) ATMO_TRY(proxy_family(draws[i].ctx, name(i).c_str(), &draws[i].frame, &L.flags[i], &L.lod[i]));   // the mode: ATMO_E_STATE
     atmo::PlanetPlanIn in[ATMO_MAX_PLANET_DRAWS];
@@ -3090,8 +3104,9 @@ int planets_layout(const char *who, const AtmoPlanetDraw *draws, int n, PlanetsL
         const int64_t px = atmo_target_pixel_bytes(d.target.format);
         const int *r = L.rect[i];
         in[i].has_tile = 1;
-        in[i].fp = {(uint64_t)reinterpret_cast<uintptr_t>(d.target.pixels) + (uint64_t)((int64_t)r[1] * L.pitch[i] + (int64_t)r[0] * px), r[3] - r[1],
-                    (r[2] - r[0]) * px, L.pitch[i]};
+        const int64_t pitch = L.sf[i].tc.pitch_bytes;
+        in[i].fp = {(uint64_t)reinterpret_cast<uintptr_t>(d.target.pixels) + (uint64_t)((int64_t)r[1] * pitch + (int64_t)r[0] * px), r[3] - r[1],
+                    (r[2] - r[0]) * px, pitch};
         // the family key (the device is the call's): the flags, the LSTEPS twin launch_default_family picks -- the direct-light families have the unrolled
         // 8-step form --, and the kernel that stores the target: the float one, or the packed one with its format (one format per packed launch)
         const uint64_t twin = ((L.flags[i] & atmo::KF_LIGHT_DIRECT) && d.ctx->light_steps == 8) ? 1u : 0u;
@@ -3111,7 +3126,7 @@ int atmo_plan_planets(const AtmoPlanetDraw *draws, int n_draws, int *launch_of, 
     return ATMO_OK;
 }
 
-// Launch by launch, in the plan's order, each as views_proxy_enqueue issues a proxy batch -- but every table entry from its own draw's context.
+// Launch by launch, in the plan's order, each a proxy batch (proxy_batch_enqueue) whose every table entry comes from its own draw's context.
 int atmo_render_planets(const AtmoPlanetDraw *draws, int n_draws, void *stream) {
     const char *who = "atmo_render_planets";
     PlanetsLayout L;
@@ -3124,39 +3139,14 @@ int atmo_render_planets(const AtmoPlanetDraw *draws, int n_draws, void *stream) 
     if (stream_is_capturing(s))   // as views_proxy_enqueue: the tables are context-owned and later batches overwrite them
         return fail(ctx0, ATMO_E_STATE, std::string(who) + " cannot be captured into a HIP graph (context-owned per-draw constants); capture atmo_render_proxy_target per draw instead");
     for (int launch = 0; launch < L.n_launches; ++launch) {
-        int member[ATMO_MAX_VIEWS], n = 0;
-        for (int i = 0; i < n_draws; ++i) if (L.launch_of[i] == launch) member[n++] = i;   // (the plan: 1 .. ATMO_MAX_VIEWS draws of one key, each with a tile)
-        AtmoContext *first = draws[member[0]].ctx;
-        const bool packed = atmo::target_format_packed(draws[member[0]].target.format);
-        AtmoContext::ViewsSlot *slot = nullptr;
-        ATMO_TRY(views_ring_slot(first, &slot));
-        atmo::ViewsProxyTargetConsts vptc;   // (its targets are read by the packed kernels only)
-        std::memset(&vptc, 0, sizeof(vptc));
-        uint32_t total = 0;
-        for (int k = 0; k <= ATMO_MAX_VIEWS; ++k) {
-            vptc.p.first_block[k] = total;
-            if (k >= n) continue;
-            const int i = member[k];
-            const AtmoPlanetDraw &d = draws[i];
-            atmo::RenderConsts &rc = slot->host[k];
-            draw_consts(d.ctx, L.frames[i], d.depth_dev, (float *)d.target.pixels, true, packed ? 0 : L.pitch[i] / 16, packed, rc);
-            proxy_cut_rect(L.rect[i], L.lod[i], L.gx[i], rc);
-            vptc.p.proxy[k] = L.pc[i];
-            if (packed) vptc.target[k] = {d.target.pixels, L.pitch[i], d.target.format};
-            total += (uint32_t)L.gx[i] * (uint32_t)L.gy[i];   // (at most 2^25 tiles a draw: the sum of eight fits)
+        ProxyBatchEntry e[ATMO_MAX_VIEWS];
+        int n = 0, flags = 0;
+        for (int i = 0; i < n_draws; ++i) {   // (the plan: 1 .. ATMO_MAX_VIEWS draws of one key, each with a tile)
+            if (L.launch_of[i] != launch) continue;
+            if (n == 0) flags = L.flags[i];
+            e[n++] = {draws[i].ctx, L.frames[i], &L.sf[i], &L.pc[i], L.rect[i], L.gx[i], L.gy[i], L.lod[i]};
         }
-        auto distinct = [&](int k) { for (int j = 0; j < k; ++j) if (draws[member[j]].ctx == draws[member[k]].ctx) return false; return true; };
-        for (int k = 0; k < n; ++k) if (distinct(k)) ATMO_TRY(tex_order(draws[member[k]].ctx, s));   // a texture updated on another stream
-        const int family = L.flags[member[0]];
-        HIP_TRY(first, hipMemcpyAsync(slot->dev, slot->host, (size_t)n * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
-        if (packed) HIP_TRY(first, atmo::launch_render_views_proxy_target(family, slot->host[0].light_steps, slot->dev, vptc, s));
-        else HIP_TRY(first, atmo::launch_render_views_proxy(family, slot->host[0].light_steps, slot->dev, vptc.p, s));
-        ATMO_TRY(views_ring_slot_used(first, slot, s));
-        for (int k = 0; k < n; ++k) {
-            if (!distinct(k)) continue;
-            hipEvent_t marker = nullptr;
-            ATMO_TRY(finish_draw(draws[member[k]].ctx, s, family | atmo::KF_VIEWS | atmo::KF_PROXY | (packed ? atmo::KF_TARGET : 0), 1, false, &marker));
-        }
+        ATMO_TRY(proxy_batch_enqueue(e, n, flags, s));
     }
     return ATMO_OK;
 }
