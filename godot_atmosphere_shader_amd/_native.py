@@ -58,6 +58,10 @@ MAX_PLANET_DRAWS = 64
 DEPTH_SYMBOLS = ("atmo_depth_texel_bytes", "atmo_render_depth_target", "atmo_render_proxy_depth_target", "atmo_render_views_depth_target",
                  "atmo_render_views_proxy_depth_target")
 DEPTH_D32_SFLOAT, DEPTH_D16_UNORM, DEPTH_X8_D24_UNORM = range(3)
+# every symbol include/atmo_debug_prologue.h declares: the camera-prologue mask of a draw and the constants handed to the cloudless direct-light kernels.
+# The ABI version stays 5 and the tuple stands beside EXPORTED_SYMBOLS, as PLANETS_SYMBOLS (NOTES.md).
+PROLOGUE_SYMBOLS = ("atmo_debug_prologue_mode", "atmo_debug_prologue_constants")
+PROLOGUE_CAMERA, PROLOGUE_POW2_STEPS, PROLOGUE_NO_SPHERE_DEPTH = 1, 2, 4
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -239,6 +243,8 @@ def load() -> C.CDLL:
         "atmo_debug_tile_order": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, C.POINTER(ip)]),
         "atmo_debug_heavy_tile_count": (ip, [vp, ip, ip, C.c_float, C.c_float, ip]),
         "atmo_debug_feedback_plan": (ip, [C.POINTER(AtmoFeedbackPlanIn), C.POINTER(AtmoFeedbackPlanOut)]),
+        "atmo_debug_prologue_mode": (ip, [vp, C.POINTER(AtmoFrame), C.POINTER(C.c_uint), C.POINTER(ip), C.POINTER(ip)]),
+        "atmo_debug_prologue_constants": (ip, [vp, C.POINTER(AtmoFrame), fp, ip, C.POINTER(ip)]),
     }
     # ATMO_HIP_LIB names an A/B build (tools/ab_build_commit.sh: possibly an OLDER commit's library): entry points it lacks are skipped
     # (callers of those guard with hasattr) and its ABI version is not held against it.  The in-tree library must match exactly.

@@ -14,6 +14,7 @@
 #include "../../include/atmo_views_proxy.h"
 #include "../../include/atmo_planets.h"
 #include "../../include/atmo_depth.h"
+#include "../../include/atmo_debug_prologue.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -203,6 +204,7 @@ struct AtmoContext {
     unsigned moving_period = 2;                        // ATMO_FB_MOVING_PERIOD: recording period while the camera moves
     int f4_footprints = 3;                             // ATMO_F4=0..3 (A/B): bit 0 = float copy of the cubemap footprints, bit 1 = of the shape volume's
     int env_lod0_cert = 1;                             // ATMO_LOD0_CERT=0 (A/B): the declared sampler's level-0 certificate off
+    int prologue_camera = 1;                           // ATMO_PROLOGUE_CAMERA=0 (A/B, tests): RenderConsts::prologue_mode is 0, every draw takes the general prologue
     int instream = 1;                                  // ATMO_FB_INSTREAM=0: never sort on the draw stream (A/B)
     int fb_axis_windows = 1;                           // ATMO_FB_AXIS_WINDOWS=0: the in-stream sort dilates by motion_px in both axes, as in round 3 (A/B)
     uint32_t *measure_cost = nullptr;                  // atmo_measure_tile_costs: the next draw records here
@@ -325,6 +327,63 @@ inline float clampf(float x, float lo, float hi) { return std::fmin(std::fmax(x,
 inline float smoothstepf(float e0, float e1, float x) {
     float t = clampf((x - e0) / (e1 - e0), 0.0f, 1.0f);
     return t * t * (3.0f - 2.0f * t);
+}
+
+// The camera prologue of the cloudless direct-light kernels (shade_pixel: ATMO_PROLOGUE_CAMERA): which short forms give THIS draw the general forms' bits,
+// and the uniform products the kernels no longer evaluate.  Every test is on bit patterns or exact comparisons -- "about zero" would change the picture.
+//   PM_CAMERA.  v = inv_p (nx, ny, nz, 1) is summed left to right, unfused.  With P[4], P[8] zeros of either sign row x is ((a + z1) + z2) + P[12],
+//     a = P[0] nx, z1 = +-0 (ny is finite), z2 = +-0 for a finite nz.  a != 0: a + zeros = a, so the row is a + P[12], the short form.  a = +-0 happens
+//     for nx = 0 only (|nx| >= 2^-24 otherwise and |P[0]| >= 2^-40), and nx = 2 uvx - 1 is then +0, never -0: a = +0 for P[0] > 0, -0 for P[0] < 0.
+//     Then the general row is s + P[12] with s the sum of the three zeros (-0 only if all three are): P[12] != 0 gives P[12] both ways; P[12] = +0 gives +0
+//     both ways; P[12] = -0 with a = +0 gives +0 both ways; P[12] = -0 with a = -0 gives -0 in the short form but +0 in the general one on the lanes where
+//     z1 or z2 is +0 -- which depends on the lane.  numpy's inverse of a symmetric perspective has exactly this: P[13] = -0, P[5] < 0.  So the pixels with
+//     nx = 0 -- the centre column of an odd-width viewport -- take the general rows when P[12] is -0 and P[0] < 0 (cam_skip_px; a wave with such a lane goes
+//     whole), and the same for row y with P[5], P[13], the centre row and cam_skip_py.  Row z is s + P[14] = P[14] for P[14] != 0.  Row w is (s + b) + P[15],
+//     b = P[11] nz: b != 0 gives b + P[15], the short form; b = +-0 makes the short vw = +-0 + P[15], and a lane whose vw is a zero takes the general rows
+//     anyway (below) -- so does a lane whose vw is +-0 for P[15] != 0, which the general row gets right by itself.  A non-finite nz makes z2 = 0 nz a NaN in
+//     the general rows x, y, z: the kernel sends a wave with such a lane through the general form (it tests vw, which P[11] != 0 makes non-finite then).
+//     With inv_v's bottom row +-0, +-0, +-0, 1 the general ww is s + 1 vw = vw for vw != 0 (vx, vy, vz are finite: the bounds below); a lane with
+//     vw = +-0 takes the general form (the sign of s + vw is s's).
+//     The bounds (2^40 on every entry, the centre and the radii, 2^-40 under |P[0]|, |P[5]|, |P[14]|) keep |v|^2 and everything up to the ground-sphere
+//     hit finite and the direction's length away from 0: what PM_NO_SPHERE_DEPTH needs.
+//   PM_POW2_STEPS.  x / 2^k and x 2^-k are the same real number, rounded once either way, subnormal results included (the kernels run with fp32
+//     denormals on; the division's fix-up and the product both round to the subnormal grid).  A march shorter than view_steps 2^-126 -- 4e-37 for 32
+//     steps -- is where a build that flushed one of the two would differ.
+//   PM_NO_SPHERE_DEPTH.  f = +-0: linear_depth (1 - f) + gd f = linear_depth 1 + (+-0) for a finite gd, and linear_depth, the root of a sum of squares,
+//     is +0, positive, inf or NaN, never -0: adding either zero leaves its bits.  gd is finite when the ray direction is: PM_CAMERA on the same wave.
+static inline uint32_t f32_bits(float x) { uint32_t u; std::memcpy(&u, &x, sizeof(u)); return u; }
+static void prologue_camera_fill(const AtmoContext *ctx, atmo::RenderConsts &rc) {
+    constexpr float LOG2E = 1.44269504088896340736f;   // atmo_kernels.hip's
+    rc.view_steps_f = (float)rc.view_steps;
+    rc.atmosphere_radius2 = rc.atmosphere_radius * rc.atmosphere_radius;
+    rc.planet_radius2 = rc.planet_radius * rc.planet_radius;
+    rc.dens2 = rc.density * rc.density;
+    rc.dens2_8 = rc.dens2 * 0.125f;
+    for (int i = 0; i < 3; ++i) rc.coeff_log2e[i] = -rc.coeff[i] * LOG2E;
+    rc.inv_view_steps = 0.0f;
+    rc.prologue_mode = 0;
+    rc.cam_skip_px = rc.cam_skip_py = -1;
+    if (!ctx->prologue_camera) return;
+    auto zero = [](float x) { return (f32_bits(x) & 0x7fffffffu) == 0u; };
+    auto minus_zero = [](float x) { return f32_bits(x) == 0x80000000u; };
+    auto bounded = [](float x) { return std::fabs(x) <= 0x1p40f; };   // false for NaN and inf
+    const float *P = rc.inv_p, *V = rc.inv_v;
+    bool cam = true;
+    for (int i : {1, 2, 3, 4, 6, 7, 8, 9, 10}) cam = cam && zero(P[i]);
+    cam = cam && zero(V[3]) && zero(V[7]) && zero(V[11]) && f32_bits(V[15]) == 0x3f800000u;
+    cam = cam && P[11] != 0.0f && std::fabs(P[0]) >= 0x1p-40f && std::fabs(P[5]) >= 0x1p-40f && std::fabs(P[14]) >= 0x1p-40f;
+    for (int i = 0; i < 16; ++i) cam = cam && bounded(P[i]) && bounded(V[i]);
+    for (int i = 0; i < 3; ++i) cam = cam && bounded(rc.center[i]);
+    cam = cam && bounded(rc.atmosphere_radius) && bounded(rc.planet_radius);
+    if (cam) rc.prologue_mode |= atmo::PM_CAMERA;
+    if (cam && minus_zero(P[12]) && P[0] < 0.0f && (rc.w & 1)) rc.cam_skip_px = rc.w / 2;   // (px + 0.5) / w == 0.5: pixel_coord is the exact quotient
+    if (cam && minus_zero(P[13]) && P[5] < 0.0f && (rc.h & 1)) rc.cam_skip_py = rc.h / 2;
+    const int n = rc.view_steps;
+    if (n >= 1 && n <= (1 << 20) && (n & (n - 1)) == 0) {
+        rc.prologue_mode |= atmo::PM_POW2_STEPS;
+        rc.inv_view_steps = 1.0f / rc.view_steps_f;
+    }
+    if (cam && zero(rc.sphere_depth_factor)) rc.prologue_mode |= atmo::PM_NO_SPHERE_DEPTH;
 }
 
 void fill_consts(const AtmoContext *ctx, const AtmoFrame *f, const float *depth, float *rgba, atmo::RenderConsts &rc) {
@@ -485,6 +544,7 @@ void fill_consts(const AtmoContext *ctx, const AtmoFrame *f, const float *depth,
     rc.store_discards = ctx->target_cleared ? 0 : 1;
     rc.gx0 = f->x0;
     rc.gy0 = f->y0;
+    prologue_camera_fill(ctx, rc);
 }
 
 // Which coverage-cubemap sampler a draw of this context uses (atmo_set_sampler_lod): 1 = the implicit LOD of the linear-mipmap sampler the
@@ -1091,6 +1151,7 @@ int atmo_create(int device, int variant, int view_steps, int cloud_steps, int li
     if (const char *ev = std::getenv("ATMO_DRAW_EVENTS")) ctx->draw_events = ev[0] == '0' ? 0 : (ev[0] == '2' ? 2 : 1);
     if (const char *ev = std::getenv("ATMO_TARGET_CLEARED")) ctx->target_cleared = ev[0] == '1' ? 1 : 0;  // tools/ab_env.sh: atmo_set_target_cleared
     if (const char *ev = std::getenv("ATMO_GEO_ORDER")) ctx->geo_order = ev[0] == '0' ? 0 : 1;
+    if (const char *ev = std::getenv("ATMO_PROLOGUE_CAMERA")) ctx->prologue_camera = ev[0] == '0' ? 0 : 1;
     if (const char *ev = std::getenv("ATMO_FB_INSTREAM")) ctx->instream = ev[0] >= '1' && ev[0] <= '2' ? ev[0] - '0' : 0;  // 2 (A/B): every cloud and direct-light kernel
     if (const char *ev = std::getenv("ATMO_FB_AXIS_WINDOWS")) ctx->fb_axis_windows = ev[0] == '1' ? 1 : 0;
     if (const char *ev = std::getenv("ATMO_FB_REACH_SCALE")) ctx->env_reach_scale = (float)std::atof(ev);
@@ -2176,6 +2237,7 @@ int atmo_debug_create_host_only(int variant, int view_steps, int cloud_steps, in
     AtmoContext *ctx = new (std::nothrow) AtmoContext();
     if (!ctx) return fail(nullptr, ATMO_E_ARG, "atmo_debug_create_host_only: out of host memory");
     init_variant(ctx, /*device: none*/ -1, variant, view_steps, cloud_steps, light_mode, light_steps);
+    if (const char *ev = std::getenv("ATMO_PROLOGUE_CAMERA")) ctx->prologue_camera = ev[0] == '0' ? 0 : 1;   // as atmo_create: atmo_debug_prologue_mode shows it
     *out = ctx;
     return ATMO_OK;
 }
@@ -2207,6 +2269,35 @@ int atmo_debug_frame_constants(AtmoContext *ctx, const AtmoFrame *frame, int cub
     return ATMO_OK;
 }
 
+// ---- the camera prologue's mode mask and handed-over constants of a draw (include/atmo_debug_prologue.h): no device needed
+int atmo_debug_prologue_mode(AtmoContext *ctx, const AtmoFrame *frame, unsigned int *mode, int *skip_px, int *skip_py) {
+    if (!ctx) return ATMO_E_ARG;
+    if (!frame || !mode) return fail(ctx, ATMO_E_ARG, "atmo_debug_prologue_mode: null argument");
+    AtmoFrame fixed;
+    atmo::RenderConsts rc;
+    fill_consts(ctx, draw_frame(ctx, frame, fixed), nullptr, nullptr, rc);
+    *mode = rc.prologue_mode;
+    if (skip_px) *skip_px = rc.cam_skip_px;
+    if (skip_py) *skip_py = rc.cam_skip_py;
+    return ATMO_OK;
+}
+
+int atmo_debug_prologue_constants(AtmoContext *ctx, const AtmoFrame *frame, float *out, int capacity, int *count) {
+    if (!ctx) return ATMO_E_ARG;
+    if (!frame) return fail(ctx, ATMO_E_ARG, "atmo_debug_prologue_constants: null frame");
+    AtmoFrame fixed;
+    atmo::RenderConsts rc;
+    fill_consts(ctx, draw_frame(ctx, frame, fixed), nullptr, nullptr, rc);
+    const float v[] = {rc.inv_view_steps, rc.view_steps_f, rc.atmosphere_radius2, rc.planet_radius2, rc.dens2, rc.dens2_8,
+                       rc.coeff_log2e[0], rc.coeff_log2e[1], rc.coeff_log2e[2],
+                       rc.atmosphere_radius, rc.planet_radius, rc.density, rc.coeff[0], rc.coeff[1], rc.coeff[2], rc.sphere_depth_factor};
+    const int n = (int)(sizeof(v) / sizeof(v[0]));
+    if (count) *count = n;
+    if (!out) return ATMO_OK;
+    if (capacity < n) return fail(ctx, ATMO_E_ARG, "atmo_debug_prologue_constants: buffer too small");
+    std::memcpy(out, v, sizeof(v));
+    return ATMO_OK;
+}
 
 // ---- the far-mode draw through the BoxMesh proxy (include/atmo_scene.h) ------------------------------------------------------------------
 // 4 x 4 matrices column-major in double: m[col * 4 + row]

@@ -102,6 +102,23 @@ struct RenderConsts {
     // r tiles_x - geo_prefix[r] <= 256 v (blocks of the second part) -- the row of block b then lies in [hint[b >> 8], hint[(b >> 8) + 1]]: one or two steps of a
     // binary search instead of nine (every step is a dependent scalar load in every wave's preamble)
     uint16_t geo_hint[2][GEO_MAX_HINTS + 2];
+    // --- what the camera and the uniforms make redundant in the prologue of the cloudless direct-light kernels (shade_pixel, march_atmosphere:
+    // ATMO_PROLOGUE_CAMERA_FORMS; prologue_camera_fill in atmo_api.hip holds the predicates and their premises).  Behind every older field: no other kernel reads
+    // them, and the older fields keep their places in the kernel-argument segment.
+    uint32_t prologue_mode;         // [host] PM_* bits: which short forms give this draw the general forms' bits; 0 under the environment's ATMO_PROLOGUE_CAMERA=0
+    int32_t cam_skip_px, cam_skip_py;   // [host] PM_CAMERA: the pixel column / row whose lanes must take the general rows (nx or ny = 0 under a -0 constant term), or -1
+    float inv_view_steps;           // [host] 1 / view_steps, exact, under PM_POW2_STEPS; else 0
+    float view_steps_f;             // [host] (float)view_steps
+    float atmosphere_radius2;       // [host] atmosphere_radius^2, planet_radius^2, density^2, density^2 / 8, -coeff * LOG2E: one IEEE operation each, which the
+    float planet_radius2;           //        kernels evaluated in vector instructions once per wave (gfx950 has no scalar float ALU)
+    float dens2, dens2_8;
+    float coeff_log2e[3];
+};
+// RenderConsts::prologue_mode
+enum PrologueMode : uint32_t {
+    PM_CAMERA = 1,           // perspective inv_projection (entries 1..4, 6..10 are zeros), rigid inv_view (bottom row 0 0 0 1)
+    PM_POW2_STEPS = 2,       // view_steps is a power of two: x / n == x * inv_view_steps
+    PM_NO_SPHERE_DEPTH = 4,  // sphere_depth_factor is a zero (and PM_CAMERA): the ground-sphere term of linear_depth is multiplied by zero
 };
 
 struct BakeConsts {

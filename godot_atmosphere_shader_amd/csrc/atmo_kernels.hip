@@ -149,6 +149,19 @@ __device__ __forceinline__ float exact_div_uniform(float a, float c, float rc) {
 #ifndef ATMO_DIRECT_PROLOGUE_DIET   // the cloudless direct-light kernels take the short forms too
 #define ATMO_DIRECT_PROLOGUE_DIET 1
 #endif
+// The camera prologue of the same family (shade_pixel; RenderConsts::prologue_mode, the host's prologue_camera_fill states the premises): short forms chosen
+// per draw by scalar branches on a wave-uniform mask, the same bits as the general forms, which stay the fall-back.  ATMO_PROLOGUE_CAMERA_FORMS: which of
+// them are compiled in, for A/B builds -- 1 the two 4 x 4 products without their zero terms, 2 the view step's length by the exact reciprocal of a power of
+// two, 4 no ground-sphere hit under a zero sphere_depth_factor, 8 the uniform products handed over from the host.
+#ifndef ATMO_PROLOGUE_CAMERA_FORMS
+#define ATMO_PROLOGUE_CAMERA_FORMS 15
+#endif
+// a wave-uniform value in a VGPR: an SGPR operand makes a fast-class instruction a slow one, which matters inside the view loop
+__device__ __forceinline__ float uniform_in_vgpr(float s) {
+    float v;
+    asm("v_mov_b32 %0, %1" : "=v"(v) : "s"(s));
+    return v;
+}
 template <bool DIET = true>
 __device__ __forceinline__ float prologue_sqrt(float x) { return DIET ? exact_sqrt(x) : ieee_sqrt(x); }
 template <bool DIET = true>
@@ -229,6 +242,14 @@ __device__ __forceinline__ SphereHit sphere_setup(V3 center, V3 dir) {
 template <bool DIET = true>
 __device__ __forceinline__ float2 hit_radius(SphereHit s, float radius) {
     float h = radius * radius - s.qc2;
+    if (h < 0.0f) return make_float2(1000000.0f, 1000000.0f);
+    h = prologue_sqrt<DIET>(h);
+    return make_float2(-s.b - h, -s.b + h);
+}
+// the same with radius * radius from the host (RenderConsts::atmosphere_radius2, planet_radius2)
+template <bool DIET = true>
+__device__ __forceinline__ float2 hit_radius2(SphereHit s, float radius2) {
+    float h = radius2 - s.qc2;
     if (h < 0.0f) return make_float2(1000000.0f, 1000000.0f);
     h = prologue_sqrt<DIET>(h);
     return make_float2(-s.b - h, -s.b + h);
@@ -1164,7 +1185,9 @@ __device__ __forceinline__ float sun_od_direct(const LightMarchConsts &k, float 
 // (H / R ~ 0.05) 64 steps of that reached 1.08e-4 of alpha (2 of 252 fuzz scenes, round 3).  Three more subtractions per step, 4-7 % on
 // the direct-light loop, so the kernels with up to 32 steps keep the cheaper form (and their ISA): this is a separate instantiation.
 __device__ __forceinline__ V3 scale_unfused(V3 d, float s) { return V3{d.x * s, d.y * s, d.z * s}; }  // no contraction here: products rounded on their own
-template <bool DIRECT, int LSTEPS, int SPLIT, bool VIEWPOS = false>
+// HANDED (the cloudless direct-light kernels, ATMO_PROLOGUE_CAMERA_FORMS & 8): density^2, density^2 / 8, atmosphere_radius^2 and -coeff * LOG2E come
+// from the host, one IEEE operation each and therefore the same bits; those the loop reads are moved to VGPRs once.
+template <bool DIRECT, int LSTEPS, int SPLIT, bool VIEWPOS = false, bool HANDED = false>
 __device__ __forceinline__ float4 march_atmosphere(const RenderConsts &rc, V3 dir, float t_begin, float step_len, float jitter, int half) {
 #pragma clang fp contract(fast)
     const int n0 = SPLIT == 2 ? (rc.view_steps + 1) / 2 : rc.view_steps;
@@ -1174,13 +1197,15 @@ __device__ __forceinline__ float4 march_atmosphere(const RenderConsts &rc, V3 di
     const float inv_h = hw_rcp(rc.atmosphere_height);
     const float ninv_h = -inv_h;
     const float c1 = fmaf(rc.planet_radius, inv_h, 1.0f);
-    const float dens2 = rc.density * rc.density;
-    const float kr = -rc.coeff[0] * LOG2E, kg = -rc.coeff[1] * LOG2E, kb = -rc.coeff[2] * LOG2E;
+    const float dens2 = HANDED ? rc.dens2 : rc.density * rc.density;
+    const float kr = HANDED ? uniform_in_vgpr(rc.coeff_log2e[0]) : -rc.coeff[0] * LOG2E;
+    const float kg = HANDED ? uniform_in_vgpr(rc.coeff_log2e[1]) : -rc.coeff[1] * LOG2E;
+    const float kb = HANDED ? uniform_in_vgpr(rc.coeff_log2e[2]) : -rc.coeff[2] * LOG2E;
     const float sx = rc.sun_dir[0], sy = rc.sun_dir[1], sz = rc.sun_dir[2];
-    const float ratm2 = rc.atmosphere_radius * rc.atmosphere_radius;
+    const float ratm2 = HANDED ? uniform_in_vgpr(rc.atmosphere_radius2) : rc.atmosphere_radius * rc.atmosphere_radius;
     const int light_steps = LSTEPS > 0 ? LSTEPS : rc.light_steps;
     const float inv_light_steps = LSTEPS > 0 ? 1.0f / (float)(LSTEPS > 0 ? LSTEPS : 1) : hw_rcp((float)light_steps);
-    const LightMarchConsts lmc = {ninv_h, c1, dens2, ratm2, inv_light_steps, light_steps, dens2 * 0.125f};
+    const LightMarchConsts lmc = {ninv_h, c1, dens2, ratm2, inv_light_steps, light_steps, HANDED ? uniform_in_vgpr(rc.dens2_8) : dens2 * 0.125f};
     const float half_w = 0.5f * (float)rc.lut_w, x_off = half_w - 0.5f;
     const float lut_hf = (float)rc.lut_h, y_off = lut_hf - 0.5f;
 
@@ -1198,18 +1223,19 @@ __device__ __forceinline__ float4 march_atmosphere(const RenderConsts &rc, V3 di
     // was 436 bytes (81 VALU instructions), and the draw took 0.0865 ms when its first instruction -- the target of the backward branch -- lay 12 bytes into a 32-byte
     // block, 0.094-0.096 ms (+8.5 ... +11 %) at each of the other seven 4-byte positions; shifted by 32 bytes it was fast again.  With ATMO_LIGHT_FOLD it is 428 bytes
     // (78 VALU instructions) and fast at 4, 12, 20 and 28 bytes into the block, 7-9 % slower at 0, 8, 16 and 24 (profiles/direct_diet/: tools/phase_sweep.py times all
-    // eight); every twin is held at 12 (0.0821 ms; 4 bytes in measured 0.0818).  Instructions inserted INSIDE the loop behind its first one
+    // eight); every twin was held at 12 (0.0821 ms; 4 bytes in measured 0.0818) and, since the camera prologue, is held at 20 -- with it the four fast positions
+    // differ by 1.5-3.5 % and 20 is the one that gains (profiles/prologue_camera/README.md; FAST_PHASE in tools/loop_phase.py).  Instructions inserted INSIDE the loop behind its first one
     // cost their issue slot and nothing else, a 2 x unrolled body has no fast position at all, the LUT kernels' and the cloud kernels' loops do not care.  It is what
     // made rounds 2-5's "any scalar instruction in the preamble costs 8-10 %" and "an 80-SGPR cap (8 waves per SIMD) loses 8 %" -- both moved this loop by 4 bytes
     // (at the right position the capped build is exactly as fast as this one: the eighth wave buys nothing).  tests/test_kernel_twins_host.py holds the position
     // (tools/loop_phase.py reads it from the built library); if a change to the code in front of the loop moves it, ATMO_LOOP_PAD = the number of s_nop that puts it back.
 #ifndef ATMO_LOOP_PAD
-#define ATMO_LOOP_PAD 0   // (the geometric tile order's first form in the preamble needed 1; with its hint tables the loop is back on 12 mod 32 by itself)
+#define ATMO_LOOP_PAD 5   // (the camera prologue moved the loop to 0 mod 32; 5 s_nop put it on 20, in the cloudless direct-light kernels only: HANDED)
 #endif
 #if ATMO_LOOP_PAD > 0
 #define ATMO_STR2(x) #x
 #define ATMO_STR(x) ATMO_STR2(x)
-    if (DIRECT && LSTEPS == 8 && SPLIT == 1 && !VIEWPOS) asm volatile(".rept " ATMO_STR(ATMO_LOOP_PAD) "\n\ts_nop 0\n\t.endr");
+    if (DIRECT && HANDED && LSTEPS == 8 && SPLIT == 1 && !VIEWPOS) asm volatile(".rept " ATMO_STR(ATMO_LOOP_PAD) "\n\ts_nop 0\n\t.endr");
 #endif
     for (int i = 0; i < steps; ++i) {
         if (VIEWPOS) {
@@ -2156,6 +2182,8 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                   "multi-view draws: the default forms, one lane per ray, float or packed targets (KF_VIEWS | KF_TARGET: atmo_render_views_target_kernel)");
     // the short exact prologue: every kernel but cloud + direct-light and raymarched cloud light (prologue_sqrt)
     constexpr bool DIET = (!DIRECT || (ATMO_DIRECT_PROLOGUE_DIET && !CLOUDS)) && !((FLAGS & KF_CLOUDS) && (FLAGS & KF_CLOUD_LIGHT_RM));
+    // the camera prologue (ATMO_PROLOGUE_CAMERA_FORMS): the same family
+    constexpr int CAMF = (DIRECT && !CLOUDS && ATMO_DIRECT_PROLOGUE_DIET) ? ATMO_PROLOGUE_CAMERA_FORMS : 0;
     constexpr bool FASTMISS = (ATMO_FAST_MISS_MASK >> ((DIRECT ? 1 : 0) + (CLOUDS ? 2 : 0) + (LITE ? 4 : 0))) & 1;
     static_assert(!LOD || (CLOUDS && PRECISE), "implicit cubemap LOD: precise cloud kernels");
     static_assert(!(LOD && SPLIT == 2) || (!ATMO_REF && !VIEWPOS && !LITE && !DIRECT), "two lanes per ray under the declared sampler: the two BASELINE cloud kernels");
@@ -2252,15 +2280,38 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     const float uvy = pixel_coord<DIET>((float)py + 0.5f, rc.vh, rc.rcp_vh);
     const float nx = uvx * 2.0f - 1.0f, ny = uvy * 2.0f - 1.0f, nz = nonlinear_depth;
     const float *P = rc.inv_p;
-    const float vx = P[0] * nx + P[4] * ny + P[8] * nz + P[12] * 1.0f;
-    const float vy = P[1] * nx + P[5] * ny + P[9] * nz + P[13] * 1.0f;
-    const float vz = P[2] * nx + P[6] * ny + P[10] * nz + P[14] * 1.0f;
-    const float vw = P[3] * nx + P[7] * ny + P[11] * nz + P[15] * 1.0f;
     const float *Vm = rc.inv_v;
+    float vx, vy, vz, vw, ww;
+    // PM_CAMERA (the host's prologue_camera_fill has the proof): the rows without their zero terms, for a wave whose lanes all have a finite, nonzero vw --
+    // a NaN or inf depth sample (0 nz is a NaN in the general rows) or vw = +-0 (the dropped zeros decide the sign of ww) sends the whole wave below
+    bool cam = false;   // wave-uniform
+    if constexpr ((CAMF & 5) != 0) {
+        if (rc.prologue_mode & PM_CAMERA) {
+            const float vws = P[11] * nz + P[15];
+            // v_cmp_class: -normal, -subnormal, +subnormal, +normal
+            // ... and the lanes of the column / row with nx = 0 / ny = 0 where a -0 constant term makes the sign of that zero the lane's (cam_skip_*)
+            cam = __builtin_amdgcn_ballot_w64(!__builtin_amdgcn_classf(vws, 0x198) || px == rc.cam_skip_px || py == rc.cam_skip_py) == 0ull;
+            if constexpr ((CAMF & 1) != 0) {
+                if (cam) {
+                    vx = P[0] * nx + P[12];
+                    vy = P[5] * ny + P[13];
+                    vz = P[14];
+                    vw = vws;
+                    ww = vws;
+                }
+            }
+        }
+    }
+    if ((CAMF & 1) == 0 || !cam) {
+        vx = P[0] * nx + P[4] * ny + P[8] * nz + P[12] * 1.0f;
+        vy = P[1] * nx + P[5] * ny + P[9] * nz + P[13] * 1.0f;
+        vz = P[2] * nx + P[6] * ny + P[10] * nz + P[14] * 1.0f;
+        vw = P[3] * nx + P[7] * ny + P[11] * nz + P[15] * 1.0f;
+        ww = Vm[3] * vx + Vm[7] * vy + Vm[11] * vz + Vm[15] * vw;
+    }
     const float wx = Vm[0] * vx + Vm[4] * vy + Vm[8] * vz + Vm[12] * vw;
     const float wy = Vm[1] * vx + Vm[5] * vy + Vm[9] * vz + Vm[13] * vw;
     const float wz = Vm[2] * vx + Vm[6] * vy + Vm[10] * vz + Vm[14] * vw;
-    const float ww = Vm[3] * vx + Vm[7] * vy + Vm[11] * vz + Vm[15] * vw;
     float pwx, pwy, pwz;
     world_div3<DIET>(wx, wy, wz, ww, pwx, pwy, pwz);
     const float ddx = rc.cam_pos_world[0] - pwx, ddy = rc.cam_pos_world[1] - pwy, ddz = rc.cam_pos_world[2] - pwz;
@@ -2273,7 +2324,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     const V3 center = {rc.center[0], rc.center[1], rc.center[2]};
 
     const SphereHit sh = sphere_setup(center, dir);
-    const float2 rs_atmo = hit_radius<DIET>(sh, rc.atmosphere_radius);
+    float2 rs_atmo;
+    if constexpr ((CAMF & 8) != 0) rs_atmo = hit_radius2<DIET>(sh, rc.atmosphere_radius2);
+    else rs_atmo = hit_radius<DIET>(sh, rc.atmosphere_radius);
 
     if (rs_atmo.x == rs_atmo.y) {  // discard: nothing reaches the blend stage
         if (rc.store_discards && half == 0 && !helper) {
@@ -2285,10 +2338,15 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     }
     const float t_begin = fmaxf(rs_atmo.x, 0.0f);
     float t_end = fmaxf(rs_atmo.y, 0.0f);
-    const float2 rs_ground = hit_radius<DIET>(sh, rc.planet_radius);
-    float gd = 10000000.0f;
-    if (rs_ground.x != rs_ground.y) gd = rs_ground.x;
-    linear_depth = linear_depth * (1.0f - rc.sphere_depth_factor) + gd * rc.sphere_depth_factor;
+    // PM_NO_SPHERE_DEPTH: gd is finite (cam: a finite direction) and multiplied by a zero, linear_depth is no -0: the sum below is linear_depth
+    if (!((CAMF & 4) != 0 && cam && (rc.prologue_mode & PM_NO_SPHERE_DEPTH))) {
+        float2 rs_ground;
+        if constexpr ((CAMF & 8) != 0) rs_ground = hit_radius2<DIET>(sh, rc.planet_radius2);
+        else rs_ground = hit_radius<DIET>(sh, rc.planet_radius);
+        float gd = 10000000.0f;
+        if (rs_ground.x != rs_ground.y) gd = rs_ground.x;
+        linear_depth = linear_depth * (1.0f - rc.sphere_depth_factor) + gd * rc.sphere_depth_factor;
+    }
     t_end = fminf(t_end, linear_depth);
 
     const float jx = rc.vw * uvx, jy = rc.vh * uvy;
@@ -2303,8 +2361,11 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
         if constexpr (ATMO_REF && SPLIT == 1) {
             rgba = march_atmosphere_v2_precise<DIRECT>(rc, dir, t_begin, t_end, jitter);  // reference order (atmo_set_precision 2)
         } else {
-            const float view_step_len = ieee_div(t_end - t_begin, (float)rc.view_steps);
-            rgba = march_atmosphere<DIRECT, LSTEPS, ASPLIT, VIEWPOS>(rc, dir, t_begin, view_step_len, jitter, ahalf);
+            float view_step_len;
+            // PM_POW2_STEPS: the quotient by 2^k and the product with 2^-k round the same real number
+            if ((CAMF & 2) != 0 && (rc.prologue_mode & PM_POW2_STEPS)) view_step_len = (t_end - t_begin) * rc.inv_view_steps;
+            else view_step_len = ieee_div(t_end - t_begin, (CAMF & 8) != 0 ? rc.view_steps_f : (float)rc.view_steps);
+            rgba = march_atmosphere<DIRECT, LSTEPS, ASPLIT, VIEWPOS, (CAMF & 8) != 0>(rc, dir, t_begin, view_step_len, jitter, ahalf);
         }
     }
 
@@ -2472,8 +2533,8 @@ __device__ __forceinline__ uint32_t geo_tile(const RenderConsts &rc, uint32_t b)
     const uint32_t o = m - (lo * tx - rc.geo_prefix[lo]), first = rc.geo_first[lo], len = rc.geo_prefix[lo + 1] - rc.geo_prefix[lo];
     return lo * tx + (o < first ? o : o + len);
 }
-#ifndef ATMO_LOOP_PAD_GEO   // s_nop in front of shade_pixel in the twin kernels <4 | KF_GEO, 8, 1>: puts their view loop 12 bytes into a 32-byte block
-#define ATMO_LOOP_PAD_GEO 5
+#ifndef ATMO_LOOP_PAD_GEO   // s_nop in front of shade_pixel in the twin kernels <4 | KF_GEO, 8, 1>: puts their view loop FAST_PHASE (20) bytes into a 32-byte block
+#define ATMO_LOOP_PAD_GEO 7
 #endif
 // N s_nop in front of a kernel's code: what every ATMO_LOOP_PAD_* knob below counts (tools/phase_sweep.py sweeps them, tools/loop_phase.py names them)
 #define ATMO_PAD_STR2(x) #x
@@ -2535,7 +2596,7 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render
 // kernels without raymarched light need the bound spelled out: their twins fit 62 VGPRs (eight waves per SIMD) under the common bound of six, these came
 // out at 68 (seven) without it.
 #ifndef ATMO_LOOP_PAD_VIEWS   // s_nop at the head of <KF_VIEWS | KF_LIGHT_DIRECT, 8>
-#define ATMO_LOOP_PAD_VIEWS 3
+#define ATMO_LOOP_PAD_VIEWS 7
 #endif
 constexpr int views_min_waves(int flags) {
     return ((flags & KF_CLOUDS) && !(flags & (KF_CLOUD_LIGHT_RM | KF_CUBE_LOD))) ? 8 : render_min_waves(flags);
@@ -2563,7 +2624,7 @@ constexpr int views_min_waves(int flags) {
 template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_kernel(const RenderConsts *__restrict__ table, const ViewsConsts vc) {
     static_assert((FLAGS & KF_VIEWS) != 0, "multi-view kernels carry KF_VIEWS");
-    // the headline kernel's twin <KF_VIEWS | KF_LIGHT_DIRECT, 8>: its view loop on ITS fast position, 12 bytes into a 32-byte block, as the float kernel's
+    // the headline kernel's twin <KF_VIEWS | KF_LIGHT_DIRECT, 8>: its view loop on ITS fast position, FAST_PHASE (20) bytes into a 32-byte block, as the float kernel's
     // (march_atmosphere; tools/loop_phase.py reads it, tests/test_kernel_twins_host.py holds it there)
     if constexpr (FLAGS == (KF_VIEWS | KF_LIGHT_DIRECT) && LSTEPS == 8) ATMO_HEAD_PAD(ATMO_LOOP_PAD_VIEWS);
     ATMO_VIEWS_KERNEL_BODY(vc, 1, nullptr, nullptr, nullptr)
@@ -2581,12 +2642,12 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) __attribute__((a
 #define ATMO_LOOP_PAD_TARGET 3
 #endif
 #ifndef ATMO_LOOP_PAD_TARGET_GEO   // ... and more of them in the geometric-order twin, on top of ATMO_LOOP_PAD_GEO
-#define ATMO_LOOP_PAD_TARGET_GEO 6
+#define ATMO_LOOP_PAD_TARGET_GEO 5
 #endif
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
 __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_target_kernel(const RenderConsts rc, const TargetConsts tc) {
     static_assert((FLAGS & KF_TARGET) != 0, "target kernels carry KF_TARGET");
-    // the headline kernel's twins <KF_TARGET | KF_LIGHT_DIRECT [| KF_GEO], 8, 1>: their view loop on ITS fast position, 12 bytes into a 32-byte block, as
+    // the headline kernel's twins <KF_TARGET | KF_LIGHT_DIRECT [| KF_GEO], 8, 1>: their view loop on ITS fast position, FAST_PHASE (20) bytes into a 32-byte block, as
     // the float kernels' (march_atmosphere; tools/loop_phase.py reads all four, tests/test_kernel_twins_host.py holds these two there)
     if constexpr ((FLAGS & ~KF_GEO) == (KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8 && SPLIT == 1) ATMO_HEAD_PAD(ATMO_LOOP_PAD_TARGET);
     if constexpr (FLAGS == (KF_TARGET | KF_LIGHT_DIRECT | KF_GEO) && LSTEPS == 8 && SPLIT == 1) ATMO_HEAD_PAD(ATMO_LOOP_PAD_TARGET_GEO);
@@ -2605,13 +2666,13 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render
 // atmo_render_target_kernel is a substring of it), so that every other kernel keeps its code to the byte.  VGPRs: launch bounds as the float batch's
 // (views_min_waves); profiles/views/README.md holds the table against the float-batch twins.
 #ifndef ATMO_LOOP_PAD_VIEWS_TARGET   // s_nop at the head of <KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8>
-#define ATMO_LOOP_PAD_VIEWS_TARGET 3
+#define ATMO_LOOP_PAD_VIEWS_TARGET 7
 #endif
 template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_target_kernel(const RenderConsts *__restrict__ table,
                                                                                                          const ViewsTargetConsts vtc) {
     static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_TARGET) != 0, "multi-view target kernels carry KF_VIEWS | KF_TARGET");
-    // the headline kernel's twin <KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8>: its view loop on ITS fast position, 12 bytes into a 32-byte block, as the
+    // the headline kernel's twin <KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8>: its view loop on ITS fast position, FAST_PHASE (20) bytes into a 32-byte block, as the
     // other twins' (march_atmosphere; tools/loop_phase.py reads it, tests/test_kernel_twins_host.py holds it there)
     if constexpr (FLAGS == (KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8) ATMO_HEAD_PAD(ATMO_LOOP_PAD_VIEWS_TARGET);
     ATMO_VIEWS_KERNEL_BODY(vtc.v, 1, nullptr, &vtc.target[view], nullptr)
@@ -3472,16 +3533,16 @@ hipError_t launch_bake(const BakeConsts &bc, hipStream_t stream) {
 #define ATMO_LOOP_PAD_DEPTH 2
 #endif
 #ifndef ATMO_LOOP_PAD_DEPTH_GEO     // ... and more of them in the geometric-order twin, on top of ATMO_LOOP_PAD_GEO
-#define ATMO_LOOP_PAD_DEPTH_GEO 2
+#define ATMO_LOOP_PAD_DEPTH_GEO 3
 #endif
 #ifndef ATMO_LOOP_PAD_DEPTH_VIEWS   // ... and at the head of <KF_DEPTH | KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8>
-#define ATMO_LOOP_PAD_DEPTH_VIEWS 0   // (0: this twin's loop lands on 12 mod 32 by itself; the knob stands for the next change in front of it)
+#define ATMO_LOOP_PAD_DEPTH_VIEWS 6
 #endif
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
 __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_depth_target_kernel(const RenderConsts rc, const TargetConsts tc,
                                                                                                       const DepthConsts dc) {
     static_assert((FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0, "depth-source kernels carry KF_DEPTH | KF_TARGET");
-    // the headline kernel's twins: their view loop 12 bytes into a 32-byte block, as every twin's before them (march_atmosphere; tools/loop_phase.py reads
+    // the headline kernel's twins: their view loop FAST_PHASE (20) bytes into a 32-byte block, as every twin's before them (march_atmosphere; tools/loop_phase.py reads
     // them, tests/test_kernel_twins_host.py holds them there)
     if constexpr ((FLAGS & ~KF_GEO) == (KF_DEPTH | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8 && SPLIT == 1) ATMO_HEAD_PAD(ATMO_LOOP_PAD_DEPTH);
     if constexpr (FLAGS == (KF_DEPTH | KF_TARGET | KF_LIGHT_DIRECT | KF_GEO) && LSTEPS == 8 && SPLIT == 1) ATMO_HEAD_PAD(ATMO_LOOP_PAD_DEPTH_GEO);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where the view loop of the direct-light kernels sits in the instruction stream (round 6, profiles/round6/ab_loop_phase.txt): the draw is 8.5-11 % slower
-unless the loop's first instruction -- the target of its backward branch -- lies 12 bytes into a 32-byte block.
+unless the loop's first instruction -- the target of its backward branch -- lies on the fast one of the eight 4-byte positions of a 32-byte block (FAST_PHASE: 12 bytes in until the camera prologue, 20 since).
 
     python tools/loop_phase.py [libatmo_hip.so] [kernel substring, default: each of HEADLINE_TWINS]
 
@@ -13,7 +13,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
-FAST_PHASE = 12   # bytes into the 32-byte block
+FAST_PHASE = 20   # bytes into the 32-byte block (12 until the camera prologue: profiles/prologue_camera/README.md)
 
 
 def device_code_object(lib, out):
