@@ -33,6 +33,10 @@
 
 namespace atmo {
 
+// Build switches.  Retired experiments: the losing arms of the settled A/B switches are removed (rounds 1-3 in round 4, rounds 4-6 and the two
+// diets after d1d99b5); NOTES.md ("Retired ablation switches", both tables) lists each switch, the record under profiles/ that settled it and the
+// last commit that still holds its code.
+//
 // Workgroup tile in pixels.  16x16 = 4 waves, 16x8 = 2 (shipped), 16x4 = one wave per workgroup.  Waves never
 // synchronise (the LDS queue of clouds_high_rm is wave-private), so the choice is purely scheduling: finer tiles give the
 // dispatcher and the tile-order feedback a finer grain.  profiles/round2/ab_tile_height.txt: 16x8 and 16x4 are 3 % faster
@@ -47,8 +51,6 @@ constexpr int TILE_H = ATMO_TILE_H;
 #ifndef ATMO_WAVE_W
 #define ATMO_WAVE_W 16
 #endif
-// Retired experiments: the losing arms of the round 1-3 A/B switches were removed in round 4; NOTES.md ("Retired ablation
-// switches") lists each switch, the record under profiles/ that settled it and the last commit that still holds its code.
 constexpr int WAVE_W = ATMO_WAVE_W;
 constexpr int WAVE_H = 64 / WAVE_W;
 static_assert(WAVE_W == 16 || WAVE_W == 8 || WAVE_W == 32, "wave tile");
@@ -57,16 +59,6 @@ constexpr float LOG2E = 1.44269504088896340736f;
 // ---- hardware transcendental units (approximate, ~1 ulp) ---------------------------------------
 __device__ __forceinline__ float hw_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float hw_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
-// The declared sampler's lambda in the oracle's own operations (round 6; cube_lod_partner_coords, cube_lod_select).  0: rounds 2-5's arithmetic, the A/B arm.
-#ifndef ATMO_LOD_LAMBDA_EXACT
-#define ATMO_LOD_LAMBDA_EXACT 1
-#endif
-#ifndef ATMO_RCP_NR   // Newton steps of exact_rcp (1: checked on every significand by atmo_selftest_exact_math)
-#define ATMO_RCP_NR 1
-#endif
-#ifndef ATMO_LOD_LOG2_CR
-#define ATMO_LOD_LOG2_CR 1
-#endif
 __device__ __forceinline__ float hw_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float hw_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float sat(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f); }
@@ -78,14 +70,12 @@ __device__ __forceinline__ float mixf(float a, float b, float t) { return a * (1
 // __fsqrt_rn to the native (1 ulp) square root.  Used in the once-per-pixel prologue and the LUT bake.
 __device__ __forceinline__ float ieee_sqrt(float x) { return __builtin_sqrtf(x); }
 __device__ __forceinline__ float ieee_div(float a, float b) { return a / b; }
-// RN(1 / d) from v_rcp_f32 (1 ulp) and ATMO_RCP_NR Newton step(s): 3 instructions against the ~11 of the compiler's IEEE division (v_div_scale /
+// RN(1 / d) from v_rcp_f32 (1 ulp) and one Newton step: 3 instructions against the ~11 of the compiler's IEEE division (v_div_scale /
 // v_div_fmas / v_div_fixup).  Equal to 1.0f / d for every normal d whose reciprocal is normal: checked on the device over all 2^23 significands of
 // fifty binades (atmo_selftest_exact_math, the divide counter; v_rcp_f32's error depends on the significand alone).
 __device__ __forceinline__ float exact_rcp(float d) {
-    float r = hw_rcp(d);
-#pragma unroll
-    for (int k = 0; k < ATMO_RCP_NR; ++k) r = __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
-    return r;
+    const float r = hw_rcp(d);
+    return __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
 }
 
 // Correctly rounded sqrt for the per-step cloud chain, x >= 0 and not denormal/inf/nan (x = |pos|^2 ~ 1e4):
@@ -142,13 +132,8 @@ __device__ __forceinline__ float exact_div_uniform(float a, float c, float rc) {
 #endif
 // Both forms give the same bits; which one a kernel variant uses is a measured choice (profiles/round2/ab_prologue.txt:
 // the short forms gain 3-4 % on the baked-LUT atmosphere kernels; the raymarched-cloud-light kernels measured 2-3 % slower with them
-// at 1920x1080 and keep the long forms).  The cloudless direct-light kernels measured "2-3 % slower" too in round 2 -- an artefact: the
-// shorter prologue moved their view loop off its fast position (march_atmosphere).  Swept over all eight positions the short forms
-// gain 2.4 % there (profiles/direct_diet/sweep_variants.txt, variant a), and ATMO_DIRECT_PROLOGUE_DIET = 1 gives them to every
-// DIRECT && !CLOUDS kernel; 0 is the long form, for A/B builds.
-#ifndef ATMO_DIRECT_PROLOGUE_DIET   // the cloudless direct-light kernels take the short forms too
-#define ATMO_DIRECT_PROLOGUE_DIET 1
-#endif
+// at 1920x1080 and keep the long forms).  The cloudless direct-light kernels take the short forms: with the view loop held on its fast
+// position (march_atmosphere) they gain 2.4 % there (profiles/direct_diet/sweep_variants.txt, variant a).
 // The camera prologue of the same family (shade_pixel; RenderConsts::prologue_mode, the host's prologue_camera_fill states the premises): short forms chosen
 // per draw by scalar branches on a wave-uniform mask, the same bits as the general forms, which stay the fall-back.  ATMO_PROLOGUE_CAMERA_FORMS: which of
 // them are compiled in, for A/B builds -- 1 the two 4 x 4 products without their zero terms, 2 the view step's length by the exact reciprocal of a power of
@@ -761,21 +746,13 @@ __device__ __forceinline__ float cube_sample_lod(const RenderConsts &rc, V3 d, b
         cube_frame(isz, isy, pos, dv, dsc, dtc, dma);
         const float ma2 = ma + dma;
         if (!(ma2 > 0.0f)) return;
-    #if ATMO_LOD_DIV_FORM == 0
-    const float inv = ieee_div(0.5f, ma * ma2);
-#else
-    const float inv = 0.5f * exact_rcp(ma * ma2);   // 0.5 / d = 0.5 RN(1 / d): the scaling is exact
-#endif
+        const float inv = ieee_div(0.5f, ma * ma2);
         const float ds = (dsc * ma - sc * dma) * inv, dt = (dtc * ma - tc * dma) * inv;
         rho2 = fmaxf(rho2, (ds * ds + dt * dt) * n2);
     };
     axis(vx, dx);
     axis(vy, dy);
-#if ATMO_LOD_LAMBDA_EXACT && ATMO_LOD_LOG2_CR
     float lambda = rho2 > 1.0f ? 0.5f * log2_cr(rho2, lvl + CUBE_LEVEL_TABLE) : 0.0f;   // correctly rounded, see cube_lod_select; rho2 <= 1: clamped to 0 below anyway
-#else
-    float lambda = rho2 > 0.0f ? 0.5f * __builtin_amdgcn_logf(rho2) : 0.0f;  // v_log_f32 = log2
-#endif
     lambda = fminf(fmaxf(lambda, 0.0f), (float)(rc.cube_levels - 1));
     const float lf = floorf(lambda), fr = lambda - lf;
     const int lo = (int)lf, hi = lo + 1 < rc.cube_levels ? lo + 1 : lo;
@@ -916,7 +893,7 @@ template <bool EXACT>
 __device__ __forceinline__ CubeLod cube_lod_select(const RenderConsts &rc, float rho2, const f32x4 *lvl) {
     // clamp(0.5 log2(rho2), 0, levels - 1); rho2 <= 1 (or 0, or NaN) => lambda = 0
     float lambda;
-    if (EXACT && ATMO_LOD_LOG2_CR) {
+    if (EXACT) {
         // log2 correctly rounded and the oracle's bits (log2_cr); rho^2 <= 1: lambda = 0 (log2(1) = 0)
         float l2 = 0.0f;
         if (rho2 > 1.0f) l2 = log2_cr(rho2, lvl + CUBE_LEVEL_TABLE);
@@ -1086,10 +1063,9 @@ __device__ __forceinline__ float cube_sample_lod_quad(const RenderConsts &rc, fl
     if (!rc.cube_lod_fast)  // faces that are not a power of two (or above 1024): the general sampler on the partners' directions (exact as it stands)
         return cube_sample_lod(rc, d, nb->vx, cube_dir_from_coords(q.fidx, q.scx, q.tcx, q.masx), nb->vy, cube_dir_from_coords(q.fidy, q.scy, q.tcy, q.masy), nb->lvl);
     const float nf = (float)rc.cube_n, n2q = 0.25f * (nf * nf);   // n^2 / 4: see cube_lod_partner_coords
-    constexpr bool EXACT = ATMO_LOD_LAMBDA_EXACT != 0;
-    float rho2 = cube_lod_partner_coords<EXACT>(fid, sc, tc, ma2x, ma, d, nb->vx, q.fidx, q.scx, q.tcx, q.masx, n2q, 0.0f);
-    rho2 = cube_lod_partner_coords<EXACT>(fid, sc, tc, ma2x, ma, d, nb->vy, q.fidy, q.scy, q.tcy, q.masy, n2q, rho2);
-    return cube_lod_finish(rc, fid, qs, qt, cube_lod_select<EXACT>(rc, rho2, nb->lvl), nb->lvl);
+    float rho2 = cube_lod_partner_coords<true>(fid, sc, tc, ma2x, ma, d, nb->vx, q.fidx, q.scx, q.tcx, q.masx, n2q, 0.0f);
+    rho2 = cube_lod_partner_coords<true>(fid, sc, tc, ma2x, ma, d, nb->vy, q.fidy, q.scy, q.tcy, q.masy, n2q, rho2);
+    return cube_lod_finish(rc, fid, qs, qt, cube_lod_select<true>(rc, rho2, nb->lvl), nb->lvl);
 }
 
 // The direct light march of one view sample (ATMO_LIGHT_DIRECT; SURVEY.md 8d "N view x M light steps"): the quantity the LUT
@@ -1099,39 +1075,36 @@ __device__ __forceinline__ float cube_sample_lod_quad(const RenderConsts &rc, fl
 struct LightMarchConsts {
     float ninv_h, c1, dens2, ratm2, inv_light_steps;
     int light_steps;
-    float dens2_8;   // dens2 / 8, exact (ATMO_LIGHT_FOLD)
+    float dens2_8;   // dens2 / 8, exact (the 8-step form's folding)
 };
-// ATMO_LIGHT_FOLD (the 8-step form; 0 = the arithmetic as first written, for A/B builds): scalings by exact powers of two folded into constants, the
-// same bits with three instructions fewer per view step (profiles/direct_diet/: -2.1 % on the headline draw).
-//   >= 1  lstep = ray_len / 8 is exact, so RN(lstep * (bdot + bdot)) = RN(ray_len * bdot) / 4 and RN(lstep * lstep) = RN(ray_len * ray_len) / 64: with
+// The 8-step form: scalings by exact powers of two folded into constants, the same bits as the arithmetic as first written with three instructions
+// fewer per view step (profiles/direct_diet/sweep_variants.txt, variant c: -2.1 % on the headline draw).
+//   fold  lstep = ray_len / 8 is exact, so RN(lstep * (bdot + bdot)) = RN(ray_len * bdot) / 4 and RN(lstep * lstep) = RN(ray_len * ray_len) / 64: with
 //         m = ray_len * bdot and l2 = ray_len^2 the FMAs fma(j^2 / 64, l2, fma(j / 4, m, r2)) round the very same real numbers (j / 4 and j^2 / 64 are
 //         exact in binary), and RN(RN(acc * ray_len) * (dens2 / 8)) = RN(RN(acc * lstep) * dens2).  Scaling by 2^k commutes with rounding unless a
 //         result is subnormal: ray_len is 0 or at least an ulp of sq or bdot, so on a planet of radius >= 1e-7 l2 and m are normal or 0; on smaller
 //         ones a subnormal l2 or m is below 2^-126 against half an ulp of r2 >= R^2 and both forms add nothing (tests/test_direct_diet_fold.py; on the
 //         device tests/test_direct_diet_gpu.py, radius 2^-45).  acc * ray_len is subnormal only for a sun_od below 1e-37 * dens2.
-//   >= 2  no fmaxf(hh, 0) in front of the root: hh < 0 gives a NaN root, fminf(NaN, NaN) = NaN, and the fmaxf(., 0) behind it returns 0 for a NaN --
+//   root  no fmaxf(hh, 0) in front of the root: hh < 0 gives a NaN root, fminf(NaN, NaN) = NaN, and the fmaxf(., 0) behind it returns 0 for a NaN --
 //         ray_len = 0 as from the clamped form's sq = 0 (min(0, -bdot) clamped at 0).  hh = -0.0 cannot come out of a difference rounded to nearest.
-#ifndef ATMO_LIGHT_FOLD
-#define ATMO_LIGHT_FOLD 2
-#endif
 template <int LSTEPS>
 __device__ __forceinline__ float sun_od_direct(const LightMarchConsts &k, float r2, float bdot, float y3) {
 #pragma clang fp contract(fast)
+    static_assert(LSTEPS == 0 || LSTEPS == 8, "the unrolled 8-step form, or light_steps at run time");
     const float ninv_h = k.ninv_h, c1 = k.c1, dens2 = k.dens2, ratm2 = k.ratm2, inv_light_steps = k.inv_light_steps;
     const int light_steps = k.light_steps;
     // chord from the sample to the outer sphere along the sun direction, then a left Riemann sum.
     // x1 - max(x0, 0) with x0 = -b - sq, x1 = sq - b  ==  min(x1 - x0, x1) = min(2 sq, sq - b)
     const float hh = ratm2 - (r2 - bdot * bdot);
-    const float sq = hw_sqrt((ATMO_LIGHT_FOLD >= 2 && LSTEPS == 8) ? hh : fmaxf(hh, 0.0f));
+    const float sq = hw_sqrt(LSTEPS == 8 ? hh : fmaxf(hh, 0.0f));
     // inside the outer sphere the forward exit distance is >= 0; hh < 0 (rounding at the shell) gives sq = 0 and
     // min(0, -b), which the max folds to the reference's 0
     const float ray_len = fmaxf(fminf(sq + sq, sq - bdot), 0.0f);
     const float lstep = ray_len * inv_light_steps;
     float acc = y3;  // sample 0 sits on the view sample itself
     if (LSTEPS == 8) {
-        constexpr bool FOLD = ATMO_LIGHT_FOLD != 0;
-        const float lb = FOLD ? ray_len * bdot : lstep * (bdot + bdot), l2 = FOLD ? ray_len * ray_len : lstep * lstep;
-        constexpr float kb = FOLD ? 0.25f : 1.0f, k2 = FOLD ? 0.015625f : 1.0f;
+        const float lb = ray_len * bdot, l2 = ray_len * ray_len;
+        constexpr float kb = 0.25f, k2 = 0.015625f;
         float q[8], rr[8];
 #pragma unroll
         for (int j = 1; j < 8; ++j) q[j] = fmaf((float)(j * j) * k2, l2, fmaf((float)j * kb, lb, r2));
@@ -1144,25 +1117,15 @@ __device__ __forceinline__ float sun_od_direct(const LightMarchConsts &k, float 
             const float yy = sat(fmaf(rr[j], ninv_h, c1));
             acc = fmaf(yy * yy, yy, acc);
         }
-        if (FOLD) return acc * ray_len * k.dens2_8;
-    } else if (LSTEPS > 0) {
-        // |o + j*l*sun|^2 = r2 + j*(l*2b) + j^2*(l*l), |sun| = 1: two FMAs per sample
-        const float lb = lstep * (bdot + bdot), l2 = lstep * lstep;
-#pragma unroll
-        for (int j = 1; j < (LSTEPS > 0 ? LSTEPS : 1); ++j) {
-            const float rr = hw_sqrt(fmaf((float)(j * j), l2, fmaf((float)j, lb, r2)));
-            const float yy = sat(fmaf(rr, ninv_h, c1));
-            acc = fmaf(yy * yy, yy, acc);
-        }
-    } else {
-        const float b2 = bdot + bdot;
-        float sl = lstep;
-        for (int j = 1; j < light_steps; ++j) {
-            const float rr = hw_sqrt(fmaf(sl, sl + b2, r2));
-            const float yy = sat(fmaf(rr, ninv_h, c1));
-            acc = fmaf(yy * yy, yy, acc);
-            sl += lstep;
-        }
+        return acc * ray_len * k.dens2_8;
+    }
+    const float b2 = bdot + bdot;
+    float sl = lstep;
+    for (int j = 1; j < light_steps; ++j) {
+        const float rr = hw_sqrt(fmaf(sl, sl + b2, r2));
+        const float yy = sat(fmaf(rr, ninv_h, c1));
+        acc = fmaf(yy * yy, yy, acc);
+        sl += lstep;
     }
     return acc * lstep * dens2;
 }
@@ -1221,7 +1184,7 @@ __device__ __forceinline__ float4 march_atmosphere(const RenderConsts &rc, V3 di
 
     // WHERE THIS LOOP SITS IN THE INSTRUCTION STREAM IS PART OF THE HEADLINE KERNEL'S SPEED (round 6, profiles/round6/ab_loop_phase.txt).  In <4, 8, 1> the loop
     // was 436 bytes (81 VALU instructions), and the draw took 0.0865 ms when its first instruction -- the target of the backward branch -- lay 12 bytes into a 32-byte
-    // block, 0.094-0.096 ms (+8.5 ... +11 %) at each of the other seven 4-byte positions; shifted by 32 bytes it was fast again.  With ATMO_LIGHT_FOLD it is 428 bytes
+    // block, 0.094-0.096 ms (+8.5 ... +11 %) at each of the other seven 4-byte positions; shifted by 32 bytes it was fast again.  With sun_od_direct's folding it is 428 bytes
     // (78 VALU instructions) and fast at 4, 12, 20 and 28 bytes into the block, 7-9 % slower at 0, 8, 16 and 24 (profiles/direct_diet/: tools/phase_sweep.py times all
     // eight); every twin was held at 12 (0.0821 ms; 4 bytes in measured 0.0818) and, since the camera prologue, is held at 20 -- with it the four fast positions
     // differ by 1.5-3.5 % and 20 is the one that gains (profiles/prologue_camera/README.md; FAST_PHASE in tools/loop_phase.py).  Instructions inserted INSIDE the loop behind its first one
@@ -1654,20 +1617,13 @@ __device__ __forceinline__ MarchRay cloud_march_ray(const RenderConsts &rc, V3 d
     return m;
 }
 
-// The uniforms the density evaluation reads at every sample, in VGPRs (round 4, late).  The declared-sampler kernels run at the SGPR ceiling and
-// spill uniforms to VGPR lanes: every use in the march loop was a v_readlane (18 static in <49, 0, 1>, 0 with this), on top of the slow-class issue
-// of a VALU instruction with an SGPR operand.  `clouds_high` 0.1907 -> 0.1745 ms, `clouds` 0.1141 -> 0.1057, P_limb -9 %, v1 -3.4 %;
-// the level-0 kernels, which spill nothing, are unchanged (+-0.5 %): profiles/round4/ab_vgpr_uniforms.txt.  NOT a general rule: the sun direction
+// The uniforms the density evaluation reads at every sample, in VGPRs: the declared-sampler kernels run at the SGPR ceiling and would spill them to VGPR
+// lanes, a v_readlane at every use in the march loop (profiles/round4/ab_vgpr_uniforms.txt: clouds_high -8.5 %).  NOT a general rule: the sun direction
 // of the hand-scheduled atmosphere march in VGPRs costs the headline kernel 10 %.
 // A copy of the constants whose hot fields pass through an empty asm with "+v" operands; everything else of the copy stays what it was.
-#ifndef ATMO_VGPR_UNIFORMS
-#define ATMO_VGPR_UNIFORMS 1
-#endif
 __device__ __forceinline__ void cloud_uniforms_to_vgprs(RenderConsts &v) {
-#if ATMO_VGPR_UNIFORMS
     asm volatile("" : "+v"(v.cov_rot[0]), "+v"(v.cov_rot[1]), "+v"(v.cov_rot[2]), "+v"(v.cov_rot[3]), "+v"(v.clouds_bottom), "+v"(v.cloud_thickness),
                  "+v"(v.inv_cloud_thickness), "+v"(v.coverage_bias));
-#endif
 }
 
 // get_planet_shadow (clouds:153-167) of a lit sample as a light factor: smoothstep(-0.3, 0.3, dot(normalize(pos), -sun_dir)) mixed into
@@ -2181,9 +2137,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     static_assert((FLAGS & KF_VIEWS) == 0 || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0),
                   "multi-view draws: the default forms, one lane per ray, float or packed targets (KF_VIEWS | KF_TARGET: atmo_render_views_target_kernel)");
     // the short exact prologue: every kernel but cloud + direct-light and raymarched cloud light (prologue_sqrt)
-    constexpr bool DIET = (!DIRECT || (ATMO_DIRECT_PROLOGUE_DIET && !CLOUDS)) && !((FLAGS & KF_CLOUDS) && (FLAGS & KF_CLOUD_LIGHT_RM));
-    // the camera prologue (ATMO_PROLOGUE_CAMERA_FORMS): the same family
-    constexpr int CAMF = (DIRECT && !CLOUDS && ATMO_DIRECT_PROLOGUE_DIET) ? ATMO_PROLOGUE_CAMERA_FORMS : 0;
+    constexpr bool DIET = (!DIRECT || !CLOUDS) && !((FLAGS & KF_CLOUDS) && (FLAGS & KF_CLOUD_LIGHT_RM));
+    // the camera prologue (ATMO_PROLOGUE_CAMERA_FORMS): the cloudless direct-light kernels
+    constexpr int CAMF = (DIRECT && !CLOUDS) ? ATMO_PROLOGUE_CAMERA_FORMS : 0;
     constexpr bool FASTMISS = (ATMO_FAST_MISS_MASK >> ((DIRECT ? 1 : 0) + (CLOUDS ? 2 : 0) + (LITE ? 4 : 0))) & 1;
     static_assert(!LOD || (CLOUDS && PRECISE), "implicit cubemap LOD: precise cloud kernels");
     static_assert(!(LOD && SPLIT == 2) || (!ATMO_REF && !VIEWPOS && !LITE && !DIRECT), "two lanes per ray under the declared sampler: the two BASELINE cloud kernels");
@@ -2457,43 +2413,20 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
 // of an animation are coherent, so earlier costs predict this frame's; the picture does not depend on the order.
 // SGPR budget: a SIMD holds 800 SGPRs and a wave is charged its allocation (16-granular) + 16, so waves per SIMD =
 // floor(800 / (ceil(.sgpr_count / 16) * 16 + 16)): .sgpr_count <= 80 => 8, 81-96 => 7, 97-112 => 6, although the occupancy API
-// and the compiler's "Occupancy" line still say 8 (MI355X_MICROARCH.md "Residency").  What the build does: NOTHING -- no kernel is
-// compiled under an SGPR cap.  The direct-light no-cloud kernels sit at .sgpr_count 82 (7 waves per SIMD; their 40 VGPRs would allow
-// 8); the twin kernel atmo_render_kernel_s80 below compiles them to 78 with the same loop ISA.  Round 4 measured that build 8 % SLOWER at
-// 1920x1080 and 4 % at 3840x2160 (profiles/round4/ab_sgpr_cap.txt) and blamed the cap; round 6 found the cause -- the capped build moves the
-// view loop by four bytes, off its fast position (march_atmosphere, profiles/round6/ab_loop_phase.txt 3) -- and that at the right position
-// 8 waves per SIMD are exactly as fast as 7 (0.0867 against 0.0865 ms): the kernel is bound by VALU issue, residency buys nothing.
-// The cloud kernels (86-106 SGPRs, 53-89 VGPRs: 5-7 waves either way) lost
-// 5-7 % under a cap in round 2.  The mask below selects families for the next A/B (amdgpu_num_sgpr takes a literal, hence the twin).
-#ifndef ATMO_MIN_WAVES  // __launch_bounds__ second argument: minimum waves per SIMD the register allocation must allow (0 = none).
+// and the compiler's "Occupancy" line still say 8 (MI355X_MICROARCH.md "Residency").  No kernel is compiled under an SGPR cap: at the fast loop
+// position 8 waves per SIMD are as fast as 7 (profiles/round4/ab_sgpr_cap.txt, profiles/round6/ab_loop_phase.txt 3).
+#ifndef ATMO_MIN_WAVES  // __launch_bounds__ second argument: minimum waves per SIMD the register allocation must allow.
 #define ATMO_MIN_WAVES 6  // 6: only atmo_render_kernel<19 / 23, ..> change (84 -> 80 VGPRs); see ATMO_RMQ_CHUNK
 #endif
 #ifndef ATMO_MIN_WAVES_LOD_RM  // the declared-sampler raymarched-light kernels: bound 4 = no constraint in practice.  The in-place form (rounds 5-6) needs 74-75
 #define ATMO_MIN_WAVES_LOD_RM 4  // VGPRs by itself = six waves; the queue form it replaced needed 111 (round 3) / 88 (round 4) and a bound of 5 cost it +3 %
 #endif                           // (profiles/round3/ab_occupancy.txt).
-#ifndef ATMO_MIN_WAVES_LOD
-#define ATMO_MIN_WAVES_LOD ATMO_MIN_WAVES
-#endif
+constexpr int MIN_WAVES = ATMO_MIN_WAVES, MIN_WAVES_LOD = ATMO_MIN_WAVES, MIN_WAVES_LOD_RM = ATMO_MIN_WAVES_LOD_RM;   // 6 / 6 / 4
 constexpr int render_min_waves(int flags) {
-    return (flags & KF_CUBE_LOD) ? ((flags & KF_CLOUD_LIGHT_RM) ? ATMO_MIN_WAVES_LOD_RM : ATMO_MIN_WAVES_LOD) : ATMO_MIN_WAVES;
-}
-#if ATMO_MIN_WAVES > 0
-#define ATMO_MIN_WAVES_ARG , render_min_waves(FLAGS)
-#else
-#define ATMO_MIN_WAVES_ARG
-#endif
-// ATMO_SGPR_CAP_MASK: bit number (direct + 2 clouds + 4 lite) set = that kernel family runs under the cap (tools/ab_build.sh x -DATMO_SGPR_CAP_MASK=0x02)
-#ifndef ATMO_SGPR_CAP_VALUE
-#define ATMO_SGPR_CAP_VALUE 80
-#endif
-#ifndef ATMO_SGPR_CAP_MASK
-#define ATMO_SGPR_CAP_MASK 0x00
-#endif
-constexpr bool render_sgpr_cap80(int flags) {
-    return (ATMO_SGPR_CAP_MASK >> (((flags & KF_LIGHT_DIRECT) ? 1 : 0) + ((flags & KF_CLOUDS) ? 2 : 0) + ((flags & KF_LITE) ? 4 : 0))) & 1;
+    return (flags & KF_CUBE_LOD) ? ((flags & KF_CLOUD_LIGHT_RM) ? MIN_WAVES_LOD_RM : MIN_WAVES_LOD) : MIN_WAVES;
 }
 
-// The kernel body, textually the same in both kernels (a shared __forceinline__ function changes hipcc's scheduling of the
+// The kernel body, textually the same in every kernel that uses it (a shared __forceinline__ function changes hipcc's scheduling of the
 // preamble, and these kernels are sensitive to exactly that: see the note inside).
 #ifdef ATMO_WAVE_TRACE
 #define ATMO_TRACE_ENTRY const uint64_t trace_entry = __builtin_amdgcn_s_memrealtime();
@@ -2575,13 +2508,13 @@ __device__ __forceinline__ uint32_t geo_tile(const RenderConsts &rc, uint32_t b)
     }
 
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
-__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_kernel(const RenderConsts rc) {
+__global__ __launch_bounds__(TILE_W *TILE_H, render_min_waves(FLAGS)) void atmo_render_kernel(const RenderConsts rc) {
     ATMO_RENDER_KERNEL_BODY(nullptr, nullptr)
 }
 // The far-mode proxy draw (KF_PROXY; atmo_render_proxy): the launch grid covers the box's screen rectangle only (the host clips it), row-major, no tile
 // order, no cost feedback -- its grid changes every frame.  A kernel of its own, so that atmo_render's kernels keep their code to the byte.
 template <int FLAGS, int LSTEPS>
-__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_proxy_kernel(const RenderConsts rc, const ProxyConsts pc) {
+__global__ __launch_bounds__(TILE_W *TILE_H, render_min_waves(FLAGS)) void atmo_render_proxy_kernel(const RenderConsts rc, const ProxyConsts pc) {
     static_assert((FLAGS & KF_PROXY) != 0, "proxy kernels carry KF_PROXY");
     shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, &pc);
 }
@@ -2629,11 +2562,6 @@ __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_r
     if constexpr (FLAGS == (KF_VIEWS | KF_LIGHT_DIRECT) && LSTEPS == 8) ATMO_HEAD_PAD(ATMO_LOOP_PAD_VIEWS);
     ATMO_VIEWS_KERNEL_BODY(vc, 1, nullptr, nullptr, nullptr)
 }
-// the same kernel under an 80-SGPR cap (8 waves per SIMD), for the families render_sgpr_cap80 names (none in the shipped build)
-template <int FLAGS, int LSTEPS, int SPLIT = 1>
-__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) __attribute__((amdgpu_num_sgpr(ATMO_SGPR_CAP_VALUE))) void atmo_render_kernel_s80(const RenderConsts rc) {
-    ATMO_RENDER_KERNEL_BODY(nullptr, nullptr)
-}
 
 // The packed-target draws (KF_TARGET; atmo_render_target / atmo_render_proxy_target, include/atmo_target.h): the bodies of the two kernels above with the
 // target as a second (third) kernel argument, which shade_pixel's stores and blend go through (store_target).  Kernels of their own names, so that the float
@@ -2645,7 +2573,7 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) __attribute__((a
 #define ATMO_LOOP_PAD_TARGET_GEO 5
 #endif
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
-__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_target_kernel(const RenderConsts rc, const TargetConsts tc) {
+__global__ __launch_bounds__(TILE_W *TILE_H, render_min_waves(FLAGS)) void atmo_render_target_kernel(const RenderConsts rc, const TargetConsts tc) {
     static_assert((FLAGS & KF_TARGET) != 0, "target kernels carry KF_TARGET");
     // the headline kernel's twins <KF_TARGET | KF_LIGHT_DIRECT [| KF_GEO], 8, 1>: their view loop on ITS fast position, FAST_PHASE (20) bytes into a 32-byte block, as
     // the float kernels' (march_atmosphere; tools/loop_phase.py reads all four, tests/test_kernel_twins_host.py holds these two there)
@@ -2654,7 +2582,7 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render
     ATMO_RENDER_KERNEL_BODY(&tc, nullptr)
 }
 template <int FLAGS, int LSTEPS>
-__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_proxy_target_kernel(const RenderConsts rc, const ProxyConsts pc,
+__global__ __launch_bounds__(TILE_W *TILE_H, render_min_waves(FLAGS)) void atmo_render_proxy_target_kernel(const RenderConsts rc, const ProxyConsts pc,
                                                                                                       const TargetConsts tc) {
     static_assert((FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0, "proxy target kernels carry KF_PROXY | KF_TARGET");
     shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, &pc, &tc);
@@ -2711,7 +2639,7 @@ __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_r
 //   scan       one workgroup turns the 256 x ORDER_CLASSES counts into the first output index of every (chunk, class);
 //   scatter    the 256 waves write their tiles, in order, behind those indices and clear the costs.
 constexpr int ORDER_BLOCKS = 256, ORDER_CLASSES = TILE_ORDER_CLASSES;
-constexpr int ORDER_SUB_BITS = TILE_ORDER_PER_OCTAVE == 4 ? 2 : 1, ORDER_KEY_BITS = 4 + ORDER_SUB_BITS;   // mantissa bits that split an octave; bits of a class index
+constexpr int ORDER_SUB_BITS = 2, ORDER_KEY_BITS = 4 + ORDER_SUB_BITS;   // mantissa bits that split an octave; bits of a class index
 __device__ __forceinline__ uint32_t tile_cost_class(uint32_t c) {
     if (c == 0) return ORDER_CLASSES - 1;
     const int msb = 31 - __builtin_clz(c);
@@ -3228,8 +3156,7 @@ static hipError_t launch_batch(Kernel kernel, const uint32_t *first_block, const
 
 template <int FLAGS, int LSTEPS, int SPLIT>
 static hipError_t launch_s(const RenderConsts &rc, hipStream_t stream, int blocks) {
-    if constexpr (render_sgpr_cap80(FLAGS)) return launch_tiles(atmo_render_kernel_s80<FLAGS, LSTEPS, SPLIT>, SPLIT, rc, blocks, stream);
-    else return launch_tiles(atmo_render_kernel<FLAGS, LSTEPS, SPLIT>, SPLIT, rc, blocks, stream);
+    return launch_tiles(atmo_render_kernel<FLAGS, LSTEPS, SPLIT>, SPLIT, rc, blocks, stream);
 }
 
 template <int FLAGS, int LSTEPS>
@@ -3500,7 +3427,7 @@ const char *render_kernel_name(int flags, int light_steps, int split) {
         snprintf(name, sizeof(name), "atmo_render_target_kernel<%d, %d, %d>", flags, lsteps, split == 2 ? 2 : 1);
         return name;
     }
-    snprintf(name, sizeof(name), "atmo_render_kernel%s<%d, %d, %d>", render_sgpr_cap80(flags) ? "_s80" : "", flags, lsteps, split == 2 ? 2 : 1);
+    snprintf(name, sizeof(name), "atmo_render_kernel<%d, %d, %d>", flags, lsteps, split == 2 ? 2 : 1);
     return name;
 }
 
@@ -3539,7 +3466,7 @@ hipError_t launch_bake(const BakeConsts &bc, hipStream_t stream) {
 #define ATMO_LOOP_PAD_DEPTH_VIEWS 6
 #endif
 template <int FLAGS, int LSTEPS, int SPLIT = 1>
-__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_depth_target_kernel(const RenderConsts rc, const TargetConsts tc,
+__global__ __launch_bounds__(TILE_W *TILE_H, render_min_waves(FLAGS)) void atmo_render_depth_target_kernel(const RenderConsts rc, const TargetConsts tc,
                                                                                                       const DepthConsts dc) {
     static_assert((FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0, "depth-source kernels carry KF_DEPTH | KF_TARGET");
     // the headline kernel's twins: their view loop FAST_PHASE (20) bytes into a 32-byte block, as every twin's before them (march_atmosphere; tools/loop_phase.py reads
@@ -3549,7 +3476,7 @@ __global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render
     ATMO_RENDER_KERNEL_BODY(&tc, &dc)
 }
 template <int FLAGS, int LSTEPS>
-__global__ __launch_bounds__(TILE_W *TILE_H ATMO_MIN_WAVES_ARG) void atmo_render_proxy_depth_target_kernel(const RenderConsts rc, const ProxyConsts pc,
+__global__ __launch_bounds__(TILE_W *TILE_H, render_min_waves(FLAGS)) void atmo_render_proxy_depth_target_kernel(const RenderConsts rc, const ProxyConsts pc,
                                                                                                             const TargetConsts tc, const DepthConsts dc) {
     static_assert((FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0, "KF_DEPTH | KF_PROXY | KF_TARGET");
     shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, &pc, &tc, &dc);

@@ -1,4 +1,4 @@
-"""The power-of-two folding in sun_od_direct<8> (ATMO_LIGHT_FOLD), emulated in float32 on the CPU: the old and the new order of the expressions give
+"""The power-of-two folding in sun_od_direct<8> (csrc/atmo_kernels.hip), emulated in float32 on the CPU: the old and the new order of the expressions give
 the same bits -- the squared distances q[1..7] that feed the seven roots and the final acc * step * density^2 -- on the chosen inputs of
 tests/golden/direct_diet and on 10^6 random ones.
 

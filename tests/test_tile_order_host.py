@@ -10,7 +10,7 @@ import tile_order_ref as R
 from godot_atmosphere_shader_amd import _native as N
 from godot_atmosphere_shader_amd import sharding
 
-NC = 64   # the shipped build's class count (csrc/atmo_device.h, ATMO_ORDER_CLASSES); test_library_states_its_class_count holds the library to it,
+NC = 64   # the library's class count (csrc/atmo_device.h, TILE_ORDER_CLASSES); test_library_states_its_class_count holds the library to it,
           # and the reference states the heavy-tile rule for this count only
 WAVES, TRIGGERS, RATIOS = (64, 512, 6144), (0.0, 1.0, 2.0), (0.1, 0.3, 0.5)
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Files the outputs of one `tools/r6_final.sh` run (gpurun_out/) as the committed evidence of a round and regenerates every table and sentence of README.md /
+"""Files the outputs of a `tools/final_check.sh` run (its output directory) as the committed evidence of a round and regenerates every table and sentence of README.md /
 DESIGN.md that quotes them, so that the documents cannot drift from the files:
     python tools/file_evidence.py round6"""
 import glob

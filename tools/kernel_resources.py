@@ -22,8 +22,8 @@ def main(argv):
         subprocess.run(["hipcc"] + FLAGS + [SRC, "-o", path], check=True, stderr=subprocess.DEVNULL)
     text = open(path).read()
     rows = []
-    for m in re.finditer(r"\.amdhsa_kernel _ZN4atmo18atmo_render_kernel(_s80)?ILi(\d+)ELi(\d+)ELi(\d+)EEEvNS_12RenderConstsE\n(.*?)\.end_amdhsa_kernel", text, re.S):
-        body = m.group(5)
+    for m in re.finditer(r"\.amdhsa_kernel _ZN4atmo18atmo_render_kernelILi(\d+)ELi(\d+)ELi(\d+)EEEvNS_12RenderConstsE\n(.*?)\.end_amdhsa_kernel", text, re.S):
+        body = m.group(4)
         g = lambda k: int(re.search(r"\.amdhsa_%s (\d+)" % k, body).group(1))
         v, s, lds, priv = g("next_free_vgpr"), g("next_free_sgpr"), g("group_segment_fixed_size"), g("private_segment_fixed_size")
         vr = (v + 7) // 8 * 8
@@ -31,7 +31,7 @@ def main(argv):
         waves = min(8, 512 // vr, 800 // (sg + 16))
         if lds:
             waves = min(waves, (160 * 1024 // lds) * 2 // 4)
-        rows.append((int(m.group(2)), int(m.group(3)), int(m.group(4)), v, s, lds, priv, waves))
+        rows.append((int(m.group(1)), int(m.group(2)), int(m.group(3)), v, s, lds, priv, waves))
     for f, l, sp, v, s, lds, priv, waves in sorted(rows):
         print(f"atmo_render_kernel<{f}, {l}, {sp}>  VGPRs {v:3d}  SGPRs {s:3d}  LDS {lds:6d} B  stack {priv:4d} B  ~{waves} waves/SIMD")
 
