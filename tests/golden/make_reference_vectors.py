@@ -12,6 +12,7 @@ vertex-stage varyings).  tests/test_reference_exec.py checks the CPU oracle agai
 through the C ABI (-m gpu).
 
     python tests/golden/make_reference_vectors.py            # needs /root/reference; about a minute
+    python tests/golden/make_reference_vectors.py --steps-only   # reference_exec_steps.npz alone (the edge step counts); the same bytes every time
 """
 import os
 import sys
@@ -347,6 +348,51 @@ def main_round5():
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def save_npz_reproducibly(path, arrays):
+    """np.savez_compressed with every member stamped 1980-01-01 (numpy stamps the current time): the same arrays give the same bytes."""
+    import io
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            zf.writestr(info, buf.getvalue(), compresslevel=9)
+
+
+def main_steps():
+    """tests/golden/reference_exec_steps.npz: the reference text at the EDGE step counts -- one, odd, one past 32, one past 64 view steps; one, odd and
+    33 cloud steps -- with ATMOSPHERE_RAYMARCH_STEPS and CLOUDS_MAX_RAYMARCH_STEPS both forced over the files' own #defines (RS.STEP_CASES), 48 x 27,
+    poses RS.STEP_POSES of the demo scene; the cloudy shaders with the samplerCube they declare (cube_chain, as main_round3).  Cameras, depths and the
+    LUT are reference_exec.npz's.  The file holds the forced counts and the outputs."""
+    t0 = time.time()
+    z = np.load(os.path.join(HERE, "reference_exec.npz"))
+    params, model_matrix = scenes()["demo"]
+    chain = T.mip_chain(S.make_coverage_cubemap(CUBE_N))
+    units = dict(u_optical_depth_texture=T.LutTexture(z["lut_demo"]), u_blue_noise_texture=T.ByteTexture2D(S.make_blue_noise()),
+                 u_cloud_shape_texture=T.ShapeTexture(S.make_shape_texture(SHAPE_N)))
+    out = {"viewport": np.array([W, H]), "poses": np.array(RS.STEP_POSES), "shaders": np.array([c[0] for c in RS.STEP_CASES]),
+           "view_steps": np.array([c[1] for c in RS.STEP_CASES], dtype=np.int64),
+           "cloud_steps": np.array([0 if c[2] is None else c[2] for c in RS.STEP_CASES], dtype=np.int64)}
+    for shader, view, cloud in RS.STEP_CASES:
+        force = {"ATMOSPHERE_RAYMARCH_STEPS": view}
+        if cloud is not None:
+            force["CLOUDS_MAX_RAYMARCH_STEPS"] = cloud
+        for pose in RS.STEP_POSES:
+            cam = RS.camera_from_fixture(z, W, H, pose)
+            rgba, disc, _, _ = run_frame(shader, None, params, np.eye(4), model_matrix, cam, z[f"depth_demo_{pose}"], units, force_defines=force,
+                                         cube_chain=chain if cloud is not None else None)
+            key = RS.step_case_key(shader, view, cloud, pose)
+            out[f"rgba_{key}"], out[f"discard_{key}"] = rgba, np.packbits(disc)
+            print(f"{time.time() - t0:6.1f}s {key}: {int((~disc).sum())} of {disc.size} fragments kept, max rgba {rgba.max():.4f}", flush=True)
+    path = os.path.join(HERE, "reference_exec_steps.npz")
+    save_npz_reproducibly(path, out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 class UnsetCube:
     """An unbound samplerCube: the engine's default white texture (README.md:46 "cover uniformly")."""
 
@@ -387,7 +433,9 @@ def main_fuzz():
 
 
 if __name__ == "__main__":
-    if "--round5-only" in sys.argv:
+    if "--steps-only" in sys.argv:
+        main_steps()
+    elif "--round5-only" in sys.argv:
         main_round5()
     elif "--round4-only" in sys.argv:
         main_round4()
@@ -404,3 +452,4 @@ if __name__ == "__main__":
         main_fuzz_lod()
         main_round4()
         main_round5()
+        main_steps()

@@ -71,6 +71,34 @@ VIEW_STEP_COUNTS = [32, 64]
 VIEW_STEP_ROWS = ("planet_atmosphere_no_clouds", 1920, 1080, "P_space", (40, 330, 539, 1000))
 
 
+# ---- the edge step counts (reference_exec_steps.npz): (shader, forced ATMOSPHERE_RAYMARCH_STEPS, forced CLOUDS_MAX_RAYMARCH_STEPS or None) ----------
+# both macros forced over the file's own #defines; the cloudy shaders executed with the declared sampler; 48 x 27, poses STEP_POSES, the demo scene
+STEP_CASES = [
+    ("planet_atmosphere_clouds_high_rm", 1, 1),
+    ("planet_atmosphere_clouds_high_rm", 3, 3),
+    ("planet_atmosphere_clouds_high_rm", 33, 5),
+    ("planet_atmosphere_clouds", 65, 33),
+    ("planet_atmosphere_v1_clouds", 33, 3),
+    ("planet_atmosphere_no_clouds", 1, None),
+    ("planet_atmosphere_no_clouds", 33, None),
+    ("planet_atmosphere_v1_no_clouds", 1, None),
+    ("planet_atmosphere_clouds_high", 7, 7),
+]
+STEP_POSES = ["P_space", "P_clouds", "P_limb"]
+
+
+def step_case_key(shader, view, cloud, pose):
+    return f"{shader}_v{view}_c{0 if cloud is None else cloud}_{pose}"
+
+
+def step_case_config(shader, view, cloud):
+    """The checker's config of a STEP_CASES row: the shader's own with the forced counts."""
+    cfg = dict(VARIANTS[shader], view_steps=view)
+    if cloud is not None:
+        cfg["cloud_steps"] = cloud
+    return cfg
+
+
 def quad_partners(width, rows, height):
     """Lane indices of the horizontal / vertical 2 x 2 quad partner of every pixel of the given rows (row-major lanes), -1
     where the partner pixel is outside the viewport or its row is not executed."""

@@ -288,6 +288,45 @@ def test_oracle_equals_reference_at_32_and_64_view_steps(oracle32, vectors, r3, 
 
 
 # ------------------------------------------------------------------------------------- random scenes (reference_exec_fuzz.npz)
+# ---- the edge step counts (reference_exec_steps.npz): both step macros forced, the declared sampler ------------------------------------------------------
+@pytest.fixture(scope="module")
+def steps_z():
+    z = np.load(os.path.join(GOLDEN, "reference_exec_steps.npz"))
+    assert list(z["poses"]) == RS.STEP_POSES and tuple(z["viewport"]) == (RS.W, RS.H)
+    stored = [(str(s), int(v), int(c) or None) for s, v, c in zip(z["shaders"], z["view_steps"], z["cloud_steps"])]
+    assert stored == RS.STEP_CASES          # the forced counts the file says it was made with are the ones the tests assume
+    return z
+
+
+def _step_case_discards(z, shader, view, cloud, pose):
+    return np.unpackbits(z[f"discard_{RS.step_case_key(shader, view, cloud, pose)}"])[:RS.W * RS.H].reshape(RS.H, RS.W).astype(bool)
+
+
+@pytest.mark.parametrize("case", RS.STEP_CASES, ids=lambda c: f"{c[0]}-v{c[1]}-c{c[2]}")
+def test_oracle_equals_reference_at_the_edge_step_counts(oracle32, vectors, r3, steps_z, textures, case):
+    """One, odd, 33 and 65 view steps and one, odd and 33 cloud steps through the reference text (ATMOSPHERE_RAYMARCH_STEPS and
+    CLOUDS_MAX_RAYMARCH_STEPS forced over the files' own #defines), the cloudy shaders under the sampler they declare: the oracle that
+    tests/test_step_counts_gpu.py holds the kernels to IS the reference at these counts -- same bound as at the shaders' own counts, same discard sets."""
+    shader, view, cloud = case
+    params, model = _scene("demo")
+    cfg = RS.step_case_config(shader, view, cloud)
+    tex = dict(textures, optical_depth=vectors["lut_demo"])
+    if cloud is not None:
+        cfg["cube_lod"] = 1
+        tex = dict(_lod_textures(textures, oracle32, r3), optical_depth=vectors["lut_demo"])
+    for pose in RS.STEP_POSES:
+        cam = RS.camera_from_fixture(vectors, RS.W, RS.H, pose)
+        frame = make_frame(cam, model, S.DEMO_SUN_POSITION, 0.0)
+        got, hits = oracle32.render(params, tex, cfg, frame, vectors[f"depth_demo_{pose}"], nthreads=4)
+        want = steps_z[f"rgba_{RS.step_case_key(shader, view, cloud, pose)}"]
+        discarded = _step_case_discards(steps_z, shader, view, cloud, pose)
+        assert hits == int((~discarded).sum()) and np.all(got[discarded] == 0.0), pose
+        assert np.array_equal(np.all(got == 0.0, axis=-1), np.all(want == 0.0, axis=-1)), pose
+        assert want.max() > 0.01 and not np.array_equal(want, vectors[f"rgba_demo_{pose}_{shader}"])   # shaded, and not the shader's own counts' picture
+        err = _rel_err(got, want)
+        assert err <= ORACLE_TOL, f"{shader} view {view} cloud {cloud} {pose}: oracle vs executed reference {err:.3e}"
+
+
 @pytest.fixture(scope="module")
 def fuzz():
     return np.load(os.path.join(GOLDEN, "reference_exec_fuzz.npz"))
