@@ -5,6 +5,7 @@ Zylann/godot_atmosphere_shader, behind the reference's `PlanetAtmosphere` / `sha
   planet_atmosphere.py  host-side mirror of addons/zylann.atmosphere/planet_atmosphere.gd
   depth_formats.py      the depth sources' contract in numpy (include/atmo_depth.h; `depth_source` wraps a renderer's own depth buffer)
   noise_cubemap.py      host-side mirror of addons/zylann.atmosphere/noise_cubemap.gd (generation on the GPU)
+  noise_volume.py       host-side mirror of the demo's NoiseTexture3D: the cloud shape volume, generated on the GPU (include/atmo_noise_volume.h)
   demo.py               the reference's demo scene + named shader configurations (tests, bench.py, smoke())
   scene.py              synthetic inputs (camera, depth, jitter, cloud textures) for tests and bench
   sharding.py           row-band / viewport sharding across the GPUs of a node + RCCL gather
@@ -14,6 +15,7 @@ from .planet_atmosphere import (  # noqa: F401
 )
 
 from .noise_cubemap import NoiseCubemap, SeededValueNoise  # noqa: F401,E402
+from .noise_volume import NoiseVolume  # noqa: F401,E402
 
-__all__ = ["NoiseCubemap", "SeededValueNoise", "PlanetAtmosphere", "Shader", "SHADERS", "DefaultShader", "Transform2D", "load_shader",
+__all__ = ["NoiseCubemap", "NoiseVolume", "SeededValueNoise", "PlanetAtmosphere", "Shader", "SHADERS", "DefaultShader", "Transform2D", "load_shader",
            "atmosphere_vertex", "make_frame", "depth_source", "DepthSource"]

@@ -62,6 +62,9 @@ DEPTH_D32_SFLOAT, DEPTH_D16_UNORM, DEPTH_X8_D24_UNORM = range(3)
 # The ABI version stays 5 and the tuple stands beside EXPORTED_SYMBOLS, as PLANETS_SYMBOLS (NOTES.md).
 PROLOGUE_SYMBOLS = ("atmo_debug_prologue_mode", "atmo_debug_prologue_constants")
 PROLOGUE_CAMERA, PROLOGUE_POW2_STEPS, PROLOGUE_NO_SPHERE_DEPTH = 1, 2, 4
+# every symbol include/atmo_noise_volume.h declares: the cloud shape volume generated on the device (a NoiseTexture3D mirror; noise_volume.py).
+# The ABI version stays 5 and the tuple stands beside EXPORTED_SYMBOLS, as PLANETS_SYMBOLS (NOTES.md): a host detects the feature by the symbol.
+NOISE_VOLUME_SYMBOLS = ("atmo_generate_noise_volume",)
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -120,6 +123,20 @@ class AtmoViewDepthTarget(C.Structure):   # include/atmo_depth.h
         ("frame", AtmoFrame),
         ("depth", AtmoDepth),
         ("target", AtmoTarget),
+    ]
+
+
+class AtmoNoiseVolume(C.Structure):   # include/atmo_noise_volume.h
+    _fields_ = [
+        ("size", C.c_int32),
+        ("seed", C.c_uint32),
+        ("frequency", C.c_float),
+        ("octaves", C.c_int32),
+        ("gain", C.c_float),
+        ("offset", C.c_float * 3),
+        ("seamless", C.c_int32),
+        ("invert", C.c_int32),
+        ("normalize", C.c_int32),
     ]
 
 
@@ -245,6 +262,7 @@ def load() -> C.CDLL:
         "atmo_debug_feedback_plan": (ip, [C.POINTER(AtmoFeedbackPlanIn), C.POINTER(AtmoFeedbackPlanOut)]),
         "atmo_debug_prologue_mode": (ip, [vp, C.POINTER(AtmoFrame), C.POINTER(C.c_uint), C.POINTER(ip), C.POINTER(ip)]),
         "atmo_debug_prologue_constants": (ip, [vp, C.POINTER(AtmoFrame), fp, ip, C.POINTER(ip)]),
+        "atmo_generate_noise_volume": (ip, [vp, C.POINTER(AtmoNoiseVolume), ip, vp, vp]),
     }
     # ATMO_HIP_LIB names an A/B build (tools/ab_build_commit.sh: possibly an OLDER commit's library): entry points it lacks are skipped
     # (callers of those guard with hasattr) and its ABI version is not held against it.  The in-tree library must match exactly.

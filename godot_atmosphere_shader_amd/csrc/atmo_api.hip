@@ -15,6 +15,7 @@
 #include "../../include/atmo_planets.h"
 #include "../../include/atmo_depth.h"
 #include "../../include/atmo_debug_prologue.h"
+#include "../../include/atmo_noise_volume.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -125,6 +126,11 @@ struct AtmoContext {
     DeviceBuffer staging;                // raw texels on their way into a re-layout kernel (grow-only)
     hipStream_t staging_stream = nullptr;
     bool staging_used = false;
+    // atmo_generate_noise_volume: the generated texels (n^3 bytes, re-allocated only when n changes) and the two words of the min/max pass.  The
+    // re-layout kernel of a bound generation reads noise_vol on its stream; the NEXT generation into it needs nothing of its own to be ordered behind
+    // that read: the update ends with tex_event recorded behind its last kernel (tex_updated), and a generation on another stream waits for that event
+    // (tex_order) before it writes -- on the same stream, stream order does.
+    DeviceBuffer noise_vol, noise_vol_minmax;
     hipEvent_t tex_event = nullptr;      // recorded after the last texture update on tex_stream
     hipStream_t tex_stream = nullptr;
     bool tex_pending = false;
@@ -1188,6 +1194,8 @@ int atmo_destroy(AtmoContext *ctx) {
     dev_free(ctx->cube_f4);
     dev_free(ctx->shape_f4);
     dev_free(ctx->staging);
+    dev_free(ctx->noise_vol);
+    dev_free(ctx->noise_vol_minmax);
     dev_free(ctx->measure_buf);
     for (AtmoContext::TileListBuf &t : ctx->tile_lists) dev_free(t.buf);
     if (ctx->tex_event) (void)hipEventDestroy(ctx->tex_event);
@@ -1551,6 +1559,59 @@ int atmo_generate_noise_cubemap(AtmoContext *ctx, int resolution, uint32_t seed,
                               dev, ATMO_MEM_DEVICE, nullptr);  // stays on the device: mip + re-layout kernels, no host round trip
     (void)hipFree(dev);
     return rc;
+}
+
+// include/atmo_noise_volume.h
+int atmo_generate_noise_volume(AtmoContext *ctx, const AtmoNoiseVolume *v, int bind, uint8_t *texels_host, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *fn = "atmo_generate_noise_volume: ";
+    if (!v) return fail(ctx, ATMO_E_ARG, std::string(fn) + "v is null");
+    if (v->size < 1 || v->size > 512) return fail(ctx, ATMO_E_ARG, std::string(fn) + "size must be 1..512 (the shape texture is cubic, atmo_set_texture's bound)");
+    if (v->octaves < 1 || v->octaves > 16) return fail(ctx, ATMO_E_ARG, std::string(fn) + "octaves must be 1..16");
+    if (!std::isfinite(v->frequency) || !(v->frequency > 0.0f)) return fail(ctx, ATMO_E_ARG, std::string(fn) + "frequency must be finite and > 0");
+    if (!std::isfinite(v->gain) || !(v->gain > 0.0f)) return fail(ctx, ATMO_E_ARG, std::string(fn) + "gain must be finite and > 0");
+    double reach = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(v->offset[a])) return fail(ctx, ATMO_E_ARG, std::string(fn) + "offset[" + std::to_string(a) + "] must be finite");
+        reach = std::max(reach, std::fabs((double)v->offset[a]));
+    }
+    const int n = v->size;
+    int period0 = 0;
+    double freq_last;
+    if (v->seamless) {
+        const float cells = (float)n * v->frequency;   // the fp32 product, rounded half to even below (the default rounding mode)
+        if (!(cells <= 16777216.0f) || ((long long)std::max(1.0f, rintf(cells)) << (v->octaves - 1)) > (1ll << 24))
+            return fail(ctx, ATMO_E_ARG, std::string(fn) + "frequency: seamless, the last octave's period max(1, rint(size * frequency)) << (octaves - 1) must not exceed 2^24");
+        period0 = std::max(1, (int)rintf(cells));
+        freq_last = (double)(period0 << (v->octaves - 1)) / (double)n;
+    } else {
+        freq_last = std::ldexp((double)v->frequency, v->octaves - 1);
+    }
+    if (!(((double)n + reach) * freq_last < 1073741824.0))
+        return fail(ctx, ATMO_E_ARG, std::string(fn) + "offset: (size + max |offset|) * the last octave's frequency must stay below 2^30 (the lattice index is an int)");
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, std::string(fn) + "a host-only context has no device to generate on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (texels_host && stream_is_capturing(s))
+        return fail(ctx, ATMO_E_STATE, std::string(fn) + "texels_host on a capturing stream: the read-back waits for the stream, which a capture cannot hold");
+    const size_t bytes = (size_t)n * n * n;
+    ATMO_TRY(dev_alloc(ctx, ctx->noise_vol, bytes));   // (a size change: hipFree waits for the device by itself)
+    ATMO_TRY(dev_alloc(ctx, ctx->noise_vol_minmax, 2 * sizeof(uint32_t)));
+    ATMO_TRY(tex_order(ctx, s));   // behind the re-layout kernels of the last update, which may still read noise_vol on another stream
+    atmo::NoiseVolumeConsts nv;
+    nv.n = n; nv.seed = v->seed; nv.frequency = v->frequency; nv.gain = v->gain; nv.octaves = v->octaves;
+    nv.offset[0] = v->offset[0]; nv.offset[1] = v->offset[1]; nv.offset[2] = v->offset[2];
+    nv.seamless = v->seamless != 0; nv.invert = v->invert != 0; nv.normalize = v->normalize != 0;
+    nv.period0 = period0;
+    nv.out = (uint8_t *)ctx->noise_vol.ptr;
+    nv.minmax = (uint32_t *)ctx->noise_vol_minmax.ptr;
+    HIP_TRY(ctx, atmo::launch_noise_volume(nv, s));
+    if (texels_host) {
+        HIP_TRY(ctx, hipMemcpyAsync(texels_host, ctx->noise_vol.ptr, bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    if (bind) return atmo_set_texture(ctx, "u_cloud_shape_texture", ATMO_TEX_3D_R8, n, n, n, 1, ctx->noise_vol.ptr, ATMO_MEM_DEVICE, stream);
+    return ATMO_OK;
 }
 
 int atmo_bake_optical_depth(AtmoContext *ctx, void *stream) {

@@ -136,6 +136,19 @@ struct NoiseCubemapConsts {
     uint8_t *out;  // 6 faces of resolution^2 bytes
 };
 
+// the shape-volume generator (include/atmo_noise_volume.h): AtmoNoiseVolume's fields, the base period the host derived from them, where the texels go
+struct NoiseVolumeConsts {
+    int32_t n;           // the volume is n^3 texels, [z][y][x]
+    uint32_t seed;
+    float frequency, gain;
+    int32_t octaves;
+    float offset[3];
+    int32_t seamless, invert, normalize;
+    int32_t period0;     // seamless: P_0 = max(1, (int)rintf((float)n * frequency)); octave o tiles with P_0 << o lattice cells per side
+    uint8_t *out;        // n^3 bytes
+    uint32_t *minmax;    // normalize: ~bits(min t) and bits(max t) over the volume, both kept as maxima (t >= +0: unsigned order is float order)
+};
+
 // kernel launchers (atmo_kernels.hip)
 enum KernelFlags : int { KF_CLOUDS = 1, KF_CLOUD_LIGHT_RM = 2, KF_LIGHT_DIRECT = 4, KF_LITE = 8, KF_PRECISE = 16, KF_CUBE_LOD = 32,
                           KF_ATMO_REF = 64 /* the v2 atmosphere march in the reference's operation order (atmo_set_precision 2) */,
@@ -284,6 +297,8 @@ hipError_t launch_cube_mip(const uint8_t *level, int n, uint8_t *next, hipStream
 void render_grid(const RenderConsts &rc, int split, int *tiles_x, int *tiles_y);
 void render_tile_size(int split, int *tile_w, int *tile_h);  // pixels per workgroup tile of a launch with `split` lanes per ray
 hipError_t launch_noise_cubemap(const NoiseCubemapConsts &nc, hipStream_t stream);
+// the whole generation on `stream`: (normalize) the two words re-initialised and the min/max pass, then the store pass
+hipError_t launch_noise_volume(const NoiseVolumeConsts &nv, hipStream_t stream);
 const char *render_kernel_name(int flags, int light_steps, int split);
 hipError_t launch_log2_cr(const float *x_dev, float *out_dev, int n, hipStream_t stream);
 hipError_t launch_light_probe(const float *pos, const float *dir, int n, float planet_radius, float atmosphere_height, float density,

@@ -3021,6 +3021,117 @@ hipError_t launch_noise_cubemap(const NoiseCubemapConsts &nc, hipStream_t stream
     return hipGetLastError();
 }
 
+// ---- cloud shape volume generator (include/atmo_noise_volume.h: a seamless NoiseTexture3D over the same seeded value noise) --------------
+// One lane per texel, the same exact fp32 arithmetic as the cubemap generator; the header states the contract, tests/noise_volume_host.py restates
+// it in numpy.  nz_value with every lattice index taken modulo `period` (non-negative) before hashing: the value then repeats every `period` cells
+// along each axis, exactly.  i1 = i0 + 1 is formed first and reduced like i0: (m0 + 1) mod period, from m0 = i0 mod period.
+__device__ __forceinline__ int nz_wrap(int i, int period) {
+    const int m = i % period;
+    return m < 0 ? m + period : m;
+}
+__device__ __forceinline__ float nz_value_periodic(float px, float py, float pz, uint32_t seed, int period) {
+    const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
+    const float tx = px - fx, ty = py - fy, tz = pz - fz;
+    const float wx = tx * tx * (3.0f - 2.0f * tx), wy = ty * ty * (3.0f - 2.0f * ty), wz = tz * tz * (3.0f - 2.0f * tz);
+    const int x0 = nz_wrap((int)fx, period), y0 = nz_wrap((int)fy, period), z0 = nz_wrap((int)fz, period);
+    const int x1 = x0 + 1 == period ? 0 : x0 + 1, y1 = y0 + 1 == period ? 0 : y0 + 1, z1 = z0 + 1 == period ? 0 : z0 + 1;
+    const float c00 = nz_lattice(x0, y0, z0, seed) * (1.0f - wx) + nz_lattice(x1, y0, z0, seed) * wx;
+    const float c10 = nz_lattice(x0, y1, z0, seed) * (1.0f - wx) + nz_lattice(x1, y1, z0, seed) * wx;
+    const float c01 = nz_lattice(x0, y0, z1, seed) * (1.0f - wx) + nz_lattice(x1, y0, z1, seed) * wx;
+    const float c11 = nz_lattice(x0, y1, z1, seed) * (1.0f - wx) + nz_lattice(x1, y1, z1, seed) * wx;
+    const float c0 = c00 * (1.0f - wy) + c10 * wy;
+    const float c1 = c01 * (1.0f - wy) + c11 * wy;
+    return c0 * (1.0f - wz) + c1 * wz;
+}
+
+// t of texel `idx` (< n^3), before normalize / quantise / invert: 0.5 + 0.5 * fractal sum, in [+0, 1]
+__device__ __forceinline__ float noise_volume_t(const NoiseVolumeConsts &nv, uint32_t idx) {
+    const uint32_t n = (uint32_t)nv.n;
+    const uint32_t x = idx % n, yz = idx / n, y = yz % n, z = yz / n;
+    const float qx = (float)x + nv.offset[0], qy = (float)y + nv.offset[1], qz = (float)z + nv.offset[2];
+    float total = 0.0f, amp = 1.0f, norm = 0.0f, freq = nv.frequency;
+    for (int o = 0; o < nv.octaves; ++o) {
+        const uint32_t seed = nv.seed + 1013u * (uint32_t)o;
+        float value;
+        if (nv.seamless) {
+            const int period = nv.period0 << o;
+            freq = ieee_div((float)period, (float)nv.n);
+            value = nz_value_periodic(qx * freq, qy * freq, qz * freq, seed, period);
+        } else {
+            value = nz_value(qx * freq, qy * freq, qz * freq, seed);
+            freq *= 2.0f;
+        }
+        total += amp * value;
+        norm += amp;
+        amp *= nv.gain;
+    }
+    const float v = 2.0f * ieee_div(total, norm) - 1.0f;
+    return 0.5f + 0.5f * v;
+}
+
+// Pass 1 of a normalised volume: min and max of t.  t is never negative, -0 or NaN, so the unsigned order of its bits is its order as a float, and
+// min / max do not depend on the order of reduction: xor-butterfly over the 64 lanes, the block's four waves through LDS, then at most ONE atomic per
+// word and block.  Both words are kept as MAXIMA -- minmax[0] holds ~bits(min t), minmax[1] bits(max t) -- so that one memset to zero re-initialises
+// them.  Lanes past the end of the volume (the last block is partial unless 4 | n) stay in the butterfly and contribute the identities.
+__global__ __launch_bounds__(256) void atmo_noise_volume_minmax_kernel(const NoiseVolumeConsts nv) {
+    __shared__ uint32_t wave_lo[4], wave_hi[4];
+    const uint32_t total = (uint32_t)nv.n * (uint32_t)nv.n * (uint32_t)nv.n;
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    uint32_t lo = 0u, hi = 0u;   // lo: the maximum of ~bits(t)
+    if (idx < total) {
+        hi = (uint32_t)__float_as_int(noise_volume_t(nv, idx));
+        lo = ~hi;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        lo = max(lo, (uint32_t)__shfl_xor((int)lo, d, 64));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, d, 64));
+    }
+    if ((threadIdx.x & 63) == 0) { wave_lo[threadIdx.x >> 6] = lo; wave_hi[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    // Atomics on ONE address serialise (11 ns each measured: one pair per wave, unconditionally, cost 64^3 94 us -- 12 x its store pass -- and 256^3
+    // 5.6 ms), and most cannot change the word: it only ever rises, so a block whose extremum does not beat the value it reads -- however stale --
+    // has nothing to contribute and skips (profiles/noise_volume/README.md).
+    if (threadIdx.x == 0) {
+        lo = max(max(wave_lo[0], wave_lo[1]), max(wave_lo[2], wave_lo[3]));
+        hi = max(max(wave_hi[0], wave_hi[1]), max(wave_hi[2], wave_hi[3]));
+        if (lo > __hip_atomic_load(&nv.minmax[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&nv.minmax[0], lo);
+        if (hi > __hip_atomic_load(&nv.minmax[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&nv.minmax[1], hi);
+    }
+}
+
+// The store pass (the only pass without normalize): t again -- recomputed, not kept: an fp32 scratch of 512^3 texels would be 512 MB --, then
+// normalize, quantise (truncating, the cubemap's L8 store) and invert.
+__global__ __launch_bounds__(256) void atmo_noise_volume_kernel(const NoiseVolumeConsts nv) {
+    const uint32_t total = (uint32_t)nv.n * (uint32_t)nv.n * (uint32_t)nv.n;
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= total) return;
+    float t = noise_volume_t(nv, idx);
+    if (nv.normalize) {
+        const float mn = __int_as_float((int)~nv.minmax[0]), mx = __int_as_float((int)nv.minmax[1]);
+        if (mx != mn) t = ieee_div(t - mn, mx - mn);
+    }
+    float v = t * 255.0f;
+    v = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);
+    const uint32_t b = (uint32_t)v;
+    nv.out[idx] = (uint8_t)(nv.invert ? 255u - b : b);
+}
+
+hipError_t launch_noise_volume(const NoiseVolumeConsts &nv, hipStream_t stream) {
+    const uint32_t total = (uint32_t)nv.n * (uint32_t)nv.n * (uint32_t)nv.n;   // <= 512^3 = 2^27
+    const dim3 grid((total + 255u) / 256u);
+    if (nv.normalize) {
+        // re-initialised in front of EVERY min/max pass: a second generation must not see the first one's extrema
+        const hipError_t e = hipMemsetAsync(nv.minmax, 0, 2 * sizeof(uint32_t), stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(atmo_noise_volume_minmax_kernel, grid, dim3(256), 0, stream, nv);
+        const hipError_t el = hipGetLastError();
+        if (el != hipSuccess) return el;
+    }
+    hipLaunchKernelGGL(atmo_noise_volume_kernel, grid, dim3(256), 0, stream, nv);
+    return hipGetLastError();
+}
+
 // ---- probe of the direct light march (atmo_debug_marched_optical_depth) ----------------------------------------------------
 // Evaluates sun_od_direct -- the very function march_atmosphere<DIRECT> inlines -- for n given sample positions (relative to the
 // planet centre) and sun directions, so the kernel's light march can be held against the reference's LUT texels, which

@@ -476,6 +476,11 @@ class PlanetAtmosphere:
 
     def _upload_texture(self, name: str, value):
         kind = _TEXTURES[name]
+        if hasattr(value, "bind_to"):  # a NoiseVolume resource: generated straight into this node's context, no host copy of the texels
+            if name != "u_cloud_shape_texture":
+                raise ValueError(f"{name} does not take a NoiseVolume (u_cloud_shape_texture does)")
+            value.bind_to(self)
+            return
         if hasattr(value, "get_images"):  # a NoiseCubemap resource
             value = value.get_images()
         if value is None:
