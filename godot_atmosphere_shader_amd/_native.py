@@ -65,6 +65,10 @@ PROLOGUE_CAMERA, PROLOGUE_POW2_STEPS, PROLOGUE_NO_SPHERE_DEPTH = 1, 2, 4
 # every symbol include/atmo_noise_volume.h declares: the cloud shape volume generated on the device (a NoiseTexture3D mirror; noise_volume.py).
 # The ABI version stays 5 and the tuple stands beside EXPORTED_SYMBOLS, as PLANETS_SYMBOLS (NOTES.md): a host detects the feature by the symbol.
 NOISE_VOLUME_SYMBOLS = ("atmo_generate_noise_volume",)
+# every symbol include/atmo_cloud_detail.h declares: the cloud variants with the reference's CLOUDS_ALWAYS_LOW_QUALITY off (the detail fetch, live TIME).
+# The ABI version stays 5 and the tuple stands beside EXPORTED_SYMBOLS, as PLANETS_SYMBOLS (NOTES.md): a host detects the feature by these symbols, and
+# load() binds them where the library has them (a library without them still loads; PlanetAtmosphere(cloud_detail=True) then raises).
+CLOUD_DETAIL_SYMBOLS = ("atmo_set_cloud_detail", "atmo_get_cloud_detail", "atmo_debug_cloud_detail_constants")
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -275,6 +279,18 @@ def load() -> C.CDLL:
             raise RuntimeError(f"libatmo_hip.so does not export {name}; rebuild it")
         fn.restype = res
         fn.argtypes = args
+    # include/atmo_cloud_detail.h: detected by symbol -- bound where present, and a library without them loads all the same
+    detail_sig = {
+        "atmo_set_cloud_detail": (ip, [vp, ip]),
+        "atmo_get_cloud_detail": (ip, [vp, C.POINTER(ip)]),
+        "atmo_debug_cloud_detail_constants": (ip, [vp, C.POINTER(AtmoFrame), fp, ip, C.POINTER(ip)]),
+    }
+    assert tuple(detail_sig) == CLOUD_DETAIL_SYMBOLS
+    for name, (res, args) in detail_sig.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     have = lib.atmo_abi_version()
     if have != ABI_VERSION:
         # An A/B library may be older, but only a version whose AtmoFrame layout and shared entry points are KNOWN to be what this binding

@@ -16,6 +16,7 @@
 #include "../../include/atmo_depth.h"
 #include "../../include/atmo_debug_prologue.h"
 #include "../../include/atmo_noise_volume.h"
+#include "../../include/atmo_cloud_detail.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -140,7 +141,8 @@ struct AtmoContext {
     int host_double_precision = 0;  // DOUBLE_PRECISION (main:25,118-125)
     int target_cleared = 0;         // atmo_set_target_cleared: discarded fragments write nothing
     int lane_split = 0;             // 0 = choose per launch by size, 1 = one lane per ray, 2 = two lanes per ray
-    int last_split = 1;             // what the most recent launch used (atmo_kernel_name)
+    int cloud_detail = 0;           // atmo_set_cloud_detail: CLOUDS_ALWAYS_LOW_QUALITY off (in effect on a cloud variant: cloud_detail_on)
+    int last_split = 1;            // what the most recent launch used (atmo_kernel_name)
     int last_flags = -1;
     // tile order with cost feedback (atmo_set_tile_feedback): -1 = default (on), 0 off, 1 on
     int tile_feedback = -1;
@@ -741,6 +743,35 @@ void draw_grid_origin(const AtmoFrame *frame, bool lod, atmo::RenderConsts &rc) 
         rc.gx0 = frame->x0 & ~1;
         rc.gy0 = frame->y0 & ~1;
     }
+}
+// ---- cloud detail (include/atmo_cloud_detail.h): CLOUDS_ALWAYS_LOW_QUALITY off ------------------------------------------------------------------
+// In effect on a cloud variant only: a context without clouds has no density to evaluate and draws as before, through every entry point.
+bool cloud_detail_on(const AtmoContext *ctx) { return ctx->cloud_detail != 0 && (ctx->flags & atmo::KF_CLOUDS) != 0; }
+// What every draw entry point but atmo_render[_composite] says where its mode check stands.  `what`: the kind of draw, as the header lists them.
+int cloud_detail_refusal(AtmoContext *ctx, const std::string &who, const char *what) {
+    if (!cloud_detail_on(ctx)) return ATMO_OK;
+    return fail(ctx, ATMO_E_STATE, who + ": cloud detail (atmo_set_cloud_detail 1) draws through atmo_render and atmo_render_composite only, not through " + what);
+}
+// ... and atmo_render[_composite] themselves for a family (launch_shape's) without a cloud-detail kernel
+int cloud_detail_mode(AtmoContext *ctx, const std::string &who, int flags, int split) {
+    if (split == 1 && atmo::detail_family_supported(flags)) return ATMO_OK;
+    return fail(ctx, ATMO_E_STATE, who + ": no cloud-detail kernel for this context's mode (atmo_set_cloud_detail 1 draws the LUT-light cloud forms: "
+                                         "atmo_set_precision 1, no direct light, up to 32 view steps, one lane per ray)");
+}
+// The kernel's constants (atmo_cloud_detail.h: the arithmetic contract).  Host fp32, nothing fused (the build's -ffp-contract=off).
+atmo::DetailConsts cloud_detail_consts(const AtmoContext *ctx, const AtmoFrame *f, float *sub_hi_out = nullptr) {
+    atmo::DetailConsts xc;
+    xc.c = f->time * 0.01f;
+    // The bounds of RN(shape - RN(0.2 * detail)): shape's range as fill_consts derives it for shape_lo01 / shape_hi01 (every fp32 step of the mix / invert is
+    // monotone in the filtered texel, which lies in [0, 1 + 2^-20]), detail in the same range; the subtraction is monotone in both.
+    const float fac = ctx->p.u_cloud_shape_factor, t_hi = 1.0f + 9.5367431640625e-07f;
+    float a = 0.5f * (1.0f - fac) + 0.0f * fac, b = 0.5f * (1.0f - fac) + t_hi * fac;
+    if (ctx->p.u_cloud_shape_invert == 1.0f) { a = 1.0f - a; b = 1.0f - b; }
+    const float sub_hi = 0.2f * t_hi;
+    xc.shape_lo_d = std::fmin(a, b) - sub_hi;
+    xc.shape_hi_d = std::fmax(a, b) - 0.2f * 0.0f;
+    if (sub_hi_out) *sub_hi_out = sub_hi;
+    return xc;
 }
 // Reads back finished timing pairs.  only_completed: keep the pairs whose second event has not happened yet
 // (used to bound `pending` without blocking); otherwise wait for every pair.
@@ -1758,6 +1789,7 @@ int atmo_render_tiles(AtmoContext *ctx, const AtmoFrame *frame, const float *dep
     if (!ctx) return ATMO_E_ARG;
     if (n_tiles < 0 || (n_tiles > 0 && !tiles_dev)) return fail(ctx, ATMO_E_ARG, "atmo_render_tiles: bad tile list");
     if (n_tiles == 0) return ATMO_OK;  // an empty share of the frame: nothing to shade
+    ATMO_TRY(cloud_detail_refusal(ctx, "atmo_render_tiles", "tile lists"));
     return render_impl(ctx, frame, float_surfaces(depth_dev, rgba_dev, false), {tiles_dev, n_tiles, 0}, stream);
 }
 
@@ -1766,6 +1798,7 @@ int atmo_render_tiles_split(AtmoContext *ctx, const AtmoFrame *frame, const floa
     if (!ctx) return ATMO_E_ARG;
     if (n_tiles < 0 || (n_tiles > 0 && !tiles_dev) || n_heavy < 0 || n_heavy > n_tiles) return fail(ctx, ATMO_E_ARG, "atmo_render_tiles_split: bad tile list");
     if (n_tiles == 0) return ATMO_OK;
+    ATMO_TRY(cloud_detail_refusal(ctx, "atmo_render_tiles_split", "tile lists"));
     return render_impl(ctx, frame, float_surfaces(depth_dev, rgba_dev, false), {tiles_dev, n_tiles, n_heavy}, stream);
 }
 
@@ -1774,6 +1807,7 @@ int atmo_measure_tile_costs(AtmoContext *ctx, const AtmoFrame *frame, const floa
     if (!ctx) return ATMO_E_ARG;
     if (!frame) return fail(ctx, ATMO_E_ARG, "atmo_measure_tile_costs: null frame");
     if (frame->x1 <= frame->x0 || frame->y1 <= frame->y0) return fail(ctx, ATMO_E_ARG, "atmo_measure_tile_costs: empty rect");
+    ATMO_TRY(cloud_detail_refusal(ctx, "atmo_measure_tile_costs", "cost measurements (its kernels record no tile costs)"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // the grid this rect is drawn with (same choice as render_impl)
     atmo::RenderConsts probe;
@@ -1978,6 +2012,17 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, DrawSurfaces sf
     ATMO_TRY(check_frame(ctx, "atmo_render", frame, &empty));
     if (empty) return ATMO_OK;  // empty rect: nothing to shade
     ATMO_TRY(check_surfaces(ctx, sf.kind == SURF_DEPTH ? "atmo_render_depth_target" : "atmo_render", frame, sf));
+    // cloud detail (include/atmo_cloud_detail.h): atmo_render[_composite] alone, in a mode that has the kernel.  A property of the context, so in front of the
+    // textures' check: a context that cannot draw this way hears so whatever is bound.  (The siblings refuse at their own mode checks; a tile list, a
+    // measurement or a target that got here did not come through one.)
+    const bool detail = cloud_detail_on(ctx);
+    if (detail) {
+        if (tiles.dev || ctx->measure_cost || sf.kind != SURF_FLOAT || sf.target)
+            return cloud_detail_refusal(ctx, "atmo_render", "tile lists, cost measurements or targets");
+        int dflags = 0, dsplit = 1;
+        launch_shape(ctx, frame, &dflags, &dsplit, nullptr);
+        ATMO_TRY(cloud_detail_mode(ctx, "atmo_render", dflags, dsplit));
+    }
     ATMO_TRY(check_draw_textures(ctx, "atmo_render"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
@@ -2000,6 +2045,19 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, DrawSurfaces sf
     atmo::render_grid(rc, split, &gx, &gy);
     rc.tiles_x = gx;
     const int tile_h = (rc.y1 - rc.y0 + gy - 1) / gy;  // pixel rows per tile of this launch (8, or 4 with two lanes per ray)
+
+    // 3a. a cloud-detail draw: its own kernel with its constants behind rc, row-major -- no feedback state, no tile order, no cost recording, nothing beside
+    // the draw stream (so a graph capture takes it as it is); timed and counted as every accepted atmo_render
+    if (detail) {
+        const atmo::DetailConsts xc = cloud_detail_consts(ctx, frame);
+        TimingBracket timing;
+        ATMO_TRY(timing_open(ctx, timing));
+        ATMO_TRY(timing_begin(ctx, timing, s));
+        HIP_TRY(ctx, atmo::launch_render_detail(flags, rc, xc, s));
+        hipEvent_t marker = nullptr;
+        ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_DETAIL, 1, true, &marker));
+        return timing_end(ctx, timing, s);
+    }
 
     // 4. feedback state, motion and poll
     // default (-1): on for every variant since the sort no longer costs the draws anything (profiles/round2/ab_tile_feedback.txt)
@@ -2158,6 +2216,31 @@ int atmo_set_lane_split(AtmoContext *ctx, int lanes_per_ray) {
     return ATMO_OK;
 }
 
+// ---- cloud detail (include/atmo_cloud_detail.h) ----------------------------------------------------------------------------------------------
+int atmo_set_cloud_detail(AtmoContext *ctx, int enable) {
+    if (!ctx) return ATMO_E_ARG;
+    ctx->cloud_detail = enable ? 1 : 0;
+    return ATMO_OK;
+}
+
+int atmo_get_cloud_detail(AtmoContext *ctx, int *enabled) {
+    if (!ctx) return ATMO_E_ARG;
+    if (!enabled) return fail(ctx, ATMO_E_ARG, "atmo_get_cloud_detail: null argument");
+    *enabled = ctx->cloud_detail;
+    return ATMO_OK;
+}
+
+int atmo_debug_cloud_detail_constants(AtmoContext *ctx, const AtmoFrame *frame, float *out, int capacity, int *count) {
+    if (!ctx) return ATMO_E_ARG;
+    if (!frame || !out || !count) return fail(ctx, ATMO_E_ARG, "atmo_debug_cloud_detail_constants: null argument");
+    if (capacity < 4) return fail(ctx, ATMO_E_ARG, "atmo_debug_cloud_detail_constants: capacity below 4");
+    float sub_hi = 0.0f;
+    const atmo::DetailConsts xc = cloud_detail_consts(ctx, frame, &sub_hi);
+    out[0] = xc.c; out[1] = xc.shape_lo_d; out[2] = xc.shape_hi_d; out[3] = sub_hi;
+    *count = 4;
+    return ATMO_OK;
+}
+
 int atmo_set_timing(AtmoContext *ctx, int every_kth) {
     if (!ctx) return ATMO_E_ARG;
     (void)hipSetDevice(ctx->device);
@@ -2271,6 +2354,7 @@ const char *atmo_kernel_name(AtmoContext *ctx) {
     // before the first draw: what a draw would launch as the context stands (render_impl's choices: long view marches, the cubemap's sampler)
     int flags = 0, split = 1;
     launch_shape(ctx, nullptr, &flags, &split, nullptr);
+    if (cloud_detail_on(ctx) && split == 1 && atmo::detail_family_supported(flags)) flags |= atmo::KF_DETAIL;   // (any other mode: atmo_render refuses)
     return atmo::render_kernel_name(flags, ctx->light_steps, split);
 }
 
@@ -2505,6 +2589,7 @@ static int proxy_setup(AtmoContext *ctx, const char *who, const AtmoFrame *f, co
 // The family a proxy draw of this context uses, or ATMO_E_STATE when there is no proxy kernel for its mode (default_family_supported).
 static int proxy_family(AtmoContext *ctx, const char *who, const AtmoFrame *frame, int *flags, bool *lod) {
     int split = 1;
+    ATMO_TRY(cloud_detail_refusal(ctx, who, "proxy draws"));
     ATMO_TRY(draw_family(ctx, frame, flags, &split, lod));
     if (split != 1 || !atmo::default_family_supported(*flags))
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": no proxy kernel for this context's mode (proxy draws exist for the default forms: atmo_set_precision 1, "
@@ -2530,6 +2615,7 @@ static int proxy_impl(AtmoContext *ctx, const char *who, const AtmoFrame *frame,
     ATMO_TRY(check_frame(ctx, who, frame, &empty));
     // (unlike render_impl, the pointers, the textures and the mode are checked in front of the empty rect's ATMO_OK)
     ATMO_TRY(check_surfaces(ctx, who, frame, sf));
+    ATMO_TRY(cloud_detail_refusal(ctx, who, "proxy draws"));   // (proxy_family's, in front of the textures' check as render_impl's: a property of the context)
     ATMO_TRY(check_draw_textures(ctx, who));
     int flags = 0;
     bool lod = false;
@@ -2632,6 +2718,7 @@ int atmo_render_target(AtmoContext *ctx, const AtmoFrame *frame, const float *de
     if (!ctx) return ATMO_E_ARG;
     DrawSurfaces sf = target_surfaces(depth_dev, target, composite != 0);
     ATMO_TRY(target_check(ctx, "atmo_render_target", frame, sf));
+    ATMO_TRY(cloud_detail_refusal(ctx, "atmo_render_target", "colour targets (any format)"));
     if (sf.kind == SURF_PACKED) ATMO_TRY(target_family(ctx, "atmo_render_target", frame, false));
     return render_impl(ctx, frame, sf, WHOLE_GRID, stream);
 }
@@ -2655,6 +2742,7 @@ int atmo_render_depth_target(AtmoContext *ctx, const AtmoFrame *frame, const Atm
     if (!ctx) return ATMO_E_ARG;
     DrawSurfaces sf = depth_target_surfaces(depth, target, composite != 0);
     ATMO_TRY(target_check(ctx, "atmo_render_depth_target", frame, sf));
+    ATMO_TRY(cloud_detail_refusal(ctx, "atmo_render_depth_target", "depth sources"));
     ATMO_TRY(target_family(ctx, "atmo_render_depth_target", frame, true));
     return render_impl(ctx, frame, sf, WHOLE_GRID, stream);
 }
@@ -2763,6 +2851,7 @@ int views_check_frames(AtmoContext *ctx, const char *who, bool have_views, const
 // The second half: the family (ATMO_E_STATE where no multi-view kernel exists; `kind`: the batch's surfaces) and the concatenated launch.
 int views_family_grid(AtmoContext *ctx, const char *who, const ViewDraw *args, int n_views, SurfaceKind kind, ViewsLayout &L) {
     int split = 1;
+    ATMO_TRY(cloud_detail_refusal(ctx, who, "view batches"));
     ATMO_TRY(draw_family(ctx, args[0].frame, &L.flags, &split, &L.lod));
     if (split != 1 || !atmo::default_family_supported(L.flags))
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": no multi-view kernel for this context's mode (they exist for the default forms: atmo_set_precision 1, "

@@ -167,7 +167,10 @@ enum KernelFlags : int { KF_CLOUDS = 1, KF_CLOUD_LIGHT_RM = 2, KF_LIGHT_DIRECT =
                           KF_DEPTH = 4096 /* the depth buffer in its own format and row pitch (atmo_render_depth_target, include/atmo_depth.h): shade_pixel's depth read
                                              goes through load_depth on DepthConsts instead of RenderConsts::depth, and its stores take all seven target formats;
                                              always with KF_TARGET, kernels of their own (atmo_render[_proxy|_views|_views_proxy]_depth_target_kernel), for the
-                                             same reason */ };
+                                             same reason */,
+                          KF_DETAIL = 8192 /* the cloud density with the reference's CLOUDS_ALWAYS_LOW_QUALITY off (atmo_set_cloud_detail, include/atmo_cloud_detail.h):
+                                              the detail fetch of get_density_full and the alpha0 branch of get_light_raymarched, through DetailConsts; a kernel of
+                                              its own (atmo_render_detail_kernel), for the same reason */ };
 
 // The far-mode draw's proxy (planet_atmosphere.gd:300-321: a BoxMesh of edge box_size centred on the node, rasterised with back-face culling, near / far
 // clipping and Godot 4.3's reverse-Z GREATER_OR_EQUAL depth test).  Pixel (nx, ny) of the existing prologue's NDC: its segment from the near plane (z = 1) to
@@ -202,6 +205,14 @@ struct DepthConsts {
     const void *texels;    // the viewport's first texel
     int32_t pitch_bytes;   // bytes from one row to the next
     int32_t format;        // uniform, read only where the sample is loaded and decoded
+};
+
+// Cloud detail (include/atmo_cloud_detail.h states the arithmetic): what the KF_DETAIL kernels read beside RenderConsts.  A kernel argument of its own, behind
+// RenderConsts, which stays what it was.
+struct DetailConsts {
+    float c;            // [host] RN(AtmoFrame::time * 0.01f): the detail fetch is the shape volume at RN(RN(p * 15) + c)
+    float shape_lo_d;   // [host] bounds of RN(shape - RN(0.2 * detail)) over every filtered texel value of `shape` and detail in [0, 1 + 2^-20]: what the
+    float shape_hi_d;   //        coverage-first early outs of a FULL-quality sample test against (RenderConsts::shape_lo01 / shape_hi01 are detail = 0.5's)
 };
 
 // Several views in one launch (include/atmo_views.h).  The per-view RenderConsts live in a device table (the kernel's first argument: a const __restrict__
@@ -275,6 +286,10 @@ hipError_t launch_render_views_depth_target(int flags, int light_steps, const Re
                                             const ViewsDepthConsts &vdc, hipStream_t stream);
 hipError_t launch_render_views_proxy_depth_target(int flags, int light_steps, const RenderConsts *table_dev, const ViewsProxyTargetConsts &vptc,
                                                   const ViewsDepthConsts &vdc, hipStream_t stream);
+// the cloud-detail draws (atmo_set_cloud_detail; include/atmo_cloud_detail.h): the six LUT-light cloud families of the default forms (detail_family_supported),
+// one lane per ray, row-major over the grid of the rect in rc, no tile order and no cost recording; flags WITHOUT KF_DETAIL, which the launcher adds
+bool detail_family_supported(int flags);
+hipError_t launch_render_detail(int flags, const RenderConsts &rc, const DetailConsts &xc, hipStream_t stream);
 // load_depth's decode over n texels of a caller's array: out[i] = decode(texels[i]) (atmo_debug_decode_depth)
 hipError_t launch_decode_depth(int format, const void *texels, float *out, size_t n, hipStream_t stream);
 // store_target<format> over n pixels: dst[i] = encode(src[i]), or encode(blend(src[i], decode(dst[i]))) when composite (atmo_debug_store_target)

@@ -1455,9 +1455,14 @@ __device__ __forceinline__ float4 march_atmosphere_v1_precise(const RenderConsts
 #define DENSITY_RAMP_ONE __uint_as_float(0x3ed70a3du)
 // QUAD (with LOD): called in lock-step by the lanes of a wave (the march): the partners' coordinates come from the whole-quad exchange;
 // otherwise from the partner positions in *nb (light taps).
-template <bool EARLY_OUT, bool LOD = false, bool QUAD = false>
-__device__ __forceinline__ float cloud_density_precise(const RenderConsts &rc, float px, float py, float pz, float hr, const QuadNb *nb = nullptr DENS_STAT_ARG) {
+// DETAIL (KF_DETAIL; include/atmo_cloud_detail.h): get_density_full with CLOUDS_ALWAYS_LOW_QUALITY off.  `full` (per lane) says whether this call is
+// get_density (the detail fetch) or get_density_low (detail = 0.5: the function as it was, bit for bit); *low_out, where asked for, receives get_density_low
+// of the same position beside a full result -- it shares coverage, shape and height curve with it and needs no fetch.  No `fp contract` pragma in here.
+template <bool EARLY_OUT, bool LOD = false, bool QUAD = false, bool DETAIL = false>
+__device__ __forceinline__ float cloud_density_precise(const RenderConsts &rc, float px, float py, float pz, float hr, const QuadNb *nb = nullptr DENS_STAT_ARG,
+                                                       const DetailConsts *xc = nullptr, bool full = false, float *low_out = nullptr) {
     DENS_STAT(0);
+    if (DETAIL && low_out != nullptr) *low_out = 0.0f;   // every early-out to 0 below holds for detail = 0.5 as well (it lies inside the bounds)
     const float t = 2.0f * hr - 1.0f;
     const float hc = fmaxf(1.0f - t * t, 0.0f);
     if (EARLY_OUT && !(hc > 0.0f)) return 0.0f;
@@ -1469,7 +1474,7 @@ __device__ __forceinline__ float cloud_density_precise(const RenderConsts &rc, f
         // that bound and at the largest shape value the exact result is 0.  ~10 % of the samples inside the layer.
         const float cov_hi = (1.0f + 9.5367431640625e-07f) - 0.25f * hr + rc.coverage_bias;
         const float m_hi = -1.2f * (1.0f - cov_hi) + 1.5f * cov_hi;
-        if ((rc.shape_hi01 + m_hi) * hc <= DENSITY_RAMP_ZERO) return 0.0f;
+        if (((DETAIL && full ? xc->shape_hi_d : rc.shape_hi01) + m_hi) * hc <= DENSITY_RAMP_ZERO) return 0.0f;   // (DETAIL: the bound below)
     }
     float coverage = 1.0f;
     if (LOD && QUAD) {
@@ -1498,14 +1503,44 @@ __device__ __forceinline__ float cloud_density_precise(const RenderConsts &rc, f
         // result is 0, and if it is >= 1 at shape_lo the exact result is 1: bit-identical, no trilinear fetch (the
         // 8-texel exact filter is ~45 % of a density evaluation).
         // (x * 50 - 20 <= 0 and >= 1 decided on x itself: DENSITY_RAMP_ZERO / _ONE, two instructions fewer per test)
-        if ((rc.shape_hi01 + m) * hc <= DENSITY_RAMP_ZERO) return 0.0f;
-        if ((rc.shape_lo01 + m) * hc >= DENSITY_RAMP_ONE) return 1.0f;
+        if constexpr (DETAIL) {
+            // The same two tests for a full-quality sample.  x(detail) = ((shape - RN(0.2 * detail)) + m) * hc, every operation rounded, is monotone
+            // non-decreasing in `shape` and NON-INCREASING in `detail` (a rounded product by +0.2, subtracted), and detail -- the same exact filter of a
+            // UNORM8 volume -- lies in [0, 1 + 2^-20].  So x <= the value at (shape_hi, detail = 0) = shape_hi_d, and x >= the value at
+            // (shape_lo, detail = 1 + 2^-20) = shape_lo_d (host: detail_consts): <= 0 at the first means 0, >= 1 at the second means 1, bit for bit, with
+            // neither fetch.  detail = 0.5 lies inside the bounds, so get_density_low of the same position is 0 / 1 with it (*low_out).
+            // A low-quality call (!full) tests against the bounds it always had.
+            const float hi = full ? xc->shape_hi_d : rc.shape_hi01, lo = full ? xc->shape_lo_d : rc.shape_lo01;
+            if ((hi + m) * hc <= DENSITY_RAMP_ZERO) return 0.0f;
+            if ((lo + m) * hc >= DENSITY_RAMP_ONE) {
+                if (low_out != nullptr) *low_out = 1.0f;
+                return 1.0f;
+            }
+        } else {
+            if ((rc.shape_hi01 + m) * hc <= DENSITY_RAMP_ZERO) return 0.0f;
+            if ((rc.shape_lo01 + m) * hc >= DENSITY_RAMP_ONE) return 1.0f;
+        }
     }
     DENS_STAT(2);
     const float s = rc.shape_scale;
     const float tex = shape_sample<true>(rc.shape, rc.shape_n, rc.shape_log2n, px * s, py * s, pz * s, rc.shape_f4);
     float shape = 0.5f * (1.0f - rc.shape_factor) + tex * rc.shape_factor;
     if (rc.shape_invert) shape = 1.0f - shape;
+    if constexpr (DETAIL) {
+        // texture(u_cloud_shape_texture, pos_world * 15.0 + vec3(time * 0.01)).r (clouds:52-53): q = RN(RN(p * 15) + c), unfused -- at a planet radius of 100
+        // the texel coordinate is ~1e5 and its last bits are the filter weights --, then the exact trilinear filter of the bound volume (repeat wrap; a
+        // volume whose size is no power of two through the unfused p * n - 0.5).  A divergent branch: the low-quality lanes skip the fetch.
+        float sub = 0.1f;   // RN(0.2f * 0.5f)
+        if (full) {
+            const float qx = add_unfused(mul_unfused(px, 15.0f), xc->c), qy = add_unfused(mul_unfused(py, 15.0f), xc->c), qz = add_unfused(mul_unfused(pz, 15.0f), xc->c);
+            const float detail = shape_sample<true>(rc.shape, rc.shape_n, rc.shape_log2n, qx, qy, qz, rc.shape_f4);
+            sub = mul_unfused(0.2f, detail);
+        }
+        if (low_out != nullptr) *low_out = fminf(fmaxf(((shape - 0.1f) + m) * hc * 50.0f - 20.0f, 0.0f), 1.0f);
+        float density = ((shape - sub) + m) * hc;
+        density = density * 50.0f - 20.0f;
+        return fminf(fmaxf(density, 0.0f), 1.0f);
+    }
     float density = (shape - 0.1f + m) * hc;
     density = density * 50.0f - 20.0f;
     return fminf(fmaxf(density, 0.0f), 1.0f);
@@ -1544,6 +1579,12 @@ template <bool EARLY_OUT, bool PRECISE, bool LOD = false, bool QUAD = false>
 __device__ __forceinline__ float cloud_density(const RenderConsts &rc, float px, float py, float pz, float hr, const QuadNb *nb = nullptr DENS_STAT_ARG) {
     return PRECISE ? cloud_density_precise<EARLY_OUT, LOD, QUAD>(rc, px, py, pz, hr, nb DENS_STAT_PASS(stat_phase)) : cloud_density_fast<EARLY_OUT>(rc, px, py, pz, hr);
 }
+// ... and with CLOUDS_ALWAYS_LOW_QUALITY off (KF_DETAIL: the precise form only): get_density (full) or get_density_low per lane
+template <bool EARLY_OUT, bool LOD, bool QUAD>
+__device__ __forceinline__ float cloud_density_detail(const RenderConsts &rc, const DetailConsts &xc, float px, float py, float pz, float hr, const QuadNb *nb,
+                                                      bool full, float *low_out = nullptr) {
+    return cloud_density_precise<EARLY_OUT, LOD, QUAD, true>(rc, px, py, pz, hr, nb DENS_STAT_PASS(0), &xc, full, low_out);
+}
 
 // exact |p| and (|p| - bottom) / thickness, as a scalar fp32 evaluation would produce them
 __device__ __forceinline__ void cloud_height_r2(const RenderConsts &rc, float r2, float &r, float &hr) {
@@ -1563,14 +1604,19 @@ __device__ __forceinline__ bool wave_may_be_in_layer(const RenderConsts &rc, flo
 // get_light_raymarched (cloud_funcs.gdshaderinc:104-151): 6 density taps towards the sun.
 // 1 - prod(exp(-d_i)) = 1 - exp(-sum d_i): one exp instead of six.
 // Tap 0 is the sample itself: pos0 + float(0) * step_len * dir = pos0 (clouds:129 with i = 0), and get_density there is the value
-// raymarch_cloud computes for the same position one line later (clouds:217) -- the same function of the same arguments (both
-// alpha0 branches are, with CLOUDS_ALWAYS_LOW_QUALITY).  The caller passes that density in as d0: five taps
+// raymarch_cloud computes for the same position one line later (clouds:217) -- the same function of the same arguments WHERE tap 0 is
+// get_density: always with CLOUDS_ALWAYS_LOW_QUALITY (both alpha0 branches are then get_density_low, and so is the march's own call), and with the
+// switch off (DETAIL) on the alpha0 < 0.3 side only.  The caller passes that density in as d0: five taps
 // are evaluated instead of six, and the one saved is the expensive one -- a lit sample has density > 0, so its tap 0 never takes
 // an early-out and always pays the full exact shape + coverage filters.  Bit-identical.
-template <bool PRECISE, bool LOD = false>
+// DETAIL: `full` = alpha0 < 0.3 (clouds:132-136; alpha0 = the march's alpha BEFORE this sample) chooses get_density or get_density_low for all six taps,
+// per lane.  On the other side tap 0 is get_density_low of the sample's position, d0_low: the march's density evaluation hands it out beside its own
+// (cloud_density_precise's *low_out -- same coverage, shape and height curve, no second fetch).
+template <bool PRECISE, bool LOD = false, bool DETAIL = false>
 __device__ __forceinline__ float light_raymarched(const RenderConsts &rc, float px, float py, float pz, float hr0, float d0,
-                                                  float sx, float sy, float sz, const QuadNb *nb = nullptr) {
-    float sum = __builtin_fmaf(d0, rc.rm_weight[0], 0.0f);
+                                                  float sx, float sy, float sz, const QuadNb *nb = nullptr, const DetailConsts *xc = nullptr, bool full = false,
+                                                  float d0_low = 0.0f) {
+    float sum = __builtin_fmaf(DETAIL && !full ? d0_low : d0, rc.rm_weight[0], 0.0f);
     auto tap_i = [&](int i) {
         // exact: pos0 + (i*step)*dir, unfused; the product (float(i) * step_len_i) * dir is uniform and comes rounded from the host
         // (two SGPR factors would cost a move and a multiply per component and tap)
@@ -1583,7 +1629,9 @@ __device__ __forceinline__ float light_raymarched(const RenderConsts &rc, float 
             tap.vx = nb->vx; tap.vy = nb->vy; tap.lvl = nb->lvl; tap.regs = nullptr;
             tap.px = nb->px; tap.py = nb->py; tap.k = V3{kx, ky, kz}; tap.e2 = nb->e2;
         }
-        const float d = cloud_density<true, PRECISE, LOD>(rc, qx, qy, qz, hr, LOD ? &tap : nullptr DENS_STAT_PASS(1));
+        float d;
+        if constexpr (DETAIL) d = cloud_density_detail<true, LOD, false>(rc, *xc, qx, qy, qz, hr, LOD ? &tap : nullptr, full);
+        else d = cloud_density<true, PRECISE, LOD>(rc, qx, qy, qz, hr, LOD ? &tap : nullptr DENS_STAT_PASS(1));
         sum = __builtin_fmaf(d, rc.rm_weight[i], sum);  // step_len_i * density_scale  [host]
     };
     if (LOD) {  // the LOD sampler inlined five times doubles the kernel's code (8 300 -> 4 200 lines of ISA): rolled, the draw is 6 % faster
@@ -1655,9 +1703,12 @@ __device__ __forceinline__ float rm_sample_weight(RmRecurrence &s, float density
 // light -- while the recurrence over the samples (transmittance floor, light sum, alpha) runs in step order on the
 // pair's values exchanged by DPP.  Every sample is evaluated with the same arithmetic as in the one-lane form (the
 // position is still advanced one rounded addition per step), so the result is bit-identical; only lane 0's is used.
-template <bool RM, bool PRECISE, int SPLIT, bool LOD = false>
+// DETAIL (KF_DETAIL, one lane per ray, precise): every sample's density is get_density -- the detail fetch -- and the raymarched light, which now depends on
+// the march's alpha before the sample (light_raymarched), is evaluated in place under BOTH samplers: a deferred lit-sample queue would have to carry alpha0.
+template <bool RM, bool PRECISE, int SPLIT, bool LOD = false, bool DETAIL = false>
 __device__ __forceinline__ float2 march_clouds(const RenderConsts &rc_in, V3 dir_m, float t_begin, float t_end, float jitter, int half,
-                                               QuadRegs *qregs = nullptr, const f32x4 *lvl = nullptr) {
+                                               QuadRegs *qregs = nullptr, const f32x4 *lvl = nullptr, const DetailConsts *xc = nullptr) {
+    static_assert(!DETAIL || (PRECISE && SPLIT == 1), "cloud detail: the precise form, one lane per ray");
     // Under the declared sampler the raymarched light is evaluated IN PLACE with one lane per ray as well (round 5) -- this function instead of the
     // lit-sample queue, whose arithmetic it keeps (same bits): 73 VGPRs and no queue in LDS instead of 86 / 15 KB, six waves per SIMD instead of five, no
     // twelve-word entries through LDS, no second whole-quad block per lit sample.  Measured then (profiles/round5/ab_rm_inplace.txt): 3840x2160 -11.4 %
@@ -1738,9 +1789,14 @@ __device__ __forceinline__ float2 march_clouds(const RenderConsts &rc_in, V3 dir
         if (SPLIT == 1 || it * SPLIT + half < steps) {
             float r = 0.0f, hr = 0.0f;
             const float r2 = px * px + py * py + pz * pz;
+            float density_low = 0.0f;   // DETAIL && RM: get_density_low of this position (tap 0 of the light where alpha0 >= 0.3)
+            // DETAIL && RM: alpha0 < 0.3 (clouds:132), alpha0 = 1 - the running product of the transmittances.  The text's alpha += (1 - t) (1 - alpha) is the
+            // same number up to the roundings of either recurrence and of the hardware exp2; the fixtures hold no pixel within 1e-4 of the threshold.
+            const bool full_taps = DETAIL && RM && (1.0f - (RMQ_FORM ? rec.one_minus_alpha : one_minus_alpha)) < 0.3f;
             if (wave_may_be_in_layer(rc, r2)) {
                 cloud_height_r2(rc, r2, r, hr);
-                density = cloud_density<true, PRECISE, LOD, LOD>(rc, px, py, pz, hr, LOD ? &nb : nullptr);
+                if constexpr (DETAIL) density = cloud_density_detail<true, LOD, LOD>(rc, *xc, px, py, pz, hr, LOD ? &nb : nullptr, true, RM ? &density_low : nullptr);
+                else density = cloud_density<true, PRECISE, LOD, LOD>(rc, px, py, pz, hr, LOD ? &nb : nullptr);
             }
             // the light value of a zero-density sample (6 more density taps in the raymarched variant) is never observed
             if (RMQ_FORM) {
@@ -1756,11 +1812,13 @@ __device__ __forceinline__ float2 march_clouds(const RenderConsts &rc_in, V3 dir
                     enb.k = V3{0.0f, 0.0f, 0.0f};
                     auto dist2 = [&](V3 p) { const float a = p.x - px, b = p.y - py, c = p.z - pz; return __builtin_fmaf(a, a, __builtin_fmaf(b, b, c * c)); };
                     enb.e2 = cube_lod_scaled_spread(rc, fmaxf(enb.vx ? dist2(enb.px) : 0.0f, enb.vy ? dist2(enb.py) : 0.0f) * 1.001f);
-                    la = light_raymarched<PRECISE, true>(rc, px, py, pz, hr, density, sx, sy, sz, &enb);
+                    if constexpr (DETAIL) la = light_raymarched<PRECISE, true, true>(rc, px, py, pz, hr, density, sx, sy, sz, &enb, xc, full_taps, density_low);
+                    else la = light_raymarched<PRECISE, true>(rc, px, py, pz, hr, density, sx, sy, sz, &enb);
                 }
             } else if (density > 0.0f) {
 #pragma clang fp contract(fast)
-                la = RM ? light_raymarched<PRECISE, false>(rc, px, py, pz, hr, density, sx, sy, sz, nullptr) : hr;
+                if constexpr (DETAIL && RM) la = light_raymarched<PRECISE, false, true>(rc, px, py, pz, hr, density, sx, sy, sz, nullptr, xc, full_taps, density_low);
+                else la = RM ? light_raymarched<PRECISE, false>(rc, px, py, pz, hr, density, sx, sy, sz, nullptr) : hr;
                 // get_planet_shadow: smoothstep(-0.3, 0.3, dot(normalize(pos), -sun_dir))
                 const float sd = -(px * sx + py * sy + pz * sz) * hw_rcp(r);
                 const float st = sat((sd + 0.3f) * (1.0f / 0.6f));
@@ -2117,7 +2175,10 @@ __device__ __forceinline__ void store_target_zero_all_rt(const int format, void 
 
 template <int FLAGS, int LSTEPS, int SPLIT>
 __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int tile_x, const int tile_y, const ProxyConsts *pc = nullptr,
-                                            const TargetConsts *tc = nullptr, const DepthConsts *dc = nullptr) {
+                                            const TargetConsts *tc = nullptr, const DepthConsts *dc = nullptr, const DetailConsts *xc = nullptr) {
+    constexpr bool DETAIL = (FLAGS & KF_DETAIL) != 0;   // the cloud march with CLOUDS_ALWAYS_LOW_QUALITY off, through *xc
+    static_assert(!DETAIL || ((FLAGS & ~(KF_DETAIL | KF_CUBE_LOD | KF_CLOUD_LIGHT_RM | KF_LITE)) == (KF_PRECISE | KF_CLOUDS) && SPLIT == 1),
+                  "cloud detail: the LUT-light precise cloud families, float output, one lane per ray");
     constexpr bool CLOUDS = (FLAGS & KF_CLOUDS) != 0;
     constexpr bool RM = (FLAGS & KF_CLOUD_LIGHT_RM) != 0;
     constexpr bool DIRECT = (FLAGS & KF_LIGHT_DIRECT) != 0;
@@ -2339,7 +2400,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                 dir_m.y = M[1] * dir.x + M[5] * dir.y + M[9] * dir.z;
                 dir_m.z = M[2] * dir.x + M[6] * dir.y + M[10] * dir.z;
                 float2 rr;
-                if constexpr (RM && SPLIT == 1 && !LOD) {
+                if constexpr (DETAIL) {   // light in place under both samplers (march_clouds)
+                    rr = march_clouds<RM, PRECISE, 1, LOD, true>(rc, dir_m, c0, c1, jitter, 0, &qregs, lvl_table, xc);
+                } else if constexpr (RM && SPLIT == 1 && !LOD) {
                     __shared__ float rmq[(TILE_W * TILE_H / 64) * RMQ_WORDS_PER_WAVE];
                     rr = march_clouds_rm_queue<PRECISE>(rc, dir_m, c0, c1, jitter, rmq + wave * RMQ_WORDS_PER_WAVE);
                 } else {
@@ -3516,6 +3579,10 @@ const char *render_kernel_name(int flags, int light_steps, int split) {
     static thread_local char name[80];
     const bool v2_precise = (flags & KF_ATMO_REF) != 0;  // its light march is a run-time loop
     const int lsteps = ((flags & KF_LIGHT_DIRECT) && light_steps == 8 && !v2_precise && !(flags & KF_VIEW_POS)) ? 8 : 0;
+    if (flags & KF_DETAIL) {   // atmo_render_detail_kernel<FLAGS, LSTEPS>
+        snprintf(name, sizeof(name), "atmo_render_detail_kernel<%d, %d>", flags, lsteps);
+        return name;
+    }
     if (flags & KF_DEPTH) {   // atmo_render[_views][_proxy]_depth_target_kernel<FLAGS, LSTEPS[, SPLIT]>
         const char *views = (flags & KF_VIEWS) ? "_views" : "", *proxy = (flags & KF_PROXY) ? "_proxy" : "";
         if (flags & (KF_VIEWS | KF_PROXY)) snprintf(name, sizeof(name), "atmo_render%s%s_depth_target_kernel<%d, %d>", views, proxy, flags, lsteps);
@@ -3655,5 +3722,50 @@ hipError_t launch_decode_depth(int format, const void *texels, float *out, size_
     hipLaunchKernelGGL(atmo_decode_depth_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, format, texels, out, n);
     return hipGetLastError();
 }
+
+// ---- cloud detail (KF_DETAIL; include/atmo_cloud_detail.h) -------------------------------------------------------------------------------------
+// The cloud draws with the reference's CLOUDS_ALWAYS_LOW_QUALITY off: atmo_render_kernel's shading with a DetailConsts behind RenderConsts, which the density
+// evaluation (cloud_density_precise<.., DETAIL>) and the raymarched light (light_raymarched<.., DETAIL>) read.  A kernel of its own name (no older kernel's
+// name is a substring of it, nor the reverse), defined and instantiated behind everything else, so that every older kernel keeps its code and its place in
+// the code object.  One lane per ray; the launch is ROW-MAJOR over the rect's grid, as the proxy draws' -- no learnt tile order, no cost recording: the
+// order is a schedule, frames do not depend on it, and nothing has been measured yet that a schedule could be tuned on (profiles/cloud_detail/README.md).
+// Launch bounds: its atmo_render_kernel twin's, but for the two declared-sampler kernels without raymarched light: under their twins' bound of six waves
+// (80 VGPRs) the second filter's eight texels and weights left them a 12 / 16-byte stack frame; under five they take 87 / 88 VGPRs and none
+// (tools/check_quad_regs.py holds every kernel of the file to ScratchSize 0).  profiles/cloud_detail/README.md has the table against the twins.
+constexpr int detail_min_waves(int flags) {
+    return (flags & KF_CUBE_LOD) && !(flags & KF_CLOUD_LIGHT_RM) ? 5 : render_min_waves(flags);
+}
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H, detail_min_waves(FLAGS)) void atmo_render_detail_kernel(const RenderConsts rc, const DetailConsts xc) {
+    static_assert((FLAGS & KF_DETAIL) != 0, "cloud-detail kernels carry KF_DETAIL");
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, nullptr, nullptr, nullptr, &xc);
+}
+// the six LUT-light cloud families of ATMO_DEFAULT_FAMILIES (the direct-light cloud families are this project's own composition: no reference shader pins them)
+#define ATMO_DETAIL_FAMILIES(ONE)                                 \
+    ONE(KF_PRECISE | KF_CLOUDS)                                   \
+    ONE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)               \
+    ONE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)                     \
+    ONE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM) \
+    ONE(KF_PRECISE | KF_LITE | KF_CLOUDS)                         \
+    ONE(KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS)
+bool detail_family_supported(int flags) {
+    switch (flags) {
+#define ATMO_DETAIL_LISTED(F) case (F):
+        ATMO_DETAIL_FAMILIES(ATMO_DETAIL_LISTED)
+#undef ATMO_DETAIL_LISTED
+        return true;
+    default: return false;
+    }
+}
+hipError_t launch_render_detail(int flags, const RenderConsts &rc, const DetailConsts &xc, hipStream_t stream) {
+    if (rc.out == nullptr || rc.tile_order != nullptr || rc.tile_cost != nullptr) return hipErrorInvalidValue;   // float output, row-major, nothing recorded
+    switch (flags) {
+#define ATMO_DETAIL_LAUNCH(F) case (F): return launch_rect(atmo_render_detail_kernel<(F) | KF_DETAIL, 0>, rc, stream, xc);
+        ATMO_DETAIL_FAMILIES(ATMO_DETAIL_LAUNCH)
+#undef ATMO_DETAIL_LAUNCH
+    default: return hipErrorInvalidValue;
+    }
+}
+#undef ATMO_DETAIL_FAMILIES
 
 }  // namespace atmo

@@ -285,7 +285,7 @@ class PlanetAtmosphere:
     def __init__(self, device: int = 0, light_mode: str = "lut", light_steps: int = 0,
                  view_steps: int | None = None, cloud_steps: int | None = None, blue_noise=None,
                  precise_clouds: bool = True, precise_atmosphere: bool = False, double_precision: bool = False, lane_split: int = 0,
-                 tile_feedback: int = -1, cubemap_lod: bool | None = None, target_cleared: bool = False):
+                 tile_feedback: int = -1, cubemap_lod: bool | None = None, target_cleared: bool = False, cloud_detail: bool = False):
         self._lib = N.load()
         self._device = int(device)
         self._light_mode = {"lut": N.LIGHT_LUT, "direct": N.LIGHT_DIRECT}[light_mode]
@@ -298,6 +298,8 @@ class PlanetAtmosphere:
         self._lane_split = int(lane_split)  # atmo_set_lane_split: 0 auto, 1 / 2 lanes per ray
         self._tile_feedback = int(tile_feedback)  # atmo_set_tile_feedback: -1 default (on), 0 off, 1 on
         self._target_cleared = bool(target_cleared)  # atmo_set_target_cleared: discarded fragments write nothing (the shader's `discard`)
+        # atmo_set_cloud_detail: `#define CLOUDS_ALWAYS_LOW_QUALITY` (main:49) commented out -- the detail fetch of the cloud density, moving with `time`
+        self._cloud_detail = bool(cloud_detail)
         # atmo_set_sampler_lod: None = as the shader declares the samplerCube (linear-mipmap: implicit LOD from the 2x2 pixel quad when a mip
         # chain is bound), True = the same, required (an error if the draw cannot use it), False = level 0 only
         self._cubemap_lod = None if cubemap_lod is None else bool(cubemap_lod)
@@ -342,6 +344,26 @@ class PlanetAtmosphere:
         if self._target_cleared:  # (an A/B library older than round 4 has no such entry point: only asked for when wanted)
             N.check(ctx, self._lib.atmo_set_target_cleared(ctx, 1))
         N.check(ctx, self._lib.atmo_set_sampler_lod(ctx, -1 if self._cubemap_lod is None else (1 if self._cubemap_lod else 0)))
+        if self._cloud_detail:  # (only asked for when wanted: a library without include/atmo_cloud_detail.h draws everything else)
+            self._set_cloud_detail(True)
+
+    def _set_cloud_detail(self, on: bool):
+        if not hasattr(self._lib, "atmo_set_cloud_detail"):
+            raise RuntimeError("this libatmo_hip.so has no cloud detail (include/atmo_cloud_detail.h); rebuild it")
+        N.check(self._ctx, self._lib.atmo_set_cloud_detail(self._ctx, 1 if on else 0))
+
+    @property
+    def cloud_detail(self) -> bool:
+        """The cloud variants with the reference's CLOUDS_ALWAYS_LOW_QUALITY off (include/atmo_cloud_detail.h): render / render_composite draw the detail
+        fetch, which moves with `time`; every other draw of a cloud variant is refused while it is on."""
+        return self._cloud_detail
+
+    @cloud_detail.setter
+    def cloud_detail(self, on):
+        on = bool(on)
+        if on != self._cloud_detail:
+            self._set_cloud_detail(on)
+            self._cloud_detail = on
 
     def close(self):
         if getattr(self, "_ctx", None) is not None and self._ctx.value:

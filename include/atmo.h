@@ -81,7 +81,8 @@ typedef struct AtmoFrame {
     int32_t viewport_w, viewport_h;  /* VIEWPORT_SIZE */
     float planet_center_viewspace[3];/* varying v_planet_center_viewspace (atmosphere_vertex, main:101-102) */
     float sun_center_viewspace[3];   /* varying v_sun_center_viewspace (main:103) */
-    float time;                      /* TIME (cloud_funcs.gdshaderinc:298; dead in the shipped shaders) */
+    float time;                      /* TIME (cloud_funcs.gdshaderinc:298).  Read by the cloud-detail draws (atmo_cloud_detail.h: the detail fetch moves with it);
+                                        dead otherwise, as in the shipped shaders, whose CLOUDS_ALWAYS_LOW_QUALITY removes its only use */
     int32_t x0, y0, x1, y1;          /* rect to shade, in pixels */
 } AtmoFrame;
 

@@ -132,7 +132,9 @@ def check_inputs(body: str, private: set):
 
 def check(asm_text: str):
     results = {}
-    for m in re.finditer(r"^(_ZN4atmo\w+):[^\n]*\n(.*?)\n\s*s_endpgm", asm_text, re.S | re.M):
+    # a kernel's body runs to its .Lfunc_end label, not to its first s_endpgm: hipcc may place an early-exit block (and its s_endpgm) near the top, in front of the
+    # march -- two of the cloud-detail kernels have one at line ~120 of 4 000, and a body cut there holds no exchange block and would be skipped unseen
+    for m in re.finditer(r"^(_ZN4atmo\w+):[^\n]*\n(.*?)\n\.Lfunc_end", asm_text, re.S | re.M):
         name, body = m.group(1), m.group(2)
         if "s_wqm_b64" not in body:
             continue

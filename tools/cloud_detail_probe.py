@@ -1,0 +1,84 @@
+"""What the detail fetch costs (include/atmo_cloud_detail.h) on the MI355X: clouds_high and clouds_high_rm at 1920 x 1080, pose P_space, under both
+cubemap samplers, cloud detail off against on.
+
+    python tools/cloud_detail_probe.py [--out profiles/cloud_detail/cloud_detail_probe.json] [--reps 20] [--rounds 3]
+
+ONE process, one context per workload and sampler; the two arms are timed INTERLEAVED -- every round times `off` (the context's usual kernel, tile-order
+feedback as shipped), then `on` (atmo_render_detail_kernel, row-major), then `off` again (off2: off2 / off is the run-to-run spread of an arm against
+itself), device events around `reps` draws through the binding, after warm-up draws of both arms (the feedback's order settles within them).  TIME
+advances by a sixtieth of a second per draw in both arms (it is dead with detail off).  Reported per arm: the median, minimum and maximum of the rounds
+(ms per draw), on / off, and the kernel each arm reported.  Prints one JSON object.  Needs a device: there is no CPU figure."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from godot_atmosphere_shader_amd import scene as S  # noqa: E402
+from godot_atmosphere_shader_amd.demo import demo_textures, make_node  # noqa: E402
+
+WORKLOADS = ["clouds_high", "clouds_high_rm"]
+SAMPLERS = {"declared": None, "lod0": False}   # PlanetAtmosphere's cubemap_lod
+W, H = 1920, 1080
+
+
+def timed(node, cam, depth, out, reps, t0):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(reps):
+        node.render(cam, depth, out=out, time=t0 + i / 60.0)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=24)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("cloud_detail_probe.py measures on a device; none is visible")
+    tex = demo_textures()
+    cam = S.Camera.from_pose(W, H, "P_space")
+    depth = torch.from_numpy(S.depth_ground_sphere(cam)).cuda()
+    out = torch.empty((H, W, 4), dtype=torch.float32, device="cuda")
+    result = {"viewport": [W, H], "pose": "P_space", "reps": args.reps, "rounds": args.rounds, "device": torch.cuda.get_device_name(0), "rows": []}
+    for workload in WORKLOADS:
+        for sampler, lod in SAMPLERS.items():
+            node = make_node(workload, tex, cubemap_lod=lod)
+            names, arms = {}, {"off": [], "on": [], "off2": []}
+            try:
+                for on in (False, True):
+                    node.cloud_detail = on
+                    timed(node, cam, depth, out, args.warmup, 0.0)
+                    names["on" if on else "off"] = node.kernel_name
+                for r in range(args.rounds):
+                    for arm in ("off", "on", "off2"):
+                        node.cloud_detail = arm == "on"
+                        arms[arm].append(timed(node, cam, depth, out, args.reps, 1.0 + r))
+            finally:
+                node.close()
+            med = {a: sorted(v)[len(v) // 2] for a, v in arms.items()}
+            row = {"workload": workload, "sampler": sampler, "kernels": names,
+                   "ms": {a: {"median": med[a], "min": min(v), "max": max(v)} for a, v in arms.items()},
+                   "on_over_off": med["on"] / med["off"], "off2_over_off": med["off2"] / med["off"]}
+            result["rows"].append(row)
+            print(f"{workload:16s} {sampler:9s} off {med['off']:.4f} ms  on {med['on']:.4f} ms  ({row['on_over_off']:.3f} x)  off again {med['off2']:.4f} ms "
+                  f"({row['off2_over_off']:.3f} x)   {names['off']} -> {names['on']}", file=sys.stderr, flush=True)
+    text = json.dumps(result)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
