@@ -69,6 +69,10 @@ NOISE_VOLUME_SYMBOLS = ("atmo_generate_noise_volume",)
 # The ABI version stays 5 and the tuple stands beside EXPORTED_SYMBOLS, as PLANETS_SYMBOLS (NOTES.md): a host detects the feature by these symbols, and
 # load() binds them where the library has them (a library without them still loads; PlanetAtmosphere(cloud_detail=True) then raises).
 CLOUD_DETAIL_SYMBOLS = ("atmo_set_cloud_detail", "atmo_get_cloud_detail", "atmo_debug_cloud_detail_constants")
+# every symbol include/atmo_rays.h declares: caller-supplied rays (origin, direction and distance per ray) shaded as atmosphere_fragment shades a fragment,
+# and a frame's camera rays from the library's own prologue.  The ABI version stays 5 and the tuple stands beside EXPORTED_SYMBOLS, as PLANETS_SYMBOLS
+# (NOTES.md): a host detects the feature by these symbols, and load() binds them where the library has them (PlanetAtmosphere.shade_rays raises without).
+RAYS_SYMBOLS = ("atmo_shade_rays", "atmo_debug_frame_rays")
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -127,6 +131,15 @@ class AtmoViewDepthTarget(C.Structure):   # include/atmo_depth.h
         ("frame", AtmoFrame),
         ("depth", AtmoDepth),
         ("target", AtmoTarget),
+    ]
+
+
+class AtmoRay(C.Structure):   # include/atmo_rays.h: 32 bytes, what one row of a (n, 8) float32 tensor holds
+    _fields_ = [
+        ("origin", C.c_float * 3),
+        ("tmax", C.c_float),
+        ("dir", C.c_float * 3),
+        ("reserved", C.c_float),
     ]
 
 
@@ -287,6 +300,17 @@ def load() -> C.CDLL:
     }
     assert tuple(detail_sig) == CLOUD_DETAIL_SYMBOLS
     for name, (res, args) in detail_sig.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
+    # include/atmo_rays.h: the same rule
+    rays_sig = {
+        "atmo_shade_rays": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+        "atmo_debug_frame_rays": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, vp]),
+    }
+    assert tuple(rays_sig) == RAYS_SYMBOLS
+    for name, (res, args) in rays_sig.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype = res

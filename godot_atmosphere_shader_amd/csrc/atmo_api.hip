@@ -17,6 +17,7 @@
 #include "../../include/atmo_debug_prologue.h"
 #include "../../include/atmo_noise_volume.h"
 #include "../../include/atmo_cloud_detail.h"
+#include "../../include/atmo_rays.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -337,6 +338,12 @@ inline float smoothstepf(float e0, float e1, float x) {
     return t * t * (3.0f - 2.0f * t);
 }
 
+// march_distance_space and march_distance_ground of raymarch_cloud (clouds:186-197): what max_d mixes between by the height of the ray's origin
+inline void cloud_march_distances(float ground, float top, float bottom, float *space, float *groundd) {
+    *space = 0.5f * std::sqrt(1.0f - pow2f(ground / top)) * bottom;
+    *groundd = 3.0f * *space;
+}
+
 // The camera prologue of the cloudless direct-light kernels (shade_pixel: ATMO_PROLOGUE_CAMERA): which short forms give THIS draw the general forms' bits,
 // and the uniform products the kernels no longer evaluate.  Every test is on bit patterns or exact comparisons -- "about zero" would change the picture.
 //   PM_CAMERA.  v = inv_p (nx, ny, nz, 1) is summed left to right, unfused.  With P[4], P[8] zeros of either sign row x is ((a + z1) + z2) + P[12],
@@ -474,9 +481,9 @@ void fill_consts(const AtmoContext *ctx, const AtmoFrame *f, const float *depth,
         rc.sun_dir_model[r] = M[0 + r] * rc.sun_dir[0] + M[4 + r] * rc.sun_dir[1] + M[8 + r] * rc.sun_dir[2] + M[12 + r] * 0.0f;
     }
     {
-        const float ground = p.u_planet_radius, top = rc.clouds_top, bottom = rc.clouds_bottom;
-        const float space = 0.5f * std::sqrt(1.0f - pow2f(ground / top)) * bottom;
-        const float groundd = 3.0f * space;
+        const float top = rc.clouds_top, bottom = rc.clouds_bottom;
+        float space, groundd;
+        cloud_march_distances(p.u_planet_radius, top, bottom, &space, &groundd);
         const float len = std::sqrt(rc.origin_model[0] * rc.origin_model[0] + rc.origin_model[1] * rc.origin_model[1] +
                                     rc.origin_model[2] * rc.origin_model[2]);
         rc.max_d = mixf(groundd, space, smoothstepf(bottom, top * 1.05f, len));
@@ -2238,6 +2245,84 @@ int atmo_debug_cloud_detail_constants(AtmoContext *ctx, const AtmoFrame *frame, 
     const atmo::DetailConsts xc = cloud_detail_consts(ctx, frame, &sub_hi);
     out[0] = xc.c; out[1] = xc.shape_lo_d; out[2] = xc.shape_hi_d; out[3] = sub_hi;
     *count = 4;
+    return ATMO_OK;
+}
+
+// ---- caller-supplied rays (include/atmo_rays.h) -------------------------------------------------------------------------------------------------
+static_assert(sizeof(AtmoRay) == 32 && sizeof(AtmoRay) == 2 * sizeof(float4), "an AtmoRay is two float4");
+// Every check stands in front of hipSetDevice, in the header's order, so that a host-only context answers the same.  No feedback state is involved: the
+// launch is row-major over the batch, timed and counted as every accepted atmo_render, with nothing beside the draw stream (a graph capture takes it as it is).
+static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
+                     void *stream) {
+    const std::string who = "atmo_shade_rays";
+    if (!ctx) return ATMO_E_ARG;
+    if (n_rays == 0) return ATMO_OK;   // nothing to shade
+    if (!frame || !rays_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": null frame or device pointer");
+    if ((reinterpret_cast<uintptr_t>(rays_dev) & 15u) != 0 || (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0)
+        return fail(ctx, ATMO_E_ARG, who + ": rays_dev and rgba_dev must be 16-byte aligned");
+    if (width == 0) return fail(ctx, ATMO_E_ARG, who + ": width must be at least 1");
+    if ((uint64_t)first + (uint64_t)n_rays > ((uint64_t)1 << 32)) return fail(ctx, ATMO_E_ARG, who + ": first + n_rays must not exceed 2^32");
+    // the mode: the default forms under the level-0 sampler (atmo::rays_family_supported)
+    if (ctx->flags & atmo::KF_ATMO_REF) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for atmo_set_precision 2 (rays are shaded in the default forms: atmo_set_precision 1)");
+    if ((ctx->flags & (atmo::KF_CLOUDS | atmo::KF_LITE)) && !(ctx->flags & atmo::KF_PRECISE))
+        return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for atmo_set_precision 0 (rays are shaded in the default forms: atmo_set_precision 1)");
+    if (ctx->view_steps > 32) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for more than 32 view steps (this context has " + std::to_string(ctx->view_steps) + ")");
+    if (choose_split(ctx, frame) == 2) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel with two lanes per ray (atmo_set_lane_split 2)");
+    if ((ctx->flags & atmo::KF_CLOUDS) && (ctx->flags & atmo::KF_LIGHT_DIRECT))
+        return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for a cloud variant in the direct light mode (ATMO_LIGHT_DIRECT)");
+    ATMO_TRY(cloud_detail_refusal(ctx, who, "ray batches"));
+    if (ctx->sampler_lod == 1 && (ctx->flags & atmo::KF_CLOUDS) && ctx->cube.ptr && ctx->cube_levels > 1)
+        return fail(ctx, ATMO_E_STATE, who + ": rays sample the coverage cubemap at level 0, and this context demands the declared sampler (atmo_set_sampler_lod 1)");
+    int flags = 0, split = 1;
+    launch_shape(ctx, frame, &flags, &split, nullptr);
+    flags &= ~atmo::KF_CUBE_LOD;   // the sampler forced to level 0
+    if (split != 1 || !atmo::rays_family_supported(flags)) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for this context's mode");
+    ATMO_TRY(check_draw_textures(ctx, who));
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to shade on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    atmo::RenderConsts rc;
+    AtmoFrame fixed;
+    frame = draw_frame(ctx, frame, fixed);
+    draw_consts(ctx, frame, float_surfaces(nullptr, rgba_dev, false), rc);   // the uniforms, the textures, the sun; its matrices' camera forms are not read
+    atmo::RayConsts yc;
+    yc.rays = reinterpret_cast<const float4 *>(rays_dev);
+    yc.out = reinterpret_cast<float4 *>(rgba_dev);
+    yc.n = n_rays; yc.width = width; yc.first = first;
+    cloud_march_distances(ctx->p.u_planet_radius, rc.clouds_top, rc.clouds_bottom, &yc.md_space, &yc.md_ground);
+    yc.md_e0 = rc.clouds_bottom;
+    yc.md_e1 = rc.clouds_top * 1.05f;
+    hipStream_t s = (hipStream_t)stream;
+    ATMO_TRY(tex_order(ctx, s));  // texture updated on another stream
+    TimingBracket timing;
+    ATMO_TRY(timing_open(ctx, timing));
+    ATMO_TRY(timing_begin(ctx, timing, s));
+    HIP_TRY(ctx, atmo::launch_shade_rays(flags, rc, yc, s));
+    hipEvent_t marker = nullptr;
+    ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_RAYS, 1, true, &marker));
+    return timing_end(ctx, timing, s);
+}
+
+int atmo_shade_rays(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
+                    void *stream) {
+    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream);
+}
+
+int atmo_debug_frame_rays(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, AtmoRay *rays_dev, void *stream) {
+    const std::string who = "atmo_debug_frame_rays";
+    if (!ctx) return ATMO_E_ARG;
+    bool empty = false;
+    ATMO_TRY(check_frame(ctx, who, frame, &empty));
+    if (empty) return ATMO_OK;
+    if (!depth_dev || !rays_dev) return fail(ctx, ATMO_E_ARG, who + ": null device pointer");
+    if ((reinterpret_cast<uintptr_t>(rays_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, who + ": rays_dev must be 16-byte aligned");
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    atmo::RenderConsts rc;
+    AtmoFrame fixed;
+    fill_consts(ctx, draw_frame(ctx, frame, fixed), depth_dev, nullptr, rc);
+    const atmo::FrameRaysConsts fc = {depth_dev, reinterpret_cast<float4 *>(rays_dev)};
+    HIP_TRY(ctx, atmo::launch_frame_rays(rc, fc, (hipStream_t)stream));
     return ATMO_OK;
 }
 

@@ -170,7 +170,10 @@ enum KernelFlags : int { KF_CLOUDS = 1, KF_CLOUD_LIGHT_RM = 2, KF_LIGHT_DIRECT =
                                              same reason */,
                           KF_DETAIL = 8192 /* the cloud density with the reference's CLOUDS_ALWAYS_LOW_QUALITY off (atmo_set_cloud_detail, include/atmo_cloud_detail.h):
                                               the detail fetch of get_density_full and the alpha0 branch of get_light_raymarched, through DetailConsts; a kernel of
-                                              its own (atmo_render_detail_kernel), for the same reason */ };
+                                              its own (atmo_render_detail_kernel), for the same reason */,
+                          KF_RAYS = 16384 /* caller-supplied rays (atmo_shade_rays, include/atmo_rays.h): no camera prologue -- origin, direction and distance limit come
+                                             from an AtmoRay per lane, through RayConsts; the planet centre and the clouds' model-space origin are per-lane operands of
+                                             the marches (their LANE forms); kernels of their own (atmo_shade_rays_kernel), for the same reason */ };
 
 // The far-mode draw's proxy (planet_atmosphere.gd:300-321: a BoxMesh of edge box_size centred on the node, rasterised with back-face culling, near / far
 // clipping and Godot 4.3's reverse-Z GREATER_OR_EQUAL depth test).  Pixel (nx, ny) of the existing prologue's NDC: its segment from the near plane (z = 1) to
@@ -213,6 +216,23 @@ struct DetailConsts {
     float c;            // [host] RN(AtmoFrame::time * 0.01f): the detail fetch is the shape volume at RN(RN(p * 15) + c)
     float shape_lo_d;   // [host] bounds of RN(shape - RN(0.2 * detail)) over every filtered texel value of `shape` and detail in [0, 1 + 2^-20]: what the
     float shape_hi_d;   //        coverage-first early outs of a FULL-quality sample test against (RenderConsts::shape_lo01 / shape_hi01 are detail = 0.5's)
+};
+
+// Caller-supplied rays (include/atmo_rays.h states the arithmetic): what the KF_RAYS kernels read beside RenderConsts.  A kernel argument of its own, behind
+// RenderConsts, which stays what it was (of it these kernels read the uniforms, the textures and the sun direction; no matrix but view_to_model, no rect).
+struct RayConsts {
+    const float4 *rays;    // n AtmoRay = 2 n float4: (origin, tmax), (dir, reserved); 16-byte aligned
+    float4 *out;           // n float4
+    uint32_t n;            // rays of this launch (> 0)
+    uint32_t width, first; // ray i is image index first + i of an image `width` wide: the blue-noise texel of its jitter
+    // [host] the march-distance cap of raymarch_cloud (clouds:186-202) up to the ray's own part, smoothstep(md_e0, md_e1, |origin_model|):
+    float md_ground, md_space;   // march_distance_ground, march_distance_space (the two values fill_consts mixes into RenderConsts::max_d)
+    float md_e0, md_e1;          // clouds_bottom, clouds_top * 1.05
+};
+// ... and of the kernel that writes a frame's camera rays (atmo_debug_frame_rays): the rect of rc, row-major
+struct FrameRaysConsts {
+    const float *depth;    // h rows of w
+    float4 *rays;          // (y1 - y0) (x1 - x0) AtmoRay
 };
 
 // Several views in one launch (include/atmo_views.h).  The per-view RenderConsts live in a device table (the kernel's first argument: a const __restrict__
@@ -290,6 +310,12 @@ hipError_t launch_render_views_proxy_depth_target(int flags, int light_steps, co
 // one lane per ray, row-major over the grid of the rect in rc, no tile order and no cost recording; flags WITHOUT KF_DETAIL, which the launcher adds
 bool detail_family_supported(int flags);
 hipError_t launch_render_detail(int flags, const RenderConsts &rc, const DetailConsts &xc, hipStream_t stream);
+// the ray draws (atmo_shade_rays; include/atmo_rays.h): six families (rays_family_supported; the direct-light one with 8 light steps unrolled or any count),
+// 64 consecutive rays per wave, 256 per workgroup, row-major over the batch; flags WITHOUT KF_RAYS, which the launcher adds
+bool rays_family_supported(int flags);
+hipError_t launch_shade_rays(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream);
+// the camera rays of the rect in rc, as the float kernels' prologue forms them (atmo_debug_frame_rays)
+hipError_t launch_frame_rays(const RenderConsts &rc, const FrameRaysConsts &fc, hipStream_t stream);
 // load_depth's decode over n texels of a caller's array: out[i] = decode(texels[i]) (atmo_debug_decode_depth)
 hipError_t launch_decode_depth(int format, const void *texels, float *out, size_t n, hipStream_t stream);
 // store_target<format> over n pixels: dst[i] = encode(src[i]), or encode(blend(src[i], decode(dst[i]))) when composite (atmo_debug_store_target)

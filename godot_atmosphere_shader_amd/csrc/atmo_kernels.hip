@@ -1150,9 +1150,13 @@ __device__ __forceinline__ float sun_od_direct(const LightMarchConsts &k, float 
 __device__ __forceinline__ V3 scale_unfused(V3 d, float s) { return V3{d.x * s, d.y * s, d.z * s}; }  // no contraction here: products rounded on their own
 // HANDED (the cloudless direct-light kernels, ATMO_PROLOGUE_CAMERA_FORMS & 8): density^2, density^2 / 8, atmosphere_radius^2 and -coeff * LOG2E come
 // from the host, one IEEE operation each and therefore the same bits; those the loop reads are moved to VGPRs once.
-template <bool DIRECT, int LSTEPS, int SPLIT, bool VIEWPOS = false, bool HANDED = false>
-__device__ __forceinline__ float4 march_atmosphere(const RenderConsts &rc, V3 dir, float t_begin, float step_len, float jitter, int half) {
+// LANE (KF_RAYS, atmo_shade_rays_kernel): the planet centre relative to the ray's origin is the lane's own, `lc` -- the same expressions on a VGPR operand; every
+// older instantiation reads rc.center and stays the code it was.
+template <bool DIRECT, int LSTEPS, int SPLIT, bool VIEWPOS = false, bool HANDED = false, bool LANE = false>
+__device__ __forceinline__ float4 march_atmosphere(const RenderConsts &rc, V3 dir, float t_begin, float step_len, float jitter, int half,
+                                                   V3 lc = V3{0.0f, 0.0f, 0.0f}) {
 #pragma clang fp contract(fast)
+    static_assert(!LANE || (!VIEWPOS && SPLIT == 1), "a per-lane centre: the running position relative to the centre, one lane per ray");
     const int n0 = SPLIT == 2 ? (rc.view_steps + 1) / 2 : rc.view_steps;
     const int first = (SPLIT == 2 && half) ? n0 : 0;
     const int steps = (SPLIT == 2 && half) ? rc.view_steps - n0 : n0;
@@ -1175,9 +1179,9 @@ __device__ __forceinline__ float4 march_atmosphere(const RenderConsts &rc, V3 di
     static_assert(!VIEWPOS || SPLIT == 1, "reference-form position accumulation: one lane per ray");
     const V3 p0 = scale_unfused(dir, t_begin), sd = scale_unfused(dir, step_len);  // ray_origin (0) + ray_dir * t_begin; ray_dir * step_len
     float pvx = p0.x, pvy = p0.y, pvz = p0.z;                                      // VIEWPOS: the view-space position
-    float ox = fmaf(dir.x, t_begin, -rc.center[0]);
-    float oy = fmaf(dir.y, t_begin, -rc.center[1]);
-    float oz = fmaf(dir.z, t_begin, -rc.center[2]);
+    float ox = fmaf(dir.x, t_begin, -(LANE ? lc.x : rc.center[0]));
+    float oy = fmaf(dir.y, t_begin, -(LANE ? lc.y : rc.center[1]));
+    float oz = fmaf(dir.z, t_begin, -(LANE ? lc.z : rc.center[2]));
     const float sdx = VIEWPOS ? sd.x : dir.x * step_len, sdy = VIEWPOS ? sd.y : dir.y * step_len, sdz = VIEWPOS ? sd.z : dir.z * step_len;
     const float dstep = dens2 * step_len;
     float lr = 0.0f, lg = 0.0f, lb = 0.0f, view_od = 0.0f;
@@ -1394,7 +1398,8 @@ __device__ __forceinline__ float4 march_atmosphere_v2_precise(const RenderConsts
     return o;
 }
 
-__device__ __forceinline__ float4 march_atmosphere_v1_precise(const RenderConsts &rc, V3 dir, float t_begin, float t_end) {
+template <bool LANE = false>   // LANE: as march_atmosphere's
+__device__ __forceinline__ float4 march_atmosphere_v1_precise(const RenderConsts &rc, V3 dir, float t_begin, float t_end, V3 lc = V3{0.0f, 0.0f, 0.0f}) {
 #pragma clang fp contract(off)
     const float inv_steps = ieee_div(1.0f, (float)rc.view_steps);
     const float step_len = (t_end - t_begin) * inv_steps;
@@ -1403,7 +1408,7 @@ __device__ __forceinline__ float4 march_atmosphere_v1_precise(const RenderConsts
     float px = 0.0f + dir.x * t_begin, py = 0.0f + dir.y * t_begin, pz = 0.0f + dir.z * t_begin;
     float factor = 1.0f, light_sum = 0.0f;
     for (int i = 0; i < rc.view_steps; ++i) {
-        const float rx = px - rc.center[0], ry = py - rc.center[1], rz = pz - rc.center[2];
+        const float rx = px - (LANE ? lc.x : rc.center[0]), ry = py - (LANE ? lc.y : rc.center[1]), rz = pz - (LANE ? lc.z : rc.center[2]);
         const float d = exact_sqrt(rx * rx + ry * ry + rz * rz);
         const float ux = ieee_div(rx, d), uy = ieee_div(ry, d), uz = ieee_div(rz, d);
         // get_atmosphere_density(d), atmosphere_common.gdshaderinc:12-24
@@ -1652,14 +1657,21 @@ struct MarchRay {
     bool valid;
     float px, py, pz, ddx, ddy, ddz, step_len;
 };
-__device__ __forceinline__ MarchRay cloud_march_ray(const RenderConsts &rc, V3 dir_m, float t_begin, float t_end, float jitter) {
+// What a ray with an origin of its own hands the cloud march in place of two uniforms (KF_RAYS): its origin in model space and the march-distance cap,
+// which is a function of that origin's length (clouds:186-202)
+struct LaneOrigin {
+    V3 origin_model;
+    float max_d;
+};
+template <bool LANE = false>   // LANE: *lo instead of rc.origin_model and rc.max_d, the same expressions
+__device__ __forceinline__ MarchRay cloud_march_ray(const RenderConsts &rc, V3 dir_m, float t_begin, float t_end, float jitter, const LaneOrigin *lo = nullptr) {
     MarchRay m;
-    t_end = t_begin + fminf(t_end - t_begin, rc.max_d);
+    t_end = t_begin + fminf(t_end - t_begin, LANE ? lo->max_d : rc.max_d);
     m.step_len = (t_end - t_begin) * rc.inv_cloud_steps;
     const float js = jitter * m.step_len;
-    m.px = (rc.origin_model[0] + dir_m.x * js) + dir_m.x * t_begin;
-    m.py = (rc.origin_model[1] + dir_m.y * js) + dir_m.y * t_begin;
-    m.pz = (rc.origin_model[2] + dir_m.z * js) + dir_m.z * t_begin;
+    m.px = ((LANE ? lo->origin_model.x : rc.origin_model[0]) + dir_m.x * js) + dir_m.x * t_begin;
+    m.py = ((LANE ? lo->origin_model.y : rc.origin_model[1]) + dir_m.y * js) + dir_m.y * t_begin;
+    m.pz = ((LANE ? lo->origin_model.z : rc.origin_model[2]) + dir_m.z * js) + dir_m.z * t_begin;
     m.ddx = dir_m.x * m.step_len; m.ddy = dir_m.y * m.step_len; m.ddz = dir_m.z * m.step_len;
     m.valid = true;
     return m;
@@ -1705,10 +1717,13 @@ __device__ __forceinline__ float rm_sample_weight(RmRecurrence &s, float density
 // position is still advanced one rounded addition per step), so the result is bit-identical; only lane 0's is used.
 // DETAIL (KF_DETAIL, one lane per ray, precise): every sample's density is get_density -- the detail fetch -- and the raymarched light, which now depends on
 // the march's alpha before the sample (light_raymarched), is evaluated in place under BOTH samplers: a deferred lit-sample queue would have to carry alpha0.
-template <bool RM, bool PRECISE, int SPLIT, bool LOD = false, bool DETAIL = false>
+// LANE (KF_RAYS): the ray's own origin and march-distance cap, *lo (cloud_march_ray); level-0 sampler, one lane per ray.
+template <bool RM, bool PRECISE, int SPLIT, bool LOD = false, bool DETAIL = false, bool LANE = false>
 __device__ __forceinline__ float2 march_clouds(const RenderConsts &rc_in, V3 dir_m, float t_begin, float t_end, float jitter, int half,
-                                               QuadRegs *qregs = nullptr, const f32x4 *lvl = nullptr, const DetailConsts *xc = nullptr) {
+                                               QuadRegs *qregs = nullptr, const f32x4 *lvl = nullptr, const DetailConsts *xc = nullptr,
+                                               const LaneOrigin *lo = nullptr) {
     static_assert(!DETAIL || (PRECISE && SPLIT == 1), "cloud detail: the precise form, one lane per ray");
+    static_assert(!LANE || (!LOD && !DETAIL && SPLIT == 1), "per-ray origins: the level-0 sampler, no cloud detail, one lane per ray");
     // Under the declared sampler the raymarched light is evaluated IN PLACE with one lane per ray as well (round 5) -- this function instead of the
     // lit-sample queue, whose arithmetic it keeps (same bits): 73 VGPRs and no queue in LDS instead of 86 / 15 KB, six waves per SIMD instead of five, no
     // twelve-word entries through LDS, no second whole-quad block per lit sample.  Measured then (profiles/round5/ab_rm_inplace.txt): 3840x2160 -11.4 %
@@ -1729,7 +1744,7 @@ __device__ __forceinline__ float2 march_clouds(const RenderConsts &rc_in, V3 dir
     const RenderConsts &rc = (PRECISE && !RMQ_FORM) ? rc_v : rc_in;
     const int steps = rc.cloud_steps;
     // exact: positions
-    const MarchRay self = cloud_march_ray(rc, dir_m, t_begin, t_end, jitter);
+    const MarchRay self = cloud_march_ray<LANE>(rc, dir_m, t_begin, t_end, jitter, lo);
     const float step_len = self.step_len;
     float px = self.px, py = self.py, pz = self.pz;
     const float ddx = self.ddx, ddy = self.ddy, ddz = self.ddz;
@@ -1873,9 +1888,9 @@ constexpr int RMQ_CAP = 128;
 constexpr int RMQ_CHUNK = ATMO_RMQ_CHUNK;
 constexpr int RMQ_WORDS_PER_WAVE = 6 * RMQ_CAP + RMQ_CHUNK * 64;
 
-template <bool PRECISE>
+template <bool PRECISE, bool LANE = false>   // LANE: as march_clouds'
 __device__ __forceinline__ float2 march_clouds_rm_queue(const RenderConsts &rc, V3 dir_m, float t_begin, float t_end, float jitter,
-                                                        float *__restrict__ lds) {
+                                                        float *__restrict__ lds, const LaneOrigin *lo = nullptr) {
     // (no cloud_uniforms_to_vgprs here: eight more VGPRs take the declared-sampler kernel from 88 to 103 -- 4 waves per SIMD, +9 % -- and under a
     //  96-VGPR bound it spills for a gain of 1 %; three or four of them (93-95 VGPRs, one short of the step) bought 0.5-1.5 %; the level-0 kernel,
     //  bound to 80 VGPRs, is 0.5-1.3 % slower with them: profiles/round4/ab_vgpr_uniforms.txt)
@@ -1904,7 +1919,7 @@ __device__ __forceinline__ float2 march_clouds_rm_queue(const RenderConsts &rc, 
 #endif
 
     const int steps = rc.cloud_steps;
-    const MarchRay self = cloud_march_ray(rc, dir_m, t_begin, t_end, jitter);
+    const MarchRay self = cloud_march_ray<LANE>(rc, dir_m, t_begin, t_end, jitter, lo);
     const float step_len = self.step_len;
     float px = self.px, py = self.py, pz = self.pz;
     const float ddx = self.ddx, ddy = self.ddy, ddz = self.ddz;
@@ -3583,6 +3598,10 @@ const char *render_kernel_name(int flags, int light_steps, int split) {
         snprintf(name, sizeof(name), "atmo_render_detail_kernel<%d, %d>", flags, lsteps);
         return name;
     }
+    if (flags & KF_RAYS) {   // atmo_shade_rays_kernel<FLAGS, LSTEPS>
+        snprintf(name, sizeof(name), "atmo_shade_rays_kernel<%d, %d>", flags, lsteps);
+        return name;
+    }
     if (flags & KF_DEPTH) {   // atmo_render[_views][_proxy]_depth_target_kernel<FLAGS, LSTEPS[, SPLIT]>
         const char *views = (flags & KF_VIEWS) ? "_views" : "", *proxy = (flags & KF_PROXY) ? "_proxy" : "";
         if (flags & (KF_VIEWS | KF_PROXY)) snprintf(name, sizeof(name), "atmo_render%s%s_depth_target_kernel<%d, %d>", views, proxy, flags, lsteps);
@@ -3767,5 +3786,209 @@ hipError_t launch_render_detail(int flags, const RenderConsts &rc, const DetailC
     }
 }
 #undef ATMO_DETAIL_FAMILIES
+
+// ---- caller-supplied rays (KF_RAYS; include/atmo_rays.h states the arithmetic item by item) ---------------------------------------------------------
+// shade_pixel behind its prologue, for a ray that did not come out of a camera matrix: origin, direction and distance limit are an AtmoRay's, the planet
+// centre relative to the origin is the lane's own c' = RN(c - origin), and everything the reference does with in_v_planet_center_viewspace and
+// ray_origin = 0 is done with c' and origin 0 -- the marches take c' (and the clouds the model-space origin and its march-distance cap) through their LANE
+// forms.  Every expression below is shade_pixel's, under the same contraction mode, with the short exact forms (DIET) and the handed-over products (CAMF & 8,
+// & 2) its twin family takes: where the rays are a camera's (atmo_debug_frame_rays) the picture is atmo_render's under the level-0 sampler, bit for bit
+// (tests/test_rays_gpu.py).  What is NOT here: the sure-miss test and the camera rows (they need a projection), the declared sampler (a ray has no 2 x 2
+// quad to difference), tile order and cost recording (the launch is row-major over the batch), composite and packed stores.
+// Lane mapping: ray i of the batch is thread i -- 64 consecutive rays per wave, 256 per workgroup.  Kernels of their own name, defined and instantiated
+// behind everything else, so that every older kernel keeps its code and its place in the code object.
+constexpr int RAYS_BLOCK = 256;
+template <int FLAGS, int LSTEPS>
+__device__ __forceinline__ void shade_ray(const RenderConsts &rc, const RayConsts &yc) {
+    constexpr bool CLOUDS = (FLAGS & KF_CLOUDS) != 0;
+    constexpr bool RM = (FLAGS & KF_CLOUD_LIGHT_RM) != 0;
+    constexpr bool DIRECT = (FLAGS & KF_LIGHT_DIRECT) != 0;
+    constexpr bool LITE = (FLAGS & KF_LITE) != 0;
+    constexpr bool PRECISE = (FLAGS & KF_PRECISE) != 0;
+    static_assert((FLAGS & KF_RAYS) != 0 && (FLAGS & ~(KF_RAYS | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT | KF_LITE | KF_PRECISE)) == 0,
+                  "ray kernels: the default forms under the level-0 sampler");
+    static_assert(!(DIRECT && CLOUDS) && (PRECISE == (CLOUDS || LITE)) && !(RM && LITE), "ray kernels: the LUT-light cloud forms in precise mode, no cloud + direct light");
+    constexpr bool DIET = (!DIRECT || !CLOUDS) && !(CLOUDS && RM);                     // as shade_pixel's
+    constexpr int CAMF = (DIRECT && !CLOUDS) ? (ATMO_PROLOGUE_CAMERA_FORMS & 10) : 0;  // ... of the camera forms, the two that need no camera: the power-of-two
+                                                                                       // step length and the handed-over products
+    const uint32_t i = blockIdx.x * (uint32_t)RAYS_BLOCK + threadIdx.x;   // (grid = ceil(n / 256) blocks and n < 2^32: no wrap)
+    if (i >= yc.n) return;
+    const float4 ray_ot = yc.rays[2 * (size_t)i], ray_d = yc.rays[2 * (size_t)i + 1];   // one dwordx4 load each
+    float4 *out = yc.out + i;
+    float linear_depth = ray_ot.w;
+    const V3 dir = {ray_d.x, ray_d.y, ray_d.z};
+    const V3 center = {rc.center[0] - ray_ot.x, rc.center[1] - ray_ot.y, rc.center[2] - ray_ot.z};   // c' = RN(c - origin)
+
+    const SphereHit sh = sphere_setup(center, dir);
+    float2 rs_atmo;
+    if constexpr ((CAMF & 8) != 0) rs_atmo = hit_radius2<DIET>(sh, rc.atmosphere_radius2);
+    else rs_atmo = hit_radius<DIET>(sh, rc.atmosphere_radius);
+    if (rs_atmo.x == rs_atmo.y) {  // discard: a ray that misses the shell always receives zeros
+        *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const float t_begin = fmaxf(rs_atmo.x, 0.0f);
+    float t_end = fmaxf(rs_atmo.y, 0.0f);
+    {
+        float2 rs_ground;
+        if constexpr ((CAMF & 8) != 0) rs_ground = hit_radius2<DIET>(sh, rc.planet_radius2);
+        else rs_ground = hit_radius<DIET>(sh, rc.planet_radius);
+        float gd = 10000000.0f;
+        if (rs_ground.x != rs_ground.y) gd = rs_ground.x;
+        linear_depth = linear_depth * (1.0f - rc.sphere_depth_factor) + gd * rc.sphere_depth_factor;
+    }
+    t_end = fminf(t_end, linear_depth);
+
+    // the jitter of image index k = first + i: texel (x & 255, y & 255), x = k % width, y = k / width -- what atmo_render reads for pixel (x, y)
+    const uint32_t k = yc.first + i;
+    const uint32_t ky = k / yc.width, kx = k - ky * yc.width;
+    const float jitter = blue_noise_value<DIET>(rc.blue[(ky & 0xffu) * 256u + (kx & 0xffu)]);
+
+    float4 rgba;
+    if (LITE) {
+        rgba = march_atmosphere_v1_precise<true>(rc, dir, t_begin, t_end, center);
+    } else {
+        float view_step_len;
+        if ((CAMF & 2) != 0 && (rc.prologue_mode & PM_POW2_STEPS)) view_step_len = (t_end - t_begin) * rc.inv_view_steps;
+        else view_step_len = ieee_div(t_end - t_begin, (CAMF & 8) != 0 ? rc.view_steps_f : (float)rc.view_steps);
+        rgba = march_atmosphere<DIRECT, LSTEPS, 1, false, (CAMF & 8) != 0, true>(rc, dir, t_begin, view_step_len, jitter, 0, center);
+    }
+
+    if (CLOUDS) {
+        // --- render_clouds (cloud_funcs.gdshaderinc:249-324), gates evaluated exactly -----------------
+        const float2 rs_top = hit_radius<DIET>(sh, rc.clouds_top);
+        if (rs_top.x != rs_top.y) {
+            const float2 rs_bottom = hit_radius<DIET>(sh, rc.clouds_bottom);
+            const float c0 = fmaxf(rs_top.x, 0.0f);
+            const float c1 = fminf(rs_top.y, linear_depth);
+            if (c0 < linear_depth && (linear_depth > rs_bottom.y || rs_bottom.x > 0.0f)) {
+                const float *M = rc.view_to_model;
+                V3 dir_m;
+                dir_m.x = M[0] * dir.x + M[4] * dir.y + M[8] * dir.z;
+                dir_m.y = M[1] * dir.x + M[5] * dir.y + M[9] * dir.z;
+                dir_m.z = M[2] * dir.x + M[6] * dir.y + M[10] * dir.z;
+                // (view_to_model * (origin, 1)).xyz, the four products summed left to right (clouds:286): fill_consts' origin_model for origin = 0
+                LaneOrigin lo;
+                lo.origin_model.x = M[0] * ray_ot.x + M[4] * ray_ot.y + M[8] * ray_ot.z + M[12] * 1.0f;
+                lo.origin_model.y = M[1] * ray_ot.x + M[5] * ray_ot.y + M[9] * ray_ot.z + M[13] * 1.0f;
+                lo.origin_model.z = M[2] * ray_ot.x + M[6] * ray_ot.y + M[10] * ray_ot.z + M[14] * 1.0f;
+                {   // max_d = mix(ground, space, smoothstep(bottom, top * 1.05, length(ray_origin))) (clouds:186-202): fill_consts' max_d, operation for operation
+                    const V3 om = lo.origin_model;
+                    const float len = ieee_sqrt(om.x * om.x + om.y * om.y + om.z * om.z);
+                    const float st = clampf(ieee_div(len - yc.md_e0, yc.md_e1 - yc.md_e0), 0.0f, 1.0f);
+                    lo.max_d = mixf(yc.md_ground, yc.md_space, st * st * (3.0f - 2.0f * st));
+                }
+                float2 rr;
+                if constexpr (RM) {   // the lit-sample queue, as the twin: wave-private, four waves a workgroup
+                    __shared__ float rmq[(RAYS_BLOCK / 64) * RMQ_WORDS_PER_WAVE];
+                    rr = march_clouds_rm_queue<PRECISE, true>(rc, dir_m, c0, c1, jitter, rmq + (threadIdx.x / 64) * RMQ_WORDS_PER_WAVE, &lo);
+                } else {
+                    rr = march_clouds<RM, PRECISE, 1, false, false, true>(rc, dir_m, c0, c1, jitter, 0, nullptr, nullptr, nullptr, &lo);
+                }
+                {
+#pragma clang fp contract(fast)
+                    const float cl = rr.x, ca = rr.y;
+                    // blend_colors(self = atmosphere, over = cloud)  (util.gdshaderinc:61-69)
+                    const float sa = 1.0f - ca;
+                    const float a = rgba.w * sa + ca;
+                    float abx = 0.0f, aby = 0.0f, abz = 0.0f, abw = 0.0f;
+                    if (a != 0.0f) {
+                        const float inv_a = ieee_div(1.0f, a);
+                        const float ws = rgba.w * sa, wo = cl * ca;
+                        abx = (rgba.x * ws + wo) * inv_a;
+                        aby = (rgba.y * ws + wo) * inv_a;
+                        abz = (rgba.z * ws + wo) * inv_a;
+                        abw = a;
+                    }
+                    const float addx = rgba.x + cl * ca, addy = rgba.y + cl * ca, addz = rgba.z + cl * ca;
+                    const float addw = fmaxf(rgba.w, ca);
+                    rgba.x = mixf(abx, addx, rc.cloud_blend);
+                    rgba.y = mixf(aby, addy, rc.cloud_blend);
+                    rgba.z = mixf(abz, addz, rc.cloud_blend);
+                    rgba.w = mixf(abw, addw, rc.cloud_blend);
+                }
+            }
+        }
+    }
+    *out = rgba;
+}
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(RAYS_BLOCK, render_min_waves(FLAGS & ~KF_RAYS)) void atmo_shade_rays_kernel(const RenderConsts rc, const RayConsts yc) {
+    shade_ray<FLAGS, LSTEPS>(rc, yc);
+}
+// The camera rays of a frame (atmo_debug_frame_rays): for every pixel of the rect, row-major, the ray the float kernels form for it -- origin 0, the prologue's
+// dir, and linear_depth before the sphere-depth mix -- in the GENERAL prologue's arithmetic (main:128-169: the IEEE quotients and roots, the full 4 x 4 rows).
+// The short forms (DIET) and the camera rows (PM_CAMERA) are held equal to these by their own tests, and tests/test_rays_gpu.py holds the frames drawn from
+// these rays to atmo_render's, bit for bit, for every family.
+__global__ __launch_bounds__(RAYS_BLOCK) void atmo_frame_rays_kernel(const RenderConsts rc, const FrameRaysConsts fc) {
+    const size_t rw = (size_t)(rc.x1 - rc.x0), n = rw * (size_t)(rc.y1 - rc.y0);
+    const size_t i = (size_t)blockIdx.x * RAYS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int px = rc.x0 + (int)(i % rw), py = rc.y0 + (int)(i / rw);
+    const float nonlinear_depth = fc.depth[(size_t)py * rc.w + px];
+    const float uvx = pixel_coord<false>((float)px + 0.5f, rc.vw, rc.rcp_vw);
+    const float uvy = pixel_coord<false>((float)py + 0.5f, rc.vh, rc.rcp_vh);
+    const float nx = uvx * 2.0f - 1.0f, ny = uvy * 2.0f - 1.0f, nz = nonlinear_depth;
+    const float *P = rc.inv_p;
+    const float *Vm = rc.inv_v;
+    const float vx = P[0] * nx + P[4] * ny + P[8] * nz + P[12] * 1.0f;
+    const float vy = P[1] * nx + P[5] * ny + P[9] * nz + P[13] * 1.0f;
+    const float vz = P[2] * nx + P[6] * ny + P[10] * nz + P[14] * 1.0f;
+    const float vw = P[3] * nx + P[7] * ny + P[11] * nz + P[15] * 1.0f;
+    const float ww = Vm[3] * vx + Vm[7] * vy + Vm[11] * vz + Vm[15] * vw;
+    const float wx = Vm[0] * vx + Vm[4] * vy + Vm[8] * vz + Vm[12] * vw;
+    const float wy = Vm[1] * vx + Vm[5] * vy + Vm[9] * vz + Vm[13] * vw;
+    const float wz = Vm[2] * vx + Vm[6] * vy + Vm[10] * vz + Vm[14] * vw;
+    float pwx, pwy, pwz;
+    world_div3<false>(wx, wy, wz, ww, pwx, pwy, pwz);
+    const float ddx = rc.cam_pos_world[0] - pwx, ddy = rc.cam_pos_world[1] - pwy, ddz = rc.cam_pos_world[2] - pwz;
+    const float linear_depth = prologue_sqrt<false>(ddx * ddx + ddy * ddy + ddz * ddz);
+    const float vvx = vx - 0.0f, vvy = vy - 0.0f, vvz = vz - 0.0f;
+    const float inv_len = ieee_div(1.0f, prologue_sqrt<false>(vvx * vvx + vvy * vvy + vvz * vvz));
+    fc.rays[2 * i] = make_float4(0.0f, 0.0f, 0.0f, linear_depth);
+    fc.rays[2 * i + 1] = make_float4(vvx * inv_len, vvy * inv_len, vvz * inv_len, 0.0f);
+}
+// ONE: a family with one kernel; TWIN: the direct-light family, 8 light steps unrolled or rc.light_steps at run time
+#define ATMO_RAYS_FAMILIES(ONE, TWIN)                \
+    ONE(0)                                           \
+    TWIN(KF_LIGHT_DIRECT)                            \
+    ONE(KF_PRECISE | KF_CLOUDS)                      \
+    ONE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)  \
+    ONE(KF_PRECISE | KF_LITE)                        \
+    ONE(KF_PRECISE | KF_LITE | KF_CLOUDS)
+bool rays_family_supported(int flags) {
+    switch (flags) {
+#define ATMO_RAYS_LISTED(F) case (F):
+        ATMO_RAYS_FAMILIES(ATMO_RAYS_LISTED, ATMO_RAYS_LISTED)
+#undef ATMO_RAYS_LISTED
+        return true;
+    default: return false;
+    }
+}
+template <class Kernel>
+static hipError_t launch_rays(Kernel kernel, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream) {
+    const unsigned blocks = (unsigned)(((uint64_t)yc.n + (RAYS_BLOCK - 1)) / RAYS_BLOCK);   // at most 2^24
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RAYS_BLOCK), 0, stream, rc, yc);
+    return hipGetLastError();
+}
+hipError_t launch_shade_rays(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream) {
+    if (yc.rays == nullptr || yc.out == nullptr || yc.n == 0 || yc.width == 0 || yc.first > 0xffffffffu - (yc.n - 1u)) return hipErrorInvalidValue;
+    switch (flags) {
+#define ATMO_RAYS_LAUNCH(F) case (F): return launch_rays(atmo_shade_rays_kernel<(F) | KF_RAYS, 0>, rc, yc, stream);
+#define ATMO_RAYS_LAUNCH_TWIN(F) case (F): return rc.light_steps == 8 ? launch_rays(atmo_shade_rays_kernel<(F) | KF_RAYS, 8>, rc, yc, stream) \
+                                                                      : launch_rays(atmo_shade_rays_kernel<(F) | KF_RAYS, 0>, rc, yc, stream);
+        ATMO_RAYS_FAMILIES(ATMO_RAYS_LAUNCH, ATMO_RAYS_LAUNCH_TWIN)
+#undef ATMO_RAYS_LAUNCH
+#undef ATMO_RAYS_LAUNCH_TWIN
+    default: return hipErrorInvalidValue;
+    }
+}
+#undef ATMO_RAYS_FAMILIES
+hipError_t launch_frame_rays(const RenderConsts &rc, const FrameRaysConsts &fc, hipStream_t stream) {
+    if (fc.depth == nullptr || fc.rays == nullptr || rc.x1 <= rc.x0 || rc.y1 <= rc.y0) return hipErrorInvalidValue;
+    const size_t n = (size_t)(rc.x1 - rc.x0) * (size_t)(rc.y1 - rc.y0);
+    hipLaunchKernelGGL(atmo_frame_rays_kernel, dim3((unsigned)((n + RAYS_BLOCK - 1) / RAYS_BLOCK)), dim3(RAYS_BLOCK), 0, stream, rc, fc);
+    return hipGetLastError();
+}
 
 }  // namespace atmo

@@ -27,6 +27,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import operator
 import time as _time
 import warnings
 
@@ -672,6 +673,56 @@ class PlanetAtmosphere:
         N.check(self._ctx, fn(self._ctx, C.byref(nf), *box, depth_arg, *where, C.c_void_p(stream or 0)))
         return colour
 
+    # ---- caller-supplied rays (include/atmo_rays.h) --------------------------------------------------------------------------------
+    def _rays_entry(self, name: str):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_rays.h); rebuild it")
+        return fn
+
+    def shade_rays(self, rays, camera=None, *, width=None, first: int = 0, out=None, stream=None, time: float = 0.0):
+        """Shades caller-supplied rays: what atmosphere_fragment returns for a fragment with each ray (atmo_shade_rays; include/atmo_rays.h states the
+        arithmetic).  `rays`: a contiguous CUDA float32 tensor of shape (n, 8), one N.AtmoRay a row -- origin xyz, tmax (the distance to the first
+        opaque hit, FLT_MAX for none), dir xyz (unit length, used as given), one unused float.  `camera` supplies inv_view, the map from ray space
+        to world space; None: ray space is world space.  Ray i is image index first + i of an image `width` wide (default: n), which picks its
+        blue-noise jitter.  Returns or fills `out`, a contiguous CUDA float32 (n, 4) tensor: ALBEDO.rgb and ALPHA per ray, zeros for a ray that misses
+        the atmosphere.  The coverage cubemap is sampled at level 0."""
+        n = _check_rays(rays, "rays", 8)
+        try:
+            width, first = max(n, 1) if width is None else operator.index(width), operator.index(first)
+        except TypeError:
+            raise TypeError("width and first must be integers") from None
+        if width < 1 or first < 0 or first + n > 1 << 32:
+            raise ValueError("width must be at least 1, first at least 0 and first + n at most 2^32")
+        if out is None:
+            import torch
+
+            out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        elif _check_rays(out, "out", 4) != n:
+            raise ValueError("out must have one row per ray: shape (n, 4)")
+        fn = self._rays_entry("atmo_shade_rays")
+        stream = _stream_handle(stream, rays)
+        self._bake_if_needed(stream)
+        nf = _to_native_frame(self.make_frame(camera if camera is not None else _WORLD_RAY_SPACE, time))
+        N.check(self._ctx, fn(self._ctx, C.byref(nf), C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr()), n, width, first, C.c_void_p(stream or 0)))
+        return out
+
+    def camera_rays(self, camera, depth, rect=None, stream=None):
+        """The rays the library's own prologue forms for `rect` (default: the whole viewport) of the camera's viewport, row-major: a CUDA float32
+        (rect_h * rect_w, 8) tensor for `shade_rays` -- origin 0, the normalised view direction, tmax = the linear depth of the depth sample
+        (atmo_debug_frame_rays).  `depth` as `render`'s float tensor."""
+        import torch
+
+        _check_depth(depth, camera, split=True)
+        frame = self.make_frame(camera, 0.0, rect)
+        x0, y0, x1, y1 = frame["rect"]
+        rays = torch.empty(((y1 - y0) * (x1 - x0), 8), dtype=torch.float32, device=depth.device)
+        fn = self._rays_entry("atmo_debug_frame_rays")
+        stream = _stream_handle(stream, depth)
+        nf = _to_native_frame(frame)
+        N.check(self._ctx, fn(self._ctx, C.byref(nf), C.c_void_p(depth.data_ptr()), C.c_void_p(rays.data_ptr()), C.c_void_p(stream or 0)))
+        return rays
+
     def prepare_frame(self, camera, time: float = 0.0, rect=None) -> N.AtmoFrame:
         """The native per-frame argument block for `render_prepared` (build once per camera pose)."""
         return _to_native_frame(self.make_frame(camera, time, rect))
@@ -954,6 +1005,26 @@ def _new_target(rows: int, cols: int, target, device, zero: bool):
     np_dtype = T.DTYPES[T.format_id(target) if target is not None else T.RGBA32F]
     dtype = {np.float32: torch.float32, np.float16: torch.float16, np.uint8: torch.uint8}[np_dtype]
     return (torch.zeros if zero else torch.empty)((rows, cols, 4), dtype=dtype, device=device)
+
+
+class _WorldRaySpace:
+    """The camera of `shade_rays(camera=None)`: ray space is world space.  atmo_shade_rays reads the view matrices only."""
+    width = height = 1
+    view = inv_view = inv_projection = np.eye(4)
+
+
+_WORLD_RAY_SPACE = _WorldRaySpace()
+
+
+def _check_rays(t, what: str, cols: int) -> int:
+    """`what` is a contiguous CUDA float32 tensor of shape (n, cols): TypeError for its kind, ValueError for its shape.  Returns n."""
+    import torch
+
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise TypeError(f"{what} must be a contiguous CUDA float32 tensor")
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError(f"{what} must have shape (n, {cols})")
+    return int(t.shape[0])
 
 
 def _stream_handle(stream, tensor) -> int:

@@ -1,0 +1,116 @@
+"""What shading caller-supplied rays costs (include/atmo_rays.h) on the MI355X, per kernel family: atmo_shade_rays on the camera rays of the 1920 x 1080
+P_space frame against the like-for-like draw, and the same rays once more in a fixed random order.
+
+    python tools/rays_probe.py [--out profiles/rays/rays_probe.json] [--reps 20] [--rounds 3]
+
+ONE process, one context per family; three arms timed INTERLEAVED, every round in the order render, rays, shuffled, render2:
+  render    atmo_render of the frame with atmo_set_sampler_lod 0 and atmo_set_tile_feedback 0 -- row-major, level 0: the draw the ray kernels are held to
+            bit for bit (tests/test_rays_gpu.py), so what differs is the lane mapping (64 consecutive rays of a row against a 16 x 4 pixel block), 32 more
+            bytes read per ray, and the planet centre (and the clouds' origin) in VGPRs instead of SGPRs;
+  rays      atmo_shade_rays on camera_rays(frame), width = 1920;
+  shuffled  the same rays in a fixed random permutation (seed 1), width = n: what a bounce-ray queue looks like -- the rays of a wave no longer march in step;
+  render2   render again: render2 / render is the run-to-run spread of an arm against itself.
+Device events around `reps` calls through the binding (one event pair around the K launches), after priming as bench.py does: warm-up calls of every arm,
+then ~25 ms of draws so that the clocks are the sustained ones.  Reported per arm: the median, minimum and maximum of the rounds (ms per call), the ratios
+of the medians, and the kernel each arm reported.  Prints one JSON object.  Needs a device: there is no CPU figure."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from godot_atmosphere_shader_amd import scene as S  # noqa: E402
+from godot_atmosphere_shader_amd.demo import demo_textures, make_node  # noqa: E402
+
+# label -> (demo configuration, PlanetAtmosphere keywords)
+FAMILIES = {
+    "lut": ("no_clouds_32_lut", {}),
+    "direct8": ("no_clouds_32x8_direct", {}),
+    "direct5": ("no_clouds_8", dict(view_steps=32, light_mode="direct", light_steps=5)),
+    "clouds_high": ("clouds_high", {}),
+    "clouds_high_rm": ("clouds_high_rm", {}),
+    "v1_no_clouds": ("v1_no_clouds", {}),
+    "v1_clouds": ("v1_clouds", {}),
+}
+W, H = 1920, 1080
+ARMS = ("render", "rays", "shuffled", "render2")
+
+
+def timed(call, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        call()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--families", default=",".join(FAMILIES))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("rays_probe.py measures on a device; none is visible")
+    tex = demo_textures()
+    cam = S.Camera.from_pose(W, H, "P_space")
+    depth = torch.from_numpy(S.depth_ground_sphere(cam)).cuda()
+    frame = torch.empty((H, W, 4), dtype=torch.float32, device="cuda")
+    out = torch.empty((H * W, 4), dtype=torch.float32, device="cuda")
+    perm = torch.randperm(H * W, generator=torch.Generator().manual_seed(1)).cuda()
+    result = {"viewport": [W, H], "pose": "P_space", "reps": args.reps, "rounds": args.rounds, "device": torch.cuda.get_device_name(0), "rows": []}
+    for label in args.families.split(","):
+        config, kw = FAMILIES[label]
+        node = make_node(config, tex, cubemap_lod=False, tile_feedback=0, **kw)   # atmo_set_sampler_lod 0, atmo_set_tile_feedback 0
+        try:
+            rays = node.camera_rays(cam, depth)
+            shuffled = rays[perm].contiguous()
+            calls = {"render": lambda: node.render(cam, depth, out=frame), "rays": lambda: node.shade_rays(rays, cam, width=W, out=out),
+                     "shuffled": lambda: node.shade_rays(shuffled, cam, out=out)}
+            calls["render2"] = calls["render"]
+            names = {}
+            for arm in ("render", "rays", "shuffled"):
+                timed(calls[arm], args.warmup)
+                names[arm] = node.kernel_name
+            # the picture is the same in all three arms: checked once, outside the timing
+            node.render(cam, depth, out=frame)
+            node.shade_rays(rays, cam, width=W, out=out)
+            same = bool(torch.equal(frame.reshape(-1, 4).view(torch.int32), out.view(torch.int32)))
+            t_warm = time.perf_counter()
+            while time.perf_counter() - t_warm < 0.025:   # sustained clocks
+                calls["render"]()
+                torch.cuda.synchronize()
+            arms = {a: [] for a in ARMS}
+            for _ in range(args.rounds):
+                for arm in ARMS:
+                    arms[arm].append(timed(calls[arm], args.reps))
+        finally:
+            node.close()
+        med = {a: sorted(v)[len(v) // 2] for a, v in arms.items()}
+        row = {"family": label, "kernels": names, "bits_equal_render": same,
+               "ms": {a: {"median": med[a], "min": min(v), "max": max(v)} for a, v in arms.items()},
+               "rays_over_render": med["rays"] / med["render"], "shuffled_over_rays": med["shuffled"] / med["rays"],
+               "render2_over_render": med["render2"] / med["render"]}
+        result["rows"].append(row)
+        print(f"{label:15s} render {med['render']:.4f} ms  rays {med['rays']:.4f} ms ({row['rays_over_render']:.3f} x)  shuffled {med['shuffled']:.4f} ms "
+              f"({row['shuffled_over_rays']:.3f} x rays)  render again {med['render2']:.4f} ms ({row['render2_over_render']:.3f} x)  bits equal: {same}  "
+              f"{names['render']} / {names['rays']}", file=sys.stderr, flush=True)
+    text = json.dumps(result)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
