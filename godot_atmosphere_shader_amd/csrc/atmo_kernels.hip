@@ -2188,12 +2188,20 @@ __device__ __forceinline__ void store_target_zero_all_rt(const int format, void 
     else store_target_zero_rt(format, p);
 }
 
+// RAYS (KF_RAYS, atmo_shade_rays_kernel; include/atmo_rays.h): the same shading for a ray that did not come out of a camera matrix.  The mode differs at the
+// function's edges only -- how a ray arrives (thread i of the batch reads ray i of *yc: no pixel, no sure-miss test, no prologue) and where its result goes
+// (yc->out[i], a plain store; zeros for a miss) -- and in the operands the ray's own origin gives the marches (their LANE forms).  Everything between is the
+// one text below.  Each site reads `if constexpr (RAYS) <the ray's form>; else <the pixel kernels' statement as it stands>`: an argument added to a pixel
+// kernel's statement, or a helper shared by both sides, moves the older kernels' code (NOTES.md "Caller-supplied rays"; tools/isa_diff.py is the check).
+constexpr int RAYS_BLOCK = 256;   // rays (threads) per workgroup of the ray kernels: 64 consecutive rays per wave
 template <int FLAGS, int LSTEPS, int SPLIT>
 __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int tile_x, const int tile_y, const ProxyConsts *pc = nullptr,
-                                            const TargetConsts *tc = nullptr, const DepthConsts *dc = nullptr, const DetailConsts *xc = nullptr) {
+                                            const TargetConsts *tc = nullptr, const DepthConsts *dc = nullptr, const DetailConsts *xc = nullptr,
+                                            const RayConsts *yc = nullptr) {
     constexpr bool DETAIL = (FLAGS & KF_DETAIL) != 0;   // the cloud march with CLOUDS_ALWAYS_LOW_QUALITY off, through *xc
     static_assert(!DETAIL || ((FLAGS & ~(KF_DETAIL | KF_CUBE_LOD | KF_CLOUD_LIGHT_RM | KF_LITE)) == (KF_PRECISE | KF_CLOUDS) && SPLIT == 1),
                   "cloud detail: the LUT-light precise cloud families, float output, one lane per ray");
+    constexpr bool RAYS = (FLAGS & KF_RAYS) != 0;   // a ray of the caller's per lane, through *yc
     constexpr bool CLOUDS = (FLAGS & KF_CLOUDS) != 0;
     constexpr bool RM = (FLAGS & KF_CLOUD_LIGHT_RM) != 0;
     constexpr bool DIRECT = (FLAGS & KF_LIGHT_DIRECT) != 0;
@@ -2212,15 +2220,21 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     static_assert(!PROXY || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0), "proxy draws: the default forms, one lane per ray, row-major");
     static_assert((FLAGS & KF_VIEWS) == 0 || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0),
                   "multi-view draws: the default forms, one lane per ray, float or packed targets (KF_VIEWS | KF_TARGET: atmo_render_views_target_kernel)");
+    static_assert(!RAYS || ((FLAGS & ~(KF_RAYS | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT | KF_LITE | KF_PRECISE)) == 0 && SPLIT == 1),
+                  "ray kernels: the default forms under the level-0 sampler, one lane per ray");
+    static_assert(!RAYS || (!(DIRECT && CLOUDS) && (PRECISE == (CLOUDS || LITE)) && !(RM && LITE)),
+                  "ray kernels: the LUT-light cloud forms in precise mode, no cloud + direct light");
     // the short exact prologue: every kernel but cloud + direct-light and raymarched cloud light (prologue_sqrt)
     constexpr bool DIET = (!DIRECT || !CLOUDS) && !((FLAGS & KF_CLOUDS) && (FLAGS & KF_CLOUD_LIGHT_RM));
-    // the camera prologue (ATMO_PROLOGUE_CAMERA_FORMS): the cloudless direct-light kernels
-    constexpr int CAMF = (DIRECT && !CLOUDS) ? ATMO_PROLOGUE_CAMERA_FORMS : 0;
-    constexpr bool FASTMISS = (ATMO_FAST_MISS_MASK >> ((DIRECT ? 1 : 0) + (CLOUDS ? 2 : 0) + (LITE ? 4 : 0))) & 1;
+    // the camera prologue (ATMO_PROLOGUE_CAMERA_FORMS): the cloudless direct-light kernels; of its forms a ray takes the two that need no camera (2 | 8: the
+    // power-of-two step length and the handed-over products)
+    constexpr int CAMF = (DIRECT && !CLOUDS) ? (RAYS ? ATMO_PROLOGUE_CAMERA_FORMS & 10 : ATMO_PROLOGUE_CAMERA_FORMS) : 0;
+    constexpr bool FASTMISS = !RAYS && ((ATMO_FAST_MISS_MASK >> ((DIRECT ? 1 : 0) + (CLOUDS ? 2 : 0) + (LITE ? 4 : 0))) & 1);   // it needs a projection
     static_assert(!LOD || (CLOUDS && PRECISE), "implicit cubemap LOD: precise cloud kernels");
     static_assert(!(LOD && SPLIT == 2) || (!ATMO_REF && !VIEWPOS && !LITE && !DIRECT), "two lanes per ray under the declared sampler: the two BASELINE cloud kernels");
     static_assert(!LOD || (WAVE_W == 16 && WAVE_H == 4), "the quad-major lane order of the LOD kernels is written for 16 x 4 pixel waves");
 
+    constexpr int BLOCK_WAVES = (RAYS ? RAYS_BLOCK : TILE_W * TILE_H) / 64;   // waves per workgroup: 2 for a tile, 4 for a block of rays
     const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     const f32x4 *lvl_table = nullptr;
     if constexpr (LOD) {  // the declared sampler's per-level constants (cube_level_table_fill), written by every wave before any lane leaves
@@ -2251,7 +2265,12 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     const int py = (LOD ? rc.gy0 : rc.y0) + tile_y * (TILE_H / SPLIT) + ly;
     QuadRegs qregs;
     if constexpr (LOD) quad_regs_define(qregs);  // all 64 lanes are still here: nothing else may ever live in these registers
-    if (LOD ? (px >= rc.w || py >= rc.h) : (px >= rc.x1 || py >= rc.y1)) return;
+    // RAYS: the work item is ray i of the batch, thread i of the launch (grid = ceil(n / 256) blocks and n < 2^32: no wrap).  The lane-to-pixel lines above
+    // are the pixel kernels': under RAYS (tile 0, 0; one lane per ray; level-0 sampler) they leave half = 0 and helper = false, and nothing reads px / py
+    const uint32_t i = RAYS ? blockIdx.x * (uint32_t)RAYS_BLOCK + threadIdx.x : 0u;
+    if constexpr (RAYS) {
+        if (i >= yc->n) return;
+    } else if (LOD ? (px >= rc.w || py >= rc.h) : (px >= rc.x1 || py >= rc.y1)) return;
     bool helper = LOD && (px < rc.x0 || py < rc.y0 || px >= rc.x1 || py >= rc.y1);
     if constexpr (PROXY) {
         // The far-mode draw: only the box's passing fragments are shaded and stored.  In front of every store of this function (the sure-miss and the
@@ -2269,7 +2288,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     }
     float4 *out = nullptr;
     char *tout = nullptr;   // KF_TARGET: the pixel's bytes in the packed target (8 per pixel RGBA16F, 4 RGBA8), rows pitch_bytes apart
-    if constexpr (DEPTH)
+    if constexpr (RAYS)
+        out = yc->out + i;
+    else if constexpr (DEPTH)
         tout = (char *)tc->pixels + (size_t)(py - rc.out_y0) * (size_t)tc->pitch_bytes + ((size_t)(px - rc.out_x0) << target_pixel_shift_all(tc->format));
     else if constexpr (TARGET)
         tout = (char *)tc->pixels + (size_t)(py - rc.out_y0) * (size_t)tc->pitch_bytes + ((size_t)(px - rc.out_x0) << (tc->format == TF_RGBA16F ? 3 : 2));
@@ -2304,56 +2325,71 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
         }
     }
 
-    // --- exact prologue (main:128-169) -----------------------------------------------------------
-    float nonlinear_depth;
-    if constexpr (DEPTH) nonlinear_depth = load_depth(*dc, px, py);
-    else nonlinear_depth = rc.depth[(size_t)py * rc.w + px];
-    const float uvx = pixel_coord<DIET>((float)px + 0.5f, rc.vw, rc.rcp_vw);
-    const float uvy = pixel_coord<DIET>((float)py + 0.5f, rc.vh, rc.rcp_vh);
-    const float nx = uvx * 2.0f - 1.0f, ny = uvy * 2.0f - 1.0f, nz = nonlinear_depth;
-    const float *P = rc.inv_p;
-    const float *Vm = rc.inv_v;
+    // --- the ray: dir, the distance limit linear_depth, and the planet centre relative to the ray's origin ----------------------------------------
+    // RAYS: they are an AtmoRay's -- origin and tmax, direction -- and the centre is the lane's own c' = RN(c - origin): everything the reference does with
+    // in_v_planet_center_viewspace and ray_origin = 0 is done with c' and origin 0.  Else the exact prologue (main:128-169) forms them from the pixel
+    // (what outlives the prologue is declared here in the order the prologue always declared it, its view-space position in front of `cam` included: the
+    // order of declaration is the order of the compiler's merges, which atmo_render_views_target_kernel<3076, 8>'s register allocation follows)
+    float uvx, uvy;   // the pixel's, for its jitter texel
     float vx, vy, vz, vw, ww;
-    // PM_CAMERA (the host's prologue_camera_fill has the proof): the rows without their zero terms, for a wave whose lanes all have a finite, nonzero vw --
-    // a NaN or inf depth sample (0 nz is a NaN in the general rows) or vw = +-0 (the dropped zeros decide the sign of ww) sends the whole wave below
-    bool cam = false;   // wave-uniform
-    if constexpr ((CAMF & 5) != 0) {
-        if (rc.prologue_mode & PM_CAMERA) {
-            const float vws = P[11] * nz + P[15];
-            // v_cmp_class: -normal, -subnormal, +subnormal, +normal
-            // ... and the lanes of the column / row with nx = 0 / ny = 0 where a -0 constant term makes the sign of that zero the lane's (cam_skip_*)
-            cam = __builtin_amdgcn_ballot_w64(!__builtin_amdgcn_classf(vws, 0x198) || px == rc.cam_skip_px || py == rc.cam_skip_py) == 0ull;
-            if constexpr ((CAMF & 1) != 0) {
-                if (cam) {
-                    vx = P[0] * nx + P[12];
-                    vy = P[5] * ny + P[13];
-                    vz = P[14];
-                    vw = vws;
-                    ww = vws;
+    bool cam = false;   // wave-uniform: the PM_CAMERA rows were taken (never under RAYS)
+    float linear_depth;
+    V3 dir, center, origin;   // origin: RAYS only (the pixel kernels' is 0)
+    if constexpr (RAYS) {
+        const float4 ray_ot = yc->rays[2 * (size_t)i], ray_d = yc->rays[2 * (size_t)i + 1];   // one dwordx4 load each
+        origin = {ray_ot.x, ray_ot.y, ray_ot.z};
+        linear_depth = ray_ot.w;
+        dir = {ray_d.x, ray_d.y, ray_d.z};
+        center = {rc.center[0] - origin.x, rc.center[1] - origin.y, rc.center[2] - origin.z};
+    } else {
+        float nonlinear_depth;
+        if constexpr (DEPTH) nonlinear_depth = load_depth(*dc, px, py);
+        else nonlinear_depth = rc.depth[(size_t)py * rc.w + px];
+        uvx = pixel_coord<DIET>((float)px + 0.5f, rc.vw, rc.rcp_vw);
+        uvy = pixel_coord<DIET>((float)py + 0.5f, rc.vh, rc.rcp_vh);
+        const float nx = uvx * 2.0f - 1.0f, ny = uvy * 2.0f - 1.0f, nz = nonlinear_depth;
+        const float *P = rc.inv_p;
+        const float *Vm = rc.inv_v;
+        // PM_CAMERA (the host's prologue_camera_fill has the proof): the rows without their zero terms, for a wave whose lanes all have a finite, nonzero vw --
+        // a NaN or inf depth sample (0 nz is a NaN in the general rows) or vw = +-0 (the dropped zeros decide the sign of ww) sends the whole wave below
+        if constexpr ((CAMF & 5) != 0) {
+            if (rc.prologue_mode & PM_CAMERA) {
+                const float vws = P[11] * nz + P[15];
+                // v_cmp_class: -normal, -subnormal, +subnormal, +normal
+                // ... and the lanes of the column / row with nx = 0 / ny = 0 where a -0 constant term makes the sign of that zero the lane's (cam_skip_*)
+                cam = __builtin_amdgcn_ballot_w64(!__builtin_amdgcn_classf(vws, 0x198) || px == rc.cam_skip_px || py == rc.cam_skip_py) == 0ull;
+                if constexpr ((CAMF & 1) != 0) {
+                    if (cam) {
+                        vx = P[0] * nx + P[12];
+                        vy = P[5] * ny + P[13];
+                        vz = P[14];
+                        vw = vws;
+                        ww = vws;
+                    }
                 }
             }
         }
-    }
-    if ((CAMF & 1) == 0 || !cam) {
-        vx = P[0] * nx + P[4] * ny + P[8] * nz + P[12] * 1.0f;
-        vy = P[1] * nx + P[5] * ny + P[9] * nz + P[13] * 1.0f;
-        vz = P[2] * nx + P[6] * ny + P[10] * nz + P[14] * 1.0f;
-        vw = P[3] * nx + P[7] * ny + P[11] * nz + P[15] * 1.0f;
-        ww = Vm[3] * vx + Vm[7] * vy + Vm[11] * vz + Vm[15] * vw;
-    }
-    const float wx = Vm[0] * vx + Vm[4] * vy + Vm[8] * vz + Vm[12] * vw;
-    const float wy = Vm[1] * vx + Vm[5] * vy + Vm[9] * vz + Vm[13] * vw;
-    const float wz = Vm[2] * vx + Vm[6] * vy + Vm[10] * vz + Vm[14] * vw;
-    float pwx, pwy, pwz;
-    world_div3<DIET>(wx, wy, wz, ww, pwx, pwy, pwz);
-    const float ddx = rc.cam_pos_world[0] - pwx, ddy = rc.cam_pos_world[1] - pwy, ddz = rc.cam_pos_world[2] - pwz;
-    float linear_depth = prologue_sqrt<DIET>(ddx * ddx + ddy * ddy + ddz * ddz);
+        if ((CAMF & 1) == 0 || !cam) {
+            vx = P[0] * nx + P[4] * ny + P[8] * nz + P[12] * 1.0f;
+            vy = P[1] * nx + P[5] * ny + P[9] * nz + P[13] * 1.0f;
+            vz = P[2] * nx + P[6] * ny + P[10] * nz + P[14] * 1.0f;
+            vw = P[3] * nx + P[7] * ny + P[11] * nz + P[15] * 1.0f;
+            ww = Vm[3] * vx + Vm[7] * vy + Vm[11] * vz + Vm[15] * vw;
+        }
+        const float wx = Vm[0] * vx + Vm[4] * vy + Vm[8] * vz + Vm[12] * vw;
+        const float wy = Vm[1] * vx + Vm[5] * vy + Vm[9] * vz + Vm[13] * vw;
+        const float wz = Vm[2] * vx + Vm[6] * vy + Vm[10] * vz + Vm[14] * vw;
+        float pwx, pwy, pwz;
+        world_div3<DIET>(wx, wy, wz, ww, pwx, pwy, pwz);
+        const float ddx = rc.cam_pos_world[0] - pwx, ddy = rc.cam_pos_world[1] - pwy, ddz = rc.cam_pos_world[2] - pwz;
+        linear_depth = prologue_sqrt<DIET>(ddx * ddx + ddy * ddy + ddz * ddz);
 
-    // ray_dir = normalize(view_coords.xyz - 0) = v * (1/sqrt(dot(v,v)))
-    const float vvx = vx - 0.0f, vvy = vy - 0.0f, vvz = vz - 0.0f;
-    const float inv_len = ieee_div(1.0f, prologue_sqrt<DIET>(vvx * vvx + vvy * vvy + vvz * vvz));
-    const V3 dir = {vvx * inv_len, vvy * inv_len, vvz * inv_len};
-    const V3 center = {rc.center[0], rc.center[1], rc.center[2]};
+        // ray_dir = normalize(view_coords.xyz - 0) = v * (1/sqrt(dot(v,v)))
+        const float vvx = vx - 0.0f, vvy = vy - 0.0f, vvz = vz - 0.0f;
+        const float inv_len = ieee_div(1.0f, prologue_sqrt<DIET>(vvx * vvx + vvy * vvy + vvz * vvz));
+        dir = {vvx * inv_len, vvy * inv_len, vvz * inv_len};
+        center = {rc.center[0], rc.center[1], rc.center[2]};
+    }
 
     const SphereHit sh = sphere_setup(center, dir);
     float2 rs_atmo;
@@ -2361,7 +2397,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     else rs_atmo = hit_radius<DIET>(sh, rc.atmosphere_radius);
 
     if (rs_atmo.x == rs_atmo.y) {  // discard: nothing reaches the blend stage
-        if (rc.store_discards && half == 0 && !helper) {
+        if constexpr (RAYS) {   // a ray that misses the shell always receives zeros
+            *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        } else if (rc.store_discards && half == 0 && !helper) {
             if constexpr (DEPTH) store_target_zero_all_rt(tc->format, tout);
             else if constexpr (TARGET) store_target_zero_rt(tc->format, tout);
             else *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -2381,13 +2419,22 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     }
     t_end = fminf(t_end, linear_depth);
 
-    const float jx = rc.vw * uvx, jy = rc.vh * uvy;
-    const int ji = ((int)jx) & 0xff, jj = ((int)jy) & 0xff;
-    const float jitter = blue_noise_value<DIET>(rc.blue[jj * 256 + ji]);
+    // the jitter texel (x & 255, y & 255) of the pixel; RAYS: of image index k = first + i, x = k % width, y = k / width -- what atmo_render reads for pixel (x, y)
+    float jitter;
+    if constexpr (RAYS) {
+        const uint32_t k = yc->first + i;
+        const uint32_t ky = k / yc->width, kx = k - ky * yc->width;
+        jitter = blue_noise_value<DIET>(rc.blue[(ky & 0xffu) * 256u + (kx & 0xffu)]);
+    } else {
+        const float jx = rc.vw * uvx, jy = rc.vh * uvy;
+        const int ji = ((int)jx) & 0xff, jj = ((int)jy) & 0xff;
+        jitter = blue_noise_value<DIET>(rc.blue[jj * 256 + ji]);
+    }
 
     float4 rgba;
     if (LITE) {
-        if constexpr (PRECISE) rgba = march_atmosphere_v1_precise(rc, dir, t_begin, t_end);
+        if constexpr (RAYS) rgba = march_atmosphere_v1_precise<true>(rc, dir, t_begin, t_end, center);
+        else if constexpr (PRECISE) rgba = march_atmosphere_v1_precise(rc, dir, t_begin, t_end);
         else rgba = march_atmosphere_v1<ASPLIT>(rc, dir, t_begin, t_end, ahalf);  // main:172-175
     } else {
         if constexpr (ATMO_REF && SPLIT == 1) {
@@ -2397,7 +2444,8 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
             // PM_POW2_STEPS: the quotient by 2^k and the product with 2^-k round the same real number
             if ((CAMF & 2) != 0 && (rc.prologue_mode & PM_POW2_STEPS)) view_step_len = (t_end - t_begin) * rc.inv_view_steps;
             else view_step_len = ieee_div(t_end - t_begin, (CAMF & 8) != 0 ? rc.view_steps_f : (float)rc.view_steps);
-            rgba = march_atmosphere<DIRECT, LSTEPS, ASPLIT, VIEWPOS, (CAMF & 8) != 0>(rc, dir, t_begin, view_step_len, jitter, ahalf);
+            if constexpr (RAYS) rgba = march_atmosphere<DIRECT, LSTEPS, 1, false, (CAMF & 8) != 0, true>(rc, dir, t_begin, view_step_len, jitter, 0, center);
+            else rgba = march_atmosphere<DIRECT, LSTEPS, ASPLIT, VIEWPOS, (CAMF & 8) != 0>(rc, dir, t_begin, view_step_len, jitter, ahalf);
         }
     }
 
@@ -2414,14 +2462,28 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                 dir_m.x = M[0] * dir.x + M[4] * dir.y + M[8] * dir.z;
                 dir_m.y = M[1] * dir.x + M[5] * dir.y + M[9] * dir.z;
                 dir_m.z = M[2] * dir.x + M[6] * dir.y + M[10] * dir.z;
+                LaneOrigin lo;   // RAYS: what the ray's origin gives the cloud march in place of rc.origin_model and rc.max_d
+                if constexpr (RAYS) {
+                    // (view_to_model * (origin, 1)).xyz, the four products summed left to right (clouds:286): fill_consts' origin_model for origin = 0
+                    lo.origin_model.x = M[0] * origin.x + M[4] * origin.y + M[8] * origin.z + M[12] * 1.0f;
+                    lo.origin_model.y = M[1] * origin.x + M[5] * origin.y + M[9] * origin.z + M[13] * 1.0f;
+                    lo.origin_model.z = M[2] * origin.x + M[6] * origin.y + M[10] * origin.z + M[14] * 1.0f;
+                    // max_d = mix(ground, space, smoothstep(bottom, top * 1.05, length(ray_origin))) (clouds:186-202): fill_consts' max_d, operation for operation
+                    const V3 om = lo.origin_model;
+                    const float len = ieee_sqrt(om.x * om.x + om.y * om.y + om.z * om.z);
+                    const float st = clampf(ieee_div(len - yc->md_e0, yc->md_e1 - yc->md_e0), 0.0f, 1.0f);
+                    lo.max_d = mixf(yc->md_ground, yc->md_space, st * st * (3.0f - 2.0f * st));
+                }
                 float2 rr;
                 if constexpr (DETAIL) {   // light in place under both samplers (march_clouds)
                     rr = march_clouds<RM, PRECISE, 1, LOD, true>(rc, dir_m, c0, c1, jitter, 0, &qregs, lvl_table, xc);
-                } else if constexpr (RM && SPLIT == 1 && !LOD) {
-                    __shared__ float rmq[(TILE_W * TILE_H / 64) * RMQ_WORDS_PER_WAVE];
-                    rr = march_clouds_rm_queue<PRECISE>(rc, dir_m, c0, c1, jitter, rmq + wave * RMQ_WORDS_PER_WAVE);
+                } else if constexpr (RM && SPLIT == 1 && !LOD) {   // the lit-sample queue: wave-private
+                    __shared__ float rmq[BLOCK_WAVES * RMQ_WORDS_PER_WAVE];
+                    if constexpr (RAYS) rr = march_clouds_rm_queue<PRECISE, true>(rc, dir_m, c0, c1, jitter, rmq + wave * RMQ_WORDS_PER_WAVE, &lo);
+                    else rr = march_clouds_rm_queue<PRECISE>(rc, dir_m, c0, c1, jitter, rmq + wave * RMQ_WORDS_PER_WAVE);
                 } else {
-                    rr = march_clouds<RM, PRECISE, SPLIT, LOD>(rc, dir_m, c0, c1, jitter, half, &qregs, lvl_table);
+                    if constexpr (RAYS) rr = march_clouds<RM, PRECISE, 1, false, false, true>(rc, dir_m, c0, c1, jitter, 0, nullptr, nullptr, nullptr, &lo);
+                    else rr = march_clouds<RM, PRECISE, SPLIT, LOD>(rc, dir_m, c0, c1, jitter, half, &qregs, lvl_table);
                 }
                 {
 #pragma clang fp contract(fast)
@@ -2447,6 +2509,10 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                 }
             }
         }
+    }
+    if constexpr (RAYS) {   // a ray's result as it is: no composite, no packed target
+        *out = rgba;
+        return;
     }
     if constexpr (TARGET) {
         // the same fp32 ALBEDO / ALPHA, encoded (and blended) per the target's format; not by the second lane of a split ray nor by a helper, as below.
@@ -3788,133 +3854,18 @@ hipError_t launch_render_detail(int flags, const RenderConsts &rc, const DetailC
 #undef ATMO_DETAIL_FAMILIES
 
 // ---- caller-supplied rays (KF_RAYS; include/atmo_rays.h states the arithmetic item by item) ---------------------------------------------------------
-// shade_pixel behind its prologue, for a ray that did not come out of a camera matrix: origin, direction and distance limit are an AtmoRay's, the planet
-// centre relative to the origin is the lane's own c' = RN(c - origin), and everything the reference does with in_v_planet_center_viewspace and
-// ray_origin = 0 is done with c' and origin 0 -- the marches take c' (and the clouds the model-space origin and its march-distance cap) through their LANE
-// forms.  Every expression below is shade_pixel's, under the same contraction mode, with the short exact forms (DIET) and the handed-over products (CAMF & 8,
-// & 2) its twin family takes: where the rays are a camera's (atmo_debug_frame_rays) the picture is atmo_render's under the level-0 sampler, bit for bit
-// (tests/test_rays_gpu.py).  What is NOT here: the sure-miss test and the camera rows (they need a projection), the declared sampler (a ray has no 2 x 2
-// quad to difference), tile order and cost recording (the launch is row-major over the batch), composite and packed stores.
-// Lane mapping: ray i of the batch is thread i -- 64 consecutive rays per wave, 256 per workgroup.  Kernels of their own name, defined and instantiated
-// behind everything else, so that every older kernel keeps its code and its place in the code object.
-constexpr int RAYS_BLOCK = 256;
-template <int FLAGS, int LSTEPS>
-__device__ __forceinline__ void shade_ray(const RenderConsts &rc, const RayConsts &yc) {
-    constexpr bool CLOUDS = (FLAGS & KF_CLOUDS) != 0;
-    constexpr bool RM = (FLAGS & KF_CLOUD_LIGHT_RM) != 0;
-    constexpr bool DIRECT = (FLAGS & KF_LIGHT_DIRECT) != 0;
-    constexpr bool LITE = (FLAGS & KF_LITE) != 0;
-    constexpr bool PRECISE = (FLAGS & KF_PRECISE) != 0;
-    static_assert((FLAGS & KF_RAYS) != 0 && (FLAGS & ~(KF_RAYS | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT | KF_LITE | KF_PRECISE)) == 0,
-                  "ray kernels: the default forms under the level-0 sampler");
-    static_assert(!(DIRECT && CLOUDS) && (PRECISE == (CLOUDS || LITE)) && !(RM && LITE), "ray kernels: the LUT-light cloud forms in precise mode, no cloud + direct light");
-    constexpr bool DIET = (!DIRECT || !CLOUDS) && !(CLOUDS && RM);                     // as shade_pixel's
-    constexpr int CAMF = (DIRECT && !CLOUDS) ? (ATMO_PROLOGUE_CAMERA_FORMS & 10) : 0;  // ... of the camera forms, the two that need no camera: the power-of-two
-                                                                                       // step length and the handed-over products
-    const uint32_t i = blockIdx.x * (uint32_t)RAYS_BLOCK + threadIdx.x;   // (grid = ceil(n / 256) blocks and n < 2^32: no wrap)
-    if (i >= yc.n) return;
-    const float4 ray_ot = yc.rays[2 * (size_t)i], ray_d = yc.rays[2 * (size_t)i + 1];   // one dwordx4 load each
-    float4 *out = yc.out + i;
-    float linear_depth = ray_ot.w;
-    const V3 dir = {ray_d.x, ray_d.y, ray_d.z};
-    const V3 center = {rc.center[0] - ray_ot.x, rc.center[1] - ray_ot.y, rc.center[2] - ray_ot.z};   // c' = RN(c - origin)
-
-    const SphereHit sh = sphere_setup(center, dir);
-    float2 rs_atmo;
-    if constexpr ((CAMF & 8) != 0) rs_atmo = hit_radius2<DIET>(sh, rc.atmosphere_radius2);
-    else rs_atmo = hit_radius<DIET>(sh, rc.atmosphere_radius);
-    if (rs_atmo.x == rs_atmo.y) {  // discard: a ray that misses the shell always receives zeros
-        *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        return;
-    }
-    const float t_begin = fmaxf(rs_atmo.x, 0.0f);
-    float t_end = fmaxf(rs_atmo.y, 0.0f);
-    {
-        float2 rs_ground;
-        if constexpr ((CAMF & 8) != 0) rs_ground = hit_radius2<DIET>(sh, rc.planet_radius2);
-        else rs_ground = hit_radius<DIET>(sh, rc.planet_radius);
-        float gd = 10000000.0f;
-        if (rs_ground.x != rs_ground.y) gd = rs_ground.x;
-        linear_depth = linear_depth * (1.0f - rc.sphere_depth_factor) + gd * rc.sphere_depth_factor;
-    }
-    t_end = fminf(t_end, linear_depth);
-
-    // the jitter of image index k = first + i: texel (x & 255, y & 255), x = k % width, y = k / width -- what atmo_render reads for pixel (x, y)
-    const uint32_t k = yc.first + i;
-    const uint32_t ky = k / yc.width, kx = k - ky * yc.width;
-    const float jitter = blue_noise_value<DIET>(rc.blue[(ky & 0xffu) * 256u + (kx & 0xffu)]);
-
-    float4 rgba;
-    if (LITE) {
-        rgba = march_atmosphere_v1_precise<true>(rc, dir, t_begin, t_end, center);
-    } else {
-        float view_step_len;
-        if ((CAMF & 2) != 0 && (rc.prologue_mode & PM_POW2_STEPS)) view_step_len = (t_end - t_begin) * rc.inv_view_steps;
-        else view_step_len = ieee_div(t_end - t_begin, (CAMF & 8) != 0 ? rc.view_steps_f : (float)rc.view_steps);
-        rgba = march_atmosphere<DIRECT, LSTEPS, 1, false, (CAMF & 8) != 0, true>(rc, dir, t_begin, view_step_len, jitter, 0, center);
-    }
-
-    if (CLOUDS) {
-        // --- render_clouds (cloud_funcs.gdshaderinc:249-324), gates evaluated exactly -----------------
-        const float2 rs_top = hit_radius<DIET>(sh, rc.clouds_top);
-        if (rs_top.x != rs_top.y) {
-            const float2 rs_bottom = hit_radius<DIET>(sh, rc.clouds_bottom);
-            const float c0 = fmaxf(rs_top.x, 0.0f);
-            const float c1 = fminf(rs_top.y, linear_depth);
-            if (c0 < linear_depth && (linear_depth > rs_bottom.y || rs_bottom.x > 0.0f)) {
-                const float *M = rc.view_to_model;
-                V3 dir_m;
-                dir_m.x = M[0] * dir.x + M[4] * dir.y + M[8] * dir.z;
-                dir_m.y = M[1] * dir.x + M[5] * dir.y + M[9] * dir.z;
-                dir_m.z = M[2] * dir.x + M[6] * dir.y + M[10] * dir.z;
-                // (view_to_model * (origin, 1)).xyz, the four products summed left to right (clouds:286): fill_consts' origin_model for origin = 0
-                LaneOrigin lo;
-                lo.origin_model.x = M[0] * ray_ot.x + M[4] * ray_ot.y + M[8] * ray_ot.z + M[12] * 1.0f;
-                lo.origin_model.y = M[1] * ray_ot.x + M[5] * ray_ot.y + M[9] * ray_ot.z + M[13] * 1.0f;
-                lo.origin_model.z = M[2] * ray_ot.x + M[6] * ray_ot.y + M[10] * ray_ot.z + M[14] * 1.0f;
-                {   // max_d = mix(ground, space, smoothstep(bottom, top * 1.05, length(ray_origin))) (clouds:186-202): fill_consts' max_d, operation for operation
-                    const V3 om = lo.origin_model;
-                    const float len = ieee_sqrt(om.x * om.x + om.y * om.y + om.z * om.z);
-                    const float st = clampf(ieee_div(len - yc.md_e0, yc.md_e1 - yc.md_e0), 0.0f, 1.0f);
-                    lo.max_d = mixf(yc.md_ground, yc.md_space, st * st * (3.0f - 2.0f * st));
-                }
-                float2 rr;
-                if constexpr (RM) {   // the lit-sample queue, as the twin: wave-private, four waves a workgroup
-                    __shared__ float rmq[(RAYS_BLOCK / 64) * RMQ_WORDS_PER_WAVE];
-                    rr = march_clouds_rm_queue<PRECISE, true>(rc, dir_m, c0, c1, jitter, rmq + (threadIdx.x / 64) * RMQ_WORDS_PER_WAVE, &lo);
-                } else {
-                    rr = march_clouds<RM, PRECISE, 1, false, false, true>(rc, dir_m, c0, c1, jitter, 0, nullptr, nullptr, nullptr, &lo);
-                }
-                {
-#pragma clang fp contract(fast)
-                    const float cl = rr.x, ca = rr.y;
-                    // blend_colors(self = atmosphere, over = cloud)  (util.gdshaderinc:61-69)
-                    const float sa = 1.0f - ca;
-                    const float a = rgba.w * sa + ca;
-                    float abx = 0.0f, aby = 0.0f, abz = 0.0f, abw = 0.0f;
-                    if (a != 0.0f) {
-                        const float inv_a = ieee_div(1.0f, a);
-                        const float ws = rgba.w * sa, wo = cl * ca;
-                        abx = (rgba.x * ws + wo) * inv_a;
-                        aby = (rgba.y * ws + wo) * inv_a;
-                        abz = (rgba.z * ws + wo) * inv_a;
-                        abw = a;
-                    }
-                    const float addx = rgba.x + cl * ca, addy = rgba.y + cl * ca, addz = rgba.z + cl * ca;
-                    const float addw = fmaxf(rgba.w, ca);
-                    rgba.x = mixf(abx, addx, rc.cloud_blend);
-                    rgba.y = mixf(aby, addy, rc.cloud_blend);
-                    rgba.z = mixf(abz, addz, rc.cloud_blend);
-                    rgba.w = mixf(abw, addw, rc.cloud_blend);
-                }
-            }
-        }
-    }
-    *out = rgba;
-}
+// shade_pixel in its RAYS mode, for a ray that did not come out of a camera matrix: origin, direction and distance limit are an AtmoRay's, the planet
+// centre relative to the origin is the lane's own c' = RN(c - origin), and the marches take c' (and the clouds the model-space origin and its march-distance
+// cap) through their LANE forms.  Behind the ray's arrival the shading is shade_pixel's one text -- sphere tests, sphere-depth mix, step length, cloud gates,
+// blend -- with the short exact forms (DIET) and the handed-over products (CAMF & 8, & 2) its twin family takes: where the rays are a camera's
+// (atmo_debug_frame_rays) the picture is atmo_render's under the level-0 sampler, bit for bit (tests/test_rays_gpu.py).  What the mode leaves out: the
+// sure-miss test and the camera rows (they need a projection), the declared sampler (a ray has no 2 x 2 quad to difference), tile order and cost recording
+// (the launch is row-major over the batch), composite and packed stores.
+// Lane mapping: ray i of the batch is thread i -- 64 consecutive rays per wave, RAYS_BLOCK (256) per workgroup.  Kernels of their own name, defined and
+// instantiated behind everything else, so that every older kernel keeps its code and its place in the code object.
 template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(RAYS_BLOCK, render_min_waves(FLAGS & ~KF_RAYS)) void atmo_shade_rays_kernel(const RenderConsts rc, const RayConsts yc) {
-    shade_ray<FLAGS, LSTEPS>(rc, yc);
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, 0, 0, nullptr, nullptr, nullptr, nullptr, &yc);
 }
 // The camera rays of a frame (atmo_debug_frame_rays): for every pixel of the rect, row-major, the ray the float kernels form for it -- origin 0, the prologue's
 // dir, and linear_depth before the sphere-depth mix -- in the GENERAL prologue's arithmetic (main:128-169: the IEEE quotients and roots, the full 4 x 4 rows).
