@@ -73,6 +73,9 @@ CLOUD_DETAIL_SYMBOLS = ("atmo_set_cloud_detail", "atmo_get_cloud_detail", "atmo_
 # and a frame's camera rays from the library's own prologue.  The ABI version stays 5 and the tuple stands beside EXPORTED_SYMBOLS, as PLANETS_SYMBOLS
 # (NOTES.md): a host detects the feature by these symbols, and load() binds them where the library has them (PlanetAtmosphere.shade_rays raises without).
 RAYS_SYMBOLS = ("atmo_shade_rays", "atmo_debug_frame_rays")
+# every symbol include/atmo_ray_quads.h declares: caller-supplied rays in 2 x 2 quads, shaded under the declared cubemap sampler.  The RAYS_SYMBOLS rule:
+# the ABI version stays 5, the tuple stands beside EXPORTED_SYMBOLS, load() binds it where the library has it (PlanetAtmosphere.shade_ray_quads raises without).
+RAY_QUADS_SYMBOLS = ("atmo_shade_ray_quads",)
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -311,6 +314,16 @@ def load() -> C.CDLL:
     }
     assert tuple(rays_sig) == RAYS_SYMBOLS
     for name, (res, args) in rays_sig.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
+    # include/atmo_ray_quads.h: the same rule
+    ray_quads_sig = {
+        "atmo_shade_ray_quads": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    }
+    assert tuple(ray_quads_sig) == RAY_QUADS_SYMBOLS
+    for name, (res, args) in ray_quads_sig.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype = res

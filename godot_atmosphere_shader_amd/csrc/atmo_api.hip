@@ -18,6 +18,7 @@
 #include "../../include/atmo_noise_volume.h"
 #include "../../include/atmo_cloud_detail.h"
 #include "../../include/atmo_rays.h"
+#include "../../include/atmo_ray_quads.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -2252,6 +2253,29 @@ int atmo_debug_cloud_detail_constants(AtmoContext *ctx, const AtmoFrame *frame, 
 static_assert(sizeof(AtmoRay) == 32 && sizeof(AtmoRay) == 2 * sizeof(float4), "an AtmoRay is two float4");
 // Every check stands in front of hipSetDevice, in the header's order, so that a host-only context answers the same.  No feedback state is involved: the
 // launch is row-major over the batch, timed and counted as every accepted atmo_render, with nothing beside the draw stream (a graph capture takes it as it is).
+// The modes no ray kernel exists for, in the headers' order (atmo_rays.h, atmo_ray_quads.h): the message names the entry point and the mode
+static int rays_mode_refusals(AtmoContext *ctx, const AtmoFrame *frame, const std::string &who) {
+    if (ctx->flags & atmo::KF_ATMO_REF) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for atmo_set_precision 2 (rays are shaded in the default forms: atmo_set_precision 1)");
+    if ((ctx->flags & (atmo::KF_CLOUDS | atmo::KF_LITE)) && !(ctx->flags & atmo::KF_PRECISE))
+        return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for atmo_set_precision 0 (rays are shaded in the default forms: atmo_set_precision 1)");
+    if (ctx->view_steps > 32) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for more than 32 view steps (this context has " + std::to_string(ctx->view_steps) + ")");
+    if (choose_split(ctx, frame) == 2) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel with two lanes per ray (atmo_set_lane_split 2)");
+    if ((ctx->flags & atmo::KF_CLOUDS) && (ctx->flags & atmo::KF_LIGHT_DIRECT))
+        return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for a cloud variant in the direct light mode (ATMO_LIGHT_DIRECT)");
+    return cloud_detail_refusal(ctx, who, "ray batches");
+}
+// What the ray kernels read beside RenderConsts (atmo::RayConsts): the batch, its place in the image, and the uniform part of the per-ray march-distance cap
+static atmo::RayConsts ray_consts(const AtmoContext *ctx, const atmo::RenderConsts &rc, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n, uint32_t width,
+                                  uint32_t first) {
+    atmo::RayConsts yc;
+    yc.rays = reinterpret_cast<const float4 *>(rays_dev);
+    yc.out = reinterpret_cast<float4 *>(rgba_dev);
+    yc.n = n; yc.width = width; yc.first = first;
+    cloud_march_distances(ctx->p.u_planet_radius, rc.clouds_top, rc.clouds_bottom, &yc.md_space, &yc.md_ground);
+    yc.md_e0 = rc.clouds_bottom;
+    yc.md_e1 = rc.clouds_top * 1.05f;
+    return yc;
+}
 static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
                      void *stream) {
     const std::string who = "atmo_shade_rays";
@@ -2263,14 +2287,7 @@ static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *ra
     if (width == 0) return fail(ctx, ATMO_E_ARG, who + ": width must be at least 1");
     if ((uint64_t)first + (uint64_t)n_rays > ((uint64_t)1 << 32)) return fail(ctx, ATMO_E_ARG, who + ": first + n_rays must not exceed 2^32");
     // the mode: the default forms under the level-0 sampler (atmo::rays_family_supported)
-    if (ctx->flags & atmo::KF_ATMO_REF) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for atmo_set_precision 2 (rays are shaded in the default forms: atmo_set_precision 1)");
-    if ((ctx->flags & (atmo::KF_CLOUDS | atmo::KF_LITE)) && !(ctx->flags & atmo::KF_PRECISE))
-        return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for atmo_set_precision 0 (rays are shaded in the default forms: atmo_set_precision 1)");
-    if (ctx->view_steps > 32) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for more than 32 view steps (this context has " + std::to_string(ctx->view_steps) + ")");
-    if (choose_split(ctx, frame) == 2) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel with two lanes per ray (atmo_set_lane_split 2)");
-    if ((ctx->flags & atmo::KF_CLOUDS) && (ctx->flags & atmo::KF_LIGHT_DIRECT))
-        return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for a cloud variant in the direct light mode (ATMO_LIGHT_DIRECT)");
-    ATMO_TRY(cloud_detail_refusal(ctx, who, "ray batches"));
+    ATMO_TRY(rays_mode_refusals(ctx, frame, who));
     if (ctx->sampler_lod == 1 && (ctx->flags & atmo::KF_CLOUDS) && ctx->cube.ptr && ctx->cube_levels > 1)
         return fail(ctx, ATMO_E_STATE, who + ": rays sample the coverage cubemap at level 0, and this context demands the declared sampler (atmo_set_sampler_lod 1)");
     int flags = 0, split = 1;
@@ -2285,13 +2302,7 @@ static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *ra
     AtmoFrame fixed;
     frame = draw_frame(ctx, frame, fixed);
     draw_consts(ctx, frame, float_surfaces(nullptr, rgba_dev, false), rc);   // the uniforms, the textures, the sun; its matrices' camera forms are not read
-    atmo::RayConsts yc;
-    yc.rays = reinterpret_cast<const float4 *>(rays_dev);
-    yc.out = reinterpret_cast<float4 *>(rgba_dev);
-    yc.n = n_rays; yc.width = width; yc.first = first;
-    cloud_march_distances(ctx->p.u_planet_radius, rc.clouds_top, rc.clouds_bottom, &yc.md_space, &yc.md_ground);
-    yc.md_e0 = rc.clouds_bottom;
-    yc.md_e1 = rc.clouds_top * 1.05f;
+    const atmo::RayConsts yc = ray_consts(ctx, rc, rays_dev, rgba_dev, n_rays, width, first);
     hipStream_t s = (hipStream_t)stream;
     ATMO_TRY(tex_order(ctx, s));  // texture updated on another stream
     TimingBracket timing;
@@ -2306,6 +2317,62 @@ static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *ra
 int atmo_shade_rays(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
                     void *stream) {
     return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream);
+}
+
+// ---- rays in quads under the declared sampler (include/atmo_ray_quads.h) ---------------------------------------------------------------------------
+// atmo_shade_rays' checks in its order, then what is this entry point's own: a cloud variant, a sampler mode that allows the declared sampler, a mip chain.
+// There is NO fallback to the level-0 ray kernels: their jitter order is row-major and this call's is quad order, a third picture.  The constants are
+// rays_impl's (ray_consts); lod0_* and the level table come from draw_consts, the path of every declared-sampler draw.
+static int ray_quads_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_quads, uint32_t width,
+                          uint32_t first_quad, void *stream) {
+    const std::string who = "atmo_shade_ray_quads";
+    if (!ctx) return ATMO_E_ARG;
+    if (n_quads == 0) return ATMO_OK;   // nothing to shade
+    if (!frame || !rays_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": null frame or device pointer");
+    if ((reinterpret_cast<uintptr_t>(rays_dev) & 15u) != 0 || (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0)
+        return fail(ctx, ATMO_E_ARG, who + ": rays_dev and rgba_dev must be 16-byte aligned");
+    if (width == 0) return fail(ctx, ATMO_E_ARG, who + ": width must be at least 1");
+    if ((uint64_t)first_quad + (uint64_t)n_quads > ((uint64_t)1 << 30)) return fail(ctx, ATMO_E_ARG, who + ": first_quad + n_quads must not exceed 2^30");
+    ATMO_TRY(rays_mode_refusals(ctx, frame, who));
+    if (!(ctx->flags & atmo::KF_CLOUDS))
+        return fail(ctx, ATMO_E_STATE, who + ": a variant without clouds has no texture call to difference; shade its rays with atmo_shade_rays");
+    if (ctx->sampler_lod == 0)
+        return fail(ctx, ATMO_E_STATE, who + ": this context samples the coverage cubemap at level 0 (atmo_set_sampler_lod 0); that is atmo_shade_rays' sampler");
+    ATMO_TRY(check_draw_textures(ctx, who));
+    if (!ctx->cube.ptr || ctx->cube_levels <= 1)
+        return fail(ctx, ATMO_E_STATE, who + ": no mip chain of u_cloud_coverage_cubemap is bound (atmo_set_sampler_lod " + std::to_string(ctx->sampler_lod) +
+                                           "): level 0 is all there is, and atmo_shade_rays samples it");
+    int flags = 0, split = 1;
+    launch_shape(ctx, frame, &flags, &split, nullptr);
+    if (split != 1 || !atmo::ray_quads_family_supported(flags)) return fail(ctx, ATMO_E_STATE, who + ": no ray-quad kernel for this context's mode");
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to shade on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    atmo::RenderConsts rc;
+    AtmoFrame fixed;
+    frame = draw_frame(ctx, frame, fixed);
+    draw_consts(ctx, frame, float_surfaces(nullptr, rgba_dev, false), rc);   // as rays_impl; with it the level-0 certificate's lod0_* of every declared-sampler draw
+    hipStream_t s = (hipStream_t)stream;
+    ATMO_TRY(tex_order(ctx, s));  // texture updated on another stream
+    TimingBracket timing;
+    ATMO_TRY(timing_open(ctx, timing));
+    ATMO_TRY(timing_begin(ctx, timing, s));
+    // slot 4 q + j: thread i = slot i; the kernel's jitter pixel comes from the quad index first_quad + (i >> 2) and the quads per row.  A launch holds at
+    // most 2^29 quads, so that its 4 n_quads rays fit RayConsts::n (the one batch of 2^30 quads the range check admits goes out as two)
+    constexpr uint32_t per_launch = 1u << 29;
+    for (uint32_t done = 0; done < n_quads; done += per_launch) {
+        const uint32_t quads = n_quads - done < per_launch ? n_quads - done : per_launch;
+        const atmo::RayConsts yc = ray_consts(ctx, rc, rays_dev + 4 * (size_t)done, rgba_dev + 16 * (size_t)done, 4u * quads, (width + 1u) / 2u, first_quad + done);
+        HIP_TRY(ctx, atmo::launch_shade_ray_quads(flags, rc, yc, s));
+    }
+    hipEvent_t marker = nullptr;
+    ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_RAYS, 1, true, &marker));
+    return timing_end(ctx, timing, s);
+}
+
+int atmo_shade_ray_quads(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_quads, uint32_t width,
+                         uint32_t first_quad, void *stream) {
+    return ray_quads_impl(ctx, frame, rays_dev, rgba_dev, n_quads, width, first_quad, stream);
 }
 
 int atmo_debug_frame_rays(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, AtmoRay *rays_dev, void *stream) {

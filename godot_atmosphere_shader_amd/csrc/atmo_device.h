@@ -314,6 +314,10 @@ hipError_t launch_render_detail(int flags, const RenderConsts &rc, const DetailC
 // 64 consecutive rays per wave, 256 per workgroup, row-major over the batch; flags WITHOUT KF_RAYS, which the launcher adds
 bool rays_family_supported(int flags);
 hipError_t launch_shade_rays(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream);
+// rays in quads under the declared sampler (atmo_shade_ray_quads; include/atmo_ray_quads.h): the three cloud families, flags WITH KF_CUBE_LOD and without
+// KF_RAYS; the same grid rule; yc.n = 4 n_quads, yc.first = first_quad, yc.width = quads per row of the image, (width + 1) / 2
+bool ray_quads_family_supported(int flags);
+hipError_t launch_shade_ray_quads(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream);
 // the camera rays of the rect in rc, as the float kernels' prologue forms them (atmo_debug_frame_rays)
 hipError_t launch_frame_rays(const RenderConsts &rc, const FrameRaysConsts &fc, hipStream_t stream);
 // load_depth's decode over n texels of a caller's array: out[i] = decode(texels[i]) (atmo_debug_decode_depth)

@@ -1717,13 +1717,21 @@ __device__ __forceinline__ float rm_sample_weight(RmRecurrence &s, float density
 // position is still advanced one rounded addition per step), so the result is bit-identical; only lane 0's is used.
 // DETAIL (KF_DETAIL, one lane per ray, precise): every sample's density is get_density -- the detail fetch -- and the raymarched light, which now depends on
 // the march's alpha before the sample (light_raymarched), is evaluated in place under BOTH samplers: a deferred lit-sample queue would have to carry alpha0.
-// LANE (KF_RAYS): the ray's own origin and march-distance cap, *lo (cloud_march_ray); level-0 sampler, one lane per ray.
+// LANE (KF_RAYS): the ray's own origin and march-distance cap, *lo (cloud_march_ray); one lane per ray, no cloud detail.
+// LANE && LOD (atmo_shade_ray_quads, include/atmo_ray_quads.h): the four lanes of a quad hold the four rays of a caller's quad, each with an origin, a
+// direction and a cap of its own.  Nothing below asks where a lane's position chain came from: the `marching` ballot counts the lanes that are here, the
+// whole-quad exchange reads whatever positions the partner lanes hold, and the level-0 certificate's E (quad_march_spread2) needs no other drift bound --
+// each lane's sample position is p0 + k dd with ITS p0 and dd (the pixel kernels' lanes differ in both already: dd = dir_m * step_len, and t_begin, t_end
+// and therefore step_len are per pixel), so the difference of two lanes is still affine in k, its norm convex, its maximum at k = 0 or k = last, which is
+// where the function measures it from the lanes' own registers; the drift term is rc.lod0_drift * pmax with pmax >= |p| of EITHER lane at any step
+// (the lane's own end points plus the distance e to its partners), whatever the origins.  A cap of its own only makes dd another length.  Origins far
+// apart make E large and the certificate is withheld: the full path, never a wrong level 0.
 template <bool RM, bool PRECISE, int SPLIT, bool LOD = false, bool DETAIL = false, bool LANE = false>
 __device__ __forceinline__ float2 march_clouds(const RenderConsts &rc_in, V3 dir_m, float t_begin, float t_end, float jitter, int half,
                                                QuadRegs *qregs = nullptr, const f32x4 *lvl = nullptr, const DetailConsts *xc = nullptr,
                                                const LaneOrigin *lo = nullptr) {
     static_assert(!DETAIL || (PRECISE && SPLIT == 1), "cloud detail: the precise form, one lane per ray");
-    static_assert(!LANE || (!LOD && !DETAIL && SPLIT == 1), "per-ray origins: the level-0 sampler, no cloud detail, one lane per ray");
+    static_assert(!LANE || (!DETAIL && SPLIT == 1), "per-ray origins: no cloud detail, one lane per ray");
     // Under the declared sampler the raymarched light is evaluated IN PLACE with one lane per ray as well (round 5) -- this function instead of the
     // lit-sample queue, whose arithmetic it keeps (same bits): 73 VGPRs and no queue in LDS instead of 86 / 15 KB, six waves per SIMD instead of five, no
     // twelve-word entries through LDS, no second whole-quad block per lit sample.  Measured then (profiles/round5/ab_rm_inplace.txt): 3840x2160 -11.4 %
@@ -2193,6 +2201,10 @@ __device__ __forceinline__ void store_target_zero_all_rt(const int format, void 
 // (yc->out[i], a plain store; zeros for a miss) -- and in the operands the ray's own origin gives the marches (their LANE forms).  Everything between is the
 // one text below.  Each site reads `if constexpr (RAYS) <the ray's form>; else <the pixel kernels' statement as it stands>`: an argument added to a pixel
 // kernel's statement, or a helper shared by both sides, moves the older kernels' code (NOTES.md "Caller-supplied rays"; tools/isa_diff.py is the check).
+// RAYS && LOD (atmo_shade_ray_quads; include/atmo_ray_quads.h): the rays arrive four to a quad, slot i = thread i, and the cloud march samples the coverage
+// cubemap as the declared-sampler pixel kernels do -- the level tables in LDS, qregs and lvl_table handed to march_clouds' LOD && LANE form, helper false,
+// an absent ray gone where a pixel outside the viewport goes, the jitter pixel from the quad index.  The same rule: `if constexpr (RAYS && LOD) <new>; else
+// <what stood there>` (NOTES.md "Ray quads").
 constexpr int RAYS_BLOCK = 256;   // rays (threads) per workgroup of the ray kernels: 64 consecutive rays per wave
 template <int FLAGS, int LSTEPS, int SPLIT>
 __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int tile_x, const int tile_y, const ProxyConsts *pc = nullptr,
@@ -2220,8 +2232,8 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     static_assert(!PROXY || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0), "proxy draws: the default forms, one lane per ray, row-major");
     static_assert((FLAGS & KF_VIEWS) == 0 || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0),
                   "multi-view draws: the default forms, one lane per ray, float or packed targets (KF_VIEWS | KF_TARGET: atmo_render_views_target_kernel)");
-    static_assert(!RAYS || ((FLAGS & ~(KF_RAYS | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT | KF_LITE | KF_PRECISE)) == 0 && SPLIT == 1),
-                  "ray kernels: the default forms under the level-0 sampler, one lane per ray");
+    static_assert(!RAYS || ((FLAGS & ~(KF_RAYS | KF_CUBE_LOD | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT | KF_LITE | KF_PRECISE)) == 0 && SPLIT == 1),
+                  "ray kernels: the default forms, one lane per ray; the declared sampler (KF_CUBE_LOD) for rays that arrive in quads (atmo_shade_ray_quads)");
     static_assert(!RAYS || (!(DIRECT && CLOUDS) && (PRECISE == (CLOUDS || LITE)) && !(RM && LITE)),
                   "ray kernels: the LUT-light cloud forms in precise mode, no cloud + direct light");
     // the short exact prologue: every kernel but cloud + direct-light and raymarched cloud light (prologue_sqrt)
@@ -2266,12 +2278,23 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     QuadRegs qregs;
     if constexpr (LOD) quad_regs_define(qregs);  // all 64 lanes are still here: nothing else may ever live in these registers
     // RAYS: the work item is ray i of the batch, thread i of the launch (grid = ceil(n / 256) blocks and n < 2^32: no wrap).  The lane-to-pixel lines above
-    // are the pixel kernels': under RAYS (tile 0, 0; one lane per ray; level-0 sampler) they leave half = 0 and helper = false, and nothing reads px / py
+    // are the pixel kernels': under RAYS (tile 0, 0; one lane per ray) they leave half = 0, and nothing reads px / py (helper is set false below)
+    // RAYS && LOD (atmo_shade_ray_quads): slot i = 4 q + j of the batch, so a quad is four consecutive lanes with its partners at lane ^ 1 and lane ^ 2, a
+    // wave holds 16 whole quads, and n = 4 n_quads never cuts one.  An ABSENT ray (dir = +-0 in every component) leaves here, where a pixel outside the
+    // viewport leaves -- behind quad_regs_define, with zeros stored: it reaches no texture call and is missing from every ballot its partners take
     const uint32_t i = RAYS ? blockIdx.x * (uint32_t)RAYS_BLOCK + threadIdx.x : 0u;
-    if constexpr (RAYS) {
+    if constexpr (RAYS && LOD) {
+        if (i >= yc->n) return;
+        const float4 absent_d = yc->rays[2 * (size_t)i + 1];
+        if (absent_d.x == 0.0f && absent_d.y == 0.0f && absent_d.z == 0.0f) {
+            yc->out[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            return;
+        }
+    } else if constexpr (RAYS) {
         if (i >= yc->n) return;
     } else if (LOD ? (px >= rc.w || py >= rc.h) : (px >= rc.x1 || py >= rc.y1)) return;
     bool helper = LOD && (px < rc.x0 || py < rc.y0 || px >= rc.x1 || py >= rc.y1);
+    if constexpr (RAYS && LOD) helper = false;   // every present ray is shaded and stored (px / py mean nothing here)
     if constexpr (PROXY) {
         // The far-mode draw: only the box's passing fragments are shaded and stored.  In front of every store of this function (the sure-miss and the
         // discard store included).  Without the declared sampler a failing lane simply leaves.  With it, a failing pixel becomes a HELPER, like a pixel
@@ -2421,7 +2444,14 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
 
     // the jitter texel (x & 255, y & 255) of the pixel; RAYS: of image index k = first + i, x = k % width, y = k / width -- what atmo_render reads for pixel (x, y)
     float jitter;
-    if constexpr (RAYS) {
+    if constexpr (RAYS && LOD) {
+        // quad order: slot i = 4 q + j is pixel (2 (Q % qpr) + (j & 1), 2 (Q / qpr) + (j >> 1)), Q = first_quad + q -- yc->first is first_quad and yc->width
+        // is qpr = (width + 1) / 2, the quads per row (the host's ray_quads_impl); Q < 2^30
+        const uint32_t kq = yc->first + (i >> 2);
+        const uint32_t qy = kq / yc->width, qx = kq - qy * yc->width;
+        const uint32_t kx = 2u * qx + (i & 1u), ky = 2u * qy + ((i >> 1) & 1u);
+        jitter = blue_noise_value<DIET>(rc.blue[(ky & 0xffu) * 256u + (kx & 0xffu)]);
+    } else if constexpr (RAYS) {
         const uint32_t k = yc->first + i;
         const uint32_t ky = k / yc->width, kx = k - ky * yc->width;
         jitter = blue_noise_value<DIET>(rc.blue[(ky & 0xffu) * 256u + (kx & 0xffu)]);
@@ -2482,7 +2512,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                     if constexpr (RAYS) rr = march_clouds_rm_queue<PRECISE, true>(rc, dir_m, c0, c1, jitter, rmq + wave * RMQ_WORDS_PER_WAVE, &lo);
                     else rr = march_clouds_rm_queue<PRECISE>(rc, dir_m, c0, c1, jitter, rmq + wave * RMQ_WORDS_PER_WAVE);
                 } else {
-                    if constexpr (RAYS) rr = march_clouds<RM, PRECISE, 1, false, false, true>(rc, dir_m, c0, c1, jitter, 0, nullptr, nullptr, nullptr, &lo);
+                    // RAYS && LOD: the declared sampler on the quad's four rays; with RM the in-place form (RMQ_FORM) of the pixel twin, no queue LDS
+                    if constexpr (RAYS && LOD) rr = march_clouds<RM, PRECISE, 1, true, false, true>(rc, dir_m, c0, c1, jitter, 0, &qregs, lvl_table, nullptr, &lo);
+                    else if constexpr (RAYS) rr = march_clouds<RM, PRECISE, 1, false, false, true>(rc, dir_m, c0, c1, jitter, 0, nullptr, nullptr, nullptr, &lo);
                     else rr = march_clouds<RM, PRECISE, SPLIT, LOD>(rc, dir_m, c0, c1, jitter, half, &qregs, lvl_table);
                 }
                 {
@@ -2511,6 +2543,7 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
         }
     }
     if constexpr (RAYS) {   // a ray's result as it is: no composite, no packed target
+        if constexpr (LOD) quad_regs_keep(qregs);
         *out = rgba;
         return;
     }
@@ -3859,7 +3892,8 @@ hipError_t launch_render_detail(int flags, const RenderConsts &rc, const DetailC
 // cap) through their LANE forms.  Behind the ray's arrival the shading is shade_pixel's one text -- sphere tests, sphere-depth mix, step length, cloud gates,
 // blend -- with the short exact forms (DIET) and the handed-over products (CAMF & 8, & 2) its twin family takes: where the rays are a camera's
 // (atmo_debug_frame_rays) the picture is atmo_render's under the level-0 sampler, bit for bit (tests/test_rays_gpu.py).  What the mode leaves out: the
-// sure-miss test and the camera rows (they need a projection), the declared sampler (a ray has no 2 x 2 quad to difference), tile order and cost recording
+// sure-miss test and the camera rows (they need a projection), the declared sampler (a ray has no 2 x 2 quad to difference -- unless the caller hands its
+// rays over in quads: the three KF_CUBE_LOD instantiations at the end of this file, atmo_shade_ray_quads), tile order and cost recording
 // (the launch is row-major over the batch), composite and packed stores.
 // Lane mapping: ray i of the batch is thread i -- 64 consecutive rays per wave, RAYS_BLOCK (256) per workgroup.  Kernels of their own name, defined and
 // instantiated behind everything else, so that every older kernel keeps its code and its place in the code object.
@@ -3941,5 +3975,36 @@ hipError_t launch_frame_rays(const RenderConsts &rc, const FrameRaysConsts &fc, 
     hipLaunchKernelGGL(atmo_frame_rays_kernel, dim3((unsigned)((n + RAYS_BLOCK - 1) / RAYS_BLOCK)), dim3(RAYS_BLOCK), 0, stream, rc, fc);
     return hipGetLastError();
 }
+
+// ---- rays in quads under the declared sampler (KF_RAYS | KF_CUBE_LOD; include/atmo_ray_quads.h) -------------------------------------------------------------
+// The three cloud families of atmo_shade_rays_kernel once more, with the coverage cubemap sampled as their pixel twins atmo_render_kernel<49 / 51 / 57, 0, 1>
+// sample it: slot i = 4 q + j of the batch is thread i, so the caller's quad q sits in four consecutive lanes and the whole-quad exchange finds a ray's
+// partners where it finds a pixel's.  flags WITHOUT KF_RAYS and WITH KF_CUBE_LOD; yc.n = 4 n_quads, yc.first = first_quad, yc.width = quads per row.
+// Instantiated here, behind every older kernel, which keep their code and their place in the code object.
+#define ATMO_RAY_QUADS_FAMILIES(ONE)                               \
+    ONE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)                      \
+    ONE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)  \
+    ONE(KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS)
+bool ray_quads_family_supported(int flags) {
+    switch (flags) {
+#define ATMO_RAY_QUADS_LISTED(F) case (F):
+        ATMO_RAY_QUADS_FAMILIES(ATMO_RAY_QUADS_LISTED)
+#undef ATMO_RAY_QUADS_LISTED
+        return true;
+    default: return false;
+    }
+}
+hipError_t launch_shade_ray_quads(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream) {
+    // whole quads only; first_quad + n_quads <= 2^30, so 2 * quad column + 1 and 4 * quad index stay below 2^32
+    if (yc.rays == nullptr || yc.out == nullptr || yc.n == 0 || (yc.n & 3u) != 0 || yc.width == 0 || (uint64_t)yc.first + (yc.n >> 2) > ((uint64_t)1 << 30))
+        return hipErrorInvalidValue;
+    switch (flags) {
+#define ATMO_RAY_QUADS_LAUNCH(F) case (F): return launch_rays(atmo_shade_rays_kernel<(F) | KF_RAYS, 0>, rc, yc, stream);
+        ATMO_RAY_QUADS_FAMILIES(ATMO_RAY_QUADS_LAUNCH)
+#undef ATMO_RAY_QUADS_LAUNCH
+    default: return hipErrorInvalidValue;
+    }
+}
+#undef ATMO_RAY_QUADS_FAMILIES
 
 }  // namespace atmo

@@ -723,6 +723,56 @@ class PlanetAtmosphere:
         N.check(self._ctx, fn(self._ctx, C.byref(nf), C.c_void_p(depth.data_ptr()), C.c_void_p(rays.data_ptr()), C.c_void_p(stream or 0)))
         return rays
 
+    # ---- rays in quads under the declared sampler (include/atmo_ray_quads.h) ------------------------------------------------------
+    def shade_ray_quads(self, quads, camera=None, *, width, first_quad: int = 0, out=None, stream=None, time: float = 0.0):
+        """Shades caller-supplied rays that arrive in 2 x 2 quads, the coverage cubemap sampled as the declared sampler samples it: each ray differences
+        against the two partner rays of its quad (atmo_shade_ray_quads; include/atmo_ray_quads.h states the layout and the arithmetic).  `quads`: a
+        contiguous CUDA float32 tensor of shape (4 * n_quads, 8), one N.AtmoRay a row in quad order (ray_quads.quad_order) -- slot 4 q + j is the ray of
+        pixel (2 (Q % qpr) + (j & 1), 2 (Q // qpr) + (j >> 1)) with Q = first_quad + q and qpr = (width + 1) // 2; an all-zero direction marks an absent
+        ray.  `camera` as in `shade_rays`.  Returns or fills `out`, a contiguous CUDA float32 (4 * n_quads, 4) tensor in the same order (zeros for an
+        absent ray and for one that misses the atmosphere); ray_quads.quads_to_image puts a whole image's back into rows."""
+        n = _check_rays(quads, "quads", 8)
+        if n % 4:
+            raise ValueError("quads must have four rows per quad: shape (4 * n_quads, 8)")
+        try:
+            width, first_quad = operator.index(width), operator.index(first_quad)
+        except TypeError:
+            raise TypeError("width and first_quad must be integers") from None
+        if width < 1 or first_quad < 0 or first_quad + n // 4 > 1 << 30:
+            raise ValueError("width must be at least 1, first_quad at least 0 and first_quad + n_quads at most 2^30")
+        if out is None:
+            import torch
+
+            out = torch.empty((n, 4), dtype=torch.float32, device=quads.device)
+        elif _check_rays(out, "out", 4) != n:
+            raise ValueError("out must have one row per ray: shape (4 * n_quads, 4)")
+        fn = getattr(self._lib, "atmo_shade_ray_quads", None)
+        if fn is None:
+            raise RuntimeError("libatmo_hip.so does not export atmo_shade_ray_quads (include/atmo_ray_quads.h); rebuild it")
+        stream = _stream_handle(stream, quads)
+        self._bake_if_needed(stream)
+        nf = _to_native_frame(self.make_frame(camera if camera is not None else _WORLD_RAY_SPACE, time))
+        N.check(self._ctx, fn(self._ctx, C.byref(nf), C.c_void_p(quads.data_ptr()), C.c_void_p(out.data_ptr()), n // 4, width, first_quad,
+                              C.c_void_p(stream or 0)))
+        return out
+
+    def camera_ray_quads(self, camera, depth, stream=None):
+        """`camera_rays` of the whole viewport gathered into quad order (ray_quads.quad_order) for `shade_ray_quads(width=camera.width)`: a CUDA float32
+        (4 * ceil(w / 2) * ceil(h / 2), 8) tensor, all-zero rows (absent rays) for the slots outside the image."""
+        import torch
+
+        from .ray_quads import quad_order
+
+        rays = self.camera_rays(camera, depth, stream=stream)
+        order = torch.as_tensor(quad_order(camera.width, camera.height), device=rays.device)
+        def gather():
+            return torch.where((order >= 0).unsqueeze(1), rays[order.clamp(min=0)], torch.zeros((), dtype=rays.dtype, device=rays.device)).contiguous()
+
+        if stream is None:   # torch's current stream: where camera_rays enqueued
+            return gather()
+        with torch.cuda.stream(torch.cuda.ExternalStream(_stream_handle(stream, depth), device=depth.device)):   # the gather behind the dump, on its stream
+            return gather()
+
     def prepare_frame(self, camera, time: float = 0.0, rect=None) -> N.AtmoFrame:
         """The native per-frame argument block for `render_prepared` (build once per camera pose)."""
         return _to_native_frame(self.make_frame(camera, time, rect))

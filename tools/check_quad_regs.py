@@ -166,11 +166,17 @@ def check(asm_text: str):
 def main(argv):
     out = os.path.join(tempfile.mkdtemp(prefix="quadregs_"), "k.s")
     subprocess.run(["hipcc"] + HIPCC_FLAGS + [SRC, "-o", out] + argv, check=True, stderr=subprocess.DEVNULL)
-    res = check(open(out).read())
+    return report(open(out).read())
+
+
+def report(text: str):
+    """The command line's output and exit status on assembly text that is already there (tests/test_ray_quads_host.py shares one compile with the twin checks)."""
+    res = check(text)
     names = subprocess.run(["c++filt"] + list(res), capture_output=True, text=True).stdout.split("\n") if res else []
     ok = bool(res)
     for (name, (blocks, private, bad, inputs, bad_inputs)), nice in zip(res.items(), names):
-        nice = nice.replace("void atmo::", "").replace("(atmo::RenderConsts)", "")
+        # (the ray-quad kernels -- atmo_shade_rays_kernel<FLAGS | 16384 | 32, 0>, include/atmo_ray_quads.h -- are listed with the declared-sampler pixel kernels)
+        nice = nice.replace("void atmo::", "").replace("(atmo::RenderConsts)", "").replace("(atmo::RenderConsts, atmo::RayConsts)", "")
         print(f"{nice:44s} {blocks} exchange blocks, {len(private)} private VGPRs: " + ("ok" if not bad else f"{len(bad)} OUTSIDE WRITES, e.g. {bad[0]}")
               + f"; {len(inputs)} input VGPRs {['v%d' % r for r in inputs]}: "
               + ("only the position update writes them in the march" if not bad_inputs else f"{len(bad_inputs)} OTHER WRITES IN THE MARCH, e.g. {bad_inputs[0]}"))
@@ -179,7 +185,6 @@ def main(argv):
         print("no kernel contains an exchange block")
     # and, for every kernel of the file: no stack.  A frame object -- even a dead spill slot of a rematerialised kernel-argument tuple, with no
     # scratch instruction left in the ISA -- makes the kernel descriptor ask for a private segment (round 4: seven kernels, 36 bytes).
-    text = open(out).read()
     scratch = re.findall(r"^; ScratchSize: (\d+)", text, re.M)
     spilled = [m for m in re.finditer(r"^\s*(scratch_(?:load|store)\w*)", text, re.M)]
     nonzero = [int(x) for x in scratch if int(x)]

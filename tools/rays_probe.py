@@ -12,7 +12,16 @@ ONE process, one context per family; three arms timed INTERLEAVED, every round i
   render2   render again: render2 / render is the run-to-run spread of an arm against itself.
 Device events around `reps` calls through the binding (one event pair around the K launches), after priming as bench.py does: warm-up calls of every arm,
 then ~25 ms of draws so that the clocks are the sustained ones.  Reported per arm: the median, minimum and maximum of the rounds (ms per call), the ratios
-of the medians, and the kernel each arm reported.  Prints one JSON object.  Needs a device: there is no CPU figure."""
+of the medians, and the kernel each arm reported.  Prints one JSON object.  Needs a device: there is no CPU figure.
+
+The QUADS table (--table quads, or both: the default), for the three cloud families under the DECLARED sampler (include/atmo_ray_quads.h), same frame, same
+timing, every round in the order render, quads, rays, render2:
+  render    atmo_render under the default, declared sampler (a chain bound) with atmo_set_tile_feedback 0: the draw the quad kernels are held to bit for bit
+            (tests/test_ray_quads_gpu.py); a wave there is a 16 x 4 pixel block, here a 32 x 2 strip (16 quads of a quad row);
+  quads     atmo_shade_ray_quads on camera_ray_quads(frame), width = 1920;
+  rays      the level-0 atmo_shade_rays of the same frame's rays, for scale (another picture: level 0);
+  render2   render again.
+`bits_equal_render`: the quads' picture, put back into rows, is the render arm's."""
 import argparse
 import json
 import os
@@ -39,6 +48,8 @@ FAMILIES = {
 }
 W, H = 1920, 1080
 ARMS = ("render", "rays", "shuffled", "render2")
+QUAD_FAMILIES = ("clouds_high", "clouds_high_rm", "v1_clouds")
+QUAD_ARMS = ("render", "quads", "rays", "render2")
 
 
 def timed(call, reps):
@@ -58,6 +69,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--families", default=",".join(FAMILIES))
+    ap.add_argument("--table", choices=("rays", "quads", "both"), default="both")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rays_probe.py measures on a device; none is visible")
@@ -68,7 +80,7 @@ def main():
     out = torch.empty((H * W, 4), dtype=torch.float32, device="cuda")
     perm = torch.randperm(H * W, generator=torch.Generator().manual_seed(1)).cuda()
     result = {"viewport": [W, H], "pose": "P_space", "reps": args.reps, "rounds": args.rounds, "device": torch.cuda.get_device_name(0), "rows": []}
-    for label in args.families.split(","):
+    for label in args.families.split(",") if args.table != "quads" else ():
         config, kw = FAMILIES[label]
         node = make_node(config, tex, cubemap_lod=False, tile_feedback=0, **kw)   # atmo_set_sampler_lod 0, atmo_set_tile_feedback 0
         try:
@@ -104,6 +116,46 @@ def main():
         print(f"{label:15s} render {med['render']:.4f} ms  rays {med['rays']:.4f} ms ({row['rays_over_render']:.3f} x)  shuffled {med['shuffled']:.4f} ms "
               f"({row['shuffled_over_rays']:.3f} x rays)  render again {med['render2']:.4f} ms ({row['render2_over_render']:.3f} x)  bits equal: {same}  "
               f"{names['render']} / {names['rays']}", file=sys.stderr, flush=True)
+    if args.table != "rays":
+        from godot_atmosphere_shader_amd.ray_quads import quads_to_image
+
+        result["quad_rows"] = []
+        for label in [f for f in args.families.split(",") if f in QUAD_FAMILIES]:
+            config, kw = FAMILIES[label]
+            node = make_node(config, tex, tile_feedback=0, **kw)   # the default sampler: declared, a chain bound; atmo_set_tile_feedback 0
+            try:
+                rays = node.camera_rays(cam, depth)
+                quads = node.camera_ray_quads(cam, depth)
+                qout = torch.empty((quads.shape[0], 4), dtype=torch.float32, device="cuda")
+                calls = {"render": lambda: node.render(cam, depth, out=frame), "quads": lambda: node.shade_ray_quads(quads, cam, width=W, out=qout),
+                         "rays": lambda: node.shade_rays(rays, cam, width=W, out=out)}
+                calls["render2"] = calls["render"]
+                names = {}
+                for arm in ("render", "quads", "rays"):
+                    timed(calls[arm], args.warmup)
+                    names[arm] = node.kernel_name
+                node.render(cam, depth, out=frame)
+                node.shade_ray_quads(quads, cam, width=W, out=qout)
+                same = bool(torch.equal(frame.view(torch.int32), quads_to_image(qout, W, H).view(torch.int32)))
+                t_warm = time.perf_counter()
+                while time.perf_counter() - t_warm < 0.025:   # sustained clocks
+                    calls["render"]()
+                    torch.cuda.synchronize()
+                arms = {a: [] for a in QUAD_ARMS}
+                for _ in range(args.rounds):
+                    for arm in QUAD_ARMS:
+                        arms[arm].append(timed(calls[arm], args.reps))
+            finally:
+                node.close()
+            med = {a: sorted(v)[len(v) // 2] for a, v in arms.items()}
+            row = {"family": label, "kernels": names, "bits_equal_render": same,
+                   "ms": {a: {"median": med[a], "min": min(v), "max": max(v)} for a, v in arms.items()},
+                   "quads_over_render": med["quads"] / med["render"], "rays_over_render": med["rays"] / med["render"],
+                   "render2_over_render": med["render2"] / med["render"]}
+            result["quad_rows"].append(row)
+            print(f"{label:15s} render {med['render']:.4f} ms  quads {med['quads']:.4f} ms ({row['quads_over_render']:.3f} x)  level-0 rays {med['rays']:.4f} ms "
+                  f"({row['rays_over_render']:.3f} x)  render again {med['render2']:.4f} ms ({row['render2_over_render']:.3f} x)  bits equal: {same}  "
+                  f"{names['render']} / {names['quads']}", file=sys.stderr, flush=True)
     text = json.dumps(result)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
