@@ -76,6 +76,11 @@ RAYS_SYMBOLS = ("atmo_shade_rays", "atmo_debug_frame_rays")
 # every symbol include/atmo_ray_quads.h declares: caller-supplied rays in 2 x 2 quads, shaded under the declared cubemap sampler.  The RAYS_SYMBOLS rule:
 # the ABI version stays 5, the tuple stands beside EXPORTED_SYMBOLS, load() binds it where the library has it (PlanetAtmosphere.shade_ray_quads raises without).
 RAY_QUADS_SYMBOLS = ("atmo_shade_ray_quads",)
+# every symbol include/atmo_ray_order.h declares: the device's coherence order of a ray queue and the ray kernels through an index list.  The RAYS_SYMBOLS
+# rule: the ABI version stays 5, the tuple stands beside EXPORTED_SYMBOLS, load() binds it where the library has it (PlanetAtmosphere.ray_order and
+# shade_rays(index=...) raise without).
+RAY_ORDER_SYMBOLS = ("atmo_ray_order_scratch_bytes", "atmo_ray_order", "atmo_shade_rays_indexed", "atmo_debug_ray_keys", "atmo_debug_sort_ray_keys")
+RAY_KEY_BITS = 18   # ATMO_RAY_KEY_BITS
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -324,6 +329,20 @@ def load() -> C.CDLL:
     }
     assert tuple(ray_quads_sig) == RAY_QUADS_SYMBOLS
     for name, (res, args) in ray_quads_sig.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
+    # include/atmo_ray_order.h: the same rule
+    ray_order_sig = {
+        "atmo_ray_order_scratch_bytes": (ip, [C.c_uint32, C.POINTER(C.c_size_t)]),
+        "atmo_ray_order": (ip, [vp, vp, C.c_uint32, vp, vp, C.c_size_t, vp]),
+        "atmo_shade_rays_indexed": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]),
+        "atmo_debug_ray_keys": (ip, [vp, vp, C.c_uint32, vp, vp]),
+        "atmo_debug_sort_ray_keys": (ip, [vp, vp, C.c_uint32, vp, vp, C.c_size_t, vp]),
+    }
+    assert tuple(ray_order_sig) == RAY_ORDER_SYMBOLS
+    for name, (res, args) in ray_order_sig.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype = res

@@ -19,6 +19,7 @@
 #include "../../include/atmo_cloud_detail.h"
 #include "../../include/atmo_rays.h"
 #include "../../include/atmo_ray_quads.h"
+#include "../../include/atmo_ray_order.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -2276,14 +2277,22 @@ static atmo::RayConsts ray_consts(const AtmoContext *ctx, const atmo::RenderCons
     yc.md_e1 = rc.clouds_top * 1.05f;
     return yc;
 }
+// index != nullptr: atmo_shade_rays_indexed (include/atmo_ray_order.h) -- the same checks under its name, its list's two in the argument block, and the
+// KF_INDEX kernels over the list; everything else is the one path
+struct RayIndexList {
+    const uint32_t *index_dev;
+    uint32_t n_index;
+};
 static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
-                     void *stream) {
-    const std::string who = "atmo_shade_rays";
+                     void *stream, const RayIndexList *index = nullptr) {
+    const std::string who = index ? "atmo_shade_rays_indexed" : "atmo_shade_rays";
     if (!ctx) return ATMO_E_ARG;
-    if (n_rays == 0) return ATMO_OK;   // nothing to shade
+    if (n_rays == 0 || (index && index->n_index == 0)) return ATMO_OK;   // nothing to shade
     if (!frame || !rays_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": null frame or device pointer");
     if ((reinterpret_cast<uintptr_t>(rays_dev) & 15u) != 0 || (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0)
         return fail(ctx, ATMO_E_ARG, who + ": rays_dev and rgba_dev must be 16-byte aligned");
+    if (index && !index->index_dev) return fail(ctx, ATMO_E_ARG, who + ": null index_dev");
+    if (index && (reinterpret_cast<uintptr_t>(index->index_dev) & 3u) != 0) return fail(ctx, ATMO_E_ARG, who + ": index_dev must be 4-byte aligned");
     if (width == 0) return fail(ctx, ATMO_E_ARG, who + ": width must be at least 1");
     if ((uint64_t)first + (uint64_t)n_rays > ((uint64_t)1 << 32)) return fail(ctx, ATMO_E_ARG, who + ": first + n_rays must not exceed 2^32");
     // the mode: the default forms under the level-0 sampler (atmo::rays_family_supported)
@@ -2308,9 +2317,14 @@ static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *ra
     TimingBracket timing;
     ATMO_TRY(timing_open(ctx, timing));
     ATMO_TRY(timing_begin(ctx, timing, s));
-    HIP_TRY(ctx, atmo::launch_shade_rays(flags, rc, yc, s));
+    if (index) {
+        const atmo::RayIndexConsts ic = {index->index_dev, index->n_index};
+        HIP_TRY(ctx, atmo::launch_shade_rays_indexed(flags, rc, yc, ic, s));
+    } else {
+        HIP_TRY(ctx, atmo::launch_shade_rays(flags, rc, yc, s));
+    }
     hipEvent_t marker = nullptr;
-    ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_RAYS, 1, true, &marker));
+    ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_RAYS | (index ? atmo::KF_INDEX : 0), 1, true, &marker));
     return timing_end(ctx, timing, s);
 }
 
@@ -2373,6 +2387,73 @@ static int ray_quads_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRa
 int atmo_shade_ray_quads(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_quads, uint32_t width,
                          uint32_t first_quad, void *stream) {
     return ray_quads_impl(ctx, frame, rays_dev, rgba_dev, n_quads, width, first_quad, stream);
+}
+
+// ---- ray queues: the device's coherence order and shading through an index list (include/atmo_ray_order.h) ------------------------------------------------
+static_assert(ATMO_RAY_KEY_BITS == atmo::RAY_KEY_BITS, "the header's key width is the kernels'");
+int atmo_shade_rays_indexed(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
+                            const uint32_t *index_dev, uint32_t n_index, void *stream) {
+    const RayIndexList list = {index_dev, n_index};
+    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, &list);
+}
+
+int atmo_ray_order_scratch_bytes(uint32_t n_rays, size_t *bytes) {
+    if (!bytes) return fail(nullptr, ATMO_E_ARG, "atmo_ray_order_scratch_bytes: null bytes");
+    if (n_rays > atmo::RAY_ORDER_MAX_RAYS) return fail(nullptr, ATMO_E_ARG, "atmo_ray_order_scratch_bytes: n_rays must not exceed 2^28");
+    *bytes = atmo::ray_order_scratch_bytes(n_rays);
+    return ATMO_OK;
+}
+
+// The three device entry points of the order share their checks: the element count, then each pointer (null, alignment) in the argument list's order, then
+// the scratch size, all in front of the device -- a host-only context answers the same up to ATMO_E_NO_DEVICE.  They only enqueue on `stream`.
+struct OrderPointer {
+    const void *p;
+    const char *name;
+    unsigned align;
+};
+static int ray_order_checks(AtmoContext *ctx, const std::string &who, uint32_t n, std::initializer_list<OrderPointer> pointers, bool has_scratch,
+                            size_t scratch_bytes) {
+    if (n > atmo::RAY_ORDER_MAX_RAYS) return fail(ctx, ATMO_E_ARG, who + ": at most 2^28 elements");
+    for (const OrderPointer &q : pointers)
+        if (!q.p) return fail(ctx, ATMO_E_ARG, who + ": null " + q.name);
+    for (const OrderPointer &q : pointers)
+        if ((reinterpret_cast<uintptr_t>(q.p) & (q.align - 1u)) != 0)
+            return fail(ctx, ATMO_E_ARG, who + ": " + q.name + " must be " + std::to_string(q.align) + "-byte aligned");
+    if (has_scratch && scratch_bytes < atmo::ray_order_scratch_bytes(n))
+        return fail(ctx, ATMO_E_ARG, who + ": scratch_bytes is below atmo_ray_order_scratch_bytes (" + std::to_string(atmo::ray_order_scratch_bytes(n)) + ")");
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
+    return ATMO_OK;
+}
+
+int atmo_ray_order(AtmoContext *ctx, const AtmoRay *rays_dev, uint32_t n_rays, uint32_t *index_dev, void *scratch_dev, size_t scratch_bytes, void *stream) {
+    const std::string who = "atmo_ray_order";
+    if (!ctx) return ATMO_E_ARG;
+    if (n_rays == 0) return ATMO_OK;   // nothing to order
+    ATMO_TRY(ray_order_checks(ctx, who, n_rays, {{rays_dev, "rays_dev", 16}, {index_dev, "index_dev", 4}, {scratch_dev, "scratch_dev", 16}}, true, scratch_bytes));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, atmo::launch_ray_order(reinterpret_cast<const float4 *>(rays_dev), n_rays, index_dev, scratch_dev, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+int atmo_debug_ray_keys(AtmoContext *ctx, const AtmoRay *rays_dev, uint32_t n_rays, uint32_t *keys_dev, void *stream) {
+    const std::string who = "atmo_debug_ray_keys";
+    if (!ctx) return ATMO_E_ARG;
+    if (n_rays == 0) return ATMO_OK;
+    ATMO_TRY(ray_order_checks(ctx, who, n_rays, {{rays_dev, "rays_dev", 16}, {keys_dev, "keys_dev", 4}}, false, 0));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, atmo::launch_ray_keys(reinterpret_cast<const float4 *>(rays_dev), n_rays, keys_dev, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+int atmo_debug_sort_ray_keys(AtmoContext *ctx, const uint32_t *keys_dev, uint32_t n, uint32_t *index_dev, void *scratch_dev, size_t scratch_bytes,
+                             void *stream) {
+    const std::string who = "atmo_debug_sort_ray_keys";
+    if (!ctx) return ATMO_E_ARG;
+    if (n == 0) return ATMO_OK;
+    ATMO_TRY(ray_order_checks(ctx, who, n, {{keys_dev, "keys_dev", 4}, {index_dev, "index_dev", 4}, {scratch_dev, "scratch_dev", 16}}, true, scratch_bytes));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, atmo::launch_ray_sort(keys_dev, n, index_dev, scratch_dev, (hipStream_t)stream));
+    return ATMO_OK;
 }
 
 int atmo_debug_frame_rays(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, AtmoRay *rays_dev, void *stream) {

@@ -173,7 +173,10 @@ enum KernelFlags : int { KF_CLOUDS = 1, KF_CLOUD_LIGHT_RM = 2, KF_LIGHT_DIRECT =
                                               its own (atmo_render_detail_kernel), for the same reason */,
                           KF_RAYS = 16384 /* caller-supplied rays (atmo_shade_rays, include/atmo_rays.h): no camera prologue -- origin, direction and distance limit come
                                              from an AtmoRay per lane, through RayConsts; the planet centre and the clouds' model-space origin are per-lane operands of
-                                             the marches (their LANE forms); kernels of their own (atmo_shade_rays_kernel), for the same reason */ };
+                                             the marches (their LANE forms); kernels of their own (atmo_shade_rays_kernel), for the same reason */,
+                          KF_INDEX = 32768 /* the ray kernels through an index list (atmo_shade_rays_indexed, include/atmo_ray_order.h): thread k shades ray index[k] of
+                                              the batch, through RayIndexConsts; always with KF_RAYS, kernels of their own (atmo_shade_rays_indexed_kernel), for the
+                                              same reason */ };
 
 // The far-mode draw's proxy (planet_atmosphere.gd:300-321: a BoxMesh of edge box_size centred on the node, rasterised with back-face culling, near / far
 // clipping and Godot 4.3's reverse-Z GREATER_OR_EQUAL depth test).  Pixel (nx, ny) of the existing prologue's NDC: its segment from the near plane (z = 1) to
@@ -228,6 +231,12 @@ struct RayConsts {
     // [host] the march-distance cap of raymarch_cloud (clouds:186-202) up to the ray's own part, smoothstep(md_e0, md_e1, |origin_model|):
     float md_ground, md_space;   // march_distance_ground, march_distance_space (the two values fill_consts mixes into RenderConsts::max_d)
     float md_e0, md_e1;          // clouds_bottom, clouds_top * 1.05
+};
+// An index list over a batch of rays (include/atmo_ray_order.h): what the KF_INDEX kernels read beside RenderConsts and RayConsts.  A kernel argument of its
+// own, behind RayConsts, which stays what it was: the rays, their outputs and their jitter texels stay addressed by the ray's place in the batch.
+struct RayIndexConsts {
+    const uint32_t *index; // n_index entries; thread k shades ray index[k]; an entry >= RayConsts::n is skipped
+    uint32_t n_index;      // entries of this launch (> 0)
 };
 // ... and of the kernel that writes a frame's camera rays (atmo_debug_frame_rays): the rect of rc, row-major
 struct FrameRaysConsts {
@@ -318,6 +327,18 @@ hipError_t launch_shade_rays(int flags, const RenderConsts &rc, const RayConsts 
 // KF_RAYS; the same grid rule; yc.n = 4 n_quads, yc.first = first_quad, yc.width = quads per row of the image, (width + 1) / 2
 bool ray_quads_family_supported(int flags);
 hipError_t launch_shade_ray_quads(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream);
+// the ray draws through an index list (atmo_shade_rays_indexed; include/atmo_ray_order.h): launch_shade_rays' seven kernels once more, the grid over the
+// list's ic.n_index entries; flags WITHOUT KF_RAYS | KF_INDEX, which the launcher adds
+hipError_t launch_shade_rays_indexed(int flags, const RenderConsts &rc, const RayConsts &yc, const RayIndexConsts &ic, hipStream_t stream);
+// the coherence order of a ray queue (atmo_ray_order; include/atmo_ray_order.h states the key): the key kernel, then a stable least-significant-digit radix
+// sort of (key, index) pairs in three 6-bit passes, every buffer in the caller's scratch (ray_order_scratch_bytes(n) bytes, 16-byte aligned), kernels on
+// `stream` only.  launch_ray_sort is the sort alone, on keys that are already there (atmo_debug_sort_ray_keys); n <= RAY_ORDER_MAX_RAYS
+constexpr int RAY_KEY_BITS = 18;                       // == ATMO_RAY_KEY_BITS
+constexpr uint32_t RAY_ORDER_MAX_RAYS = 1u << 28;
+size_t ray_order_scratch_bytes(uint32_t n);
+hipError_t launch_ray_keys(const float4 *rays, uint32_t n, uint32_t *keys, hipStream_t stream);
+hipError_t launch_ray_sort(const uint32_t *keys, uint32_t n, uint32_t *index, void *scratch, hipStream_t stream);
+hipError_t launch_ray_order(const float4 *rays, uint32_t n, uint32_t *index, void *scratch, hipStream_t stream);
 // the camera rays of the rect in rc, as the float kernels' prologue forms them (atmo_debug_frame_rays)
 hipError_t launch_frame_rays(const RenderConsts &rc, const FrameRaysConsts &fc, hipStream_t stream);
 // load_depth's decode over n texels of a caller's array: out[i] = decode(texels[i]) (atmo_debug_decode_depth)

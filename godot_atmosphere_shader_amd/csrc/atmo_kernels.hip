@@ -2209,11 +2209,13 @@ constexpr int RAYS_BLOCK = 256;   // rays (threads) per workgroup of the ray ker
 template <int FLAGS, int LSTEPS, int SPLIT>
 __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int tile_x, const int tile_y, const ProxyConsts *pc = nullptr,
                                             const TargetConsts *tc = nullptr, const DepthConsts *dc = nullptr, const DetailConsts *xc = nullptr,
-                                            const RayConsts *yc = nullptr) {
+                                            const RayConsts *yc = nullptr, const RayIndexConsts *ic = nullptr) {
     constexpr bool DETAIL = (FLAGS & KF_DETAIL) != 0;   // the cloud march with CLOUDS_ALWAYS_LOW_QUALITY off, through *xc
     static_assert(!DETAIL || ((FLAGS & ~(KF_DETAIL | KF_CUBE_LOD | KF_CLOUD_LIGHT_RM | KF_LITE)) == (KF_PRECISE | KF_CLOUDS) && SPLIT == 1),
                   "cloud detail: the LUT-light precise cloud families, float output, one lane per ray");
     constexpr bool RAYS = (FLAGS & KF_RAYS) != 0;   // a ray of the caller's per lane, through *yc
+    constexpr bool INDEXED = (FLAGS & KF_INDEX) != 0;   // ... the ray an index list names, through *ic (atmo_shade_rays_indexed)
+    static_assert(!INDEXED || (RAYS && (FLAGS & KF_CUBE_LOD) == 0), "index lists: the level-0 ray kernels (ray quads have no indexed form)");
     constexpr bool CLOUDS = (FLAGS & KF_CLOUDS) != 0;
     constexpr bool RM = (FLAGS & KF_CLOUD_LIGHT_RM) != 0;
     constexpr bool DIRECT = (FLAGS & KF_LIGHT_DIRECT) != 0;
@@ -2232,7 +2234,7 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     static_assert(!PROXY || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0), "proxy draws: the default forms, one lane per ray, row-major");
     static_assert((FLAGS & KF_VIEWS) == 0 || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0),
                   "multi-view draws: the default forms, one lane per ray, float or packed targets (KF_VIEWS | KF_TARGET: atmo_render_views_target_kernel)");
-    static_assert(!RAYS || ((FLAGS & ~(KF_RAYS | KF_CUBE_LOD | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT | KF_LITE | KF_PRECISE)) == 0 && SPLIT == 1),
+    static_assert(!RAYS || ((FLAGS & ~(KF_RAYS | KF_INDEX | KF_CUBE_LOD | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT | KF_LITE | KF_PRECISE)) == 0 && SPLIT == 1),
                   "ray kernels: the default forms, one lane per ray; the declared sampler (KF_CUBE_LOD) for rays that arrive in quads (atmo_shade_ray_quads)");
     static_assert(!RAYS || (!(DIRECT && CLOUDS) && (PRECISE == (CLOUDS || LITE)) && !(RM && LITE)),
                   "ray kernels: the LUT-light cloud forms in precise mode, no cloud + direct light");
@@ -2282,7 +2284,16 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     // RAYS && LOD (atmo_shade_ray_quads): slot i = 4 q + j of the batch, so a quad is four consecutive lanes with its partners at lane ^ 1 and lane ^ 2, a
     // wave holds 16 whole quads, and n = 4 n_quads never cuts one.  An ABSENT ray (dir = +-0 in every component) leaves here, where a pixel outside the
     // viewport leaves -- behind quad_regs_define, with zeros stored: it reaches no texture call and is missing from every ballot its partners take
-    const uint32_t i = RAYS ? blockIdx.x * (uint32_t)RAYS_BLOCK + threadIdx.x : 0u;
+    // RAYS && INDEXED (atmo_shade_rays_indexed; include/atmo_ray_order.h): thread k of the launch (grid = ceil(n_index / 256) blocks) shades ray i = index[k].
+    // Everything behind this site addresses by i -- the ray, its jitter texel (first + i), its output -- so a ray is shaded as the plain kernel shades it,
+    // wherever the list names it; an entry beyond the batch leaves here (and at the bound below), and nothing is stored for it
+    uint32_t i;
+    if constexpr (RAYS && INDEXED) {
+        const uint32_t k = blockIdx.x * (uint32_t)RAYS_BLOCK + threadIdx.x;
+        if (k >= ic->n_index) return;
+        i = ic->index[k];
+        if (i >= yc->n) return;
+    } else i = RAYS ? blockIdx.x * (uint32_t)RAYS_BLOCK + threadIdx.x : 0u;
     if constexpr (RAYS && LOD) {
         if (i >= yc->n) return;
         const float4 absent_d = yc->rays[2 * (size_t)i + 1];
@@ -3697,8 +3708,8 @@ const char *render_kernel_name(int flags, int light_steps, int split) {
         snprintf(name, sizeof(name), "atmo_render_detail_kernel<%d, %d>", flags, lsteps);
         return name;
     }
-    if (flags & KF_RAYS) {   // atmo_shade_rays_kernel<FLAGS, LSTEPS>
-        snprintf(name, sizeof(name), "atmo_shade_rays_kernel<%d, %d>", flags, lsteps);
+    if (flags & KF_RAYS) {   // atmo_shade_rays_kernel<FLAGS, LSTEPS>; with KF_INDEX atmo_shade_rays_indexed_kernel<FLAGS, LSTEPS>
+        snprintf(name, sizeof(name), (flags & KF_INDEX) ? "atmo_shade_rays_indexed_kernel<%d, %d>" : "atmo_shade_rays_kernel<%d, %d>", flags, lsteps);
         return name;
     }
     if (flags & KF_DEPTH) {   // atmo_render[_views][_proxy]_depth_target_kernel<FLAGS, LSTEPS[, SPLIT]>
@@ -3968,7 +3979,7 @@ hipError_t launch_shade_rays(int flags, const RenderConsts &rc, const RayConsts 
     default: return hipErrorInvalidValue;
     }
 }
-#undef ATMO_RAYS_FAMILIES
+// (ATMO_RAYS_FAMILIES is read once more at the end of this file: the indexed kernels)
 hipError_t launch_frame_rays(const RenderConsts &rc, const FrameRaysConsts &fc, hipStream_t stream) {
     if (fc.depth == nullptr || fc.rays == nullptr || rc.x1 <= rc.x0 || rc.y1 <= rc.y0) return hipErrorInvalidValue;
     const size_t n = (size_t)(rc.x1 - rc.x0) * (size_t)(rc.y1 - rc.y0);
@@ -4006,5 +4017,232 @@ hipError_t launch_shade_ray_quads(int flags, const RenderConsts &rc, const RayCo
     }
 }
 #undef ATMO_RAY_QUADS_FAMILIES
+
+// ---- ray queues: shading through an index list, and the device's coherence order (KF_INDEX; include/atmo_ray_order.h) -----------------------------------------
+// The seven level-0 ray kernels once more, with ONE more site in shade_pixel: where i is formed, thread k of the launch takes i = index[k].  The rays, the
+// outputs and the jitter texels stay addressed by i, so a listed ray receives the bits atmo_shade_rays_kernel gives it, whatever the list's order; what the
+// order changes is which 64 rays share a wavefront.  The list travels in a RayIndexConsts, a kernel argument of its own behind RayConsts.  Kernels of their
+// own name, instantiated here, behind every older kernel, which keep their code and their place in the code object (tools/isa_diff.py).
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(RAYS_BLOCK, render_min_waves(FLAGS & ~(KF_RAYS | KF_INDEX))) void atmo_shade_rays_indexed_kernel(const RenderConsts rc, const RayConsts yc,
+                                                                                                                             const RayIndexConsts ic) {
+    static_assert((FLAGS & KF_RAYS) != 0 && (FLAGS & KF_INDEX) != 0, "indexed ray kernels carry KF_RAYS | KF_INDEX");
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, 0, 0, nullptr, nullptr, nullptr, nullptr, &yc, &ic);
+}
+template <class Kernel>
+static hipError_t launch_rays_indexed(Kernel kernel, const RenderConsts &rc, const RayConsts &yc, const RayIndexConsts &ic, hipStream_t stream) {
+    const unsigned blocks = (unsigned)(((uint64_t)ic.n_index + (RAYS_BLOCK - 1)) / RAYS_BLOCK);   // at most 2^24
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RAYS_BLOCK), 0, stream, rc, yc, ic);
+    return hipGetLastError();
+}
+hipError_t launch_shade_rays_indexed(int flags, const RenderConsts &rc, const RayConsts &yc, const RayIndexConsts &ic, hipStream_t stream) {
+    if (yc.rays == nullptr || yc.out == nullptr || yc.n == 0 || yc.width == 0 || yc.first > 0xffffffffu - (yc.n - 1u) || ic.index == nullptr || ic.n_index == 0)
+        return hipErrorInvalidValue;
+    switch (flags) {
+#define ATMO_RAYS_LAUNCH(F) case (F): return launch_rays_indexed(atmo_shade_rays_indexed_kernel<(F) | KF_RAYS | KF_INDEX, 0>, rc, yc, ic, stream);
+#define ATMO_RAYS_LAUNCH_TWIN(F) case (F): return rc.light_steps == 8 ? launch_rays_indexed(atmo_shade_rays_indexed_kernel<(F) | KF_RAYS | KF_INDEX, 8>, rc, yc, ic, stream) \
+                                                                      : launch_rays_indexed(atmo_shade_rays_indexed_kernel<(F) | KF_RAYS | KF_INDEX, 0>, rc, yc, ic, stream);
+        ATMO_RAYS_FAMILIES(ATMO_RAYS_LAUNCH, ATMO_RAYS_LAUNCH_TWIN)
+#undef ATMO_RAYS_LAUNCH
+#undef ATMO_RAYS_LAUNCH_TWIN
+    default: return hipErrorInvalidValue;
+    }
+}
+#undef ATMO_RAYS_FAMILIES
+
+// The key (include/atmo_ray_order.h, THE KEY, item by item): the direction's cell in a 512 x 512 octahedral map, Morton-interleaved.  Every operation fp32
+// and rounded on its own: no `fp contract` pragma in this function (the file is compiled with -ffp-contract=off), so RN(RN(u * 256) + 256) stays a
+// multiplication and an addition, and the quotients are the IEEE ones.
+__device__ __forceinline__ uint32_t ray_key_spread(uint32_t q) {   // bit b of a 9-bit number to bit 2 b
+    q = (q | (q << 8)) & 0x00ff00ffu;
+    q = (q | (q << 4)) & 0x0f0f0f0fu;
+    q = (q | (q << 2)) & 0x33333333u;
+    return (q | (q << 1)) & 0x55555555u;
+}
+__device__ __forceinline__ uint32_t ray_key_cell(float t) {   // clamp((int)floor(RN(RN(t * 256) + 256)), 0, 511), t in [-1, 1]
+    const int q = (int)floorf(t * 256.0f + 256.0f);
+    return (uint32_t)(q < 0 ? 0 : (q > 511 ? 511 : q));
+}
+__device__ __forceinline__ uint32_t ray_key(float dx, float dy, float dz) {
+    const float s = (fabsf(dx) + fabsf(dy)) + fabsf(dz);
+    if (!(s > 0.0f) || s == __builtin_inff()) return (1u << RAY_KEY_BITS) - 1u;   // an all-zero direction, any NaN, an overflow
+    const float u = ieee_div(dx, s), v = ieee_div(dy, s);
+    float fu = u, fv = v;
+    if ((__float_as_uint(dz) >> 31) != 0u) {   // the lower hemisphere (and dz = -0) folds outwards; both from the unfolded u and v
+        fu = copysignf(1.0f - fabsf(v), u);
+        fv = copysignf(1.0f - fabsf(u), v);
+    }
+    return ray_key_spread(ray_key_cell(fu)) | (ray_key_spread(ray_key_cell(fv)) << 1);
+}
+// one ray per lane; of the AtmoRay it reads the direction half, the 16-byte load the ray kernels take it with
+__global__ __launch_bounds__(256) void atmo_ray_key_kernel(const float4 *__restrict__ rays, uint32_t n, uint32_t *__restrict__ keys) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 d = rays[2 * (size_t)i + 1];
+    keys[i] = ray_key(d.x, d.y, d.z);
+}
+
+// The sort: a least-significant-digit radix sort of (key, index) pairs, three passes of 6 bits, stable in every pass -- the tile order's pattern
+// (atmo_tile_hist_kernel / atmo_tile_scan_kernel / atmo_tile_scatter_kernel) with match_class and lanes_below as they are: a single-wave workgroup owns a
+// contiguous chunk and walks it in order, ballots rank the lanes of one digit inside a step, and the stability comes from the walk.  No position is decided by
+// an atomic, nothing passes from one workgroup to another inside a launch; the kernel boundaries on the stream order histogram, scan and scatter.
+// What is NOT the pattern's is the sizing.  A chunk is RAY_SORT_CHUNK keys whatever n is (2 M rays: 2 025 waves of 16 steps, not 256 waves of 127), the
+// histogram is [digit][chunk] with as many chunks as n needs, and the scan -- one workgroup per digit -- walks its row in trips of RAY_SCAN_TRIP chunks with
+// a carry; the digits' own bases are the exclusive scan of 64 totals, which every scatter wave forms for itself in one lane each.
+// Pass 0 reads plain keys (the index is the position), passes 1 and 2 read the pairs the pass before wrote (8 bytes, one store per element), pass 2 writes
+// the indices alone.  Scratch, in uint32 words: pairs B [0, 2 n), pairs C [2 n, 4 n), histogram [4 n, 4 n + 64 chunks), totals (64).  atmo_ray_order's keys
+// lie in the first n words of C, which pass 1 overwrites when pass 0 has read them.
+constexpr int RAY_SORT_PASSES = 3, RAY_SORT_DIGITS = 1 << ORDER_KEY_BITS;
+static_assert(ORDER_KEY_BITS * RAY_SORT_PASSES == RAY_KEY_BITS && RAY_SORT_DIGITS == 64, "three passes of match_class's six bits; one lane per digit");
+constexpr int RAY_SORT_STEPS = 16;                        // steps of 64 keys a wave walks
+constexpr uint32_t RAY_SORT_CHUNK = 64u * RAY_SORT_STEPS; // keys per chunk (per single-wave workgroup)
+constexpr int RAY_SCAN_BLOCK = 256, RAY_SCAN_PER_THREAD = 4;
+constexpr uint32_t RAY_SCAN_TRIP = (uint32_t)RAY_SCAN_BLOCK * RAY_SCAN_PER_THREAD;   // chunks per trip of the scan
+static uint32_t ray_sort_chunks(uint32_t n) { return (uint32_t)(((uint64_t)n + RAY_SORT_CHUNK - 1u) / RAY_SORT_CHUNK); }
+size_t ray_order_scratch_bytes(uint32_t n) {
+    return 4 * (size_t)n * sizeof(uint32_t) + ((size_t)RAY_SORT_DIGITS * ray_sort_chunks(n) + RAY_SORT_DIGITS) * sizeof(uint32_t);
+}
+
+// PAIRS: `in` holds (key, index) pairs, else plain keys.  hist[digit][chunk] = keys of the chunk with that digit
+template <bool PAIRS>
+__global__ __launch_bounds__(64) void atmo_ray_sort_hist_kernel(const uint32_t *__restrict__ in, uint32_t n, int shift, uint32_t chunks,
+                                                                uint32_t *__restrict__ hist) {
+    __shared__ uint32_t cnt[RAY_SORT_DIGITS];
+    const uint32_t lane = threadIdx.x, i0 = blockIdx.x * RAY_SORT_CHUNK;
+    cnt[lane] = 0;
+    uint32_t key[RAY_SORT_STEPS];
+#pragma unroll
+    for (int t = 0; t < RAY_SORT_STEPS; ++t) {   // every load of the chunk in flight before the walk
+        const uint32_t j = i0 + (uint32_t)t * 64u + lane;
+        key[t] = j < n ? in[PAIRS ? 2u * j : j] : 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < RAY_SORT_STEPS; ++t) {
+        const bool valid = i0 + (uint32_t)t * 64u + lane < n;
+        const uint32_t d = (key[t] >> shift) & (uint32_t)(RAY_SORT_DIGITS - 1);
+        const unsigned long long m = match_class(d, valid);
+        if (valid && lanes_below(m) == 0) cnt[d] += (uint32_t)__builtin_popcountll(m);   // one lane per digit present
+    }
+    __syncthreads();
+    hist[lane * chunks + blockIdx.x] = cnt[lane];
+}
+
+// hist[digit][chunk] -> the chunk's first position INSIDE its digit (exclusive, chunks in order); totals[digit] = keys with that digit.  One workgroup per
+// digit; a row longer than RAY_SCAN_TRIP is walked in trips with a carry
+__global__ __launch_bounds__(RAY_SCAN_BLOCK) void atmo_ray_sort_scan_kernel(uint32_t *__restrict__ hist, uint32_t chunks, uint32_t *__restrict__ totals) {
+    __shared__ uint32_t wave_sum[RAY_SCAN_BLOCK / 64];
+    uint32_t *row = hist + (size_t)blockIdx.x * chunks;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < chunks; base += RAY_SCAN_TRIP) {   // (uniform over the workgroup)
+        const uint32_t j0 = base + threadIdx.x * (uint32_t)RAY_SCAN_PER_THREAD;
+        uint32_t excl[RAY_SCAN_PER_THREAD], sum = 0;
+#pragma unroll
+        for (int k = 0; k < RAY_SCAN_PER_THREAD; ++k) {
+            excl[k] = sum;
+            sum += j0 + (uint32_t)k < chunks ? row[j0 + (uint32_t)k] : 0u;
+        }
+        uint32_t incl = sum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t x = __shfl_up(incl, d);
+            if (lane >= (uint32_t)d) incl += x;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        uint32_t before = carry, all = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < RAY_SCAN_BLOCK / 64; ++w) {
+            const uint32_t s = wave_sum[w];
+            before += w < wave ? s : 0u;
+            all += s;
+        }
+#pragma unroll
+        for (int k = 0; k < RAY_SCAN_PER_THREAD; ++k)
+            if (j0 + (uint32_t)k < chunks) row[j0 + (uint32_t)k] = before + (incl - sum) + excl[k];
+        carry += all;
+        __syncthreads();   // wave_sum is written again in the next trip
+    }
+    if (threadIdx.x == 0) totals[blockIdx.x] = carry;
+}
+
+// The wave writes its chunk, in order, behind base[digit][chunk] + the digit's own base.  LAST: the indices alone (the order), else (key, index) pairs
+template <bool PAIRS, bool LAST>
+__global__ __launch_bounds__(64) void atmo_ray_sort_scatter_kernel(const uint32_t *__restrict__ in, uint32_t n, int shift, uint32_t chunks,
+                                                                   const uint32_t *__restrict__ base, const uint32_t *__restrict__ totals,
+                                                                   uint32_t *__restrict__ out) {
+    __shared__ uint32_t off[RAY_SORT_DIGITS];
+    const uint32_t lane = threadIdx.x, i0 = blockIdx.x * RAY_SORT_CHUNK;
+    {   // digit `lane`: the keys of all smaller digits, then the chunks in front of this one
+        const uint32_t total = totals[lane];
+        uint32_t incl = total;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t x = __shfl_up(incl, d);
+            if (lane >= (uint32_t)d) incl += x;
+        }
+        off[lane] = (incl - total) + base[lane * chunks + blockIdx.x];
+    }
+    uint32_t key[RAY_SORT_STEPS], idx[RAY_SORT_STEPS];
+#pragma unroll
+    for (int t = 0; t < RAY_SORT_STEPS; ++t) {   // every load of the chunk in flight before the walk
+        const uint32_t j = i0 + (uint32_t)t * 64u + lane;
+        if constexpr (PAIRS) {
+            const uint2 p = j < n ? reinterpret_cast<const uint2 *>(in)[j] : make_uint2(0u, 0u);
+            key[t] = p.x;
+            idx[t] = p.y;
+        } else {
+            key[t] = j < n ? in[j] : 0u;
+            idx[t] = j;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < RAY_SORT_STEPS; ++t) {
+        const bool valid = i0 + (uint32_t)t * 64u + lane < n;
+        const uint32_t d = (key[t] >> shift) & (uint32_t)(RAY_SORT_DIGITS - 1);
+        const unsigned long long m = match_class(d, valid);
+        const int r = lanes_below(m);
+        uint32_t pos = 0;
+        if (valid) pos = off[d] + (uint32_t)r;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (valid && r == 0) off[d] += (uint32_t)__builtin_popcountll(m);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (valid && pos < n) {   // (pos < n always holds for a histogram of these keys; the bound keeps a store inside the buffers whatever the scratch held)
+            if constexpr (LAST) out[pos] = idx[t];
+            else reinterpret_cast<uint2 *>(out)[pos] = make_uint2(key[t], idx[t]);
+        }
+    }
+}
+
+hipError_t launch_ray_keys(const float4 *rays, uint32_t n, uint32_t *keys, hipStream_t stream) {
+    if (rays == nullptr || keys == nullptr || n == 0 || n > RAY_ORDER_MAX_RAYS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(atmo_ray_key_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, rays, n, keys);
+    return hipGetLastError();
+}
+hipError_t launch_ray_sort(const uint32_t *keys, uint32_t n, uint32_t *index, void *scratch, hipStream_t stream) {
+    if (keys == nullptr || index == nullptr || scratch == nullptr || n == 0 || n > RAY_ORDER_MAX_RAYS) return hipErrorInvalidValue;
+    const uint32_t chunks = ray_sort_chunks(n);
+    uint32_t *pairs_b = static_cast<uint32_t *>(scratch), *pairs_c = pairs_b + 2 * (size_t)n, *hist = pairs_b + 4 * (size_t)n;
+    uint32_t *totals = hist + (size_t)RAY_SORT_DIGITS * chunks;
+    const dim3 waves(chunks), wave(64), digits(RAY_SORT_DIGITS), scan(RAY_SCAN_BLOCK);
+    hipLaunchKernelGGL(atmo_ray_sort_hist_kernel<false>, waves, wave, 0, stream, keys, n, 0, chunks, hist);
+    hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
+    hipLaunchKernelGGL((atmo_ray_sort_scatter_kernel<false, false>), waves, wave, 0, stream, keys, n, 0, chunks, hist, totals, pairs_b);
+    hipLaunchKernelGGL(atmo_ray_sort_hist_kernel<true>, waves, wave, 0, stream, pairs_b, n, ORDER_KEY_BITS, chunks, hist);
+    hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
+    hipLaunchKernelGGL((atmo_ray_sort_scatter_kernel<true, false>), waves, wave, 0, stream, pairs_b, n, ORDER_KEY_BITS, chunks, hist, totals, pairs_c);
+    hipLaunchKernelGGL(atmo_ray_sort_hist_kernel<true>, waves, wave, 0, stream, pairs_c, n, 2 * ORDER_KEY_BITS, chunks, hist);
+    hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
+    hipLaunchKernelGGL((atmo_ray_sort_scatter_kernel<true, true>), waves, wave, 0, stream, pairs_c, n, 2 * ORDER_KEY_BITS, chunks, hist, totals, index);
+    return hipGetLastError();
+}
+hipError_t launch_ray_order(const float4 *rays, uint32_t n, uint32_t *index, void *scratch, hipStream_t stream) {
+    if (scratch == nullptr) return hipErrorInvalidValue;
+    uint32_t *keys = static_cast<uint32_t *>(scratch) + 2 * (size_t)n;   // the first n words of pairs C: read by pass 0, overwritten by pass 1
+    const hipError_t e = launch_ray_keys(rays, n, keys, stream);
+    return e != hipSuccess ? e : launch_ray_sort(keys, n, index, scratch, stream);
+}
 
 }  // namespace atmo

@@ -680,14 +680,19 @@ class PlanetAtmosphere:
             raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_rays.h); rebuild it")
         return fn
 
-    def shade_rays(self, rays, camera=None, *, width=None, first: int = 0, out=None, stream=None, time: float = 0.0):
+    def shade_rays(self, rays, camera=None, *, width=None, first: int = 0, out=None, stream=None, time: float = 0.0, index=None):
         """Shades caller-supplied rays: what atmosphere_fragment returns for a fragment with each ray (atmo_shade_rays; include/atmo_rays.h states the
         arithmetic).  `rays`: a contiguous CUDA float32 tensor of shape (n, 8), one N.AtmoRay a row -- origin xyz, tmax (the distance to the first
         opaque hit, FLT_MAX for none), dir xyz (unit length, used as given), one unused float.  `camera` supplies inv_view, the map from ray space
         to world space; None: ray space is world space.  Ray i is image index first + i of an image `width` wide (default: n), which picks its
         blue-noise jitter.  Returns or fills `out`, a contiguous CUDA float32 (n, 4) tensor: ALBEDO.rgb and ALPHA per ray, zeros for a ray that misses
-        the atmosphere.  The coverage cubemap is sampled at level 0."""
+        the atmosphere.  The coverage cubemap is sampled at level 0.
+        `index` (a contiguous CUDA int32 (m,) tensor, `ray_order`'s or any list of ray numbers): the rays it names are shaded, 64 consecutive entries a
+        wavefront, each to its own row of `out` with the bits the plain call gives it (atmo_shade_rays_indexed; include/atmo_ray_order.h); rows it does
+        not name are left as they are -- zeros where `out` is created here."""
         n = _check_rays(rays, "rays", 8)
+        if index is not None:
+            _check_index(index)
         try:
             width, first = max(n, 1) if width is None else operator.index(width), operator.index(first)
         except TypeError:
@@ -697,15 +702,50 @@ class PlanetAtmosphere:
         if out is None:
             import torch
 
-            out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+            out = (torch.empty if index is None else torch.zeros)((n, 4), dtype=torch.float32, device=rays.device)
         elif _check_rays(out, "out", 4) != n:
             raise ValueError("out must have one row per ray: shape (n, 4)")
-        fn = self._rays_entry("atmo_shade_rays")
+        fn = self._rays_entry("atmo_shade_rays") if index is None else self._ray_order_entry("atmo_shade_rays_indexed")
         stream = _stream_handle(stream, rays)
         self._bake_if_needed(stream)
         nf = _to_native_frame(self.make_frame(camera if camera is not None else _WORLD_RAY_SPACE, time))
-        N.check(self._ctx, fn(self._ctx, C.byref(nf), C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr()), n, width, first, C.c_void_p(stream or 0)))
+        listed = () if index is None else (C.c_void_p(index.data_ptr()), int(index.shape[0]))
+        N.check(self._ctx, fn(self._ctx, C.byref(nf), C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr()), n, width, first, *listed,
+                              C.c_void_p(stream or 0)))
         return out
+
+    # ---- coherent ray queues (include/atmo_ray_order.h) ---------------------------------------------------------------------------
+    def _ray_order_entry(self, name: str):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_ray_order.h); rebuild it")
+        return fn
+
+    def ray_order(self, rays, stream=None):
+        """The coherence order of a ray queue, computed on the device (atmo_ray_order; include/atmo_ray_order.h states the key): a CUDA int32 (n,) tensor,
+        the stable ascending sort of the rays' numbers by the octahedral cell of their directions -- godot_atmosphere_shader_amd.ray_order.ray_order is
+        the same permutation in numpy.  `rays` as `shade_rays`'; hand the result to `shade_rays(index=...)`.  The scratch comes from torch's allocator."""
+        import torch
+
+        n = _check_rays(rays, "rays", 8)
+        if n > 1 << 28:
+            raise ValueError("at most 2^28 rays")
+        order = torch.empty((n,), dtype=torch.int32, device=rays.device)
+        if n == 0:
+            return order
+        fn, size = self._ray_order_entry("atmo_ray_order"), self._ray_order_entry("atmo_ray_order_scratch_bytes")
+        need = C.c_size_t(0)
+        N.check(self._ctx, size(n, C.byref(need)))
+        handle = _stream_handle(stream, rays)
+        words = (need.value + 15) // 16 * 4
+        if stream is None:   # torch's current stream: the allocator reuses the scratch behind the sort, in stream order
+            scratch = torch.empty((words,), dtype=torch.int32, device=rays.device)
+        else:                # ... and so it does on the caller's stream, when the scratch is allocated there
+            with torch.cuda.stream(torch.cuda.ExternalStream(handle, device=rays.device)):
+                scratch = torch.empty((words,), dtype=torch.int32, device=rays.device)
+        N.check(self._ctx, fn(self._ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(order.data_ptr()), C.c_void_p(scratch.data_ptr()), need.value,
+                              C.c_void_p(handle or 0)))
+        return order
 
     def camera_rays(self, camera, depth, rect=None, stream=None):
         """The rays the library's own prologue forms for `rect` (default: the whole viewport) of the camera's viewport, row-major: a CUDA float32
@@ -1074,6 +1114,17 @@ def _check_rays(t, what: str, cols: int) -> int:
         raise TypeError(f"{what} must be a contiguous CUDA float32 tensor")
     if t.dim() != 2 or t.shape[1] != cols:
         raise ValueError(f"{what} must have shape (n, {cols})")
+    return int(t.shape[0])
+
+
+def _check_index(t) -> int:
+    """`index` is a contiguous CUDA int32 tensor of shape (m,): TypeError for its kind, ValueError for its shape.  Returns m."""
+    import torch
+
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise TypeError("index must be a contiguous CUDA int32 tensor")
+    if t.dim() != 1:
+        raise ValueError("index must have shape (m,)")
     return int(t.shape[0])
 
 

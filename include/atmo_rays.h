@@ -36,7 +36,7 @@
  * direct light march; the v1 variants with and without clouds; precise cloud and v1 arithmetic (atmo_set_precision 1, their default), up to 32 view
  * steps, one lane per ray, cloud detail off.  atmo_kernel_name reports atmo_shade_rays_kernel<FLAGS | 16384, LSTEPS>.  64 consecutive rays share a
  * wavefront: a batch whose neighbouring rays are neighbours in space marches in step; a shuffled queue gives the same values, slower
- * (profiles/rays/README.md has both).
+ * (profiles/rays/README.md has both) -- atmo_ray_order.h orders such a queue on the device and shades it through the order, in place.
  */
 #ifndef ATMO_RAYS_H
 #define ATMO_RAYS_H

@@ -21,7 +21,20 @@ timing, every round in the order render, quads, rays, render2:
   quads     atmo_shade_ray_quads on camera_ray_quads(frame), width = 1920;
   rays      the level-0 atmo_shade_rays of the same frame's rays, for scale (another picture: level 0);
   render2   render again.
-`bits_equal_render`: the quads' picture, put back into rows, is the render arm's."""
+`bits_equal_render`: the quads' picture, put back into rows, is the render arm's.
+
+The ORDER table (--table order; include/atmo_ray_order.h), all seven families under the level-0 sampler, same frame, same timing, every round in the order
+rays, shuffled, order, indexed, indexed_id, order_indexed:
+  rays           the frame's order, plain (width = 1920);
+  shuffled       the fixed permutation, plain (width = n): the queue the order is for;
+  order          atmo_ray_order alone on the shuffled queue, scratch and index allocated once;
+  indexed        atmo_shade_rays_indexed on the shuffled queue through the device's order;
+  indexed_id     the coherent queue through the identity: what the indirection costs by itself;
+  order_indexed  order, then indexed, back to back in one timed call: the sum as a queue's owner pays it.
+The plain arms run the parent commit's instructions (tools/isa_diff.py is the proof), so no second library is needed.  `bits_equal`, per arm: rays -- the
+render frame's; shuffled -- its own second run's; order -- ray_order.ray_order of the same rays in numpy; indexed and order_indexed -- the shuffled arm's;
+indexed_id -- the rays arm's.  `order_plus_indexed_ms` is the sum of the two medians, `below_shuffled_range` whether it and the order_indexed median lie
+below the MINIMUM of the shuffled arm's rounds."""
 import argparse
 import json
 import os
@@ -50,6 +63,100 @@ W, H = 1920, 1080
 ARMS = ("render", "rays", "shuffled", "render2")
 QUAD_FAMILIES = ("clouds_high", "clouds_high_rm", "v1_clouds")
 QUAD_ARMS = ("render", "quads", "rays", "render2")
+ORDER_ARMS = ("rays", "shuffled", "order", "indexed", "indexed_id", "order_indexed")
+
+
+def order_rows(args, tex, cam, depth, frame, out, perm):
+    """The ORDER table's rows (the module's docstring)."""
+    import ctypes as C
+
+    import numpy as np
+
+    from godot_atmosphere_shader_amd import _native as N
+    from godot_atmosphere_shader_amd import ray_order as R
+
+    n = H * W
+    rows = []
+    identity = torch.arange(n, dtype=torch.int32, device="cuda")
+    out2 = torch.empty_like(out)
+    for label in args.families.split(","):
+        config, kw = FAMILIES[label]
+        node = make_node(config, tex, cubemap_lod=False, tile_feedback=0, **kw)   # atmo_set_sampler_lod 0, atmo_set_tile_feedback 0
+        try:
+            rays = node.camera_rays(cam, depth)
+            shuffled = rays[perm].contiguous()
+            need = C.c_size_t()
+            N.check(node._ctx, node._lib.atmo_ray_order_scratch_bytes(n, C.byref(need)))
+            scratch = torch.empty(((need.value + 3) // 4,), dtype=torch.int32, device="cuda")
+            index = torch.empty((n,), dtype=torch.int32, device="cuda")
+            stream = torch.cuda.current_stream().cuda_stream
+
+            def order():
+                N.check(node._ctx, node._lib.atmo_ray_order(node._ctx, shuffled.data_ptr(), n, index.data_ptr(), scratch.data_ptr(), need.value, stream))
+
+            def indexed():
+                node.shade_rays(shuffled, cam, out=out2, index=index)
+
+            def both():
+                order()
+                indexed()
+
+            calls = {"rays": lambda: node.shade_rays(rays, cam, width=W, out=out), "shuffled": lambda: node.shade_rays(shuffled, cam, out=out),
+                     "order": order, "indexed": indexed, "indexed_id": lambda: node.shade_rays(rays, cam, width=W, out=out2, index=identity),
+                     "order_indexed": both}
+            names = {}
+            for arm in ORDER_ARMS:
+                timed(calls[arm], args.warmup)
+                names[arm] = node.kernel_name
+            # the pictures, outside the timing
+            bits = lambda t: t.view(torch.int32)   # noqa: E731
+            equal = {}
+            node.render(cam, depth, out=frame)
+            calls["rays"]()
+            plain = out.clone()
+            equal["rays"] = bool(torch.equal(bits(frame.reshape(-1, 4)), bits(plain)))
+            calls["shuffled"]()
+            plain_shuffled = out.clone()
+            calls["shuffled"]()
+            equal["shuffled"] = bool(torch.equal(bits(out), bits(plain_shuffled)))
+            index.fill_(-1)
+            order()
+            torch.cuda.synchronize()
+            equal["order"] = bool(np.array_equal(index.cpu().numpy().astype(np.int64), R.ray_order(shuffled.cpu().numpy())))
+            out2.fill_(float("nan"))
+            indexed()
+            equal["indexed"] = bool(torch.equal(bits(out2), bits(plain_shuffled)))
+            out2.fill_(float("nan"))
+            calls["indexed_id"]()
+            equal["indexed_id"] = bool(torch.equal(bits(out2), bits(plain)))
+            out2.fill_(float("nan"))
+            index.fill_(-1)
+            both()
+            equal["order_indexed"] = bool(torch.equal(bits(out2), bits(plain_shuffled)))
+            t_warm = time.perf_counter()
+            while time.perf_counter() - t_warm < 0.025:   # sustained clocks
+                calls["rays"]()
+                torch.cuda.synchronize()
+            arms = {a: [] for a in ORDER_ARMS}
+            for _ in range(args.rounds):
+                for arm in ORDER_ARMS:
+                    arms[arm].append(timed(calls[arm], args.reps))
+        finally:
+            node.close()
+        med = {a: sorted(v)[len(v) // 2] for a, v in arms.items()}
+        total = med["order"] + med["indexed"]
+        row = {"family": label, "kernels": names, "bits_equal": equal,
+               "ms": {a: {"median": med[a], "min": min(v), "max": max(v)} for a, v in arms.items()},
+               "shuffled_over_rays": med["shuffled"] / med["rays"], "indexed_over_rays": med["indexed"] / med["rays"],
+               "indexed_id_over_rays": med["indexed_id"] / med["rays"], "order_plus_indexed_ms": total,
+               "order_plus_indexed_over_shuffled": total / med["shuffled"], "order_indexed_over_shuffled": med["order_indexed"] / med["shuffled"],
+               "below_shuffled_range": bool(total < min(arms["shuffled"]) and med["order_indexed"] < min(arms["shuffled"]))}
+        rows.append(row)
+        print(f"{label:15s} rays {med['rays']:.4f}  shuffled {med['shuffled']:.4f} ({min(arms['shuffled']):.4f} - {max(arms['shuffled']):.4f})  order "
+              f"{med['order']:.4f}  indexed {med['indexed']:.4f}  indexed_id {med['indexed_id']:.4f}  order + indexed {total:.4f} (one call: "
+              f"{med['order_indexed']:.4f}) ms = {row['order_plus_indexed_over_shuffled']:.3f} x shuffled  below its range: {row['below_shuffled_range']}  "
+              f"bits equal: {equal}  {names['indexed']}", file=sys.stderr, flush=True)
+    return rows
 
 
 def timed(call, reps):
@@ -69,7 +176,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--families", default=",".join(FAMILIES))
-    ap.add_argument("--table", choices=("rays", "quads", "both"), default="both")
+    ap.add_argument("--table", choices=("rays", "quads", "both", "order"), default="both")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rays_probe.py measures on a device; none is visible")
@@ -80,7 +187,9 @@ def main():
     out = torch.empty((H * W, 4), dtype=torch.float32, device="cuda")
     perm = torch.randperm(H * W, generator=torch.Generator().manual_seed(1)).cuda()
     result = {"viewport": [W, H], "pose": "P_space", "reps": args.reps, "rounds": args.rounds, "device": torch.cuda.get_device_name(0), "rows": []}
-    for label in args.families.split(",") if args.table != "quads" else ():
+    if args.table == "order":
+        result["order_rows"] = order_rows(args, tex, cam, depth, frame, out, perm)
+    for label in args.families.split(",") if args.table in ("rays", "both") else ():
         config, kw = FAMILIES[label]
         node = make_node(config, tex, cubemap_lod=False, tile_feedback=0, **kw)   # atmo_set_sampler_lod 0, atmo_set_tile_feedback 0
         try:
@@ -116,7 +225,7 @@ def main():
         print(f"{label:15s} render {med['render']:.4f} ms  rays {med['rays']:.4f} ms ({row['rays_over_render']:.3f} x)  shuffled {med['shuffled']:.4f} ms "
               f"({row['shuffled_over_rays']:.3f} x rays)  render again {med['render2']:.4f} ms ({row['render2_over_render']:.3f} x)  bits equal: {same}  "
               f"{names['render']} / {names['rays']}", file=sys.stderr, flush=True)
-    if args.table != "rays":
+    if args.table in ("quads", "both"):
         from godot_atmosphere_shader_amd.ray_quads import quads_to_image
 
         result["quad_rows"] = []
