@@ -81,6 +81,11 @@ RAY_QUADS_SYMBOLS = ("atmo_shade_ray_quads",)
 # shade_rays(index=...) raise without).
 RAY_ORDER_SYMBOLS = ("atmo_ray_order_scratch_bytes", "atmo_ray_order", "atmo_shade_rays_indexed", "atmo_debug_ray_keys", "atmo_debug_sort_ray_keys")
 RAY_KEY_BITS = 18   # ATMO_RAY_KEY_BITS
+# every symbol include/atmo_ray_list.h declares: index lists built on the device for a queue whose length is a device word, with the sure-miss cull.  The
+# RAYS_SYMBOLS rule: the ABI version stays 5, the tuple stands beside EXPORTED_SYMBOLS, load() binds it where the library has it
+# (PlanetAtmosphere.ray_list raises without).
+RAY_LIST_SYMBOLS = ("atmo_ray_list_scratch_bytes", "atmo_ray_list", "atmo_debug_ray_cull_constants")
+RAY_LIST_ORDER, RAY_LIST_CULL, RAY_LIST_END = 1, 2, 0xFFFFFFFF   # ATMO_RAY_LIST_ORDER, ATMO_RAY_LIST_CULL, ATMO_RAY_LIST_END
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -343,6 +348,18 @@ def load() -> C.CDLL:
     }
     assert tuple(ray_order_sig) == RAY_ORDER_SYMBOLS
     for name, (res, args) in ray_order_sig.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
+    # include/atmo_ray_list.h: the same rule
+    ray_list_sig = {
+        "atmo_ray_list_scratch_bytes": (ip, [C.c_uint32, C.POINTER(C.c_size_t)]),
+        "atmo_ray_list": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, ip, vp, vp, vp, vp, C.c_size_t, vp]),
+        "atmo_debug_ray_cull_constants": (ip, [vp, C.POINTER(AtmoFrame), fp, ip, C.POINTER(ip)]),
+    }
+    assert tuple(ray_list_sig) == RAY_LIST_SYMBOLS
+    for name, (res, args) in ray_list_sig.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype = res

@@ -20,6 +20,7 @@
 #include "../../include/atmo_rays.h"
 #include "../../include/atmo_ray_quads.h"
 #include "../../include/atmo_ray_order.h"
+#include "../../include/atmo_ray_list.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -2453,6 +2454,69 @@ int atmo_debug_sort_ray_keys(AtmoContext *ctx, const uint32_t *keys_dev, uint32_
     ATMO_TRY(ray_order_checks(ctx, who, n, {{keys_dev, "keys_dev", 4}, {index_dev, "index_dev", 4}, {scratch_dev, "scratch_dev", 16}}, true, scratch_bytes));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, atmo::launch_ray_sort(keys_dev, n, index_dev, scratch_dev, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+// ---- ray lists: counted queues and the sure-miss cull (include/atmo_ray_list.h) ---------------------------------------------------------------------------
+static_assert(ATMO_RAY_LIST_ORDER == atmo::RAY_LIST_ORDER && ATMO_RAY_LIST_CULL == atmo::RAY_LIST_CULL && ATMO_RAY_LIST_END == atmo::RAY_LIST_END,
+              "the header's flags and end mark are the kernels'");
+// THE CULL's constants: the centre and the squared shell radius as every draw forms them (draw_frame, fill_consts), and the far bound's one product
+static atmo::RayCullConsts ray_cull_consts(const AtmoContext *ctx, const AtmoFrame *frame) {
+    AtmoFrame fixed;
+    atmo::RenderConsts rc;
+    fill_consts(ctx, draw_frame(ctx, frame, fixed), nullptr, nullptr, rc);
+    atmo::RayCullConsts k;
+    k.cx = rc.center[0]; k.cy = rc.center[1]; k.cz = rc.center[2];
+    k.r2 = rc.atmosphere_radius2;
+    k.r2_far = rc.atmosphere_radius2 * 1.02f;
+    return k;
+}
+
+int atmo_ray_list_scratch_bytes(uint32_t capacity, size_t *bytes) {
+    if (!bytes) return fail(nullptr, ATMO_E_ARG, "atmo_ray_list_scratch_bytes: null bytes");
+    if (capacity > atmo::RAY_ORDER_MAX_RAYS) return fail(nullptr, ATMO_E_ARG, "atmo_ray_list_scratch_bytes: capacity must not exceed 2^28");
+    *bytes = atmo::ray_list_scratch_bytes(capacity);
+    return ATMO_OK;
+}
+
+// Every check stands in front of hipSetDevice, in the header's order.  The call enqueues and nothing else: *count_dev is the kernels' to read
+int atmo_ray_list(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, const uint32_t *count_dev, uint32_t capacity, int flags, float *rgba_dev,
+                  uint32_t *index_dev, uint32_t *listed_dev, void *scratch_dev, size_t scratch_bytes, void *stream) {
+    const std::string who = "atmo_ray_list";
+    if (!ctx) return ATMO_E_ARG;
+    if (capacity == 0) return ATMO_OK;   // nothing to list
+    if (capacity > atmo::RAY_ORDER_MAX_RAYS) return fail(ctx, ATMO_E_ARG, who + ": at most 2^28 rays");
+    if (flags & ~(ATMO_RAY_LIST_ORDER | ATMO_RAY_LIST_CULL)) return fail(ctx, ATMO_E_ARG, who + ": unknown flag bits");
+    if (!rays_dev) return fail(ctx, ATMO_E_ARG, who + ": null rays_dev");
+    if (!index_dev) return fail(ctx, ATMO_E_ARG, who + ": null index_dev");
+    if (!scratch_dev) return fail(ctx, ATMO_E_ARG, who + ": null scratch_dev");
+    const bool cull = (flags & ATMO_RAY_LIST_CULL) != 0;
+    if (cull && !frame) return fail(ctx, ATMO_E_ARG, who + ": ATMO_RAY_LIST_CULL needs a frame");
+    if (cull && !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": ATMO_RAY_LIST_CULL needs rgba_dev");
+    auto misaligned = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0; };
+    if (misaligned(rays_dev, 16)) return fail(ctx, ATMO_E_ARG, who + ": rays_dev must be 16-byte aligned");
+    if (misaligned(rgba_dev, 16)) return fail(ctx, ATMO_E_ARG, who + ": rgba_dev must be 16-byte aligned");
+    if (misaligned(scratch_dev, 16)) return fail(ctx, ATMO_E_ARG, who + ": scratch_dev must be 16-byte aligned");
+    if (misaligned(index_dev, 4)) return fail(ctx, ATMO_E_ARG, who + ": index_dev must be 4-byte aligned");
+    if (misaligned(count_dev, 4)) return fail(ctx, ATMO_E_ARG, who + ": count_dev must be 4-byte aligned");
+    if (misaligned(listed_dev, 4)) return fail(ctx, ATMO_E_ARG, who + ": listed_dev must be 4-byte aligned");
+    if (scratch_bytes < atmo::ray_list_scratch_bytes(capacity))
+        return fail(ctx, ATMO_E_ARG, who + ": scratch_bytes is below atmo_ray_list_scratch_bytes (" + std::to_string(atmo::ray_list_scratch_bytes(capacity)) + ")");
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const atmo::RayCullConsts k = cull ? ray_cull_consts(ctx, frame) : atmo::RayCullConsts{};
+    HIP_TRY(ctx, atmo::launch_ray_list(reinterpret_cast<const float4 *>(rays_dev), count_dev, capacity, flags, k, reinterpret_cast<float4 *>(rgba_dev), index_dev,
+                                       listed_dev, scratch_dev, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+int atmo_debug_ray_cull_constants(AtmoContext *ctx, const AtmoFrame *frame, float *out, int capacity, int *count) {
+    if (!ctx) return ATMO_E_ARG;
+    if (!frame || !out || !count) return fail(ctx, ATMO_E_ARG, "atmo_debug_ray_cull_constants: null argument");
+    if (capacity < 5) return fail(ctx, ATMO_E_ARG, "atmo_debug_ray_cull_constants: capacity below 5");
+    const atmo::RayCullConsts k = ray_cull_consts(ctx, frame);
+    out[0] = k.cx; out[1] = k.cy; out[2] = k.cz; out[3] = k.r2; out[4] = k.r2_far;
+    *count = 5;
     return ATMO_OK;
 }
 

@@ -339,6 +339,19 @@ size_t ray_order_scratch_bytes(uint32_t n);
 hipError_t launch_ray_keys(const float4 *rays, uint32_t n, uint32_t *keys, hipStream_t stream);
 hipError_t launch_ray_sort(const uint32_t *keys, uint32_t n, uint32_t *index, void *scratch, hipStream_t stream);
 hipError_t launch_ray_order(const float4 *rays, uint32_t n, uint32_t *index, void *scratch, hipStream_t stream);
+// a ray list (atmo_ray_list; include/atmo_ray_list.h): the order's passes in COUNTED form -- the bound of every kernel is a device word, *count clamped to
+// capacity, then the live total the first scatter leaves in the scratch -- with the sure-miss cull in the key kernel and a tail fill behind the last pass.
+// Kernels of their own beside the order's (which stay what they are); the scan is the order's.  ray_list_scratch_bytes(capacity) bytes, 16-byte aligned
+constexpr int RAY_LIST_ORDER = 1, RAY_LIST_CULL = 2;   // == ATMO_RAY_LIST_ORDER, ATMO_RAY_LIST_CULL
+constexpr uint32_t RAY_LIST_END = 0xFFFFFFFFu;         // == ATMO_RAY_LIST_END
+// THE CULL's constants: a kernel argument of the list's key kernel alone
+struct RayCullConsts {
+    float cx, cy, cz;   // the view-space centre, RenderConsts::center
+    float r2, r2_far;   // RenderConsts::atmosphere_radius2 and RN(r2 * 1.02f)
+};
+size_t ray_list_scratch_bytes(uint32_t capacity);
+hipError_t launch_ray_list(const float4 *rays, const uint32_t *count, uint32_t capacity, int flags, const RayCullConsts &cull, float4 *rgba, uint32_t *index,
+                           uint32_t *listed, void *scratch, hipStream_t stream);
 // the camera rays of the rect in rc, as the float kernels' prologue forms them (atmo_debug_frame_rays)
 hipError_t launch_frame_rays(const RenderConsts &rc, const FrameRaysConsts &fc, hipStream_t stream);
 // load_depth's decode over n texels of a caller's array: out[i] = decode(texels[i]) (atmo_debug_decode_depth)

@@ -4245,4 +4245,177 @@ hipError_t launch_ray_order(const float4 *rays, uint32_t n, uint32_t *index, voi
     return e != hipSuccess ? e : launch_ray_sort(keys, n, index, scratch, stream);
 }
 
+// ---- ray lists: counted queues and the sure-miss cull (include/atmo_ray_list.h) --------------------------------------------------------------------------------
+// The order's passes once more, in COUNTED form: what bounds a kernel is a device word -- the caller's *count clamped to the capacity in front of the first
+// scatter, the live total m that scatter leaves in the scratch behind it -- so the host never learns a length and a captured graph serves every one.  The
+// grids are the capacity's; a wave whose chunk lies beyond the bound writes its zero histogram column and leaves.  Kernels of their own names, behind every
+// older kernel, which keep their code and their place in the code object (tools/isa_diff.py); the scan is the order's, over ray_sort_chunks(capacity) rows.
+// Scratch: the order's for `capacity` elements, then the word m (ray_list_scratch_bytes).
+
+// THE CULL (include/atmo_ray_list.h, item by item).  Every operation fp32 and rounded on its own: no `fp contract` pragma in this function (the file is
+// compiled with -ffp-contract=off), as ray_key.  Why "true" implies that shade_pixel's RAYS mode stores zeros for the ray: its rs_atmo.x == rs_atmo.y branch
+// is taken when ray_sphere misses, h = R2 - |oc - b d|^2 < 0 with oc = -c', and in exact arithmetic |oc - b d|^2 = cc - b^2 (2 - dd), so the ray misses iff
+// b^2 (2 - dd) < cc - R2.  cc >= 1.02 R2 bounds the cancellation in e = cc - R2 to a relative error of about 1e-5 (a few ulps of cc, which is at most 51 e);
+// the right-hand side shrunk by 0.2 % is two orders of magnitude above that and above the kernels' own rounding of h (a few ulps of cc against |h| >= 0.002 e).
+// Rays from inside the shell or within 1 % of it and directions far from unit length are kept, and so is every ray with a NaN: a false comparison keeps.
+// This is NOT sphere_setup / hit_radius shared through a helper: the shading kernels keep their own code (NOTES.md, "Caller-supplied rays").
+__device__ __forceinline__ bool ray_surely_misses(const RayCullConsts &k, float4 o, float4 d) {
+    const float cx = k.cx - o.x, cy = k.cy - o.y, cz = k.cz - o.z;
+    const float cc = cx * cx + cy * cy + cz * cz;
+    const float b = cx * d.x + cy * d.y + cz * d.z;
+    const float dd = d.x * d.x + d.y * d.y + d.z * d.z;
+    const float g = (b * b) * (2.0f - dd);
+    const float e = cc - k.r2;
+    return cc >= k.r2_far && dd >= 0.25f && dd <= 1.75f && g < e * 0.998f;
+}
+constexpr uint32_t RAY_LIST_DEAD = 1u << 31;   // a culled ray's key: no pass lists it
+__device__ __forceinline__ uint32_t ray_list_bound(const uint32_t *bound, uint32_t capacity) {   // min(*bound, capacity); no word: the capacity
+    if (bound == nullptr) return capacity;
+    const uint32_t n = *bound;
+    return n < capacity ? n : capacity;
+}
+// one ray per lane, rays i < n only: keys[i] = THE KEY under RAY_LIST_ORDER, else 0; a ray RAY_LIST_CULL removes is marked dead and receives its zeros here
+__global__ __launch_bounds__(256) void atmo_ray_list_key_kernel(const float4 *__restrict__ rays, const uint32_t *__restrict__ count, uint32_t capacity,
+                                                                int flags, const RayCullConsts cull, uint32_t *__restrict__ keys,
+                                                                float4 *__restrict__ rgba) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= ray_list_bound(count, capacity)) return;
+    uint32_t key = 0u;
+    if (flags != 0) {
+        const float4 d = rays[2 * (size_t)i + 1];
+        if (flags & RAY_LIST_ORDER) key = ray_key(d.x, d.y, d.z);
+        if (flags & RAY_LIST_CULL) {
+            if (ray_surely_misses(cull, rays[2 * (size_t)i], d)) {
+                key |= RAY_LIST_DEAD;
+                rgba[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+        }
+    }
+    keys[i] = key;
+}
+
+// atmo_ray_sort_hist_kernel bounded by a device word.  DEAD: elements with RAY_LIST_DEAD set do not count (pass 0; the later passes never see one)
+template <bool PAIRS, bool DEAD>
+__global__ __launch_bounds__(64) void atmo_ray_list_hist_kernel(const uint32_t *__restrict__ in, const uint32_t *__restrict__ bound, uint32_t capacity,
+                                                                int shift, uint32_t chunks, uint32_t *__restrict__ hist) {
+    __shared__ uint32_t cnt[RAY_SORT_DIGITS];
+    const uint32_t lane = threadIdx.x, i0 = blockIdx.x * RAY_SORT_CHUNK;
+    const uint32_t n = ray_list_bound(bound, capacity);
+    if (i0 >= n) {   // (uniform: the wave is the workgroup)
+        hist[lane * chunks + blockIdx.x] = 0u;
+        return;
+    }
+    cnt[lane] = 0;
+    uint32_t key[RAY_SORT_STEPS];
+#pragma unroll
+    for (int t = 0; t < RAY_SORT_STEPS; ++t) {
+        const uint32_t j = i0 + (uint32_t)t * 64u + lane;
+        key[t] = j < n ? in[PAIRS ? 2u * j : j] : 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < RAY_SORT_STEPS; ++t) {
+        const bool valid = i0 + (uint32_t)t * 64u + lane < n && !(DEAD && (key[t] & RAY_LIST_DEAD) != 0u);
+        const uint32_t d = (key[t] >> shift) & (uint32_t)(RAY_SORT_DIGITS - 1);
+        const unsigned long long m = match_class(d, valid);
+        if (valid && lanes_below(m) == 0) cnt[d] += (uint32_t)__builtin_popcountll(m);
+    }
+    __syncthreads();
+    hist[lane * chunks + blockIdx.x] = cnt[lane];
+}
+
+// atmo_ray_sort_scatter_kernel bounded by a device word; a store lands inside the capacity whatever the scratch held.  total_out (pass 0, else null): the
+// live total -- the sum of the 64 digit totals, which every wave forms -- leaves through the first wave's last lane, a plain vector store
+template <bool PAIRS, bool LAST, bool DEAD>
+__global__ __launch_bounds__(64) void atmo_ray_list_scatter_kernel(const uint32_t *__restrict__ in, const uint32_t *__restrict__ bound, uint32_t capacity,
+                                                                   int shift, uint32_t chunks, const uint32_t *__restrict__ base,
+                                                                   const uint32_t *__restrict__ totals, uint32_t *__restrict__ out,
+                                                                   uint32_t *__restrict__ total_out) {
+    __shared__ uint32_t off[RAY_SORT_DIGITS];
+    const uint32_t lane = threadIdx.x, i0 = blockIdx.x * RAY_SORT_CHUNK;
+    const uint32_t n = ray_list_bound(bound, capacity);
+    {
+        const uint32_t total = totals[lane];
+        uint32_t incl = total;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t x = __shfl_up(incl, d);
+            if (lane >= (uint32_t)d) incl += x;
+        }
+        if (total_out != nullptr && blockIdx.x == 0 && lane == 63u) *total_out = incl;
+        if (i0 >= n) return;   // (uniform)
+        off[lane] = (incl - total) + base[lane * chunks + blockIdx.x];
+    }
+    uint32_t key[RAY_SORT_STEPS], idx[RAY_SORT_STEPS];
+#pragma unroll
+    for (int t = 0; t < RAY_SORT_STEPS; ++t) {
+        const uint32_t j = i0 + (uint32_t)t * 64u + lane;
+        if constexpr (PAIRS) {
+            const uint2 p = j < n ? reinterpret_cast<const uint2 *>(in)[j] : make_uint2(0u, 0u);
+            key[t] = p.x;
+            idx[t] = p.y;
+        } else {
+            key[t] = j < n ? in[j] : 0u;
+            idx[t] = j;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < RAY_SORT_STEPS; ++t) {
+        const bool valid = i0 + (uint32_t)t * 64u + lane < n && !(DEAD && (key[t] & RAY_LIST_DEAD) != 0u);
+        const uint32_t d = (key[t] >> shift) & (uint32_t)(RAY_SORT_DIGITS - 1);
+        const unsigned long long m = match_class(d, valid);
+        const int r = lanes_below(m);
+        uint32_t pos = 0;
+        if (valid) pos = off[d] + (uint32_t)r;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (valid && r == 0) off[d] += (uint32_t)__builtin_popcountll(m);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (valid && pos < capacity) {
+            if constexpr (LAST) out[pos] = idx[t];
+            else reinterpret_cast<uint2 *>(out)[pos] = make_uint2(key[t], idx[t]);
+        }
+    }
+}
+
+// index[m .. capacity) = RAY_LIST_END and *listed = m (where there is a word), m the live total
+__global__ __launch_bounds__(256) void atmo_ray_list_tail_kernel(const uint32_t *__restrict__ live, uint32_t capacity, uint32_t *__restrict__ index,
+                                                                 uint32_t *__restrict__ listed) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t m = ray_list_bound(live, capacity);
+    if (i == 0u && listed != nullptr) *listed = m;
+    if (i >= m && i < capacity) index[i] = RAY_LIST_END;
+}
+
+size_t ray_list_scratch_bytes(uint32_t capacity) { return ray_order_scratch_bytes(capacity) + 4 * sizeof(uint32_t); }
+hipError_t launch_ray_list(const float4 *rays, const uint32_t *count, uint32_t capacity, int flags, const RayCullConsts &cull, float4 *rgba, uint32_t *index,
+                           uint32_t *listed, void *scratch, hipStream_t stream) {
+    if (rays == nullptr || index == nullptr || scratch == nullptr || capacity == 0 || capacity > RAY_ORDER_MAX_RAYS ||
+        (flags & ~(RAY_LIST_ORDER | RAY_LIST_CULL)) != 0 || ((flags & RAY_LIST_CULL) != 0 && rgba == nullptr))
+        return hipErrorInvalidValue;
+    const uint32_t chunks = ray_sort_chunks(capacity);
+    uint32_t *pairs_b = static_cast<uint32_t *>(scratch), *pairs_c = pairs_b + 2 * (size_t)capacity, *hist = pairs_b + 4 * (size_t)capacity;
+    uint32_t *totals = hist + (size_t)RAY_SORT_DIGITS * chunks, *live = totals + RAY_SORT_DIGITS;
+    uint32_t *keys = pairs_c;   // the first `capacity` words of pairs C: read by pass 0, overwritten by pass 1
+    const dim3 rays_grid((capacity + 255u) / 256u), block(256), waves(chunks), wave(64), digits(RAY_SORT_DIGITS), scan(RAY_SCAN_BLOCK);
+    hipLaunchKernelGGL(atmo_ray_list_key_kernel, rays_grid, block, 0, stream, rays, count, capacity, flags, cull, keys, rgba);
+    hipLaunchKernelGGL((atmo_ray_list_hist_kernel<false, true>), waves, wave, 0, stream, keys, count, capacity, 0, chunks, hist);
+    hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
+    if (flags & RAY_LIST_ORDER) {
+        hipLaunchKernelGGL((atmo_ray_list_scatter_kernel<false, false, true>), waves, wave, 0, stream, keys, count, capacity, 0, chunks, hist, totals, pairs_b, live);
+        hipLaunchKernelGGL((atmo_ray_list_hist_kernel<true, false>), waves, wave, 0, stream, pairs_b, live, capacity, ORDER_KEY_BITS, chunks, hist);
+        hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
+        hipLaunchKernelGGL((atmo_ray_list_scatter_kernel<true, false, false>), waves, wave, 0, stream, pairs_b, live, capacity, ORDER_KEY_BITS, chunks, hist, totals,
+                           pairs_c, (uint32_t *)nullptr);
+        hipLaunchKernelGGL((atmo_ray_list_hist_kernel<true, false>), waves, wave, 0, stream, pairs_c, live, capacity, 2 * ORDER_KEY_BITS, chunks, hist);
+        hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
+        hipLaunchKernelGGL((atmo_ray_list_scatter_kernel<true, true, false>), waves, wave, 0, stream, pairs_c, live, capacity, 2 * ORDER_KEY_BITS, chunks, hist, totals,
+                           index, (uint32_t *)nullptr);
+    } else {   // queue order: one stable compaction pass, every live key's digit 0
+        hipLaunchKernelGGL((atmo_ray_list_scatter_kernel<false, true, true>), waves, wave, 0, stream, keys, count, capacity, 0, chunks, hist, totals, index, live);
+    }
+    hipLaunchKernelGGL(atmo_ray_list_tail_kernel, rays_grid, block, 0, stream, live, capacity, index, listed);
+    return hipGetLastError();
+}
+
 }  // namespace atmo

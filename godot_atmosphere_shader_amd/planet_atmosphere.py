@@ -25,6 +25,7 @@ The fragment work runs only on the GPU: `render` raises if libatmo_hip.so or a g
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import operator
@@ -746,6 +747,55 @@ class PlanetAtmosphere:
         N.check(self._ctx, fn(self._ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(order.data_ptr()), C.c_void_p(scratch.data_ptr()), need.value,
                               C.c_void_p(handle or 0)))
         return order
+
+    # ---- ray lists: counted queues and the sure-miss cull (include/atmo_ray_list.h) ------------------------------------------------
+    def _ray_list_entry(self, name: str):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_ray_list.h); rebuild it")
+        return fn
+
+    def ray_list(self, rays, count=None, order=True, cull=False, camera=None, out=None, stream=None):
+        """An index list for `shade_rays(index=...)` built on the device (atmo_ray_list; include/atmo_ray_list.h): `(index, listed)`, a CUDA int32
+        (capacity,) tensor -- the listed rays, then -1 (ATMO_RAY_LIST_END) entries, which the indexed call skips -- and a CUDA int32 (1,) tensor, their
+        number.  `rays` as `shade_rays`'; its rows are the queue's CAPACITY.  `count`: a one-element CUDA int32 tensor holding the queue's live length,
+        read by the kernels when they run and never by the host (None: every row is live); rows behind it are not looked at.  `order`: the listed rays in
+        `ray_order`'s order, else in queue order.  `cull`: rays that surely miss the shell seen through `camera` (None: ray space is world space) are
+        left out and their rows of `out` are set to zero -- pass the same `out` to `shade_rays(index=...)`; None: a tensor of zeros, as that call's own
+        default is.  The scratch comes from torch's allocator, on the call's stream.  godot_atmosphere_shader_amd.ray_list.ray_list is the same list
+        in numpy."""
+        import torch
+
+        capacity = _check_rays(rays, "rays", 8)
+        if capacity > 1 << 28:
+            raise ValueError("at most 2^28 rays")
+        if count is not None:
+            if not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()):
+                raise TypeError("count must be a contiguous CUDA int32 tensor")
+            if count.numel() != 1:
+                raise ValueError("count must have one element")
+        flags = (N.RAY_LIST_ORDER if order else 0) | (N.RAY_LIST_CULL if cull else 0)
+        if cull and out is not None and _check_rays(out, "out", 4) != capacity:
+            raise ValueError("out must have one row per ray: shape (n, 4)")
+        if capacity == 0:
+            return torch.empty((0,), dtype=torch.int32, device=rays.device), torch.zeros((1,), dtype=torch.int32, device=rays.device)
+        fn, size = self._ray_list_entry("atmo_ray_list"), self._ray_list_entry("atmo_ray_list_scratch_bytes")
+        need = C.c_size_t(0)
+        N.check(self._ctx, size(capacity, C.byref(need)))
+        handle = _stream_handle(stream, rays)
+        words = (need.value + 15) // 16 * 4
+        # as ray_order: what is allocated (and zeroed) here belongs to the call's stream, where the allocator reuses the scratch behind the list
+        with contextlib.nullcontext() if stream is None else torch.cuda.stream(torch.cuda.ExternalStream(handle, device=rays.device)):
+            scratch = torch.empty((words,), dtype=torch.int32, device=rays.device)
+            index = torch.empty((capacity,), dtype=torch.int32, device=rays.device)
+            listed = torch.empty((1,), dtype=torch.int32, device=rays.device)
+            if cull and out is None:
+                out = torch.zeros((capacity, 4), dtype=torch.float32, device=rays.device)
+        nf = _to_native_frame(self.make_frame(camera if camera is not None else _WORLD_RAY_SPACE, 0.0)) if cull else None
+        N.check(self._ctx, fn(self._ctx, C.byref(nf) if cull else None, C.c_void_p(rays.data_ptr()), C.c_void_p(count.data_ptr()) if count is not None else None,
+                              capacity, flags, C.c_void_p(out.data_ptr()) if cull else None, C.c_void_p(index.data_ptr()), C.c_void_p(listed.data_ptr()),
+                              C.c_void_p(scratch.data_ptr()), need.value, C.c_void_p(handle or 0)))
+        return index, listed
 
     def camera_rays(self, camera, depth, rect=None, stream=None):
         """The rays the library's own prologue forms for `rect` (default: the whole viewport) of the camera's viewport, row-major: a CUDA float32

@@ -34,7 +34,21 @@ rays, shuffled, order, indexed, indexed_id, order_indexed:
 The plain arms run the parent commit's instructions (tools/isa_diff.py is the proof), so no second library is needed.  `bits_equal`, per arm: rays -- the
 render frame's; shuffled -- its own second run's; order -- ray_order.ray_order of the same rays in numpy; indexed and order_indexed -- the shuffled arm's;
 indexed_id -- the rays arm's.  `order_plus_indexed_ms` is the sum of the two medians, `below_shuffled_range` whether it and the order_indexed median lie
-below the MINIMUM of the shuffled arm's rounds."""
+below the MINIMUM of the shuffled arm's rounds.
+
+The LIST table (--table list --rounds 5; include/atmo_ray_list.h), the ORDER table's shuffled queue from P_space and from P_limb, same timing.  Per pose,
+once (the list does not depend on the family): atmo_ray_list alone for each flag combination (list_0, list_order, list_cull, list_order_cull) against
+atmo_ray_order of the same queue (order), every ray live; `parity`: whether list_order's median lies inside order's min-max range widened by 5 %.  Per
+pose and family, every round in the order shuffled, order_indexed, cull_indexed, order_cull_indexed, eighth_plain, eighth_list, tail:
+  shuffled            the plain atmo_shade_rays of the queue;
+  order_indexed       atmo_ray_order, then atmo_shade_rays_indexed;
+  cull_indexed        atmo_ray_list(CULL), then atmo_shade_rays_indexed over the capacity;
+  order_cull_indexed  atmo_ray_list(ORDER | CULL), then the same;
+  eighth_plain        the plain call on the first capacity / 8 rays: what a host that read the count back would launch;
+  eighth_list         *count = capacity / 8: atmo_ray_list(ORDER | CULL) and the indexed call, both over the whole capacity;
+  tail                the indexed call through a list of END entries alone: one index load per thread and nothing else.
+The baselines are kernels this library shares with its parent byte for byte (tools/isa_diff.py).  `bits_equal`: every list arm's picture against the
+shuffled arm's (eighth_list: against eighth_plain's, on the live rows)."""
 import argparse
 import json
 import os
@@ -159,6 +173,110 @@ def order_rows(args, tex, cam, depth, frame, out, perm):
     return rows
 
 
+LIST_ALONE = ("order", "list_0", "list_order", "list_cull", "list_order_cull")
+LIST_ARMS = ("shuffled", "order_indexed", "cull_indexed", "order_cull_indexed", "eighth_plain", "eighth_list", "tail")
+
+
+def list_rows(args, tex, out, perm):
+    """The LIST table's rows (the module's docstring)."""
+    import ctypes as C
+
+    from godot_atmosphere_shader_amd import _native as N
+    from godot_atmosphere_shader_amd.planet_atmosphere import _to_native_frame
+
+    n = H * W
+    stats = lambda v: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)}   # noqa: E731
+    bits = lambda t: t.view(torch.int32)   # noqa: E731
+    poses = []
+    out2 = torch.empty_like(out)
+    for pose in ("P_space", "P_limb"):
+        cam = S.Camera.from_pose(W, H, pose)
+        depth = torch.from_numpy(S.depth_ground_sphere(cam)).cuda()
+        entry = {"pose": pose, "rows": []}
+        for label in args.families.split(","):
+            config, kw = FAMILIES[label]
+            node = make_node(config, tex, cubemap_lod=False, tile_feedback=0, **kw)
+            try:
+                shuffled = node.camera_rays(cam, depth)[perm].contiguous()
+                need = C.c_size_t()
+                N.check(node._ctx, node._lib.atmo_ray_list_scratch_bytes(n, C.byref(need)))
+                scratch = torch.empty(((need.value + 3) // 4,), dtype=torch.int32, device="cuda")
+                index = torch.empty((n,), dtype=torch.int32, device="cuda")
+                ends = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+                listed = torch.zeros((1,), dtype=torch.int32, device="cuda")
+                full = torch.tensor([n], dtype=torch.int32, device="cuda")
+                eighth = torch.tensor([n // 8], dtype=torch.int32, device="cuda")
+                nf = _to_native_frame(node.make_frame(cam, 0.0))
+                stream = torch.cuda.current_stream().cuda_stream
+
+                def order():
+                    N.check(node._ctx, node._lib.atmo_ray_order(node._ctx, shuffled.data_ptr(), n, index.data_ptr(), scratch.data_ptr(), need.value, stream))
+
+                def build(flags, count=full, rgba=out2):
+                    N.check(node._ctx, node._lib.atmo_ray_list(node._ctx, C.byref(nf), shuffled.data_ptr(), count.data_ptr(), n, flags, rgba.data_ptr(),
+                                                               index.data_ptr(), listed.data_ptr(), scratch.data_ptr(), need.value, stream))
+
+                def indexed(through=index):
+                    node.shade_rays(shuffled, cam, out=out2, index=through)
+
+                def pair(first):
+                    first()
+                    indexed()
+
+                if not entry.get("list_alone"):   # the list alone, once per pose
+                    alone = {"order": order, "list_0": lambda: build(0), "list_order": lambda: build(1), "list_cull": lambda: build(2),
+                             "list_order_cull": lambda: build(3)}
+                    for arm in LIST_ALONE:
+                        timed(alone[arm], args.warmup)
+                    t = {a: [] for a in LIST_ALONE}
+                    for _ in range(args.rounds):
+                        for arm in LIST_ALONE:
+                            t[arm].append(timed(alone[arm], args.reps))
+                    entry["list_alone"] = {a: stats(v) for a, v in t.items()}
+                    lo, hi = min(t["order"]) / 1.05, max(t["order"]) * 1.05
+                    entry["parity"] = bool(lo <= entry["list_alone"]["list_order"]["median"] <= hi)
+                    build(3)
+                    torch.cuda.synchronize()
+                    entry["listed_order_cull"] = int(listed.item())
+                calls = {"shuffled": lambda: node.shade_rays(shuffled, cam, out=out), "order_indexed": lambda: pair(order),
+                         "cull_indexed": lambda: pair(lambda: build(2)), "order_cull_indexed": lambda: pair(lambda: build(3)),
+                         "eighth_plain": lambda: node.shade_rays(shuffled[:n // 8], cam, width=n, out=out[:n // 8]),
+                         "eighth_list": lambda: pair(lambda: build(3, eighth)), "tail": lambda: indexed(ends)}
+                for arm in LIST_ARMS:
+                    timed(calls[arm], args.warmup)
+                # the pictures, outside the timing
+                equal = {}
+                calls["shuffled"]()
+                plain = out.clone()
+                for arm in ("order_indexed", "cull_indexed", "order_cull_indexed"):
+                    out2.fill_(float("nan"))
+                    calls[arm]()
+                    equal[arm] = bool(torch.equal(bits(out2), bits(plain)))
+                out2.fill_(float("nan"))
+                calls["eighth_list"]()
+                equal["eighth_list"] = bool(torch.equal(bits(out2[:n // 8]), bits(plain[:n // 8])) and torch.isnan(out2[n // 8:]).all())
+                t_warm = time.perf_counter()
+                while time.perf_counter() - t_warm < 0.025:   # sustained clocks
+                    calls["shuffled"]()
+                    torch.cuda.synchronize()
+                arms = {a: [] for a in LIST_ARMS}
+                for _ in range(args.rounds):
+                    for arm in LIST_ARMS:
+                        arms[arm].append(timed(calls[arm], args.reps))
+            finally:
+                node.close()
+            med = {a: sorted(v)[len(v) // 2] for a, v in arms.items()}
+            row = {"family": label, "bits_equal": equal, "ms": {a: stats(v) for a, v in arms.items()},
+                   **{f"{a}_over_shuffled": med[a] / med["shuffled"] for a in ("order_indexed", "cull_indexed", "order_cull_indexed")},
+                   "eighth_list_over_plain": med["eighth_list"] / med["eighth_plain"]}
+            entry["rows"].append(row)
+            print(f"{pose} {label:15s} " + "  ".join(f"{a} {med[a]:.4f}" for a in LIST_ARMS) + f"  bits equal: {equal}", file=sys.stderr, flush=True)
+        print(f"{pose} list alone: " + "  ".join(f"{a} {v['median']:.4f} ({v['min']:.4f} - {v['max']:.4f})" for a, v in entry["list_alone"].items()) +
+              f"  parity: {entry['parity']}  listed under ORDER | CULL: {entry['listed_order_cull']} of {n}", file=sys.stderr, flush=True)
+        poses.append(entry)
+    return poses
+
+
 def timed(call, reps):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -176,7 +294,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--families", default=",".join(FAMILIES))
-    ap.add_argument("--table", choices=("rays", "quads", "both", "order"), default="both")
+    ap.add_argument("--table", choices=("rays", "quads", "both", "order", "list"), default="both")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rays_probe.py measures on a device; none is visible")
@@ -189,6 +307,8 @@ def main():
     result = {"viewport": [W, H], "pose": "P_space", "reps": args.reps, "rounds": args.rounds, "device": torch.cuda.get_device_name(0), "rows": []}
     if args.table == "order":
         result["order_rows"] = order_rows(args, tex, cam, depth, frame, out, perm)
+    if args.table == "list":
+        result["list_poses"] = list_rows(args, tex, out, perm)
     for label in args.families.split(",") if args.table in ("rays", "both") else ():
         config, kw = FAMILIES[label]
         node = make_node(config, tex, cubemap_lod=False, tile_feedback=0, **kw)   # atmo_set_sampler_lod 0, atmo_set_tile_feedback 0
