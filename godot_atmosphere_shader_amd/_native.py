@@ -86,6 +86,10 @@ RAY_KEY_BITS = 18   # ATMO_RAY_KEY_BITS
 # (PlanetAtmosphere.ray_list raises without).
 RAY_LIST_SYMBOLS = ("atmo_ray_list_scratch_bytes", "atmo_ray_list", "atmo_debug_ray_cull_constants")
 RAY_LIST_ORDER, RAY_LIST_CULL, RAY_LIST_END = 1, 2, 0xFFFFFFFF   # ATMO_RAY_LIST_ORDER, ATMO_RAY_LIST_CULL, ATMO_RAY_LIST_END
+# every symbol include/atmo_ray_detail.h declares: the ray batches, ray lists and ray quads of a cloud context with cloud detail on.  The RAYS_SYMBOLS
+# rule: the ABI version stays 5, the tuple stands beside EXPORTED_SYMBOLS, load() binds it where the library has it (PlanetAtmosphere.shade_rays and
+# shade_ray_quads raise without, on a cloud node with cloud_detail on).
+RAY_DETAIL_SYMBOLS = ("atmo_shade_rays_detail", "atmo_shade_ray_quads_detail")
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -360,6 +364,17 @@ def load() -> C.CDLL:
     }
     assert tuple(ray_list_sig) == RAY_LIST_SYMBOLS
     for name, (res, args) in ray_list_sig.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
+    # include/atmo_ray_detail.h: the same rule
+    ray_detail_sig = {
+        "atmo_shade_rays_detail": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]),
+        "atmo_shade_ray_quads_detail": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    }
+    assert tuple(ray_detail_sig) == RAY_DETAIL_SYMBOLS
+    for name, (res, args) in ray_detail_sig.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype = res

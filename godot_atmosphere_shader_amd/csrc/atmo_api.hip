@@ -21,6 +21,7 @@
 #include "../../include/atmo_ray_quads.h"
 #include "../../include/atmo_ray_order.h"
 #include "../../include/atmo_ray_list.h"
+#include "../../include/atmo_ray_detail.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -2256,7 +2257,8 @@ static_assert(sizeof(AtmoRay) == 32 && sizeof(AtmoRay) == 2 * sizeof(float4), "a
 // Every check stands in front of hipSetDevice, in the header's order, so that a host-only context answers the same.  No feedback state is involved: the
 // launch is row-major over the batch, timed and counted as every accepted atmo_render, with nothing beside the draw stream (a graph capture takes it as it is).
 // The modes no ray kernel exists for, in the headers' order (atmo_rays.h, atmo_ray_quads.h): the message names the entry point and the mode
-static int rays_mode_refusals(AtmoContext *ctx, const AtmoFrame *frame, const std::string &who) {
+// serves_detail (atmo_shade_rays_detail, atmo_shade_ray_quads_detail; include/atmo_ray_detail.h): the last item is gone, everything in front of it stands
+static int rays_mode_refusals(AtmoContext *ctx, const AtmoFrame *frame, const std::string &who, bool serves_detail) {
     if (ctx->flags & atmo::KF_ATMO_REF) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for atmo_set_precision 2 (rays are shaded in the default forms: atmo_set_precision 1)");
     if ((ctx->flags & (atmo::KF_CLOUDS | atmo::KF_LITE)) && !(ctx->flags & atmo::KF_PRECISE))
         return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for atmo_set_precision 0 (rays are shaded in the default forms: atmo_set_precision 1)");
@@ -2264,7 +2266,7 @@ static int rays_mode_refusals(AtmoContext *ctx, const AtmoFrame *frame, const st
     if (choose_split(ctx, frame) == 2) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel with two lanes per ray (atmo_set_lane_split 2)");
     if ((ctx->flags & atmo::KF_CLOUDS) && (ctx->flags & atmo::KF_LIGHT_DIRECT))
         return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for a cloud variant in the direct light mode (ATMO_LIGHT_DIRECT)");
-    return cloud_detail_refusal(ctx, who, "ray batches");
+    return serves_detail ? ATMO_OK : cloud_detail_refusal(ctx, who, "ray batches");
 }
 // What the ray kernels read beside RenderConsts (atmo::RayConsts): the batch, its place in the image, and the uniform part of the per-ray march-distance cap
 static atmo::RayConsts ray_consts(const AtmoContext *ctx, const atmo::RenderConsts &rc, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n, uint32_t width,
@@ -2279,14 +2281,15 @@ static atmo::RayConsts ray_consts(const AtmoContext *ctx, const atmo::RenderCons
     return yc;
 }
 // index != nullptr: atmo_shade_rays_indexed (include/atmo_ray_order.h) -- the same checks under its name, its list's two in the argument block, and the
-// KF_INDEX kernels over the list; everything else is the one path
+// KF_INDEX kernels over the list; everything else is the one path.
+// serves_detail (include/atmo_ray_detail.h): the entry point shades a cloud context with cloud detail on -- no refusal, DetailConsts as render_impl's step 3a
+// fills them, the detail launchers, KF_DETAIL in the kernel's name; with the switch off or no clouds it is the path below under another name
 struct RayIndexList {
     const uint32_t *index_dev;
     uint32_t n_index;
 };
 static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
-                     void *stream, const RayIndexList *index = nullptr) {
-    const std::string who = index ? "atmo_shade_rays_indexed" : "atmo_shade_rays";
+                     void *stream, const std::string &who, bool serves_detail, const RayIndexList *index = nullptr) {
     if (!ctx) return ATMO_E_ARG;
     if (n_rays == 0 || (index && index->n_index == 0)) return ATMO_OK;   // nothing to shade
     if (!frame || !rays_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": null frame or device pointer");
@@ -2297,7 +2300,7 @@ static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *ra
     if (width == 0) return fail(ctx, ATMO_E_ARG, who + ": width must be at least 1");
     if ((uint64_t)first + (uint64_t)n_rays > ((uint64_t)1 << 32)) return fail(ctx, ATMO_E_ARG, who + ": first + n_rays must not exceed 2^32");
     // the mode: the default forms under the level-0 sampler (atmo::rays_family_supported)
-    ATMO_TRY(rays_mode_refusals(ctx, frame, who));
+    ATMO_TRY(rays_mode_refusals(ctx, frame, who, serves_detail));
     if (ctx->sampler_lod == 1 && (ctx->flags & atmo::KF_CLOUDS) && ctx->cube.ptr && ctx->cube_levels > 1)
         return fail(ctx, ATMO_E_STATE, who + ": rays sample the coverage cubemap at level 0, and this context demands the declared sampler (atmo_set_sampler_lod 1)");
     int flags = 0, split = 1;
@@ -2318,20 +2321,25 @@ static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *ra
     TimingBracket timing;
     ATMO_TRY(timing_open(ctx, timing));
     ATMO_TRY(timing_begin(ctx, timing, s));
-    if (index) {
+    const bool detail = serves_detail && cloud_detail_on(ctx);
+    if (detail) {
+        const atmo::DetailConsts xc = cloud_detail_consts(ctx, frame);
+        const atmo::RayIndexConsts ic = {index ? index->index_dev : nullptr, index ? index->n_index : 0u};
+        HIP_TRY(ctx, atmo::launch_shade_rays_detail(flags, rc, yc, xc, index ? &ic : nullptr, s));
+    } else if (index) {
         const atmo::RayIndexConsts ic = {index->index_dev, index->n_index};
         HIP_TRY(ctx, atmo::launch_shade_rays_indexed(flags, rc, yc, ic, s));
     } else {
         HIP_TRY(ctx, atmo::launch_shade_rays(flags, rc, yc, s));
     }
     hipEvent_t marker = nullptr;
-    ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_RAYS | (index ? atmo::KF_INDEX : 0), 1, true, &marker));
+    ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_RAYS | (index ? atmo::KF_INDEX : 0) | (detail ? atmo::KF_DETAIL : 0), 1, true, &marker));
     return timing_end(ctx, timing, s);
 }
 
 int atmo_shade_rays(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
                     void *stream) {
-    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream);
+    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, "atmo_shade_rays", false);
 }
 
 // ---- rays in quads under the declared sampler (include/atmo_ray_quads.h) ---------------------------------------------------------------------------
@@ -2339,8 +2347,7 @@ int atmo_shade_rays(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *ray
 // There is NO fallback to the level-0 ray kernels: their jitter order is row-major and this call's is quad order, a third picture.  The constants are
 // rays_impl's (ray_consts); lod0_* and the level table come from draw_consts, the path of every declared-sampler draw.
 static int ray_quads_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_quads, uint32_t width,
-                          uint32_t first_quad, void *stream) {
-    const std::string who = "atmo_shade_ray_quads";
+                          uint32_t first_quad, void *stream, const std::string &who, bool serves_detail) {
     if (!ctx) return ATMO_E_ARG;
     if (n_quads == 0) return ATMO_OK;   // nothing to shade
     if (!frame || !rays_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": null frame or device pointer");
@@ -2348,7 +2355,7 @@ static int ray_quads_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRa
         return fail(ctx, ATMO_E_ARG, who + ": rays_dev and rgba_dev must be 16-byte aligned");
     if (width == 0) return fail(ctx, ATMO_E_ARG, who + ": width must be at least 1");
     if ((uint64_t)first_quad + (uint64_t)n_quads > ((uint64_t)1 << 30)) return fail(ctx, ATMO_E_ARG, who + ": first_quad + n_quads must not exceed 2^30");
-    ATMO_TRY(rays_mode_refusals(ctx, frame, who));
+    ATMO_TRY(rays_mode_refusals(ctx, frame, who, serves_detail));
     if (!(ctx->flags & atmo::KF_CLOUDS))
         return fail(ctx, ATMO_E_STATE, who + ": a variant without clouds has no texture call to difference; shade its rays with atmo_shade_rays");
     if (ctx->sampler_lod == 0)
@@ -2375,19 +2382,22 @@ static int ray_quads_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRa
     // slot 4 q + j: thread i = slot i; the kernel's jitter pixel comes from the quad index first_quad + (i >> 2) and the quads per row.  A launch holds at
     // most 2^29 quads, so that its 4 n_quads rays fit RayConsts::n (the one batch of 2^30 quads the range check admits goes out as two)
     constexpr uint32_t per_launch = 1u << 29;
+    const bool detail = serves_detail && cloud_detail_on(ctx);   // (include/atmo_ray_detail.h: as rays_impl's)
+    const atmo::DetailConsts xc = cloud_detail_consts(ctx, frame);
     for (uint32_t done = 0; done < n_quads; done += per_launch) {
         const uint32_t quads = n_quads - done < per_launch ? n_quads - done : per_launch;
         const atmo::RayConsts yc = ray_consts(ctx, rc, rays_dev + 4 * (size_t)done, rgba_dev + 16 * (size_t)done, 4u * quads, (width + 1u) / 2u, first_quad + done);
-        HIP_TRY(ctx, atmo::launch_shade_ray_quads(flags, rc, yc, s));
+        if (detail) HIP_TRY(ctx, atmo::launch_shade_ray_quads_detail(flags, rc, yc, xc, s));
+        else HIP_TRY(ctx, atmo::launch_shade_ray_quads(flags, rc, yc, s));
     }
     hipEvent_t marker = nullptr;
-    ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_RAYS, 1, true, &marker));
+    ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_RAYS | (detail ? atmo::KF_DETAIL : 0), 1, true, &marker));
     return timing_end(ctx, timing, s);
 }
 
 int atmo_shade_ray_quads(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_quads, uint32_t width,
                          uint32_t first_quad, void *stream) {
-    return ray_quads_impl(ctx, frame, rays_dev, rgba_dev, n_quads, width, first_quad, stream);
+    return ray_quads_impl(ctx, frame, rays_dev, rgba_dev, n_quads, width, first_quad, stream, "atmo_shade_ray_quads", false);
 }
 
 // ---- ray queues: the device's coherence order and shading through an index list (include/atmo_ray_order.h) ------------------------------------------------
@@ -2395,7 +2405,22 @@ static_assert(ATMO_RAY_KEY_BITS == atmo::RAY_KEY_BITS, "the header's key width i
 int atmo_shade_rays_indexed(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
                             const uint32_t *index_dev, uint32_t n_index, void *stream) {
     const RayIndexList list = {index_dev, n_index};
-    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, &list);
+    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, "atmo_shade_rays_indexed", false, &list);
+}
+
+// ---- cloud detail for rays, ray lists and ray quads (include/atmo_ray_detail.h) ---------------------------------------------------------------------------
+// The ray paths above under a name of their own, with the cloud-detail item of the mode checks gone: index_dev == NULL is atmo_shade_rays' call, a list
+// atmo_shade_rays_indexed's (n_index is not looked at without one)
+int atmo_shade_rays_detail(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
+                           const uint32_t *index_dev, uint32_t n_index, void *stream) {
+    if (!index_dev) return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, "atmo_shade_rays_detail", true);
+    const RayIndexList list = {index_dev, n_index};
+    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, "atmo_shade_rays_detail", true, &list);
+}
+
+int atmo_shade_ray_quads_detail(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_quads, uint32_t width,
+                                uint32_t first_quad, void *stream) {
+    return ray_quads_impl(ctx, frame, rays_dev, rgba_dev, n_quads, width, first_quad, stream, "atmo_shade_ray_quads_detail", true);
 }
 
 int atmo_ray_order_scratch_bytes(uint32_t n_rays, size_t *bytes) {

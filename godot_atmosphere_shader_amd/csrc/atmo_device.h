@@ -330,6 +330,11 @@ hipError_t launch_shade_ray_quads(int flags, const RenderConsts &rc, const RayCo
 // the ray draws through an index list (atmo_shade_rays_indexed; include/atmo_ray_order.h): launch_shade_rays' seven kernels once more, the grid over the
 // list's ic.n_index entries; flags WITHOUT KF_RAYS | KF_INDEX, which the launcher adds
 hipError_t launch_shade_rays_indexed(int flags, const RenderConsts &rc, const RayConsts &yc, const RayIndexConsts &ic, hipStream_t stream);
+// the ray draws with cloud detail (atmo_shade_rays_detail, atmo_shade_ray_quads_detail; include/atmo_ray_detail.h): the three cloud families of
+// launch_shade_rays (flags WITHOUT KF_RAYS | KF_INDEX | KF_DETAIL, which the launcher adds; ic == nullptr: the whole batch, else the grid over the list) and of
+// launch_shade_ray_quads (flags WITH KF_CUBE_LOD), DetailConsts behind the ray arguments; the siblings' argument checks, hipErrorInvalidValue for any other family
+hipError_t launch_shade_rays_detail(int flags, const RenderConsts &rc, const RayConsts &yc, const DetailConsts &xc, const RayIndexConsts *ic, hipStream_t stream);
+hipError_t launch_shade_ray_quads_detail(int flags, const RenderConsts &rc, const RayConsts &yc, const DetailConsts &xc, hipStream_t stream);
 // the coherence order of a ray queue (atmo_ray_order; include/atmo_ray_order.h states the key): the key kernel, then a stable least-significant-digit radix
 // sort of (key, index) pairs in three 6-bit passes, every buffer in the caller's scratch (ray_order_scratch_bytes(n) bytes, 16-byte aligned), kernels on
 // `stream` only.  launch_ray_sort is the sort alone, on keys that are already there (atmo_debug_sort_ray_keys); n <= RAY_ORDER_MAX_RAYS

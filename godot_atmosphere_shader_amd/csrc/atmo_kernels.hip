@@ -1717,7 +1717,9 @@ __device__ __forceinline__ float rm_sample_weight(RmRecurrence &s, float density
 // position is still advanced one rounded addition per step), so the result is bit-identical; only lane 0's is used.
 // DETAIL (KF_DETAIL, one lane per ray, precise): every sample's density is get_density -- the detail fetch -- and the raymarched light, which now depends on
 // the march's alpha before the sample (light_raymarched), is evaluated in place under BOTH samplers: a deferred lit-sample queue would have to carry alpha0.
-// LANE (KF_RAYS): the ray's own origin and march-distance cap, *lo (cloud_march_ray); one lane per ray, no cloud detail.
+// LANE (KF_RAYS): the ray's own origin and march-distance cap, *lo (cloud_march_ray); one lane per ray.
+// LANE && DETAIL (atmo_shade_rays_detail, include/atmo_ray_detail.h): both at once.  The detail fetch reads the lane's sample position, wherever the chain
+// started (cloud_march_ray<true>), and alpha0 is the lane's own recurrence: neither form has a site that asks about the other.
 // LANE && LOD (atmo_shade_ray_quads, include/atmo_ray_quads.h): the four lanes of a quad hold the four rays of a caller's quad, each with an origin, a
 // direction and a cap of its own.  Nothing below asks where a lane's position chain came from: the `marching` ballot counts the lanes that are here, the
 // whole-quad exchange reads whatever positions the partner lanes hold, and the level-0 certificate's E (quad_march_spread2) needs no other drift bound --
@@ -1731,7 +1733,7 @@ __device__ __forceinline__ float2 march_clouds(const RenderConsts &rc_in, V3 dir
                                                QuadRegs *qregs = nullptr, const f32x4 *lvl = nullptr, const DetailConsts *xc = nullptr,
                                                const LaneOrigin *lo = nullptr) {
     static_assert(!DETAIL || (PRECISE && SPLIT == 1), "cloud detail: the precise form, one lane per ray");
-    static_assert(!LANE || (!DETAIL && SPLIT == 1), "per-ray origins: no cloud detail, one lane per ray");
+    static_assert(!LANE || SPLIT == 1, "per-ray origins: one lane per ray");
     // Under the declared sampler the raymarched light is evaluated IN PLACE with one lane per ray as well (round 5) -- this function instead of the
     // lit-sample queue, whose arithmetic it keeps (same bits): 73 VGPRs and no queue in LDS instead of 86 / 15 KB, six waves per SIMD instead of five, no
     // twelve-word entries through LDS, no second whole-quad block per lit sample.  Measured then (profiles/round5/ab_rm_inplace.txt): 3840x2160 -11.4 %
@@ -2211,8 +2213,8 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                                             const TargetConsts *tc = nullptr, const DepthConsts *dc = nullptr, const DetailConsts *xc = nullptr,
                                             const RayConsts *yc = nullptr, const RayIndexConsts *ic = nullptr) {
     constexpr bool DETAIL = (FLAGS & KF_DETAIL) != 0;   // the cloud march with CLOUDS_ALWAYS_LOW_QUALITY off, through *xc
-    static_assert(!DETAIL || ((FLAGS & ~(KF_DETAIL | KF_CUBE_LOD | KF_CLOUD_LIGHT_RM | KF_LITE)) == (KF_PRECISE | KF_CLOUDS) && SPLIT == 1),
-                  "cloud detail: the LUT-light precise cloud families, float output, one lane per ray");
+    static_assert(!DETAIL || ((FLAGS & ~(KF_DETAIL | KF_CUBE_LOD | KF_CLOUD_LIGHT_RM | KF_LITE | KF_RAYS | KF_INDEX)) == (KF_PRECISE | KF_CLOUDS) && SPLIT == 1),
+                  "cloud detail: the LUT-light precise cloud families, float output, one lane per ray (with KF_RAYS: atmo_detail_rays_kernel)");
     constexpr bool RAYS = (FLAGS & KF_RAYS) != 0;   // a ray of the caller's per lane, through *yc
     constexpr bool INDEXED = (FLAGS & KF_INDEX) != 0;   // ... the ray an index list names, through *ic (atmo_shade_rays_indexed)
     static_assert(!INDEXED || (RAYS && (FLAGS & KF_CUBE_LOD) == 0), "index lists: the level-0 ray kernels (ray quads have no indexed form)");
@@ -2234,7 +2236,7 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     static_assert(!PROXY || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0), "proxy draws: the default forms, one lane per ray, row-major");
     static_assert((FLAGS & KF_VIEWS) == 0 || (!VIEWPOS && !ATMO_REF && SPLIT == 1 && (FLAGS & KF_GEO) == 0),
                   "multi-view draws: the default forms, one lane per ray, float or packed targets (KF_VIEWS | KF_TARGET: atmo_render_views_target_kernel)");
-    static_assert(!RAYS || ((FLAGS & ~(KF_RAYS | KF_INDEX | KF_CUBE_LOD | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT | KF_LITE | KF_PRECISE)) == 0 && SPLIT == 1),
+    static_assert(!RAYS || ((FLAGS & ~(KF_RAYS | KF_INDEX | KF_DETAIL | KF_CUBE_LOD | KF_CLOUDS | KF_CLOUD_LIGHT_RM | KF_LIGHT_DIRECT | KF_LITE | KF_PRECISE)) == 0 && SPLIT == 1),
                   "ray kernels: the default forms, one lane per ray; the declared sampler (KF_CUBE_LOD) for rays that arrive in quads (atmo_shade_ray_quads)");
     static_assert(!RAYS || (!(DIRECT && CLOUDS) && (PRECISE == (CLOUDS || LITE)) && !(RM && LITE)),
                   "ray kernels: the LUT-light cloud forms in precise mode, no cloud + direct light");
@@ -2517,7 +2519,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                 }
                 float2 rr;
                 if constexpr (DETAIL) {   // light in place under both samplers (march_clouds)
-                    rr = march_clouds<RM, PRECISE, 1, LOD, true>(rc, dir_m, c0, c1, jitter, 0, &qregs, lvl_table, xc);
+                    // RAYS && DETAIL (atmo_shade_rays_detail, atmo_shade_ray_quads_detail): the same march from the ray's own origin, no queue LDS
+                    if constexpr (RAYS) rr = march_clouds<RM, PRECISE, 1, LOD, true, true>(rc, dir_m, c0, c1, jitter, 0, &qregs, lvl_table, xc, &lo);
+                    else rr = march_clouds<RM, PRECISE, 1, LOD, true>(rc, dir_m, c0, c1, jitter, 0, &qregs, lvl_table, xc);
                 } else if constexpr (RM && SPLIT == 1 && !LOD) {   // the lit-sample queue: wave-private
                     __shared__ float rmq[BLOCK_WAVES * RMQ_WORDS_PER_WAVE];
                     if constexpr (RAYS) rr = march_clouds_rm_queue<PRECISE, true>(rc, dir_m, c0, c1, jitter, rmq + wave * RMQ_WORDS_PER_WAVE, &lo);
@@ -3704,8 +3708,9 @@ const char *render_kernel_name(int flags, int light_steps, int split) {
     static thread_local char name[80];
     const bool v2_precise = (flags & KF_ATMO_REF) != 0;  // its light march is a run-time loop
     const int lsteps = ((flags & KF_LIGHT_DIRECT) && light_steps == 8 && !v2_precise && !(flags & KF_VIEW_POS)) ? 8 : 0;
-    if (flags & KF_DETAIL) {   // atmo_render_detail_kernel<FLAGS, LSTEPS>
-        snprintf(name, sizeof(name), "atmo_render_detail_kernel<%d, %d>", flags, lsteps);
+    if (flags & KF_DETAIL) {   // atmo_render_detail_kernel<FLAGS, LSTEPS>; with KF_RAYS atmo_detail_rays_kernel, with KF_RAYS | KF_INDEX atmo_detail_rays_indexed_kernel
+        if (flags & KF_RAYS) snprintf(name, sizeof(name), (flags & KF_INDEX) ? "atmo_detail_rays_indexed_kernel<%d, %d>" : "atmo_detail_rays_kernel<%d, %d>", flags, lsteps);
+        else snprintf(name, sizeof(name), "atmo_render_detail_kernel<%d, %d>", flags, lsteps);
         return name;
     }
     if (flags & KF_RAYS) {   // atmo_shade_rays_kernel<FLAGS, LSTEPS>; with KF_INDEX atmo_shade_rays_indexed_kernel<FLAGS, LSTEPS>
@@ -4417,5 +4422,63 @@ hipError_t launch_ray_list(const float4 *rays, const uint32_t *count, uint32_t c
     hipLaunchKernelGGL(atmo_ray_list_tail_kernel, rays_grid, block, 0, stream, live, capacity, index, listed);
     return hipGetLastError();
 }
+
+// ---- cloud detail for caller-supplied rays (KF_RAYS | KF_DETAIL; include/atmo_ray_detail.h) ------------------------------------------------------------------
+// The three cloud families of the ray kernels once more, in their three call shapes -- plain, in quads under the declared sampler, through an index list --
+// with the cloud march of atmo_render_detail_kernel: shade_pixel under RAYS && DETAIL has ONE site of its own, the march_clouds call (its DETAIL && LANE
+// form: the detail fetch at the lane's sample position, marched from the ray's own model-space origin).  With raymarched light the light is evaluated in
+// place under both samplers, as in the detail draws: no lit-sample queue, no queue LDS.  DetailConsts travels behind RayConsts (and RayIndexConsts).
+// Launch bounds: the detail draws' (detail_min_waves).  Kernels of their own names (no older kernel's name is a substring of them, nor the reverse),
+// defined and instantiated here, behind every older kernel, which keep their code and their place in the code object (tools/isa_diff.py).
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(RAYS_BLOCK, detail_min_waves(FLAGS & ~(KF_RAYS | KF_INDEX))) void atmo_detail_rays_kernel(const RenderConsts rc, const RayConsts yc,
+                                                                                                                       const DetailConsts xc) {
+    static_assert((FLAGS & KF_RAYS) != 0 && (FLAGS & KF_DETAIL) != 0 && (FLAGS & KF_INDEX) == 0, "detail ray kernels carry KF_RAYS | KF_DETAIL");
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, 0, 0, nullptr, nullptr, nullptr, &xc, &yc);
+}
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(RAYS_BLOCK, detail_min_waves(FLAGS & ~(KF_RAYS | KF_INDEX))) void atmo_detail_rays_indexed_kernel(const RenderConsts rc, const RayConsts yc,
+                                                                                                                               const RayIndexConsts ic,
+                                                                                                                               const DetailConsts xc) {
+    static_assert((FLAGS & KF_RAYS) != 0 && (FLAGS & KF_DETAIL) != 0 && (FLAGS & KF_INDEX) != 0, "indexed detail ray kernels carry KF_RAYS | KF_INDEX | KF_DETAIL");
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, 0, 0, nullptr, nullptr, nullptr, &xc, &yc, &ic);
+}
+// the level-0 cloud families of ATMO_RAYS_FAMILIES; with KF_CUBE_LOD they are ATMO_RAY_QUADS_FAMILIES
+#define ATMO_RAYS_DETAIL_FAMILIES(ONE, LOD)              \
+    ONE((LOD) | KF_PRECISE | KF_CLOUDS)                      \
+    ONE((LOD) | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)  \
+    ONE((LOD) | KF_PRECISE | KF_LITE | KF_CLOUDS)
+// flags WITHOUT KF_RAYS | KF_INDEX | KF_DETAIL, which the launcher adds; ic == nullptr: the whole batch
+hipError_t launch_shade_rays_detail(int flags, const RenderConsts &rc, const RayConsts &yc, const DetailConsts &xc, const RayIndexConsts *ic, hipStream_t stream) {
+    if (yc.rays == nullptr || yc.out == nullptr || yc.n == 0 || yc.width == 0 || yc.first > 0xffffffffu - (yc.n - 1u)) return hipErrorInvalidValue;
+    if (ic != nullptr && (ic->index == nullptr || ic->n_index == 0)) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)(((uint64_t)(ic ? ic->n_index : yc.n) + (RAYS_BLOCK - 1)) / RAYS_BLOCK);   // at most 2^24
+    switch (flags) {
+#define ATMO_RAYS_DETAIL_LAUNCH(F)                                                                                                                             \
+    case (F):                                                                                                                                                  \
+        if (ic) hipLaunchKernelGGL((atmo_detail_rays_indexed_kernel<(F) | KF_RAYS | KF_INDEX | KF_DETAIL, 0>), dim3(blocks), dim3(RAYS_BLOCK), 0, stream, rc, yc, *ic, xc); \
+        else hipLaunchKernelGGL((atmo_detail_rays_kernel<(F) | KF_RAYS | KF_DETAIL, 0>), dim3(blocks), dim3(RAYS_BLOCK), 0, stream, rc, yc, xc);               \
+        return hipGetLastError();
+        ATMO_RAYS_DETAIL_FAMILIES(ATMO_RAYS_DETAIL_LAUNCH, 0)
+#undef ATMO_RAYS_DETAIL_LAUNCH
+    default: return hipErrorInvalidValue;
+    }
+}
+// flags WITH KF_CUBE_LOD; yc as launch_shade_ray_quads'
+hipError_t launch_shade_ray_quads_detail(int flags, const RenderConsts &rc, const RayConsts &yc, const DetailConsts &xc, hipStream_t stream) {
+    if (yc.rays == nullptr || yc.out == nullptr || yc.n == 0 || (yc.n & 3u) != 0 || yc.width == 0 || (uint64_t)yc.first + (yc.n >> 2) > ((uint64_t)1 << 30))
+        return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)(((uint64_t)yc.n + (RAYS_BLOCK - 1)) / RAYS_BLOCK);
+    switch (flags) {
+#define ATMO_RAY_QUADS_DETAIL_LAUNCH(F)                                                                                                          \
+    case (F):                                                                                                                                    \
+        hipLaunchKernelGGL((atmo_detail_rays_kernel<(F) | KF_RAYS | KF_DETAIL, 0>), dim3(blocks), dim3(RAYS_BLOCK), 0, stream, rc, yc, xc);      \
+        return hipGetLastError();
+        ATMO_RAYS_DETAIL_FAMILIES(ATMO_RAY_QUADS_DETAIL_LAUNCH, KF_CUBE_LOD)
+#undef ATMO_RAY_QUADS_DETAIL_LAUNCH
+    default: return hipErrorInvalidValue;
+    }
+}
+#undef ATMO_RAYS_DETAIL_FAMILIES
 
 }  // namespace atmo

@@ -357,7 +357,8 @@ class PlanetAtmosphere:
     @property
     def cloud_detail(self) -> bool:
         """The cloud variants with the reference's CLOUDS_ALWAYS_LOW_QUALITY off (include/atmo_cloud_detail.h): render / render_composite draw the detail
-        fetch, which moves with `time`; every other draw of a cloud variant is refused while it is on."""
+        fetch, which moves with `time`, and so do shade_rays (plain or through an index list) and shade_ray_quads (include/atmo_ray_detail.h); every other
+        draw of a cloud variant is refused while it is on."""
         return self._cloud_detail
 
     @cloud_detail.setter
@@ -681,13 +682,24 @@ class PlanetAtmosphere:
             raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_rays.h); rebuild it")
         return fn
 
+    def _ray_detail_entry(self, name: str):
+        """The entry point of include/atmo_ray_detail.h where this node's rays are shaded with cloud detail -- `cloud_detail` on and a shader with clouds --
+        else None: the call goes where it went before (a node without clouds has no density to evaluate)."""
+        if not (getattr(self, "_cloud_detail", False) and getattr(self, "_shader", DefaultShader).cloud_steps):
+            return None
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_ray_detail.h): no cloud detail for rays; rebuild it")
+        return fn
+
     def shade_rays(self, rays, camera=None, *, width=None, first: int = 0, out=None, stream=None, time: float = 0.0, index=None):
         """Shades caller-supplied rays: what atmosphere_fragment returns for a fragment with each ray (atmo_shade_rays; include/atmo_rays.h states the
         arithmetic).  `rays`: a contiguous CUDA float32 tensor of shape (n, 8), one N.AtmoRay a row -- origin xyz, tmax (the distance to the first
         opaque hit, FLT_MAX for none), dir xyz (unit length, used as given), one unused float.  `camera` supplies inv_view, the map from ray space
         to world space; None: ray space is world space.  Ray i is image index first + i of an image `width` wide (default: n), which picks its
         blue-noise jitter.  Returns or fills `out`, a contiguous CUDA float32 (n, 4) tensor: ALBEDO.rgb and ALPHA per ray, zeros for a ray that misses
-        the atmosphere.  The coverage cubemap is sampled at level 0.
+        the atmosphere.  The coverage cubemap is sampled at level 0; with `cloud_detail`, the detail fetch: the clouds are get_density_full's and move
+        with `time` (atmo_shade_rays_detail; include/atmo_ray_detail.h), plain or through `index`.
         `index` (a contiguous CUDA int32 (m,) tensor, `ray_order`'s or any list of ray numbers): the rays it names are shaded, 64 consecutive entries a
         wavefront, each to its own row of `out` with the bits the plain call gives it (atmo_shade_rays_indexed; include/atmo_ray_order.h); rows it does
         not name are left as they are -- zeros where `out` is created here."""
@@ -706,11 +718,16 @@ class PlanetAtmosphere:
             out = (torch.empty if index is None else torch.zeros)((n, 4), dtype=torch.float32, device=rays.device)
         elif _check_rays(out, "out", 4) != n:
             raise ValueError("out must have one row per ray: shape (n, 4)")
-        fn = self._rays_entry("atmo_shade_rays") if index is None else self._ray_order_entry("atmo_shade_rays_indexed")
+        fn = self._ray_detail_entry("atmo_shade_rays_detail")
+        detail = fn is not None
+        if not detail:
+            fn = self._rays_entry("atmo_shade_rays") if index is None else self._ray_order_entry("atmo_shade_rays_indexed")
         stream = _stream_handle(stream, rays)
         self._bake_if_needed(stream)
         nf = _to_native_frame(self.make_frame(camera if camera is not None else _WORLD_RAY_SPACE, time))
         listed = () if index is None else (C.c_void_p(index.data_ptr()), int(index.shape[0]))
+        if detail and index is None:   # atmo_shade_rays_detail: a null list is the whole batch
+            listed = (None, 0)
         N.check(self._ctx, fn(self._ctx, C.byref(nf), C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr()), n, width, first, *listed,
                               C.c_void_p(stream or 0)))
         return out
@@ -820,7 +837,8 @@ class PlanetAtmosphere:
         contiguous CUDA float32 tensor of shape (4 * n_quads, 8), one N.AtmoRay a row in quad order (ray_quads.quad_order) -- slot 4 q + j is the ray of
         pixel (2 (Q % qpr) + (j & 1), 2 (Q // qpr) + (j >> 1)) with Q = first_quad + q and qpr = (width + 1) // 2; an all-zero direction marks an absent
         ray.  `camera` as in `shade_rays`.  Returns or fills `out`, a contiguous CUDA float32 (4 * n_quads, 4) tensor in the same order (zeros for an
-        absent ray and for one that misses the atmosphere); ray_quads.quads_to_image puts a whole image's back into rows."""
+        absent ray and for one that misses the atmosphere); ray_quads.quads_to_image puts a whole image's back into rows.  The declared sampler; with
+        `cloud_detail`, the detail fetch as well, moving with `time` (atmo_shade_ray_quads_detail; include/atmo_ray_detail.h)."""
         n = _check_rays(quads, "quads", 8)
         if n % 4:
             raise ValueError("quads must have four rows per quad: shape (4 * n_quads, 8)")
@@ -836,7 +854,7 @@ class PlanetAtmosphere:
             out = torch.empty((n, 4), dtype=torch.float32, device=quads.device)
         elif _check_rays(out, "out", 4) != n:
             raise ValueError("out must have one row per ray: shape (4 * n_quads, 4)")
-        fn = getattr(self._lib, "atmo_shade_ray_quads", None)
+        fn = self._ray_detail_entry("atmo_shade_ray_quads_detail") or getattr(self._lib, "atmo_shade_ray_quads", None)
         if fn is None:
             raise RuntimeError("libatmo_hip.so does not export atmo_shade_ray_quads (include/atmo_ray_quads.h); rebuild it")
         stream = _stream_handle(stream, quads)

@@ -53,7 +53,8 @@ extern "C" {
  *   ATMO_E_STATE  every other draw entry point -- atmo_render_tiles[_split], atmo_measure_tile_costs, atmo_render_target and atmo_render_depth_target
  *                 (every format), the proxy draws, the view batches, atmo_render_planets and atmo_plan_planets (the message names the draw) -- where its
  *                 mode check stands; and atmo_render[_composite] themselves with atmo_set_precision 0 or 2, atmo_set_lane_split 2, the direct light
- *                 mode or more than 32 view steps.  The message names cloud detail.  Nothing is enqueued.
+ *                 mode or more than 32 view steps.  The message names cloud detail.  Nothing is enqueued.  (Ray batches, ray lists and ray quads of
+ *                 such a context: atmo_ray_detail.h.)
  */
 int atmo_set_cloud_detail(AtmoContext *ctx, int enable);
 int atmo_get_cloud_detail(AtmoContext *ctx, int *enabled);

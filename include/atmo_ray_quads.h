@@ -60,7 +60,7 @@ extern "C" {
  *   ATMO_OK       n_quads == 0: nothing is enqueued, nothing else is looked at
  *   ATMO_E_ARG    a null frame, rays_dev or rgba_dev; a pointer that is not 16-byte aligned; width == 0; first_quad + n_quads beyond 2^30
  *   ATMO_E_STATE  atmo_shade_rays' refusals in its order: atmo_set_precision 0 or 2; more than 32 view steps; atmo_set_lane_split 2; a cloud variant in the
- *                 direct light mode; a cloud variant with cloud detail on
+ *                 direct light mode; a cloud variant with cloud detail on (atmo_ray_detail.h has the entry point that shades it)
  *   ATMO_E_STATE  a variant without clouds: it has no texture call to difference (use atmo_shade_rays)
  *   ATMO_E_STATE  atmo_set_sampler_lod 0: level 0 is atmo_shade_rays' sampler
  *   ATMO_E_STATE  u_optical_depth_texture / u_cloud_shape_texture not set, as every draw; then, under atmo_set_sampler_lod -1 or 1: no mip chain of

@@ -67,7 +67,8 @@ typedef struct AtmoRay {      /* 32 bytes, the array 16-byte aligned */
  *   ATMO_OK       n_rays == 0: nothing is enqueued, nothing else is looked at
  *   ATMO_E_ARG    a null frame, rays_dev or rgba_dev; a pointer that is not 16-byte aligned; width == 0; first + n_rays beyond 2^32
  *   ATMO_E_STATE  (the message names the mode) atmo_set_precision 0 or 2; more than 32 view steps; atmo_set_lane_split 2; a cloud variant in the direct light
- *                 mode; a cloud variant with cloud detail on; atmo_set_sampler_lod 1 with a mip chain bound
+ *                 mode; a cloud variant with cloud detail on (atmo_ray_detail.h has the entry point that shades it); atmo_set_sampler_lod 1 with a mip
+ *                 chain bound
  *   ATMO_E_STATE  u_optical_depth_texture / u_cloud_shape_texture not set, as every draw
  */
 int atmo_shade_rays(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,

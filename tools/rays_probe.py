@@ -48,7 +48,20 @@ pose and family, every round in the order shuffled, order_indexed, cull_indexed,
   eighth_list         *count = capacity / 8: atmo_ray_list(ORDER | CULL) and the indexed call, both over the whole capacity;
   tail                the indexed call through a list of END entries alone: one index load per thread and nothing else.
 The baselines are kernels this library shares with its parent byte for byte (tools/isa_diff.py).  `bits_equal`: every list arm's picture against the
-shuffled arm's (eighth_list: against eighth_plain's, on the live rows)."""
+shuffled arm's (eighth_list: against eighth_plain's, on the live rows).
+
+The DETAIL table (--table detail --rounds 5; include/atmo_ray_detail.h), the three cloud families with atmo_set_cloud_detail 1, the frame from P_space and
+from P_limb, same timing.  Two contexts per pose and family, atmo_set_tile_feedback 0; every round in the order of DETAIL_ARMS:
+  render, rays             level-0 context: the detail draw (atmo_render_detail_kernel) and atmo_shade_rays_detail on the camera's rays in order;
+  shuffled                 the plain detail call on the fixed shuffled queue;
+  list_indexed             atmo_ray_list(ORDER | CULL), then the indexed detail call;
+  order_indexed            atmo_ray_order, then the indexed detail call;
+  render_off, rays_off     the same context with the switch off: atmo_render_kernel and atmo_shade_rays_kernel, for the on / off ratios;
+  render_q, quads          declared-sampler context: the detail draw and atmo_shade_ray_quads_detail on the camera's quads;
+  render_q_off, quads_off  the same with the switch off;
+  render2                  the level-0 detail draw again: the run-to-run spread.
+The pixel-side kernels are the parent commit's byte for byte (tools/isa_diff.py).  `bits_equal`: rays and quads against their draws, the two list arms
+against the shuffled arm."""
 import argparse
 import json
 import os
@@ -277,6 +290,116 @@ def list_rows(args, tex, out, perm):
     return poses
 
 
+DETAIL_FAMILIES = ("clouds_high", "clouds_high_rm", "v1_clouds")
+DETAIL_ARMS = ("render", "rays", "shuffled", "list_indexed", "order_indexed", "render_off", "rays_off", "render_q", "quads", "render_q_off", "quads_off",
+               "render2")
+
+
+def detail_rows(args, tex, out, perm):
+    """The DETAIL table's rows (the module's docstring)."""
+    import ctypes as C
+
+    from godot_atmosphere_shader_amd import _native as N
+    from godot_atmosphere_shader_amd.planet_atmosphere import _to_native_frame
+    from godot_atmosphere_shader_amd.ray_quads import quads_to_image
+
+    n = H * W
+    stats = lambda v: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)}   # noqa: E731
+    bits = lambda t: t.view(torch.int32)   # noqa: E731
+    frame = torch.empty((H, W, 4), dtype=torch.float32, device="cuda")
+    out2 = torch.empty_like(out)
+    poses = []
+    for pose in ("P_space", "P_limb"):
+        cam = S.Camera.from_pose(W, H, pose)
+        depth = torch.from_numpy(S.depth_ground_sphere(cam)).cuda()
+        entry = {"pose": pose, "rows": []}
+        for label in [f for f in args.families.split(",") if f in DETAIL_FAMILIES]:
+            config, kw = FAMILIES[label]
+            node = make_node(config, tex, cubemap_lod=False, tile_feedback=0, cloud_detail=True, **kw)   # level 0
+            qnode = make_node(config, tex, tile_feedback=0, cloud_detail=True, **kw)                     # the declared sampler, a chain bound
+            try:
+                rays = node.camera_rays(cam, depth)
+                shuffled = rays[perm].contiguous()
+                quads = qnode.camera_ray_quads(cam, depth)
+                qout = torch.empty((quads.shape[0], 4), dtype=torch.float32, device="cuda")
+                need = C.c_size_t()
+                N.check(node._ctx, node._lib.atmo_ray_list_scratch_bytes(n, C.byref(need)))
+                scratch = torch.empty(((need.value + 3) // 4,), dtype=torch.int32, device="cuda")
+                index = torch.empty((n,), dtype=torch.int32, device="cuda")
+                listed = torch.zeros((1,), dtype=torch.int32, device="cuda")
+                full = torch.tensor([n], dtype=torch.int32, device="cuda")
+                nf = _to_native_frame(node.make_frame(cam, 0.0))
+                stream = torch.cuda.current_stream().cuda_stream
+
+                def order():
+                    N.check(node._ctx, node._lib.atmo_ray_order(node._ctx, shuffled.data_ptr(), n, index.data_ptr(), scratch.data_ptr(), need.value, stream))
+
+                def build():
+                    N.check(node._ctx, node._lib.atmo_ray_list(node._ctx, C.byref(nf), shuffled.data_ptr(), full.data_ptr(), n, 3, out2.data_ptr(),
+                                                               index.data_ptr(), listed.data_ptr(), scratch.data_ptr(), need.value, stream))
+
+                def pair(first):
+                    first()
+                    node.shade_rays(shuffled, cam, out=out2, index=index)
+
+                calls = {"render": lambda: node.render(cam, depth, out=frame), "rays": lambda: node.shade_rays(rays, cam, width=W, out=out),
+                         "shuffled": lambda: node.shade_rays(shuffled, cam, out=out), "list_indexed": lambda: pair(build),
+                         "order_indexed": lambda: pair(order), "render_q": lambda: qnode.render(cam, depth, out=frame),
+                         "quads": lambda: qnode.shade_ray_quads(quads, cam, width=W, out=qout)}
+                for arm, on in (("render_off", "render"), ("rays_off", "rays"), ("render_q_off", "render_q"), ("quads_off", "quads")):
+                    calls[arm] = calls[on]
+                calls["render2"] = calls["render"]
+
+                def switch(arm):   # outside the timing: a host call
+                    node.cloud_detail = qnode.cloud_detail = not arm.endswith("_off")
+
+                names = {}
+                for arm in DETAIL_ARMS:
+                    switch(arm)
+                    timed(calls[arm], args.warmup)
+                    names[arm] = (qnode if arm in ("render_q", "quads", "render_q_off", "quads_off") else node).kernel_name
+                # the pictures, outside the timing
+                switch("render")
+                equal = {}
+                calls["render"]()
+                calls["rays"]()
+                equal["rays"] = bool(torch.equal(bits(frame.reshape(-1, 4)), bits(out)))
+                calls["render_q"]()
+                calls["quads"]()
+                equal["quads"] = bool(torch.equal(bits(frame), bits(quads_to_image(qout, W, H))))
+                calls["shuffled"]()
+                plain = out.clone()
+                for arm in ("list_indexed", "order_indexed"):
+                    out2.fill_(float("nan"))
+                    calls[arm]()
+                    equal[arm] = bool(torch.equal(bits(out2), bits(plain)))
+                t_warm = time.perf_counter()
+                while time.perf_counter() - t_warm < 0.025:   # sustained clocks
+                    calls["render"]()
+                    torch.cuda.synchronize()
+                arms = {a: [] for a in DETAIL_ARMS}
+                for _ in range(args.rounds):
+                    for arm in DETAIL_ARMS:
+                        switch(arm)
+                        arms[arm].append(timed(calls[arm], args.reps))
+            finally:
+                node.close()
+                qnode.close()
+            med = {a: sorted(v)[len(v) // 2] for a, v in arms.items()}
+            row = {"family": label, "kernels": names, "bits_equal": equal, "ms": {a: stats(v) for a, v in arms.items()},
+                   "rays_over_render": med["rays"] / med["render"], "quads_over_render_q": med["quads"] / med["render_q"],
+                   "shuffled_over_rays": med["shuffled"] / med["rays"], "list_indexed_over_shuffled": med["list_indexed"] / med["shuffled"],
+                   "order_indexed_over_shuffled": med["order_indexed"] / med["shuffled"],
+                   "on_over_off": {a: med[a] / med[a + "_off"] for a in ("render", "rays", "render_q", "quads")},
+                   "render2_over_render": med["render2"] / med["render"]}
+            entry["rows"].append(row)
+            print(f"{pose} {label:15s} " + "  ".join(f"{a} {med[a]:.4f}" for a in DETAIL_ARMS) + f"  rays / render {row['rays_over_render']:.3f}  quads / render_q "
+                  f"{row['quads_over_render_q']:.3f}  on / off {({a: round(v, 3) for a, v in row['on_over_off'].items()})}  bits equal: {equal}  "
+                  f"{names['rays']} / {names['quads']} / {names['order_indexed']}", file=sys.stderr, flush=True)
+        poses.append(entry)
+    return poses
+
+
 def timed(call, reps):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -294,7 +417,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--families", default=",".join(FAMILIES))
-    ap.add_argument("--table", choices=("rays", "quads", "both", "order", "list"), default="both")
+    ap.add_argument("--table", choices=("rays", "quads", "both", "order", "list", "detail"), default="both")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rays_probe.py measures on a device; none is visible")
@@ -309,6 +432,8 @@ def main():
         result["order_rows"] = order_rows(args, tex, cam, depth, frame, out, perm)
     if args.table == "list":
         result["list_poses"] = list_rows(args, tex, out, perm)
+    if args.table == "detail":
+        result["detail_poses"] = detail_rows(args, tex, out, perm)
     for label in args.families.split(",") if args.table in ("rays", "both") else ():
         config, kw = FAMILIES[label]
         node = make_node(config, tex, cubemap_lod=False, tile_feedback=0, **kw)   # atmo_set_sampler_lod 0, atmo_set_tile_feedback 0
