@@ -90,6 +90,10 @@ RAY_LIST_ORDER, RAY_LIST_CULL, RAY_LIST_END = 1, 2, 0xFFFFFFFF   # ATMO_RAY_LIST
 # rule: the ABI version stays 5, the tuple stands beside EXPORTED_SYMBOLS, load() binds it where the library has it (PlanetAtmosphere.shade_rays and
 # shade_ray_quads raise without, on a cloud node with cloud_detail on).
 RAY_DETAIL_SYMBOLS = ("atmo_shade_rays_detail", "atmo_shade_ray_quads_detail")
+# every symbol include/atmo_detail_target.h declares: the depth-source target draw and its view batch for a cloud context with cloud detail on.  The
+# RAYS_SYMBOLS rule: the ABI version stays 5, the tuple stands beside EXPORTED_SYMBOLS, load() binds it where the library has it (PlanetAtmosphere's
+# target draws raise without, on a cloud node with cloud_detail on).
+DETAIL_TARGET_SYMBOLS = ("atmo_render_detail_target", "atmo_render_views_detail_target")
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -375,6 +379,17 @@ def load() -> C.CDLL:
     }
     assert tuple(ray_detail_sig) == RAY_DETAIL_SYMBOLS
     for name, (res, args) in ray_detail_sig.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
+    # include/atmo_detail_target.h: the same rule
+    detail_target_sig = {
+        "atmo_render_detail_target": (ip, [vp, C.POINTER(AtmoFrame), C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), ip, vp]),
+        "atmo_render_views_detail_target": (ip, [vp, C.POINTER(AtmoViewDepthTarget), ip, ip, vp]),
+    }
+    assert tuple(detail_target_sig) == DETAIL_TARGET_SYMBOLS
+    for name, (res, args) in detail_target_sig.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype = res

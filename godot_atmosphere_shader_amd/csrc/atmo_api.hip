@@ -22,6 +22,7 @@
 #include "../../include/atmo_ray_order.h"
 #include "../../include/atmo_ray_list.h"
 #include "../../include/atmo_ray_detail.h"
+#include "../../include/atmo_detail_target.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -768,6 +769,12 @@ int cloud_detail_mode(AtmoContext *ctx, const std::string &who, int flags, int s
     if (split == 1 && atmo::detail_family_supported(flags)) return ATMO_OK;
     return fail(ctx, ATMO_E_STATE, who + ": no cloud-detail kernel for this context's mode (atmo_set_cloud_detail 1 draws the LUT-light cloud forms: "
                                          "atmo_set_precision 1, no direct light, up to 32 view steps, one lane per ray)");
+}
+// ... from the frame: launch_shape's family and split, where atmo_render's and atmo_render[_views]_detail_target's mode checks stand
+int cloud_detail_family(AtmoContext *ctx, const std::string &who, const AtmoFrame *frame) {
+    int flags = 0, split = 1;
+    launch_shape(ctx, frame, &flags, &split, nullptr);
+    return cloud_detail_mode(ctx, who, flags, split);
 }
 // The kernel's constants (atmo_cloud_detail.h: the arithmetic contract).  Host fp32, nothing fused (the build's -ffp-contract=off).
 atmo::DetailConsts cloud_detail_consts(const AtmoContext *ctx, const AtmoFrame *f, float *sub_hi_out = nullptr) {
@@ -1711,7 +1718,9 @@ struct TileList {
 };
 static constexpr TileList WHOLE_GRID = {nullptr, 0, 0};
 // sf: the entry point's (a target's already through target_check, which the caller runs; the depth is checked here, behind the empty rect)
-static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, DrawSurfaces sf, TileList tiles, void *stream);
+// detail_target: null, or the caller is atmo_render_detail_target (include/atmo_detail_target.h) and this is its name -- every message names it, it has run
+// the mode check of a cloud-detail draw itself, and such a draw goes to the detail target kernels
+static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, DrawSurfaces sf, TileList tiles, void *stream, const char *detail_target = nullptr);
 
 int atmo_render(AtmoContext *ctx, const AtmoFrame *frame, const float *depth_dev, float *rgba_dev, void *stream) {
     return render_impl(ctx, frame, float_surfaces(depth_dev, rgba_dev, false), WHOLE_GRID, stream);
@@ -2016,25 +2025,26 @@ static int launch_heavy_split(AtmoContext *ctx, const DrawSurfaces &sf, int flag
     return ATMO_OK;
 }
 
-static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, DrawSurfaces sf, TileList tiles, void *stream) {
-    // 1. checks (every message but the depth source's says atmo_render, whichever sibling called)
+static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, DrawSurfaces sf, TileList tiles, void *stream, const char *detail_target) {
+    // 1. checks (every message but the depth source's says atmo_render, whichever sibling called -- but atmo_render_detail_target, whose own name they say)
     if (!ctx) return ATMO_E_ARG;
+    const char *who = detail_target ? detail_target : "atmo_render";
     bool empty = false;
-    ATMO_TRY(check_frame(ctx, "atmo_render", frame, &empty));
+    ATMO_TRY(check_frame(ctx, who, frame, &empty));
     if (empty) return ATMO_OK;  // empty rect: nothing to shade
-    ATMO_TRY(check_surfaces(ctx, sf.kind == SURF_DEPTH ? "atmo_render_depth_target" : "atmo_render", frame, sf));
+    ATMO_TRY(check_surfaces(ctx, detail_target ? detail_target : sf.kind == SURF_DEPTH ? "atmo_render_depth_target" : "atmo_render", frame, sf));
     // cloud detail (include/atmo_cloud_detail.h): atmo_render[_composite] alone, in a mode that has the kernel.  A property of the context, so in front of the
     // textures' check: a context that cannot draw this way hears so whatever is bound.  (The siblings refuse at their own mode checks; a tile list, a
-    // measurement or a target that got here did not come through one.)
+    // measurement or a target that got here did not come through one.)  atmo_render_detail_target is the target draw that may: a depth source and a target
+    // of any format, whole grid; its mode check stood where atmo_render_depth_target's stands, in front of this function.
     const bool detail = cloud_detail_on(ctx);
-    if (detail) {
+    if (detail && !(detail_target && sf.kind == SURF_DEPTH && !tiles.dev && !ctx->measure_cost)) {
         if (tiles.dev || ctx->measure_cost || sf.kind != SURF_FLOAT || sf.target)
             return cloud_detail_refusal(ctx, "atmo_render", "tile lists, cost measurements or targets");
-        int dflags = 0, dsplit = 1;
-        launch_shape(ctx, frame, &dflags, &dsplit, nullptr);
-        ATMO_TRY(cloud_detail_mode(ctx, "atmo_render", dflags, dsplit));
+        ATMO_TRY(cloud_detail_family(ctx, "atmo_render", frame));
     }
-    ATMO_TRY(check_draw_textures(ctx, "atmo_render"));
+    ATMO_TRY(check_draw_textures(ctx, who));
+    if (detail_target && ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, std::string(who) + ": a host-only context has no device to draw on");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
     // 2. constants
@@ -2064,9 +2074,9 @@ static int render_impl(AtmoContext *ctx, const AtmoFrame *frame, DrawSurfaces sf
         TimingBracket timing;
         ATMO_TRY(timing_open(ctx, timing));
         ATMO_TRY(timing_begin(ctx, timing, s));
-        HIP_TRY(ctx, atmo::launch_render_detail(flags, rc, xc, s));
+        HIP_TRY(ctx, sf.kind == SURF_DEPTH ? atmo::launch_render_detail_target(flags, rc, sf.tc, sf.dc, xc, s) : atmo::launch_render_detail(flags, rc, xc, s));
         hipEvent_t marker = nullptr;
-        ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_DETAIL, 1, true, &marker));
+        ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_DETAIL | surface_family_bits(sf.kind), 1, true, &marker));
         return timing_end(ctx, timing, s);
     }
 
@@ -3069,6 +3079,18 @@ int atmo_render_depth_target(AtmoContext *ctx, const AtmoFrame *frame, const Atm
     return render_impl(ctx, frame, sf, WHOLE_GRID, stream);
 }
 
+// include/atmo_detail_target.h: atmo_render_depth_target with the cloud-detail refusal gone.  Detail in effect: the mode check is the detail families'
+// (a subset of the depth-source kernels' modes), and render_impl draws with the detail target kernels; not in effect: the call is atmo_render_depth_target
+int atmo_render_detail_target(AtmoContext *ctx, const AtmoFrame *frame, const AtmoDepth *depth, const AtmoTarget *target, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_detail_target";
+    DrawSurfaces sf = depth_target_surfaces(depth, target, composite != 0);
+    ATMO_TRY(target_check(ctx, who, frame, sf));
+    if (cloud_detail_on(ctx)) ATMO_TRY(cloud_detail_family(ctx, who, frame));
+    else ATMO_TRY(target_family(ctx, who, frame, true));
+    return render_impl(ctx, frame, sf, WHOLE_GRID, stream, who);
+}
+
 int atmo_render_proxy_depth_target(AtmoContext *ctx, const AtmoFrame *frame, const float *model_matrix, float box_size, const AtmoDepth *depth,
                                    const AtmoTarget *target, int composite, void *stream) {
     if (!ctx) return ATMO_E_ARG;
@@ -3125,6 +3147,7 @@ struct ViewsLayout {
     int flags = 0;
     int family = 0;                               // the kernel family the batch launches: flags | KF_VIEWS [| KF_TARGET] (a part of the feedback signature)
     bool lod = false;
+    bool serves_detail = false;                   // the caller is atmo_render_views_detail_target (views_family_grid)
     int n_drawn = 0;                              // views with a non-empty rect
     bool empty[ATMO_MAX_VIEWS];
     int gx0[ATMO_MAX_VIEWS], gy0[ATMO_MAX_VIEWS];  // each view's grid origin (its rect's, rounded down to even under the declared sampler)
@@ -3171,14 +3194,19 @@ int views_check_frames(AtmoContext *ctx, const char *who, bool have_views, const
     return ATMO_OK;
 }
 // The second half: the family (ATMO_E_STATE where no multi-view kernel exists; `kind`: the batch's surfaces) and the concatenated launch.
-int views_family_grid(AtmoContext *ctx, const char *who, const ViewDraw *args, int n_views, SurfaceKind kind, ViewsLayout &L) {
+// serves_detail: the caller is atmo_render_views_detail_target (include/atmo_detail_target.h), which draws a cloud-detail context -- a depth-source batch, the
+// detail families' mode check in place of the refusal, KF_DETAIL in L.family (views_enqueue reads it there)
+int views_family_grid(AtmoContext *ctx, const char *who, const ViewDraw *args, int n_views, SurfaceKind kind, ViewsLayout &L, bool serves_detail = false) {
     int split = 1;
-    ATMO_TRY(cloud_detail_refusal(ctx, who, "view batches"));
+    L.serves_detail = serves_detail;
+    const bool detail = serves_detail && cloud_detail_on(ctx);   // (kind is SURF_DEPTH, or SURF_FLOAT where every rect is empty and nothing is drawn)
+    if (!detail) ATMO_TRY(cloud_detail_refusal(ctx, who, "view batches"));
     ATMO_TRY(draw_family(ctx, args[0].frame, &L.flags, &split, &L.lod));
-    if (split != 1 || !atmo::default_family_supported(L.flags))
+    if (detail) ATMO_TRY(cloud_detail_mode(ctx, who, L.flags, split));
+    else if (split != 1 || !atmo::default_family_supported(L.flags))
         return fail(ctx, ATMO_E_STATE, std::string(who) + ": no multi-view kernel for this context's mode (they exist for the default forms: atmo_set_precision 1, "
                                                           "up to 32 view steps, one lane per ray)");
-    L.family = L.flags | atmo::KF_VIEWS | surface_family_bits(kind);
+    L.family = L.flags | atmo::KF_VIEWS | surface_family_bits(kind) | (detail ? atmo::KF_DETAIL : 0);
     int tw = 0, th = 0;
     atmo::render_tile_size(1, &tw, &th);
     uint64_t total = 0;
@@ -3280,6 +3308,7 @@ static int views_ring_slot_used(AtmoContext *ctx, AtmoContext::ViewsSlot *slot, 
 int views_enqueue(AtmoContext *ctx, const char *who, const ViewDraw *args, int n_views, SurfaceKind kind, const ViewsLayout &L, void *stream) {
     if (L.n_drawn == 0) return ATMO_OK;   // n_views == 0, or every rect empty: nothing to shade
     ATMO_TRY(check_draw_textures(ctx, who));
+    if (L.serves_detail && ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, std::string(who) + ": a host-only context has no device to draw on");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
     // the table the kernel reads is the context's and the next batch overwrites it: a replayed graph would shade with another batch's constants
@@ -3307,11 +3336,18 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewDraw *args, int n
     atmo::ViewsDepthConsts vdc;    // (read by the depth-source kernels only)
     std::memset(&vdc, 0, sizeof(vdc));
     for (int i = 0; kind == SURF_DEPTH && i < n_views; ++i) if (!L.empty[i]) vdc.depth[i] = args[i].sf.dc;
+    // a cloud-detail batch (views_family_grid: atmo_render_views_detail_target on a context that has it in effect): every view's own constants, c from its
+    // own frame's time; view-major -- no feedback state, no tile order, no cost recording, as render_impl's detail draw
+    const bool detail = (L.family & atmo::KF_DETAIL) != 0;
+    atmo::ViewsDetailConsts vxc;
+    std::memset(&vxc, 0, sizeof(vxc));
+    for (int i = 0; detail && i < n_views; ++i) if (!L.empty[i]) vxc.detail[i] = cloud_detail_consts(ctx, frames[i]);
     for (int i = 0; i <= ATMO_MAX_VIEWS; ++i) vc.first_block[i] = L.first_block[i];
     const uint32_t total = L.first_block[ATMO_MAX_VIEWS];
     // One tile order over all views, learnt as render_impl learns a single draw's on a still camera: feedback_plan's batch form
     bool feedback = ctx->env_feedback >= 0 ? ctx->env_feedback != 0 : ctx->tile_feedback != 0;
     if (total < 512u) feedback = false;   // tiny launches: nothing to schedule
+    if (detail) feedback = false;
     AtmoContext::FeedbackState *fb = nullptr;
     AtmoFeedbackPlanOut plan = {atmo::FB_ORDER_NONE, 0, 0, 0, 0, 0, 0.0f, 0};
     if (feedback) {
@@ -3325,7 +3361,8 @@ int views_enqueue(AtmoContext *ctx, const char *who, const ViewDraw *args, int n
     ATMO_TRY(timing_open(ctx, timing));
     HIP_TRY(ctx, hipMemcpyAsync(slot->dev, slot->host, (size_t)n_views * sizeof(atmo::RenderConsts), hipMemcpyHostToDevice, s));
     ATMO_TRY(timing_begin(ctx, timing, s));   // the bracket is the one launch's
-    HIP_TRY(ctx, launch_views(kind, L.flags, slot->host[first].light_steps, slot->dev, vtc, vdc, s));
+    if (detail) HIP_TRY(ctx, atmo::launch_render_views_detail_target(L.flags, slot->dev, vtc, vdc, vxc, s));
+    else HIP_TRY(ctx, launch_views(kind, L.flags, slot->host[first].light_steps, slot->dev, vtc, vdc, s));
     ATMO_TRY(timing_end(ctx, timing, s));
     ATMO_TRY(views_ring_slot_used(ctx, slot, s));
     if (plan.sort_side) ATMO_TRY(feedback_sort_side(ctx, *fb, (int)total, 1, plan, s));
@@ -3530,7 +3567,7 @@ int atmo_render_views(AtmoContext *ctx, const AtmoView *views, int n_views, int 
 // every target format draws with the KF_DEPTH kernels).  All argument checks (ATMO_E_ARG) in front of the mode check (ATMO_E_STATE), both in front of
 // anything that touches a device.
 extern "C++" template <class View>
-static int render_views_target(AtmoContext *ctx, const char *who, const View *views, int n_views, int composite, void *stream) {
+static int render_views_target(AtmoContext *ctx, const char *who, const View *views, int n_views, int composite, void *stream, bool serves_detail = false) {
     if (!ctx) return ATMO_E_ARG;
     ViewsLayout L;
     ViewDraws<View> args(views, n_views, composite);
@@ -3538,7 +3575,7 @@ static int render_views_target(AtmoContext *ctx, const char *who, const View *vi
     SurfaceKind kind = SURF_FLOAT;
     ATMO_TRY(views_target_outputs(ctx, who, views != nullptr, args.v, n_views, L, &done, &kind));
     if (done) return ATMO_OK;
-    ATMO_TRY(views_family_grid(ctx, who, args.v, n_views, kind, L));
+    ATMO_TRY(views_family_grid(ctx, who, args.v, n_views, kind, L, serves_detail));
     return views_enqueue(ctx, who, args.v, n_views, kind, L, stream);
 }
 int atmo_render_views_target(AtmoContext *ctx, const AtmoViewTarget *views, int n_views, int composite, void *stream) {
@@ -3546,6 +3583,10 @@ int atmo_render_views_target(AtmoContext *ctx, const AtmoViewTarget *views, int 
 }
 int atmo_render_views_depth_target(AtmoContext *ctx, const AtmoViewDepthTarget *views, int n_views, int composite, void *stream) {
     return render_views_target(ctx, "atmo_render_views_depth_target", views, n_views, composite, stream);
+}
+// include/atmo_detail_target.h: atmo_render_views_depth_target with the cloud-detail refusal gone
+int atmo_render_views_detail_target(AtmoContext *ctx, const AtmoViewDepthTarget *views, int n_views, int composite, void *stream) {
+    return render_views_target(ctx, "atmo_render_views_detail_target", views, n_views, composite, stream, true);
 }
 
 // include/atmo_views_proxy.h: the far-mode (proxy) batches.  Argument checks that need no matrix arithmetic (ATMO_E_ARG) in front of the mode check

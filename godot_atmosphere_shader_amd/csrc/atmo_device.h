@@ -278,6 +278,11 @@ struct ViewsProxyTargetConsts {
 struct ViewsDepthConsts {
     DepthConsts depth[MAX_VIEWS];          // entries of views without a tile and behind n_views are zero: no tile maps to them
 };
+// ... and every view's cloud-detail constants (atmo_render_views_detail_target, include/atmo_detail_target.h): c = RN(time * 0.01f) is the view's own frame's,
+// so there are eight DetailConsts, by value in the kernel-argument segment behind ViewsDepthConsts, indexed by the wave-uniform view number
+struct ViewsDetailConsts {
+    DetailConsts detail[MAX_VIEWS];        // entries of views without a tile and behind n_views are zero: no tile maps to them
+};
 
 hipError_t launch_render(int flags, int split, const RenderConsts &rc, hipStream_t stream, int tile_list_blocks = 0);  // > 0: rc.tile_order lists that many tiles of the rect's grid
 // Every launcher below draws the DEFAULT-FORM families (what a default context selects: one lane per ray, the precise cloud and v1 forms, up to 32 view
@@ -319,6 +324,13 @@ hipError_t launch_render_views_proxy_depth_target(int flags, int light_steps, co
 // one lane per ray, row-major over the grid of the rect in rc, no tile order and no cost recording; flags WITHOUT KF_DETAIL, which the launcher adds
 bool detail_family_supported(int flags);
 hipError_t launch_render_detail(int flags, const RenderConsts &rc, const DetailConsts &xc, hipStream_t stream);
+// ... into a colour target of any of the seven formats, reading a depth source (atmo_render_detail_target, atmo_render_views_detail_target;
+// include/atmo_detail_target.h): the same six families (detail_family_supported) with the KF_DETAIL | KF_DEPTH | KF_TARGET kernels, the single draw row-major
+// over the rect's grid as launch_render_detail, the batch view-major over the concatenation of the views' grids as launch_render_views_depth_target without a
+// tile order or a cost map (vtc.v.order and vtc.v.cost must be null); flags WITHOUT the four entry-point bits, which the launchers add
+hipError_t launch_render_detail_target(int flags, const RenderConsts &rc, const TargetConsts &tc, const DepthConsts &dc, const DetailConsts &xc, hipStream_t stream);
+hipError_t launch_render_views_detail_target(int flags, const RenderConsts *table_dev, const ViewsTargetConsts &vtc, const ViewsDepthConsts &vdc,
+                                             const ViewsDetailConsts &vxc, hipStream_t stream);
 // the ray draws (atmo_shade_rays; include/atmo_rays.h): six families (rays_family_supported; the direct-light one with 8 light steps unrolled or any count),
 // 64 consecutive rays per wave, 256 per workgroup, row-major over the batch; flags WITHOUT KF_RAYS, which the launcher adds
 bool rays_family_supported(int flags);

@@ -2213,8 +2213,12 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
                                             const TargetConsts *tc = nullptr, const DepthConsts *dc = nullptr, const DetailConsts *xc = nullptr,
                                             const RayConsts *yc = nullptr, const RayIndexConsts *ic = nullptr) {
     constexpr bool DETAIL = (FLAGS & KF_DETAIL) != 0;   // the cloud march with CLOUDS_ALWAYS_LOW_QUALITY off, through *xc
-    static_assert(!DETAIL || ((FLAGS & ~(KF_DETAIL | KF_CUBE_LOD | KF_CLOUD_LIGHT_RM | KF_LITE | KF_RAYS | KF_INDEX)) == (KF_PRECISE | KF_CLOUDS) && SPLIT == 1),
-                  "cloud detail: the LUT-light precise cloud families, float output, one lane per ray (with KF_RAYS: atmo_detail_rays_kernel)");
+    static_assert(!DETAIL || ((FLAGS & ~(KF_DETAIL | KF_CUBE_LOD | KF_CLOUD_LIGHT_RM | KF_LITE | KF_RAYS | KF_INDEX | KF_TARGET | KF_DEPTH | KF_VIEWS)) == (KF_PRECISE | KF_CLOUDS) && SPLIT == 1),
+                  "cloud detail: the LUT-light precise cloud families, one lane per ray (with KF_RAYS: atmo_detail_rays_kernel; with KF_DEPTH | KF_TARGET [| KF_VIEWS]: "
+                  "atmo_detail_target_kernel, atmo_detail_views_target_kernel)");
+    static_assert(!DETAIL || (((FLAGS & KF_TARGET) != 0) == ((FLAGS & KF_DEPTH) != 0) && ((FLAGS & KF_VIEWS) == 0 || (FLAGS & KF_DEPTH) != 0) &&
+                              ((FLAGS & KF_RAYS) == 0 || (FLAGS & KF_DEPTH) == 0)),
+                  "cloud detail into targets: through a depth source, every target format (KF_DEPTH | KF_TARGET); view batches only so; never with KF_RAYS");
     constexpr bool RAYS = (FLAGS & KF_RAYS) != 0;   // a ray of the caller's per lane, through *yc
     constexpr bool INDEXED = (FLAGS & KF_INDEX) != 0;   // ... the ray an index list names, through *ic (atmo_shade_rays_indexed)
     static_assert(!INDEXED || (RAYS && (FLAGS & KF_CUBE_LOD) == 0), "index lists: the level-0 ray kernels (ray quads have no indexed form)");
@@ -2727,11 +2731,11 @@ constexpr int views_min_waves(int flags) {
     return ((flags & KF_CLOUDS) && !(flags & (KF_CLOUD_LIGHT_RM | KF_CUBE_LOD))) ? 8 : render_min_waves(flags);
 }
 // The body of the six view-batch kernels, textually the same in all of them for the reason ATMO_RENDER_KERNEL_BODY is.  V: the kernel argument that holds
-// first_block (and, ORDERED = 1, the tile order and the cost map; the proxy batches have neither: 0); PROXY, TARGET, DEPTH: shade_pixel's arguments behind
+// first_block (and, ORDERED = 1, the tile order and the cost map; the proxy and the detail batches have neither: 0); PROXY, TARGET, DEPTH, DETAIL: shade_pixel's arguments behind
 // the tile, each the view's entry of an array in the kernel-argument segment or nullptr.
 #define ATMO_VIEWS_ORDERED_0(...)
 #define ATMO_VIEWS_ORDERED_1(...) __VA_ARGS__
-#define ATMO_VIEWS_KERNEL_BODY(V, ORDERED, PROXY, TARGET, DEPTH)                                                                       \
+#define ATMO_VIEWS_KERNEL_BODY(V, ORDERED, PROXY, TARGET, DEPTH, DETAIL)                                                               \
     uint32_t tile = blockIdx.x;                                                                                                        \
     ATMO_VIEWS_ORDERED_##ORDERED(if (V.order != nullptr) tile = V.order[tile];)                                                        \
     uint32_t view = 0; /* the last view whose first block is <= tile (empty views share their successor's first block and are stepped over) */ \
@@ -2741,7 +2745,7 @@ constexpr int views_min_waves(int flags) {
     const uint32_t local = tile - V.first_block[view];                                                                                 \
     const uint32_t tile_y = local / (uint32_t)rc.tiles_x, tile_x = local - tile_y * (uint32_t)rc.tiles_x;                              \
     ATMO_VIEWS_ORDERED_##ORDERED(uint64_t t0 = 0; if (V.cost != nullptr) t0 = __builtin_amdgcn_s_memtime();)                           \
-    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, PROXY, TARGET, DEPTH);                                                 \
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)tile_x, (int)tile_y, PROXY, TARGET, DEPTH, DETAIL);                                         \
     ATMO_VIEWS_ORDERED_##ORDERED(if (V.cost != nullptr && (threadIdx.x & 63) == 0) {                                                   \
         const uint64_t dt = __builtin_amdgcn_s_memtime() - t0;                                                                         \
         atomicMax(&V.cost[tile], (uint32_t)(dt > 0xffffffffull ? 0xffffffffull : dt));                                                 \
@@ -2752,7 +2756,7 @@ __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_r
     // the headline kernel's twin <KF_VIEWS | KF_LIGHT_DIRECT, 8>: its view loop on ITS fast position, FAST_PHASE (20) bytes into a 32-byte block, as the float kernel's
     // (march_atmosphere; tools/loop_phase.py reads it, tests/test_kernel_twins_host.py holds it there)
     if constexpr (FLAGS == (KF_VIEWS | KF_LIGHT_DIRECT) && LSTEPS == 8) ATMO_HEAD_PAD(ATMO_LOOP_PAD_VIEWS);
-    ATMO_VIEWS_KERNEL_BODY(vc, 1, nullptr, nullptr, nullptr)
+    ATMO_VIEWS_KERNEL_BODY(vc, 1, nullptr, nullptr, nullptr, nullptr)
 }
 
 // The packed-target draws (KF_TARGET; atmo_render_target / atmo_render_proxy_target, include/atmo_target.h): the bodies of the two kernels above with the
@@ -2795,7 +2799,7 @@ __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_r
     // the headline kernel's twin <KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT, 8>: its view loop on ITS fast position, FAST_PHASE (20) bytes into a 32-byte block, as the
     // other twins' (march_atmosphere; tools/loop_phase.py reads it, tests/test_kernel_twins_host.py holds it there)
     if constexpr (FLAGS == (KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8) ATMO_HEAD_PAD(ATMO_LOOP_PAD_VIEWS_TARGET);
-    ATMO_VIEWS_KERNEL_BODY(vtc.v, 1, nullptr, &vtc.target[view], nullptr)
+    ATMO_VIEWS_KERNEL_BODY(vtc.v, 1, nullptr, &vtc.target[view], nullptr, nullptr)
 }
 // Several far-mode (proxy) views in one launch (KF_VIEWS | KF_PROXY [| KF_TARGET]; atmo_render_views_proxy[_target], include/atmo_views_proxy.h): the view
 // lookup of atmo_render_views_kernel in front of the proxy draw's shade_pixel.  table[view] carries the view's CUT rectangle -- the box's screen rectangle
@@ -2808,14 +2812,14 @@ template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_proxy_kernel(const RenderConsts *__restrict__ table,
                                                                                                         const ViewsProxyConsts vpc) {
     static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) == 0, "multi-view proxy kernels carry KF_VIEWS | KF_PROXY");
-    ATMO_VIEWS_KERNEL_BODY(vpc, 0, &vpc.proxy[view], nullptr, nullptr)
+    ATMO_VIEWS_KERNEL_BODY(vpc, 0, &vpc.proxy[view], nullptr, nullptr, nullptr)
 }
 template <int FLAGS, int LSTEPS>
 __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_render_views_proxy_target_kernel(const RenderConsts *__restrict__ table,
                                                                                                                const ViewsProxyTargetConsts vptc) {
     static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0,
                   "multi-view proxy target kernels carry KF_VIEWS | KF_PROXY | KF_TARGET");
-    ATMO_VIEWS_KERNEL_BODY(vptc.p, 0, &vptc.p.proxy[view], &vptc.target[view], nullptr)
+    ATMO_VIEWS_KERNEL_BODY(vptc.p, 0, &vptc.p.proxy[view], &vptc.target[view], nullptr, nullptr)
 }
 
 // Stable counting sort of the tiles by the cost a recording draw measured, heaviest class first; clears the costs for
@@ -3710,6 +3714,8 @@ const char *render_kernel_name(int flags, int light_steps, int split) {
     const int lsteps = ((flags & KF_LIGHT_DIRECT) && light_steps == 8 && !v2_precise && !(flags & KF_VIEW_POS)) ? 8 : 0;
     if (flags & KF_DETAIL) {   // atmo_render_detail_kernel<FLAGS, LSTEPS>; with KF_RAYS atmo_detail_rays_kernel, with KF_RAYS | KF_INDEX atmo_detail_rays_indexed_kernel
         if (flags & KF_RAYS) snprintf(name, sizeof(name), (flags & KF_INDEX) ? "atmo_detail_rays_indexed_kernel<%d, %d>" : "atmo_detail_rays_kernel<%d, %d>", flags, lsteps);
+        // with KF_DEPTH | KF_TARGET atmo_detail_target_kernel, with KF_VIEWS as well atmo_detail_views_target_kernel (include/atmo_detail_target.h)
+        else if (flags & KF_DEPTH) snprintf(name, sizeof(name), (flags & KF_VIEWS) ? "atmo_detail_views_target_kernel<%d, %d>" : "atmo_detail_target_kernel<%d, %d>", flags, lsteps);
         else snprintf(name, sizeof(name), "atmo_render_detail_kernel<%d, %d>", flags, lsteps);
         return name;
     }
@@ -3799,7 +3805,7 @@ __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_r
                                                                                                                const ViewsDepthConsts vdc) {
     static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0, "KF_DEPTH | KF_VIEWS | KF_TARGET");
     if constexpr (FLAGS == (KF_DEPTH | KF_VIEWS | KF_TARGET | KF_LIGHT_DIRECT) && LSTEPS == 8) ATMO_HEAD_PAD(ATMO_LOOP_PAD_DEPTH_VIEWS);
-    ATMO_VIEWS_KERNEL_BODY(vtc.v, 1, nullptr, &vtc.target[view], &vdc.depth[view])
+    ATMO_VIEWS_KERNEL_BODY(vtc.v, 1, nullptr, &vtc.target[view], &vdc.depth[view], nullptr)
 }
 // (unpadded, as every proxy kernel)
 template <int FLAGS, int LSTEPS>
@@ -3807,7 +3813,7 @@ __global__ __launch_bounds__(TILE_W *TILE_H, views_min_waves(FLAGS)) void atmo_r
     const RenderConsts *__restrict__ table, const ViewsProxyTargetConsts vptc, const ViewsDepthConsts vdc) {
     static_assert((FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_PROXY) != 0 && (FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0,
                   "KF_DEPTH | KF_VIEWS | KF_PROXY | KF_TARGET");
-    ATMO_VIEWS_KERNEL_BODY(vptc.p, 0, &vptc.p.proxy[view], &vptc.target[view], &vdc.depth[view])
+    ATMO_VIEWS_KERNEL_BODY(vptc.p, 0, &vptc.p.proxy[view], &vptc.target[view], &vdc.depth[view], nullptr)
 }
 
 // their launches: those of the four packed-target draws
@@ -3900,7 +3906,7 @@ hipError_t launch_render_detail(int flags, const RenderConsts &rc, const DetailC
     default: return hipErrorInvalidValue;
     }
 }
-#undef ATMO_DETAIL_FAMILIES
+// (ATMO_DETAIL_FAMILIES stays defined: the detail target kernels at the end of the file launch from the same list)
 
 // ---- caller-supplied rays (KF_RAYS; include/atmo_rays.h states the arithmetic item by item) ---------------------------------------------------------
 // shade_pixel in its RAYS mode, for a ray that did not come out of a camera matrix: origin, direction and distance limit are an AtmoRay's, the planet
@@ -4480,5 +4486,62 @@ hipError_t launch_shade_ray_quads_detail(int flags, const RenderConsts &rc, cons
     }
 }
 #undef ATMO_RAYS_DETAIL_FAMILIES
+
+// ---- cloud detail into colour targets through a depth source (KF_DETAIL | KF_DEPTH | KF_TARGET [| KF_VIEWS]; include/atmo_detail_target.h) -----------------
+// The six families of ATMO_DETAIL_FAMILIES once more, as a single draw and as a view batch: atmo_render_detail_kernel's shading -- shade_pixel's DETAIL form,
+// the light in place under both samplers, no queue LDS -- with the depth read through load_depth (DepthConsts) and the store, or the composite's decode /
+// blend / encode, through store_target in all seven formats (TargetConsts).  shade_pixel states none of it a second time: the three forms meet in its
+// arguments.  Single draw: row-major over the rect's grid, as atmo_render_detail_kernel.  Batch: ATMO_VIEWS_KERNEL_BODY in its unordered form (no tile
+// order, no cost map: the detail draws learn none), view-major; c = RN(time * 0.01f) is each view's own frame's, so the eight DetailConsts sit by value in
+// the kernel-argument segment behind ViewsDepthConsts and are indexed by the wave-uniform view number, as ViewsTargetConsts::target: scalar loads.
+// Launch bounds: the detail draws' (detail_min_waves).  Kernels of their own names (no older kernel's name is a substring of them, nor the reverse),
+// defined and instantiated here, behind every older kernel, which keep their code and their place in the code object (tools/isa_diff.py).
+// profiles/cloud_detail/README.md has the register table against both twins.
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H, detail_min_waves(FLAGS)) void atmo_detail_target_kernel(const RenderConsts rc, const TargetConsts tc, const DepthConsts dc,
+                                                                                                    const DetailConsts xc) {
+    static_assert((FLAGS & KF_DETAIL) != 0 && (FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0 && (FLAGS & KF_VIEWS) == 0, "KF_DETAIL | KF_DEPTH | KF_TARGET");
+    shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, nullptr, &tc, &dc, &xc);
+}
+// The view's DetailConsts BY VALUE for the length of the shade_pixel call (a temporary of the call's full expression): three scalars read once from the
+// kernel-argument segment.  Handed on as a pointer into that segment, `full ? xc->shape_hi_d : rc.shape_hi01` -- both operands in memory here, the second in
+// the table -- became a per-lane select of two ADDRESSES and a flat load of the bound at every light tap of <15411, 0> (two vector loads more inside its
+// loops than its twin has: tools/twin_resources.py); a value cannot be selected by address
+struct DetailByValue {
+    DetailConsts xc;
+    __device__ __forceinline__ const DetailConsts *get() const { return &xc; }
+};
+template <int FLAGS, int LSTEPS>
+__global__ __launch_bounds__(TILE_W *TILE_H, detail_min_waves(FLAGS)) void atmo_detail_views_target_kernel(const RenderConsts *__restrict__ table,
+                                                                                                          const ViewsTargetConsts vtc, const ViewsDepthConsts vdc,
+                                                                                                          const ViewsDetailConsts vxc) {
+    static_assert((FLAGS & KF_DETAIL) != 0 && (FLAGS & KF_VIEWS) != 0 && (FLAGS & KF_TARGET) != 0 && (FLAGS & KF_DEPTH) != 0,
+                  "KF_DETAIL | KF_DEPTH | KF_VIEWS | KF_TARGET");
+    ATMO_VIEWS_KERNEL_BODY(vtc.v, 0, nullptr, &vtc.target[view], &vdc.depth[view], DetailByValue{vxc.detail[view]}.get())
+}
+// flags WITHOUT KF_DETAIL | KF_DEPTH | KF_TARGET [| KF_VIEWS], which the launchers add
+hipError_t launch_render_detail_target(int flags, const RenderConsts &rc, const TargetConsts &tc, const DepthConsts &dc, const DetailConsts &xc, hipStream_t stream) {
+    if (rc.tile_order != nullptr || rc.tile_cost != nullptr) return hipErrorInvalidValue;   // row-major, nothing recorded
+    if (tc.pixels == nullptr || tc.pitch_bytes <= 0 || !target_format_known(tc.format) || !depth_consts_valid(dc)) return hipErrorInvalidValue;
+    switch (flags) {
+#define ATMO_DETAIL_TARGET_LAUNCH(F) case (F): return launch_rect(atmo_detail_target_kernel<(F) | KF_DETAIL | KF_DEPTH | KF_TARGET, 0>, rc, stream, tc, dc, xc);
+        ATMO_DETAIL_FAMILIES(ATMO_DETAIL_TARGET_LAUNCH)
+#undef ATMO_DETAIL_TARGET_LAUNCH
+    default: return hipErrorInvalidValue;
+    }
+}
+hipError_t launch_render_views_detail_target(int flags, const RenderConsts *table, const ViewsTargetConsts &vtc, const ViewsDepthConsts &vdc,
+                                             const ViewsDetailConsts &vxc, hipStream_t stream) {
+    if (vtc.v.order != nullptr || vtc.v.cost != nullptr) return hipErrorInvalidValue;   // view-major, nothing recorded
+    if (!batch_targets_valid(vtc.v.first_block, vtc.target, vdc.depth)) return hipErrorInvalidValue;
+    switch (flags) {
+#define ATMO_DETAIL_VIEWS_TARGET_LAUNCH(F) \
+    case (F): return launch_batch(atmo_detail_views_target_kernel<(F) | KF_DETAIL | KF_DEPTH | KF_VIEWS | KF_TARGET, 0>, vtc.v.first_block, table, stream, vtc, vdc, vxc);
+        ATMO_DETAIL_FAMILIES(ATMO_DETAIL_VIEWS_TARGET_LAUNCH)
+#undef ATMO_DETAIL_VIEWS_TARGET_LAUNCH
+    default: return hipErrorInvalidValue;
+    }
+}
+#undef ATMO_DETAIL_FAMILIES
 
 }  // namespace atmo

@@ -357,7 +357,9 @@ class PlanetAtmosphere:
     @property
     def cloud_detail(self) -> bool:
         """The cloud variants with the reference's CLOUDS_ALWAYS_LOW_QUALITY off (include/atmo_cloud_detail.h): render / render_composite draw the detail
-        fetch, which moves with `time`, and so do shade_rays (plain or through an index list) and shade_ray_quads (include/atmo_ray_detail.h); every other
+        fetch, which moves with `time`, and so do shade_rays (plain or through an index list) and shade_ray_quads (include/atmo_ray_detail.h), and -- into
+        packed or pitched colour tensors, or from a `depth_source(...)` -- render, render_composite, draw and the target forms of render_views / draw_views
+        (atmo_render_detail_target, atmo_render_views_detail_target; include/atmo_detail_target.h); every other
         draw of a cloud variant is refused while it is on."""
         return self._cloud_detail
 
@@ -665,10 +667,16 @@ class PlanetAtmosphere:
         tgt = _colour_target(colour, rows, cols, "scene_rgba" if composite else "out", target)
         if src is not None and tgt is None:   # the depth-source entry points take every colour tensor as an N.AtmoTarget
             tgt = N.AtmoTarget(colour.data_ptr(), N.TARGET_RGBA32F, 0)
+        # cloud detail into a packed or pitched colour tensor, or from a depth source (include/atmo_detail_target.h): one entry point, which takes both as
+        # structures -- a plain depth tensor is a tight D32 source.  Float colour with float depth stays atmo_render; the proxy draws have no detail form
+        fn = self._detail_target_entry("atmo_render_detail_target") if proxy is None and tgt is not None else None
+        if fn is not None and src is None:
+            src = N.AtmoDepth(depth.data_ptr(), N.DEPTH_D32_SFLOAT, 0)
         stream = _stream_handle(stream, depth)
         self._bake_if_needed(stream)
         nf = _to_native_frame(frame)
-        fn = getattr(self._lib, _SINGLE_DRAWS[proxy is not None, tgt is not None, src is not None][bool(composite)])
+        if fn is None:
+            fn = getattr(self._lib, _SINGLE_DRAWS[proxy is not None, tgt is not None, src is not None][bool(composite)])
         box = () if proxy is None else (proxy[0], C.c_float(proxy[1]))
         where = (C.c_void_p(colour.data_ptr()),) if tgt is None else (C.byref(tgt), int(composite))
         depth_arg = C.c_void_p(depth.data_ptr()) if src is None else C.byref(src)
@@ -680,6 +688,16 @@ class PlanetAtmosphere:
         fn = getattr(self._lib, name, None)
         if fn is None:
             raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_rays.h); rebuild it")
+        return fn
+
+    def _detail_target_entry(self, name: str):
+        """The entry point of include/atmo_detail_target.h where this node's target draws are shaded with cloud detail -- `cloud_detail` on and a shader
+        with clouds --, else None: the call goes where it went before."""
+        if not (getattr(self, "_cloud_detail", False) and getattr(self, "_shader", DefaultShader).cloud_steps):
+            return None
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_detail_target.h): no cloud detail into targets; rebuild it")
         return fn
 
     def _ray_detail_entry(self, name: str):
@@ -984,13 +1002,20 @@ class PlanetAtmosphere:
         stream = _stream_handle(stream, depths[0])
         depth_ptrs = [d.data_ptr() for d in depths] if not sources[0] else srcs
         packed = sources[0] or any(t is not None for t in tgts)   # (the depth-source batches take every colour tensor as an N.AtmoTarget)
+        # cloud detail into targets (include/atmo_detail_target.h): the depth-source batch's structures, plain depth tensors as tight D32 sources.  The
+        # float-only batch and the proxy batches have no detail form and refuse as before
+        fn = self._detail_target_entry("atmo_render_views_detail_target") if proxy is None and packed else None
+        if fn is not None and not sources[0]:
+            depth_ptrs = [N.AtmoDepth(p, N.DEPTH_D32_SFLOAT, 0) for p in depth_ptrs]
         if packed:   # one batch, one struct: a contiguous float32 tensor among pitched ones is an RGBA32F target without a pitch
             tgts = [t if t is not None else N.AtmoTarget(o.data_ptr(), N.TARGET_RGBA32F, 0) for t, o in zip(tgts, outs)]
-            prepare = self.prepare_views_depth_target if sources[0] else self.prepare_views_target
+            prepare = self.prepare_views_depth_target if sources[0] or fn is not None else self.prepare_views_target
             views = prepare(cameras, depth_ptrs, tgts, rects, time)
         else:
             views = self.prepare_views(cameras, depth_ptrs, [o.data_ptr() for o in outs], rects, time)
-        self._enqueue_views(getattr(self._lib, _BATCH_DRAWS[proxy is not None, packed, sources[0]]), views, n, proxy, composite, stream)
+        if fn is None:
+            fn = getattr(self._lib, _BATCH_DRAWS[proxy is not None, packed, sources[0]])
+        self._enqueue_views(fn, views, n, proxy, composite, stream)
         return outs
 
     # ---- several far-mode views in one launch (include/atmo_views_proxy.h) -----------------------------------------------------------

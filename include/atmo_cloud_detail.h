@@ -54,7 +54,8 @@ extern "C" {
  *                 (every format), the proxy draws, the view batches, atmo_render_planets and atmo_plan_planets (the message names the draw) -- where its
  *                 mode check stands; and atmo_render[_composite] themselves with atmo_set_precision 0 or 2, atmo_set_lane_split 2, the direct light
  *                 mode or more than 32 view steps.  The message names cloud detail.  Nothing is enqueued.  (Ray batches, ray lists and ray quads of
- *                 such a context: atmo_ray_detail.h.)
+ *                 such a context: atmo_ray_detail.h.  Packed and pitched colour targets and depth sources, single draws and view batches:
+ *                 atmo_detail_target.h.)
  */
 int atmo_set_cloud_detail(AtmoContext *ctx, int enable);
 int atmo_get_cloud_detail(AtmoContext *ctx, int *enabled);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Static check of every render-kernel family that was added beside an older "twin" (the view batches, the proxy batches, the depth-source kernels),
-in the ISA hipcc emits -- no GPU needed.  These kernels take their per-view or per-target constants from somewhere else than their twins do (a device
+"""Static check of every render-kernel family that was added beside an older "twin" (the view batches, the proxy batches, the depth-source kernels, the
+cloud-detail target kernels), in the ISA hipcc emits -- no GPU needed.  These kernels take their per-view or per-target constants from somewhere else than their twins do (a device
 table, arrays by value in the kernel-argument segment indexed by the wave-uniform view number, a DepthConsts argument of its own); what must hold for
 that to cost nothing:
 
@@ -29,7 +29,7 @@ from typing import NamedTuple
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "godot_atmosphere_shader_amd", "csrc", "atmo_kernels.hip")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-S", "--cuda-device-only"]
-KF_PROXY, KF_TARGET, KF_VIEWS, KF_DEPTH = 512, 1024, 2048, 4096   # the family bits of KernelFlags (csrc/atmo_device.h)
+KF_PROXY, KF_TARGET, KF_VIEWS, KF_DEPTH, KF_DETAIL = 512, 1024, 2048, 4096, 8192   # the family bits of KernelFlags (csrc/atmo_device.h)
 # Lane reads a kernel may have beyond its twin's.  Chosen, not derived: the shipped build's largest difference is 21 (<5139, 0, 1>: 62 against 41; the next
 # is 14), the failure this check exists for was 150-300 beyond the twin in sixteen kernels.  24 passes the former and catches the latter with a factor of
 # six to spare; a build that fails here by a few reads has to be measured (tools/depth_probe.py), not waved through by raising the number.
@@ -57,15 +57,21 @@ FAMILIES = (
     Family("atmo_render_views_depth_target_kernel", KF_DEPTH | KF_VIEWS | KF_TARGET, False, (("atmo_render_views_target_kernel", KF_VIEWS | KF_TARGET),), True, 18),
     Family("atmo_render_views_proxy_depth_target_kernel", KF_DEPTH | KF_VIEWS | KF_PROXY | KF_TARGET, False,
            (("atmo_render_views_proxy_target_kernel", KF_VIEWS | KF_PROXY | KF_TARGET),), True, 18),
+    # cloud detail into targets through a depth source (include/atmo_detail_target.h): the shading -- and with it the loop loads and the occupancy step to
+    # keep -- is the detail draw's, the depth load and the stores are the depth-target kernels'
+    Family("atmo_detail_target_kernel", KF_DETAIL | KF_DEPTH | KF_TARGET, False,
+           (("atmo_render_detail_kernel", KF_DETAIL), ("atmo_render_depth_target_kernel", KF_DEPTH | KF_TARGET)), True, 6),
+    Family("atmo_detail_views_target_kernel", KF_DETAIL | KF_DEPTH | KF_VIEWS | KF_TARGET, False,
+           (("atmo_render_detail_kernel", KF_DETAIL), ("atmo_render_views_depth_target_kernel", KF_DEPTH | KF_VIEWS | KF_TARGET)), True, 6),
 )
 NUMBERS = ("vgprs", "sgprs", "loop_vector", "loop_scalar", "spill_reads", "scratch")
 _BB = re.compile(r"^(\.LBB\d+_\d+:|; %bb\.\d+:)")
-_NAME = re.compile(r"_ZN4atmo\d+(atmo_render_(?:[a-z_]+_)?kernel)ILi(\d+)ELi(\d+)E(?:Li(\d+)E)?E")
+_NAME = re.compile(r"_ZN4atmo\d+(atmo_(?:render|detail)_(?:[a-z_]+_)?kernel)ILi(\d+)ELi(\d+)E(?:Li(\d+)E)?E")
 
 
 def short_name(kernel: str) -> str:
-    """views_proxy of atmo_render_views_proxy_kernel: what --family takes."""
-    return kernel[len("atmo_render_"):-len("_kernel")]
+    """views_proxy of atmo_render_views_proxy_kernel, detail_target of atmo_detail_target_kernel: what --family takes."""
+    return kernel[len("atmo_render_" if kernel.startswith("atmo_render_") else "atmo_"):-len("_kernel")]
 
 
 def vgpr_waves(vgprs: int) -> int:
