@@ -214,6 +214,57 @@ class AtmoError(RuntimeError):
 _lib = None
 
 
+def optional_headers() -> dict:
+    """The headers whose symbols a library may lack (each `*_SYMBOLS` comment above says what then raises): header -> (its symbols' tuple, what the
+    missing-symbol message adds behind the header's name, name -> (restype, argtypes))."""
+    vp, ip, fp, u32, sz = C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_uint32, C.c_size_t
+    frame = C.POINTER(AtmoFrame)
+    rays = [vp, frame, vp, vp, u32, u32, u32]   # ctx, frame, rays_dev, rgba_dev, n, width, first
+    return {
+        "atmo_cloud_detail.h": (CLOUD_DETAIL_SYMBOLS, "", {
+            "atmo_set_cloud_detail": (ip, [vp, ip]),
+            "atmo_get_cloud_detail": (ip, [vp, C.POINTER(ip)]),
+            "atmo_debug_cloud_detail_constants": (ip, [vp, frame, fp, ip, C.POINTER(ip)]),
+        }),
+        "atmo_rays.h": (RAYS_SYMBOLS, "", {
+            "atmo_shade_rays": (ip, rays + [vp]),
+            "atmo_debug_frame_rays": (ip, [vp, frame, vp, vp, vp]),
+        }),
+        "atmo_ray_quads.h": (RAY_QUADS_SYMBOLS, "", {
+            "atmo_shade_ray_quads": (ip, rays + [vp]),
+        }),
+        "atmo_ray_order.h": (RAY_ORDER_SYMBOLS, "", {
+            "atmo_ray_order_scratch_bytes": (ip, [u32, C.POINTER(sz)]),
+            "atmo_ray_order": (ip, [vp, vp, u32, vp, vp, sz, vp]),
+            "atmo_shade_rays_indexed": (ip, rays + [vp, u32, vp]),
+            "atmo_debug_ray_keys": (ip, [vp, vp, u32, vp, vp]),
+            "atmo_debug_sort_ray_keys": (ip, [vp, vp, u32, vp, vp, sz, vp]),
+        }),
+        "atmo_ray_list.h": (RAY_LIST_SYMBOLS, "", {
+            "atmo_ray_list_scratch_bytes": (ip, [u32, C.POINTER(sz)]),
+            "atmo_ray_list": (ip, [vp, frame, vp, vp, u32, ip, vp, vp, vp, vp, sz, vp]),
+            "atmo_debug_ray_cull_constants": (ip, [vp, frame, fp, ip, C.POINTER(ip)]),
+        }),
+        "atmo_ray_detail.h": (RAY_DETAIL_SYMBOLS, ": no cloud detail for rays", {
+            "atmo_shade_rays_detail": (ip, rays + [vp, u32, vp]),
+            "atmo_shade_ray_quads_detail": (ip, rays + [vp]),
+        }),
+        "atmo_detail_target.h": (DETAIL_TARGET_SYMBOLS, ": no cloud detail into targets", {
+            "atmo_render_detail_target": (ip, [vp, frame, C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), ip, vp]),
+            "atmo_render_views_detail_target": (ip, [vp, C.POINTER(AtmoViewDepthTarget), ip, ip, vp]),
+        }),
+    }
+
+
+def optional_entry(lib, name: str):
+    """An optional header's entry point of `lib`; RuntimeError naming the header where the library lacks it."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        header, suffix = next((h, sfx) for h, (symbols, sfx, _) in optional_headers().items() if name in symbols)
+        raise RuntimeError(f"libatmo_hip.so does not export {name} (include/{header}){suffix}; rebuild it")
+    return fn
+
+
 def load() -> C.CDLL:
     """Load libatmo_hip.so; raises if it has not been built (run __graft_entry__.build())."""
     global _lib
@@ -313,87 +364,14 @@ def load() -> C.CDLL:
             raise RuntimeError(f"libatmo_hip.so does not export {name}; rebuild it")
         fn.restype = res
         fn.argtypes = args
-    # include/atmo_cloud_detail.h: detected by symbol -- bound where present, and a library without them loads all the same
-    detail_sig = {
-        "atmo_set_cloud_detail": (ip, [vp, ip]),
-        "atmo_get_cloud_detail": (ip, [vp, C.POINTER(ip)]),
-        "atmo_debug_cloud_detail_constants": (ip, [vp, C.POINTER(AtmoFrame), fp, ip, C.POINTER(ip)]),
-    }
-    assert tuple(detail_sig) == CLOUD_DETAIL_SYMBOLS
-    for name, (res, args) in detail_sig.items():
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.restype = res
-            fn.argtypes = args
-    # include/atmo_rays.h: the same rule
-    rays_sig = {
-        "atmo_shade_rays": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
-        "atmo_debug_frame_rays": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, vp]),
-    }
-    assert tuple(rays_sig) == RAYS_SYMBOLS
-    for name, (res, args) in rays_sig.items():
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.restype = res
-            fn.argtypes = args
-    # include/atmo_ray_quads.h: the same rule
-    ray_quads_sig = {
-        "atmo_shade_ray_quads": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
-    }
-    assert tuple(ray_quads_sig) == RAY_QUADS_SYMBOLS
-    for name, (res, args) in ray_quads_sig.items():
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.restype = res
-            fn.argtypes = args
-    # include/atmo_ray_order.h: the same rule
-    ray_order_sig = {
-        "atmo_ray_order_scratch_bytes": (ip, [C.c_uint32, C.POINTER(C.c_size_t)]),
-        "atmo_ray_order": (ip, [vp, vp, C.c_uint32, vp, vp, C.c_size_t, vp]),
-        "atmo_shade_rays_indexed": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]),
-        "atmo_debug_ray_keys": (ip, [vp, vp, C.c_uint32, vp, vp]),
-        "atmo_debug_sort_ray_keys": (ip, [vp, vp, C.c_uint32, vp, vp, C.c_size_t, vp]),
-    }
-    assert tuple(ray_order_sig) == RAY_ORDER_SYMBOLS
-    for name, (res, args) in ray_order_sig.items():
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.restype = res
-            fn.argtypes = args
-    # include/atmo_ray_list.h: the same rule
-    ray_list_sig = {
-        "atmo_ray_list_scratch_bytes": (ip, [C.c_uint32, C.POINTER(C.c_size_t)]),
-        "atmo_ray_list": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, ip, vp, vp, vp, vp, C.c_size_t, vp]),
-        "atmo_debug_ray_cull_constants": (ip, [vp, C.POINTER(AtmoFrame), fp, ip, C.POINTER(ip)]),
-    }
-    assert tuple(ray_list_sig) == RAY_LIST_SYMBOLS
-    for name, (res, args) in ray_list_sig.items():
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.restype = res
-            fn.argtypes = args
-    # include/atmo_ray_detail.h: the same rule
-    ray_detail_sig = {
-        "atmo_shade_rays_detail": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]),
-        "atmo_shade_ray_quads_detail": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
-    }
-    assert tuple(ray_detail_sig) == RAY_DETAIL_SYMBOLS
-    for name, (res, args) in ray_detail_sig.items():
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.restype = res
-            fn.argtypes = args
-    # include/atmo_detail_target.h: the same rule
-    detail_target_sig = {
-        "atmo_render_detail_target": (ip, [vp, C.POINTER(AtmoFrame), C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), ip, vp]),
-        "atmo_render_views_detail_target": (ip, [vp, C.POINTER(AtmoViewDepthTarget), ip, ip, vp]),
-    }
-    assert tuple(detail_target_sig) == DETAIL_TARGET_SYMBOLS
-    for name, (res, args) in detail_target_sig.items():
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.restype = res
-            fn.argtypes = args
+    # the optional headers: detected by symbol -- bound where present, and a library without them loads all the same
+    for header, (symbols, _, optional_sig) in optional_headers().items():
+        assert tuple(optional_sig) == symbols, header
+        for name, (res, args) in optional_sig.items():
+            fn = getattr(lib, name, None)
+            if fn is not None:
+                fn.restype = res
+                fn.argtypes = args
     have = lib.atmo_abi_version()
     if have != ABI_VERSION:
         # An A/B library may be older, but only a version whose AtmoFrame layout and shared entry points are KNOWN to be what this binding

@@ -2290,82 +2290,34 @@ static atmo::RayConsts ray_consts(const AtmoContext *ctx, const atmo::RenderCons
     yc.md_e1 = rc.clouds_top * 1.05f;
     return yc;
 }
-// index != nullptr: atmo_shade_rays_indexed (include/atmo_ray_order.h) -- the same checks under its name, its list's two in the argument block, and the
-// KF_INDEX kernels over the list; everything else is the one path.
-// serves_detail (include/atmo_ray_detail.h): the entry point shades a cloud context with cloud detail on -- no refusal, DetailConsts as render_impl's step 3a
-// fills them, the detail launchers, KF_DETAIL in the kernel's name; with the switch off or no clouds it is the path below under another name
+// One ray draw, for the five entry points (atmo_rays.h, atmo_ray_quads.h, atmo_ray_order.h, atmo_ray_detail.h).  What a call is:
+//   shape          RAY_BATCH: n rays, image index first + i.  RAY_QUADS: n quads of four rays, quad index first + q, under the declared sampler
+//   index          a list over the batch (its two checks in the argument block, the KF_INDEX kernels over the list); nullptr: the whole batch
+//   serves_detail  the entry point shades a cloud context with cloud detail on: no refusal, DetailConsts as render_impl's step 3a fills them, KF_DETAIL in
+//                  the kernel's name; with the switch off or no clouds it is the plain path under another name
 struct RayIndexList {
     const uint32_t *index_dev;
     uint32_t n_index;
 };
-static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
-                     void *stream, const std::string &who, bool serves_detail, const RayIndexList *index = nullptr) {
-    if (!ctx) return ATMO_E_ARG;
-    if (n_rays == 0 || (index && index->n_index == 0)) return ATMO_OK;   // nothing to shade
-    if (!frame || !rays_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": null frame or device pointer");
-    if ((reinterpret_cast<uintptr_t>(rays_dev) & 15u) != 0 || (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0)
-        return fail(ctx, ATMO_E_ARG, who + ": rays_dev and rgba_dev must be 16-byte aligned");
-    if (index && !index->index_dev) return fail(ctx, ATMO_E_ARG, who + ": null index_dev");
-    if (index && (reinterpret_cast<uintptr_t>(index->index_dev) & 3u) != 0) return fail(ctx, ATMO_E_ARG, who + ": index_dev must be 4-byte aligned");
-    if (width == 0) return fail(ctx, ATMO_E_ARG, who + ": width must be at least 1");
-    if ((uint64_t)first + (uint64_t)n_rays > ((uint64_t)1 << 32)) return fail(ctx, ATMO_E_ARG, who + ": first + n_rays must not exceed 2^32");
-    // the mode: the default forms under the level-0 sampler (atmo::rays_family_supported)
-    ATMO_TRY(rays_mode_refusals(ctx, frame, who, serves_detail));
+struct RayCall {
+    std::string who;
+    bool serves_detail;
+    atmo::RayShape shape;
+    const RayIndexList *index;
+};
+// The state checks of a batch behind rays_mode_refusals, in atmo_rays.h's order: the default forms under the level-0 sampler (atmo::rays_family_supported)
+static int ray_batch_state(AtmoContext *ctx, const AtmoFrame *frame, const std::string &who, int *flags) {
     if (ctx->sampler_lod == 1 && (ctx->flags & atmo::KF_CLOUDS) && ctx->cube.ptr && ctx->cube_levels > 1)
         return fail(ctx, ATMO_E_STATE, who + ": rays sample the coverage cubemap at level 0, and this context demands the declared sampler (atmo_set_sampler_lod 1)");
-    int flags = 0, split = 1;
-    launch_shape(ctx, frame, &flags, &split, nullptr);
-    flags &= ~atmo::KF_CUBE_LOD;   // the sampler forced to level 0
-    if (split != 1 || !atmo::rays_family_supported(flags)) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for this context's mode");
-    ATMO_TRY(check_draw_textures(ctx, who));
-    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to shade on");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-
-    atmo::RenderConsts rc;
-    AtmoFrame fixed;
-    frame = draw_frame(ctx, frame, fixed);
-    draw_consts(ctx, frame, float_surfaces(nullptr, rgba_dev, false), rc);   // the uniforms, the textures, the sun; its matrices' camera forms are not read
-    const atmo::RayConsts yc = ray_consts(ctx, rc, rays_dev, rgba_dev, n_rays, width, first);
-    hipStream_t s = (hipStream_t)stream;
-    ATMO_TRY(tex_order(ctx, s));  // texture updated on another stream
-    TimingBracket timing;
-    ATMO_TRY(timing_open(ctx, timing));
-    ATMO_TRY(timing_begin(ctx, timing, s));
-    const bool detail = serves_detail && cloud_detail_on(ctx);
-    if (detail) {
-        const atmo::DetailConsts xc = cloud_detail_consts(ctx, frame);
-        const atmo::RayIndexConsts ic = {index ? index->index_dev : nullptr, index ? index->n_index : 0u};
-        HIP_TRY(ctx, atmo::launch_shade_rays_detail(flags, rc, yc, xc, index ? &ic : nullptr, s));
-    } else if (index) {
-        const atmo::RayIndexConsts ic = {index->index_dev, index->n_index};
-        HIP_TRY(ctx, atmo::launch_shade_rays_indexed(flags, rc, yc, ic, s));
-    } else {
-        HIP_TRY(ctx, atmo::launch_shade_rays(flags, rc, yc, s));
-    }
-    hipEvent_t marker = nullptr;
-    ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_RAYS | (index ? atmo::KF_INDEX : 0) | (detail ? atmo::KF_DETAIL : 0), 1, true, &marker));
-    return timing_end(ctx, timing, s);
+    int split = 1;
+    launch_shape(ctx, frame, flags, &split, nullptr);
+    *flags &= ~atmo::KF_CUBE_LOD;   // the sampler forced to level 0
+    if (split != 1 || !atmo::rays_family_supported(*flags)) return fail(ctx, ATMO_E_STATE, who + ": no ray kernel for this context's mode");
+    return check_draw_textures(ctx, who);
 }
-
-int atmo_shade_rays(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
-                    void *stream) {
-    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, "atmo_shade_rays", false);
-}
-
-// ---- rays in quads under the declared sampler (include/atmo_ray_quads.h) ---------------------------------------------------------------------------
-// atmo_shade_rays' checks in its order, then what is this entry point's own: a cloud variant, a sampler mode that allows the declared sampler, a mip chain.
-// There is NO fallback to the level-0 ray kernels: their jitter order is row-major and this call's is quad order, a third picture.  The constants are
-// rays_impl's (ray_consts); lod0_* and the level table come from draw_consts, the path of every declared-sampler draw.
-static int ray_quads_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_quads, uint32_t width,
-                          uint32_t first_quad, void *stream, const std::string &who, bool serves_detail) {
-    if (!ctx) return ATMO_E_ARG;
-    if (n_quads == 0) return ATMO_OK;   // nothing to shade
-    if (!frame || !rays_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": null frame or device pointer");
-    if ((reinterpret_cast<uintptr_t>(rays_dev) & 15u) != 0 || (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0)
-        return fail(ctx, ATMO_E_ARG, who + ": rays_dev and rgba_dev must be 16-byte aligned");
-    if (width == 0) return fail(ctx, ATMO_E_ARG, who + ": width must be at least 1");
-    if ((uint64_t)first_quad + (uint64_t)n_quads > ((uint64_t)1 << 30)) return fail(ctx, ATMO_E_ARG, who + ": first_quad + n_quads must not exceed 2^30");
-    ATMO_TRY(rays_mode_refusals(ctx, frame, who, serves_detail));
+// ... and of quads, in atmo_ray_quads.h's: a cloud variant, a sampler mode that allows the declared sampler, a mip chain.  There is NO fallback to the
+// level-0 ray kernels: their jitter order is row-major and this call's is quad order, a third picture.
+static int ray_quads_state(AtmoContext *ctx, const AtmoFrame *frame, const std::string &who, int *flags) {
     if (!(ctx->flags & atmo::KF_CLOUDS))
         return fail(ctx, ATMO_E_STATE, who + ": a variant without clouds has no texture call to difference; shade its rays with atmo_shade_rays");
     if (ctx->sampler_lod == 0)
@@ -2374,40 +2326,68 @@ static int ray_quads_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRa
     if (!ctx->cube.ptr || ctx->cube_levels <= 1)
         return fail(ctx, ATMO_E_STATE, who + ": no mip chain of u_cloud_coverage_cubemap is bound (atmo_set_sampler_lod " + std::to_string(ctx->sampler_lod) +
                                            "): level 0 is all there is, and atmo_shade_rays samples it");
-    int flags = 0, split = 1;
-    launch_shape(ctx, frame, &flags, &split, nullptr);
-    if (split != 1 || !atmo::ray_quads_family_supported(flags)) return fail(ctx, ATMO_E_STATE, who + ": no ray-quad kernel for this context's mode");
+    int split = 1;
+    launch_shape(ctx, frame, flags, &split, nullptr);
+    if (split != 1 || !atmo::ray_quads_family_supported(*flags)) return fail(ctx, ATMO_E_STATE, who + ": no ray-quad kernel for this context's mode");
+    return ATMO_OK;
+}
+static int rays_impl(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n, uint32_t width, uint32_t first, void *stream,
+                     const RayCall &call) {
+    const std::string &who = call.who;
+    const RayIndexList *index = call.index;
+    const bool quads = call.shape == atmo::RAY_QUADS;
+    if (!ctx) return ATMO_E_ARG;
+    if (n == 0 || (index && index->n_index == 0)) return ATMO_OK;   // nothing to shade
+    if (!frame || !rays_dev || !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": null frame or device pointer");
+    if ((reinterpret_cast<uintptr_t>(rays_dev) & 15u) != 0 || (reinterpret_cast<uintptr_t>(rgba_dev) & 15u) != 0)
+        return fail(ctx, ATMO_E_ARG, who + ": rays_dev and rgba_dev must be 16-byte aligned");
+    if (index && !index->index_dev) return fail(ctx, ATMO_E_ARG, who + ": null index_dev");
+    if (index && (reinterpret_cast<uintptr_t>(index->index_dev) & 3u) != 0) return fail(ctx, ATMO_E_ARG, who + ": index_dev must be 4-byte aligned");
+    if (width == 0) return fail(ctx, ATMO_E_ARG, who + ": width must be at least 1");
+    if ((uint64_t)first + (uint64_t)n > ((uint64_t)1 << (quads ? 30 : 32)))
+        return fail(ctx, ATMO_E_ARG, who + (quads ? ": first_quad + n_quads must not exceed 2^30" : ": first + n_rays must not exceed 2^32"));
+    ATMO_TRY(rays_mode_refusals(ctx, frame, who, call.serves_detail));
+    int flags = 0;
+    ATMO_TRY(quads ? ray_quads_state(ctx, frame, who, &flags) : ray_batch_state(ctx, frame, who, &flags));
     if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to shade on");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
     atmo::RenderConsts rc;
     AtmoFrame fixed;
     frame = draw_frame(ctx, frame, fixed);
-    draw_consts(ctx, frame, float_surfaces(nullptr, rgba_dev, false), rc);   // as rays_impl; with it the level-0 certificate's lod0_* of every declared-sampler draw
+    // the uniforms, the textures, the sun (the matrices' camera forms are not read); for quads the level-0 certificate's lod0_* and the level table, as in
+    // every declared-sampler draw
+    draw_consts(ctx, frame, float_surfaces(nullptr, rgba_dev, false), rc);
     hipStream_t s = (hipStream_t)stream;
     ATMO_TRY(tex_order(ctx, s));  // texture updated on another stream
     TimingBracket timing;
     ATMO_TRY(timing_open(ctx, timing));
     ATMO_TRY(timing_begin(ctx, timing, s));
-    // slot 4 q + j: thread i = slot i; the kernel's jitter pixel comes from the quad index first_quad + (i >> 2) and the quads per row.  A launch holds at
-    // most 2^29 quads, so that its 4 n_quads rays fit RayConsts::n (the one batch of 2^30 quads the range check admits goes out as two)
-    constexpr uint32_t per_launch = 1u << 29;
-    const bool detail = serves_detail && cloud_detail_on(ctx);   // (include/atmo_ray_detail.h: as rays_impl's)
-    const atmo::DetailConsts xc = cloud_detail_consts(ctx, frame);
-    for (uint32_t done = 0; done < n_quads; done += per_launch) {
-        const uint32_t quads = n_quads - done < per_launch ? n_quads - done : per_launch;
-        const atmo::RayConsts yc = ray_consts(ctx, rc, rays_dev + 4 * (size_t)done, rgba_dev + 16 * (size_t)done, 4u * quads, (width + 1u) / 2u, first_quad + done);
-        if (detail) HIP_TRY(ctx, atmo::launch_shade_ray_quads_detail(flags, rc, yc, xc, s));
-        else HIP_TRY(ctx, atmo::launch_shade_ray_quads(flags, rc, yc, s));
+    const bool detail = call.serves_detail && cloud_detail_on(ctx);
+    const atmo::DetailConsts xc = detail ? cloud_detail_consts(ctx, frame) : atmo::DetailConsts{};
+    const atmo::RayIndexConsts ic = {index ? index->index_dev : nullptr, index ? index->n_index : 0u};
+    // Quads: slot 4 q + j is thread 4 q + j, the jitter pixel comes from the quad index first + q and the quads per row, and a launch holds at most 2^29
+    // quads, so that its rays fit RayConsts::n (the one batch of 2^30 quads the range check admits goes out as two).  A batch is one launch.
+    const uint32_t per_launch = quads ? 1u << 29 : n, rays_each = quads ? 4u : 1u, row = quads ? (width + 1u) / 2u : width;
+    for (uint32_t done = 0; done < n; done += per_launch) {
+        const uint32_t count = n - done < per_launch ? n - done : per_launch;
+        const atmo::RayConsts yc = ray_consts(ctx, rc, rays_dev + rays_each * (size_t)done, rgba_dev + 4 * rays_each * (size_t)done, rays_each * count, row, first + done);
+        HIP_TRY(ctx, atmo::launch_shade_rays(flags, call.shape, rc, yc, index ? &ic : nullptr, detail ? &xc : nullptr, s));
     }
     hipEvent_t marker = nullptr;
-    ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_RAYS | (detail ? atmo::KF_DETAIL : 0), 1, true, &marker));
+    ATMO_TRY(finish_draw(ctx, s, flags | atmo::KF_RAYS | (index ? atmo::KF_INDEX : 0) | (detail ? atmo::KF_DETAIL : 0), 1, true, &marker));
     return timing_end(ctx, timing, s);
 }
 
+int atmo_shade_rays(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
+                    void *stream) {
+    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, {"atmo_shade_rays", false, atmo::RAY_BATCH, nullptr});
+}
+
+// ---- rays in quads under the declared sampler (include/atmo_ray_quads.h) ---------------------------------------------------------------------------
 int atmo_shade_ray_quads(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_quads, uint32_t width,
                          uint32_t first_quad, void *stream) {
-    return ray_quads_impl(ctx, frame, rays_dev, rgba_dev, n_quads, width, first_quad, stream, "atmo_shade_ray_quads", false);
+    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_quads, width, first_quad, stream, {"atmo_shade_ray_quads", false, atmo::RAY_QUADS, nullptr});
 }
 
 // ---- ray queues: the device's coherence order and shading through an index list (include/atmo_ray_order.h) ------------------------------------------------
@@ -2415,7 +2395,7 @@ static_assert(ATMO_RAY_KEY_BITS == atmo::RAY_KEY_BITS, "the header's key width i
 int atmo_shade_rays_indexed(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
                             const uint32_t *index_dev, uint32_t n_index, void *stream) {
     const RayIndexList list = {index_dev, n_index};
-    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, "atmo_shade_rays_indexed", false, &list);
+    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, {"atmo_shade_rays_indexed", false, atmo::RAY_BATCH, &list});
 }
 
 // ---- cloud detail for rays, ray lists and ray quads (include/atmo_ray_detail.h) ---------------------------------------------------------------------------
@@ -2423,14 +2403,13 @@ int atmo_shade_rays_indexed(AtmoContext *ctx, const AtmoFrame *frame, const Atmo
 // atmo_shade_rays_indexed's (n_index is not looked at without one)
 int atmo_shade_rays_detail(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_rays, uint32_t width, uint32_t first,
                            const uint32_t *index_dev, uint32_t n_index, void *stream) {
-    if (!index_dev) return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, "atmo_shade_rays_detail", true);
     const RayIndexList list = {index_dev, n_index};
-    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, "atmo_shade_rays_detail", true, &list);
+    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_rays, width, first, stream, {"atmo_shade_rays_detail", true, atmo::RAY_BATCH, index_dev ? &list : nullptr});
 }
 
 int atmo_shade_ray_quads_detail(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_dev, float *rgba_dev, uint32_t n_quads, uint32_t width,
                                 uint32_t first_quad, void *stream) {
-    return ray_quads_impl(ctx, frame, rays_dev, rgba_dev, n_quads, width, first_quad, stream, "atmo_shade_ray_quads_detail", true);
+    return rays_impl(ctx, frame, rays_dev, rgba_dev, n_quads, width, first_quad, stream, {"atmo_shade_ray_quads_detail", true, atmo::RAY_QUADS, nullptr});
 }
 
 int atmo_ray_order_scratch_bytes(uint32_t n_rays, size_t *bytes) {

@@ -287,9 +287,11 @@ struct ViewsDetailConsts {
 hipError_t launch_render(int flags, int split, const RenderConsts &rc, hipStream_t stream, int tile_list_blocks = 0);  // > 0: rc.tile_order lists that many tiles of the rect's grid
 // Every launcher below draws the DEFAULT-FORM families (what a default context selects: one lane per ray, the precise cloud and v1 forms, up to 32 view
 // steps) and no other.  The list stands once, ATMO_DEFAULT_FAMILIES in atmo_kernels.hip: default_family_supported and launch_default_family are made from it.
-//   a new family:       one line at the end of that list; every launcher below then has it
-//   a new entry point:  its kernel, and one launch_default_family call whose lambda names that kernel and its family bits
-// flags = a draw's family WITHOUT the entry point's own bits (KF_PROXY, KF_VIEWS, KF_TARGET), which the launcher adds.
+//   a new family:       one line at the end of that list; every launcher below then has it.  The ray and cloud-detail launchers draw the SUBSET a constexpr
+//                       predicate beside their kernels selects (rays_family, ray_quads_family, detail_family, rays_detail_family): there it is a change
+//                       to that predicate and to the count its static_assert holds
+//   a new entry point:  its kernel, and one launch_default_family (or launch_family_subset<predicate>) call whose lambda names that kernel and its family bits
+// flags = a draw's family WITHOUT the entry point's own bits (KF_PROXY, KF_VIEWS, KF_TARGET, ...), which the launcher adds.
 bool default_family_supported(int flags);
 // the proxy draws: one lane per ray, row-major grid of the rect in rc
 hipError_t launch_render_proxy(int flags, const RenderConsts &rc, const ProxyConsts &pc, hipStream_t stream);
@@ -325,28 +327,23 @@ hipError_t launch_render_views_proxy_depth_target(int flags, int light_steps, co
 bool detail_family_supported(int flags);
 hipError_t launch_render_detail(int flags, const RenderConsts &rc, const DetailConsts &xc, hipStream_t stream);
 // ... into a colour target of any of the seven formats, reading a depth source (atmo_render_detail_target, atmo_render_views_detail_target;
-// include/atmo_detail_target.h): the same six families (detail_family_supported) with the KF_DETAIL | KF_DEPTH | KF_TARGET kernels, the single draw row-major
-// over the rect's grid as launch_render_detail, the batch view-major over the concatenation of the views' grids as launch_render_views_depth_target without a
-// tile order or a cost map (vtc.v.order and vtc.v.cost must be null); flags WITHOUT the four entry-point bits, which the launchers add
+// include/atmo_detail_target.h): the same six families with the KF_DETAIL | KF_DEPTH | KF_TARGET kernels, the single draw as launch_render_detail, the batch
+// view-major as launch_render_views_depth_target without a tile order or a cost map (vtc.v.order and vtc.v.cost must be null); flags WITHOUT these bits
 hipError_t launch_render_detail_target(int flags, const RenderConsts &rc, const TargetConsts &tc, const DepthConsts &dc, const DetailConsts &xc, hipStream_t stream);
 hipError_t launch_render_views_detail_target(int flags, const RenderConsts *table_dev, const ViewsTargetConsts &vtc, const ViewsDepthConsts &vdc,
                                              const ViewsDetailConsts &vxc, hipStream_t stream);
-// the ray draws (atmo_shade_rays; include/atmo_rays.h): six families (rays_family_supported; the direct-light one with 8 light steps unrolled or any count),
-// 64 consecutive rays per wave, 256 per workgroup, row-major over the batch; flags WITHOUT KF_RAYS, which the launcher adds
+// the ray draws (include/atmo_rays.h, atmo_ray_quads.h, atmo_ray_order.h, atmo_ray_detail.h), one launcher for all five entry points.  flags WITHOUT
+// KF_RAYS | KF_INDEX | KF_DETAIL, which the launcher adds.  64 consecutive rays per wave, 256 per workgroup, row-major over the batch -- or, with ic, over
+// the list's ic->n_index entries.  hipErrorInvalidValue for arguments outside the limits and for any other family.
+//   RAY_BATCH: the six level-0 families (rays_family_supported; the direct-light one with 8 light steps unrolled or any count); first + n <= 2^32
+//   RAY_QUADS: the three cloud families under the declared sampler (ray_quads_family_supported; flags WITH KF_CUBE_LOD); yc.n = 4 n_quads, yc.first =
+//              first_quad, yc.width = quads per row of the image, (width + 1) / 2; first_quad + n_quads <= 2^30; no ic
+//   xc:        the KF_DETAIL kernels, DetailConsts behind the ray arguments: the three cloud families of the shape
+enum RayShape : int { RAY_BATCH, RAY_QUADS };
 bool rays_family_supported(int flags);
-hipError_t launch_shade_rays(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream);
-// rays in quads under the declared sampler (atmo_shade_ray_quads; include/atmo_ray_quads.h): the three cloud families, flags WITH KF_CUBE_LOD and without
-// KF_RAYS; the same grid rule; yc.n = 4 n_quads, yc.first = first_quad, yc.width = quads per row of the image, (width + 1) / 2
 bool ray_quads_family_supported(int flags);
-hipError_t launch_shade_ray_quads(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream);
-// the ray draws through an index list (atmo_shade_rays_indexed; include/atmo_ray_order.h): launch_shade_rays' seven kernels once more, the grid over the
-// list's ic.n_index entries; flags WITHOUT KF_RAYS | KF_INDEX, which the launcher adds
-hipError_t launch_shade_rays_indexed(int flags, const RenderConsts &rc, const RayConsts &yc, const RayIndexConsts &ic, hipStream_t stream);
-// the ray draws with cloud detail (atmo_shade_rays_detail, atmo_shade_ray_quads_detail; include/atmo_ray_detail.h): the three cloud families of
-// launch_shade_rays (flags WITHOUT KF_RAYS | KF_INDEX | KF_DETAIL, which the launcher adds; ic == nullptr: the whole batch, else the grid over the list) and of
-// launch_shade_ray_quads (flags WITH KF_CUBE_LOD), DetailConsts behind the ray arguments; the siblings' argument checks, hipErrorInvalidValue for any other family
-hipError_t launch_shade_rays_detail(int flags, const RenderConsts &rc, const RayConsts &yc, const DetailConsts &xc, const RayIndexConsts *ic, hipStream_t stream);
-hipError_t launch_shade_ray_quads_detail(int flags, const RenderConsts &rc, const RayConsts &yc, const DetailConsts &xc, hipStream_t stream);
+hipError_t launch_shade_rays(int flags, RayShape shape, const RenderConsts &rc, const RayConsts &yc, const RayIndexConsts *ic, const DetailConsts *xc,
+                             hipStream_t stream);
 // the coherence order of a ray queue (atmo_ray_order; include/atmo_ray_order.h states the key): the key kernel, then a stable least-significant-digit radix
 // sort of (key, index) pairs in three 6-bit passes, every buffer in the caller's scratch (ray_order_scratch_bytes(n) bytes, 16-byte aligned), kernels on
 // `stream` only.  launch_ray_sort is the sort alone, on keys that are already there (atmo_debug_sort_ray_keys); n <= RAY_ORDER_MAX_RAYS

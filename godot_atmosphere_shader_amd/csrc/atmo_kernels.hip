@@ -2463,7 +2463,7 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
     float jitter;
     if constexpr (RAYS && LOD) {
         // quad order: slot i = 4 q + j is pixel (2 (Q % qpr) + (j & 1), 2 (Q / qpr) + (j >> 1)), Q = first_quad + q -- yc->first is first_quad and yc->width
-        // is qpr = (width + 1) / 2, the quads per row (the host's ray_quads_impl); Q < 2^30
+        // is qpr = (width + 1) / 2, the quads per row (the host's rays_impl); Q < 2^30
         const uint32_t kq = yc->first + (i >> 2);
         const uint32_t qy = kq / yc->width, qx = kq - qy * yc->width;
         const uint32_t kx = 2u * qx + (i & 1u), ky = 2u * qy + ((i >> 1) & 1u);
@@ -3605,6 +3605,25 @@ static hipError_t launch_default_family(int flags, int light_steps, Launch &&lau
 #undef ATMO_FAMILY_TWIN
 #undef ATMO_FAMILY_GEO_TWIN
 }
+// A SUBSET of the list, in the list's order: the ray and cloud-detail draws exist for the families a constexpr predicate over a default family's flags
+// selects, and launch through this with their own kernel.  A listed family outside the subset answers like an unlisted one.
+using FamilyPredicate = bool (*)(int);
+template <FamilyPredicate IN_SUBSET, class Launch>
+static hipError_t launch_family_subset(int flags, int light_steps, Launch &&launch) {
+    return launch_default_family(flags, light_steps, [&](auto F, auto L) -> hipError_t {
+        if constexpr (IN_SUBSET(F)) return launch(F, L);
+        else return hipErrorInvalidValue;
+    });
+}
+template <FamilyPredicate IN_SUBSET>
+static bool family_in_subset(int flags) { return default_family_supported(flags) && IN_SUBSET(flags); }
+// how many of the thirteen a predicate selects, and how many of those are TWINs: what the static_assert beside each predicate holds
+#define ATMO_FAMILY_COUNTED(F) + (IN_SUBSET(F) ? 1 : 0)
+template <FamilyPredicate IN_SUBSET>
+constexpr int subset_families = 0 ATMO_DEFAULT_FAMILIES(ATMO_FAMILY_COUNTED, ATMO_FAMILY_COUNTED, ATMO_FAMILY_SKIPPED);
+template <FamilyPredicate IN_SUBSET>
+constexpr int subset_twins = 0 ATMO_DEFAULT_FAMILIES(ATMO_FAMILY_SKIPPED, ATMO_FAMILY_COUNTED, ATMO_FAMILY_SKIPPED);
+#undef ATMO_FAMILY_COUNTED
 #undef ATMO_FAMILY_LISTED
 #undef ATMO_FAMILY_SKIPPED
 #undef ATMO_DEFAULT_FAMILIES
@@ -3880,33 +3899,16 @@ __global__ __launch_bounds__(TILE_W *TILE_H, detail_min_waves(FLAGS)) void atmo_
     static_assert((FLAGS & KF_DETAIL) != 0, "cloud-detail kernels carry KF_DETAIL");
     shade_pixel<FLAGS, LSTEPS, 1>(rc, (int)blockIdx.x, (int)blockIdx.y, nullptr, nullptr, nullptr, &xc);
 }
-// the six LUT-light cloud families of ATMO_DEFAULT_FAMILIES (the direct-light cloud families are this project's own composition: no reference shader pins them)
-#define ATMO_DETAIL_FAMILIES(ONE)                                 \
-    ONE(KF_PRECISE | KF_CLOUDS)                                   \
-    ONE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)               \
-    ONE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)                     \
-    ONE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM) \
-    ONE(KF_PRECISE | KF_LITE | KF_CLOUDS)                         \
-    ONE(KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS)
-bool detail_family_supported(int flags) {
-    switch (flags) {
-#define ATMO_DETAIL_LISTED(F) case (F):
-        ATMO_DETAIL_FAMILIES(ATMO_DETAIL_LISTED)
-#undef ATMO_DETAIL_LISTED
-        return true;
-    default: return false;
-    }
-}
+// the six LUT-light cloud families of the default list (the direct-light cloud families are this project's own composition: no reference shader pins them)
+constexpr bool detail_family(int flags) { return (flags & KF_CLOUDS) != 0 && (flags & KF_LIGHT_DIRECT) == 0; }
+static_assert(subset_families<detail_family> == 6 && subset_twins<detail_family> == 0, "six cloud-detail families, none of them a twin");
+bool detail_family_supported(int flags) { return family_in_subset<detail_family>(flags); }
 hipError_t launch_render_detail(int flags, const RenderConsts &rc, const DetailConsts &xc, hipStream_t stream) {
     if (rc.out == nullptr || rc.tile_order != nullptr || rc.tile_cost != nullptr) return hipErrorInvalidValue;   // float output, row-major, nothing recorded
-    switch (flags) {
-#define ATMO_DETAIL_LAUNCH(F) case (F): return launch_rect(atmo_render_detail_kernel<(F) | KF_DETAIL, 0>, rc, stream, xc);
-        ATMO_DETAIL_FAMILIES(ATMO_DETAIL_LAUNCH)
-#undef ATMO_DETAIL_LAUNCH
-    default: return hipErrorInvalidValue;
-    }
+    return launch_family_subset<detail_family>(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_rect(atmo_render_detail_kernel<F | KF_DETAIL, L>, rc, stream, xc);
+    });
 }
-// (ATMO_DETAIL_FAMILIES stays defined: the detail target kernels at the end of the file launch from the same list)
 
 // ---- caller-supplied rays (KF_RAYS; include/atmo_rays.h states the arithmetic item by item) ---------------------------------------------------------
 // shade_pixel in its RAYS mode, for a ray that did not come out of a camera matrix: origin, direction and distance limit are an AtmoRay's, the planet
@@ -3955,42 +3957,34 @@ __global__ __launch_bounds__(RAYS_BLOCK) void atmo_frame_rays_kernel(const Rende
     fc.rays[2 * i] = make_float4(0.0f, 0.0f, 0.0f, linear_depth);
     fc.rays[2 * i + 1] = make_float4(vvx * inv_len, vvy * inv_len, vvz * inv_len, 0.0f);
 }
-// ONE: a family with one kernel; TWIN: the direct-light family, 8 light steps unrolled or rc.light_steps at run time
-#define ATMO_RAYS_FAMILIES(ONE, TWIN)                \
-    ONE(0)                                           \
-    TWIN(KF_LIGHT_DIRECT)                            \
-    ONE(KF_PRECISE | KF_CLOUDS)                      \
-    ONE(KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)  \
-    ONE(KF_PRECISE | KF_LITE)                        \
-    ONE(KF_PRECISE | KF_LITE | KF_CLOUDS)
-bool rays_family_supported(int flags) {
-    switch (flags) {
-#define ATMO_RAYS_LISTED(F) case (F):
-        ATMO_RAYS_FAMILIES(ATMO_RAYS_LISTED, ATMO_RAYS_LISTED)
-#undef ATMO_RAYS_LISTED
-        return true;
-    default: return false;
-    }
-}
-template <class Kernel>
-static hipError_t launch_rays(Kernel kernel, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream) {
-    const unsigned blocks = (unsigned)(((uint64_t)yc.n + (RAYS_BLOCK - 1)) / RAYS_BLOCK);   // at most 2^24
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RAYS_BLOCK), 0, stream, rc, yc);
+// the level-0 ray families: no declared sampler, no cloud variant in the direct light mode; the direct-light family is the one twin (8 light steps unrolled,
+// or rc.light_steps at run time)
+constexpr bool rays_family(int flags) { return (flags & KF_CUBE_LOD) == 0 && !((flags & KF_CLOUDS) != 0 && (flags & KF_LIGHT_DIRECT) != 0); }
+static_assert(subset_families<rays_family> == 6 && subset_twins<rays_family> == 1 && rays_family(KF_LIGHT_DIRECT), "six level-0 ray families, one twin");
+bool rays_family_supported(int flags) { return family_in_subset<rays_family>(flags); }
+// Every ray launch: one thread per ray of the batch, or per entry of the index list, RAYS_BLOCK to a workgroup (at most 2^24 of them); consts: the kernel's
+// arguments
+template <class Kernel, class... Consts>
+static hipError_t launch_rays(Kernel kernel, uint32_t threads, hipStream_t stream, const Consts &...consts) {
+    const unsigned blocks = (unsigned)(((uint64_t)threads + (RAYS_BLOCK - 1)) / RAYS_BLOCK);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RAYS_BLOCK), 0, stream, consts...);
     return hipGetLastError();
 }
-hipError_t launch_shade_rays(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream) {
-    if (yc.rays == nullptr || yc.out == nullptr || yc.n == 0 || yc.width == 0 || yc.first > 0xffffffffu - (yc.n - 1u)) return hipErrorInvalidValue;
-    switch (flags) {
-#define ATMO_RAYS_LAUNCH(F) case (F): return launch_rays(atmo_shade_rays_kernel<(F) | KF_RAYS, 0>, rc, yc, stream);
-#define ATMO_RAYS_LAUNCH_TWIN(F) case (F): return rc.light_steps == 8 ? launch_rays(atmo_shade_rays_kernel<(F) | KF_RAYS, 8>, rc, yc, stream) \
-                                                                      : launch_rays(atmo_shade_rays_kernel<(F) | KF_RAYS, 0>, rc, yc, stream);
-        ATMO_RAYS_FAMILIES(ATMO_RAYS_LAUNCH, ATMO_RAYS_LAUNCH_TWIN)
-#undef ATMO_RAYS_LAUNCH
-#undef ATMO_RAYS_LAUNCH_TWIN
-    default: return hipErrorInvalidValue;
-    }
+// ... and what its arguments must be.  A batch: first + n <= 2^32.  Quads: whole ones, first_quad + n_quads <= 2^30, so that 2 * quad column + 1 and
+// 4 * quad index stay below 2^32.  An index list: not empty.
+static bool ray_batch_valid(const RayConsts &yc) {
+    return yc.rays != nullptr && yc.out != nullptr && yc.n != 0 && yc.width != 0 && yc.first <= 0xffffffffu - (yc.n - 1u);
 }
-// (ATMO_RAYS_FAMILIES is read once more at the end of this file: the indexed kernels)
+static bool ray_quads_valid(const RayConsts &yc) {
+    return yc.rays != nullptr && yc.out != nullptr && yc.n != 0 && (yc.n & 3u) == 0 && yc.width != 0 && (uint64_t)yc.first + (yc.n >> 2) <= ((uint64_t)1 << 30);
+}
+static bool ray_index_valid(const RayIndexConsts &ic) { return ic.index != nullptr && ic.n_index != 0; }
+static hipError_t shade_ray_batch(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream) {
+    if (!ray_batch_valid(yc)) return hipErrorInvalidValue;
+    return launch_family_subset<rays_family>(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_rays(atmo_shade_rays_kernel<F | KF_RAYS, L>, yc.n, stream, rc, yc);
+    });
+}
 hipError_t launch_frame_rays(const RenderConsts &rc, const FrameRaysConsts &fc, hipStream_t stream) {
     if (fc.depth == nullptr || fc.rays == nullptr || rc.x1 <= rc.x0 || rc.y1 <= rc.y0) return hipErrorInvalidValue;
     const size_t n = (size_t)(rc.x1 - rc.x0) * (size_t)(rc.y1 - rc.y0);
@@ -4003,31 +3997,15 @@ hipError_t launch_frame_rays(const RenderConsts &rc, const FrameRaysConsts &fc, 
 // sample it: slot i = 4 q + j of the batch is thread i, so the caller's quad q sits in four consecutive lanes and the whole-quad exchange finds a ray's
 // partners where it finds a pixel's.  flags WITHOUT KF_RAYS and WITH KF_CUBE_LOD; yc.n = 4 n_quads, yc.first = first_quad, yc.width = quads per row.
 // Instantiated here, behind every older kernel, which keep their code and their place in the code object.
-#define ATMO_RAY_QUADS_FAMILIES(ONE)                               \
-    ONE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS)                      \
-    ONE(KF_CUBE_LOD | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)  \
-    ONE(KF_CUBE_LOD | KF_PRECISE | KF_LITE | KF_CLOUDS)
-bool ray_quads_family_supported(int flags) {
-    switch (flags) {
-#define ATMO_RAY_QUADS_LISTED(F) case (F):
-        ATMO_RAY_QUADS_FAMILIES(ATMO_RAY_QUADS_LISTED)
-#undef ATMO_RAY_QUADS_LISTED
-        return true;
-    default: return false;
-    }
+constexpr bool ray_quads_family(int flags) { return (flags & KF_CUBE_LOD) != 0 && (flags & KF_LIGHT_DIRECT) == 0; }
+static_assert(subset_families<ray_quads_family> == 3 && subset_twins<ray_quads_family> == 0, "three ray-quad families, none of them a twin");
+bool ray_quads_family_supported(int flags) { return family_in_subset<ray_quads_family>(flags); }
+static hipError_t shade_ray_quads(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream) {
+    if (!ray_quads_valid(yc)) return hipErrorInvalidValue;
+    return launch_family_subset<ray_quads_family>(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_rays(atmo_shade_rays_kernel<F | KF_RAYS, L>, yc.n, stream, rc, yc);
+    });
 }
-hipError_t launch_shade_ray_quads(int flags, const RenderConsts &rc, const RayConsts &yc, hipStream_t stream) {
-    // whole quads only; first_quad + n_quads <= 2^30, so 2 * quad column + 1 and 4 * quad index stay below 2^32
-    if (yc.rays == nullptr || yc.out == nullptr || yc.n == 0 || (yc.n & 3u) != 0 || yc.width == 0 || (uint64_t)yc.first + (yc.n >> 2) > ((uint64_t)1 << 30))
-        return hipErrorInvalidValue;
-    switch (flags) {
-#define ATMO_RAY_QUADS_LAUNCH(F) case (F): return launch_rays(atmo_shade_rays_kernel<(F) | KF_RAYS, 0>, rc, yc, stream);
-        ATMO_RAY_QUADS_FAMILIES(ATMO_RAY_QUADS_LAUNCH)
-#undef ATMO_RAY_QUADS_LAUNCH
-    default: return hipErrorInvalidValue;
-    }
-}
-#undef ATMO_RAY_QUADS_FAMILIES
 
 // ---- ray queues: shading through an index list, and the device's coherence order (KF_INDEX; include/atmo_ray_order.h) -----------------------------------------
 // The seven level-0 ray kernels once more, with ONE more site in shade_pixel: where i is formed, thread k of the launch takes i = index[k].  The rays, the
@@ -4040,26 +4018,12 @@ __global__ __launch_bounds__(RAYS_BLOCK, render_min_waves(FLAGS & ~(KF_RAYS | KF
     static_assert((FLAGS & KF_RAYS) != 0 && (FLAGS & KF_INDEX) != 0, "indexed ray kernels carry KF_RAYS | KF_INDEX");
     shade_pixel<FLAGS, LSTEPS, 1>(rc, 0, 0, nullptr, nullptr, nullptr, nullptr, &yc, &ic);
 }
-template <class Kernel>
-static hipError_t launch_rays_indexed(Kernel kernel, const RenderConsts &rc, const RayConsts &yc, const RayIndexConsts &ic, hipStream_t stream) {
-    const unsigned blocks = (unsigned)(((uint64_t)ic.n_index + (RAYS_BLOCK - 1)) / RAYS_BLOCK);   // at most 2^24
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RAYS_BLOCK), 0, stream, rc, yc, ic);
-    return hipGetLastError();
+static hipError_t shade_rays_indexed(int flags, const RenderConsts &rc, const RayConsts &yc, const RayIndexConsts &ic, hipStream_t stream) {
+    if (!ray_batch_valid(yc) || !ray_index_valid(ic)) return hipErrorInvalidValue;
+    return launch_family_subset<rays_family>(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_rays(atmo_shade_rays_indexed_kernel<F | KF_RAYS | KF_INDEX, L>, ic.n_index, stream, rc, yc, ic);
+    });
 }
-hipError_t launch_shade_rays_indexed(int flags, const RenderConsts &rc, const RayConsts &yc, const RayIndexConsts &ic, hipStream_t stream) {
-    if (yc.rays == nullptr || yc.out == nullptr || yc.n == 0 || yc.width == 0 || yc.first > 0xffffffffu - (yc.n - 1u) || ic.index == nullptr || ic.n_index == 0)
-        return hipErrorInvalidValue;
-    switch (flags) {
-#define ATMO_RAYS_LAUNCH(F) case (F): return launch_rays_indexed(atmo_shade_rays_indexed_kernel<(F) | KF_RAYS | KF_INDEX, 0>, rc, yc, ic, stream);
-#define ATMO_RAYS_LAUNCH_TWIN(F) case (F): return rc.light_steps == 8 ? launch_rays_indexed(atmo_shade_rays_indexed_kernel<(F) | KF_RAYS | KF_INDEX, 8>, rc, yc, ic, stream) \
-                                                                      : launch_rays_indexed(atmo_shade_rays_indexed_kernel<(F) | KF_RAYS | KF_INDEX, 0>, rc, yc, ic, stream);
-        ATMO_RAYS_FAMILIES(ATMO_RAYS_LAUNCH, ATMO_RAYS_LAUNCH_TWIN)
-#undef ATMO_RAYS_LAUNCH
-#undef ATMO_RAYS_LAUNCH_TWIN
-    default: return hipErrorInvalidValue;
-    }
-}
-#undef ATMO_RAYS_FAMILIES
 
 // The key (include/atmo_ray_order.h, THE KEY, item by item): the direction's cell in a 512 x 512 octahedral map, Morton-interleaved.  Every operation fp32
 // and rounded on its own: no `fp contract` pragma in this function (the file is compiled with -ffp-contract=off), so RN(RN(u * 256) + 256) stays a
@@ -4449,46 +4413,33 @@ __global__ __launch_bounds__(RAYS_BLOCK, detail_min_waves(FLAGS & ~(KF_RAYS | KF
     static_assert((FLAGS & KF_RAYS) != 0 && (FLAGS & KF_DETAIL) != 0 && (FLAGS & KF_INDEX) != 0, "indexed detail ray kernels carry KF_RAYS | KF_INDEX | KF_DETAIL");
     shade_pixel<FLAGS, LSTEPS, 1>(rc, 0, 0, nullptr, nullptr, nullptr, &xc, &yc, &ic);
 }
-// the level-0 cloud families of ATMO_RAYS_FAMILIES; with KF_CUBE_LOD they are ATMO_RAY_QUADS_FAMILIES
-#define ATMO_RAYS_DETAIL_FAMILIES(ONE, LOD)              \
-    ONE((LOD) | KF_PRECISE | KF_CLOUDS)                      \
-    ONE((LOD) | KF_PRECISE | KF_CLOUDS | KF_CLOUD_LIGHT_RM)  \
-    ONE((LOD) | KF_PRECISE | KF_LITE | KF_CLOUDS)
-// flags WITHOUT KF_RAYS | KF_INDEX | KF_DETAIL, which the launcher adds; ic == nullptr: the whole batch
-hipError_t launch_shade_rays_detail(int flags, const RenderConsts &rc, const RayConsts &yc, const DetailConsts &xc, const RayIndexConsts *ic, hipStream_t stream) {
-    if (yc.rays == nullptr || yc.out == nullptr || yc.n == 0 || yc.width == 0 || yc.first > 0xffffffffu - (yc.n - 1u)) return hipErrorInvalidValue;
-    if (ic != nullptr && (ic->index == nullptr || ic->n_index == 0)) return hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)(((uint64_t)(ic ? ic->n_index : yc.n) + (RAYS_BLOCK - 1)) / RAYS_BLOCK);   // at most 2^24
-    switch (flags) {
-#define ATMO_RAYS_DETAIL_LAUNCH(F)                                                                                                                             \
-    case (F):                                                                                                                                                  \
-        if (ic) hipLaunchKernelGGL((atmo_detail_rays_indexed_kernel<(F) | KF_RAYS | KF_INDEX | KF_DETAIL, 0>), dim3(blocks), dim3(RAYS_BLOCK), 0, stream, rc, yc, *ic, xc); \
-        else hipLaunchKernelGGL((atmo_detail_rays_kernel<(F) | KF_RAYS | KF_DETAIL, 0>), dim3(blocks), dim3(RAYS_BLOCK), 0, stream, rc, yc, xc);               \
-        return hipGetLastError();
-        ATMO_RAYS_DETAIL_FAMILIES(ATMO_RAYS_DETAIL_LAUNCH, 0)
-#undef ATMO_RAYS_DETAIL_LAUNCH
-    default: return hipErrorInvalidValue;
-    }
+// the cloud families of the level-0 ray kernels; under the declared sampler every ray-quad family is one
+constexpr bool rays_detail_family(int flags) { return rays_family(flags) && (flags & KF_CLOUDS) != 0; }
+static_assert(subset_families<rays_detail_family> == 3 && subset_twins<rays_detail_family> == 0, "three ray-detail families, none of them a twin");
+static hipError_t shade_rays_detail(int flags, const RenderConsts &rc, const RayConsts &yc, const RayIndexConsts *ic, const DetailConsts &xc, hipStream_t stream) {
+    if (!ray_batch_valid(yc) || (ic != nullptr && !ray_index_valid(*ic))) return hipErrorInvalidValue;
+    return launch_family_subset<rays_detail_family>(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        return ic ? launch_rays(atmo_detail_rays_indexed_kernel<F | KF_RAYS | KF_INDEX | KF_DETAIL, L>, ic->n_index, stream, rc, yc, *ic, xc)
+                  : launch_rays(atmo_detail_rays_kernel<F | KF_RAYS | KF_DETAIL, L>, yc.n, stream, rc, yc, xc);
+    });
 }
-// flags WITH KF_CUBE_LOD; yc as launch_shade_ray_quads'
-hipError_t launch_shade_ray_quads_detail(int flags, const RenderConsts &rc, const RayConsts &yc, const DetailConsts &xc, hipStream_t stream) {
-    if (yc.rays == nullptr || yc.out == nullptr || yc.n == 0 || (yc.n & 3u) != 0 || yc.width == 0 || (uint64_t)yc.first + (yc.n >> 2) > ((uint64_t)1 << 30))
-        return hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)(((uint64_t)yc.n + (RAYS_BLOCK - 1)) / RAYS_BLOCK);
-    switch (flags) {
-#define ATMO_RAY_QUADS_DETAIL_LAUNCH(F)                                                                                                          \
-    case (F):                                                                                                                                    \
-        hipLaunchKernelGGL((atmo_detail_rays_kernel<(F) | KF_RAYS | KF_DETAIL, 0>), dim3(blocks), dim3(RAYS_BLOCK), 0, stream, rc, yc, xc);      \
-        return hipGetLastError();
-        ATMO_RAYS_DETAIL_FAMILIES(ATMO_RAY_QUADS_DETAIL_LAUNCH, KF_CUBE_LOD)
-#undef ATMO_RAY_QUADS_DETAIL_LAUNCH
-    default: return hipErrorInvalidValue;
-    }
+static hipError_t shade_ray_quads_detail(int flags, const RenderConsts &rc, const RayConsts &yc, const DetailConsts &xc, hipStream_t stream) {
+    if (!ray_quads_valid(yc)) return hipErrorInvalidValue;
+    return launch_family_subset<ray_quads_family>(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_rays(atmo_detail_rays_kernel<F | KF_RAYS | KF_DETAIL, L>, yc.n, stream, rc, yc, xc);
+    });
 }
-#undef ATMO_RAYS_DETAIL_FAMILIES
+// The one ray launcher (atmo_device.h): the call's shape, list and detail constants choose among the five launches above.  They stay five functions,
+// each behind its kernel, because that is the order the kernels are instantiated in, and with it their places in the code object (tools/isa_diff.py).
+hipError_t launch_shade_rays(int flags, RayShape shape, const RenderConsts &rc, const RayConsts &yc, const RayIndexConsts *ic, const DetailConsts *xc,
+                             hipStream_t stream) {
+    if (shape == RAY_QUADS) return ic ? hipErrorInvalidValue : xc ? shade_ray_quads_detail(flags, rc, yc, *xc, stream) : shade_ray_quads(flags, rc, yc, stream);
+    if (xc) return shade_rays_detail(flags, rc, yc, ic, *xc, stream);
+    return ic ? shade_rays_indexed(flags, rc, yc, *ic, stream) : shade_ray_batch(flags, rc, yc, stream);
+}
 
 // ---- cloud detail into colour targets through a depth source (KF_DETAIL | KF_DEPTH | KF_TARGET [| KF_VIEWS]; include/atmo_detail_target.h) -----------------
-// The six families of ATMO_DETAIL_FAMILIES once more, as a single draw and as a view batch: atmo_render_detail_kernel's shading -- shade_pixel's DETAIL form,
+// The six cloud-detail families (detail_family) once more, as a single draw and as a view batch: atmo_render_detail_kernel's shading -- shade_pixel's DETAIL form,
 // the light in place under both samplers, no queue LDS -- with the depth read through load_depth (DepthConsts) and the store, or the composite's decode /
 // blend / encode, through store_target in all seven formats (TargetConsts).  shade_pixel states none of it a second time: the three forms meet in its
 // arguments.  Single draw: row-major over the rect's grid, as atmo_render_detail_kernel.  Batch: ATMO_VIEWS_KERNEL_BODY in its unordered form (no tile
@@ -4523,25 +4474,17 @@ __global__ __launch_bounds__(TILE_W *TILE_H, detail_min_waves(FLAGS)) void atmo_
 hipError_t launch_render_detail_target(int flags, const RenderConsts &rc, const TargetConsts &tc, const DepthConsts &dc, const DetailConsts &xc, hipStream_t stream) {
     if (rc.tile_order != nullptr || rc.tile_cost != nullptr) return hipErrorInvalidValue;   // row-major, nothing recorded
     if (tc.pixels == nullptr || tc.pitch_bytes <= 0 || !target_format_known(tc.format) || !depth_consts_valid(dc)) return hipErrorInvalidValue;
-    switch (flags) {
-#define ATMO_DETAIL_TARGET_LAUNCH(F) case (F): return launch_rect(atmo_detail_target_kernel<(F) | KF_DETAIL | KF_DEPTH | KF_TARGET, 0>, rc, stream, tc, dc, xc);
-        ATMO_DETAIL_FAMILIES(ATMO_DETAIL_TARGET_LAUNCH)
-#undef ATMO_DETAIL_TARGET_LAUNCH
-    default: return hipErrorInvalidValue;
-    }
+    return launch_family_subset<detail_family>(flags, rc.light_steps, [&](auto F, auto L) -> hipError_t {
+        return launch_rect(atmo_detail_target_kernel<F | KF_DETAIL | KF_DEPTH | KF_TARGET, L>, rc, stream, tc, dc, xc);
+    });
 }
 hipError_t launch_render_views_detail_target(int flags, const RenderConsts *table, const ViewsTargetConsts &vtc, const ViewsDepthConsts &vdc,
                                              const ViewsDetailConsts &vxc, hipStream_t stream) {
     if (vtc.v.order != nullptr || vtc.v.cost != nullptr) return hipErrorInvalidValue;   // view-major, nothing recorded
     if (!batch_targets_valid(vtc.v.first_block, vtc.target, vdc.depth)) return hipErrorInvalidValue;
-    switch (flags) {
-#define ATMO_DETAIL_VIEWS_TARGET_LAUNCH(F) \
-    case (F): return launch_batch(atmo_detail_views_target_kernel<(F) | KF_DETAIL | KF_DEPTH | KF_VIEWS | KF_TARGET, 0>, vtc.v.first_block, table, stream, vtc, vdc, vxc);
-        ATMO_DETAIL_FAMILIES(ATMO_DETAIL_VIEWS_TARGET_LAUNCH)
-#undef ATMO_DETAIL_VIEWS_TARGET_LAUNCH
-    default: return hipErrorInvalidValue;
-    }
+    return launch_family_subset<detail_family>(flags, 0, [&](auto F, auto L) -> hipError_t {   // (no detail family is a twin: no light-step count to pass)
+        return launch_batch(atmo_detail_views_target_kernel<F | KF_DETAIL | KF_DEPTH | KF_VIEWS | KF_TARGET, L>, vtc.v.first_block, table, stream, vtc, vdc, vxc);
+    });
 }
-#undef ATMO_DETAIL_FAMILIES
 
 }  // namespace atmo

@@ -669,7 +669,7 @@ class PlanetAtmosphere:
             tgt = N.AtmoTarget(colour.data_ptr(), N.TARGET_RGBA32F, 0)
         # cloud detail into a packed or pitched colour tensor, or from a depth source (include/atmo_detail_target.h): one entry point, which takes both as
         # structures -- a plain depth tensor is a tight D32 source.  Float colour with float depth stays atmo_render; the proxy draws have no detail form
-        fn = self._detail_target_entry("atmo_render_detail_target") if proxy is None and tgt is not None else None
+        fn = self._entry("atmo_render_detail_target") if proxy is None and tgt is not None and self._serves_cloud_detail() else None
         if fn is not None and src is None:
             src = N.AtmoDepth(depth.data_ptr(), N.DEPTH_D32_SFLOAT, 0)
         stream = _stream_handle(stream, depth)
@@ -684,31 +684,14 @@ class PlanetAtmosphere:
         return colour
 
     # ---- caller-supplied rays (include/atmo_rays.h) --------------------------------------------------------------------------------
-    def _rays_entry(self, name: str):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_rays.h); rebuild it")
-        return fn
+    def _entry(self, name: str):
+        """An entry point of one of the optional headers (N.optional_headers); RuntimeError naming the header where the library lacks it."""
+        return N.optional_entry(self._lib, name)
 
-    def _detail_target_entry(self, name: str):
-        """The entry point of include/atmo_detail_target.h where this node's target draws are shaded with cloud detail -- `cloud_detail` on and a shader
-        with clouds --, else None: the call goes where it went before."""
-        if not (getattr(self, "_cloud_detail", False) and getattr(self, "_shader", DefaultShader).cloud_steps):
-            return None
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_detail_target.h): no cloud detail into targets; rebuild it")
-        return fn
-
-    def _ray_detail_entry(self, name: str):
-        """The entry point of include/atmo_ray_detail.h where this node's rays are shaded with cloud detail -- `cloud_detail` on and a shader with clouds --
-        else None: the call goes where it went before (a node without clouds has no density to evaluate)."""
-        if not (getattr(self, "_cloud_detail", False) and getattr(self, "_shader", DefaultShader).cloud_steps):
-            return None
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_ray_detail.h): no cloud detail for rays; rebuild it")
-        return fn
+    def _serves_cloud_detail(self) -> bool:
+        """Whether this node's rays and target draws are shaded with cloud detail (include/atmo_ray_detail.h, atmo_detail_target.h): `cloud_detail` on and
+        a shader with clouds.  Without, the call goes where it went before (a node without clouds has no density to evaluate)."""
+        return bool(getattr(self, "_cloud_detail", False) and getattr(self, "_shader", DefaultShader).cloud_steps)
 
     def shade_rays(self, rays, camera=None, *, width=None, first: int = 0, out=None, stream=None, time: float = 0.0, index=None):
         """Shades caller-supplied rays: what atmosphere_fragment returns for a fragment with each ray (atmo_shade_rays; include/atmo_rays.h states the
@@ -736,10 +719,8 @@ class PlanetAtmosphere:
             out = (torch.empty if index is None else torch.zeros)((n, 4), dtype=torch.float32, device=rays.device)
         elif _check_rays(out, "out", 4) != n:
             raise ValueError("out must have one row per ray: shape (n, 4)")
-        fn = self._ray_detail_entry("atmo_shade_rays_detail")
-        detail = fn is not None
-        if not detail:
-            fn = self._rays_entry("atmo_shade_rays") if index is None else self._ray_order_entry("atmo_shade_rays_indexed")
+        detail = self._serves_cloud_detail()
+        fn = self._entry("atmo_shade_rays_detail" if detail else "atmo_shade_rays" if index is None else "atmo_shade_rays_indexed")
         stream = _stream_handle(stream, rays)
         self._bake_if_needed(stream)
         nf = _to_native_frame(self.make_frame(camera if camera is not None else _WORLD_RAY_SPACE, time))
@@ -751,12 +732,6 @@ class PlanetAtmosphere:
         return out
 
     # ---- coherent ray queues (include/atmo_ray_order.h) ---------------------------------------------------------------------------
-    def _ray_order_entry(self, name: str):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_ray_order.h); rebuild it")
-        return fn
-
     def ray_order(self, rays, stream=None):
         """The coherence order of a ray queue, computed on the device (atmo_ray_order; include/atmo_ray_order.h states the key): a CUDA int32 (n,) tensor,
         the stable ascending sort of the rays' numbers by the octahedral cell of their directions -- godot_atmosphere_shader_amd.ray_order.ray_order is
@@ -769,7 +744,7 @@ class PlanetAtmosphere:
         order = torch.empty((n,), dtype=torch.int32, device=rays.device)
         if n == 0:
             return order
-        fn, size = self._ray_order_entry("atmo_ray_order"), self._ray_order_entry("atmo_ray_order_scratch_bytes")
+        fn, size = self._entry("atmo_ray_order"), self._entry("atmo_ray_order_scratch_bytes")
         need = C.c_size_t(0)
         N.check(self._ctx, size(n, C.byref(need)))
         handle = _stream_handle(stream, rays)
@@ -784,12 +759,6 @@ class PlanetAtmosphere:
         return order
 
     # ---- ray lists: counted queues and the sure-miss cull (include/atmo_ray_list.h) ------------------------------------------------
-    def _ray_list_entry(self, name: str):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise RuntimeError(f"libatmo_hip.so does not export {name} (include/atmo_ray_list.h); rebuild it")
-        return fn
-
     def ray_list(self, rays, count=None, order=True, cull=False, camera=None, out=None, stream=None):
         """An index list for `shade_rays(index=...)` built on the device (atmo_ray_list; include/atmo_ray_list.h): `(index, listed)`, a CUDA int32
         (capacity,) tensor -- the listed rays, then -1 (ATMO_RAY_LIST_END) entries, which the indexed call skips -- and a CUDA int32 (1,) tensor, their
@@ -814,7 +783,7 @@ class PlanetAtmosphere:
             raise ValueError("out must have one row per ray: shape (n, 4)")
         if capacity == 0:
             return torch.empty((0,), dtype=torch.int32, device=rays.device), torch.zeros((1,), dtype=torch.int32, device=rays.device)
-        fn, size = self._ray_list_entry("atmo_ray_list"), self._ray_list_entry("atmo_ray_list_scratch_bytes")
+        fn, size = self._entry("atmo_ray_list"), self._entry("atmo_ray_list_scratch_bytes")
         need = C.c_size_t(0)
         N.check(self._ctx, size(capacity, C.byref(need)))
         handle = _stream_handle(stream, rays)
@@ -842,7 +811,7 @@ class PlanetAtmosphere:
         frame = self.make_frame(camera, 0.0, rect)
         x0, y0, x1, y1 = frame["rect"]
         rays = torch.empty(((y1 - y0) * (x1 - x0), 8), dtype=torch.float32, device=depth.device)
-        fn = self._rays_entry("atmo_debug_frame_rays")
+        fn = self._entry("atmo_debug_frame_rays")
         stream = _stream_handle(stream, depth)
         nf = _to_native_frame(frame)
         N.check(self._ctx, fn(self._ctx, C.byref(nf), C.c_void_p(depth.data_ptr()), C.c_void_p(rays.data_ptr()), C.c_void_p(stream or 0)))
@@ -872,9 +841,7 @@ class PlanetAtmosphere:
             out = torch.empty((n, 4), dtype=torch.float32, device=quads.device)
         elif _check_rays(out, "out", 4) != n:
             raise ValueError("out must have one row per ray: shape (4 * n_quads, 4)")
-        fn = self._ray_detail_entry("atmo_shade_ray_quads_detail") or getattr(self._lib, "atmo_shade_ray_quads", None)
-        if fn is None:
-            raise RuntimeError("libatmo_hip.so does not export atmo_shade_ray_quads (include/atmo_ray_quads.h); rebuild it")
+        fn = self._entry("atmo_shade_ray_quads_detail" if self._serves_cloud_detail() else "atmo_shade_ray_quads")
         stream = _stream_handle(stream, quads)
         self._bake_if_needed(stream)
         nf = _to_native_frame(self.make_frame(camera if camera is not None else _WORLD_RAY_SPACE, time))
@@ -1004,7 +971,7 @@ class PlanetAtmosphere:
         packed = sources[0] or any(t is not None for t in tgts)   # (the depth-source batches take every colour tensor as an N.AtmoTarget)
         # cloud detail into targets (include/atmo_detail_target.h): the depth-source batch's structures, plain depth tensors as tight D32 sources.  The
         # float-only batch and the proxy batches have no detail form and refuse as before
-        fn = self._detail_target_entry("atmo_render_views_detail_target") if proxy is None and packed else None
+        fn = self._entry("atmo_render_views_detail_target") if proxy is None and packed and self._serves_cloud_detail() else None
         if fn is not None and not sources[0]:
             depth_ptrs = [N.AtmoDepth(p, N.DEPTH_D32_SFLOAT, 0) for p in depth_ptrs]
         if packed:   # one batch, one struct: a contiguous float32 tensor among pitched ones is an RGBA32F target without a pitch
