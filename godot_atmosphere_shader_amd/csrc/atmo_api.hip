@@ -2426,14 +2426,22 @@ struct OrderPointer {
     const char *name;
     unsigned align;
 };
-static int ray_order_checks(AtmoContext *ctx, const std::string &who, uint32_t n, std::initializer_list<OrderPointer> pointers, bool has_scratch,
-                            size_t scratch_bytes) {
-    if (n > atmo::RAY_ORDER_MAX_RAYS) return fail(ctx, ATMO_E_ARG, who + ": at most 2^28 elements");
+static int refuse_null(AtmoContext *ctx, const std::string &who, std::initializer_list<OrderPointer> pointers) {   // the first null pointer of the list
     for (const OrderPointer &q : pointers)
         if (!q.p) return fail(ctx, ATMO_E_ARG, who + ": null " + q.name);
+    return ATMO_OK;
+}
+static int refuse_misaligned(AtmoContext *ctx, const std::string &who, std::initializer_list<OrderPointer> pointers) {   // the first; an optional pointer's null is aligned
     for (const OrderPointer &q : pointers)
         if ((reinterpret_cast<uintptr_t>(q.p) & (q.align - 1u)) != 0)
             return fail(ctx, ATMO_E_ARG, who + ": " + q.name + " must be " + std::to_string(q.align) + "-byte aligned");
+    return ATMO_OK;
+}
+static int ray_order_checks(AtmoContext *ctx, const std::string &who, uint32_t n, std::initializer_list<OrderPointer> pointers, bool has_scratch,
+                            size_t scratch_bytes) {
+    if (n > atmo::RAY_ORDER_MAX_RAYS) return fail(ctx, ATMO_E_ARG, who + ": at most 2^28 elements");
+    ATMO_TRY(refuse_null(ctx, who, pointers));
+    ATMO_TRY(refuse_misaligned(ctx, who, pointers));
     if (has_scratch && scratch_bytes < atmo::ray_order_scratch_bytes(n))
         return fail(ctx, ATMO_E_ARG, who + ": scratch_bytes is below atmo_ray_order_scratch_bytes (" + std::to_string(atmo::ray_order_scratch_bytes(n)) + ")");
     if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
@@ -2501,19 +2509,12 @@ int atmo_ray_list(AtmoContext *ctx, const AtmoFrame *frame, const AtmoRay *rays_
     if (capacity == 0) return ATMO_OK;   // nothing to list
     if (capacity > atmo::RAY_ORDER_MAX_RAYS) return fail(ctx, ATMO_E_ARG, who + ": at most 2^28 rays");
     if (flags & ~(ATMO_RAY_LIST_ORDER | ATMO_RAY_LIST_CULL)) return fail(ctx, ATMO_E_ARG, who + ": unknown flag bits");
-    if (!rays_dev) return fail(ctx, ATMO_E_ARG, who + ": null rays_dev");
-    if (!index_dev) return fail(ctx, ATMO_E_ARG, who + ": null index_dev");
-    if (!scratch_dev) return fail(ctx, ATMO_E_ARG, who + ": null scratch_dev");
+    const OrderPointer rays = {rays_dev, "rays_dev", 16}, index = {index_dev, "index_dev", 4}, scratch = {scratch_dev, "scratch_dev", 16};
+    ATMO_TRY(refuse_null(ctx, who, {rays, index, scratch}));
     const bool cull = (flags & ATMO_RAY_LIST_CULL) != 0;
     if (cull && !frame) return fail(ctx, ATMO_E_ARG, who + ": ATMO_RAY_LIST_CULL needs a frame");
     if (cull && !rgba_dev) return fail(ctx, ATMO_E_ARG, who + ": ATMO_RAY_LIST_CULL needs rgba_dev");
-    auto misaligned = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0; };
-    if (misaligned(rays_dev, 16)) return fail(ctx, ATMO_E_ARG, who + ": rays_dev must be 16-byte aligned");
-    if (misaligned(rgba_dev, 16)) return fail(ctx, ATMO_E_ARG, who + ": rgba_dev must be 16-byte aligned");
-    if (misaligned(scratch_dev, 16)) return fail(ctx, ATMO_E_ARG, who + ": scratch_dev must be 16-byte aligned");
-    if (misaligned(index_dev, 4)) return fail(ctx, ATMO_E_ARG, who + ": index_dev must be 4-byte aligned");
-    if (misaligned(count_dev, 4)) return fail(ctx, ATMO_E_ARG, who + ": count_dev must be 4-byte aligned");
-    if (misaligned(listed_dev, 4)) return fail(ctx, ATMO_E_ARG, who + ": listed_dev must be 4-byte aligned");
+    ATMO_TRY(refuse_misaligned(ctx, who, {rays, {rgba_dev, "rgba_dev", 16}, scratch, index, {count_dev, "count_dev", 4}, {listed_dev, "listed_dev", 4}}));
     if (scratch_bytes < atmo::ray_list_scratch_bytes(capacity))
         return fail(ctx, ATMO_E_ARG, who + ": scratch_bytes is below atmo_ray_list_scratch_bytes (" + std::to_string(atmo::ray_list_scratch_bytes(capacity)) + ")");
     if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
@@ -2541,7 +2542,7 @@ int atmo_debug_frame_rays(AtmoContext *ctx, const AtmoFrame *frame, const float 
     ATMO_TRY(check_frame(ctx, who, frame, &empty));
     if (empty) return ATMO_OK;
     if (!depth_dev || !rays_dev) return fail(ctx, ATMO_E_ARG, who + ": null device pointer");
-    if ((reinterpret_cast<uintptr_t>(rays_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, who + ": rays_dev must be 16-byte aligned");
+    ATMO_TRY(refuse_misaligned(ctx, who, {{rays_dev, "rays_dev", 16}}));
     if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     atmo::RenderConsts rc;

@@ -4065,25 +4065,38 @@ __global__ __launch_bounds__(256) void atmo_ray_key_kernel(const float4 *__restr
 // histogram is [digit][chunk] with as many chunks as n needs, and the scan -- one workgroup per digit -- walks its row in trips of RAY_SCAN_TRIP chunks with
 // a carry; the digits' own bases are the exclusive scan of 64 totals, which every scatter wave forms for itself in one lane each.
 // Pass 0 reads plain keys (the index is the position), passes 1 and 2 read the pairs the pass before wrote (8 bytes, one store per element), pass 2 writes
-// the indices alone.  Scratch, in uint32 words: pairs B [0, 2 n), pairs C [2 n, 4 n), histogram [4 n, 4 n + 64 chunks), totals (64).  atmo_ray_order's keys
-// lie in the first n words of C, which pass 1 overwrites when pass 0 has read them.
+// the indices alone.  Scratch (RaySortScratch), in uint32 words: pairs B [0, 2 n), pairs C [2 n, 4 n), histogram [4 n, 4 n + 64 chunks), totals (64), and
+// behind them the ray list's word m.  The keys of atmo_ray_order and atmo_ray_list lie in the first n words of C, which pass 1 overwrites when pass 0 has
+// read them.
+// The pass has TWO FORMS, one body (ray_sort_hist_pass, ray_sort_scatter_pass).  The order's kernels are bounded by an argument n.  The ray list's
+// (include/atmo_ray_list.h) are COUNTED: what bounds them is a device word -- the caller's *count clamped to the capacity in front of the first scatter,
+// the live total m that scatter leaves in the scratch behind it -- so the host never learns a length and a captured graph serves every one.  The counted
+// grids are the capacity's, and so are the scan's rows; a wave whose chunk lies beyond the bound writes its zero histogram column, or nothing, and leaves.
+// A counted pass 0 also drops the DEAD keys, those RAY_LIST_CULL marked: no pass lists them, and the later passes never see one.
 constexpr int RAY_SORT_PASSES = 3, RAY_SORT_DIGITS = 1 << ORDER_KEY_BITS;
 static_assert(ORDER_KEY_BITS * RAY_SORT_PASSES == RAY_KEY_BITS && RAY_SORT_DIGITS == 64, "three passes of match_class's six bits; one lane per digit");
 constexpr int RAY_SORT_STEPS = 16;                        // steps of 64 keys a wave walks
 constexpr uint32_t RAY_SORT_CHUNK = 64u * RAY_SORT_STEPS; // keys per chunk (per single-wave workgroup)
 constexpr int RAY_SCAN_BLOCK = 256, RAY_SCAN_PER_THREAD = 4;
 constexpr uint32_t RAY_SCAN_TRIP = (uint32_t)RAY_SCAN_BLOCK * RAY_SCAN_PER_THREAD;   // chunks per trip of the scan
-static uint32_t ray_sort_chunks(uint32_t n) { return (uint32_t)(((uint64_t)n + RAY_SORT_CHUNK - 1u) / RAY_SORT_CHUNK); }
-size_t ray_order_scratch_bytes(uint32_t n) {
-    return 4 * (size_t)n * sizeof(uint32_t) + ((size_t)RAY_SORT_DIGITS * ray_sort_chunks(n) + RAY_SORT_DIGITS) * sizeof(uint32_t);
+constexpr uint32_t RAY_LIST_DEAD = 1u << 31;   // a culled ray's key: no pass lists it
+__device__ __forceinline__ uint32_t ray_list_bound(const uint32_t *bound, uint32_t capacity) {   // min(*bound, capacity); no word: the capacity
+    if (bound == nullptr) return capacity;
+    const uint32_t n = *bound;
+    return n < capacity ? n : capacity;
 }
 
 // PAIRS: `in` holds (key, index) pairs, else plain keys.  hist[digit][chunk] = keys of the chunk with that digit
-template <bool PAIRS>
-__global__ __launch_bounds__(64) void atmo_ray_sort_hist_kernel(const uint32_t *__restrict__ in, uint32_t n, int shift, uint32_t chunks,
-                                                                uint32_t *__restrict__ hist) {
+template <bool PAIRS, bool COUNTED, bool DEAD>
+__device__ __forceinline__ void ray_sort_hist_pass(const uint32_t *in, uint32_t n, int shift, uint32_t chunks, uint32_t *hist) {
     __shared__ uint32_t cnt[RAY_SORT_DIGITS];
     const uint32_t lane = threadIdx.x, i0 = blockIdx.x * RAY_SORT_CHUNK;
+    if constexpr (COUNTED) {
+        if (i0 >= n) {   // (uniform: the wave is the workgroup)
+            hist[lane * chunks + blockIdx.x] = 0u;
+            return;
+        }
+    }
     cnt[lane] = 0;
     uint32_t key[RAY_SORT_STEPS];
 #pragma unroll
@@ -4094,13 +4107,18 @@ __global__ __launch_bounds__(64) void atmo_ray_sort_hist_kernel(const uint32_t *
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < RAY_SORT_STEPS; ++t) {
-        const bool valid = i0 + (uint32_t)t * 64u + lane < n;
+        const bool valid = i0 + (uint32_t)t * 64u + lane < n && !(DEAD && (key[t] & RAY_LIST_DEAD) != 0u);
         const uint32_t d = (key[t] >> shift) & (uint32_t)(RAY_SORT_DIGITS - 1);
         const unsigned long long m = match_class(d, valid);
         if (valid && lanes_below(m) == 0) cnt[d] += (uint32_t)__builtin_popcountll(m);   // one lane per digit present
     }
     __syncthreads();
     hist[lane * chunks + blockIdx.x] = cnt[lane];
+}
+template <bool PAIRS>
+__global__ __launch_bounds__(64) void atmo_ray_sort_hist_kernel(const uint32_t *__restrict__ in, uint32_t n, int shift, uint32_t chunks,
+                                                                uint32_t *__restrict__ hist) {
+    ray_sort_hist_pass<PAIRS, false, false>(in, n, shift, chunks, hist);
 }
 
 // hist[digit][chunk] -> the chunk's first position INSIDE its digit (exclusive, chunks in order); totals[digit] = keys with that digit.  One workgroup per
@@ -4142,11 +4160,13 @@ __global__ __launch_bounds__(RAY_SCAN_BLOCK) void atmo_ray_sort_scan_kernel(uint
     if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
 
-// The wave writes its chunk, in order, behind base[digit][chunk] + the digit's own base.  LAST: the indices alone (the order), else (key, index) pairs
-template <bool PAIRS, bool LAST>
-__global__ __launch_bounds__(64) void atmo_ray_sort_scatter_kernel(const uint32_t *__restrict__ in, uint32_t n, int shift, uint32_t chunks,
-                                                                   const uint32_t *__restrict__ base, const uint32_t *__restrict__ totals,
-                                                                   uint32_t *__restrict__ out) {
+// The wave writes its chunk, in order, behind base[digit][chunk] + the digit's own base.  LAST: the indices alone (the order), else (key, index) pairs.
+// `limit` bounds the store: a store lands inside the buffers whatever the scratch held (pos < n always holds for a histogram of these keys).  COUNTED,
+// total_out (pass 0, else null): the live total -- the sum of the 64 digit totals, which every wave forms -- leaves through the first wave's last lane, a
+// plain vector store
+template <bool PAIRS, bool LAST, bool COUNTED, bool DEAD>
+__device__ __forceinline__ void ray_sort_scatter_pass(const uint32_t *in, uint32_t n, uint32_t limit, int shift, uint32_t chunks, const uint32_t *base,
+                                                      const uint32_t *totals, uint32_t *out, uint32_t *total_out) {
     __shared__ uint32_t off[RAY_SORT_DIGITS];
     const uint32_t lane = threadIdx.x, i0 = blockIdx.x * RAY_SORT_CHUNK;
     {   // digit `lane`: the keys of all smaller digits, then the chunks in front of this one
@@ -4156,6 +4176,14 @@ __global__ __launch_bounds__(64) void atmo_ray_sort_scatter_kernel(const uint32_
         for (int d = 1; d < 64; d <<= 1) {
             const uint32_t x = __shfl_up(incl, d);
             if (lane >= (uint32_t)d) incl += x;
+        }
+        // (true: the sum holds `total`, and all 64 sum to n at most.  It is here as a second use of the scan's result: this body reaches a kernel unrolled,
+        // and with a single use the compiler's reassociation splits the last step of the scan off the difference below -- another prologue than the one the
+        // kernels had with the loop written in their own bodies, tools/isa_diff.py)
+        __builtin_assume(incl >= total);
+        if constexpr (COUNTED) {
+            if (total_out != nullptr && blockIdx.x == 0 && lane == 63u) *total_out = incl;
+            if (i0 >= n) return;   // (uniform: the wave is the workgroup)
         }
         off[lane] = (incl - total) + base[lane * chunks + blockIdx.x];
     }
@@ -4175,7 +4203,7 @@ __global__ __launch_bounds__(64) void atmo_ray_sort_scatter_kernel(const uint32_
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < RAY_SORT_STEPS; ++t) {
-        const bool valid = i0 + (uint32_t)t * 64u + lane < n;
+        const bool valid = i0 + (uint32_t)t * 64u + lane < n && !(DEAD && (key[t] & RAY_LIST_DEAD) != 0u);
         const uint32_t d = (key[t] >> shift) & (uint32_t)(RAY_SORT_DIGITS - 1);
         const unsigned long long m = match_class(d, valid);
         const int r = lanes_below(m);
@@ -4184,11 +4212,51 @@ __global__ __launch_bounds__(64) void atmo_ray_sort_scatter_kernel(const uint32_
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         if (valid && r == 0) off[d] += (uint32_t)__builtin_popcountll(m);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (valid && pos < n) {   // (pos < n always holds for a histogram of these keys; the bound keeps a store inside the buffers whatever the scratch held)
+        if (valid && pos < limit) {
             if constexpr (LAST) out[pos] = idx[t];
             else reinterpret_cast<uint2 *>(out)[pos] = make_uint2(key[t], idx[t]);
         }
     }
+}
+template <bool PAIRS, bool LAST>
+__global__ __launch_bounds__(64) void atmo_ray_sort_scatter_kernel(const uint32_t *__restrict__ in, uint32_t n, int shift, uint32_t chunks,
+                                                                   const uint32_t *__restrict__ base, const uint32_t *__restrict__ totals,
+                                                                   uint32_t *__restrict__ out) {
+    ray_sort_scatter_pass<PAIRS, LAST, false, false>(in, n, n, shift, chunks, base, totals, out, nullptr);
+}
+
+// The scratch for n elements, sliced behind `base`: pointers into a scratch buffer, or -- base = size_t(0) -- the slices' first words, the last of them
+// the order's size.  pairs_c's first n words are also the keys
+template <class P>
+struct RaySortScratch {
+    P pairs_b, pairs_c, hist, totals, live;
+    uint32_t chunks;
+};
+template <class P>
+static RaySortScratch<P> ray_sort_scratch(P base, uint32_t n) {
+    const uint32_t chunks = (uint32_t)(((uint64_t)n + RAY_SORT_CHUNK - 1u) / RAY_SORT_CHUNK);
+    const size_t hist = 4 * (size_t)n, totals = hist + (size_t)RAY_SORT_DIGITS * chunks;
+    return {base, base + 2 * (size_t)n, base + hist, base + totals, base + (totals + RAY_SORT_DIGITS), chunks};
+}
+size_t ray_order_scratch_bytes(uint32_t n) { return ray_sort_scratch(size_t(0), n).live * sizeof(uint32_t); }
+size_t ray_list_scratch_bytes(uint32_t capacity) { return (ray_sort_scratch(size_t(0), capacity).live + 4) * sizeof(uint32_t); }   // m, in 16 bytes of its own
+
+// One pass over `in`: histogram, scan, scatter, ordered by the stream.  `bound` is what bounds the two kernels: the order's n, or the list's device word
+// and capacity, whose scatter also takes total_out.  The two pair passes read B into C and C into the index
+template <class Hist, class Scatter, class... Bound>
+static void ray_sort_pass(const RaySortScratch<uint32_t *> &s, hipStream_t stream, Hist hist_kernel, Scatter scatter_kernel, const uint32_t *in, int shift,
+                          uint32_t *out, uint32_t *total_out, Bound... bound) {
+    const dim3 waves(s.chunks), wave(64);
+    hipLaunchKernelGGL(hist_kernel, waves, wave, 0, stream, in, bound..., shift, s.chunks, s.hist);
+    hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, dim3(RAY_SORT_DIGITS), dim3(RAY_SCAN_BLOCK), 0, stream, s.hist, s.chunks, s.totals);
+    if constexpr (sizeof...(Bound) == 1) hipLaunchKernelGGL(scatter_kernel, waves, wave, 0, stream, in, bound..., shift, s.chunks, s.hist, s.totals, out);
+    else hipLaunchKernelGGL(scatter_kernel, waves, wave, 0, stream, in, bound..., shift, s.chunks, s.hist, s.totals, out, total_out);
+}
+template <class Hist, class Scatter, class ScatterLast, class... Bound>
+static void ray_sort_pair_passes(const RaySortScratch<uint32_t *> &s, hipStream_t stream, Hist hist_kernel, Scatter scatter_kernel, ScatterLast last_kernel,
+                                 uint32_t *index, Bound... bound) {
+    ray_sort_pass(s, stream, hist_kernel, scatter_kernel, s.pairs_b, ORDER_KEY_BITS, s.pairs_c, nullptr, bound...);
+    ray_sort_pass(s, stream, hist_kernel, last_kernel, s.pairs_c, 2 * ORDER_KEY_BITS, index, nullptr, bound...);
 }
 
 hipError_t launch_ray_keys(const float4 *rays, uint32_t n, uint32_t *keys, hipStream_t stream) {
@@ -4198,34 +4266,21 @@ hipError_t launch_ray_keys(const float4 *rays, uint32_t n, uint32_t *keys, hipSt
 }
 hipError_t launch_ray_sort(const uint32_t *keys, uint32_t n, uint32_t *index, void *scratch, hipStream_t stream) {
     if (keys == nullptr || index == nullptr || scratch == nullptr || n == 0 || n > RAY_ORDER_MAX_RAYS) return hipErrorInvalidValue;
-    const uint32_t chunks = ray_sort_chunks(n);
-    uint32_t *pairs_b = static_cast<uint32_t *>(scratch), *pairs_c = pairs_b + 2 * (size_t)n, *hist = pairs_b + 4 * (size_t)n;
-    uint32_t *totals = hist + (size_t)RAY_SORT_DIGITS * chunks;
-    const dim3 waves(chunks), wave(64), digits(RAY_SORT_DIGITS), scan(RAY_SCAN_BLOCK);
-    hipLaunchKernelGGL(atmo_ray_sort_hist_kernel<false>, waves, wave, 0, stream, keys, n, 0, chunks, hist);
-    hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
-    hipLaunchKernelGGL((atmo_ray_sort_scatter_kernel<false, false>), waves, wave, 0, stream, keys, n, 0, chunks, hist, totals, pairs_b);
-    hipLaunchKernelGGL(atmo_ray_sort_hist_kernel<true>, waves, wave, 0, stream, pairs_b, n, ORDER_KEY_BITS, chunks, hist);
-    hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
-    hipLaunchKernelGGL((atmo_ray_sort_scatter_kernel<true, false>), waves, wave, 0, stream, pairs_b, n, ORDER_KEY_BITS, chunks, hist, totals, pairs_c);
-    hipLaunchKernelGGL(atmo_ray_sort_hist_kernel<true>, waves, wave, 0, stream, pairs_c, n, 2 * ORDER_KEY_BITS, chunks, hist);
-    hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
-    hipLaunchKernelGGL((atmo_ray_sort_scatter_kernel<true, true>), waves, wave, 0, stream, pairs_c, n, 2 * ORDER_KEY_BITS, chunks, hist, totals, index);
+    const RaySortScratch<uint32_t *> s = ray_sort_scratch(static_cast<uint32_t *>(scratch), n);
+    ray_sort_pass(s, stream, atmo_ray_sort_hist_kernel<false>, atmo_ray_sort_scatter_kernel<false, false>, keys, 0, s.pairs_b, nullptr, n);
+    ray_sort_pair_passes(s, stream, atmo_ray_sort_hist_kernel<true>, atmo_ray_sort_scatter_kernel<true, false>, atmo_ray_sort_scatter_kernel<true, true>, index, n);
     return hipGetLastError();
 }
 hipError_t launch_ray_order(const float4 *rays, uint32_t n, uint32_t *index, void *scratch, hipStream_t stream) {
     if (scratch == nullptr) return hipErrorInvalidValue;
-    uint32_t *keys = static_cast<uint32_t *>(scratch) + 2 * (size_t)n;   // the first n words of pairs C: read by pass 0, overwritten by pass 1
+    uint32_t *keys = ray_sort_scratch(static_cast<uint32_t *>(scratch), n).pairs_c;   // read by pass 0, overwritten by pass 1
     const hipError_t e = launch_ray_keys(rays, n, keys, stream);
     return e != hipSuccess ? e : launch_ray_sort(keys, n, index, scratch, stream);
 }
 
 // ---- ray lists: counted queues and the sure-miss cull (include/atmo_ray_list.h) --------------------------------------------------------------------------------
-// The order's passes once more, in COUNTED form: what bounds a kernel is a device word -- the caller's *count clamped to the capacity in front of the first
-// scatter, the live total m that scatter leaves in the scratch behind it -- so the host never learns a length and a captured graph serves every one.  The
-// grids are the capacity's; a wave whose chunk lies beyond the bound writes its zero histogram column and leaves.  Kernels of their own names, behind every
-// older kernel, which keep their code and their place in the code object (tools/isa_diff.py); the scan is the order's, over ray_sort_chunks(capacity) rows.
-// Scratch: the order's for `capacity` elements, then the word m (ray_list_scratch_bytes).
+// The sort's counted form (above) behind a key kernel that culls, and in front of a tail kernel that ends the list.  Kernels of their own names, behind
+// every older kernel, which keep their code and their place in the code object (tools/isa_diff.py).
 
 // THE CULL (include/atmo_ray_list.h, item by item).  Every operation fp32 and rounded on its own: no `fp contract` pragma in this function (the file is
 // compiled with -ffp-contract=off), as ray_key.  Why "true" implies that shade_pixel's RAYS mode stores zeros for the ray: its rs_atmo.x == rs_atmo.y branch
@@ -4242,12 +4297,6 @@ __device__ __forceinline__ bool ray_surely_misses(const RayCullConsts &k, float4
     const float g = (b * b) * (2.0f - dd);
     const float e = cc - k.r2;
     return cc >= k.r2_far && dd >= 0.25f && dd <= 1.75f && g < e * 0.998f;
-}
-constexpr uint32_t RAY_LIST_DEAD = 1u << 31;   // a culled ray's key: no pass lists it
-__device__ __forceinline__ uint32_t ray_list_bound(const uint32_t *bound, uint32_t capacity) {   // min(*bound, capacity); no word: the capacity
-    if (bound == nullptr) return capacity;
-    const uint32_t n = *bound;
-    return n < capacity ? n : capacity;
 }
 // one ray per lane, rays i < n only: keys[i] = THE KEY under RAY_LIST_ORDER, else 0; a ray RAY_LIST_CULL removes is marked dead and receives its zeros here
 __global__ __launch_bounds__(256) void atmo_ray_list_key_kernel(const float4 *__restrict__ rays, const uint32_t *__restrict__ count, uint32_t capacity,
@@ -4269,88 +4318,18 @@ __global__ __launch_bounds__(256) void atmo_ray_list_key_kernel(const float4 *__
     keys[i] = key;
 }
 
-// atmo_ray_sort_hist_kernel bounded by a device word.  DEAD: elements with RAY_LIST_DEAD set do not count (pass 0; the later passes never see one)
+// The sort's passes in their counted form: n is the device word clamped to the capacity, and the capacity bounds the store.  DEAD: pass 0
 template <bool PAIRS, bool DEAD>
 __global__ __launch_bounds__(64) void atmo_ray_list_hist_kernel(const uint32_t *__restrict__ in, const uint32_t *__restrict__ bound, uint32_t capacity,
                                                                 int shift, uint32_t chunks, uint32_t *__restrict__ hist) {
-    __shared__ uint32_t cnt[RAY_SORT_DIGITS];
-    const uint32_t lane = threadIdx.x, i0 = blockIdx.x * RAY_SORT_CHUNK;
-    const uint32_t n = ray_list_bound(bound, capacity);
-    if (i0 >= n) {   // (uniform: the wave is the workgroup)
-        hist[lane * chunks + blockIdx.x] = 0u;
-        return;
-    }
-    cnt[lane] = 0;
-    uint32_t key[RAY_SORT_STEPS];
-#pragma unroll
-    for (int t = 0; t < RAY_SORT_STEPS; ++t) {
-        const uint32_t j = i0 + (uint32_t)t * 64u + lane;
-        key[t] = j < n ? in[PAIRS ? 2u * j : j] : 0u;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < RAY_SORT_STEPS; ++t) {
-        const bool valid = i0 + (uint32_t)t * 64u + lane < n && !(DEAD && (key[t] & RAY_LIST_DEAD) != 0u);
-        const uint32_t d = (key[t] >> shift) & (uint32_t)(RAY_SORT_DIGITS - 1);
-        const unsigned long long m = match_class(d, valid);
-        if (valid && lanes_below(m) == 0) cnt[d] += (uint32_t)__builtin_popcountll(m);
-    }
-    __syncthreads();
-    hist[lane * chunks + blockIdx.x] = cnt[lane];
+    ray_sort_hist_pass<PAIRS, true, DEAD>(in, ray_list_bound(bound, capacity), shift, chunks, hist);
 }
-
-// atmo_ray_sort_scatter_kernel bounded by a device word; a store lands inside the capacity whatever the scratch held.  total_out (pass 0, else null): the
-// live total -- the sum of the 64 digit totals, which every wave forms -- leaves through the first wave's last lane, a plain vector store
 template <bool PAIRS, bool LAST, bool DEAD>
 __global__ __launch_bounds__(64) void atmo_ray_list_scatter_kernel(const uint32_t *__restrict__ in, const uint32_t *__restrict__ bound, uint32_t capacity,
                                                                    int shift, uint32_t chunks, const uint32_t *__restrict__ base,
                                                                    const uint32_t *__restrict__ totals, uint32_t *__restrict__ out,
                                                                    uint32_t *__restrict__ total_out) {
-    __shared__ uint32_t off[RAY_SORT_DIGITS];
-    const uint32_t lane = threadIdx.x, i0 = blockIdx.x * RAY_SORT_CHUNK;
-    const uint32_t n = ray_list_bound(bound, capacity);
-    {
-        const uint32_t total = totals[lane];
-        uint32_t incl = total;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t x = __shfl_up(incl, d);
-            if (lane >= (uint32_t)d) incl += x;
-        }
-        if (total_out != nullptr && blockIdx.x == 0 && lane == 63u) *total_out = incl;
-        if (i0 >= n) return;   // (uniform)
-        off[lane] = (incl - total) + base[lane * chunks + blockIdx.x];
-    }
-    uint32_t key[RAY_SORT_STEPS], idx[RAY_SORT_STEPS];
-#pragma unroll
-    for (int t = 0; t < RAY_SORT_STEPS; ++t) {
-        const uint32_t j = i0 + (uint32_t)t * 64u + lane;
-        if constexpr (PAIRS) {
-            const uint2 p = j < n ? reinterpret_cast<const uint2 *>(in)[j] : make_uint2(0u, 0u);
-            key[t] = p.x;
-            idx[t] = p.y;
-        } else {
-            key[t] = j < n ? in[j] : 0u;
-            idx[t] = j;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < RAY_SORT_STEPS; ++t) {
-        const bool valid = i0 + (uint32_t)t * 64u + lane < n && !(DEAD && (key[t] & RAY_LIST_DEAD) != 0u);
-        const uint32_t d = (key[t] >> shift) & (uint32_t)(RAY_SORT_DIGITS - 1);
-        const unsigned long long m = match_class(d, valid);
-        const int r = lanes_below(m);
-        uint32_t pos = 0;
-        if (valid) pos = off[d] + (uint32_t)r;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (valid && r == 0) off[d] += (uint32_t)__builtin_popcountll(m);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (valid && pos < capacity) {
-            if constexpr (LAST) out[pos] = idx[t];
-            else reinterpret_cast<uint2 *>(out)[pos] = make_uint2(key[t], idx[t]);
-        }
-    }
+    ray_sort_scatter_pass<PAIRS, LAST, true, DEAD>(in, ray_list_bound(bound, capacity), capacity, shift, chunks, base, totals, out, total_out);
 }
 
 // index[m .. capacity) = RAY_LIST_END and *listed = m (where there is a word), m the live total
@@ -4362,34 +4341,23 @@ __global__ __launch_bounds__(256) void atmo_ray_list_tail_kernel(const uint32_t 
     if (i >= m && i < capacity) index[i] = RAY_LIST_END;
 }
 
-size_t ray_list_scratch_bytes(uint32_t capacity) { return ray_order_scratch_bytes(capacity) + 4 * sizeof(uint32_t); }
 hipError_t launch_ray_list(const float4 *rays, const uint32_t *count, uint32_t capacity, int flags, const RayCullConsts &cull, float4 *rgba, uint32_t *index,
                            uint32_t *listed, void *scratch, hipStream_t stream) {
     if (rays == nullptr || index == nullptr || scratch == nullptr || capacity == 0 || capacity > RAY_ORDER_MAX_RAYS ||
         (flags & ~(RAY_LIST_ORDER | RAY_LIST_CULL)) != 0 || ((flags & RAY_LIST_CULL) != 0 && rgba == nullptr))
         return hipErrorInvalidValue;
-    const uint32_t chunks = ray_sort_chunks(capacity);
-    uint32_t *pairs_b = static_cast<uint32_t *>(scratch), *pairs_c = pairs_b + 2 * (size_t)capacity, *hist = pairs_b + 4 * (size_t)capacity;
-    uint32_t *totals = hist + (size_t)RAY_SORT_DIGITS * chunks, *live = totals + RAY_SORT_DIGITS;
-    uint32_t *keys = pairs_c;   // the first `capacity` words of pairs C: read by pass 0, overwritten by pass 1
-    const dim3 rays_grid((capacity + 255u) / 256u), block(256), waves(chunks), wave(64), digits(RAY_SORT_DIGITS), scan(RAY_SCAN_BLOCK);
+    const RaySortScratch<uint32_t *> s = ray_sort_scratch(static_cast<uint32_t *>(scratch), capacity);
+    uint32_t *keys = s.pairs_c;   // read by pass 0, overwritten by pass 1
+    const dim3 rays_grid((capacity + 255u) / 256u), block(256);
     hipLaunchKernelGGL(atmo_ray_list_key_kernel, rays_grid, block, 0, stream, rays, count, capacity, flags, cull, keys, rgba);
-    hipLaunchKernelGGL((atmo_ray_list_hist_kernel<false, true>), waves, wave, 0, stream, keys, count, capacity, 0, chunks, hist);
-    hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
     if (flags & RAY_LIST_ORDER) {
-        hipLaunchKernelGGL((atmo_ray_list_scatter_kernel<false, false, true>), waves, wave, 0, stream, keys, count, capacity, 0, chunks, hist, totals, pairs_b, live);
-        hipLaunchKernelGGL((atmo_ray_list_hist_kernel<true, false>), waves, wave, 0, stream, pairs_b, live, capacity, ORDER_KEY_BITS, chunks, hist);
-        hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
-        hipLaunchKernelGGL((atmo_ray_list_scatter_kernel<true, false, false>), waves, wave, 0, stream, pairs_b, live, capacity, ORDER_KEY_BITS, chunks, hist, totals,
-                           pairs_c, (uint32_t *)nullptr);
-        hipLaunchKernelGGL((atmo_ray_list_hist_kernel<true, false>), waves, wave, 0, stream, pairs_c, live, capacity, 2 * ORDER_KEY_BITS, chunks, hist);
-        hipLaunchKernelGGL(atmo_ray_sort_scan_kernel, digits, scan, 0, stream, hist, chunks, totals);
-        hipLaunchKernelGGL((atmo_ray_list_scatter_kernel<true, true, false>), waves, wave, 0, stream, pairs_c, live, capacity, 2 * ORDER_KEY_BITS, chunks, hist, totals,
-                           index, (uint32_t *)nullptr);
+        ray_sort_pass(s, stream, atmo_ray_list_hist_kernel<false, true>, atmo_ray_list_scatter_kernel<false, false, true>, keys, 0, s.pairs_b, s.live, count, capacity);
+        ray_sort_pair_passes(s, stream, atmo_ray_list_hist_kernel<true, false>, atmo_ray_list_scatter_kernel<true, false, false>,
+                             atmo_ray_list_scatter_kernel<true, true, false>, index, s.live, capacity);
     } else {   // queue order: one stable compaction pass, every live key's digit 0
-        hipLaunchKernelGGL((atmo_ray_list_scatter_kernel<false, true, true>), waves, wave, 0, stream, keys, count, capacity, 0, chunks, hist, totals, index, live);
+        ray_sort_pass(s, stream, atmo_ray_list_hist_kernel<false, true>, atmo_ray_list_scatter_kernel<false, true, true>, keys, 0, index, s.live, count, capacity);
     }
-    hipLaunchKernelGGL(atmo_ray_list_tail_kernel, rays_grid, block, 0, stream, live, capacity, index, listed);
+    hipLaunchKernelGGL(atmo_ray_list_tail_kernel, rays_grid, block, 0, stream, s.live, capacity, index, listed);
     return hipGetLastError();
 }
 

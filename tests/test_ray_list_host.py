@@ -142,6 +142,17 @@ def test_scratch_bytes_are_monotone():
     assert lib.atmo_ray_list_scratch_bytes(5, None) == N.ATMO_E_ARG
 
 
+def test_scratch_bytes_are_the_layout_s():
+    """Two buffers of n pairs (16 n bytes), 64 histogram words per chunk of 1024 elements and 64 totals (256 bytes each); the list's live word in 16 bytes
+    of its own behind them."""
+    N, lib = _lib()
+    b, o = C.c_size_t(), C.c_size_t()
+    for n, want in ((0, 256), (1, 528), (1024, 16_896), (1025, 17_168), (2 ** 28, 4_362_076_416)):
+        assert want == 16 * n + 256 * (-(-n // 1024) + 1)
+        assert lib.atmo_ray_order_scratch_bytes(n, C.byref(o)) == N.ATMO_OK and lib.atmo_ray_list_scratch_bytes(n, C.byref(b)) == N.ATMO_OK
+        assert (o.value, b.value) == (want, want + 16), (n, o.value, b.value)
+
+
 def test_atmo_ray_list_refuses_in_the_header_s_order():
     """The capacity, the flags, null pointers, CULL's two, 16-byte alignment, 4-byte alignment, the scratch size -- each under the entry point's name -- and
     ATMO_E_NO_DEVICE behind all of them."""
