@@ -5,6 +5,7 @@ Zylann/godot_atmosphere_shader, behind the reference's `PlanetAtmosphere` / `sha
   planet_atmosphere.py  host-side mirror of addons/zylann.atmosphere/planet_atmosphere.gd
   depth_formats.py      the depth sources' contract in numpy (include/atmo_depth.h; `depth_source` wraps a renderer's own depth buffer)
   noise_cubemap.py      host-side mirror of addons/zylann.atmosphere/noise_cubemap.gd (generation on the GPU)
+  lens.py               lens rays in numpy: panorama, fisheye, octahedral map, cube face (include/atmo_lens.h; `Lens` describes one for `render_lens`)
   noise_volume.py       host-side mirror of the demo's NoiseTexture3D: the cloud shape volume, generated on the GPU (include/atmo_noise_volume.h)
   demo.py               the reference's demo scene + named shader configurations (tests, bench.py, smoke())
   scene.py              synthetic inputs (camera, depth, jitter, cloud textures) for tests and bench
@@ -16,6 +17,7 @@ from .planet_atmosphere import (  # noqa: F401
 
 from .noise_cubemap import NoiseCubemap, SeededValueNoise  # noqa: F401,E402
 from .noise_volume import NoiseVolume  # noqa: F401,E402
+from .lens import Lens  # noqa: F401,E402
 
 __all__ = ["NoiseCubemap", "NoiseVolume", "SeededValueNoise", "PlanetAtmosphere", "Shader", "SHADERS", "DefaultShader", "Transform2D", "load_shader",
-           "atmosphere_vertex", "make_frame", "depth_source", "DepthSource"]
+           "atmosphere_vertex", "make_frame", "depth_source", "DepthSource", "Lens"]

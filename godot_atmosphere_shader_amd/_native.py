@@ -94,6 +94,12 @@ RAY_DETAIL_SYMBOLS = ("atmo_shade_rays_detail", "atmo_shade_ray_quads_detail")
 # RAYS_SYMBOLS rule: the ABI version stays 5, the tuple stands beside EXPORTED_SYMBOLS, load() binds it where the library has it (PlanetAtmosphere's
 # target draws raise without, on a cloud node with cloud_detail on).
 DETAIL_TARGET_SYMBOLS = ("atmo_render_detail_target", "atmo_render_views_detail_target")
+# every symbol include/atmo_lens.h declares: the rays of a lens image formed on the device (panorama, fisheye, octahedral map, cube face; lens.py), row-major
+# with the 16 x 4 tile index or in quad order.  The RAYS_SYMBOLS rule: the ABI version stays 5, the tuple stands beside EXPORTED_SYMBOLS, load() binds it
+# where the library has it (PlanetAtmosphere.lens_rays and render_lens raise without).
+LENS_SYMBOLS = ("atmo_lens_ray_counts", "atmo_lens_rays")
+LENS_EQUIRECT, LENS_FISHEYE, LENS_OCTAHEDRAL, LENS_CUBE_FACE = range(4)   # AtmoLensKind
+LENS_QUADS = 1                                                            # ATMO_LENS_QUADS
 EXPORTED_SYMBOLS = CORE_SYMBOLS + DEBUG_SYMBOLS + SCENE_SYMBOLS + TARGET_SYMBOLS + VIEWS_SYMBOLS + VIEWS_PROXY_SYMBOLS + VIEWS_TARGET_SYMBOLS
 TARGET_RGBA32F, TARGET_RGBA16F, TARGET_RGBA8_UNORM = range(3)
 TARGET_RGBA8_SRGB, TARGET_BGRA8_UNORM, TARGET_BGRA8_SRGB, TARGET_A2B10G10R10_UNORM = range(16, 20)   # 3 .. 15 and 20 up: unknown formats
@@ -161,6 +167,21 @@ class AtmoRay(C.Structure):   # include/atmo_rays.h: 32 bytes, what one row of a
         ("tmax", C.c_float),
         ("dir", C.c_float * 3),
         ("reserved", C.c_float),
+    ]
+
+
+class AtmoLens(C.Structure):   # include/atmo_lens.h: 20 words
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("y0", C.c_int32),
+        ("y1", C.c_int32),
+        ("face", C.c_int32),
+        ("fov", C.c_float),
+        ("tmax", C.c_float),
+        ("origin", C.c_float * 3),
+        ("basis", C.c_float * 9),
     ]
 
 
@@ -252,6 +273,10 @@ def optional_headers() -> dict:
         "atmo_detail_target.h": (DETAIL_TARGET_SYMBOLS, ": no cloud detail into targets", {
             "atmo_render_detail_target": (ip, [vp, frame, C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), ip, vp]),
             "atmo_render_views_detail_target": (ip, [vp, C.POINTER(AtmoViewDepthTarget), ip, ip, vp]),
+        }),
+        "atmo_lens.h": (LENS_SYMBOLS, ": no lens rays", {
+            "atmo_lens_ray_counts": (ip, [C.POINTER(AtmoLens), u32, C.POINTER(u32), C.POINTER(u32)]),
+            "atmo_lens_rays": (ip, [vp, C.POINTER(AtmoLens), u32, vp, u32, vp, vp, vp]),
         }),
     }
 

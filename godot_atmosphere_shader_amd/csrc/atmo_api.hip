@@ -23,6 +23,7 @@
 #include "../../include/atmo_ray_list.h"
 #include "../../include/atmo_ray_detail.h"
 #include "../../include/atmo_detail_target.h"
+#include "../../include/atmo_lens.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -2550,6 +2551,84 @@ int atmo_debug_frame_rays(AtmoContext *ctx, const AtmoFrame *frame, const float 
     fill_consts(ctx, draw_frame(ctx, frame, fixed), depth_dev, nullptr, rc);
     const atmo::FrameRaysConsts fc = {depth_dev, reinterpret_cast<float4 *>(rays_dev)};
     HIP_TRY(ctx, atmo::launch_frame_rays(rc, fc, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+// ---- lens rays: panorama, fisheye, octahedral map, cube face (include/atmo_lens.h) -----------------------------------------------------------------------
+static_assert(ATMO_LENS_EQUIRECT == atmo::LENS_EQUIRECT && ATMO_LENS_FISHEYE == atmo::LENS_FISHEYE && ATMO_LENS_OCTAHEDRAL == atmo::LENS_OCTAHEDRAL &&
+                  ATMO_LENS_CUBE_FACE == atmo::LENS_CUBE_FACE, "the header's lens kinds are the kernels'");
+static_assert(sizeof(AtmoLens) == 20 * 4, "AtmoLens is 20 words: 6 + 2 + 3 + 9");
+// What a lens and its flags give, once the checks that concern them alone have passed: the band's lengths
+struct LensCounts {
+    bool empty;
+    uint32_t qpr, tpr;
+    uint64_t n_rays, n_index;   // n_index may exceed 32 bits for a one-pixel-wide image of more than 2^28 - 4 rows
+};
+// The header's checks on the lens and the flags, in its order; the pointers' stand behind them in atmo_lens_rays
+static int lens_checks(AtmoContext *ctx, const std::string &who, const AtmoLens *lens, uint32_t flags, LensCounts &out) {
+    out = LensCounts{};
+    if (!lens) return fail(ctx, ATMO_E_ARG, who + ": null lens");
+    if (lens->y0 == lens->y1) {   // an empty band: nothing else is looked at
+        out.empty = true;
+        return ATMO_OK;
+    }
+    if (lens->kind < ATMO_LENS_EQUIRECT || lens->kind > ATMO_LENS_CUBE_FACE) return fail(ctx, ATMO_E_ARG, who + ": unknown lens kind " + std::to_string(lens->kind));
+    if (flags & ~ATMO_LENS_QUADS) return fail(ctx, ATMO_E_ARG, who + ": unknown flag bits");
+    if (lens->width < 1 || lens->height < 1) return fail(ctx, ATMO_E_ARG, who + ": width and height must be at least 1");
+    if ((int64_t)lens->width * lens->height > ((int64_t)1 << 28)) return fail(ctx, ATMO_E_ARG, who + ": width * height must not exceed 2^28");
+    if (lens->y0 < 0 || lens->y1 > lens->height || lens->y1 < lens->y0) return fail(ctx, ATMO_E_ARG, who + ": the band [y0, y1) must lie inside [0, height]");
+    if (lens->kind == ATMO_LENS_FISHEYE && !(lens->fov > 0.0f && lens->fov <= 6.2831855f))
+        return fail(ctx, ATMO_E_ARG, who + ": a fisheye's fov must lie in (0, 6.2831855] radians");
+    if (lens->kind == ATMO_LENS_CUBE_FACE && lens->width != lens->height) return fail(ctx, ATMO_E_ARG, who + ": a cube face is square: width == height");
+    if (lens->kind == ATMO_LENS_CUBE_FACE && (lens->face < 0 || lens->face > 5)) return fail(ctx, ATMO_E_ARG, who + ": face must be 0 .. 5");
+    const bool quads = (flags & ATMO_LENS_QUADS) != 0;
+    if (quads && ((lens->y0 & 1) != 0 || ((lens->y1 & 1) != 0 && lens->y1 != lens->height)))
+        return fail(ctx, ATMO_E_ARG, who + ": ATMO_LENS_QUADS needs an even y0, and an even y1 or y1 == height");
+    const uint64_t w = (uint64_t)lens->width, rows = (uint64_t)(lens->y1 - lens->y0);
+    out.qpr = (uint32_t)((w + 1) / 2);
+    out.tpr = (uint32_t)((w + 15) / 16);
+    out.n_rays = quads ? 4 * (uint64_t)out.qpr * ((rows + 1) / 2) : w * rows;
+    out.n_index = 64 * (uint64_t)out.tpr * ((rows + 3) / 4);
+    return ATMO_OK;
+}
+
+int atmo_lens_ray_counts(const AtmoLens *lens, uint32_t flags, uint32_t *n_rays, uint32_t *n_index) {
+    LensCounts k;
+    ATMO_TRY(lens_checks(nullptr, "atmo_lens_ray_counts", lens, flags, k));
+    if (n_rays) *n_rays = (uint32_t)k.n_rays;   // at most 2^28 + 2^15 or so: 4 (W + 1) / 2 (rows + 1) / 2
+    if (n_index) *n_index = k.n_index > 0xffffffffu ? 0xffffffffu : (uint32_t)k.n_index;   // saturated: atmo_lens_rays refuses an index that long
+    return ATMO_OK;
+}
+
+// Every check stands in front of hipSetDevice, in the header's order.  The call enqueues and nothing else
+int atmo_lens_rays(AtmoContext *ctx, const AtmoLens *lens, uint32_t flags, const float *distance_dev, uint32_t distance_pitch, AtmoRay *rays_dev,
+                   uint32_t *index_dev, void *stream) {
+    const std::string who = "atmo_lens_rays";
+    if (!ctx) return ATMO_E_ARG;
+    LensCounts k;
+    ATMO_TRY(lens_checks(ctx, who, lens, flags, k));
+    if (k.empty) return ATMO_OK;
+    const bool quads = (flags & ATMO_LENS_QUADS) != 0;
+    ATMO_TRY(refuse_null(ctx, who, {{rays_dev, "rays_dev", 16}}));
+    ATMO_TRY(refuse_misaligned(ctx, who, {{rays_dev, "rays_dev", 16}, {index_dev, "index_dev", 4}}));
+    if (quads && index_dev) return fail(ctx, ATMO_E_ARG, who + ": the tile index is row-major only: no index_dev with ATMO_LENS_QUADS");
+    if (index_dev && k.n_index > 0xffffffffu) return fail(ctx, ATMO_E_ARG, who + ": the tile index of this band would have more than 2^32 - 1 entries");
+    if (distance_dev && distance_pitch < (uint32_t)lens->width) return fail(ctx, ATMO_E_ARG, who + ": distance_pitch is below width");
+    if (!distance_dev && distance_pitch != 0) return fail(ctx, ATMO_E_ARG, who + ": distance_pitch without a distance buffer");
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    atmo::LensConsts lc{};
+    lc.rays = reinterpret_cast<float4 *>(rays_dev);
+    lc.index = index_dev;
+    lc.distance = distance_dev;
+    lc.pitch = distance_pitch;
+    lc.w = lens->width; lc.h = lens->height; lc.y0 = lens->y0; lc.y1 = lens->y1; lc.face = lens->face;
+    lc.qpr = k.qpr; lc.tpr = k.tpr;
+    lc.n = index_dev ? k.n_index : k.n_rays;
+    lc.fov = lens->fov; lc.tmax = lens->tmax;
+    std::memcpy(lc.origin, lens->origin, sizeof(lc.origin));
+    std::memcpy(lc.basis, lens->basis, sizeof(lc.basis));
+    HIP_TRY(ctx, atmo::launch_lens_rays(lens->kind, quads, lc, (hipStream_t)stream));
     return ATMO_OK;
 }
 

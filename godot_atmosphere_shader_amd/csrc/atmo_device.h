@@ -368,6 +368,22 @@ hipError_t launch_ray_list(const float4 *rays, const uint32_t *count, uint32_t c
                            uint32_t *listed, void *scratch, hipStream_t stream);
 // the camera rays of the rect in rc, as the float kernels' prologue forms them (atmo_debug_frame_rays)
 hipError_t launch_frame_rays(const RenderConsts &rc, const FrameRaysConsts &fc, hipStream_t stream);
+// the rays of a lens image (atmo_lens_rays; include/atmo_lens.h states the arithmetic): atmo_lens_rays_kernel<KIND, QUADS>, one lane per ray, and with
+// lc.index the 16 x 4 tile index in the same launch.  lc.n = the launch's threads: 4 per quad of the band (quads), the index's entries (lc.index), else the
+// band's rays; at most 2^32.  The band is not empty.  Kernels on `stream` only
+constexpr int LENS_EQUIRECT = 0, LENS_FISHEYE = 1, LENS_OCTAHEDRAL = 2, LENS_CUBE_FACE = 3;   // == AtmoLensKind
+struct LensConsts {
+    float4 *rays;            // the band's AtmoRay array, 16-byte aligned
+    uint32_t *index;         // null, or the tile index (row-major only)
+    const float *distance;   // null, or h rows of `pitch` floats: every ray's tmax
+    uint32_t pitch;
+    int w, h, y0, y1, face;  // the image, the band [y0, y1) and CUBE_FACE's face
+    uint32_t qpr, tpr;       // quads per row, (w + 1) / 2; tiles per row, (w + 15) / 16
+    uint64_t n;              // threads of the launch
+    float fov, tmax;
+    float origin[3], basis[9];
+};
+hipError_t launch_lens_rays(int kind, bool quads, const LensConsts &lc, hipStream_t stream);
 // load_depth's decode over n texels of a caller's array: out[i] = decode(texels[i]) (atmo_debug_decode_depth)
 hipError_t launch_decode_depth(int format, const void *texels, float *out, size_t n, hipStream_t stream);
 // store_target<format> over n pixels: dst[i] = encode(src[i]), or encode(blend(src[i], decode(dst[i]))) when composite (atmo_debug_store_target)

@@ -4455,4 +4455,163 @@ hipError_t launch_render_views_detail_target(int flags, const RenderConsts *tabl
     });
 }
 
+// ---- lens rays (include/atmo_lens.h states the arithmetic operation by operation) -------------------------------------------------------------------------
+// The generator of a lens image's AtmoRay array: one family, atmo_lens_rays_kernel<KIND, QUADS>, one lane per ray.  Three lane maps:
+//   QUADS                   thread i is slot 4 q + j of the band's quad q (atmo_ray_quads.h LAYOUT): four consecutive lanes write one quad's 128 contiguous bytes
+//   row-major               thread i is ray i = (y - y0) W + x: a wave writes 2 KiB in one piece
+//   row-major + tile index  thread k is ENTRY k of the index, lane k % 64 of the 16 x 4 tile k / 64: it writes its pixel's ray where the row-major order has
+//                           it (16 consecutive lanes 512 contiguous bytes) and entry k itself -- the same launch, every entry once, the END marks of the
+//                           ragged tiles and of the absent pixels included
+// Each lane writes its whole ray as two 16-byte stores; an absent ray (a quad slot outside the image, a fisheye pixel outside the circle) is eight +0 floats.
+// There is nothing else: no atomics, nothing handed from one workgroup to another.  The fp32 sequences (OCTAHEDRAL, CUBE_FACE, BASIS) carry no `fp contract`
+// pragma, as the ray key's: the file is compiled with -ffp-contract=off, every product and sum is rounded on its own, roots and quotients are the IEEE ones.
+// The two trigonometric lenses are evaluated in fp64 and rounded once.  Their arguments never leave [-pi, pi] (theta of a fisheye: [0, 3.1415928]), so
+// the sine and cosine are lens_sincos below and not the math library's, whose large-argument reduction would bring a private-memory stack: a reduction by
+// at most two quarter turns, pi / 2 in two doubles whose products with k = 0, +-1, +-2 are exact, and the Taylor polynomials on [-pi/4, pi/4] (the first
+// neglected term is below 2e-25 of the leading one).  A few double ulps from the correctly rounded value, which can only move a component across one fp32
+// rounding boundary (the header's 1-ulp rule).  Kernels of their own name, defined and instantiated here, behind every older kernel, which keep their code
+// and their place in the code object (tools/isa_diff.py).
+__device__ __forceinline__ void lens_sincos(double x, double &s, double &c) {
+    const double k = rint(x * 0.63661977236758138);   // 2 / pi; |k| <= 2
+    double r = fma(-k, 1.5707963267948966, x);        // exact: k pi/2_hi is exact, and the difference of neighbours is
+    r = fma(-k, 6.123233995736766e-17, r);
+    const double r2 = r * r;
+    double ps = 1.0 / 51090942171709440000.0;         // 1 / 21!
+    ps = fma(ps, r2, -1.0 / 121645100408832000.0);    // 19!
+    ps = fma(ps, r2, 1.0 / 355687428096000.0);        // 17!
+    ps = fma(ps, r2, -1.0 / 1307674368000.0);         // 15!
+    ps = fma(ps, r2, 1.0 / 6227020800.0);             // 13!
+    ps = fma(ps, r2, -1.0 / 39916800.0);              // 11!
+    ps = fma(ps, r2, 1.0 / 362880.0);                 // 9!
+    ps = fma(ps, r2, -1.0 / 5040.0);                  // 7!
+    ps = fma(ps, r2, 1.0 / 120.0);                    // 5!
+    ps = fma(ps, r2, -1.0 / 6.0);                     // 3!
+    const double sr = fma(r * r2, ps, r);
+    double pc = 1.0 / 2432902008176640000.0;          // 1 / 20!
+    pc = fma(pc, r2, -1.0 / 6402373705728000.0);      // 18!
+    pc = fma(pc, r2, 1.0 / 20922789888000.0);         // 16!
+    pc = fma(pc, r2, -1.0 / 87178291200.0);           // 14!
+    pc = fma(pc, r2, 1.0 / 479001600.0);              // 12!
+    pc = fma(pc, r2, -1.0 / 3628800.0);               // 10!
+    pc = fma(pc, r2, 1.0 / 40320.0);                  // 8!
+    pc = fma(pc, r2, -1.0 / 720.0);                   // 6!
+    pc = fma(pc, r2, 1.0 / 24.0);                     // 4!
+    pc = fma(pc, r2, -0.5);                           // 2!
+    const double cr = fma(r2, pc, 1.0);
+    const int q = (int)k & 3;                         // quarter turns: (s, c) = (sr, cr), (cr, -sr), (-sr, -cr), (-cr, sr)
+    const double sa = (q & 1) ? cr : sr, ca = (q & 1) ? sr : cr;
+    s = (q & 2) ? -sa : sa;
+    c = ((q + 1) & 2) ? -ca : ca;
+}
+// the lens-space direction of pixel (x, y); false: the pixel is absent (FISHEYE outside the image circle)
+template <int KIND>
+__device__ __forceinline__ bool lens_direction(const LensConsts &lc, int x, int y, float &dx, float &dy, float &dz) {
+    if constexpr (KIND == LENS_OCTAHEDRAL) {
+        const float u = ieee_div((float)(2 * x + 1), (float)lc.w) - 1.0f, v = ieee_div((float)(2 * y + 1), (float)lc.h) - 1.0f;
+        const float z = (1.0f - fabsf(u)) - fabsf(v);
+        float a = u, b = v;
+        if (z < 0.0f) {   // the lower hemisphere unfolds; both from the folded u and v
+            a = copysignf(1.0f - fabsf(v), u);
+            b = copysignf(1.0f - fabsf(u), v);
+        }
+        const float n = ieee_sqrt((a * a + b * b) + z * z);
+        dx = ieee_div(a, n); dy = ieee_div(b, n); dz = ieee_div(z, n);
+        return true;
+    } else if constexpr (KIND == LENS_CUBE_FACE) {   // the coverage cubemap's texel-to-direction table (atmo_noise_cubemap_kernel's), in its operation order
+        const float half = 0.5f * (float)lc.w;
+        const float p2x = ieee_div((float)x + 0.5f, half) - 1.0f, p2y = ieee_div((float)(lc.w - y - 1) + 0.5f, half) - 1.0f;
+        float vx = 1.0f, vy = p2y, vz = -p2x;
+        const float len = ieee_sqrt((vx * vx + vy * vy) + vz * vz);
+        vx = ieee_div(vx, len); vy = ieee_div(vy, len); vz = ieee_div(vz, len);
+        switch (lc.face) {   // wave-uniform
+        case 0: dx = vx; dy = vy; dz = vz; break;
+        case 1: dx = -vx; dy = vy; dz = -vz; break;
+        case 2: dx = -vz; dy = vx; dz = -vy; break;
+        case 3: dx = -vz; dy = -vx; dz = vy; break;
+        case 4: dx = -vz; dy = vy; dz = vx; break;
+        default: dx = vz; dy = vy; dz = -vx; break;
+        }
+        return true;
+    } else if constexpr (KIND == LENS_EQUIRECT) {
+        const double phi = (((double)x + 0.5) / (double)lc.w - 0.5) * 6.283185307179586;
+        const double theta = (0.5 - ((double)y + 0.5) / (double)lc.h) * 3.141592653589793;
+        double sp, cp, st, ct;
+        lens_sincos(phi, sp, cp);
+        lens_sincos(theta, st, ct);
+        dx = (float)(ct * sp); dy = (float)st; dz = (float)(-(ct * cp));
+        return true;
+    } else {
+        static_assert(KIND == LENS_FISHEYE, "four lenses");
+        // r > 1 decided exactly, in integers: (2 x + 1 - W)^2 + (H - 2 y - 1)^2 > min(W, H)^2 (each below 2^58)
+        const long long ax = 2ll * x + 1 - lc.w, ay = (long long)lc.h - 2ll * y - 1, m = lc.w < lc.h ? lc.w : lc.h;
+        if (ax * ax + ay * ay > m * m) return false;
+        const double px = ((double)x + 0.5) - (double)lc.w / 2.0, py = (double)lc.h / 2.0 - ((double)y + 0.5);
+        const double rho = sqrt(px * px + py * py);
+        if (rho == 0.0) {
+            dx = 0.0f; dy = 0.0f; dz = -1.0f;
+            return true;
+        }
+        const double theta = (rho / ((double)m / 2.0)) * ((double)lc.fov / 2.0);
+        double st, ct;
+        lens_sincos(theta, st, ct);
+        dx = (float)(st * (px / rho)); dy = (float)(st * (py / rho)); dz = (float)(-ct);
+        return true;
+    }
+}
+template <int KIND, int QUADS>
+__global__ __launch_bounds__(RAYS_BLOCK) void atmo_lens_rays_kernel(const LensConsts lc) {
+    const uint64_t i = (uint64_t)blockIdx.x * RAYS_BLOCK + threadIdx.x;
+    if (i >= lc.n) return;
+    int x, y;
+    uint64_t slot = i;
+    if constexpr (QUADS != 0) {
+        const uint64_t q = i >> 2;
+        x = 2 * (int)(q % lc.qpr) + (int)(i & 1u);
+        y = lc.y0 + 2 * (int)(q / lc.qpr) + (int)((i >> 1) & 1u);
+    } else if (lc.index != nullptr) {   // wave-uniform: the tile map
+        const uint64_t t = i >> 6;
+        x = 16 * (int)(t % lc.tpr) + (int)(i & 15u);
+        y = lc.y0 + 4 * (int)(t / lc.tpr) + (int)((i >> 4) & 3u);
+        slot = (uint64_t)(y - lc.y0) * (uint64_t)lc.w + (uint64_t)x;
+    } else {
+        x = (int)(i % (uint64_t)lc.w);
+        y = lc.y0 + (int)(i / (uint64_t)lc.w);
+    }
+    const bool inside = x < lc.w && y < lc.y1;   // a quad slot or a tile lane beyond the image or the band
+    float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+    const bool present = inside && lens_direction<KIND>(lc, x, y, dx, dy, dz);
+    if (QUADS == 0 && lc.index != nullptr) lc.index[i] = present ? (uint32_t)slot : RAY_LIST_END;
+    if (!inside && QUADS == 0) return;           // a tile lane has no ray; a quad slot has one, absent
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+    if (present) {
+        const float *B = lc.basis;
+        b.x = (B[0] * dx + B[3] * dy) + B[6] * dz;
+        b.y = (B[1] * dx + B[4] * dy) + B[7] * dz;
+        b.z = (B[2] * dx + B[5] * dy) + B[8] * dz;
+        a = make_float4(lc.origin[0], lc.origin[1], lc.origin[2], lc.distance ? lc.distance[(size_t)y * lc.pitch + (size_t)x] : lc.tmax);
+    }
+    lc.rays[2 * slot] = a;
+    lc.rays[2 * slot + 1] = b;
+}
+template <int KIND>
+static hipError_t launch_lens_kind(const LensConsts &lc, bool quads, hipStream_t stream) {
+    const unsigned blocks = (unsigned)((lc.n + (RAYS_BLOCK - 1)) / RAYS_BLOCK);
+    if (quads) hipLaunchKernelGGL((atmo_lens_rays_kernel<KIND, 1>), dim3(blocks), dim3(RAYS_BLOCK), 0, stream, lc);
+    else hipLaunchKernelGGL((atmo_lens_rays_kernel<KIND, 0>), dim3(blocks), dim3(RAYS_BLOCK), 0, stream, lc);
+    return hipGetLastError();
+}
+// lc.n = the threads of the launch: 4 quads (QUADS), the index's entries (row-major with lc.index), else the rays
+hipError_t launch_lens_rays(int kind, bool quads, const LensConsts &lc, hipStream_t stream) {
+    if (lc.rays == nullptr || lc.n == 0 || lc.n > ((uint64_t)1 << 32) || lc.w < 1 || lc.h < 1 || lc.y0 < 0 || lc.y1 > lc.h || lc.y0 >= lc.y1 ||
+        (quads && (lc.index != nullptr || lc.qpr == 0)) || (lc.index != nullptr && lc.tpr == 0) || (lc.distance != nullptr && lc.pitch < (uint32_t)lc.w))
+        return hipErrorInvalidValue;
+    switch (kind) {
+    case LENS_EQUIRECT: return launch_lens_kind<LENS_EQUIRECT>(lc, quads, stream);
+    case LENS_FISHEYE: return launch_lens_kind<LENS_FISHEYE>(lc, quads, stream);
+    case LENS_OCTAHEDRAL: return launch_lens_kind<LENS_OCTAHEDRAL>(lc, quads, stream);
+    case LENS_CUBE_FACE: return launch_lens_kind<LENS_CUBE_FACE>(lc, quads, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace atmo

@@ -866,6 +866,89 @@ class PlanetAtmosphere:
         with torch.cuda.stream(torch.cuda.ExternalStream(_stream_handle(stream, depth), device=depth.device)):   # the gather behind the dump, on its stream
             return gather()
 
+    # ---- lens rays: panorama, fisheye, octahedral map, cube face (include/atmo_lens.h) ---------------------------------------------
+    def lens_rays(self, lens, distance=None, quads: bool = False, tile_index: bool = False, stream=None):
+        """The rays of a lens image, formed on the device (atmo_lens_rays; include/atmo_lens.h states the arithmetic, lens.lens_rays is the same statement
+        in numpy): a CUDA float32 (n, 8) tensor for `shade_rays(width=lens.width, first=y0 * lens.width)` -- the rows `lens.rows` of the image, row-major
+        -- or, with `quads`, in quad order for `shade_ray_quads(width=lens.width, first_quad=(y0 // 2) * ((lens.width + 1) // 2))`, slots outside the image
+        and fisheye pixels outside the circle absent.  `lens`: a lens.Lens.  `distance`: a CUDA float32 (lens.height, >= lens.width) tensor whose rows may
+        be further apart, every ray's tmax (default: lens.tmax).  `tile_index` (row-major only): returns `(rays, index)`, index the CUDA int32 tile index
+        for `shade_rays(index=...)` -- the image's 16 x 4 tiles one after the other, -1 entries for the absent pixels and the ragged tiles' rest."""
+        import torch
+
+        if quads and tile_index:
+            raise ValueError("the tile index is row-major only")
+        pitch = 0
+        if distance is not None:
+            if not (isinstance(distance, torch.Tensor) and distance.is_cuda and distance.dtype == torch.float32):
+                raise TypeError("distance must be a CUDA float32 tensor")
+            if distance.dim() != 2 or distance.shape[0] != lens.height or distance.shape[1] < lens.width or distance.stride(1) != 1 or (
+                    lens.height > 1 and distance.stride(0) < lens.width):
+                raise ValueError("distance must have shape (lens.height, >= lens.width) with contiguous rows")
+            pitch = int(distance.stride(0)) if lens.height > 1 else int(distance.shape[1])
+        fn, counts = self._entry("atmo_lens_rays"), self._entry("atmo_lens_ray_counts")
+        nl, flags = lens.native(), N.LENS_QUADS if quads else 0
+        n_rays, n_index = C.c_uint32(0), C.c_uint32(0)
+        N.check(self._ctx, counts(C.byref(nl), flags, C.byref(n_rays), C.byref(n_index)))
+        device = distance.device if distance is not None else torch.device("cuda", self._device)
+        handle = torch.cuda.current_stream(device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+        # as ray_order: what is allocated here belongs to the call's stream
+        with contextlib.nullcontext() if stream is None else torch.cuda.stream(torch.cuda.ExternalStream(handle, device=device)):
+            rays = torch.empty((n_rays.value, 8), dtype=torch.float32, device=device)
+            index = torch.empty((n_index.value,), dtype=torch.int32, device=device) if tile_index else None
+        N.check(self._ctx, fn(self._ctx, C.byref(nl), flags, C.c_void_p(distance.data_ptr()) if distance is not None else None, pitch,
+                              C.c_void_p(rays.data_ptr()), C.c_void_p(index.data_ptr()) if tile_index else None, C.c_void_p(handle or 0)))
+        return (rays, index) if tile_index else rays
+
+    def _shades_ray_quads(self) -> bool:
+        """Whether atmo_shade_ray_quads accepts this node (include/atmo_ray_quads.h): a cloud shader, a sampler mode other than 0, a mip chain bound."""
+        if not getattr(self, "_shader", DefaultShader).cloud_steps or self._cubemap_lod is False:
+            return False
+        mips = C.c_int(0)
+        N.check(self._ctx, self._lib.atmo_get_texture_size(self._ctx, b"u_cloud_coverage_cubemap", None, None, None, C.byref(mips)))
+        return mips.value > 1
+
+    def render_lens(self, lens, camera=None, distance=None, out=None, time: float = 0.0, stream=None, quads=None):
+        """Draws the sky through a lens: the rows `lens.rows` of a panorama, a fisheye, an octahedral map or a cube face (lens.Lens), a CUDA float32
+        (rows, lens.width, 4) image -- ALBEDO.rgb and ALPHA, zeros where a ray misses the atmosphere and outside a fisheye's circle.  The rays are
+        formed on the device (`lens_rays`) and shaded by the ray entry points; `camera` as in `shade_rays` (None: ray space is world space), `distance`
+        as in `lens_rays`.  `quads`: None picks the quad order -- the declared cubemap sampler, `shade_ray_quads` -- exactly when this node has one (a
+        cloud shader, a sampler mode other than level 0, a mip chain bound); else the rays are row-major and shaded through the tile index, in 16 x 4
+        blocks of the image, into a zeroed `out`.  With `cloud_detail` both paths go through the detail entry points.  An image drawn in several bands
+        is the one-call image: `first` and `first_quad` carry the jitter."""
+        import torch
+
+        from .ray_quads import quads_to_image
+
+        if quads is None:
+            quads = self._shades_ray_quads()
+        y0, y1 = lens.rows
+        rows, w = y1 - y0, lens.width
+        if out is not None:
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()):
+                raise TypeError("out must be a contiguous CUDA float32 tensor")
+            if tuple(out.shape) != (rows, w, 4):
+                raise ValueError(f"out must have shape ({rows}, {w}, 4)")
+        if rows == 0:
+            return out if out is not None else torch.zeros((0, w, 4), dtype=torch.float32, device=torch.device("cuda", self._device))
+        handle = None if stream is None else getattr(stream, "cuda_stream", stream)
+        with contextlib.nullcontext() if stream is None else torch.cuda.stream(torch.cuda.ExternalStream(handle, device=torch.device("cuda", self._device))):
+            if quads:
+                rays = self.lens_rays(lens, distance=distance, quads=True, stream=stream)
+                shaded = self.shade_ray_quads(rays, camera, width=w, first_quad=(y0 // 2) * ((w + 1) // 2), stream=stream, time=time)
+                image = quads_to_image(shaded, w, rows)
+                if out is None:
+                    return image.contiguous()
+                out.copy_(image)
+                return out
+            rays, index = self.lens_rays(lens, distance=distance, tile_index=True, stream=stream)
+            if out is None:
+                out = torch.zeros((rows, w, 4), dtype=torch.float32, device=rays.device)
+            else:
+                out.zero_()
+            self.shade_rays(rays, camera, width=w, first=y0 * w, out=out.view(rows * w, 4), stream=stream, time=time, index=index)
+            return out
+
     def prepare_frame(self, camera, time: float = 0.0, rect=None) -> N.AtmoFrame:
         """The native per-frame argument block for `render_prepared` (build once per camera pose)."""
         return _to_native_frame(self.make_frame(camera, time, rect))

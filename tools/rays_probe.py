@@ -61,7 +61,15 @@ from P_limb, same timing.  Two contexts per pose and family, atmo_set_tile_feedb
   render_q_off, quads_off  the same with the switch off;
   render2                  the level-0 detail draw again: the run-to-run spread.
 The pixel-side kernels are the parent commit's byte for byte (tools/isa_diff.py).  `bits_equal`: rays and quads against their draws, the two list arms
-against the shuffled arm."""
+against the shuffled arm.
+
+The LENS table (--table lens --rounds 5; include/atmo_lens.h), 2048 x 1024 (the cube face 1448 x 1448, as many rays within 0.03 %), same timing, every
+entry the median of the interleaved rounds.  `generator`: per lens, atmo_lens_rays alone -- row-major (`rows`), row-major with the tile index (`tiles`)
+and in quad order (`quads`) -- beside the 32 B / ray write floor at 6.2 TB/s (`floor_ms`; the tile index adds 4 B an entry).  `panorama`: per pose
+(P_space: 13 % of the sphere is the planet; P_clouds: the eye inside the cloud layer, every ray hits the shell) and family (clouds_high, clouds_high_rm, lut;
+the default sampler, a chain bound) the equirect's rays shaded three ways: `plain` = atmo_shade_rays row by row, `tiles` = the same rays through the
+tile index (atmo_shade_rays_indexed), `quads` = atmo_shade_ray_quads (the declared sampler: another picture; null for lut, which has no texture call).
+`bits_equal`: the tile arm against the plain arm."""
 import argparse
 import json
 import os
@@ -400,6 +408,105 @@ def detail_rows(args, tex, out, perm):
     return poses
 
 
+LENS_W, LENS_H, LENS_FACE = 2048, 1024, 1448
+LENS_FAMILIES = ("clouds_high", "clouds_high_rm", "lut")
+LENS_ORDERS = ("rows", "tiles", "quads")
+WRITE_TBPS = 6.2   # plain stores, MI355X
+
+
+def lens_rows(args, tex):
+    """The LENS table (the module's docstring)."""
+    import math
+
+    from godot_atmosphere_shader_amd.lens import Lens
+
+    def medians(calls, warm, graphs=False):
+        """ms per call of every arm, the rounds interleaved.  graphs: a call replays a captured graph of args.reps launches -- device time, no host between"""
+        for call in calls.values():
+            timed(call, 2 if graphs else args.warmup)
+        t_warm = time.perf_counter()
+        while time.perf_counter() - t_warm < 0.025:   # sustained clocks
+            warm()
+            torch.cuda.synchronize()
+        arms = {a: [] for a in calls}
+        for _ in range(args.rounds):
+            for arm, call in calls.items():
+                arms[arm].append(timed(call, 1) / args.reps if graphs else timed(call, args.reps))
+        return {a: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)} for a, v in arms.items()}
+
+    lenses = {"equirect": Lens.equirect(LENS_W, LENS_H), "fisheye": Lens.fisheye(LENS_W, LENS_H, fov=math.radians(180.0)),
+              "octahedral": Lens.octahedral(LENS_W, LENS_H), "cube_face": Lens.cube_face(LENS_FACE, 5)}
+    result = {"generator": [], "panorama": []}
+    node = make_node(FAMILIES["lut"][0], tex, tile_feedback=0)
+    try:
+        import ctypes as C
+
+        from godot_atmosphere_shader_amd import _native as N
+
+        # the generator alone is some tens of microseconds: each arm is a captured graph of args.reps calls into buffers of its own
+        calls, keep = {}, []
+        side = torch.cuda.Stream()
+        for name, lens in lenses.items():
+            for order in LENS_ORDERS:
+                n_rays, n_index = lens.counts(order == "quads")
+                rays = torch.empty((n_rays, 8), dtype=torch.float32, device="cuda")
+                index = torch.empty((n_index,), dtype=torch.int32, device="cuda") if order == "tiles" else None
+                nl, graph = lens.native(), torch.cuda.CUDAGraph()
+                with torch.cuda.stream(side):
+                    with torch.cuda.graph(graph, stream=side):   # one stream, no parallel branches
+                        for _ in range(args.reps):
+                            N.check(node._ctx, node._lib.atmo_lens_rays(node._ctx, C.byref(nl), N.LENS_QUADS if order == "quads" else 0, None, 0,
+                                                                        C.c_void_p(rays.data_ptr()), C.c_void_p(index.data_ptr()) if index is not None else None,
+                                                                        C.c_void_p(side.cuda_stream)))
+                torch.cuda.synchronize()
+                keep.append((rays, index, graph))
+                calls[f"{name}/{order}"] = graph.replay
+        ms = medians(calls, calls["equirect/rows"], graphs=True)
+        for name, lens in lenses.items():
+            n_rows, n_index = lens.counts(False)
+            n_quads = lens.counts(True)[0]
+            floor = {"rows": 32 * n_rows, "tiles": 32 * n_rows + 4 * n_index, "quads": 32 * n_quads}
+            row = {"lens": name, "size": [lens.width, lens.height], "ms": {o: ms[f"{name}/{o}"] for o in LENS_ORDERS},
+                   "floor_ms": {o: floor[o] / (WRITE_TBPS * 1e9) for o in LENS_ORDERS}}
+            result["generator"].append(row)
+            print(f"{name:11s} " + "  ".join(f"{o} {row['ms'][o]['median']:.4f} ms (floor {row['floor_ms'][o]:.4f})" for o in LENS_ORDERS), file=sys.stderr, flush=True)
+    finally:
+        node.close()
+    lens = lenses["equirect"]
+    for pose in ("P_space", "P_clouds"):
+        cam = S.Camera.from_pose(LENS_W, LENS_H, pose)   # of the camera the rays take the view matrix: the eye and its orientation
+        for label in LENS_FAMILIES:
+            config, kw = FAMILIES[label]
+            node = make_node(config, tex, tile_feedback=0, **kw)   # the default sampler: declared, a chain bound
+            try:
+                rays, index = node.lens_rays(lens, tile_index=True)
+                out = torch.empty((rays.shape[0], 4), dtype=torch.float32, device="cuda")
+                out2 = torch.zeros_like(out)
+                calls = {"plain": lambda: node.shade_rays(rays, cam, width=LENS_W, out=out),
+                         "tiles": lambda: node.shade_rays(rays, cam, width=LENS_W, out=out2, index=index)}
+                if label != "lut":
+                    quads = node.lens_rays(lens, quads=True)
+                    qout = torch.empty((quads.shape[0], 4), dtype=torch.float32, device="cuda")
+                    calls["quads"] = lambda: node.shade_ray_quads(quads, cam, width=LENS_W, out=qout)
+                names = {}
+                for arm, call in calls.items():
+                    call()
+                    names[arm] = node.kernel_name
+                torch.cuda.synchronize()
+                same = bool(torch.equal(out.view(torch.int32), out2.view(torch.int32)))
+                hit = float((out != 0).any(dim=1).float().mean())
+                ms = medians(calls, calls["plain"])
+            finally:
+                node.close()
+            row = {"pose": pose, "family": label, "kernels": names, "bits_equal": same, "shaded": hit, "ms": {a: ms.get(a) for a in ("plain", "tiles", "quads")},
+                   "tiles_over_plain": ms["tiles"]["median"] / ms["plain"]["median"],
+                   "quads_over_plain": ms["quads"]["median"] / ms["plain"]["median"] if "quads" in ms else None}
+            result["panorama"].append(row)
+            print(f"{pose} {label:15s} " + "  ".join(f"{a} {v['median']:.4f} ({v['min']:.4f} - {v['max']:.4f})" for a, v in ms.items()) +
+                  f"  tiles / plain {row['tiles_over_plain']:.3f}  shaded {hit:.3f}  bits equal: {same}", file=sys.stderr, flush=True)
+    return result
+
+
 def timed(call, reps):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -417,11 +524,20 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--families", default=",".join(FAMILIES))
-    ap.add_argument("--table", choices=("rays", "quads", "both", "order", "list", "detail"), default="both")
+    ap.add_argument("--table", choices=("rays", "quads", "both", "order", "list", "detail", "lens"), default="both")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rays_probe.py measures on a device; none is visible")
     tex = demo_textures()
+    if args.table == "lens":
+        result = {"reps": args.reps, "rounds": args.rounds, "device": torch.cuda.get_device_name(0), "lens": lens_rows(args, tex)}
+        text = json.dumps(result)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                fh.write(text + "\n")
+        print(text)
+        return
     cam = S.Camera.from_pose(W, H, "P_space")
     depth = torch.from_numpy(S.depth_ground_sphere(cam)).cuda()
     frame = torch.empty((H, W, 4), dtype=torch.float32, device="cuda")
