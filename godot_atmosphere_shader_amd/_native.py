@@ -234,51 +234,147 @@ class AtmoError(RuntimeError):
 
 _lib = None
 
+_vp, _cp, _ip, _fp, _u32, _sz = C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_uint32, C.c_size_t
+_ipp, _upp, _frame = C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(AtmoFrame)
+_rays = [_vp, _frame, _vp, _vp, _u32, _u32, _u32]   # ctx, frame, rays_dev, rgba_dev, n, width, first
+# THE signatures of the C ABI, one block a header: header -> (its `*_SYMBOLS` tuple, required?, what the missing-symbol message of an optional header adds
+# behind the header's name, name -> (restype, argtypes) in the tuple's order).  load() binds from it and holds every block to its tuple: a symbol added
+# to a tuple and forgotten here fails the load instead of running with ctypes' default int signature.  A library must export the required headers
+# (ATMO_HIP_LIB's A/B rule apart); the optional ones are detected by symbol (each `*_SYMBOLS` comment above says what raises without).
+HEADERS = {
+    "atmo.h": (CORE_SYMBOLS, True, "", {
+        "atmo_abi_version": (_ip, []),
+        "atmo_device_count": (_ip, []),
+        "atmo_create": (_ip, [_ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(_vp)]),
+        "atmo_destroy": (_ip, [_vp]),
+        "atmo_set_param_f32": (_ip, [_vp, _cp, _fp, _ip]),
+        "atmo_get_param_f32": (_ip, [_vp, _cp, _fp, _ip]),
+        "atmo_set_texture": (_ip, [_vp, _cp, _ip, _ip, _ip, _ip, _ip, _vp, _ip, _vp]),
+        "atmo_get_texture_size": (_ip, [_vp, _cp, _ipp, _ipp, _ipp, _ipp]),
+        "atmo_set_sampler_lod": (_ip, [_vp, _ip]),
+        "atmo_bake_optical_depth": (_ip, [_vp, _vp]),
+        "atmo_generate_noise_cubemap": (_ip, [_vp, _ip, _u32, C.c_float, _ip, C.c_float, _fp, _ip, _vp, C.POINTER(C.c_double)]),
+        "atmo_read_optical_depth": (_ip, [_vp, _vp, _vp, _ip, _vp]),
+        "atmo_render": (_ip, [_vp, _frame, _vp, _vp, _vp]),
+        "atmo_render_composite": (_ip, [_vp, _frame, _vp, _vp, _vp]),
+        "atmo_render_tiles": (_ip, [_vp, _frame, _vp, _vp, _vp, _ip, _vp]),
+        "atmo_render_tiles_split": (_ip, [_vp, _frame, _vp, _vp, _vp, _ip, _ip, _vp]),
+        "atmo_measure_tile_costs": (_ip, [_vp, _frame, _vp, _vp, _vp, _vp, _ip, _ipp, _ipp, _ipp, _ipp]),
+        "atmo_set_precision": (_ip, [_vp, _ip]),
+        "atmo_set_host_double_precision": (_ip, [_vp, _ip]),
+        "atmo_set_target_cleared": (_ip, [_vp, _ip]),
+        "atmo_set_tile_feedback": (_ip, [_vp, _ip]),
+        "atmo_last_error_string": (_cp, [_vp]),
+    }),
+    "atmo_debug.h": (DEBUG_SYMBOLS, True, "", {
+        "atmo_set_lane_split": (_ip, [_vp, _ip]),
+        "atmo_debug_motion_px": (C.c_float, [_frame, _frame, C.c_float, _ip]),
+        "atmo_get_feedback_stats": (_ip, [_vp, _ipp, _upp, _upp, _upp]),
+        "atmo_set_timing": (_ip, [_vp, _ip]),
+        "atmo_get_timing": (_ip, [_vp, _ipp, C.POINTER(C.c_double)]),
+        "atmo_host_layout_cubemap": (_ip, [_vp, _ip, _vp]),
+        "atmo_host_layout_shape": (_ip, [_vp, _ip, _vp]),
+        "atmo_host_layout_lut": (_ip, [_vp, _ip, _ip, _vp]),
+        "atmo_host_cubemap_mip": (_ip, [_vp, _ip, _vp]),
+        "atmo_read_texture_layout": (_ip, [_vp, _cp, _vp, _sz, C.POINTER(_sz), _vp]),
+        "atmo_selftest_exact_math": (_ip, [_vp, _u32, _u32, C.c_float, C.POINTER(_u32), C.POINTER(_u32)]),
+        "atmo_debug_marched_optical_depth": (_ip, [_vp, _ip, _vp, _vp, _ip, _vp]),
+        "atmo_debug_log2_cr": (_ip, [_vp, _ip, _vp, _vp]),
+        "atmo_kernel_name": (_cp, [_vp]),
+        "atmo_build_id": (_cp, []),
+        "atmo_get_host_wait_stats": (_ip, [_vp, _upp]),
+        "atmo_get_split_stats": (_ip, [_vp, _upp, _upp]),
+        "atmo_debug_create_host_only": (_ip, [_ip, _ip, _ip, _ip, _ip, C.POINTER(_vp)]),
+        "atmo_debug_frame_constants": (_ip, [_vp, _frame, _ip, _fp, _ip, _ipp]),
+        "atmo_debug_proxy_launch_rect": (_ip, [_vp, _frame, _fp, C.c_float, _ipp, _ipp]),
+        "atmo_debug_store_target": (_ip, [_vp, _ip, _ip, _vp, _vp, _sz, _vp]),
+        "atmo_debug_views_layout": (_ip, [_vp, C.POINTER(AtmoView), _ip, _ipp, _ipp]),
+        "atmo_debug_views_proxy_layout": (_ip, [_vp, C.POINTER(AtmoView), _ip, _fp, C.c_float, _ipp, _ipp, _ipp]),
+        "atmo_debug_tile_order": (_ip, [_vp, _vp, _ip, _ip, _ip, _ip, _vp, _vp, _vp, _vp, _ipp]),
+        "atmo_debug_heavy_tile_count": (_ip, [_vp, _ip, _ip, C.c_float, C.c_float, _ip]),
+        "atmo_debug_feedback_plan": (_ip, [C.POINTER(AtmoFeedbackPlanIn), C.POINTER(AtmoFeedbackPlanOut)]),
+        "atmo_debug_decode_depth": (_ip, [_ip, _vp, _vp, _sz, _vp]),
+    }),
+    "atmo_scene.h": (SCENE_SYMBOLS, True, "", {
+        "atmo_render_proxy": (_ip, [_vp, _frame, _fp, C.c_float, _vp, _vp, _vp]),
+        "atmo_render_proxy_composite": (_ip, [_vp, _frame, _fp, C.c_float, _vp, _vp, _vp]),
+    }),
+    "atmo_target.h": (TARGET_SYMBOLS, True, "", {
+        "atmo_target_pixel_bytes": (_ip, [_ip]),
+        "atmo_render_target": (_ip, [_vp, _frame, _vp, C.POINTER(AtmoTarget), _ip, _vp]),
+        "atmo_render_proxy_target": (_ip, [_vp, _frame, _fp, C.c_float, _vp, C.POINTER(AtmoTarget), _ip, _vp]),
+    }),
+    "atmo_views.h": (VIEWS_SYMBOLS, True, "", {
+        "atmo_render_views": (_ip, [_vp, C.POINTER(AtmoView), _ip, _ip, _vp]),
+    }),
+    "atmo_views_target.h": (VIEWS_TARGET_SYMBOLS, True, "", {
+        "atmo_render_views_target": (_ip, [_vp, C.POINTER(AtmoViewTarget), _ip, _ip, _vp]),
+    }),
+    "atmo_views_proxy.h": (VIEWS_PROXY_SYMBOLS, True, "", {
+        "atmo_render_views_proxy": (_ip, [_vp, C.POINTER(AtmoView), _ip, _fp, C.c_float, _ip, _vp]),
+        "atmo_render_views_proxy_target": (_ip, [_vp, C.POINTER(AtmoViewTarget), _ip, _fp, C.c_float, _ip, _vp]),
+    }),
+    "atmo_planets.h": (PLANETS_SYMBOLS, True, "", {
+        "atmo_render_planets": (_ip, [C.POINTER(AtmoPlanetDraw), _ip, _vp]),
+        "atmo_plan_planets": (_ip, [C.POINTER(AtmoPlanetDraw), _ip, _ipp, _ipp]),
+    }),
+    "atmo_depth.h": (DEPTH_SYMBOLS, True, "", {
+        "atmo_depth_texel_bytes": (_ip, [_ip]),
+        "atmo_render_depth_target": (_ip, [_vp, _frame, C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), _ip, _vp]),
+        "atmo_render_proxy_depth_target": (_ip, [_vp, _frame, _fp, C.c_float, C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), _ip, _vp]),
+        "atmo_render_views_depth_target": (_ip, [_vp, C.POINTER(AtmoViewDepthTarget), _ip, _ip, _vp]),
+        "atmo_render_views_proxy_depth_target": (_ip, [_vp, C.POINTER(AtmoViewDepthTarget), _ip, _fp, C.c_float, _ip, _vp]),
+    }),
+    "atmo_debug_prologue.h": (PROLOGUE_SYMBOLS, True, "", {
+        "atmo_debug_prologue_mode": (_ip, [_vp, _frame, _upp, _ipp, _ipp]),
+        "atmo_debug_prologue_constants": (_ip, [_vp, _frame, _fp, _ip, _ipp]),
+    }),
+    "atmo_noise_volume.h": (NOISE_VOLUME_SYMBOLS, True, "", {
+        "atmo_generate_noise_volume": (_ip, [_vp, C.POINTER(AtmoNoiseVolume), _ip, _vp, _vp]),
+    }),
+    "atmo_cloud_detail.h": (CLOUD_DETAIL_SYMBOLS, False, "", {
+        "atmo_set_cloud_detail": (_ip, [_vp, _ip]),
+        "atmo_get_cloud_detail": (_ip, [_vp, _ipp]),
+        "atmo_debug_cloud_detail_constants": (_ip, [_vp, _frame, _fp, _ip, _ipp]),
+    }),
+    "atmo_rays.h": (RAYS_SYMBOLS, False, "", {
+        "atmo_shade_rays": (_ip, _rays + [_vp]),
+        "atmo_debug_frame_rays": (_ip, [_vp, _frame, _vp, _vp, _vp]),
+    }),
+    "atmo_ray_quads.h": (RAY_QUADS_SYMBOLS, False, "", {
+        "atmo_shade_ray_quads": (_ip, _rays + [_vp]),
+    }),
+    "atmo_ray_order.h": (RAY_ORDER_SYMBOLS, False, "", {
+        "atmo_ray_order_scratch_bytes": (_ip, [_u32, C.POINTER(_sz)]),
+        "atmo_ray_order": (_ip, [_vp, _vp, _u32, _vp, _vp, _sz, _vp]),
+        "atmo_shade_rays_indexed": (_ip, _rays + [_vp, _u32, _vp]),
+        "atmo_debug_ray_keys": (_ip, [_vp, _vp, _u32, _vp, _vp]),
+        "atmo_debug_sort_ray_keys": (_ip, [_vp, _vp, _u32, _vp, _vp, _sz, _vp]),
+    }),
+    "atmo_ray_list.h": (RAY_LIST_SYMBOLS, False, "", {
+        "atmo_ray_list_scratch_bytes": (_ip, [_u32, C.POINTER(_sz)]),
+        "atmo_ray_list": (_ip, [_vp, _frame, _vp, _vp, _u32, _ip, _vp, _vp, _vp, _vp, _sz, _vp]),
+        "atmo_debug_ray_cull_constants": (_ip, [_vp, _frame, _fp, _ip, _ipp]),
+    }),
+    "atmo_ray_detail.h": (RAY_DETAIL_SYMBOLS, False, ": no cloud detail for rays", {
+        "atmo_shade_rays_detail": (_ip, _rays + [_vp, _u32, _vp]),
+        "atmo_shade_ray_quads_detail": (_ip, _rays + [_vp]),
+    }),
+    "atmo_detail_target.h": (DETAIL_TARGET_SYMBOLS, False, ": no cloud detail into targets", {
+        "atmo_render_detail_target": (_ip, [_vp, _frame, C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), _ip, _vp]),
+        "atmo_render_views_detail_target": (_ip, [_vp, C.POINTER(AtmoViewDepthTarget), _ip, _ip, _vp]),
+    }),
+    "atmo_lens.h": (LENS_SYMBOLS, False, ": no lens rays", {
+        "atmo_lens_ray_counts": (_ip, [C.POINTER(AtmoLens), _u32, C.POINTER(_u32), C.POINTER(_u32)]),
+        "atmo_lens_rays": (_ip, [_vp, C.POINTER(AtmoLens), _u32, _vp, _u32, _vp, _vp, _vp]),
+    }),
+}
+
 
 def optional_headers() -> dict:
     """The headers whose symbols a library may lack (each `*_SYMBOLS` comment above says what then raises): header -> (its symbols' tuple, what the
     missing-symbol message adds behind the header's name, name -> (restype, argtypes))."""
-    vp, ip, fp, u32, sz = C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_uint32, C.c_size_t
-    frame = C.POINTER(AtmoFrame)
-    rays = [vp, frame, vp, vp, u32, u32, u32]   # ctx, frame, rays_dev, rgba_dev, n, width, first
-    return {
-        "atmo_cloud_detail.h": (CLOUD_DETAIL_SYMBOLS, "", {
-            "atmo_set_cloud_detail": (ip, [vp, ip]),
-            "atmo_get_cloud_detail": (ip, [vp, C.POINTER(ip)]),
-            "atmo_debug_cloud_detail_constants": (ip, [vp, frame, fp, ip, C.POINTER(ip)]),
-        }),
-        "atmo_rays.h": (RAYS_SYMBOLS, "", {
-            "atmo_shade_rays": (ip, rays + [vp]),
-            "atmo_debug_frame_rays": (ip, [vp, frame, vp, vp, vp]),
-        }),
-        "atmo_ray_quads.h": (RAY_QUADS_SYMBOLS, "", {
-            "atmo_shade_ray_quads": (ip, rays + [vp]),
-        }),
-        "atmo_ray_order.h": (RAY_ORDER_SYMBOLS, "", {
-            "atmo_ray_order_scratch_bytes": (ip, [u32, C.POINTER(sz)]),
-            "atmo_ray_order": (ip, [vp, vp, u32, vp, vp, sz, vp]),
-            "atmo_shade_rays_indexed": (ip, rays + [vp, u32, vp]),
-            "atmo_debug_ray_keys": (ip, [vp, vp, u32, vp, vp]),
-            "atmo_debug_sort_ray_keys": (ip, [vp, vp, u32, vp, vp, sz, vp]),
-        }),
-        "atmo_ray_list.h": (RAY_LIST_SYMBOLS, "", {
-            "atmo_ray_list_scratch_bytes": (ip, [u32, C.POINTER(sz)]),
-            "atmo_ray_list": (ip, [vp, frame, vp, vp, u32, ip, vp, vp, vp, vp, sz, vp]),
-            "atmo_debug_ray_cull_constants": (ip, [vp, frame, fp, ip, C.POINTER(ip)]),
-        }),
-        "atmo_ray_detail.h": (RAY_DETAIL_SYMBOLS, ": no cloud detail for rays", {
-            "atmo_shade_rays_detail": (ip, rays + [vp, u32, vp]),
-            "atmo_shade_ray_quads_detail": (ip, rays + [vp]),
-        }),
-        "atmo_detail_target.h": (DETAIL_TARGET_SYMBOLS, ": no cloud detail into targets", {
-            "atmo_render_detail_target": (ip, [vp, frame, C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), ip, vp]),
-            "atmo_render_views_detail_target": (ip, [vp, C.POINTER(AtmoViewDepthTarget), ip, ip, vp]),
-        }),
-        "atmo_lens.h": (LENS_SYMBOLS, ": no lens rays", {
-            "atmo_lens_ray_counts": (ip, [C.POINTER(AtmoLens), u32, C.POINTER(u32), C.POINTER(u32)]),
-            "atmo_lens_rays": (ip, [vp, C.POINTER(AtmoLens), u32, vp, u32, vp, vp, vp]),
-        }),
-    }
+    return {header: (symbols, suffix, signatures) for header, (symbols, required, suffix, signatures) in HEADERS.items() if not required}
 
 
 def optional_entry(lib, name: str):
@@ -307,96 +403,20 @@ def load() -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    vp, cp, ip, fp = C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_float)
-    sig = {
-        "atmo_abi_version": (ip, []),
-        "atmo_device_count": (ip, []),
-        "atmo_create": (ip, [ip, ip, ip, ip, ip, ip, C.POINTER(vp)]),
-        "atmo_destroy": (ip, [vp]),
-        "atmo_set_param_f32": (ip, [vp, cp, fp, ip]),
-        "atmo_get_param_f32": (ip, [vp, cp, fp, ip]),
-        "atmo_set_texture": (ip, [vp, cp, ip, ip, ip, ip, ip, vp, ip, vp]),
-        "atmo_get_texture_size": (ip, [vp, cp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]),
-        "atmo_set_sampler_lod": (ip, [vp, ip]),
-        "atmo_read_texture_layout": (ip, [vp, cp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]),
-        "atmo_host_cubemap_mip": (ip, [vp, ip, vp]),
-        "atmo_generate_noise_cubemap": (ip, [vp, ip, C.c_uint32, C.c_float, ip, C.c_float, fp, ip, vp, C.POINTER(C.c_double)]),
-        "atmo_bake_optical_depth": (ip, [vp, vp]),
-        "atmo_read_optical_depth": (ip, [vp, vp, vp, ip, vp]),
-        "atmo_render": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, vp]),
-        "atmo_render_composite": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, vp]),
-        "atmo_render_tiles": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, vp, ip, vp]),
-        "atmo_measure_tile_costs": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, vp, vp, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]),
-        "atmo_set_precision": (ip, [vp, ip]),
-        "atmo_set_host_double_precision": (ip, [vp, ip]),
-        "atmo_set_lane_split": (ip, [vp, ip]),
-        "atmo_set_tile_feedback": (ip, [vp, ip]),
-        "atmo_set_target_cleared": (ip, [vp, ip]),
-        "atmo_debug_motion_px": (C.c_float, [C.POINTER(AtmoFrame), C.POINTER(AtmoFrame), C.c_float, ip]),
-        "atmo_get_feedback_stats": (ip, [vp, C.POINTER(ip), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
-        "atmo_set_timing": (ip, [vp, ip]),
-        "atmo_get_timing": (ip, [vp, C.POINTER(ip), C.POINTER(C.c_double)]),
-        "atmo_selftest_exact_math": (ip, [vp, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-        "atmo_debug_marched_optical_depth": (ip, [vp, ip, vp, vp, ip, vp]),
-        "atmo_debug_log2_cr": (ip, [vp, ip, vp, vp]),
-        "atmo_host_layout_cubemap": (ip, [vp, ip, vp]),
-        "atmo_host_layout_shape": (ip, [vp, ip, vp]),
-        "atmo_host_layout_lut": (ip, [vp, ip, ip, vp]),
-        "atmo_kernel_name": (cp, [vp]),
-        "atmo_build_id": (cp, []),
-        "atmo_get_host_wait_stats": (ip, [vp, C.POINTER(C.c_uint)]),
-        "atmo_get_split_stats": (ip, [vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
-        "atmo_render_tiles_split": (ip, [vp, C.POINTER(AtmoFrame), vp, vp, vp, ip, ip, vp]),
-        "atmo_debug_create_host_only": (ip, [ip, ip, ip, ip, ip, C.POINTER(vp)]),
-        "atmo_debug_frame_constants": (ip, [vp, C.POINTER(AtmoFrame), ip, C.POINTER(C.c_float), ip, C.POINTER(ip)]),
-        "atmo_last_error_string": (cp, [vp]),
-        "atmo_debug_proxy_launch_rect": (ip, [vp, C.POINTER(AtmoFrame), fp, C.c_float, C.POINTER(ip), C.POINTER(ip)]),
-        "atmo_render_proxy": (ip, [vp, C.POINTER(AtmoFrame), fp, C.c_float, vp, vp, vp]),
-        "atmo_render_proxy_composite": (ip, [vp, C.POINTER(AtmoFrame), fp, C.c_float, vp, vp, vp]),
-        "atmo_target_pixel_bytes": (ip, [ip]),
-        "atmo_render_target": (ip, [vp, C.POINTER(AtmoFrame), vp, C.POINTER(AtmoTarget), ip, vp]),
-        "atmo_render_proxy_target": (ip, [vp, C.POINTER(AtmoFrame), fp, C.c_float, vp, C.POINTER(AtmoTarget), ip, vp]),
-        "atmo_debug_store_target": (ip, [vp, ip, ip, vp, vp, C.c_size_t, vp]),
-        "atmo_render_views": (ip, [vp, C.POINTER(AtmoView), ip, ip, vp]),
-        "atmo_debug_views_layout": (ip, [vp, C.POINTER(AtmoView), ip, C.POINTER(ip), C.POINTER(ip)]),
-        "atmo_render_views_target": (ip, [vp, C.POINTER(AtmoViewTarget), ip, ip, vp]),
-        "atmo_render_views_proxy": (ip, [vp, C.POINTER(AtmoView), ip, fp, C.c_float, ip, vp]),
-        "atmo_render_views_proxy_target": (ip, [vp, C.POINTER(AtmoViewTarget), ip, fp, C.c_float, ip, vp]),
-        "atmo_debug_views_proxy_layout": (ip, [vp, C.POINTER(AtmoView), ip, fp, C.c_float, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]),
-        "atmo_render_planets": (ip, [C.POINTER(AtmoPlanetDraw), ip, vp]),
-        "atmo_plan_planets": (ip, [C.POINTER(AtmoPlanetDraw), ip, C.POINTER(ip), C.POINTER(ip)]),
-        "atmo_depth_texel_bytes": (ip, [ip]),
-        "atmo_render_depth_target": (ip, [vp, C.POINTER(AtmoFrame), C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), ip, vp]),
-        "atmo_render_proxy_depth_target": (ip, [vp, C.POINTER(AtmoFrame), fp, C.c_float, C.POINTER(AtmoDepth), C.POINTER(AtmoTarget), ip, vp]),
-        "atmo_render_views_depth_target": (ip, [vp, C.POINTER(AtmoViewDepthTarget), ip, ip, vp]),
-        "atmo_render_views_proxy_depth_target": (ip, [vp, C.POINTER(AtmoViewDepthTarget), ip, fp, C.c_float, ip, vp]),
-        "atmo_debug_decode_depth": (ip, [ip, vp, vp, C.c_size_t, vp]),
-        "atmo_debug_tile_order": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, C.POINTER(ip)]),
-        "atmo_debug_heavy_tile_count": (ip, [vp, ip, ip, C.c_float, C.c_float, ip]),
-        "atmo_debug_feedback_plan": (ip, [C.POINTER(AtmoFeedbackPlanIn), C.POINTER(AtmoFeedbackPlanOut)]),
-        "atmo_debug_prologue_mode": (ip, [vp, C.POINTER(AtmoFrame), C.POINTER(C.c_uint), C.POINTER(ip), C.POINTER(ip)]),
-        "atmo_debug_prologue_constants": (ip, [vp, C.POINTER(AtmoFrame), fp, ip, C.POINTER(ip)]),
-        "atmo_generate_noise_volume": (ip, [vp, C.POINTER(AtmoNoiseVolume), ip, vp, vp]),
-    }
     # ATMO_HIP_LIB names an A/B build (tools/ab_build_commit.sh: possibly an OLDER commit's library): entry points it lacks are skipped
     # (callers of those guard with hasattr) and its ABI version is not held against it.  The in-tree library must match exactly.
+    # The optional headers are detected by symbol: bound where present, and a library without them loads all the same.
     ab_build = bool(os.environ.get("ATMO_HIP_LIB"))
-    for name, (res, args) in sig.items():
-        fn = getattr(lib, name, None)
-        if fn is None:
-            if ab_build:
-                continue
-            raise RuntimeError(f"libatmo_hip.so does not export {name}; rebuild it")
-        fn.restype = res
-        fn.argtypes = args
-    # the optional headers: detected by symbol -- bound where present, and a library without them loads all the same
-    for header, (symbols, _, optional_sig) in optional_headers().items():
-        assert tuple(optional_sig) == symbols, header
-        for name, (res, args) in optional_sig.items():
+    for header, (symbols, required, _, signatures) in HEADERS.items():
+        assert tuple(signatures) == symbols, header
+        for name, (res, args) in signatures.items():
             fn = getattr(lib, name, None)
-            if fn is not None:
-                fn.restype = res
-                fn.argtypes = args
+            if fn is None:
+                if required and not ab_build:
+                    raise RuntimeError(f"libatmo_hip.so does not export {name}; rebuild it")
+                continue
+            fn.restype = res
+            fn.argtypes = args
     have = lib.atmo_abi_version()
     if have != ABI_VERSION:
         # An A/B library may be older, but only a version whose AtmoFrame layout and shared entry points are KNOWN to be what this binding

@@ -226,6 +226,19 @@ _BATCH_DRAWS = {
     (True, False, False): "atmo_render_views_proxy", (True, True, False): "atmo_render_views_proxy_target",
     (False, True, True): "atmo_render_views_depth_target", (True, True, True): "atmo_render_views_proxy_depth_target",
 }
+# The C entry point of a batch of caller-supplied rays, by (in 2 x 2 quads?, with cloud detail -- `_serves_cloud_detail` --?, through an index list?).
+# All take (ctx, &frame, rays, rgba, n or n_quads, width, first or first_quad, [index, n_index,] stream); the quads have no indexed form.  Cloud detail
+# has ONE entry point for rays, plain and indexed: atmo_shade_rays_detail takes (None, 0) for the whole batch (`_WHOLE_BATCH`).
+# `PlanetAtmosphere._shade_batch` builds the call from the row; a new entry point is a new row.
+_RAY_ENTRIES = {
+    (False, False, False): "atmo_shade_rays", (False, False, True): "atmo_shade_rays_indexed",
+    (False, True, False): "atmo_shade_rays_detail", (False, True, True): "atmo_shade_rays_detail",
+    (True, False, False): "atmo_shade_ray_quads", (True, True, False): "atmo_shade_ray_quads_detail",
+}
+_WHOLE_BATCH = {"atmo_shade_rays_detail": (None, 0)}
+# ... and what the two public methods call their arguments, by the rows of a unit: (the tensor, the first unit's number, the count of units, `out`'s shape
+# as the message states it, the bits of first + count)
+_RAY_BATCH_NAMES = {1: ("rays", "first", "n", "(n, 4)", 32), 4: ("quads", "first_quad", "n_quads", "(4 * n_quads, 4)", 30)}
 
 
 class DepthSource:
@@ -704,32 +717,48 @@ class PlanetAtmosphere:
         `index` (a contiguous CUDA int32 (m,) tensor, `ray_order`'s or any list of ray numbers): the rays it names are shaded, 64 consecutive entries a
         wavefront, each to its own row of `out` with the bits the plain call gives it (atmo_shade_rays_indexed; include/atmo_ray_order.h); rows it does
         not name are left as they are -- zeros where `out` is created here."""
-        n = _check_rays(rays, "rays", 8)
+        return self._shade_batch(1, rays, camera, width, first, out, stream, time, index)
+
+    def _shade_batch(self, per, rays, camera, width, first, out, stream, time, index=None):
+        """`shade_rays` (per = 1: a unit is a ray) and `shade_ray_quads` (per = 4: a unit is a quad): the checks in one order under each method's own
+        names, `out` created where it is None -- zeros under an index list, whose unnamed rows are left as they are --, the bake, the `_RAY_ENTRIES` row."""
+        what, first_name, units, out_shape, bits = _RAY_BATCH_NAMES[per]
+        n = _check_rays(rays, what, 8)
+        if n % per:
+            raise ValueError("quads must have four rows per quad: shape (4 * n_quads, 8)")
         if index is not None:
             _check_index(index)
         try:
-            width, first = max(n, 1) if width is None else operator.index(width), operator.index(first)
+            width, first = max(n, 1) if width is None and per == 1 else operator.index(width), operator.index(first)
         except TypeError:
-            raise TypeError("width and first must be integers") from None
-        if width < 1 or first < 0 or first + n > 1 << 32:
-            raise ValueError("width must be at least 1, first at least 0 and first + n at most 2^32")
+            raise TypeError(f"width and {first_name} must be integers") from None
+        if width < 1 or first < 0 or first + n // per > 1 << bits:
+            raise ValueError(f"width must be at least 1, {first_name} at least 0 and {first_name} + {units} at most 2^{bits}")
         if out is None:
             import torch
 
             out = (torch.empty if index is None else torch.zeros)((n, 4), dtype=torch.float32, device=rays.device)
         elif _check_rays(out, "out", 4) != n:
-            raise ValueError("out must have one row per ray: shape (n, 4)")
-        detail = self._serves_cloud_detail()
-        fn = self._entry("atmo_shade_rays_detail" if detail else "atmo_shade_rays" if index is None else "atmo_shade_rays_indexed")
+            raise ValueError(f"out must have one row per ray: shape {out_shape}")
+        name = _RAY_ENTRIES[per == 4, self._serves_cloud_detail(), index is not None]
+        fn = self._entry(name)
         stream = _stream_handle(stream, rays)
         self._bake_if_needed(stream)
-        nf = _to_native_frame(self.make_frame(camera if camera is not None else _WORLD_RAY_SPACE, time))
-        listed = () if index is None else (C.c_void_p(index.data_ptr()), int(index.shape[0]))
-        if detail and index is None:   # atmo_shade_rays_detail: a null list is the whole batch
-            listed = (None, 0)
-        N.check(self._ctx, fn(self._ctx, C.byref(nf), C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr()), n, width, first, *listed,
+        nf = self._ray_frame(camera, time)
+        listed = _WHOLE_BATCH.get(name, ()) if index is None else (C.c_void_p(index.data_ptr()), int(index.shape[0]))
+        N.check(self._ctx, fn(self._ctx, C.byref(nf), C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr()), n // per, width, first, *listed,
                               C.c_void_p(stream or 0)))
         return out
+
+    def _ray_frame(self, camera, time: float) -> N.AtmoFrame:
+        """The frame of a ray call: `camera` supplies inv_view, the map from ray space to world space; None: ray space is world space."""
+        return _to_native_frame(self.make_frame(camera if camera is not None else _WORLD_RAY_SPACE, time))
+
+    def _scratch(self, size_entry: str, count: int):
+        """(bytes, int32 words) of the scratch a `*_scratch_bytes` entry point asks for `count` rays: the words fill whole 16-byte units."""
+        need = C.c_size_t(0)
+        N.check(self._ctx, self._entry(size_entry)(count, C.byref(need)))
+        return need.value, (need.value + 15) // 16 * 4
 
     # ---- coherent ray queues (include/atmo_ray_order.h) ---------------------------------------------------------------------------
     def ray_order(self, rays, stream=None):
@@ -744,17 +773,12 @@ class PlanetAtmosphere:
         order = torch.empty((n,), dtype=torch.int32, device=rays.device)
         if n == 0:
             return order
-        fn, size = self._entry("atmo_ray_order"), self._entry("atmo_ray_order_scratch_bytes")
-        need = C.c_size_t(0)
-        N.check(self._ctx, size(n, C.byref(need)))
-        handle = _stream_handle(stream, rays)
-        words = (need.value + 15) // 16 * 4
-        if stream is None:   # torch's current stream: the allocator reuses the scratch behind the sort, in stream order
+        fn = self._entry("atmo_ray_order")
+        need, words = self._scratch("atmo_ray_order_scratch_bytes", n)
+        handle, on_stream = _on_stream(stream, rays.device)
+        with on_stream:
             scratch = torch.empty((words,), dtype=torch.int32, device=rays.device)
-        else:                # ... and so it does on the caller's stream, when the scratch is allocated there
-            with torch.cuda.stream(torch.cuda.ExternalStream(handle, device=rays.device)):
-                scratch = torch.empty((words,), dtype=torch.int32, device=rays.device)
-        N.check(self._ctx, fn(self._ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(order.data_ptr()), C.c_void_p(scratch.data_ptr()), need.value,
+        N.check(self._ctx, fn(self._ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(order.data_ptr()), C.c_void_p(scratch.data_ptr()), need,
                               C.c_void_p(handle or 0)))
         return order
 
@@ -774,8 +798,7 @@ class PlanetAtmosphere:
         if capacity > 1 << 28:
             raise ValueError("at most 2^28 rays")
         if count is not None:
-            if not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()):
-                raise TypeError("count must be a contiguous CUDA int32 tensor")
+            _check_kind(count, "count must be a contiguous CUDA int32 tensor", "int32")
             if count.numel() != 1:
                 raise ValueError("count must have one element")
         flags = (N.RAY_LIST_ORDER if order else 0) | (N.RAY_LIST_CULL if cull else 0)
@@ -783,22 +806,19 @@ class PlanetAtmosphere:
             raise ValueError("out must have one row per ray: shape (n, 4)")
         if capacity == 0:
             return torch.empty((0,), dtype=torch.int32, device=rays.device), torch.zeros((1,), dtype=torch.int32, device=rays.device)
-        fn, size = self._entry("atmo_ray_list"), self._entry("atmo_ray_list_scratch_bytes")
-        need = C.c_size_t(0)
-        N.check(self._ctx, size(capacity, C.byref(need)))
-        handle = _stream_handle(stream, rays)
-        words = (need.value + 15) // 16 * 4
-        # as ray_order: what is allocated (and zeroed) here belongs to the call's stream, where the allocator reuses the scratch behind the list
-        with contextlib.nullcontext() if stream is None else torch.cuda.stream(torch.cuda.ExternalStream(handle, device=rays.device)):
+        fn = self._entry("atmo_ray_list")
+        need, words = self._scratch("atmo_ray_list_scratch_bytes", capacity)
+        handle, on_stream = _on_stream(stream, rays.device)
+        with on_stream:   # what is allocated (and zeroed) here belongs to the call's stream, as the scratch does
             scratch = torch.empty((words,), dtype=torch.int32, device=rays.device)
             index = torch.empty((capacity,), dtype=torch.int32, device=rays.device)
             listed = torch.empty((1,), dtype=torch.int32, device=rays.device)
             if cull and out is None:
                 out = torch.zeros((capacity, 4), dtype=torch.float32, device=rays.device)
-        nf = _to_native_frame(self.make_frame(camera if camera is not None else _WORLD_RAY_SPACE, 0.0)) if cull else None
+        nf = self._ray_frame(camera, 0.0) if cull else None
         N.check(self._ctx, fn(self._ctx, C.byref(nf) if cull else None, C.c_void_p(rays.data_ptr()), C.c_void_p(count.data_ptr()) if count is not None else None,
                               capacity, flags, C.c_void_p(out.data_ptr()) if cull else None, C.c_void_p(index.data_ptr()), C.c_void_p(listed.data_ptr()),
-                              C.c_void_p(scratch.data_ptr()), need.value, C.c_void_p(handle or 0)))
+                              C.c_void_p(scratch.data_ptr()), need, C.c_void_p(handle or 0)))
         return index, listed
 
     def camera_rays(self, camera, depth, rect=None, stream=None):
@@ -826,28 +846,7 @@ class PlanetAtmosphere:
         ray.  `camera` as in `shade_rays`.  Returns or fills `out`, a contiguous CUDA float32 (4 * n_quads, 4) tensor in the same order (zeros for an
         absent ray and for one that misses the atmosphere); ray_quads.quads_to_image puts a whole image's back into rows.  The declared sampler; with
         `cloud_detail`, the detail fetch as well, moving with `time` (atmo_shade_ray_quads_detail; include/atmo_ray_detail.h)."""
-        n = _check_rays(quads, "quads", 8)
-        if n % 4:
-            raise ValueError("quads must have four rows per quad: shape (4 * n_quads, 8)")
-        try:
-            width, first_quad = operator.index(width), operator.index(first_quad)
-        except TypeError:
-            raise TypeError("width and first_quad must be integers") from None
-        if width < 1 or first_quad < 0 or first_quad + n // 4 > 1 << 30:
-            raise ValueError("width must be at least 1, first_quad at least 0 and first_quad + n_quads at most 2^30")
-        if out is None:
-            import torch
-
-            out = torch.empty((n, 4), dtype=torch.float32, device=quads.device)
-        elif _check_rays(out, "out", 4) != n:
-            raise ValueError("out must have one row per ray: shape (4 * n_quads, 4)")
-        fn = self._entry("atmo_shade_ray_quads_detail" if self._serves_cloud_detail() else "atmo_shade_ray_quads")
-        stream = _stream_handle(stream, quads)
-        self._bake_if_needed(stream)
-        nf = _to_native_frame(self.make_frame(camera if camera is not None else _WORLD_RAY_SPACE, time))
-        N.check(self._ctx, fn(self._ctx, C.byref(nf), C.c_void_p(quads.data_ptr()), C.c_void_p(out.data_ptr()), n // 4, width, first_quad,
-                              C.c_void_p(stream or 0)))
-        return out
+        return self._shade_batch(4, quads, camera, width, first_quad, out, stream, time)
 
     def camera_ray_quads(self, camera, depth, stream=None):
         """`camera_rays` of the whole viewport gathered into quad order (ray_quads.quad_order) for `shade_ray_quads(width=camera.width)`: a CUDA float32
@@ -858,13 +857,8 @@ class PlanetAtmosphere:
 
         rays = self.camera_rays(camera, depth, stream=stream)
         order = torch.as_tensor(quad_order(camera.width, camera.height), device=rays.device)
-        def gather():
+        with _on_stream(stream, depth.device)[1]:   # the gather behind the dump, on its stream
             return torch.where((order >= 0).unsqueeze(1), rays[order.clamp(min=0)], torch.zeros((), dtype=rays.dtype, device=rays.device)).contiguous()
-
-        if stream is None:   # torch's current stream: where camera_rays enqueued
-            return gather()
-        with torch.cuda.stream(torch.cuda.ExternalStream(_stream_handle(stream, depth), device=depth.device)):   # the gather behind the dump, on its stream
-            return gather()
 
     # ---- lens rays: panorama, fisheye, octahedral map, cube face (include/atmo_lens.h) ---------------------------------------------
     def lens_rays(self, lens, distance=None, quads: bool = False, tile_index: bool = False, stream=None):
@@ -880,8 +874,7 @@ class PlanetAtmosphere:
             raise ValueError("the tile index is row-major only")
         pitch = 0
         if distance is not None:
-            if not (isinstance(distance, torch.Tensor) and distance.is_cuda and distance.dtype == torch.float32):
-                raise TypeError("distance must be a CUDA float32 tensor")
+            _check_kind(distance, "distance must be a CUDA float32 tensor", contiguous=False)
             if distance.dim() != 2 or distance.shape[0] != lens.height or distance.shape[1] < lens.width or distance.stride(1) != 1 or (
                     lens.height > 1 and distance.stride(0) < lens.width):
                 raise ValueError("distance must have shape (lens.height, >= lens.width) with contiguous rows")
@@ -891,9 +884,8 @@ class PlanetAtmosphere:
         n_rays, n_index = C.c_uint32(0), C.c_uint32(0)
         N.check(self._ctx, counts(C.byref(nl), flags, C.byref(n_rays), C.byref(n_index)))
         device = distance.device if distance is not None else torch.device("cuda", self._device)
-        handle = torch.cuda.current_stream(device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
-        # as ray_order: what is allocated here belongs to the call's stream
-        with contextlib.nullcontext() if stream is None else torch.cuda.stream(torch.cuda.ExternalStream(handle, device=device)):
+        handle, on_stream = _on_stream(stream, device)
+        with on_stream:
             rays = torch.empty((n_rays.value, 8), dtype=torch.float32, device=device)
             index = torch.empty((n_index.value,), dtype=torch.int32, device=device) if tile_index else None
         N.check(self._ctx, fn(self._ctx, C.byref(nl), flags, C.c_void_p(distance.data_ptr()) if distance is not None else None, pitch,
@@ -925,14 +917,12 @@ class PlanetAtmosphere:
         y0, y1 = lens.rows
         rows, w = y1 - y0, lens.width
         if out is not None:
-            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()):
-                raise TypeError("out must be a contiguous CUDA float32 tensor")
+            _check_kind(out, "out must be a contiguous CUDA float32 tensor")
             if tuple(out.shape) != (rows, w, 4):
                 raise ValueError(f"out must have shape ({rows}, {w}, 4)")
         if rows == 0:
             return out if out is not None else torch.zeros((0, w, 4), dtype=torch.float32, device=torch.device("cuda", self._device))
-        handle = None if stream is None else getattr(stream, "cuda_stream", stream)
-        with contextlib.nullcontext() if stream is None else torch.cuda.stream(torch.cuda.ExternalStream(handle, device=torch.device("cuda", self._device))):
+        with _on_stream(stream, torch.device("cuda", self._device))[1]:   # the gather and the zeroed image beside the two calls, which enter it again
             if quads:
                 rays = self.lens_rays(lens, distance=distance, quads=True, stream=stream)
                 shaded = self.shade_ray_quads(rays, camera, width=w, first_quad=(y0 // 2) * ((w + 1) // 2), stream=stream, time=time)
@@ -1249,12 +1239,17 @@ class _WorldRaySpace:
 _WORLD_RAY_SPACE = _WorldRaySpace()
 
 
-def _check_rays(t, what: str, cols: int) -> int:
-    """`what` is a contiguous CUDA float32 tensor of shape (n, cols): TypeError for its kind, ValueError for its shape.  Returns n."""
+def _check_kind(t, message: str, dtype: str = "float32", contiguous: bool = True) -> None:
+    """THE kind test of a tensor argument: a CUDA tensor of torch's `dtype`, contiguous where asked; TypeError(`message`, the site's own) otherwise."""
     import torch
 
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise TypeError(f"{what} must be a contiguous CUDA float32 tensor")
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == getattr(torch, dtype) and (not contiguous or t.is_contiguous())):
+        raise TypeError(message)
+
+
+def _check_rays(t, what: str, cols: int) -> int:
+    """`what` is a contiguous CUDA float32 tensor of shape (n, cols): TypeError for its kind, ValueError for its shape.  Returns n."""
+    _check_kind(t, f"{what} must be a contiguous CUDA float32 tensor")
     if t.dim() != 2 or t.shape[1] != cols:
         raise ValueError(f"{what} must have shape (n, {cols})")
     return int(t.shape[0])
@@ -1262,33 +1257,38 @@ def _check_rays(t, what: str, cols: int) -> int:
 
 def _check_index(t) -> int:
     """`index` is a contiguous CUDA int32 tensor of shape (m,): TypeError for its kind, ValueError for its shape.  Returns m."""
-    import torch
-
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
-        raise TypeError("index must be a contiguous CUDA int32 tensor")
+    _check_kind(t, "index must be a contiguous CUDA int32 tensor", "int32")
     if t.dim() != 1:
         raise ValueError("index must have shape (m,)")
     return int(t.shape[0])
 
 
-def _stream_handle(stream, tensor) -> int:
-    """The hipStream_t behind a draw's `stream` argument: a torch stream's, a raw handle as it is, None = torch's current stream on the tensor's device."""
+def _stream_handle(stream, where) -> int:
+    """The hipStream_t behind a draw's `stream` argument: a torch stream's, a raw handle as it is, None = torch's current stream on the device of `where`,
+    a tensor or a device."""
     if stream is None:
         import torch
 
-        return torch.cuda.current_stream(tensor.device).cuda_stream
+        return torch.cuda.current_stream(getattr(where, "device", where)).cuda_stream
     return getattr(stream, "cuda_stream", stream)
+
+
+def _on_stream(stream, device):
+    """(`_stream_handle`'s handle, the context in which a call allocates): torch's allocator reuses a tensor's memory in the order of the stream that was
+    current when it was allocated, so the scratch and the results of a call on the caller's stream are allocated with that stream current.  None is
+    torch's current stream already: a null context."""
+    import torch
+
+    handle = _stream_handle(stream, device)
+    return handle, contextlib.nullcontext() if stream is None else torch.cuda.stream(torch.cuda.ExternalStream(handle, device=device))
 
 
 def _check_depth(depth, camera, prefix: str = "", split: bool = False):
     """A depth buffer is a contiguous CUDA float32 (viewport_h, viewport_w) tensor.  split: `render` and the view batches raise TypeError for the tensor's
     kind and ValueError for its shape; the other single draws raise one TypeError that names both (kept as it was: NOTES.md)."""
-    import torch
-
     kind = "depth must be a contiguous CUDA float32 tensor"
     both = kind + " of shape (viewport_h, viewport_w)"
-    if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()):
-        raise TypeError(prefix + (kind if split else both))
+    _check_kind(depth, prefix + (kind if split else both))
     if tuple(depth.shape) != (camera.height, camera.width):
         raise ValueError(prefix + "depth must have shape (viewport_h, viewport_w)") if split else TypeError(prefix + both)
 

@@ -94,6 +94,17 @@ class Recorder:
         return [(name, _decode(name, args)) for name, args in self.calls if name != "atmo_destroy"]
 
 
+def library_without(*names):
+    """A Recorder that stands for a library without the symbols `names`: an older build, which the optional headers' entry points are detected against."""
+    class Old(Recorder):
+        def __getattr__(self, name):
+            if name in names:
+                raise AttributeError(name)
+            return super().__getattr__(name)
+
+    return Old()
+
+
 def _by_value(a):
     if isinstance(a, (C.c_void_p, C.c_float)):
         return a.value or 0

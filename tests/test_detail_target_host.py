@@ -400,16 +400,10 @@ def test_with_it_off_or_without_clouds_the_old_entry_points_serve():
 
 
 def test_a_library_without_the_symbols_says_so():
-    class Old(B.Recorder):
-        def __getattr__(self, name):
-            if name in NAMES:
-                raise AttributeError(name)
-            return super().__getattr__(name)
-
     cam = B._cam()
     depth = B._depth(cam)
     h, w = cam.height, cam.width
-    node = _detail_node(lib=Old())
+    node = _detail_node(lib=B.library_without(*NAMES))
     with pytest.raises(RuntimeError, match=r"atmo_render_detail_target \(include/atmo_detail_target.h\)"):
         node.render(cam, depth, B._fake((h, w, 4), torch.float16), stream=B.STREAM)
     with pytest.raises(RuntimeError, match=r"atmo_render_views_detail_target \(include/atmo_detail_target.h\)"):
@@ -417,6 +411,6 @@ def test_a_library_without_the_symbols_says_so():
     assert _calls(node) == []
     node.render(cam, depth, B._fake((h, w, 4)), stream=B.STREAM)          # float / float needs no new symbol
     assert [c[0] for c in _calls(node)] == ["atmo_render"]
-    for node in (_detail_node(on=False, lib=Old()), _detail_node("planet_atmosphere_no_clouds", lib=Old())):
+    for node in (_detail_node(on=False, lib=B.library_without(*NAMES)), _detail_node("planet_atmosphere_no_clouds", lib=B.library_without(*NAMES))):
         node.render(cam, depth, B._fake((h, w, 4), torch.float16), stream=B.STREAM)
         assert [c[0] for c in _calls(node)] == ["atmo_render_target"]

@@ -282,21 +282,15 @@ def test_with_it_off_or_without_clouds_the_old_entry_points_serve():
 
 
 def test_a_library_without_the_symbols_says_so():
-    class Old(B.Recorder):
-        def __getattr__(self, name):
-            if name in NAMES:
-                raise AttributeError(name)
-            return super().__getattr__(name)
-
     cam = B._cam()
     rays, out = B._fake((8, 8)), B._fake((8, 4))
-    node = _detail_node(lib=Old())
+    node = _detail_node(lib=B.library_without(*NAMES))
     with pytest.raises(RuntimeError, match=r"atmo_shade_rays_detail \(include/atmo_ray_detail.h\)"):
         node.shade_rays(rays, cam, out=out, stream=B.STREAM)
     with pytest.raises(RuntimeError, match=r"atmo_shade_ray_quads_detail \(include/atmo_ray_detail.h\)"):
         node.shade_ray_quads(rays, cam, width=4, out=out, stream=B.STREAM)
     assert _calls(node) == []
     # with the switch off, or on a node without clouds, such a library serves as before
-    for node in (_detail_node(on=False, lib=Old()), _detail_node("planet_atmosphere_no_clouds", lib=Old())):
+    for node in (_detail_node(on=False, lib=B.library_without(*NAMES)), _detail_node("planet_atmosphere_no_clouds", lib=B.library_without(*NAMES))):
         assert node.shade_rays(rays, cam, out=out, stream=B.STREAM) is out and node.shade_ray_quads(rays, cam, width=4, out=out, stream=B.STREAM) is out
         assert [name for name, _ in _calls(node)] == ["atmo_shade_rays", "atmo_shade_ray_quads"]

@@ -374,12 +374,6 @@ def test_ray_list_binding_without_a_device(monkeypatch):
     with pytest.raises(ValueError, match="out must have one row per ray"):
         node.ray_list(rays, cull=True, out=B._fake((69, 4)), stream=B.STREAM)
 
-    class Old(B.Recorder):
-        def __getattr__(self, name):
-            if name in ("atmo_ray_list", "atmo_ray_list_scratch_bytes"):
-                raise AttributeError(name)
-            return super().__getattr__(name)
-
-    node = B._node(lib=Old())
+    node = B._node(lib=B.library_without("atmo_ray_list", "atmo_ray_list_scratch_bytes"))
     with pytest.raises(RuntimeError, match=r"atmo_ray_list \(include/atmo_ray_list.h\)"), B._AllocateAsCuda():
         node.ray_list(rays, stream=B.STREAM)

@@ -288,13 +288,7 @@ def test_shade_rays_with_an_index_reaches_the_indexed_entry_point():
     with pytest.raises(ValueError, match=r"index must have shape \(m,\)"):
         node.shade_rays(rays, cam, out=out, stream=B.STREAM, index=B._fake((5, 1), torch.int32))
 
-    class Old(B.Recorder):
-        def __getattr__(self, name):
-            if name in ("atmo_shade_rays_indexed", "atmo_ray_order", "atmo_ray_order_scratch_bytes"):
-                raise AttributeError(name)
-            return super().__getattr__(name)
-
-    node = B._node(lib=Old())
+    node = B._node(lib=B.library_without("atmo_shade_rays_indexed", "atmo_ray_order", "atmo_ray_order_scratch_bytes"))
     with pytest.raises(RuntimeError, match=r"atmo_shade_rays_indexed \(include/atmo_ray_order.h\)"):
         node.shade_rays(rays, cam, out=out, stream=B.STREAM, index=index)
     with pytest.raises(RuntimeError, match=r"atmo_ray_order \(include/atmo_ray_order.h\)"), B._AllocateAsCuda():

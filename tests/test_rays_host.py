@@ -47,6 +47,25 @@ def test_binding_exposes_the_rays_header():
     assert lib.atmo_abi_version() == N.ABI_VERSION == 5
 
 
+def test_every_header_s_signatures_are_its_tuple_and_every_symbol_is_bound():
+    """N.HEADERS is the one table of signatures: a block a header, each block's names its `*_SYMBOLS` tuple in the tuple's order, the nineteen tuples
+    pairwise disjoint, and after load() no name of any tuple is left with ctypes' default signature (argtypes None: an int for every pointer)."""
+    N, lib = _lib()
+    tuples = {k: v for k, v in vars(N).items() if k.endswith("_SYMBOLS") and k != "EXPORTED_SYMBOLS"}
+    assert len(tuples) == len(N.HEADERS) == 19 and all(_functions(h) >= set(block[0]) for h, block in N.HEADERS.items())      # under its own header's name
+    assert sorted(map(id, tuples.values())) == sorted(id(symbols) for symbols, _, _, _ in N.HEADERS.values())      # every tuple heads one block
+    for header, (symbols, required, suffix, signatures) in N.HEADERS.items():
+        assert tuple(signatures) == symbols and len(set(symbols)) == len(symbols), header
+        assert required or header in N.optional_headers() and N.optional_headers()[header] == (symbols, suffix, signatures), header
+        for name in symbols:
+            assert getattr(lib, name).argtypes is not None and len(getattr(lib, name).argtypes) == len(signatures[name][1]), name
+    names = [name for symbols in tuples.values() for name in symbols]
+    assert len(names) == len(set(names)) == 88      # pairwise disjoint
+    assert [h for h, block in N.HEADERS.items() if not block[1]] == list(N.optional_headers()) == [
+        "atmo_cloud_detail.h", "atmo_rays.h", "atmo_ray_quads.h", "atmo_ray_order.h", "atmo_ray_list.h", "atmo_ray_detail.h", "atmo_detail_target.h",
+        "atmo_lens.h"]
+
+
 def test_an_atmo_ray_is_32_bytes_on_both_sides(tmp_path):
     N, _ = _lib()
     assert C.sizeof(N.AtmoRay) == 32
@@ -267,13 +286,7 @@ def test_bad_tensors_raise_before_anything_reaches_the_library():
 
 
 def test_a_library_without_the_symbols_says_so():
-    class Old(B.Recorder):
-        def __getattr__(self, name):
-            if name in ("atmo_shade_rays", "atmo_debug_frame_rays"):
-                raise AttributeError(name)
-            return super().__getattr__(name)
-
-    node, cam = B._node(lib=Old()), B._cam()
+    node, cam = B._node(lib=B.library_without("atmo_shade_rays", "atmo_debug_frame_rays")), B._cam()
     with pytest.raises(RuntimeError, match="atmo_shade_rays"):
         node.shade_rays(B._fake((4, 8)), cam, out=B._fake((4, 4)), stream=B.STREAM)
     with pytest.raises(RuntimeError, match="atmo_debug_frame_rays"), B._AllocateAsCuda():
