@@ -2198,6 +2198,24 @@ __device__ __forceinline__ void store_target_zero_all_rt(const int format, void 
     else store_target_zero_rt(format, p);
 }
 
+// The 16-byte store of a float frame's pixel: every store of shade_pixel through `out` in the pixel kernels (the RAYS kernels' stores and the packed- and
+// depth-target kernels' stay plain).  A draw streams its frame through the eight 4 MB L2s once and never reads it again, and what is still dirty there when
+// the last wave ends -- 12 MB of a 1920x1080 frame -- is written back before the next draw may start.  `sc1` writes the line through and drops it: nothing
+// is left for the kernel's end (profiles/frame_store/README.md: -2.1 % on the headline draw, the same 1.4 - 2.0 us at every frame size).  The cloudless
+// LUT-light kernels (lut32, shipped8: a third of their time is the store stream itself) lose 2.6 - 2.9 % with it and keep the plain store.  The asm form ends
+// in the wait state a store of more than 8 bytes needs before its data registers are rewritten; it sits behind the view loop and moves no ATMO_LOOP_PAD*.
+template <int FLAGS>
+__device__ __forceinline__ void store_frame(float4 *p, const float4 &v) {
+    constexpr bool WRITE_THROUGH = (FLAGS & (KF_LIGHT_DIRECT | KF_CLOUDS)) != 0;
+    if constexpr (WRITE_THROUGH) {
+        typedef float frame_f4 __attribute__((ext_vector_type(4)));
+        const frame_f4 d = {v.x, v.y, v.z, v.w};
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(d) : "memory");
+    } else {
+        *p = v;
+    }
+}
+
 // RAYS (KF_RAYS, atmo_shade_rays_kernel; include/atmo_rays.h): the same shading for a ray that did not come out of a camera matrix.  The mode differs at the
 // function's edges only -- how a ray arrives (thread i of the batch reads ray i of *yc: no pixel, no sure-miss test, no prologue) and where its result goes
 // (yc->out[i], a plain store; zeros for a miss) -- and in the operands the ray's own origin gives the marches (their LANE forms).  Everything between is the
@@ -2359,7 +2377,7 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
             if (rc.store_discards && half == 0 && !helper) {
                 if constexpr (DEPTH) store_target_zero_all_rt(tc->format, tout);
                 else if constexpr (TARGET) store_target_zero_rt(tc->format, tout);
-                else *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                else store_frame<FLAGS>(out, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
             }
             return;
         }
@@ -2442,7 +2460,7 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
         } else if (rc.store_discards && half == 0 && !helper) {
             if constexpr (DEPTH) store_target_zero_all_rt(tc->format, tout);
             else if constexpr (TARGET) store_target_zero_rt(tc->format, tout);
-            else *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            else store_frame<FLAGS>(out, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
         }
         return;
     }
@@ -2591,9 +2609,9 @@ __device__ __forceinline__ void shade_pixel(const RenderConsts &rc, const int ti
         o.y = rgba.y * rgba.w + dst.y * ia;
         o.z = rgba.z * rgba.w + dst.z * ia;
         o.w = rgba.w + dst.w * ia;
-        *out = o;
+        store_frame<FLAGS>(out, o);
     } else {
-        *out = rgba;
+        store_frame<FLAGS>(out, rgba);
     }
 }
 
