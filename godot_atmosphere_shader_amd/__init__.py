@@ -6,6 +6,7 @@ Zylann/godot_atmosphere_shader, behind the reference's `PlanetAtmosphere` / `sha
   depth_formats.py      the depth sources' contract in numpy (include/atmo_depth.h; `depth_source` wraps a renderer's own depth buffer)
   noise_cubemap.py      host-side mirror of addons/zylann.atmosphere/noise_cubemap.gd (generation on the GPU)
   lens.py               lens rays in numpy: panorama, fisheye, octahedral map, cube face (include/atmo_lens.h; `Lens` describes one for `render_lens`)
+  reduced.py            reduced-resolution draws in numpy and the header's ctypes declarations (include/atmo_reduced.h; `PlanetAtmosphere.render_reduced`)
   noise_volume.py       host-side mirror of the demo's NoiseTexture3D: the cloud shape volume, generated on the GPU (include/atmo_noise_volume.h)
   demo.py               the reference's demo scene + named shader configurations (tests, bench.py, smoke())
   scene.py              synthetic inputs (camera, depth, jitter, cloud textures) for tests and bench

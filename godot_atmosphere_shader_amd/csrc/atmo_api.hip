@@ -24,6 +24,7 @@
 #include "../../include/atmo_ray_detail.h"
 #include "../../include/atmo_detail_target.h"
 #include "../../include/atmo_lens.h"
+#include "../../include/atmo_reduced.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -3156,6 +3157,142 @@ int atmo_render_proxy_depth_target(AtmoContext *ctx, const AtmoFrame *frame, con
     DrawSurfaces sf = depth_target_surfaces(depth, target, composite != 0);
     ATMO_TRY(target_check(ctx, "atmo_render_proxy_depth_target", frame, sf));   // (proxy_impl refuses the modes without a proxy kernel: the same set)
     return proxy_impl(ctx, "atmo_render_proxy_depth_target", frame, model_matrix, box_size, sf, stream);
+}
+
+// ---- reduced-resolution draws (include/atmo_reduced.h): depth reduction, atmo_render of the low frame, depth-aware upsample --------------------------
+namespace {
+bool reduced_scale_ok(int scale) { return scale == 2 || scale == 4; }
+// The low frame (atmo_reduced.h, item 2): `frame` with the viewport (low_w, low_h), all of it as the rect, and inv_projection * A -- the product in double,
+// rounded once per element, and the caller's bits where the scale divides both sides.  reduced.py's low_frame is the same arithmetic.
+AtmoFrame reduced_low_frame(const AtmoFrame &frame, int scale, int low_w, int low_h) {
+    AtmoFrame low = frame;
+    low.viewport_w = low_w;
+    low.viewport_h = low_h;
+    low.x0 = 0; low.y0 = 0; low.x1 = low_w; low.y1 = low_h;
+    const double kx = (double)(low_w * scale) / (double)frame.viewport_w, ky = (double)(low_h * scale) / (double)frame.viewport_h;
+    if (kx == 1.0 && ky == 1.0) return low;
+    const float *m = frame.inv_projection_matrix;
+    for (int r = 0; r < 4; ++r) {
+        const double m0 = m[r], m1 = m[4 + r], m3 = m[12 + r];
+        low.inv_projection_matrix[r] = (float)(kx * m0);
+        low.inv_projection_matrix[4 + r] = (float)(ky * m1);
+        low.inv_projection_matrix[12 + r] = (float)((m0 * (kx - 1.0) + m1 * (ky - 1.0)) + m3);
+    }
+    return low;
+}
+// What the two passes read: the frame's rows z and w, the sizes; the caller adds the buffers
+atmo::ReducedConsts reduced_consts(const AtmoFrame &frame, int scale) {
+    atmo::ReducedConsts c = {};
+    const float *m = frame.inv_projection_matrix;
+    for (int k = 0; k < 4; ++k) { c.pz[k] = m[4 * k + 2]; c.pw[k] = m[4 * k + 3]; }
+    c.w = frame.viewport_w;
+    c.h = frame.viewport_h;
+    c.log2s = scale == 2 ? 1 : 2;
+    c.low_w = (c.w + scale - 1) / scale;
+    c.low_h = (c.h + scale - 1) / scale;
+    return c;
+}
+int reduced_whole_viewport(AtmoContext *ctx, const std::string &who, const AtmoFrame *frame) {
+    if (frame->x0 != 0 || frame->y0 != 0 || frame->x1 != frame->viewport_w || frame->y1 != frame->viewport_h)
+        return fail(ctx, ATMO_E_ARG, who + ": the rect must be the whole viewport (a reduced draw has no rects)");
+    return ATMO_OK;
+}
+int reduced_options(AtmoContext *ctx, const std::string &who, const AtmoReduced *opt) {
+    if (!opt) return fail(ctx, ATMO_E_ARG, who + ": null opt");
+    if (!reduced_scale_ok(opt->scale)) return fail(ctx, ATMO_E_ARG, who + ": scale must be 2 or 4, not " + std::to_string(opt->scale));
+    if (!(opt->depth_tolerance >= 0.0f) || !std::isfinite(opt->depth_tolerance)) return fail(ctx, ATMO_E_ARG, who + ": depth_tolerance must be finite and at least 0");
+    return ATMO_OK;
+}
+// The scratch's low depth, padded to whole 16-byte units, in floats
+size_t reduced_depth_floats(int low_w, int low_h) { return ((size_t)low_w * (size_t)low_h + 3) & ~(size_t)3; }
+}  // namespace
+
+int atmo_reduced_size(int viewport_w, int viewport_h, int scale, int *low_w, int *low_h, size_t *scratch_bytes) {
+    if (viewport_w < 1 || viewport_h < 1 || viewport_w > 65536 || viewport_h > 65536 || !reduced_scale_ok(scale)) return ATMO_E_ARG;
+    const int lw = (viewport_w + scale - 1) / scale, lh = (viewport_h + scale - 1) / scale;
+    if (low_w) *low_w = lw;
+    if (low_h) *low_h = lh;
+    if (scratch_bytes) *scratch_bytes = reduced_depth_floats(lw, lh) * sizeof(float) + (size_t)lw * (size_t)lh * 4 * sizeof(float);
+    return ATMO_OK;
+}
+
+int atmo_reduced_depth(AtmoContext *ctx, const AtmoFrame *frame, const AtmoDepth *depth, int scale, float *low_depth_dev, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const std::string who = "atmo_reduced_depth";
+    bool empty = false;
+    ATMO_TRY(check_frame(ctx, who, frame, &empty));
+    if (!reduced_scale_ok(scale)) return fail(ctx, ATMO_E_ARG, who + ": scale must be 2 or 4, not " + std::to_string(scale));
+    ATMO_TRY(reduced_whole_viewport(ctx, who, frame));
+    if (!low_depth_dev) return fail(ctx, ATMO_E_ARG, who + ": null low_depth_dev");
+    if ((reinterpret_cast<uintptr_t>(low_depth_dev) & 3u) != 0) return fail(ctx, ATMO_E_ARG, who + ": low_depth_dev must be 4-byte aligned");
+    atmo::DepthConsts dc = {nullptr, 0, 0};
+    ATMO_TRY(depth_check(ctx, who, depth, frame->viewport_w, frame->viewport_h, &dc));
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    atmo::ReducedConsts c = reduced_consts(*frame, scale);
+    c.low_depth = low_depth_dev;
+    HIP_TRY(ctx, atmo::launch_reduced_pick(c, dc, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+// The checks the upsample and the whole path share, in the header's order: the target (addressed as a composite's: the viewport's rows), the options, the rect
+static int reduced_target_check(AtmoContext *ctx, const char *who, const AtmoFrame *frame, const AtmoReduced *opt, DrawSurfaces &sf) {
+    ATMO_TRY(target_check(ctx, who, frame, sf));
+    ATMO_TRY(reduced_options(ctx, who, opt));
+    return reduced_whole_viewport(ctx, who, frame);
+}
+
+int atmo_reduced_upsample(AtmoContext *ctx, const AtmoFrame *frame, const AtmoDepth *depth, const AtmoReduced *opt, const float *low_depth_dev,
+                          const float *low_rgba_dev, const AtmoTarget *target, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_reduced_upsample";
+    DrawSurfaces sf = depth_target_surfaces(depth, target, true);
+    ATMO_TRY(reduced_target_check(ctx, who, frame, opt, sf));
+    if (!low_depth_dev || !low_rgba_dev) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null low_depth_dev or low_rgba_dev");
+    if ((reinterpret_cast<uintptr_t>(low_depth_dev) & 3u) != 0 || (reinterpret_cast<uintptr_t>(low_rgba_dev) & 15u) != 0)
+        return fail(ctx, ATMO_E_ARG, std::string(who) + ": low_depth_dev must be 4-byte aligned and low_rgba_dev 16-byte aligned");
+    ATMO_TRY(check_surfaces(ctx, who, frame, sf));
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, std::string(who) + ": a host-only context has no device to run on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    atmo::ReducedConsts c = reduced_consts(*frame, opt->scale);
+    c.tol = opt->depth_tolerance;
+    c.composite = composite != 0;
+    c.low_depth = const_cast<float *>(low_depth_dev);   // (read only by this pass)
+    c.low_rgba = (const float4 *)low_rgba_dev;
+    HIP_TRY(ctx, atmo::launch_reduced_upsample(c, sf.dc, sf.tc, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+int atmo_render_reduced_target(AtmoContext *ctx, const AtmoFrame *frame, const AtmoDepth *depth, const AtmoReduced *opt, void *scratch_dev,
+                               const AtmoTarget *target, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_reduced_target";
+    DrawSurfaces sf = depth_target_surfaces(depth, target, true);
+    ATMO_TRY(reduced_target_check(ctx, who, frame, opt, sf));
+    if (!scratch_dev) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null scratch_dev");
+    if ((reinterpret_cast<uintptr_t>(scratch_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, std::string(who) + ": scratch_dev must be 16-byte aligned");
+    ATMO_TRY(check_surfaces(ctx, who, frame, sf));
+    // what atmo_render would refuse the low frame for, in front of the first kernel: nothing is enqueued by a refused call
+    atmo::ReducedConsts c = reduced_consts(*frame, opt->scale);
+    const AtmoFrame low = reduced_low_frame(*frame, opt->scale, c.low_w, c.low_h);
+    if (cloud_detail_on(ctx)) ATMO_TRY(cloud_detail_family(ctx, who, &low));
+    {
+        int flags = 0, split = 1;
+        bool lod = false;
+        ATMO_TRY(draw_family(ctx, &low, &flags, &split, &lod));
+    }
+    ATMO_TRY(check_draw_textures(ctx, who));
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, std::string(who) + ": a host-only context has no device to draw on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    float *low_depth = (float *)scratch_dev, *low_rgba = low_depth + reduced_depth_floats(c.low_w, c.low_h);
+    c.tol = opt->depth_tolerance;
+    c.composite = composite != 0;
+    c.low_depth = low_depth;
+    c.low_rgba = (const float4 *)low_rgba;
+    HIP_TRY(ctx, atmo::launch_reduced_pick(c, sf.dc, (hipStream_t)stream));
+    ATMO_TRY(render_impl(ctx, &low, float_surfaces(low_depth, low_rgba, false), WHOLE_GRID, stream));   // atmo_render of the low frame
+    HIP_TRY(ctx, atmo::launch_reduced_upsample(c, sf.dc, sf.tc, (hipStream_t)stream));
+    return ATMO_OK;
 }
 
 // atmo_debug.h: the kernels' depth decode on a caller-supplied DEVICE array

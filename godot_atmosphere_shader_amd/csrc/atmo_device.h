@@ -413,5 +413,20 @@ hipError_t launch_log2_cr(const float *x_dev, float *out_dev, int n, hipStream_t
 hipError_t launch_light_probe(const float *pos, const float *dir, int n, float planet_radius, float atmosphere_height, float density,
                               int light_steps, float *out, hipStream_t stream);
 hipError_t launch_selftest(uint32_t first_bits, uint32_t count, float c, float rc, unsigned int *mismatch_dev, hipStream_t stream);
+// Reduced-resolution draws (include/atmo_reduced.h states the arithmetic): what the two passes around the low draw read.  The viewport is w x h, the low
+// image low_w x low_h = ceil(w / s) x ceil(h / s), s = 1 << log2s (2 or 4).  pz / pw: rows 2 and 3 of the frame's inv_projection (m[2], m[6], m[10], m[14]
+// and m[3], m[7], m[11], m[15]).
+struct ReducedConsts {
+    float pz[4], pw[4];
+    int32_t w, h, low_w, low_h, log2s;
+    float tol;                // AtmoReduced::depth_tolerance (the upsample)
+    int32_t composite;        // the upsample blends into the target and leaves pixels without alpha alone
+    float *low_depth;         // low_w * low_h floats, tight: written by the reduction, read by the upsample
+    const float4 *low_rgba;   // low_w * low_h float4, tight (the upsample)
+};
+// atmo_reduced_pick_kernel: one lane per low texel, the block scanned row-major
+hipError_t launch_reduced_pick(const ReducedConsts &dc, const DepthConsts &depth, hipStream_t stream);
+// atmo_reduced_upsample_kernel: one lane per pixel of the viewport, 64 consecutive pixels of a row per wave; every target format
+hipError_t launch_reduced_upsample(const ReducedConsts &dc, const DepthConsts &depth, const TargetConsts &tc, hipStream_t stream);
 
 }  // namespace atmo

@@ -4632,4 +4632,131 @@ hipError_t launch_lens_rays(int kind, bool quads, const LensConsts &lc, hipStrea
     }
 }
 
+// ---- reduced-resolution draws (include/atmo_reduced.h states the arithmetic item by item; reduced.py restates it in numpy) -------------------------
+// The two passes around a low-resolution draw: the depth buffer reduced to one texel per s x s block, and the low frame put into the full-resolution target,
+// each low neighbour weighed only where its depth agrees with the pixel's own.  Both are held to the numpy statement bit for bit, so nothing in them is
+// contracted and every quotient is IEEE.  Kernels of their own name (no older kernel's name is a substring of theirs, nor the reverse), defined behind
+// everything else, so that every older kernel keeps its code and its place in the code object.  Lane map of both: a workgroup is 64 x 4 texels of the image
+// it writes, a wave 64 consecutive texels of one row -- the 16 / 8 / 4-byte stores of a wave are one contiguous run.  No LDS: the low frame is 1 / s^2 of the
+// target and is re-read through the caches.
+constexpr int REDUCED_BLOCK_W = 64, REDUCED_BLOCK_H = 4;
+// the draws' NDC of a pixel centre: 2 ((p + 0.5) / size) - 1, the quotient IEEE
+__device__ __forceinline__ float reduced_ndc(const int p, const int size) {
+#pragma clang fp contract(off)
+    return ieee_div((float)p + 0.5f, (float)size) * 2.0f - 1.0f;
+}
+// the reciprocal eye depth w / z of depth d through a pixel whose share of the two rows is zb = m[2] nx + m[6] ny, wb = m[3] nx + m[7] ny
+__device__ __forceinline__ float reduced_eye_q(const ReducedConsts &c, const float zb, const float wb, const float d) {
+#pragma clang fp contract(off)
+    const float z = (zb + c.pz[2] * d) + c.pz[3];
+    const float w = (wb + c.pw[2] * d) + c.pw[3];
+    return ieee_div(w, z);
+}
+// Step 4: low texel (i, j) = the decoded depth of the farthest (i + j even) or nearest (odd) texel of its block; strict comparisons, the first texel wins ties
+// and a NaN never replaces the choice
+__global__ __launch_bounds__(REDUCED_BLOCK_W *REDUCED_BLOCK_H) void atmo_reduced_pick_kernel(const ReducedConsts c, const DepthConsts dc) {
+#pragma clang fp contract(off)
+    const int i = (int)blockIdx.x * REDUCED_BLOCK_W + (int)threadIdx.x, j = (int)blockIdx.y * REDUCED_BLOCK_H + (int)threadIdx.y;
+    if (i >= c.low_w || j >= c.low_h) return;
+    const int s = 1 << c.log2s;
+    const int x0 = i << c.log2s, y0 = j << c.log2s, x1 = min(x0 + s, c.w), y1 = min(y0 + s, c.h);   // the texels of the block that exist: at least one
+    const bool nearest = ((i + j) & 1) != 0;
+    float best_d = 0.0f, best_q = 0.0f;
+    bool first = true;
+    for (int y = y0; y < y1; ++y) {
+        const float ny = reduced_ndc(y, c.h);
+        for (int x = x0; x < x1; ++x) {
+            const float nx = reduced_ndc(x, c.w);
+            const float d = load_depth(dc, x, y);
+            const float aq = fabsf(reduced_eye_q(c, c.pz[0] * nx + c.pz[1] * ny, c.pw[0] * nx + c.pw[1] * ny, d));
+            const bool take = first || (nearest ? aq > best_q : aq < best_q);
+            best_d = take ? d : best_d;
+            best_q = take ? aq : best_q;
+            first = false;
+        }
+    }
+    c.low_depth[(size_t)j * (size_t)c.low_w + (size_t)i] = best_d;
+}
+hipError_t launch_reduced_pick(const ReducedConsts &c, const DepthConsts &depth, hipStream_t stream) {
+    if (c.low_depth == nullptr || depth.texels == nullptr || depth_texel_bytes(depth.format) == 0 || (c.log2s != 1 && c.log2s != 2) || c.w < 1 || c.h < 1 ||
+        c.low_w != ((c.w - 1) >> c.log2s) + 1 || c.low_h != ((c.h - 1) >> c.log2s) + 1)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((c.low_w + REDUCED_BLOCK_W - 1) / REDUCED_BLOCK_W), (unsigned)((c.low_h + REDUCED_BLOCK_H - 1) / REDUCED_BLOCK_H));
+    hipLaunchKernelGGL(atmo_reduced_pick_kernel, grid, dim3(REDUCED_BLOCK_W, REDUCED_BLOCK_H), 0, stream, c, depth);
+    return hipGetLastError();
+}
+// Steps 5 and 6: pixel (x, y) of the viewport from its four low neighbours, through the store of the KF_DEPTH kernels (every target format, a uniform field)
+__global__ __launch_bounds__(REDUCED_BLOCK_W *REDUCED_BLOCK_H) void atmo_reduced_upsample_kernel(const ReducedConsts c, const DepthConsts dc,
+                                                                                                  const TargetConsts tc) {
+#pragma clang fp contract(off)
+    const int x = (int)blockIdx.x * REDUCED_BLOCK_W + (int)threadIdx.x, y = (int)blockIdx.y * REDUCED_BLOCK_H + (int)threadIdx.y;
+    if (x >= c.w || y >= c.h) return;
+    // t = 2 p + 1 - s is odd, so the fraction (t mod 2 s) / 2 s is never 0: all four weights are positive dyadics, and their sum is 1 exactly
+    const int s = 1 << c.log2s, sh = c.log2s + 1;
+    const int tx = 2 * x + 1 - s, ty = 2 * y + 1 - s;
+    const int i0 = tx >> sh, j0 = ty >> sh;   // floor: -1 along the image's first s / 2 pixels
+    const float inv2s = c.log2s == 1 ? 0.25f : 0.125f;
+    const float fx = (float)(tx - i0 * 2 * s) * inv2s, fy = (float)(ty - j0 * 2 * s) * inv2s;
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+    const float wgt[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
+    const int ia = min(max(i0, 0), c.low_w - 1), ib = min(max(i0 + 1, 0), c.low_w - 1);
+    const int ja = min(max(j0, 0), c.low_h - 1), jb = min(max(j0 + 1, 0), c.low_h - 1);
+    const size_t at[4] = {(size_t)ja * (size_t)c.low_w + (size_t)ia, (size_t)ja * (size_t)c.low_w + (size_t)ib,
+                          (size_t)jb * (size_t)c.low_w + (size_t)ia, (size_t)jb * (size_t)c.low_w + (size_t)ib};
+    const float nx = reduced_ndc(x, c.w), ny = reduced_ndc(y, c.h);
+    const float zb = c.pz[0] * nx + c.pz[1] * ny, wb = c.pw[0] * nx + c.pw[1] * ny;
+    const float q0 = reduced_eye_q(c, zb, wb, load_depth(dc, x, y));
+    float diff[4];
+    bool valid[4];
+    float4 low[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        low[k] = c.low_rgba[at[k]];
+        const float qk = reduced_eye_q(c, zb, wb, c.low_depth[at[k]]);
+        diff[k] = fabsf(q0 - qk);
+        valid[k] = diff[k] <= c.tol * fmaxf(fabsf(q0), fabsf(qk));
+    }
+    float w4[4] = {wgt[0], wgt[1], wgt[2], wgt[3]};
+    if (!(valid[0] || valid[1] || valid[2] || valid[3])) {   // the closest in depth alone, with weight 1
+        int best = 0;
+#pragma unroll
+        for (int k = 1; k < 4; ++k) best = diff[k] < diff[best] ? k : best;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            valid[k] = k == best;
+            w4[k] = 1.0f;
+        }
+    }
+    float wsum = 0.0f, a = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float wk = w4[k], ak = low[k].w;
+        wsum = valid[k] ? wsum + wk : wsum;
+        a = valid[k] ? a + wk * ak : a;
+        cr = valid[k] ? cr + wk * (ak * low[k].x) : cr;
+        cg = valid[k] ? cg + wk * (ak * low[k].y) : cg;
+        cb = valid[k] ? cb + wk * (ak * low[k].z) : cb;
+    }
+    if (wsum != 1.0f) {
+        a = ieee_div(a, wsum);
+        cr = ieee_div(cr, wsum);
+        cg = ieee_div(cg, wsum);
+        cb = ieee_div(cb, wsum);
+    }
+    const bool has = a > 0.0f;
+    if (c.composite != 0 && !has) return;   // a composite leaves the pixel's bytes alone
+    const float4 px = make_float4(has ? ieee_div(cr, a) : 0.0f, has ? ieee_div(cg, a) : 0.0f, has ? ieee_div(cb, a) : 0.0f, a);
+    void *p = (char *)tc.pixels + (size_t)y * (size_t)tc.pitch_bytes + ((size_t)x << target_pixel_shift_all(tc.format));
+    store_target_all_rt(tc.format, p, px, c.composite != 0);
+}
+hipError_t launch_reduced_upsample(const ReducedConsts &c, const DepthConsts &depth, const TargetConsts &tc, hipStream_t stream) {
+    if (c.low_depth == nullptr || c.low_rgba == nullptr || depth.texels == nullptr || depth_texel_bytes(depth.format) == 0 || tc.pixels == nullptr ||
+        (c.log2s != 1 && c.log2s != 2) || c.w < 1 || c.h < 1 || c.low_w != ((c.w - 1) >> c.log2s) + 1 || c.low_h != ((c.h - 1) >> c.log2s) + 1 ||
+        (long long)tc.pitch_bytes < ((long long)c.w << (tc.format == TF_RGBA32F ? 4 : tc.format == TF_RGBA16F ? 3 : 2)))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((c.w + REDUCED_BLOCK_W - 1) / REDUCED_BLOCK_W), (unsigned)((c.h + REDUCED_BLOCK_H - 1) / REDUCED_BLOCK_H));
+    hipLaunchKernelGGL(atmo_reduced_upsample_kernel, grid, dim3(REDUCED_BLOCK_W, REDUCED_BLOCK_H), 0, stream, c, depth, tc);
+    return hipGetLastError();
+}
+
 }  // namespace atmo

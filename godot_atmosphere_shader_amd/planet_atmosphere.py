@@ -665,9 +665,11 @@ class PlanetAtmosphere:
         RGBA8_UNORM's (`_colour_target`).  A name that contradicts the tensor's dtype raises ValueError."""
         return self._render_one(camera, depth, out, rect, stream, time, target, False, None, split_depth_errors=True)
 
-    def _render_one(self, camera, depth, colour, rect, stream, time, target, composite, proxy, split_depth_errors=False):
+    def _render_one(self, camera, depth, colour, rect, stream, time, target, composite, proxy, split_depth_errors=False, reduced=None):
         """The four single draws: `composite` blends into the whole viewport's buffer, else `colour` holds the rect (allocated when None);
-        `proxy` is None or `_proxy`'s (model, box_size): zero-filled allocations, the proxy entry points."""
+        `proxy` is None or `_proxy`'s (model, box_size): zero-filled allocations, the proxy entry points.  `reduced` is None or `render_reduced`'s
+        (entry point, what makes its (&options, scratch) of a camera and a device): atmo_render_reduced_target takes the two behind the depth, and a
+        depth source and a target structure always."""
         frame = self.make_frame(camera, time, rect)
         x0, y0, x1, y1 = frame["rect"]
         src = depth.native(camera) if isinstance(depth, DepthSource) else None   # (a plain tensor: today's path, checks and messages)
@@ -678,11 +680,16 @@ class PlanetAtmosphere:
             colour = _new_target(rows, cols, target, depth.device, zero=proxy is not None)
         # a contiguous float32 tensor (None), or the N.AtmoTarget of a float16 / uint8 / pitched one
         tgt = _colour_target(colour, rows, cols, "scene_rgba" if composite else "out", target)
-        if src is not None and tgt is None:   # the depth-source entry points take every colour tensor as an N.AtmoTarget
+        if (src is not None or reduced is not None) and tgt is None:   # the depth-source entry points take every colour tensor as an N.AtmoTarget
             tgt = N.AtmoTarget(colour.data_ptr(), N.TARGET_RGBA32F, 0)
         # cloud detail into a packed or pitched colour tensor, or from a depth source (include/atmo_detail_target.h): one entry point, which takes both as
-        # structures -- a plain depth tensor is a tight D32 source.  Float colour with float depth stays atmo_render; the proxy draws have no detail form
-        fn = self._entry("atmo_render_detail_target") if proxy is None and tgt is not None and self._serves_cloud_detail() else None
+        # structures -- a plain depth tensor is a tight D32 source.  Float colour with float depth stays atmo_render; the proxy draws have no detail form.
+        # A reduced draw (include/atmo_reduced.h) takes the same two structures, with cloud detail or without: its low draw is atmo_render's
+        fn = None
+        if reduced is not None:
+            fn = reduced[0]
+        elif proxy is None and tgt is not None and self._serves_cloud_detail():
+            fn = self._entry("atmo_render_detail_target")
         if fn is not None and src is None:
             src = N.AtmoDepth(depth.data_ptr(), N.DEPTH_D32_SFLOAT, 0)
         stream = _stream_handle(stream, depth)
@@ -693,8 +700,54 @@ class PlanetAtmosphere:
         box = () if proxy is None else (proxy[0], C.c_float(proxy[1]))
         where = (C.c_void_p(colour.data_ptr()),) if tgt is None else (C.byref(tgt), int(composite))
         depth_arg = C.c_void_p(depth.data_ptr()) if src is None else C.byref(src)
-        N.check(self._ctx, fn(self._ctx, C.byref(nf), *box, depth_arg, *where, C.c_void_p(stream or 0)))
+        extra = () if reduced is None else reduced[1](camera, depth.device)   # (&options, scratch) behind the depth
+        N.check(self._ctx, fn(self._ctx, C.byref(nf), *box, depth_arg, *extra, *where, C.c_void_p(stream or 0)))
         return colour
+
+    # ---- reduced-resolution draws (include/atmo_reduced.h) -------------------------------------------------------------------------
+    def render_reduced(self, camera, depth, target=None, out=None, *, scale: int = 2, depth_tolerance: float = 0.1, composite: bool = False,
+                       scratch=None, stream=None, time: float = 0.0):
+        """One draw of the whole viewport at 1 / `scale` (2 or 4) of the resolution along each axis, upsampled into the full-resolution colour buffer by a
+        filter that respects depth edges (atmo_render_reduced_target; include/atmo_reduced.h states every step, godot_atmosphere_shader_amd.reduced
+        restates it in numpy).  `depth` and `out` / `target` are `render`'s: a float32 depth tensor or a `depth_source(...)`; a float32, float16 or uint8
+        (H, W, 4) tensor whose rows may be further apart than a row, `target` naming a packed format.  composite=False: `out` is written whole (allocated
+        when None).  composite=True: `out` is the scene colour buffer, blended in place; pixels the atmosphere does not cover keep their bytes.
+        `depth_tolerance`: the relative difference of reciprocal eye depth up to which a low-resolution neighbour is averaged into a pixel.
+        `scratch`: a contiguous CUDA tensor of at least `reduced.scratch_layout(W, H, scale)[1]` bytes, 16-byte aligned, for the low depth and the low
+        frame; None: one is allocated on the first call and kept for the later ones (calls that share it must be ordered on one stream, and a call
+        captured into a graph should be given its own: the node's is replaced when a later draw needs a larger one).
+        Returns `out`."""
+        from . import reduced as R
+
+        if scale not in R.SCALES:
+            raise ValueError(f"scale must be 2 or 4, not {scale!r}")
+        if composite and out is None:
+            raise ValueError("composite=True blends into `out`, the scene colour buffer: it must be given")
+        fn = R.bind(self._lib).atmo_render_reduced_target
+        opt = R.AtmoReduced(int(scale), float(depth_tolerance))
+
+        def extra(cam, device):
+            return C.byref(opt), C.c_void_p(self._reduced_scratch(cam, scale, scratch, device).data_ptr())
+
+        return self._render_one(camera, depth, out, None, stream, time, target, composite, None, split_depth_errors=True, reduced=(fn, extra))
+
+    def _reduced_scratch(self, camera, scale, scratch, device):
+        """The scratch tensor of a reduced draw: the caller's, checked, or this node's own, grown when a draw needs more (or another device)."""
+        import torch
+
+        from . import reduced as R
+
+        need = R.scratch_layout(camera.width, camera.height, scale)[1]
+        if scratch is not None:
+            if not (isinstance(scratch, torch.Tensor) and scratch.is_cuda and scratch.is_contiguous()):
+                raise TypeError("scratch must be a contiguous CUDA tensor")
+            if scratch.numel() * scratch.element_size() < need or scratch.data_ptr() % 16:
+                raise ValueError(f"scratch must hold at least {need} bytes (reduced.scratch_layout) and be 16-byte aligned")
+            return scratch
+        own = getattr(self, "_reduced_scratch_tensor", None)
+        if own is None or own.device != torch.device(device) or own.numel() < need:
+            own = self._reduced_scratch_tensor = torch.empty(need, dtype=torch.uint8, device=device)
+        return own
 
     # ---- caller-supplied rays (include/atmo_rays.h) --------------------------------------------------------------------------------
     def _entry(self, name: str):
