@@ -24,6 +24,7 @@
 #include "../../include/atmo_ray_detail.h"
 #include "../../include/atmo_detail_target.h"
 #include "../../include/atmo_lens.h"
+#include "../../include/atmo_sky_sh.h"
 #include "../../include/atmo_reduced.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
@@ -2630,6 +2631,75 @@ int atmo_lens_rays(AtmoContext *ctx, const AtmoLens *lens, uint32_t flags, const
     std::memcpy(lc.origin, lens->origin, sizeof(lc.origin));
     std::memcpy(lc.basis, lens->basis, sizeof(lc.basis));
     HIP_TRY(ctx, atmo::launch_lens_rays(lens->kind, quads, lc, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+// ---- sky ambient light: lens-pixel solid angles and the SH9 projection (include/atmo_sky_sh.h) -----------------------------------------------------------
+static_assert(ATMO_SKY_SH_LANES == atmo::SKY_SH_LANES && ATMO_SKY_SH_RAYS_PER_LANE == atmo::SKY_SH_PER_LANE && ATMO_SKY_SH_FLOATS == atmo::SKY_SH_ROW &&
+                  ATMO_SKY_SH_ACCUMULATE == atmo::SKY_SH_ACCUMULATE, "the header's order of the sums is the kernels'");
+// atmo_lens_rays' checks on the lens and the flags, then the one pointer.  The call enqueues and nothing else
+int atmo_lens_solid_angles(AtmoContext *ctx, const AtmoLens *lens, uint32_t flags, float *weight_dev, void *stream) {
+    const std::string who = "atmo_lens_solid_angles";
+    if (!ctx) return ATMO_E_ARG;
+    LensCounts k;
+    ATMO_TRY(lens_checks(ctx, who, lens, flags, k));
+    if (k.empty) return ATMO_OK;
+    ATMO_TRY(refuse_null(ctx, who, {{weight_dev, "weight_dev", 4}}));
+    ATMO_TRY(refuse_misaligned(ctx, who, {{weight_dev, "weight_dev", 4}}));
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    atmo::LensConsts lc{};
+    lc.w = lens->width; lc.h = lens->height; lc.y0 = lens->y0; lc.y1 = lens->y1; lc.face = lens->face;
+    lc.qpr = k.qpr; lc.tpr = k.tpr;
+    lc.n = k.n_rays;
+    lc.fov = lens->fov;
+    HIP_TRY(ctx, atmo::launch_lens_solid_angles(lens->kind, (flags & ATMO_LENS_QUADS) != 0, lc, weight_dev, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+int atmo_sky_sh9_scratch_bytes(uint32_t n_rays, size_t *bytes) {
+    if (!bytes) return fail(nullptr, ATMO_E_ARG, "atmo_sky_sh9_scratch_bytes: null bytes");
+    if (n_rays > atmo::SKY_SH_MAX_RAYS) return fail(nullptr, ATMO_E_ARG, "atmo_sky_sh9_scratch_bytes: n_rays must not exceed 2^28");
+    *bytes = atmo::sky_sh_scratch_bytes(n_rays);
+    return ATMO_OK;
+}
+
+// Every check stands in front of hipSetDevice, in the header's order.  Two kernels on the stream (or one memset), nothing else
+int atmo_sky_sh9(AtmoContext *ctx, const AtmoRay *rays_dev, const float *rgba_dev, const float *weight_dev, uint32_t n_rays, uint32_t flags,
+                 void *scratch_dev, size_t scratch_bytes, float *out_dev, void *stream) {
+    const std::string who = "atmo_sky_sh9";
+    if (!ctx) return ATMO_E_ARG;
+    ATMO_TRY(refuse_null(ctx, who, {{out_dev, "out_dev", 16}}));
+    ATMO_TRY(refuse_misaligned(ctx, who, {{out_dev, "out_dev", 16}}));
+    if (flags & ~ATMO_SKY_SH_ACCUMULATE) return fail(ctx, ATMO_E_ARG, who + ": unknown flag bits");
+    const bool accumulate = (flags & ATMO_SKY_SH_ACCUMULATE) != 0;
+    if (n_rays == 0) {   // nothing else is looked at
+        if (accumulate) return ATMO_OK;
+        if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipMemsetAsync(out_dev, 0, atmo::SKY_SH_ROW * sizeof(float), (hipStream_t)stream));
+        return ATMO_OK;
+    }
+    ATMO_TRY(refuse_null(ctx, who, {{rays_dev, "rays_dev", 16}, {rgba_dev, "rgba_dev", 16}}));
+    ATMO_TRY(refuse_misaligned(ctx, who, {{rays_dev, "rays_dev", 16}, {rgba_dev, "rgba_dev", 16}}));
+    ATMO_TRY(refuse_misaligned(ctx, who, {{weight_dev, "weight_dev", 4}}));
+    if (n_rays > atmo::SKY_SH_MAX_RAYS) return fail(ctx, ATMO_E_ARG, who + ": at most 2^28 rays");
+    ATMO_TRY(refuse_null(ctx, who, {{scratch_dev, "scratch_dev", 16}}));
+    ATMO_TRY(refuse_misaligned(ctx, who, {{scratch_dev, "scratch_dev", 16}}));
+    if (scratch_bytes < atmo::sky_sh_scratch_bytes(n_rays))
+        return fail(ctx, ATMO_E_ARG, who + ": scratch_bytes is below atmo_sky_sh9_scratch_bytes (" + std::to_string(atmo::sky_sh_scratch_bytes(n_rays)) + ")");
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    atmo::SkyShConsts c{};
+    c.rays = reinterpret_cast<const float4 *>(rays_dev);
+    c.rgba = reinterpret_cast<const float4 *>(rgba_dev);
+    c.weight = weight_dev;
+    c.partial = reinterpret_cast<float4 *>(scratch_dev);
+    c.out = reinterpret_cast<float4 *>(out_dev);
+    c.n = n_rays;
+    c.segments = atmo::sky_sh_segments(n_rays);
+    c.accumulate = accumulate ? 1 : 0;
+    HIP_TRY(ctx, atmo::launch_sky_sh9(c, (hipStream_t)stream));
     return ATMO_OK;
 }
 

@@ -428,5 +428,26 @@ struct ReducedConsts {
 hipError_t launch_reduced_pick(const ReducedConsts &dc, const DepthConsts &depth, hipStream_t stream);
 // atmo_reduced_upsample_kernel: one lane per pixel of the viewport, 64 consecutive pixels of a row per wave; every target format
 hipError_t launch_reduced_upsample(const ReducedConsts &dc, const DepthConsts &depth, const TargetConsts &tc, hipStream_t stream);
+// Sky ambient light (include/atmo_sky_sh.h states the arithmetic and THE ORDER OF THE SUMS; sky_sh.py reads these constants out of the header's text).
+// atmo_lens_solid_angle_kernel<KIND, QUADS>: one lane per slot of the band's ray array -- lc.rays names nothing here, lc.index is null, lc.n = the band's
+// rays --, one float each.  The projection: atmo_sky_sh9_segment_kernel, one workgroup of SKY_SH_LANES per SKY_SH_SEGMENT consecutive rays, its partial
+// (SKY_SH_ROW floats) to the scratch; atmo_sky_sh9_total_kernel, one workgroup over the partials, to `out`.  Kernels on `stream` only
+constexpr int SKY_SH_LANES = 256, SKY_SH_PER_LANE = 16, SKY_SH_SEGMENT = SKY_SH_LANES * SKY_SH_PER_LANE;
+constexpr int SKY_SH_SUMS = 37, SKY_SH_ROW = 40;   // 9 coefficients x rgba and the weights' sum; a partial and `out` are 40 floats, the last three +0
+constexpr uint32_t SKY_SH_MAX_RAYS = 1u << 28;
+constexpr int SKY_SH_ACCUMULATE = 1;               // == ATMO_SKY_SH_ACCUMULATE
+inline uint32_t sky_sh_segments(uint32_t n_rays) { return (n_rays + (uint32_t)(SKY_SH_SEGMENT - 1)) / (uint32_t)SKY_SH_SEGMENT; }
+inline size_t sky_sh_scratch_bytes(uint32_t n_rays) { return (size_t)sky_sh_segments(n_rays) * SKY_SH_ROW * sizeof(float); }
+struct SkyShConsts {
+    const float4 *rays;    // n AtmoRay, 16-byte aligned: the second float4 of each is read
+    const float4 *rgba;    // n rows
+    const float *weight;   // null: every ray weighs 1
+    float4 *partial;       // the scratch: sky_sh_segments(n) rows of SKY_SH_ROW floats
+    float4 *out;           // SKY_SH_ROW floats
+    uint32_t n, segments;
+    int32_t accumulate;
+};
+hipError_t launch_lens_solid_angles(int kind, bool quads, const LensConsts &lc, float *weight, hipStream_t stream);
+hipError_t launch_sky_sh9(const SkyShConsts &c, hipStream_t stream);
 
 }  // namespace atmo

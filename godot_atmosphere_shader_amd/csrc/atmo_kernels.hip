@@ -4521,9 +4521,15 @@ __device__ __forceinline__ void lens_sincos(double x, double &s, double &c) {
     s = (q & 2) ? -sa : sa;
     c = ((q + 1) & 2) ? -ca : ca;
 }
+// What lens_direction_parts forms on its way to a direction and the pixel's solid angle is stated in (include/atmo_sky_sh.h): the fp32 lenses' root and the cube
+// face's half size; the trigonometric lenses' cos theta and sin theta (fp64) and the fisheye's rho.  A caller that wants the direction alone drops them
+struct LensParts {
+    float norm, half;    // OCTAHEDRAL: n.  CUBE_FACE: len and h
+    double st, ct, rho;  // EQUIRECT: ct.  FISHEYE: st and rho (rho == 0: the centre pixel)
+};
 // the lens-space direction of pixel (x, y); false: the pixel is absent (FISHEYE outside the image circle)
 template <int KIND>
-__device__ __forceinline__ bool lens_direction(const LensConsts &lc, int x, int y, float &dx, float &dy, float &dz) {
+__device__ __forceinline__ bool lens_direction_parts(const LensConsts &lc, int x, int y, float &dx, float &dy, float &dz, LensParts &parts) {
     if constexpr (KIND == LENS_OCTAHEDRAL) {
         const float u = ieee_div((float)(2 * x + 1), (float)lc.w) - 1.0f, v = ieee_div((float)(2 * y + 1), (float)lc.h) - 1.0f;
         const float z = (1.0f - fabsf(u)) - fabsf(v);
@@ -4533,6 +4539,7 @@ __device__ __forceinline__ bool lens_direction(const LensConsts &lc, int x, int 
             b = copysignf(1.0f - fabsf(u), v);
         }
         const float n = ieee_sqrt((a * a + b * b) + z * z);
+        parts.norm = n;
         dx = ieee_div(a, n); dy = ieee_div(b, n); dz = ieee_div(z, n);
         return true;
     } else if constexpr (KIND == LENS_CUBE_FACE) {   // the coverage cubemap's texel-to-direction table (atmo_noise_cubemap_kernel's), in its operation order
@@ -4540,6 +4547,7 @@ __device__ __forceinline__ bool lens_direction(const LensConsts &lc, int x, int 
         const float p2x = ieee_div((float)x + 0.5f, half) - 1.0f, p2y = ieee_div((float)(lc.w - y - 1) + 0.5f, half) - 1.0f;
         float vx = 1.0f, vy = p2y, vz = -p2x;
         const float len = ieee_sqrt((vx * vx + vy * vy) + vz * vz);
+        parts.norm = len; parts.half = half;
         vx = ieee_div(vx, len); vy = ieee_div(vy, len); vz = ieee_div(vz, len);
         switch (lc.face) {   // wave-uniform
         case 0: dx = vx; dy = vy; dz = vz; break;
@@ -4556,6 +4564,7 @@ __device__ __forceinline__ bool lens_direction(const LensConsts &lc, int x, int 
         double sp, cp, st, ct;
         lens_sincos(phi, sp, cp);
         lens_sincos(theta, st, ct);
+        parts.ct = ct;
         dx = (float)(ct * sp); dy = (float)st; dz = (float)(-(ct * cp));
         return true;
     } else {
@@ -4565,6 +4574,7 @@ __device__ __forceinline__ bool lens_direction(const LensConsts &lc, int x, int 
         if (ax * ax + ay * ay > m * m) return false;
         const double px = ((double)x + 0.5) - (double)lc.w / 2.0, py = (double)lc.h / 2.0 - ((double)y + 0.5);
         const double rho = sqrt(px * px + py * py);
+        parts.rho = rho;
         if (rho == 0.0) {
             dx = 0.0f; dy = 0.0f; dz = -1.0f;
             return true;
@@ -4572,9 +4582,15 @@ __device__ __forceinline__ bool lens_direction(const LensConsts &lc, int x, int 
         const double theta = (rho / ((double)m / 2.0)) * ((double)lc.fov / 2.0);
         double st, ct;
         lens_sincos(theta, st, ct);
+        parts.st = st;
         dx = (float)(st * (px / rho)); dy = (float)(st * (py / rho)); dz = (float)(-ct);
         return true;
     }
+}
+template <int KIND>
+__device__ __forceinline__ bool lens_direction(const LensConsts &lc, int x, int y, float &dx, float &dy, float &dz) {
+    LensParts parts;
+    return lens_direction_parts<KIND>(lc, x, y, dx, dy, dz, parts);
 }
 template <int KIND, int QUADS>
 __global__ __launch_bounds__(RAYS_BLOCK) void atmo_lens_rays_kernel(const LensConsts lc) {
@@ -4756,6 +4772,195 @@ hipError_t launch_reduced_upsample(const ReducedConsts &c, const DepthConsts &de
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)((c.w + REDUCED_BLOCK_W - 1) / REDUCED_BLOCK_W), (unsigned)((c.h + REDUCED_BLOCK_H - 1) / REDUCED_BLOCK_H));
     hipLaunchKernelGGL(atmo_reduced_upsample_kernel, grid, dim3(REDUCED_BLOCK_W, REDUCED_BLOCK_H), 0, stream, c, depth, tc);
+    return hipGetLastError();
+}
+
+// ---- sky ambient light: lens-pixel solid angles and the SH9 projection (include/atmo_sky_sh.h states both; sky_sh.py restates them in numpy) ---------
+// Kernels of their own names (no older kernel's name is a substring of theirs, nor the reverse), defined behind everything else, so that every older kernel
+// keeps its code and its place in the code object (tools/isa_diff.py).  Nothing here is contracted (the file is compiled with -ffp-contract=off and no
+// pragma opts back in), quotients and roots are the IEEE ones.
+//
+// The solid angle of a lens pixel comes out of what lens_direction_parts forms on its way to the direction (LensParts): nothing of the lenses is stated a
+// second time.  The two fp32 lenses are the header's operations one by one; the two trigonometric ones are fp64, clamped at +0 and rounded once.
+template <int KIND>
+__device__ __forceinline__ float lens_solid_angle(const LensConsts &lc, const LensParts &p) {
+    if constexpr (KIND == LENS_OCTAHEDRAL) {
+        return ieee_div(ieee_div(ieee_div(4.0f, (float)lc.w), (float)lc.h), (p.norm * p.norm) * p.norm);
+    } else if constexpr (KIND == LENS_CUBE_FACE) {
+        return ieee_div(ieee_div(ieee_div(1.0f, p.half), p.half), (p.norm * p.norm) * p.norm);
+    } else if constexpr (KIND == LENS_EQUIRECT) {
+        const double w = ((6.283185307179586 / (double)lc.w) * (3.141592653589793 / (double)lc.h)) * p.ct;
+        return (float)(w > 0.0 ? w : 0.0);
+    } else {
+        static_assert(KIND == LENS_FISHEYE, "four lenses");
+        const int m = lc.w < lc.h ? lc.w : lc.h;
+        const double k = ((double)lc.fov / 2.0) / ((double)m / 2.0);
+        const double w = p.rho == 0.0 ? k * k : (k * p.st) / p.rho;
+        return (float)(w > 0.0 ? w : 0.0);
+    }
+}
+// lane i is slot i of the band's ray array, in atmo_lens_rays_kernel's two orders (no tile map: there is one float per slot, in the array's own order)
+template <int KIND, int QUADS>
+__global__ __launch_bounds__(RAYS_BLOCK) void atmo_lens_solid_angle_kernel(const LensConsts lc, float *__restrict__ weight) {
+    const uint64_t i = (uint64_t)blockIdx.x * RAYS_BLOCK + threadIdx.x;
+    if (i >= lc.n) return;
+    int x, y;
+    if constexpr (QUADS != 0) {
+        const uint64_t q = i >> 2;
+        x = 2 * (int)(q % lc.qpr) + (int)(i & 1u);
+        y = lc.y0 + 2 * (int)(q / lc.qpr) + (int)((i >> 1) & 1u);
+    } else {
+        x = (int)(i % (uint64_t)lc.w);
+        y = lc.y0 + (int)(i / (uint64_t)lc.w);
+    }
+    float w = 0.0f;   // an absent slot: a quad slot beyond the image or the band, a fisheye pixel outside the circle
+    if (x < lc.w && y < lc.y1) {
+        float dx, dy, dz;
+        LensParts parts;
+        if (lens_direction_parts<KIND>(lc, x, y, dx, dy, dz, parts)) w = lens_solid_angle<KIND>(lc, parts);
+    }
+    weight[i] = w;
+}
+template <int KIND>
+static hipError_t launch_solid_angle_kind(const LensConsts &lc, bool quads, float *weight, hipStream_t stream) {
+    const unsigned blocks = (unsigned)((lc.n + (RAYS_BLOCK - 1)) / RAYS_BLOCK);
+    if (quads) hipLaunchKernelGGL((atmo_lens_solid_angle_kernel<KIND, 1>), dim3(blocks), dim3(RAYS_BLOCK), 0, stream, lc, weight);
+    else hipLaunchKernelGGL((atmo_lens_solid_angle_kernel<KIND, 0>), dim3(blocks), dim3(RAYS_BLOCK), 0, stream, lc, weight);
+    return hipGetLastError();
+}
+// lc.n = the band's rays (at most 2^28 + a row of quads); lc.rays, lc.index and lc.distance are not looked at
+hipError_t launch_lens_solid_angles(int kind, bool quads, const LensConsts &lc, float *weight, hipStream_t stream) {
+    if (weight == nullptr || lc.n == 0 || lc.n > ((uint64_t)1 << 30) || lc.w < 1 || lc.h < 1 || lc.y0 < 0 || lc.y1 > lc.h || lc.y0 >= lc.y1 || (quads && lc.qpr == 0))
+        return hipErrorInvalidValue;
+    switch (kind) {
+    case LENS_EQUIRECT: return launch_solid_angle_kind<LENS_EQUIRECT>(lc, quads, weight, stream);
+    case LENS_FISHEYE: return launch_solid_angle_kind<LENS_FISHEYE>(lc, quads, weight, stream);
+    case LENS_OCTAHEDRAL: return launch_solid_angle_kind<LENS_OCTAHEDRAL>(lc, quads, weight, stream);
+    case LENS_CUBE_FACE: return launch_solid_angle_kind<LENS_CUBE_FACE>(lc, quads, weight, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// THE ORDER OF THE SUMS (the header's): lane t of a workgroup holds SKY_SH_SUMS running sums in registers; sky_sh_tree then reduces the SKY_SH_LANES lane
+// values of each by v[t] = RN(v[t] + v[t + s]), s = 128, 64, ..., 1.  The two steps across the four waves go through LDS ([sum][lane]: consecutive lanes
+// on consecutive banks): lane t < 64 forms RN(RN(v[t] + v[t + 128]) + RN(v[t + 64] + v[t + 192])), which is the tree's v[t] behind s = 64.  The six steps
+// inside wave 0 are xor shuffles: lane t gets RN(v[t] + v[t ^ s]), for t & s == 0 the tree's sum, and since the addition commutes the partner lane holds
+// the same bits -- every lane of the wave ends with the tree's v[0].  Returns true in wave 0, whose lanes then all hold the totals.
+static_assert(SKY_SH_LANES == 256, "sky_sh_tree is written for four waves");
+__device__ __forceinline__ bool sky_sh_tree(float (&acc)[SKY_SH_SUMS], float *lds) {
+    const int t = (int)threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < SKY_SH_SUMS; ++j) lds[j * SKY_SH_LANES + t] = acc[j];
+    __syncthreads();
+    if (t >= 64) return false;
+#pragma unroll
+    for (int j = 0; j < SKY_SH_SUMS; ++j) {
+        const float *v = lds + j * SKY_SH_LANES + t;
+        float s = (v[0] + v[128]) + (v[64] + v[192]);
+#pragma unroll
+        for (int step = 32; step >= 1; step >>= 1) s = s + __shfl_xor(s, step);
+        acc[j] = s;
+    }
+    return true;
+}
+// a row of SKY_SH_ROW floats from the sums: ten 16-byte stores, the last three floats +0
+__device__ __forceinline__ void sky_sh_store_row(float4 *row, const float (&v)[SKY_SH_SUMS]) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) row[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+    row[9] = make_float4(v[36], 0.0f, 0.0f, 0.0f);
+}
+// One ray's 37 terms onto the lane's sums (the header's BASIS and TERM, operation by operation)
+__device__ __forceinline__ void sky_sh_add_ray(float (&acc)[SKY_SH_SUMS], const float w, const float4 d, const float4 px) {
+    const float x = d.x, y = d.y, z = d.z;
+    const float c[4] = {px.x * px.w, px.y * px.w, px.z * px.w, px.w};
+    const float Y[9] = {0.28209479f,
+                        0.48860251f * y,
+                        0.48860251f * z,
+                        0.48860251f * x,
+                        1.0925484f * (x * y),
+                        1.0925484f * (y * z),
+                        0.31539157f * (3.0f * (z * z) - 1.0f),
+                        1.0925484f * (x * z),
+                        0.54627422f * (x * x - y * y)};
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const float wy = w * Y[k];
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) acc[4 * k + ch] = acc[4 * k + ch] + wy * c[ch];
+    }
+    acc[36] = acc[36] + w;
+}
+// Segment `blockIdx.x`: lane t adds the rays SEGMENT seg + LANES j + t, j = 0 .. 15, in that order.  The weight is read first; where it is 0 (either sign)
+// or the ray lies at or beyond n, neither the ray nor its rgba row is read and nothing is added.  Four rays' loads are in flight at a time.
+__global__ __launch_bounds__(SKY_SH_LANES) void atmo_sky_sh9_segment_kernel(const SkyShConsts c) {
+    __shared__ float lds[SKY_SH_SUMS * SKY_SH_LANES];
+    float acc[SKY_SH_SUMS];
+#pragma unroll
+    for (int j = 0; j < SKY_SH_SUMS; ++j) acc[j] = 0.0f;
+    const uint32_t base = blockIdx.x * (uint32_t)SKY_SH_SEGMENT + threadIdx.x;   // below 2^28 + 4096
+    for (int j0 = 0; j0 < SKY_SH_PER_LANE; j0 += 4) {
+        float w[4];
+        float4 d[4], px[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t i = base + (uint32_t)((j0 + q) * SKY_SH_LANES);
+            w[q] = i < c.n ? (c.weight != nullptr ? c.weight[i] : 1.0f) : 0.0f;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t i = base + (uint32_t)((j0 + q) * SKY_SH_LANES);
+            d[q] = px[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (w[q] != 0.0f) {
+                d[q] = c.rays[2 * (size_t)i + 1];
+                px[q] = c.rgba[i];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (w[q] != 0.0f) sky_sh_add_ray(acc, w[q], d[q], px[q]);
+    }
+    if (sky_sh_tree(acc, lds) && threadIdx.x == 0) sky_sh_store_row(c.partial + (size_t)blockIdx.x * (SKY_SH_ROW / 4), acc);
+}
+// One workgroup: lane t adds the partials t, t + 256, ... in that order, the same tree, and lane 0 writes `out` -- the totals, or RN(out + total)
+__global__ __launch_bounds__(SKY_SH_LANES) void atmo_sky_sh9_total_kernel(const SkyShConsts c) {
+    __shared__ float lds[SKY_SH_SUMS * SKY_SH_LANES];
+    float acc[SKY_SH_SUMS];
+#pragma unroll
+    for (int j = 0; j < SKY_SH_SUMS; ++j) acc[j] = 0.0f;
+    for (uint32_t p = threadIdx.x; p < c.segments; p += (uint32_t)SKY_SH_LANES) {
+        const float4 *row = c.partial + (size_t)p * (SKY_SH_ROW / 4);
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            const float4 v = row[q];
+            acc[4 * q] = acc[4 * q] + v.x;
+            acc[4 * q + 1] = acc[4 * q + 1] + v.y;
+            acc[4 * q + 2] = acc[4 * q + 2] + v.z;
+            acc[4 * q + 3] = acc[4 * q + 3] + v.w;
+        }
+        acc[36] = acc[36] + row[9].x;
+    }
+    if (!sky_sh_tree(acc, lds) || threadIdx.x != 0) return;
+    if (c.accumulate != 0) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            const float4 v = c.out[q];
+            acc[4 * q] = v.x + acc[4 * q];
+            acc[4 * q + 1] = v.y + acc[4 * q + 1];
+            acc[4 * q + 2] = v.z + acc[4 * q + 2];
+            acc[4 * q + 3] = v.w + acc[4 * q + 3];
+        }
+        acc[36] = c.out[9].x + acc[36];
+    }
+    sky_sh_store_row(c.out, acc);
+}
+hipError_t launch_sky_sh9(const SkyShConsts &c, hipStream_t stream) {
+    if (c.rays == nullptr || c.rgba == nullptr || c.partial == nullptr || c.out == nullptr || c.n == 0 || c.n > SKY_SH_MAX_RAYS ||
+        c.segments != sky_sh_segments(c.n))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(atmo_sky_sh9_segment_kernel, dim3(c.segments), dim3(SKY_SH_LANES), 0, stream, c);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(atmo_sky_sh9_total_kernel, dim3(1), dim3(SKY_SH_LANES), 0, stream, c);
     return hipGetLastError();
 }
 

@@ -976,21 +976,119 @@ class PlanetAtmosphere:
         if rows == 0:
             return out if out is not None else torch.zeros((0, w, 4), dtype=torch.float32, device=torch.device("cuda", self._device))
         with _on_stream(stream, torch.device("cuda", self._device))[1]:   # the gather and the zeroed image beside the two calls, which enter it again
+            _, shaded = self._shade_lens(lens, camera, distance, time, stream, quads, out)
             if quads:
-                rays = self.lens_rays(lens, distance=distance, quads=True, stream=stream)
-                shaded = self.shade_ray_quads(rays, camera, width=w, first_quad=(y0 // 2) * ((w + 1) // 2), stream=stream, time=time)
                 image = quads_to_image(shaded, w, rows)
                 if out is None:
                     return image.contiguous()
                 out.copy_(image)
                 return out
-            rays, index = self.lens_rays(lens, distance=distance, tile_index=True, stream=stream)
+            return out if out is not None else shaded.view(rows, w, 4)
+
+    def _shade_lens(self, lens, camera, distance, time, stream, quads, image=None):
+        """What `render_lens` and `ambient_sh9` share: `(rays, shaded)` of the lens's band in ray order, (n, 8) and (n, 4).  `quads`: the quad order through
+        `shade_ray_quads`; else row-major through the tile index into zeros -- into `image` (rows, width, 4) where one is given -- so that the rows of
+        absent pixels, which the indexed call leaves alone, are zero.  The band is not empty; the caller has entered the stream."""
+        import torch
+
+        y0, y1 = lens.rows
+        rows, w = y1 - y0, lens.width
+        if quads:
+            rays = self.lens_rays(lens, distance=distance, quads=True, stream=stream)
+            return rays, self.shade_ray_quads(rays, camera, width=w, first_quad=(y0 // 2) * ((w + 1) // 2), stream=stream, time=time)
+        rays, index = self.lens_rays(lens, distance=distance, tile_index=True, stream=stream)
+        if image is None:
+            image = torch.zeros((rows, w, 4), dtype=torch.float32, device=rays.device)
+        else:
+            image.zero_()
+        shaded = image.view(rows * w, 4)
+        self.shade_rays(rays, camera, width=w, first=y0 * w, out=shaded, stream=stream, time=time, index=index)
+        return rays, shaded
+
+    # ---- the sky as light: solid angles and the SH9 projection (include/atmo_sky_sh.h) ---------------------------------------------
+    def lens_solid_angles(self, lens, quads: bool = False, stream=None):
+        """The solid angle, in steradians, of the pixel in every slot of `lens_rays(lens, quads=quads)`, computed on the device (atmo_lens_solid_angles;
+        include/atmo_sky_sh.h states the arithmetic, sky_sh.solid_angles is the same statement in numpy): a CUDA float32 (n_rays,) tensor, +0 for an absent
+        slot.  The weights `project_sh9` wants beside that lens's rays."""
+        import torch
+
+        from . import sky_sh as SH
+
+        fn = SH.bind(self._lib).atmo_lens_solid_angles
+        nl, flags = lens.native(), N.LENS_QUADS if quads else 0
+        n_rays = C.c_uint32(0)
+        N.check(self._ctx, self._entry("atmo_lens_ray_counts")(C.byref(nl), flags, C.byref(n_rays), None))
+        device = torch.device("cuda", self._device)
+        handle, on_stream = _on_stream(stream, device)
+        with on_stream:
+            weights = torch.empty((n_rays.value,), dtype=torch.float32, device=device)
+        N.check(self._ctx, fn(self._ctx, C.byref(nl), flags, C.c_void_p(weights.data_ptr()), C.c_void_p(handle or 0)))
+        return weights
+
+    def project_sh9(self, rays, rgba, weights=None, out=None, accumulate: bool = False, stream=None):
+        """Projects shaded rays onto the nine real spherical harmonics of bands 0 to 2, on the device and in one fixed order of summation (atmo_sky_sh9;
+        include/atmo_sky_sh.h, sky_sh.sh9_project is the same sums in numpy, bit for bit).  `rays` as `shade_rays`' (their directions are used as given: the
+        coefficients live in ray space), `rgba` what a shading call returned for them, `weights` a contiguous CUDA float32 (n,) tensor -- `lens_solid_angles`'
+        -- or None: every ray weighs 1.  A ray whose weight is 0 is not read.  Returns or fills `out`, a contiguous CUDA float32 (40,) tensor:
+        out[4 k + ch] the coefficient of Y_k in channel ch (rgb premultiplied by alpha, then alpha), out[36] the weights' sum, three zeros.  `accumulate`:
+        the sums are added to what `out` holds (six cube faces: six calls, the five behind the first with it).  The scratch comes from torch's allocator,
+        on the call's stream."""
+        import torch
+
+        from . import sky_sh as SH
+
+        lib = SH.bind(self._lib)
+        n = _check_rays(rays, "rays", 8)
+        if _check_rays(rgba, "rgba", 4) != n:
+            raise ValueError("rgba must have one row per ray: shape (n, 4)")
+        if weights is not None:
+            _check_kind(weights, "weights must be a contiguous CUDA float32 tensor")
+            if tuple(weights.shape) != (n,):
+                raise ValueError("weights must have one float per ray: shape (n,)")
+        if n > SH.MAX_RAYS:
+            raise ValueError("at most 2^28 rays")
+        if out is not None:
+            _check_kind(out, "out must be a contiguous CUDA float32 tensor")
+            if tuple(out.shape) != (SH.FLOATS,):
+                raise ValueError(f"out must have shape ({SH.FLOATS},)")
+        elif accumulate:
+            raise ValueError("accumulate needs the `out` it adds to")
+        need = C.c_size_t(0)
+        N.check(self._ctx, lib.atmo_sky_sh9_scratch_bytes(n, C.byref(need)))
+        handle, on_stream = _on_stream(stream, rays.device)
+        with on_stream:
+            scratch = torch.empty((max(need.value // 4, 4),), dtype=torch.float32, device=rays.device)
             if out is None:
-                out = torch.zeros((rows, w, 4), dtype=torch.float32, device=rays.device)
-            else:
-                out.zero_()
-            self.shade_rays(rays, camera, width=w, first=y0 * w, out=out.view(rows * w, 4), stream=stream, time=time, index=index)
-            return out
+                out = torch.empty((SH.FLOATS,), dtype=torch.float32, device=rays.device)
+        N.check(self._ctx, lib.atmo_sky_sh9(self._ctx, C.c_void_p(rays.data_ptr()), C.c_void_p(rgba.data_ptr()),
+                                            C.c_void_p(weights.data_ptr()) if weights is not None else None, n, SH.ACCUMULATE if accumulate else 0,
+                                            C.c_void_p(scratch.data_ptr()), need, C.c_void_p(out.data_ptr()), C.c_void_p(handle or 0)))
+        return out
+
+    def ambient_sh9(self, lenses, camera=None, time: float = 0.0, stream=None):
+        """The sky's light through one lens or several (a lens.Lens or a sequence: an octahedral map, six cube faces) as nine spherical-harmonic
+        coefficients per channel: each lens is shaded as `render_lens` shades it -- in quad order under the declared sampler where this node has one, else
+        row-major through the tile index; with `cloud_detail` through the detail entry points --, weighed by `lens_solid_angles` and projected by
+        `project_sh9` from the ray-ordered arrays, accumulating across the lenses.  `camera` as in `shade_rays`: the coefficients live in ray space.  Returns
+        the CUDA float32 (40,) tensor of `project_sh9`; nothing is read back and nothing waits on the host.  sky_sh.sh9_irradiance turns it into the
+        irradiance on a surface."""
+        import torch
+
+        from . import sky_sh as SH
+        from .lens import Lens
+
+        lenses = [lenses] if isinstance(lenses, Lens) else list(lenses)
+        device = torch.device("cuda", self._device)
+        quads = self._shades_ray_quads()
+        with _on_stream(stream, device)[1]:
+            out = None
+            for lens in lenses:
+                if lens.rows[0] == lens.rows[1]:
+                    continue
+                rays, shaded = self._shade_lens(lens, camera, None, time, stream, quads)
+                out = self.project_sh9(rays, shaded, self.lens_solid_angles(lens, quads=quads, stream=stream), out=out, accumulate=out is not None,
+                                       stream=stream)
+            return out if out is not None else torch.zeros((SH.FLOATS,), dtype=torch.float32, device=device)
 
     def prepare_frame(self, camera, time: float = 0.0, rect=None) -> N.AtmoFrame:
         """The native per-frame argument block for `render_prepared` (build once per camera pose)."""
