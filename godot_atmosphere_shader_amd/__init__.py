@@ -9,6 +9,8 @@ Zylann/godot_atmosphere_shader, behind the reference's `PlanetAtmosphere` / `sha
   reduced.py            reduced-resolution draws in numpy and the header's ctypes declarations (include/atmo_reduced.h; `PlanetAtmosphere.render_reduced`)
   sky_sh.py             the sky as light in numpy -- lens-pixel solid angles, the SH9 projection in its fixed order of summation, irradiance -- and the
                         header's ctypes declarations (include/atmo_sky_sh.h; `PlanetAtmosphere.lens_solid_angles`, `project_sh9`, `ambient_sh9`)
+  sky_image.py          sky images in numpy -- the resolve of a lens's shaded rays into a target format, the mip chain -- and the header's ctypes
+                        declarations (include/atmo_sky_image.h; `PlanetAtmosphere.resolve_lens`, `sky_image_mips`, `render_sky_image`)
   noise_volume.py       host-side mirror of the demo's NoiseTexture3D: the cloud shape volume, generated on the GPU (include/atmo_noise_volume.h)
   demo.py               the reference's demo scene + named shader configurations (tests, bench.py, smoke())
   scene.py              synthetic inputs (camera, depth, jitter, cloud textures) for tests and bench

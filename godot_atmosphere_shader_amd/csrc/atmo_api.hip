@@ -25,6 +25,7 @@
 #include "../../include/atmo_detail_target.h"
 #include "../../include/atmo_lens.h"
 #include "../../include/atmo_sky_sh.h"
+#include "../../include/atmo_sky_image.h"
 #include "../../include/atmo_reduced.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
@@ -2700,6 +2701,104 @@ int atmo_sky_sh9(AtmoContext *ctx, const AtmoRay *rays_dev, const float *rgba_de
     c.segments = atmo::sky_sh_segments(n_rays);
     c.accumulate = accumulate ? 1 : 0;
     HIP_TRY(ctx, atmo::launch_sky_sh9(c, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+// ---- sky images: the resolve into a target and the mip chain (include/atmo_sky_image.h) ---------------------------------------------------------------------
+static_assert(ATMO_LENS_QUADS == atmo::SKY_IMAGE_QUADS && ATMO_SKY_IMAGE_PREMULTIPLIED == atmo::SKY_IMAGE_PREMULTIPLIED &&
+                  ATMO_SKY_IMAGE_COMPOSITE == atmo::SKY_IMAGE_COMPOSITE, "the header's flags are the kernel's");
+static_assert(sizeof(AtmoSkyLevel) == 24, "AtmoSkyLevel: a pointer, two words, a 64-bit pitch");
+// Every check stands in front of hipSetDevice, in the header's order.  The lens is checked twice: without ATMO_LENS_QUADS first, so that the flag checks of
+// this header stand between the lens's own checks and QUADS' even rows, which is all the second pass can still refuse
+int atmo_sky_image_resolve(AtmoContext *ctx, const AtmoLens *lens, uint32_t flags, const float *rgba_dev, const AtmoTarget *target, void *stream) {
+    const std::string who = "atmo_sky_image_resolve";
+    if (!ctx) return ATMO_E_ARG;
+    LensCounts k;
+    ATMO_TRY(lens_checks(ctx, who, lens, 0, k));
+    if (k.empty) return ATMO_OK;
+    if (flags & ~(ATMO_LENS_QUADS | ATMO_SKY_IMAGE_PREMULTIPLIED | ATMO_SKY_IMAGE_COMPOSITE)) return fail(ctx, ATMO_E_ARG, who + ": unknown flag bits");
+    if ((flags & ATMO_SKY_IMAGE_PREMULTIPLIED) && (flags & ATMO_SKY_IMAGE_COMPOSITE))
+        return fail(ctx, ATMO_E_ARG, who + ": ATMO_SKY_IMAGE_PREMULTIPLIED together with ATMO_SKY_IMAGE_COMPOSITE (the blend multiplies by alpha itself)");
+    ATMO_TRY(lens_checks(ctx, who, lens, flags & ATMO_LENS_QUADS, k));
+    ATMO_TRY(refuse_null(ctx, who, {{rgba_dev, "rgba_dev", 16}}));
+    ATMO_TRY(refuse_misaligned(ctx, who, {{rgba_dev, "rgba_dev", 16}}));
+    if (!target) return fail(ctx, ATMO_E_ARG, who + ": null target");
+    const int px = atmo_target_pixel_bytes(target->format);
+    if (px == 0) return fail(ctx, ATMO_E_ARG, who + ": unknown target format " + std::to_string(target->format));
+    if (!target->pixels) return fail(ctx, ATMO_E_ARG, who + ": null target pixels");
+    if ((reinterpret_cast<uintptr_t>(target->pixels) & (uintptr_t)(px - 1)) != 0)
+        return fail(ctx, ATMO_E_ARG, who + ": target pixels must be aligned to the pixel size (" + std::to_string(px) + " bytes)");
+    const long long row_bytes = (long long)lens->width * px;
+    const long long pitch = target->row_pitch_bytes == 0 ? row_bytes : (long long)target->row_pitch_bytes;
+    if (pitch < row_bytes || pitch % px != 0 || pitch > 0x7fffffffll)
+        return fail(ctx, ATMO_E_ARG, who + ": row_pitch_bytes must be 0, or at least the row's bytes (" + std::to_string(row_bytes) +
+                                         ") and a multiple of the pixel size (" + std::to_string(px) + ")");
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    atmo::SkyResolveConsts c{};
+    c.rgba = reinterpret_cast<const float4 *>(rgba_dev);
+    c.w = lens->width; c.h = lens->height; c.y0 = lens->y0; c.y1 = lens->y1;
+    c.fisheye = lens->kind == ATMO_LENS_FISHEYE ? 1 : 0;
+    c.qpr = k.qpr;
+    c.flags = flags;
+    const atmo::TargetConsts tc = {target->pixels, (int32_t)pitch, target->format};
+    HIP_TRY(ctx, atmo::launch_sky_image_resolve(c, tc, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+int atmo_sky_image_level_count(int width, int height, int *n_levels) {
+    if (!n_levels) return fail(nullptr, ATMO_E_ARG, "atmo_sky_image_level_count: null n_levels");
+    if (width < 1 || height < 1 || width > 65536 || height > 65536)
+        return fail(nullptr, ATMO_E_ARG, "atmo_sky_image_level_count: width and height must lie in 1 .. 65536");
+    int n = 1;
+    for (int m = width > height ? width : height; m > 1; m >>= 1) ++n;
+    *n_levels = n;
+    return ATMO_OK;
+}
+
+// Every check stands in front of hipSetDevice, in the header's order; then ceil((n_levels - 1) / 5) launches on the stream, nothing else
+int atmo_sky_image_mips(AtmoContext *ctx, const AtmoSkyLevel *levels, int n_levels, int format, int width, int height, int layers, void *stream) {
+    const std::string who = "atmo_sky_image_mips";
+    if (!ctx) return ATMO_E_ARG;
+    const int px = atmo_target_pixel_bytes(format);
+    if (px == 0) return fail(ctx, ATMO_E_ARG, who + ": unknown target format " + std::to_string(format));
+    if (width < 1 || height < 1 || width > 65536 || height > 65536) return fail(ctx, ATMO_E_ARG, who + ": width and height must lie in 1 .. 65536");
+    if (layers < 1 || layers > 4096) return fail(ctx, ATMO_E_ARG, who + ": layers must lie in 1 .. 4096");
+    if ((long long)width * height * layers > (1ll << 30)) return fail(ctx, ATMO_E_ARG, who + ": width * height * layers must not exceed 2^30");
+    int full = 0;
+    (void)atmo_sky_image_level_count(width, height, &full);
+    if (n_levels < 1 || n_levels > full)
+        return fail(ctx, ATMO_E_ARG, who + ": n_levels must lie in 1 .. " + std::to_string(full) + " (atmo_sky_image_level_count)");
+    if (!levels) return fail(ctx, ATMO_E_ARG, who + ": null levels");
+    std::array<atmo::SkyMipLevel, 17> lv{};   // 65536 has 17 levels
+    for (int l = 0; l < n_levels; ++l) {
+        const std::string level = who + ": level " + std::to_string(l);
+        const AtmoSkyLevel &in = levels[l];
+        const long long w = width >> l > 1 ? width >> l : 1, h = height >> l > 1 ? height >> l : 1;
+        if (!in.pixels) return fail(ctx, ATMO_E_ARG, level + ": null pixels");
+        if ((reinterpret_cast<uintptr_t>(in.pixels) & (uintptr_t)(px - 1)) != 0)
+            return fail(ctx, ATMO_E_ARG, level + ": pixels must be aligned to the pixel size (" + std::to_string(px) + " bytes)");
+        const long long row_bytes = w * px, row_pitch = in.row_pitch_bytes == 0 ? row_bytes : (long long)in.row_pitch_bytes;
+        if (row_pitch < row_bytes || row_pitch % px != 0)
+            return fail(ctx, ATMO_E_ARG, level + ": row_pitch_bytes must be 0, or at least the row's bytes (" + std::to_string(row_bytes) +
+                                             ") and a multiple of the pixel size (" + std::to_string(px) + ")");
+        const long long layer_bytes = h * row_pitch, layer_pitch = in.layer_pitch_bytes == 0 ? layer_bytes : (long long)in.layer_pitch_bytes;
+        if (layer_pitch < layer_bytes || layer_pitch % px != 0)
+            return fail(ctx, ATMO_E_ARG, level + ": layer_pitch_bytes must be 0, or at least the layer's " + std::to_string(h) + " rows (" +
+                                             std::to_string(layer_bytes) + " bytes) and a multiple of the pixel size (" + std::to_string(px) + ")");
+        if (in.reserved != 0) return fail(ctx, ATMO_E_ARG, level + ": reserved must be 0");
+        lv[(size_t)l] = {in.pixels, (int64_t)layer_pitch, (int32_t)row_pitch, (int32_t)w, (int32_t)h, 0};
+    }
+    if (n_levels == 1) return ATMO_OK;   // level 0 alone: nothing to write, nothing is enqueued
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (int first = 0; first < n_levels - 1; first += atmo::SKY_MIP_STEPS) {
+        atmo::SkyMipConsts c{};
+        c.steps = n_levels - 1 - first < atmo::SKY_MIP_STEPS ? n_levels - 1 - first : atmo::SKY_MIP_STEPS;
+        c.layers = layers;
+        for (int k = 0; k <= c.steps; ++k) c.lv[k] = lv[(size_t)(first + k)];
+        HIP_TRY(ctx, atmo::launch_sky_image_mips(format, c, (hipStream_t)stream));
+    }
     return ATMO_OK;
 }
 

@@ -449,5 +449,34 @@ struct SkyShConsts {
 };
 hipError_t launch_lens_solid_angles(int kind, bool quads, const LensConsts &lc, float *weight, hipStream_t stream);
 hipError_t launch_sky_sh9(const SkyShConsts &c, hipStream_t stream);
+// Sky images (include/atmo_sky_image.h states both operations; sky_image.py restates them in numpy).
+// atmo_sky_image_resolve_kernel: one lane per pixel of the band, the row of its ray slot as one 16-byte load, the store of the KF_DEPTH kernels (every
+// target format, a uniform field).  tc.pixels is pixel (0, 0) of the whole image.  Row-major: a wave is 64 pixels of a row; QUADS: 32 pixels of two rows,
+// 16 whole quads.  atmo_sky_image_mip_kernel<FMT>: one workgroup of SKY_MIP_LANES per SKY_MIP_BLOCK x SKY_MIP_BLOCK texels of lv[0] of one layer, up to
+// SKY_MIP_STEPS levels below it through LDS.  Kernels on `stream` only
+constexpr uint32_t SKY_IMAGE_QUADS = 1u, SKY_IMAGE_PREMULTIPLIED = 2u, SKY_IMAGE_COMPOSITE = 4u;   // == ATMO_LENS_QUADS, ATMO_SKY_IMAGE_*
+struct SkyResolveConsts {
+    const float4 *rgba;     // the band's rows in ray order, 16-byte aligned
+    int32_t w, h, y0, y1;   // the image and the band [y0, y1), not empty
+    int32_t fisheye;        // the lens has absent pixels: atmo_lens.h's integer test on (w, h)
+    uint32_t qpr;           // quads per row, (w + 1) / 2
+    uint32_t flags;         // SKY_IMAGE_*
+    uint32_t blocks_x;      // [launcher] workgroups along a row
+};
+hipError_t launch_sky_image_resolve(SkyResolveConsts c, const TargetConsts &tc, hipStream_t stream);
+constexpr int SKY_MIP_STEPS = 5, SKY_MIP_BLOCK = 32, SKY_MIP_LANES = 256;
+struct SkyMipLevel {
+    void *pixels;
+    int64_t layer_pitch;    // bytes, in effect (never 0)
+    int32_t row_pitch;      // bytes, in effect
+    int32_t w, h;
+    int32_t unused;
+};
+struct SkyMipConsts {
+    SkyMipLevel lv[SKY_MIP_STEPS + 1];   // lv[0] is read, lv[1 .. steps] are written; by value in the kernel arguments
+    int32_t steps;                       // 1 .. SKY_MIP_STEPS
+    int32_t layers;
+};
+hipError_t launch_sky_image_mips(int format, const SkyMipConsts &c, hipStream_t stream);
 
 }  // namespace atmo

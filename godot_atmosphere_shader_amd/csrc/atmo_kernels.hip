@@ -4964,4 +4964,158 @@ hipError_t launch_sky_sh9(const SkyShConsts &c, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// ---- sky images: the resolve of ray results into a target, and its mip chain (include/atmo_sky_image.h states both; sky_image.py restates them) ----------
+// Kernels of their own names, defined behind everything else: every older kernel keeps its code and its place in the code object (tools/isa_diff.py).
+// The formats are stated once, in target_decode / target_encode / store_target_all_rt above; nothing here is contracted.
+//
+// The resolve: lane = pixel.  A workgroup of 256 lanes is 64 x 4 pixels in the row-major order (a wave: 64 pixels of a row, 1024 contiguous bytes of rows)
+// and 32 x 8 pixels under QUADS (a wave: 32 pixels of two rows = 16 whole quads, the same 1024 contiguous bytes; a wave of 64 x 1 would use half of every
+// 64-byte quad).  The stores stay whole either way: a wave's row segment is 32 or 64 pixels of 4 to 16 bytes, 128 bytes or more.  An absent pixel is decided
+// from (w, h) alone, in front of the load.
+constexpr int SKY_RESOLVE_LANES = 256;
+__global__ __launch_bounds__(SKY_RESOLVE_LANES) void atmo_sky_image_resolve_kernel(const SkyResolveConsts c, const TargetConsts tc) {
+    const bool quads = (c.flags & SKY_IMAGE_QUADS) != 0, composite = (c.flags & SKY_IMAGE_COMPOSITE) != 0;
+    const int log2w = quads ? 5 : 6;   // the workgroup's width in pixels, uniform
+    const uint32_t bx = blockIdx.x % c.blocks_x, by = blockIdx.x / c.blocks_x;
+    const uint32_t t = threadIdx.x;
+    const uint32_t ux = (bx << log2w) + (t & ((1u << log2w) - 1u));
+    const uint32_t ry = by * (uint32_t)(SKY_RESOLVE_LANES >> log2w) + (t >> log2w);   // the row inside the band; rows <= 2^28
+    if (ux >= (uint32_t)c.w || ry >= (uint32_t)(c.y1 - c.y0)) return;
+    const int x = (int)ux, y = c.y0 + (int)ry;
+    void *p = (char *)tc.pixels + (size_t)y * (size_t)tc.pitch_bytes + ((size_t)x << target_pixel_shift_all(tc.format));
+    if (c.fisheye != 0) {   // atmo_lens.h: r > 1 decided in integers (each term below 2^58)
+        const long long ax = 2ll * x + 1 - c.w, ay = (long long)c.h - 2ll * y - 1, m = c.w < c.h ? c.w : c.h;
+        if (ax * ax + ay * ay > m * m) {   // absent: its row is not read
+            if (!composite) store_target_zero_all_rt(tc.format, p);
+            return;
+        }
+    }
+    const size_t slot = quads ? 4 * ((size_t)(ry >> 1) * c.qpr + (size_t)(ux >> 1)) + (size_t)(((ry & 1u) << 1) | (ux & 1u)) : (size_t)ry * (size_t)c.w + ux;
+    float4 px = c.rgba[slot];
+    if (composite && !(px.w > 0.0f)) return;   // nothing to blend: the pixel keeps its bytes (a NaN alpha too)
+    if ((c.flags & SKY_IMAGE_PREMULTIPLIED) != 0) {
+        px.x = px.x * px.w;
+        px.y = px.y * px.w;
+        px.z = px.z * px.w;
+    }
+    store_target_all_rt(tc.format, p, px, composite);
+}
+hipError_t launch_sky_image_resolve(SkyResolveConsts c, const TargetConsts &tc, hipStream_t stream) {
+    const int shift = tc.format == TF_RGBA32F ? 4 : tc.format == TF_RGBA16F ? 3 : 2;
+    if (c.rgba == nullptr || tc.pixels == nullptr || (tc.format != TF_RGBA32F && !target_format_packed(tc.format)) || c.w < 1 || c.h < 1 || c.y0 < 0 ||
+        c.y1 > c.h || c.y0 >= c.y1 || (long long)c.w * c.h > (1ll << 28) || (long long)tc.pitch_bytes < ((long long)c.w << shift) ||
+        c.qpr != ((uint32_t)c.w + 1u) / 2u || (c.flags & ~(SKY_IMAGE_QUADS | SKY_IMAGE_PREMULTIPLIED | SKY_IMAGE_COMPOSITE)) != 0)
+        return hipErrorInvalidValue;
+    const bool quads = (c.flags & SKY_IMAGE_QUADS) != 0;
+    const uint32_t bw = quads ? 32u : 64u, bh = (uint32_t)SKY_RESOLVE_LANES / bw, rows = (uint32_t)(c.y1 - c.y0);
+    c.blocks_x = ((uint32_t)c.w + bw - 1u) / bw;
+    const uint64_t blocks = (uint64_t)c.blocks_x * ((rows + bh - 1u) / bh);   // at most 2^28 / 256 + 2^28 / 4 + ...: far below 2^31
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(atmo_sky_image_resolve_kernel, dim3((unsigned)blocks), dim3(SKY_RESOLVE_LANES), 0, stream, c, tc);
+    return hipGetLastError();
+}
+
+// The mip chain, fused: a workgroup takes the 32 x 32 texels of lv[0] at (32 bx, 32 by) of one layer and writes the 16 x 16, 8 x 8, 4 x 4, 2 x 2 and 1 x 1
+// texels below them.  With floor sizes, texel (i, j) of level k depends on the aligned 2^k x 2^k block of level 0 alone, and the clamp acts only where a
+// side has reached 1 (there the block's origin is 0 and the one texel is counted twice): nothing is handed from one workgroup to another.  Every level goes
+// through the format's encode, and the bits are decoded again in registers: the next level is computed from what was stored, as the statement says.
+template <int FMT> constexpr int sky_mip_shift = FMT == TF_RGBA32F ? 4 : (FMT == TF_RGBA16F ? 3 : 2);
+template <int FMT>
+__device__ __forceinline__ float4 sky_mip_store(void *p, const float4 &v) {   // stores encode(v), returns decode(encode(v))
+    if constexpr (FMT == TF_RGBA32F) {
+        *(float4 *)p = v;
+        return v;
+    } else if constexpr (FMT == TF_RGBA16F) {
+        uint2 bits;
+        target_encode<FMT>(&bits, v);
+        *(uint2 *)p = bits;
+        return target_decode<FMT>(&bits);
+    } else {
+        uint32_t bits;
+        target_encode<FMT>(&bits, v);
+        *(uint32_t *)p = bits;
+        return target_decode<FMT>(&bits);
+    }
+}
+__device__ __forceinline__ float4 sky_mip_average(const float4 &t00, const float4 &t10, const float4 &t01, const float4 &t11) {
+#pragma clang fp contract(off)
+    return make_float4(((t00.x + t10.x) + (t01.x + t11.x)) * 0.25f, ((t00.y + t10.y) + (t01.y + t11.y)) * 0.25f,
+                       ((t00.z + t10.z) + (t01.z + t11.z)) * 0.25f, ((t00.w + t10.w) + (t01.w + t11.w)) * 0.25f);
+}
+template <int FMT>
+__device__ __forceinline__ char *sky_mip_texel(const SkyMipLevel &lv, const size_t layer, const int x, const int y) {
+    return (char *)lv.pixels + layer * (size_t)lv.layer_pitch + (size_t)y * (size_t)lv.row_pitch + ((size_t)x << sky_mip_shift<FMT>);
+}
+// level K of the launch (2 .. 5) from level K - 1 in LDS: `src` holds the block's (2 N) x (2 N) decoded texels, `dst` receives its N x N
+template <int FMT, int K>
+__device__ __forceinline__ void sky_mip_step(const SkyMipConsts &c, const float4 *src, float4 *dst, const int bx, const int by, const size_t layer) {
+    constexpr int N = SKY_MIP_BLOCK >> K, P = 2 * N;
+    const int t = (int)threadIdx.x;
+    if (t >= N * N) return;
+    const int lx = t % N, ly = t / N;
+    const int gi = bx * N + lx, gj = by * N + ly;
+    const SkyMipLevel &prev = c.lv[K - 1], &cur = c.lv[K];
+    if (gi >= cur.w || gj >= cur.h) return;
+    const int x0 = min(2 * gi, prev.w - 1) - bx * P, x1 = min(2 * gi + 1, prev.w - 1) - bx * P;
+    const int y0 = min(2 * gj, prev.h - 1) - by * P, y1 = min(2 * gj + 1, prev.h - 1) - by * P;
+    const float4 v = sky_mip_average(src[y0 * P + x0], src[y0 * P + x1], src[y1 * P + x0], src[y1 * P + x1]);
+    dst[ly * N + lx] = sky_mip_store<FMT>(sky_mip_texel<FMT>(cur, layer, gi, gj), v);
+}
+template <int FMT>
+__global__ __launch_bounds__(SKY_MIP_LANES) void atmo_sky_image_mip_kernel(const SkyMipConsts c) {
+    static_assert(SKY_MIP_BLOCK == 32 && SKY_MIP_LANES == 256 && SKY_MIP_STEPS == 5, "a lane per 2 x 2 texels of the block, five halvings to one texel");
+    __shared__ float4 lds_a[256], lds_b[64];
+    const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    const size_t layer = blockIdx.z;
+    {   // level 1 from memory: lane t is texel (t & 15, t >> 4) of the block's 16 x 16
+        const int t = (int)threadIdx.x, gi = bx * 16 + (t & 15), gj = by * 16 + (t >> 4);
+        const SkyMipLevel &prev = c.lv[0], &cur = c.lv[1];
+        if (gi < cur.w && gj < cur.h) {
+            const int x0 = min(2 * gi, prev.w - 1), x1 = min(2 * gi + 1, prev.w - 1), y0 = min(2 * gj, prev.h - 1), y1 = min(2 * gj + 1, prev.h - 1);
+            const float4 t00 = target_decode<FMT>(sky_mip_texel<FMT>(prev, layer, x0, y0)), t10 = target_decode<FMT>(sky_mip_texel<FMT>(prev, layer, x1, y0));
+            const float4 t01 = target_decode<FMT>(sky_mip_texel<FMT>(prev, layer, x0, y1)), t11 = target_decode<FMT>(sky_mip_texel<FMT>(prev, layer, x1, y1));
+            lds_a[t] = sky_mip_store<FMT>(sky_mip_texel<FMT>(cur, layer, gi, gj), sky_mip_average(t00, t10, t01, t11));
+        }
+    }
+    if (c.steps < 2) return;   // uniform, as every test of c.steps: the barriers below are reached by all lanes or by none
+    __syncthreads();
+    sky_mip_step<FMT, 2>(c, lds_a, lds_b, bx, by, layer);
+    if (c.steps < 3) return;
+    __syncthreads();
+    sky_mip_step<FMT, 3>(c, lds_b, lds_a, bx, by, layer);
+    if (c.steps < 4) return;
+    __syncthreads();
+    sky_mip_step<FMT, 4>(c, lds_a, lds_b, bx, by, layer);
+    if (c.steps < 5) return;
+    __syncthreads();
+    sky_mip_step<FMT, 5>(c, lds_b, lds_a, bx, by, layer);
+}
+template <int FMT>
+static hipError_t launch_sky_mip_format(const SkyMipConsts &c, hipStream_t stream) {
+    const dim3 grid((unsigned)((c.lv[1].w + 15) / 16), (unsigned)((c.lv[1].h + 15) / 16), (unsigned)c.layers);
+    hipLaunchKernelGGL((atmo_sky_image_mip_kernel<FMT>), grid, dim3(SKY_MIP_LANES), 0, stream, c);
+    return hipGetLastError();
+}
+hipError_t launch_sky_image_mips(int format, const SkyMipConsts &c, hipStream_t stream) {
+    if (c.steps < 1 || c.steps > SKY_MIP_STEPS || c.layers < 1 || c.layers > 4096) return hipErrorInvalidValue;
+    const int shift = format == TF_RGBA32F ? 4 : format == TF_RGBA16F ? 3 : 2;
+    for (int k = 0; k <= c.steps; ++k) {   // every level the launch touches: a size that follows from the one above, pitches that hold it
+        const SkyMipLevel &lv = c.lv[k];
+        if (lv.pixels == nullptr || lv.w < 1 || lv.h < 1 || lv.w > 65536 || lv.h > 65536 || (long long)lv.row_pitch < ((long long)lv.w << shift) ||
+            lv.layer_pitch < (long long)lv.row_pitch * lv.h)
+            return hipErrorInvalidValue;
+        if (k > 0 && (lv.w != (c.lv[k - 1].w > 1 ? c.lv[k - 1].w >> 1 : 1) || lv.h != (c.lv[k - 1].h > 1 ? c.lv[k - 1].h >> 1 : 1))) return hipErrorInvalidValue;
+    }
+    switch (format) {
+    case TF_RGBA32F: return launch_sky_mip_format<TF_RGBA32F>(c, stream);
+    case TF_RGBA16F: return launch_sky_mip_format<TF_RGBA16F>(c, stream);
+    case TF_RGBA8_UNORM: return launch_sky_mip_format<TF_RGBA8_UNORM>(c, stream);
+    case TF_RGBA8_SRGB: return launch_sky_mip_format<TF_RGBA8_SRGB>(c, stream);
+    case TF_BGRA8_UNORM: return launch_sky_mip_format<TF_BGRA8_UNORM>(c, stream);
+    case TF_BGRA8_SRGB: return launch_sky_mip_format<TF_BGRA8_SRGB>(c, stream);
+    case TF_A2B10G10R10_UNORM: return launch_sky_mip_format<TF_A2B10G10R10_UNORM>(c, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace atmo

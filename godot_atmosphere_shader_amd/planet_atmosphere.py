@@ -1090,6 +1090,97 @@ class PlanetAtmosphere:
                                        stream=stream)
             return out if out is not None else torch.zeros((SH.FLOATS,), dtype=torch.float32, device=device)
 
+    # ---- the sky as an image: the resolve into a target and its mip chain (include/atmo_sky_image.h) -------------------------------
+    def resolve_lens(self, lens, rgba, out, *, target=None, quads: bool = False, premultiplied: bool = False, composite: bool = False, stream=None):
+        """Resolves what a shading call returned for `lens_rays(lens, quads=quads)` -- `rgba`, a contiguous CUDA float32 (n_rays, 4) tensor in ray order --
+        into the rows `lens.rows` of the image `out` (atmo_sky_image_resolve; include/atmo_sky_image.h states it, sky_image.resolve is the same in numpy,
+        bit for bit).  `out` is the WHOLE image: a CUDA float32, float16 or uint8 (lens.height, lens.width, 4) tensor whose rows may be further apart than
+        a row, `target` naming a packed format, as in `render(..., target=)`; rows outside the band and bytes between rows are not written.  The rows of
+        absent pixels (outside a fisheye's circle) are never read: a plain call stores zeros there, `composite` leaves them alone.  `premultiplied`: rgb
+        times alpha is stored.  `composite`: blended into `out` where alpha > 0.  Returns `out`."""
+        from . import sky_image as SI
+
+        fn = SI.bind(self._lib).atmo_sky_image_resolve
+        if premultiplied and composite:
+            raise ValueError("premultiplied together with composite: the blend multiplies by alpha itself")
+        n = _check_rays(rgba, "rgba", 4)
+        if n != lens.counts(quads)[0]:
+            raise ValueError(f"rgba must have one row per slot of the lens's ray array: shape ({lens.counts(quads)[0]}, 4)")
+        tgt = _colour_target(out, lens.height, lens.width, "out", target)
+        if tgt is None:
+            tgt = N.AtmoTarget(out.data_ptr(), N.TARGET_RGBA32F, 0)
+        flags = (SI.QUADS if quads else 0) | (SI.PREMULTIPLIED if premultiplied else 0) | (SI.COMPOSITE if composite else 0)
+        nl = lens.native()
+        N.check(self._ctx, fn(self._ctx, C.byref(nl), flags, C.c_void_p(rgba.data_ptr()), C.byref(tgt), C.c_void_p(_stream_handle(stream, rgba) or 0)))
+        return out
+
+    def sky_image_mips(self, levels, target=None, stream=None):
+        """Fills the mip chain of an image (atmo_sky_image_mips; sky_image.mip_chain is the same in numpy, bit for bit): `levels[0]` is read, `levels[1:]`
+        are written, each texel the average of the 2 x 2 stored texels above it.  `levels`: CUDA tensors (layers, h_l, w_l, 4) or (h_l, w_l, 4), float32,
+        float16 or uint8 (`target` names a 4-byte format other than RGBA8_UNORM), h_l = max(1, h >> l), w_l = max(1, w >> l); row and layer pitches are
+        taken from the strides.  All layers in one call, five levels a launch.  Returns `levels`."""
+        import torch
+
+        from . import sky_image as SI
+        from . import targets as T
+
+        fn = SI.bind(self._lib).atmo_sky_image_mips
+        levels = list(levels)
+        fmts = {torch.float32: T.RGBA32F, torch.float16: T.RGBA16F, torch.uint8: T.RGBA8}
+        first = levels[0] if levels else None
+        if not (isinstance(first, torch.Tensor) and first.is_cuda and first.dtype in fmts and first.dim() in (3, 4) and first.shape[-1] == 4):
+            raise ValueError("levels must be CUDA float32, float16 or uint8 tensors of shape (layers, h, w, 4) or (h, w, 4)")
+        fmt = fmts[first.dtype]
+        if target is not None:
+            fmt = T.format_id(target)
+            if np.dtype(T.DTYPES[fmt]).name != str(first.dtype).replace("torch.", ""):
+                raise ValueError(f"levels: target={target!r} is a {np.dtype(T.DTYPES[fmt]).name} format, the tensors are {first.dtype}")
+        layers = int(first.shape[0]) if first.dim() == 4 else 1
+        h, w = int(first.shape[-3]), int(first.shape[-2])
+        if not 1 <= len(levels) <= SI.level_count(w, h):
+            raise ValueError(f"a {w} x {h} image has 1 .. {SI.level_count(w, h)} levels")
+        arr = (SI.AtmoSkyLevel * len(levels))()
+        for l, t in enumerate(levels):
+            wl, hl = SI.level_size(w, h, l)
+            shape = (layers, hl, wl, 4) if first.dim() == 4 else (hl, wl, 4)
+            if not (isinstance(t, torch.Tensor) and t.device == first.device and t.dtype == first.dtype and tuple(t.shape) == shape):
+                raise ValueError(f"levels[{l}] must be a {first.dtype} tensor of shape {shape} on {first.device}")
+            row = t.stride(-3) if hl > 1 else 4 * wl
+            layer = t.stride(0) if (t.dim() == 4 and layers > 1) else 0
+            if not (t.stride(-1) == 1 and t.stride(-2) == 4 and row >= 4 * wl and (layer == 0 or layer >= hl * row)):
+                raise ValueError(f"levels[{l}]: the texels of a row must be contiguous, rows at least a row and layers at least a layer apart")
+            arr[l] = SI.AtmoSkyLevel(t.data_ptr(), row * t.element_size(), 0, layer * t.element_size())
+        N.check(self._ctx, fn(self._ctx, arr, len(levels), fmt, w, h, layers, C.c_void_p(_stream_handle(stream, first) or 0)))
+        return levels
+
+    def render_sky_image(self, lenses, target="rgba16f", *, mips: bool = True, premultiplied: bool = True, camera=None, time: float = 0.0, stream=None):
+        """The sky through one lens or several of equal size (a lens.Lens or a sequence: an octahedral map, a panorama, six cube faces = six layers) as an
+        image a renderer can bind: each lens is shaded as `render_lens` shades it -- in quad order under the declared sampler where this node has one,
+        else row-major through the tile index --, resolved into its layer by `resolve_lens` (`premultiplied`: rgb times alpha, what filtering wants) and
+        followed by ONE `sky_image_mips` call over all layers.  `target`: a format name of `render(..., target=)`.  Returns the list of level tensors,
+        (layers, h_l, w_l, 4) each -- one tensor without `mips`; nothing is read back and nothing waits on the host."""
+        import torch
+
+        from . import sky_image as SI
+        from .lens import Lens
+
+        lenses = [lenses] if isinstance(lenses, Lens) else list(lenses)
+        if not lenses or any((l.width, l.height) != (lenses[0].width, lenses[0].height) or l.rows != (0, l.height) for l in lenses):
+            raise ValueError("render_sky_image takes one lens or several of equal size, each with its whole image as the band")
+        w, h = lenses[0].width, lenses[0].height
+        device = torch.device("cuda", self._device)
+        quads = self._shades_ray_quads()
+        with _on_stream(stream, device)[1]:
+            n_levels = SI.level_count(w, h) if mips else 1
+            levels = [_new_target(len(lenses) * hl, wl, target, device, zero=False).view(len(lenses), hl, wl, 4)
+                      for wl, hl in (SI.level_size(w, h, l) for l in range(n_levels))]
+            for layer, lens in enumerate(lenses):
+                _, shaded = self._shade_lens(lens, camera, None, time, stream, quads)
+                self.resolve_lens(lens, shaded, levels[0][layer], target=target, quads=quads, premultiplied=premultiplied, stream=stream)
+            if n_levels > 1:
+                self.sky_image_mips(levels, target=target, stream=stream)
+            return levels
+
     def prepare_frame(self, camera, time: float = 0.0, rect=None) -> N.AtmoFrame:
         """The native per-frame argument block for `render_prepared` (build once per camera pose)."""
         return _to_native_frame(self.make_frame(camera, time, rect))

@@ -64,7 +64,7 @@
  * 37 running sums per lane in registers, 86 VGPRs, 37888 bytes of LDS (37 x 256 floats for the tree's two steps across waves), no private-memory
  * stack.  atmo_sky_sh9_total_kernel: one workgroup, 91 VGPRs, the same LDS, no stack.  profiles/sky_sh/README.md holds the timings.
  *
- * Not here: a resolve of ray results into packed image formats, mip chains, prefiltered radiance, bands above 2.
+ * Not here: prefiltered radiance, bands above 2.  (The resolve of ray results into packed image formats and the mip chain: atmo_sky_image.h.)
  */
 #ifndef ATMO_SKY_SH_H
 #define ATMO_SKY_SH_H
