@@ -7,6 +7,8 @@ Zylann/godot_atmosphere_shader, behind the reference's `PlanetAtmosphere` / `sha
   noise_cubemap.py      host-side mirror of addons/zylann.atmosphere/noise_cubemap.gd (generation on the GPU)
   lens.py               lens rays in numpy: panorama, fisheye, octahedral map, cube face (include/atmo_lens.h; `Lens` describes one for `render_lens`)
   reduced.py            reduced-resolution draws in numpy and the header's ctypes declarations (include/atmo_reduced.h; `PlanetAtmosphere.render_reduced`)
+  temporal.py           temporal draws in numpy -- phases, the phase frame, the history, the resolve -- and the header's ctypes declarations
+                        (include/atmo_temporal.h; `PlanetAtmosphere.render_temporal`, `TemporalHistory`)
   sky_sh.py             the sky as light in numpy -- lens-pixel solid angles, the SH9 projection in its fixed order of summation, irradiance -- and the
                         header's ctypes declarations (include/atmo_sky_sh.h; `PlanetAtmosphere.lens_solid_angles`, `project_sh9`, `ambient_sh9`)
   sky_image.py          sky images in numpy -- the resolve of a lens's shaded rays into a target format, the mip chain -- and the header's ctypes

@@ -24,7 +24,8 @@ HEADERS = ["atmo_device.h", "atmo_layout.h", "atmo_feedback_plan.h", "atmo_plane
            os.path.join("..", "..", "include", "atmo_ray_order.h"), os.path.join("..", "..", "include", "atmo_ray_list.h"),
            os.path.join("..", "..", "include", "atmo_ray_detail.h"), os.path.join("..", "..", "include", "atmo_detail_target.h"),
            os.path.join("..", "..", "include", "atmo_lens.h"), os.path.join("..", "..", "include", "atmo_reduced.h"),
-           os.path.join("..", "..", "include", "atmo_sky_sh.h"), os.path.join("..", "..", "include", "atmo_sky_image.h")]
+           os.path.join("..", "..", "include", "atmo_sky_sh.h"), os.path.join("..", "..", "include", "atmo_sky_image.h"),
+           os.path.join("..", "..", "include", "atmo_temporal.h")]
 
 # -ffp-contract=off: the kernels and the host-side per-frame constants must round exactly like a scalar
 # fp32 evaluation of the shader wherever control flow or the ill-conditioned cloud chain is involved;

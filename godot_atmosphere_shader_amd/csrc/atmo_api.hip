@@ -27,6 +27,7 @@
 #include "../../include/atmo_sky_sh.h"
 #include "../../include/atmo_sky_image.h"
 #include "../../include/atmo_reduced.h"
+#include "../../include/atmo_temporal.h"
 #include "atmo_device.h"
 #include "atmo_layout.h"
 #include "atmo_feedback_plan.h"
@@ -3333,19 +3334,24 @@ namespace {
 bool reduced_scale_ok(int scale) { return scale == 2 || scale == 4; }
 // The low frame (atmo_reduced.h, item 2): `frame` with the viewport (low_w, low_h), all of it as the rect, and inv_projection * A -- the product in double,
 // rounded once per element, and the caller's bits where the scale divides both sides.  reduced.py's low_frame is the same arithmetic.
-AtmoFrame reduced_low_frame(const AtmoFrame &frame, int scale, int low_w, int low_h) {
+// phase_x / phase_y >= 0 (atmo_temporal.h, item 2): the low pixels' centres on the centres of the full pixels i s + phase_x, j s + phase_y instead of on
+// their blocks' -- one more term in the translation, which is then never 0 (temporal.py's phase_frame).
+AtmoFrame reduced_low_frame(const AtmoFrame &frame, int scale, int low_w, int low_h, int phase_x = -1, int phase_y = -1) {
     AtmoFrame low = frame;
     low.viewport_w = low_w;
     low.viewport_h = low_h;
     low.x0 = 0; low.y0 = 0; low.x1 = low_w; low.y1 = low_h;
     const double kx = (double)(low_w * scale) / (double)frame.viewport_w, ky = (double)(low_h * scale) / (double)frame.viewport_h;
-    if (kx == 1.0 && ky == 1.0) return low;
+    const bool phased = phase_x >= 0;
+    if (!phased && kx == 1.0 && ky == 1.0) return low;
+    const double tx = phased ? (kx - 1.0) + (double)(2 * phase_x + 1 - scale) / (double)frame.viewport_w : kx - 1.0;
+    const double ty = phased ? (ky - 1.0) + (double)(2 * phase_y + 1 - scale) / (double)frame.viewport_h : ky - 1.0;
     const float *m = frame.inv_projection_matrix;
     for (int r = 0; r < 4; ++r) {
         const double m0 = m[r], m1 = m[4 + r], m3 = m[12 + r];
         low.inv_projection_matrix[r] = (float)(kx * m0);
         low.inv_projection_matrix[4 + r] = (float)(ky * m1);
-        low.inv_projection_matrix[12 + r] = (float)((m0 * (kx - 1.0) + m1 * (ky - 1.0)) + m3);
+        low.inv_projection_matrix[12 + r] = (float)((m0 * tx + m1 * ty) + m3);
     }
     return low;
 }
@@ -3461,6 +3467,161 @@ int atmo_render_reduced_target(AtmoContext *ctx, const AtmoFrame *frame, const A
     HIP_TRY(ctx, atmo::launch_reduced_pick(c, sf.dc, (hipStream_t)stream));
     ATMO_TRY(render_impl(ctx, &low, float_surfaces(low_depth, low_rgba, false), WHOLE_GRID, stream));   // atmo_render of the low frame
     HIP_TRY(ctx, atmo::launch_reduced_upsample(c, sf.dc, sf.tc, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+// ---- temporal draws (include/atmo_temporal.h): the phase's depth gather, atmo_render of the phase frame, the resolve against the previous history ----------
+namespace {
+const int TEMPORAL_ORDER_2[4] = {0, 3, 1, 2};
+const int TEMPORAL_ORDER_4[16] = {0, 10, 2, 8, 5, 15, 7, 13, 1, 11, 3, 9, 4, 14, 6, 12};
+size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
+// one history buffer: W H float4, W H floats, W H bytes, each part padded to 16 bytes
+size_t temporal_history_bytes(int w, int h) {
+    const size_t n = (size_t)w * (size_t)h;
+    return 16 * n + pad16(4 * n) + pad16(n);
+}
+int temporal_phase_ok(AtmoContext *ctx, const std::string &who, int scale, int phase) {
+    if (phase < 0 || phase >= scale * scale)
+        return fail(ctx, ATMO_E_ARG, who + ": phase must be 0 .. scale^2 - 1, not " + std::to_string(phase));
+    return ATMO_OK;
+}
+// The checks the resolve and the whole path share, in the header's order: atmo_reduced_upsample's (the target, the options of the spatial filter, the rect),
+// then the fields AtmoReduced does not have
+int temporal_target_check(AtmoContext *ctx, const char *who, const AtmoFrame *frame, const AtmoTemporal *opt, DrawSurfaces &sf) {
+    const AtmoReduced ro = {opt ? opt->scale : 0, opt ? opt->depth_tolerance : 0.0f};
+    ATMO_TRY(reduced_target_check(ctx, who, frame, opt ? &ro : nullptr, sf));
+    ATMO_TRY(temporal_phase_ok(ctx, who, opt->scale, opt->phase));
+    if (!(opt->history_tolerance >= 0.0f) || !std::isfinite(opt->history_tolerance))
+        return fail(ctx, ATMO_E_ARG, std::string(who) + ": history_tolerance must be finite and at least 0");
+    if (opt->max_age < 1 || opt->max_age > 255) return fail(ctx, ATMO_E_ARG, std::string(who) + ": max_age must be 1 .. 255, not " + std::to_string(opt->max_age));
+    return ATMO_OK;
+}
+int temporal_history_check(AtmoContext *ctx, const char *who, const AtmoFrame *frame, const AtmoTemporal *opt, const void *prev, const void *cur) {
+    if (!cur) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null history_cur_dev");
+    const uintptr_t a = reinterpret_cast<uintptr_t>(prev), b = reinterpret_cast<uintptr_t>(cur);
+    if ((a & 15u) != 0 || (b & 15u) != 0) return fail(ctx, ATMO_E_ARG, std::string(who) + ": history_prev_dev and history_cur_dev must be 16-byte aligned");
+    const size_t n = temporal_history_bytes(frame->viewport_w, frame->viewport_h);
+    if (prev && a < b + n && b < a + n) return fail(ctx, ATMO_E_ARG, std::string(who) + ": history_prev_dev and history_cur_dev overlap");
+    if (!prev && opt->reset == 0) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null history_prev_dev without reset");
+    return ATMO_OK;
+}
+// What the resolve reads beside ReducedConsts
+atmo::TemporalConsts temporal_consts(const AtmoFrame &frame, const AtmoTemporal &opt, const void *prev, void *cur) {
+    atmo::TemporalConsts t = {};
+    for (int k = 0; k < 16; ++k) {
+        t.m[k] = frame.inv_projection_matrix[k];
+        t.pc[k] = opt.prev_clip_from_view[k];
+    }
+    for (int k = 0; k < 4; ++k) { t.rz[k] = opt.prev_inv_projection[4 * k + 2]; t.rw[k] = opt.prev_inv_projection[4 * k + 3]; }
+    t.ox = opt.phase % opt.scale;
+    t.oy = opt.phase / opt.scale;
+    t.max_age = opt.max_age;
+    t.reset = opt.reset != 0;
+    t.htol = opt.history_tolerance;
+    const size_t n = (size_t)frame.viewport_w * (size_t)frame.viewport_h;
+    if (prev && !t.reset) {
+        const char *p = (const char *)prev;
+        t.prev_rgba = (const float4 *)p;
+        t.prev_q = (const float *)(p + 16 * n);
+        t.prev_age = (const uint8_t *)(p + 16 * n + pad16(4 * n));
+    }
+    char *q = (char *)cur;
+    t.cur_rgba = (float4 *)q;
+    t.cur_q = (float *)(q + 16 * n);
+    t.cur_age = (uint8_t *)(q + 16 * n + pad16(4 * n));
+    return t;
+}
+}  // namespace
+
+int atmo_temporal_size(int viewport_w, int viewport_h, int scale, int *low_w, int *low_h, size_t *scratch_bytes, size_t *history_bytes) {
+    ATMO_TRY(atmo_reduced_size(viewport_w, viewport_h, scale, low_w, low_h, scratch_bytes));
+    if (history_bytes) *history_bytes = temporal_history_bytes(viewport_w, viewport_h);
+    return ATMO_OK;
+}
+
+int atmo_temporal_phase(int scale, int frame_index) {
+    if (!reduced_scale_ok(scale)) return -1;
+    const int n = scale * scale, k = ((frame_index % n) + n) % n;
+    return scale == 2 ? TEMPORAL_ORDER_2[k] : TEMPORAL_ORDER_4[k];
+}
+
+int atmo_temporal_depth(AtmoContext *ctx, const AtmoFrame *frame, const AtmoDepth *depth, int scale, int phase, float *low_depth_dev, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const std::string who = "atmo_temporal_depth";
+    bool empty = false;
+    ATMO_TRY(check_frame(ctx, who, frame, &empty));
+    if (!reduced_scale_ok(scale)) return fail(ctx, ATMO_E_ARG, who + ": scale must be 2 or 4, not " + std::to_string(scale));
+    ATMO_TRY(temporal_phase_ok(ctx, who, scale, phase));
+    ATMO_TRY(reduced_whole_viewport(ctx, who, frame));
+    if (!low_depth_dev) return fail(ctx, ATMO_E_ARG, who + ": null low_depth_dev");
+    if ((reinterpret_cast<uintptr_t>(low_depth_dev) & 3u) != 0) return fail(ctx, ATMO_E_ARG, who + ": low_depth_dev must be 4-byte aligned");
+    atmo::DepthConsts dc = {nullptr, 0, 0};
+    ATMO_TRY(depth_check(ctx, who, depth, frame->viewport_w, frame->viewport_h, &dc));
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, who + ": a host-only context has no device to run on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    atmo::ReducedConsts c = reduced_consts(*frame, scale);
+    c.low_depth = low_depth_dev;
+    atmo::TemporalConsts t = {};
+    t.ox = phase % scale;
+    t.oy = phase / scale;
+    HIP_TRY(ctx, atmo::launch_temporal_depth(c, t, dc, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+int atmo_temporal_resolve(AtmoContext *ctx, const AtmoFrame *frame, const AtmoDepth *depth, const AtmoTemporal *opt, const float *low_depth_dev,
+                          const float *low_rgba_dev, const void *history_prev_dev, void *history_cur_dev, const AtmoTarget *target, int composite,
+                          void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_temporal_resolve";
+    DrawSurfaces sf = depth_target_surfaces(depth, target, true);
+    ATMO_TRY(temporal_target_check(ctx, who, frame, opt, sf));
+    if (!low_depth_dev || !low_rgba_dev) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null low_depth_dev or low_rgba_dev");
+    if ((reinterpret_cast<uintptr_t>(low_depth_dev) & 3u) != 0 || (reinterpret_cast<uintptr_t>(low_rgba_dev) & 15u) != 0)
+        return fail(ctx, ATMO_E_ARG, std::string(who) + ": low_depth_dev must be 4-byte aligned and low_rgba_dev 16-byte aligned");
+    ATMO_TRY(temporal_history_check(ctx, who, frame, opt, history_prev_dev, history_cur_dev));
+    ATMO_TRY(check_surfaces(ctx, who, frame, sf));
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, std::string(who) + ": a host-only context has no device to run on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    atmo::ReducedConsts c = reduced_consts(*frame, opt->scale);
+    c.tol = opt->depth_tolerance;
+    c.composite = composite != 0;
+    c.low_depth = const_cast<float *>(low_depth_dev);   // (read only by this pass)
+    c.low_rgba = (const float4 *)low_rgba_dev;
+    HIP_TRY(ctx, atmo::launch_temporal_resolve(c, temporal_consts(*frame, *opt, history_prev_dev, history_cur_dev), sf.dc, sf.tc, (hipStream_t)stream));
+    return ATMO_OK;
+}
+
+int atmo_render_temporal_target(AtmoContext *ctx, const AtmoFrame *frame, const AtmoDepth *depth, const AtmoTemporal *opt, void *scratch_dev,
+                                const void *history_prev_dev, void *history_cur_dev, const AtmoTarget *target, int composite, void *stream) {
+    if (!ctx) return ATMO_E_ARG;
+    const char *who = "atmo_render_temporal_target";
+    DrawSurfaces sf = depth_target_surfaces(depth, target, true);
+    ATMO_TRY(temporal_target_check(ctx, who, frame, opt, sf));
+    if (!scratch_dev) return fail(ctx, ATMO_E_ARG, std::string(who) + ": null scratch_dev");
+    if ((reinterpret_cast<uintptr_t>(scratch_dev) & 15u) != 0) return fail(ctx, ATMO_E_ARG, std::string(who) + ": scratch_dev must be 16-byte aligned");
+    ATMO_TRY(temporal_history_check(ctx, who, frame, opt, history_prev_dev, history_cur_dev));
+    ATMO_TRY(check_surfaces(ctx, who, frame, sf));
+    // what atmo_render would refuse the phase frame for, in front of the first kernel: nothing is enqueued by a refused call
+    atmo::ReducedConsts c = reduced_consts(*frame, opt->scale);
+    const atmo::TemporalConsts t = temporal_consts(*frame, *opt, history_prev_dev, history_cur_dev);
+    const AtmoFrame low = reduced_low_frame(*frame, opt->scale, c.low_w, c.low_h, t.ox, t.oy);
+    if (cloud_detail_on(ctx)) ATMO_TRY(cloud_detail_family(ctx, who, &low));
+    {
+        int flags = 0, split = 1;
+        bool lod = false;
+        ATMO_TRY(draw_family(ctx, &low, &flags, &split, &lod));
+    }
+    ATMO_TRY(check_draw_textures(ctx, who));
+    if (ctx->device < 0) return fail(ctx, ATMO_E_NO_DEVICE, std::string(who) + ": a host-only context has no device to draw on");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    float *low_depth = (float *)scratch_dev, *low_rgba = low_depth + reduced_depth_floats(c.low_w, c.low_h);
+    c.tol = opt->depth_tolerance;
+    c.composite = composite != 0;
+    c.low_depth = low_depth;
+    c.low_rgba = (const float4 *)low_rgba;
+    HIP_TRY(ctx, atmo::launch_temporal_depth(c, t, sf.dc, (hipStream_t)stream));
+    ATMO_TRY(render_impl(ctx, &low, float_surfaces(low_depth, low_rgba, false), WHOLE_GRID, stream));   // atmo_render of the phase frame
+    HIP_TRY(ctx, atmo::launch_temporal_resolve(c, t, sf.dc, sf.tc, (hipStream_t)stream));
     return ATMO_OK;
 }
 

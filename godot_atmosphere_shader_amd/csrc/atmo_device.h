@@ -478,5 +478,25 @@ struct SkyMipConsts {
     int32_t layers;
 };
 hipError_t launch_sky_image_mips(int format, const SkyMipConsts &c, hipStream_t stream);
+// Temporal draws (include/atmo_temporal.h states the arithmetic; temporal.py restates it in numpy): what the two passes read beside ReducedConsts (the
+// sizes, rows 2 and 3 of the current inv_projection, depth_tolerance, composite, the low buffers).  By value in the kernel arguments.
+struct TemporalConsts {
+    float m[16];               // the frame's inv_projection_matrix, column-major (the resolve forms all four rows)
+    float pc[16];              // AtmoTemporal::prev_clip_from_view
+    float rz[4], rw[4];        // rows 2 and 3 of AtmoTemporal::prev_inv_projection
+    int32_t ox, oy;            // the phase's texel of every block
+    int32_t max_age, reset;
+    float htol;                // AtmoTemporal::history_tolerance
+    const float4 *prev_rgba;   // the previous history's three parts (all null under reset: never read)
+    const float *prev_q;
+    const uint8_t *prev_age;
+    float4 *cur_rgba;          // the current history's
+    float *cur_q;
+    uint8_t *cur_age;
+};
+// atmo_temporal_depth_kernel: one lane per low texel, a plain gather (reads c's sizes and low_depth, t's ox and oy)
+hipError_t launch_temporal_depth(const ReducedConsts &c, const TemporalConsts &t, const DepthConsts &depth, hipStream_t stream);
+// atmo_temporal_resolve_kernel: one lane per pixel of the viewport in the upsample kernel's lane map; every target format
+hipError_t launch_temporal_resolve(const ReducedConsts &c, const TemporalConsts &t, const DepthConsts &depth, const TargetConsts &tc, hipStream_t stream);
 
 }  // namespace atmo

@@ -5118,4 +5118,180 @@ hipError_t launch_sky_image_mips(int format, const SkyMipConsts &c, hipStream_t 
     }
 }
 
+// ---- temporal draws (include/atmo_temporal.h states the arithmetic item by item; temporal.py restates it in numpy) ------------------------------------------
+// The two passes around the low draw of one phase: the gather of the depth under this frame's texel of every block, and the resolve of every pixel of the
+// viewport from the low frame, the reprojected previous history or the spatial filter.  Both are held to the numpy statement bit for bit: nothing is
+// contracted and every quotient is IEEE.  Kernels of their own names (no older kernel's name is a substring of theirs, nor the reverse), defined behind
+// everything else, so that every older kernel keeps its code and its place in the code object (tools/isa_diff.py).  The lane map is the upsample kernel's:
+// a workgroup is 64 x 4 texels of the image it writes, a wave 64 consecutive texels of a row.  No LDS, no stack, no atomics.
+__global__ __launch_bounds__(REDUCED_BLOCK_W *REDUCED_BLOCK_H) void atmo_temporal_depth_kernel(const ReducedConsts c, const int ox, const int oy,
+                                                                                                const DepthConsts dc) {
+    const int i = (int)blockIdx.x * REDUCED_BLOCK_W + (int)threadIdx.x, j = (int)blockIdx.y * REDUCED_BLOCK_H + (int)threadIdx.y;
+    if (i >= c.low_w || j >= c.low_h) return;
+    const int x = min((i << c.log2s) + ox, c.w - 1), y = min((j << c.log2s) + oy, c.h - 1);
+    c.low_depth[(size_t)j * (size_t)c.low_w + (size_t)i] = load_depth(dc, x, y);
+}
+static bool temporal_sizes_ok(const ReducedConsts &c, const TemporalConsts &t) {
+    const int s = 1 << c.log2s;
+    return (c.log2s == 1 || c.log2s == 2) && c.w >= 1 && c.h >= 1 && c.w <= 65536 && c.h <= 65536 && c.low_w == ((c.w - 1) >> c.log2s) + 1 &&
+           c.low_h == ((c.h - 1) >> c.log2s) + 1 && t.ox >= 0 && t.ox < s && t.oy >= 0 && t.oy < s;
+}
+hipError_t launch_temporal_depth(const ReducedConsts &c, const TemporalConsts &t, const DepthConsts &depth, hipStream_t stream) {
+    if (c.low_depth == nullptr || depth.texels == nullptr || depth_texel_bytes(depth.format) == 0 || !temporal_sizes_ok(c, t)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((c.low_w + REDUCED_BLOCK_W - 1) / REDUCED_BLOCK_W), (unsigned)((c.low_h + REDUCED_BLOCK_H - 1) / REDUCED_BLOCK_H));
+    hipLaunchKernelGGL(atmo_temporal_depth_kernel, grid, dim3(REDUCED_BLOCK_W, REDUCED_BLOCK_H), 0, stream, c, t.ox, t.oy, depth);
+    return hipGetLastError();
+}
+// 5c: history texel (fi, fj) -- floats that hold integers, or anything else, which is outside -- is valid; its index and age where it is.  Nothing is read
+// of a texel outside the image
+__device__ __forceinline__ bool temporal_texel_valid(const ReducedConsts &c, const TemporalConsts &t, const bool front, const float qe, const float fi,
+                                                     const float fj, size_t &at, int &age) {
+#pragma clang fp contract(off)
+    at = 0;
+    age = 255;
+    if (!(front && fi >= 0.0f && fi < (float)c.w && fj >= 0.0f && fj < (float)c.h)) return false;
+    at = (size_t)(int)fj * (size_t)c.w + (size_t)(int)fi;
+    age = (int)t.prev_age[at];
+    if (age >= t.max_age) return false;
+    const float qk = t.prev_q[at];
+    return fabsf(qe - qk) <= t.htol * fmaxf(fabsf(qe), fabsf(qk));
+}
+// items 5e / 5f: the premultiplied sums over the taps that count, the division, the pixel
+__device__ __forceinline__ float4 temporal_blend(const float4 (&tap)[4], const float (&w4)[4], const bool (&counts)[4]) {
+#pragma clang fp contract(off)
+    float wsum = 0.0f, a = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float wk = w4[k], ak = tap[k].w;
+        wsum = counts[k] ? wsum + wk : wsum;
+        a = counts[k] ? a + wk * ak : a;
+        cr = counts[k] ? cr + wk * (ak * tap[k].x) : cr;
+        cg = counts[k] ? cg + wk * (ak * tap[k].y) : cg;
+        cb = counts[k] ? cb + wk * (ak * tap[k].z) : cb;
+    }
+    if (wsum != 1.0f) {
+        a = ieee_div(a, wsum);
+        cr = ieee_div(cr, wsum);
+        cg = ieee_div(cg, wsum);
+        cb = ieee_div(cb, wsum);
+    }
+    const bool has = a > 0.0f;
+    return make_float4(has ? ieee_div(cr, a) : 0.0f, has ? ieee_div(cg, a) : 0.0f, has ? ieee_div(cb, a) : 0.0f, a);
+}
+__global__ __launch_bounds__(REDUCED_BLOCK_W *REDUCED_BLOCK_H) void atmo_temporal_resolve_kernel(const ReducedConsts c, const TemporalConsts t,
+                                                                                                  const DepthConsts dc, const TargetConsts tc) {
+#pragma clang fp contract(off)
+    const int x = (int)blockIdx.x * REDUCED_BLOCK_W + (int)threadIdx.x, y = (int)blockIdx.y * REDUCED_BLOCK_H + (int)threadIdx.y;
+    if (x >= c.w || y >= c.h) return;
+    const int s = 1 << c.log2s;
+    const float nx = reduced_ndc(x, c.w), ny = reduced_ndc(y, c.h);
+    const float d0 = load_depth(dc, x, y);
+    float V[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) V[r] = ((t.m[r] * nx + t.m[4 + r] * ny) + t.m[8 + r] * d0) + t.m[12 + r];
+    const float q0 = ieee_div(V[3], V[2]);
+    float4 px = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int age = 255;
+    bool done = false;
+    if ((x & (s - 1)) == t.ox && (y & (s - 1)) == t.oy) {   // 5a
+        px = c.low_rgba[(size_t)(y >> c.log2s) * (size_t)c.low_w + (size_t)(x >> c.log2s)];
+        age = 0;
+        done = true;
+    } else if (t.reset == 0) {   // 5b
+        float C[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) C[r] = ((t.pc[r] * V[0] + t.pc[4 + r] * V[1]) + t.pc[8 + r] * V[2]) + t.pc[12 + r] * V[3];
+        const bool front = C[3] > 0.0f;
+        const float u = ieee_div(C[0], C[3]), v = ieee_div(C[1], C[3]), dp = ieee_div(C[2], C[3]);
+        const float fpx = ((u + 1.0f) * 0.5f) * (float)c.w - 0.5f, fpy = ((v + 1.0f) * 0.5f) * (float)c.h - 0.5f;
+        const float qe = ieee_div(((t.rw[0] * u + t.rw[1] * v) + t.rw[2] * dp) + t.rw[3], ((t.rz[0] * u + t.rz[1] * v) + t.rz[2] * dp) + t.rz[3]);
+        const float jx = floorf(fpx + 0.5f), jy = floorf(fpy + 0.5f);
+        if (fabsf(fpx - jx) <= 0.015625f && fabsf(fpy - jy) <= 0.015625f) {   // 5d
+            size_t at;
+            int a;
+            if (temporal_texel_valid(c, t, front, qe, jx, jy, at, a)) {
+                px = t.prev_rgba[at];
+                age = min(a + 1, 254);
+                done = true;
+            }
+        } else {   // 5e
+            const float i0 = floorf(fpx), j0 = floorf(fpy);
+            const float fx = fpx - i0, fy = fpy - j0, gx = 1.0f - fx, gy = 1.0f - fy;
+            const float w4[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
+            float4 tap[4];
+            bool counts[4];
+            int oldest = -1;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                size_t at;
+                int a;
+                counts[k] = temporal_texel_valid(c, t, front, qe, i0 + (float)(k & 1), j0 + (float)(k >> 1), at, a) && w4[k] > 0.0f;
+                tap[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (counts[k]) {
+                    tap[k] = t.prev_rgba[at];
+                    oldest = max(oldest, a);
+                }
+            }
+            if (oldest >= 0) {
+                px = temporal_blend(tap, w4, counts);
+                age = min(oldest + 1, 254);
+                done = true;
+            }
+        }
+    }
+    if (!done) {   // 5f
+        const float invs = c.log2s == 1 ? 0.5f : 0.25f;
+        const int ex = max((c.w - t.ox + s - 1) >> c.log2s, 1) - 1, ey = max((c.h - t.oy + s - 1) >> c.log2s, 1) - 1;
+        const int tx = x - t.ox, ty = y - t.oy;
+        const int i0 = tx >> c.log2s, j0 = ty >> c.log2s;   // floor: -1 in front of the first sample
+        const float fx = (float)(tx - (i0 << c.log2s)) * invs, fy = (float)(ty - (j0 << c.log2s)) * invs;
+        const float gx = 1.0f - fx, gy = 1.0f - fy;
+        const float wgt[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
+        const int ia = min(max(i0, 0), ex), ib = min(max(i0 + 1, 0), ex), ja = min(max(j0, 0), ey), jb = min(max(j0 + 1, 0), ey);
+        const size_t at[4] = {(size_t)ja * (size_t)c.low_w + (size_t)ia, (size_t)ja * (size_t)c.low_w + (size_t)ib,
+                              (size_t)jb * (size_t)c.low_w + (size_t)ia, (size_t)jb * (size_t)c.low_w + (size_t)ib};
+        const float zb = c.pz[0] * nx + c.pz[1] * ny, wb = c.pw[0] * nx + c.pw[1] * ny;
+        float diff[4], w4[4];
+        bool counts[4];
+        float4 tap[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            tap[k] = c.low_rgba[at[k]];
+            const float qk = reduced_eye_q(c, zb, wb, c.low_depth[at[k]]);
+            diff[k] = fabsf(q0 - qk);
+            counts[k] = diff[k] <= c.tol * fmaxf(fabsf(q0), fabsf(qk)) && wgt[k] > 0.0f;
+            w4[k] = wgt[k];
+        }
+        if (!(counts[0] || counts[1] || counts[2] || counts[3])) {   // the closest in depth alone, with weight 1
+            int best = 0;
+#pragma unroll
+            for (int k = 1; k < 4; ++k) best = diff[k] < diff[best] ? k : best;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                counts[k] = k == best;
+                w4[k] = 1.0f;
+            }
+        }
+        px = temporal_blend(tap, w4, counts);
+        age = 255;
+    }
+    const size_t idx = (size_t)y * (size_t)c.w + (size_t)x;   // 5h
+    t.cur_rgba[idx] = px;
+    t.cur_q[idx] = q0;
+    t.cur_age[idx] = (uint8_t)age;
+    if (c.composite != 0 && !(px.w > 0.0f)) return;   // a composite leaves the pixel's bytes alone
+    void *p = (char *)tc.pixels + (size_t)y * (size_t)tc.pitch_bytes + ((size_t)x << target_pixel_shift_all(tc.format));
+    store_target_all_rt(tc.format, p, px, c.composite != 0);
+}
+hipError_t launch_temporal_resolve(const ReducedConsts &c, const TemporalConsts &t, const DepthConsts &depth, const TargetConsts &tc, hipStream_t stream) {
+    if (c.low_depth == nullptr || c.low_rgba == nullptr || depth.texels == nullptr || depth_texel_bytes(depth.format) == 0 || tc.pixels == nullptr ||
+        !temporal_sizes_ok(c, t) || t.cur_rgba == nullptr || t.cur_q == nullptr || t.cur_age == nullptr || t.max_age < 1 || t.max_age > 255 ||
+        (t.reset == 0 && (t.prev_rgba == nullptr || t.prev_q == nullptr || t.prev_age == nullptr)) ||
+        (long long)tc.pitch_bytes < ((long long)c.w << (tc.format == TF_RGBA32F ? 4 : tc.format == TF_RGBA16F ? 3 : 2)))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((c.w + REDUCED_BLOCK_W - 1) / REDUCED_BLOCK_W), (unsigned)((c.h + REDUCED_BLOCK_H - 1) / REDUCED_BLOCK_H));
+    hipLaunchKernelGGL(atmo_temporal_resolve_kernel, grid, dim3(REDUCED_BLOCK_W, REDUCED_BLOCK_H), 0, stream, c, t, depth, tc);
+    return hipGetLastError();
+}
+
 }  // namespace atmo

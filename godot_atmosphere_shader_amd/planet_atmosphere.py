@@ -749,6 +749,46 @@ class PlanetAtmosphere:
             own = self._reduced_scratch_tensor = torch.empty(need, dtype=torch.uint8, device=device)
         return own
 
+    # ---- temporal draws (include/atmo_temporal.h) -------------------------------------------------------------------------------------
+    def render_temporal(self, camera, depth, target="rgba16f", out=None, *, scale: int = 2, history=None, depth_tolerance: float = 0.1,
+                        history_tolerance: float = 0.1, max_age=None, phase=None, reset: bool = False, composite: bool = False, scratch=None,
+                        stream=None, time: float = 0.0):
+        """One draw of the whole viewport that marches one pixel of every `scale` x `scale` block and takes the others from the last call's result,
+        reprojected, or from `render_reduced`'s spatial filter where that history is gone (atmo_render_temporal_target; include/atmo_temporal.h states
+        every step, godot_atmosphere_shader_amd.temporal restates it in numpy).  `depth`, `target`, `out`, `composite`, `depth_tolerance`, `scratch`,
+        `stream` and `time` are `render_reduced`'s.
+        `history`: the `temporal.TemporalHistory` an earlier call returned, or None for a new one.  It owns the two history buffers, the previous camera's
+        matrices and the frame index; the call swaps the buffers, and starts over (as with reset=True) when the history is new or was made for another
+        viewport, scale or device.  Calls that share a history must be ordered on one stream.
+        `history_tolerance`: the relative difference of reciprocal eye depth up to which a reprojected pixel is the same surface.  `max_age`: a history
+        pixel is reused while it is younger than this many frames (None: 2 scale^2).  `phase`: None for the Bayer sequence at the history's frame index.
+        Returns (`out`, history)."""
+        from . import temporal as TP
+
+        if scale not in TP.SCALES:
+            raise ValueError(f"scale must be 2 or 4, not {scale!r}")
+        if composite and out is None:
+            raise ValueError("composite=True blends into `out`, the scene colour buffer: it must be given")
+        fn = TP.bind(self._lib).atmo_render_temporal_target
+        state = {}
+
+        def extra(cam, device):
+            hist = history
+            if hist is None or not hist.matches(cam, scale, device):
+                hist = TP.TemporalHistory(cam.width, cam.height, scale, device)
+            restart = bool(reset) or hist.fresh
+            frame = self.make_frame(cam, time)
+            opt = TP.options(scale, TP.phase_of_frame(scale, hist.frame_index) if phase is None else phase, depth_tolerance, history_tolerance, max_age,
+                             restart, None if restart else TP.prev_clip_from_view(frame, hist.prev_camera),
+                             None if restart else hist.prev_camera.inv_projection_cm)
+            state["opt"], state["history"] = opt, hist      # (the structure outlives the call)
+            return (C.byref(opt), C.c_void_p(self._reduced_scratch(cam, scale, scratch, device).data_ptr()),
+                    C.c_void_p(None if restart else hist.previous.data_ptr()), C.c_void_p(hist.current.data_ptr()))
+
+        out = self._render_one(camera, depth, out, None, stream, time, target, composite, None, split_depth_errors=True, reduced=(fn, extra))
+        state["history"].advance(camera)
+        return out, state["history"]
+
     # ---- caller-supplied rays (include/atmo_rays.h) --------------------------------------------------------------------------------
     def _entry(self, name: str):
         """An entry point of one of the optional headers (N.optional_headers); RuntimeError naming the header where the library lacks it."""
